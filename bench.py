@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X-native hot paths.
 
-Metric (BASELINE.json): Mrays/s on the Cornell box, 1024x1024, 2048 spp, image-tiled over N GPUs;
-plus Mfrags/s of the DrawSVG triangle fill (single GPU) as a second object on the same JSON line.
+Metric (BASELINE.json): Mrays/s on the Cornell box, 1024x1024, 2048 spp, image-tiled over N GPUs.  With --full the same
+JSON line also carries the golden check, kernel timings, roofline, dead-ray elision, CPU baseline, cfg5, the drop-in class
+and Mfrags/s of the DrawSVG triangle fill (single GPU); a plain run sets up, warms up, times the K steps and prints the line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes what the timed path computed in its last step (rank 0): DIR/image.npy, the running mean the K
+epochs folded into, DIR/epoch.npy, the last epoch's image (both float32, H x W x 3), and DIR/ray_count.npy (rays, camera
+samples; float64).  Images above 20 MiB are stored as the same seeded sample of pixels, listed in DIR/pixel_index.npy.
 
 One STEP = one epoch (Pathtracer::do_trace) of --spp-per-step (default 64) samples per pixel over the whole
 1024x1024 image: 67.1 M camera samples, ~0.5 G rays.  32 steps are the full 2048-spp render of
@@ -35,6 +40,7 @@ L2_PEAK_GBS = 34500.0  # aggregate L2 bandwidth (8 XCDs x 4 MiB), same guide: wh
 SIMDS = 256 * 4
 VALU_PEAK_GUIDE = SIMDS * 2.4e9 / 2.0     # wave-instructions / s: one wave64 VALU op per 2 cycles per SIMD at 2.4 GHz (the guide)
 VALU_NS_UBENCH = 1.09                     # measured issue interval of a SIMD with >= 2 waves (tools/ubench/pk_rate.hip)
+DUMP_BYTES_PER_IMAGE = 20 << 20           # --dump-outputs: two images + a pixel index stay under 64 MB
 
 
 def kernel_source_sha():
@@ -714,6 +720,12 @@ def main():
     ap.add_argument("--group", default=None, metavar="N[,M..]",
                     help="time the in-process multi-GPU path (srt_pt_create_multi: what the C++ drop-in uses) for these rank counts and print "
                          "one JSON line {\"group\": [...]}; ranks share device 0 where the box has fewer GPUs (a rehearsal, labelled)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: golden check, one-stream and kernel timings, roofline, "
+                         "dead-ray elision, CPU baseline, cfg5, drop-in and rasterizer objects (the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy: image (the running mean), "
+                         "epoch (that step's epoch image), ray_count (rays, camera samples)")
     args = ap.parse_args()
     if args.group:
         print(json.dumps({"metric": "Mrays/s", "mode": "in-process group (srt_pt_group_render_epoch_device)", "scene": args.scene,
@@ -832,12 +844,18 @@ def main():
     elapsed = time.perf_counter() - t0
 
     rays, cams = pt.ray_count()
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step, copied before anything below reuses the buffers
+        outputs = {"image": acc.cpu().numpy().reshape(H, W, 3),
+                   "epoch": image[(args.steps - 1) % nstreams].cpu().numpy().reshape(H, W, 3)}
+    # Everything below that only --full asks for runs after the clock, on the same context and buffers.
     # One more step THROUGH THE SAME PATH (tiles, gather, un-tiling), outside the clock: seed 0, samples 0 .. 63 - the epoch whose
     # image the reference build rendered for tests/golden/pt_fullsize.json (cfg4_cbox_1024_64spp).  Every `--gpus N` run says
     # whether its N ranks and its collective reproduce that image bit for bit.
     golden = None
     gkey = "cfg4_cbox_1024_64spp"
-    if args.scene == "cbox" and (W, args.depth) == (1024, 8) and not args.no_golden_check:
+    if args.full and args.scene == "cbox" and (W, args.depth) == (1024, 8) and not args.no_golden_check:
         import hashlib
 
         import _harness as harness                     # (H is the image height here)
@@ -864,7 +882,7 @@ def main():
         pt.ray_count(reset=True)
     # the same steps on ONE stream: a step on its own, wall clock (the timed region above overlaps consecutive launches on two streams)
     no_overlap_ms = None
-    if nstreams > 1 and world == 1:
+    if args.full and nstreams > 1 and world == 1:
         pt.ray_count(reset=True)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -872,37 +890,37 @@ def main():
             pt.render_epoch_device(streams[0].cuda_stream, args.seed, i * spp, spp, tiles[0].data_ptr())
         torch.cuda.synchronize()
         no_overlap_ms = (time.perf_counter() - t1) * 1e3 / args.steps
-    pt.kernel_time(enable=True)
-    sc = None
-    if form >= 3:
-        pt.stream_times(enable=True)
-        pt.stream_counters(reset=True)
-    # the dominant kernel on its own (HIP events inside the library, on the launch stream): two launches after the
-    # timed region, nothing else in flight - inside the timed region consecutive launches overlap by design
-    for j in range(2):
-        pt.render_epoch_device(streams[0].cuda_stream, args.seed, j * spp, spp, tiles[0].data_ptr())
-    torch.cuda.synchronize()
-    wave_ms_total, wave_launches = pt.kernel_time(enable=False)
-    kernel_ms = wave_ms_total / max(1, wave_launches)          # agrees with rocprofv3 AverageNs of a non-overlapped run
-    stream_split = None
-    if form >= 3:                                              # the streamed forms: the epoch's kernels one by one
-        ms3, gens = pt.stream_times(enable=False)
-        stream_split = {k: v / 2 for k, v in ms3.items()}
-        stream_split["generations_enqueued_per_step"] = gens // 2
-        sc = pt.stream_counters(reset=True)
-        sc["entries_queued"] //= 2; sc["alive_slot_generations"] //= 2        # (two launches were counted)
-    pt.ray_count(reset=True)
+    kernel_ms = wave_launches = stream_split = sc = None
+    if args.full:
+        pt.kernel_time(enable=True)
+        if form >= 3:
+            pt.stream_times(enable=True)
+            pt.stream_counters(reset=True)
+        # the dominant kernel on its own (HIP events inside the library, on the launch stream): two launches after the
+        # timed region, nothing else in flight - inside the timed region consecutive launches overlap by design
+        for j in range(2):
+            pt.render_epoch_device(streams[0].cuda_stream, args.seed, j * spp, spp, tiles[0].data_ptr())
+        torch.cuda.synchronize()
+        wave_ms_total, wave_launches = pt.kernel_time(enable=False)
+        kernel_ms = wave_ms_total / max(1, wave_launches)          # agrees with rocprofv3 AverageNs of a non-overlapped run
+        if form >= 3:                                              # the streamed forms: the epoch's kernels one by one
+            ms3, gens = pt.stream_times(enable=False)
+            stream_split = {k: v / 2 for k, v in ms3.items()}
+            stream_split["generations_enqueued_per_step"] = gens // 2
+            sc = pt.stream_counters(reset=True)
+            sc["entries_queued"] //= 2; sc["alive_slot_generations"] //= 2        # (two launches were counted)
+        pt.ray_count(reset=True)
     epoch_ms = sum(a.elapsed_time(b) for a, b in kernel_events) / max(1, len(kernel_events))  # per step, overlapped
     if world > 1:
         cdev = torch.device("cpu") if rehearse else dev
-        t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device=cdev)
+        t = torch.tensor([elapsed, kernel_ms or 0.0], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms_max = float(t[0]), float(t[1])
         c = torch.tensor([rays, cams], dtype=torch.int64, device=cdev)
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
         total_rays, total_cams = int(c[0]), int(c[1])
         rank_stats = [torch.zeros(3, dtype=torch.float64, device=cdev) for _ in range(world)]
-        dist.all_gather(rank_stats, torch.tensor([kernel_ms, epoch_ms, float(rays)], dtype=torch.float64, device=cdev))
+        dist.all_gather(rank_stats, torch.tensor([kernel_ms or 0.0, epoch_ms, float(rays)], dtype=torch.float64, device=cdev))
         rank_kernel_ms = [float(t[0]) for t in rank_stats]
         rank_step_span_ms = [float(t[1]) for t in rank_stats]
         rank_rays = [int(t[2]) for t in rank_stats]
@@ -912,12 +930,12 @@ def main():
     gather_ms = (sum(a.elapsed_time(b) for a, b in gather_events) / len(gather_events)) if gather_events else None
 
     main_sha = main_mean = None
-    if rank == 0:
+    if args.full and rank == 0:
         import hashlib
         main_sha = hashlib.sha256(acc.cpu().numpy().tobytes()).hexdigest()
         main_mean = float(acc.mean().item())
     elision = None
-    if world == 1 and not args.no_elision:
+    if args.full and world == 1 and not args.no_elision:
         # Second pass with dead-ray elision (include/srt_pt.h: srt_pt_set_elision): the headline above traces EVERY ray the
         # reference issues; here the wave kernel skips the BSDF-sampled direct ray whose term the reference adds and subtracts
         # again (legal, both ray counts reported).  Same steps, fresh accumulator, image compared.
@@ -948,26 +966,10 @@ def main():
         pt.set_elision(False)
 
     if rank == 0:
-        # traversal averages of this workload from an instrumented launch (outside the timed region)
-        rng = np.random.default_rng(1)
-        n = 1 << 16
-        xs, ys = rng.integers(0, W, n).astype(np.uint32), rng.integers(0, H, n).astype(np.uint32)
-        ss = rng.integers(0, spp * args.steps, n).astype(np.uint32)
-        pt.trace_samples(args.seed, xs, ys, ss)
-        cnt = pt.counters()
-        rays_per_launch_rank0 = rays / args.steps
-        cams_per_launch_rank0 = cams / args.steps
-        mean_radiance = main_mean
-        image_sha = main_sha[:16]
-        prof_doc, why_not = profile_doc(args.scene, W, spp, world)
-        # ray state that goes through memory per launch (SURVEY.md 8(d)'s last term): a 32-byte record per shaded bounce,
-        # written once and read once, and one 16-byte store per sample (read again by the ordered reduction)
-        scratch, scratch_terms = ray_state_bytes(rays_per_launch_rank0, cams_per_launch_rank0, sc)
         out = {
             "metric": "Mrays/s", "value": total_rays / elapsed / 1e6, "unit": "Mrays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
-            "ms_per_step_no_overlap": no_overlap_ms,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {
                 "workload": (f"Scotty3D Pathtracer: Cornell box + 131 072-triangle glass mesh + mirror sphere (BASELINE configs[4]; seeded procedural "
                              f"stand-in for the Stanford dragon, a missing blob of the reference checkout), {W}x{H}, {spp} spp per step "
@@ -979,40 +981,67 @@ def main():
                                "one RCCL gather of tile radiance per step") if world > 1 else "none (1 GPU)",
                 "seed": args.seed,
             },
-            # what a multi-GPU record needs to verify and decompose itself: the epoch image against the reference-built golden, every
-            # rank's own kernel time (one launch alone, after the timed region) and step span, the exchange step on rank 0
-            "image_equals_golden": golden["image_equals_golden"] if golden else None, "golden_check": golden,
-            "rank_kernel_ms": rank_kernel_ms, "rank_step_span_ms": rank_step_span_ms, "rank_rays": rank_rays,
             "gather_ms": gather_ms,
             "collective": {"backend": (dist.get_backend() if world > 1 else None), "ranks": (dist.get_world_size() if world > 1 else 1),
                            "is_rccl": bool(world > 1 and not rehearse), "bytes_per_step_to_rank0": (world - 1) * per_rank_floats * 4 if world > 1 else 0},
             "camera_samples_per_s": total_cams / elapsed, "rays": total_rays, "camera_samples": total_cams,
             "rays_per_camera_sample": total_rays / max(1, total_cams),
             "rays_counted": "every scene.hit the reference performs (no ray is elided)",
-            "mean_radiance": mean_radiance, "image_sha256_16": image_sha,
-            "roofline": pt_roofline(cnt, rays_per_launch_rank0, kernel_ms, prof_doc, why_not, kernel_name, scratch, {
-                "kernel_ms_max_over_ranks": kernel_ms_max, "kernel_launches": wave_launches,
-                "kernel_ms_is": "one launch on its own, after the timed region (the streamed forms: every kernel of one epoch); "
-                                "`ms_per_step` is wall time of the timed region / steps, where consecutive launches overlap on two streams",
-                "step_span_ms_on_its_stream": epoch_ms,   # start-to-end of a step on its own stream; the other stream's step shares the GPU meanwhile
-                "stream_kernels_ms": stream_split, "ray_state_terms": scratch_terms,
-            }),
         }
-        if elision is not None:
-            out["dead_ray_elision"] = elision
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = pt_cpu_baseline(scene, W, H, args.depth, args.seed, pt)
-        if not args.no_cfg5 and world == 1 and args.scene != "cfg5":
-            out["cfg5"] = cfg5_bench(local_rank, args)
-            out["cfg5_value"], out["cfg5_ms_per_step"] = out["cfg5"]["value"], out["cfg5"]["ms_per_step"]
-        if not args.no_dropin and world == 1 and args.scene == "cbox":
-            out["dropin"] = dropin_pt_bench(local_rank, args)
-            out["dropin_value"], out["dropin_fraction_of_c_abi"] = out["dropin"].get("value"), out["dropin"].get("fraction_of_c_abi")
-        if not args.no_raster and world == 1:
-            out["raster"] = raster_bench(local_rank)
-            out["raster_value"], out["raster_wall_ms"] = out["raster"]["value"], out["raster"]["wall_ms_per_frame"]
-            out["raster_c_abi_wall_ms"] = out["raster"]["c_abi_wall_ms"]["new_stream_every_frame"]
-            out["raster_device_ms_per_frame"] = out["raster"]["device_ms_per_frame"]
+        if outputs is not None:
+            if W * H * 3 * 4 > DUMP_BYTES_PER_IMAGE:          # a larger image: the same seeded sample of pixels from every run
+                pick = np.sort(np.random.default_rng(0).choice(W * H, DUMP_BYTES_PER_IMAGE // 12, replace=False))
+                outputs = {k: v.reshape(-1, 3)[pick] for k, v in outputs.items()}
+                outputs["pixel_index"] = pick.astype(np.float64)
+            outputs["ray_count"] = np.array([total_rays, total_cams], np.float64)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            out["dumped_outputs"] = sorted(outputs)
+        if args.full:
+            # traversal averages of this workload from an instrumented launch (outside the timed region)
+            rng = np.random.default_rng(1)
+            n = 1 << 16
+            xs, ys = rng.integers(0, W, n).astype(np.uint32), rng.integers(0, H, n).astype(np.uint32)
+            ss = rng.integers(0, spp * args.steps, n).astype(np.uint32)
+            pt.trace_samples(args.seed, xs, ys, ss)
+            cnt = pt.counters()
+            rays_per_launch_rank0 = rays / args.steps
+            cams_per_launch_rank0 = cams / args.steps
+            prof_doc, why_not = profile_doc(args.scene, W, spp, world)
+            # ray state that goes through memory per launch (SURVEY.md 8(d)'s last term): a 32-byte record per shaded bounce,
+            # written once and read once, and one 16-byte store per sample (read again by the ordered reduction)
+            scratch, scratch_terms = ray_state_bytes(rays_per_launch_rank0, cams_per_launch_rank0, sc)
+            out.update({
+                "ms_per_step_no_overlap": no_overlap_ms,
+                # what a multi-GPU record needs to verify and decompose itself: the epoch image against the reference-built golden, every
+                # rank's own kernel time (one launch alone, after the timed region) and step span, the exchange step on rank 0
+                "image_equals_golden": golden["image_equals_golden"] if golden else None, "golden_check": golden,
+                "rank_kernel_ms": rank_kernel_ms, "rank_step_span_ms": rank_step_span_ms, "rank_rays": rank_rays,
+                "mean_radiance": main_mean, "image_sha256_16": main_sha[:16],
+                "roofline": pt_roofline(cnt, rays_per_launch_rank0, kernel_ms, prof_doc, why_not, kernel_name, scratch, {
+                    "kernel_ms_max_over_ranks": kernel_ms_max, "kernel_launches": wave_launches,
+                    "kernel_ms_is": "one launch on its own, after the timed region (the streamed forms: every kernel of one epoch); "
+                                    "`ms_per_step` is wall time of the timed region / steps, where consecutive launches overlap on two streams",
+                    "step_span_ms_on_its_stream": epoch_ms,   # start-to-end of a step on its own stream; the other stream's step shares the GPU meanwhile
+                    "stream_kernels_ms": stream_split, "ray_state_terms": scratch_terms,
+                }),
+            })
+            if elision is not None:
+                out["dead_ray_elision"] = elision
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = pt_cpu_baseline(scene, W, H, args.depth, args.seed, pt)
+            if not args.no_cfg5 and world == 1 and args.scene != "cfg5":
+                out["cfg5"] = cfg5_bench(local_rank, args)
+                out["cfg5_value"], out["cfg5_ms_per_step"] = out["cfg5"]["value"], out["cfg5"]["ms_per_step"]
+            if not args.no_dropin and world == 1 and args.scene == "cbox":
+                out["dropin"] = dropin_pt_bench(local_rank, args)
+                out["dropin_value"], out["dropin_fraction_of_c_abi"] = out["dropin"].get("value"), out["dropin"].get("fraction_of_c_abi")
+            if not args.no_raster and world == 1:
+                out["raster"] = raster_bench(local_rank)
+                out["raster_value"], out["raster_wall_ms"] = out["raster"]["value"], out["raster"]["wall_ms_per_frame"]
+                out["raster_c_abi_wall_ms"] = out["raster"]["c_abi_wall_ms"]["new_stream_every_frame"]
+                out["raster_device_ms_per_frame"] = out["raster"]["device_ms_per_frame"]
         print(json.dumps(out), flush=True)
     pt.close()
     if world > 1:

@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Generate the fixtures that pin the oracles against the REFERENCE build without it: the inputs of the reference-build
+tests in tests/test_raster_oracle.py and tests/test_pt_oracle.py and what oracle/_ref/libref_*.so returned for them.
+
+Run where the reference checkout is present and `make -C oracle ref` has built oracle/_ref:
+
+    python tests/golden/make_refbuild_vectors.py
+
+refbuild_raster_random.npz  per supersample rate and seed: the primitive stream, the reference's RGBA8 and the SHA-256 of
+                            its float supersample buffer
+refbuild_pt_samples.npz     per scene: its digest, the sample list, the reference's per-sample radiance and RNG draw counts
+refbuild_tonemap.npz        per seed: the radiance image (NaN and negative values included), the exposure, the reference's bytes
+"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import _harness as H  # noqa: E402
+from _cases import adversarial_stream, pt_sample_list, pt_scene, random_triangles, scene_digest, tonemap_image  # noqa: E402
+
+RASTER_W, RASTER_H = 83, 59
+RASTER_RATES = (1, 2, 3, 4, 7)
+RASTER_SEEDS = (0, 1, 2)
+PT_W, PT_H, PT_DEPTH, PT_SEED = 40, 30, 8, 123456789
+PT_CASES = (("cbox", True), ("cbox_lambertian", False), ("cbox_blob512_glass", True))
+TONEMAP_CASES = ((101, 1.0), (102, 0.8), (103, 3.0))
+
+
+def raster_stream(sr, seed):
+    return np.concatenate([random_triangles(100 * sr + seed, 120, RASTER_W, RASTER_H, 50), adversarial_stream(seed, RASTER_W, RASTER_H)])
+
+
+def tonemap_input(seed):
+    rgb = tonemap_image("mixed", 96, 64, seed)
+    rng = np.random.default_rng(seed)
+    flat = rgb.reshape(-1)
+    flat[rng.integers(0, flat.size, 200)] = np.float32(np.nan)
+    flat[rng.integers(0, flat.size, 200)] = -np.abs(rng.normal(size=200)).astype(np.float32)
+    return rgb
+
+
+def main():
+    assert H.ref_raster() is not None and H.ref_pt_lib() is not None, "build oracle/_ref first: make -C oracle ref"
+    out = {}
+    for sr in RASTER_RATES:
+        for seed in RASTER_SEEDS:
+            prims = raster_stream(sr, seed)
+            rgba, ss = H.ref_raster_prims(prims, RASTER_W, RASTER_H, sr, want_samples=True)
+            out[f"prims_sr{sr}_s{seed}"], out[f"rgba_sr{sr}_s{seed}"] = prims, rgba
+            out[f"ss_sha256_sr{sr}_s{seed}"] = np.array(H.sha(ss))
+    np.savez_compressed(os.path.join(HERE, "refbuild_raster_random.npz"), meta=np.array([RASTER_W, RASTER_H], np.int64), **out)
+
+    out = {}
+    for name, use_bvh in PT_CASES:
+        xs, ys, ss = pt_sample_list(77, PT_W, PT_H, 6000, max_sample=1 << 20)
+        rgb, draws = H.RefPT(pt_scene(name), PT_W, PT_H, PT_DEPTH, use_bvh).trace_samples(PT_SEED, xs, ys, ss)
+        for k, v in (("xs", xs), ("ys", ys), ("ss", ss), ("rgb", rgb), ("draws", draws)):
+            out[f"{k}_{name}"] = np.asarray(v)
+        out[f"scene_sha256_{name}"] = np.array(scene_digest(pt_scene(name)))
+    np.savez_compressed(os.path.join(HERE, "refbuild_pt_samples.npz"), meta=np.array([PT_W, PT_H, PT_DEPTH, PT_SEED], np.int64),
+                        unqualified_sqrt_is_double=np.int64(H.ref_pt_lib().ref_pt_unqualified_sqrt_is_double()), **out)
+
+    out = {}
+    for seed, exposure in TONEMAP_CASES:
+        rgb = tonemap_input(seed)
+        out[f"rgb_{seed}"], out[f"exposure_{seed}"], out[f"rgba_{seed}"] = rgb, np.float32(exposure), H.ref_tonemap(rgb, exposure)
+    np.savez_compressed(os.path.join(HERE, "refbuild_tonemap.npz"), **out)
+    for f in ("refbuild_raster_random.npz", "refbuild_pt_samples.npz", "refbuild_tonemap.npz"):
+        print("wrote", f, os.path.getsize(os.path.join(HERE, f)), "bytes")
+
+
+if __name__ == "__main__":
+    main()

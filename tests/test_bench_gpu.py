@@ -26,7 +26,7 @@ def test_bench_two_ranks_rehearsal_reproduces_the_reference_image(ranks):
     env = dict(os.environ, SRT_BENCH_REHEARSE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(H.ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--no-cfg5", "--no-raster", "--no-elision", "--no-cpu-baseline", "--no-dropin"]
+           "--full", "--no-cfg5", "--no-raster", "--no-elision", "--no-cpu-baseline", "--no-dropin"]
     # a FRESH child process (never an exec from a process that has touched the GPU)
     p = subprocess.run(cmd, env=env, cwd=H.ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]

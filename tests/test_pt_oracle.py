@@ -215,19 +215,23 @@ def test_tonemap_goldens_present():
     assert len(TONEMAP_GOLDENS) >= 4
 
 
-@pytest.mark.skipif(H.ref_pt_lib() is None, reason="reference build (oracle/_ref) not present")
 def test_oracle_tonemap_matches_reference_build():
-    """Fresh seeded images, negative radiance and NaN included (their byte goes through the float -> unsigned char cast the
-    way x86-64 compiles it), against the reference's HDR_Image::tonemap_to itself."""
+    """Seeded images, negative radiance and NaN included (their byte goes through the float -> unsigned char cast the
+    way x86-64 compiles it), against the bytes of the reference's HDR_Image::tonemap_to (tests/golden/refbuild_tonemap.npz,
+    make_refbuild_vectors.py) and, where oracle/_ref is built, against the reference itself."""
     from _cases import tonemap_image
 
+    g = np.load(os.path.join(H.GOLDEN, "refbuild_tonemap.npz"))
     for seed, exposure in ((101, 1.0), (102, 0.8), (103, 3.0)):
         rgb = tonemap_image("mixed", 96, 64, seed)
         rng = np.random.default_rng(seed)
         flat = rgb.reshape(-1)
         flat[rng.integers(0, flat.size, 200)] = np.float32(np.nan)
         flat[rng.integers(0, flat.size, 200)] = -np.abs(rng.normal(size=200)).astype(np.float32)
-        assert np.array_equal(H.oracle_tonemap(rgb, exposure), H.ref_tonemap(rgb, exposure))
+        assert np.array_equal(rgb.view(np.uint32), g[f"rgb_{seed}"].view(np.uint32))
+        assert np.array_equal(H.oracle_tonemap(rgb, exposure), g[f"rgba_{seed}"])
+        if H.ref_pt_lib() is not None:
+            assert np.array_equal(H.ref_tonemap(rgb, exposure), g[f"rgba_{seed}"])
 
 
 def test_accumulate_running_mean():
@@ -241,20 +245,26 @@ def test_accumulate_running_mean():
     assert np.array_equal(acc, want)
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(H.ref_pt_lib() is None, reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("name,use_bvh", [("cbox", True), ("cbox_lambertian", False), ("cbox_blob512_glass", True)])
 def test_oracle_matches_reference_build(name, use_bvh):
+    """Per-sample radiance and draw counts of the reference build on a seeded sample list (tests/golden/refbuild_pt_samples.npz,
+    make_refbuild_vectors.py); where oracle/_ref is built, the reference itself is run on the same samples as well."""
+    g = np.load(os.path.join(H.GOLDEN, "refbuild_pt_samples.npz"))
+    w, h, depth, seed = (int(x) for x in g["meta"])
     scene = pt_scene(name)
-    w, h = 40, 30
-    ref = H.RefPT(scene, w, h, 8, use_bvh)
-    xs, ys, ss = pt_sample_list(77, w, h, 6000, max_sample=1 << 20)
-    r_rgb, r_draws = ref.trace_samples(123456789, xs, ys, ss)
+    assert scene_digest(scene) == str(g[f"scene_sha256_{name}"]), "scene description drifted from the fixture"
+    xs, ys, ss = (g[f"{k}_{name}"] for k in ("xs", "ys", "ss"))
+    assert all(np.array_equal(a, b) for a, b in zip((xs, ys, ss), pt_sample_list(77, w, h, 6000, max_sample=1 << 20)))
+    r_rgb, r_draws = g[f"rgb_{name}"], g[f"draws_{name}"]
+    if H.ref_pt_lib() is not None:
+        l_rgb, l_draws = H.RefPT(scene, w, h, depth, use_bvh).trace_samples(seed, xs, ys, ss)
+        assert bits_equal(l_rgb, r_rgb) and np.array_equal(l_draws, r_draws)
+        assert H.ref_pt_lib().ref_pt_unqualified_sqrt_is_double() == 1
     for mode in (0, 1):
-        o = H.OraclePT(scene, w, h, 8, use_bvh, math_mode=mode)
-        rgb, draws, _ = o.trace_samples(123456789, xs, ys, ss)
+        o = H.OraclePT(scene, w, h, depth, use_bvh, math_mode=mode)
+        rgb, draws, _ = o.trace_samples(seed, xs, ys, ss)
         assert bits_equal(rgb, r_rgb) and np.array_equal(draws, r_draws)
-    assert H.ref_pt_lib().ref_pt_unqualified_sqrt_is_double() == 1  # shapes.cpp's sqrt(delta) is fp64
+    assert int(g["unqualified_sqrt_is_double"]) == 1  # shapes.cpp's sqrt(delta) is fp64
 
 
 def test_fullsize_fixture_matches_scenes_and_oracle_crop():

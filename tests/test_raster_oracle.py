@@ -80,17 +80,22 @@ def test_opaque_cover_hides_history():
     assert (b[..., :3] == [63, 127, 191]).all() and (b[..., 3] == 255).all()
 
 
-@pytest.mark.ref
-@pytest.mark.skipif(H.ref_raster() is None, reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("sr", [1, 2, 3, 4, 7])
 def test_oracle_matches_reference_build_random(sr):
-    w, h = 83, 59
+    """Seeded random + adversarial streams against the reference build's frames of them (tests/golden/refbuild_raster_random.npz,
+    make_refbuild_vectors.py); where oracle/_ref is built, against the reference itself as well."""
+    g = np.load(os.path.join(H.GOLDEN, "refbuild_raster_random.npz"))
+    w, h = (int(x) for x in g["meta"])
     for seed in range(3):
-        prims = np.concatenate([random_triangles(100 * sr + seed, 120, w, h, 50), adversarial_stream(seed, w, h)])
-        r_rgba, r_ss = H.ref_raster_prims(prims, w, h, sr, want_samples=True)
+        prims = g[f"prims_sr{sr}_s{seed}"]
+        assert np.array_equal(prims, np.concatenate([random_triangles(100 * sr + seed, 120, w, h, 50), adversarial_stream(seed, w, h)]))
         o_rgba, o_ss, _ = H.oracle_raster_frame(prims, w, h, sr, want_samples=True)
-        assert np.array_equal(r_rgba, o_rgba)
-        assert np.array_equal(r_ss.view(np.uint32), o_ss.view(np.uint32))
+        assert np.array_equal(g[f"rgba_sr{sr}_s{seed}"], o_rgba)
+        assert H.sha(o_ss) == str(g[f"ss_sha256_sr{sr}_s{seed}"])
+        if H.ref_raster() is not None:
+            r_rgba, r_ss = H.ref_raster_prims(prims, w, h, sr, want_samples=True)
+            assert np.array_equal(r_rgba, o_rgba)
+            assert np.array_equal(r_ss.view(np.uint32), o_ss.view(np.uint32))
 
 
 def _svg_files():

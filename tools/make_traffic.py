@@ -111,7 +111,7 @@ def main():
         "per_kernel_read_bytes": per_kernel(fetch, epochs, "FETCH_SIZE", 2048.0),
         "per_kernel_write_bytes": per_kernel(write, epochs, "WRITE_SIZE", 1024.0),
         "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum in separate passes of "
-                  f"`bench.py --scene {scene} --steps 2 --warmup 0 --no-cpu-baseline --no-raster --no-cfg5 --no-overlap --no-elision` "
+                  f"`bench.py --full --scene {scene} --steps 2 --warmup 0 --no-cpu-baseline --no-raster --no-cfg5 --no-overlap --no-elision` "
                   "(2 timed + 2 measuring epochs), summed over the path tracer's kernels and divided by the epochs; FETCH_SIZE doubled per the "
                   "gfx950 note in MI355X_MICROARCH.md; WRITE_SIZE is uncalibrated for dword-per-lane stores",
     }
