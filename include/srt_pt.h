@@ -123,7 +123,11 @@ int srt_pt_group_render_epoch_lane(srt_pt_group* g, int lane, uint64_t seed, uin
  *   srt_pt_group_accumulator_image   every rank's running mean as tile radiance, ONE ncclGather to rank 0 (copies between ranks that
  *                                    share a device), un-tiled: the width * height * 3 image on rank 0's device and its stream
  * Threads: fold and accumulator_image are not reentrant against each other - the caller serialises them (the drop-in class holds
- * its accumulator mutex); render_samples / wait_lane / fold belong to the render thread, accumulator_image may come from another. */
+ * its accumulator mutex); render_samples / wait_lane / fold belong to the render thread, accumulator_image may come from another.
+ * Lanes and accumulators never move once srt_pt_group_set_params has returned (fixed storage, buffers sized there), so that one
+ * thread's render_samples / wait_lane / fold / render_epoch_lane / read_ray_log on lanes 0 .. 2 may run concurrently with another
+ * thread's accumulator_image (the display lane), and srt_pt_group_cancel may come from any thread at any time.  set_params,
+ * reset_accumulator, set_ray_log and clear_cancel run while nothing else is called on the group. */
 int srt_pt_group_reset_accumulator(srt_pt_group* g);
 int srt_pt_group_max_samples_per_launch(srt_pt_group* g, uint32_t* samples);
 int srt_pt_group_render_samples(srt_pt_group* g, int lane, uint64_t seed, uint32_t sample_base, uint32_t samples);
@@ -240,7 +244,10 @@ int srt_pt_accumulate_device(srt_pt* pt, void* stream, float* d_accumulator, con
  *   d_accumulator   DEVICE, srt_pt_accumulator_floats floats (per pixel slot: the running mean, and the epoch in progress so that
  *                   an epoch may span launches), zeroed by the caller before a render that does not add samples
  *   position        samples of this render folded before this launch;  total_samples: of the whole render (its last epoch may
- *                   be short);  accumulator_samples: epochs the accumulator held before the render (Add Samples continues it)
+ *                   be short);  accumulator_samples: epochs the accumulator held before the render (Add Samples continues it).
+ *                   A fold at position 0 starts with an empty epoch in progress: whatever partial epoch an earlier render left in
+ *                   d_accumulator (one that was cancelled, or whose launches ended off an epoch boundary) is discarded, as the
+ *                   reference drops a cancelled epoch; only the running mean carries over into an Add Samples render
  * The fold goes on the same stream as the launch it folds (it reads that stream's sample buffer) and is skipped when the
  * launch was cancelled.  Launches on two streams overlap; their folds must be ordered by the caller (events).
  * srt_pt_accumulator_tiles_device writes the running mean in the tile layout of srt_pt_render_epoch_device (gather, un-tile). */

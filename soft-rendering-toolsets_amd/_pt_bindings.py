@@ -24,6 +24,8 @@ class SrtCancelled(Exception):
     """A render call returned SRT_CANCELLED: srt_pt_cancel cut it short, its output was not written."""
 
 
+_HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
+
 COUNTER_NAMES = ("rays", "box_tests", "objects_entered", "tri_tests", "sphere_tests", "tlas_nodes", "blas_nodes",
                  "light_tri_tests")
 
@@ -96,6 +98,22 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_group_clear_cancel.argtypes = [c_void_p]
     lib.srt_pt_group_set_ray_log.argtypes = [c_void_p, c_uint32]
     lib.srt_pt_group_read_ray_log.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_uint64)]
+    lib.srt_pt_max_samples_per_launch.argtypes = [c_void_p, POINTER(c_uint32)]
+    lib.srt_pt_accumulator_floats.argtypes = [c_void_p, POINTER(c_size_t)]
+    lib.srt_pt_render_samples_device.argtypes = [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32]
+    lib.srt_pt_fold_epochs_device.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p]
+    lib.srt_pt_accumulator_tiles_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_group_reset_accumulator.argtypes = [c_void_p]
+    lib.srt_pt_group_max_samples_per_launch.argtypes = [c_void_p, POINTER(c_uint32)]
+    lib.srt_pt_group_render_samples.argtypes = [c_void_p, c_int, c_uint64, c_uint32, c_uint32]
+    lib.srt_pt_group_wait_lane.argtypes = [c_void_p, c_int]
+    lib.srt_pt_group_fold.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_uint32, c_uint32]
+    lib.srt_pt_group_accumulator_image.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p)]
+    lib.srt_pt_group_cancel_requested.argtypes = [c_void_p]
+    # (the HIP runtime's own calls, for PathtracerGroup.accumulator_image's read-back)
+    lib.hipSetDevice.argtypes = [c_int]
+    lib.hipMemcpyAsync.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    lib.hipStreamSynchronize.argtypes = [c_void_p]
 
 
 def _p(a):
@@ -305,6 +323,33 @@ class Pathtracer:
     def accumulate_device(self, stream: int, d_acc: int, d_epoch: int, nfloats: int, k: int) -> None:
         self._check(self._lib, self._lib.srt_pt_accumulate_device(self._ctx, c_void_p(stream), c_void_p(d_acc), c_void_p(d_epoch), nfloats, k))
 
+    # -- launches decoupled from the reference's epochs (include/srt_pt.h) -----------------------------------
+    def max_samples_per_launch(self) -> int:
+        m = c_uint32()
+        self._check(self._lib, self._lib.srt_pt_max_samples_per_launch(self._ctx, ctypes.byref(m)))
+        return int(m.value)
+
+    def accumulator_floats(self) -> int:
+        """Floats of the device accumulator a fold keeps (8 per pixel slot of this rank's tiles: running mean, epoch in progress)."""
+        n = c_size_t()
+        self._check(self._lib, self._lib.srt_pt_accumulator_floats(self._ctx, ctypes.byref(n)))
+        return int(n.value)
+
+    def render_samples_device(self, stream: int, seed: int, base: int, n: int) -> None:
+        """One launch of n samples per pixel into `stream`'s sample buffer (srt_pt_fold_epochs_device folds it). No wait."""
+        st = self._lib.srt_pt_render_samples_device(self._ctx, c_void_p(stream), seed, base, n)
+        if st == SRT_CANCELLED:
+            raise SrtCancelled()
+        self._check(self._lib, st)
+
+    def fold_epochs_device(self, stream: int, spe: int, position: int, total: int, first_k: int, d_acc: int) -> None:
+        """do_trace's epoch means and accumulate's running mean over the last launch on `stream`, into the device accumulator d_acc."""
+        self._check(self._lib, self._lib.srt_pt_fold_epochs_device(self._ctx, c_void_p(stream), spe, position, total, first_k, c_void_p(d_acc)))
+
+    def accumulator_tiles_device(self, stream: int, d_acc: int, d_tiles: int) -> None:
+        """The running mean in d_acc as tile radiance (the layout of render_epoch_device)."""
+        self._check(self._lib, self._lib.srt_pt_accumulator_tiles_device(self._ctx, c_void_p(stream), c_void_p(d_acc), c_void_p(d_tiles)))
+
     def set_stream_slots(self, slots: int) -> None:
         """Paths in flight per launch of the streamed forms (0 = default); the image does not depend on it."""
         self._check(self._lib, self._lib.srt_pt_set_stream_slots(self._ctx, int(slots)))
@@ -467,7 +512,8 @@ class PathtracerGroup:
         self._SrtError, self._check = SrtError, _check
         self._lib = load_library()
         self._g = c_void_p()
-        devs = (c_int * len(devices))(*[int(d) for d in devices])
+        self.devices = [int(d) for d in devices]
+        devs = (c_int * len(devices))(*self.devices)
         _check(self._lib, self._lib.srt_pt_create_multi(devs, len(devices), ctypes.byref(self._g)))
         self.members = [Pathtracer(_borrowed_ctx=self._lib.srt_pt_group_context(self._g, r)) for r in range(len(devices))]
         self.out_w = self.out_h = 0
@@ -516,6 +562,42 @@ class PathtracerGroup:
             raise SrtCancelled()
         self._check(self._lib, st)
         return d.value, s.value
+
+    # -- a render with the accumulator on the devices (what the drop-in class renders with) ----------------------------
+    def max_samples_per_launch(self) -> int:
+        m = c_uint32()
+        self._check(self._lib, self._lib.srt_pt_group_max_samples_per_launch(self._g, ctypes.byref(m)))
+        return int(m.value)
+
+    def reset_accumulator(self) -> None:
+        self._check(self._lib, self._lib.srt_pt_group_reset_accumulator(self._g))
+
+    def render_samples(self, lane: int, seed: int, base: int, n: int) -> None:
+        """One launch of n samples per pixel on every rank, on lane `lane`. No wait."""
+        st = self._lib.srt_pt_group_render_samples(self._g, int(lane), seed, base, n)
+        if st == SRT_CANCELLED:
+            raise SrtCancelled()
+        self._check(self._lib, st)
+
+    def wait_lane(self, lane: int) -> None:
+        self._check(self._lib, self._lib.srt_pt_group_wait_lane(self._g, int(lane)))
+
+    def fold(self, lane: int, spe: int, position: int, total: int, first_k: int) -> None:
+        """Fold the launch last rendered on `lane` into every rank's accumulator (call in launch order)."""
+        self._check(self._lib, self._lib.srt_pt_group_fold(self._g, int(lane), spe, position, total, first_k))
+
+    def accumulator_image(self) -> np.ndarray:
+        """The running mean gathered to rank 0 and copied to the host: (h, w, 3) float32, row 0 = bottom (waits for it)."""
+        d, s = c_void_p(), c_void_p()
+        self._check(self._lib, self._lib.srt_pt_group_accumulator_image(self._g, ctypes.byref(d), ctypes.byref(s)))
+        out = np.zeros((self.out_h, self.out_w, 3), np.float32)
+        L = self._lib                                   # the HIP runtime the library is linked to (dlsym searches its dependencies)
+        if L.hipSetDevice(self.devices[0]) != 0 or L.hipMemcpyAsync(_p(out), d, out.nbytes, _HIP_MEMCPY_D2H, s) != 0 or L.hipStreamSynchronize(s) != 0:
+            raise self._SrtError(-3, "srt_pt_group_accumulator_image: copy to the host failed")
+        return out
+
+    def cancel_requested(self) -> bool:
+        return bool(self._lib.srt_pt_group_cancel_requested(self._g))
 
     def cancel_device(self) -> None:
         self._check(self._lib, self._lib.srt_pt_group_cancel(self._g))

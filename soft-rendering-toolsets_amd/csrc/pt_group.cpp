@@ -15,6 +15,7 @@
 #include <cstring>
 #include <new>
 #include <algorithm>
+#include <array>
 #include <set>
 #include <vector>
 
@@ -58,7 +59,8 @@ struct Rccl {
 }  // namespace
 
 // One set of what an epoch in flight needs: a stream and an event per rank, the ranks' tile buffers, the gathered tiles and the
-// image on rank 0.  Lane 0 always exists; further lanes (srt_pt_group_render_epoch_lane) let epochs overlap.
+// image on rank 0.  Lane 0 always exists; further lanes (srt_pt_group_render_epoch_lane) let epochs overlap.  A lane whose streams
+// are not created yet has empty vectors.
 struct GroupLane {
   std::vector<hipStream_t> streams;
   std::vector<hipEvent_t> events;
@@ -72,7 +74,9 @@ constexpr int kMaxLanes = 4;
 struct srt_pt_group {
   std::vector<int> devices;
   std::vector<srt_pt*> ctx;
-  std::vector<GroupLane> lanes;
+  // fixed storage: a lane is created in place, so the render thread creating lane 1 never moves the display lane another thread
+  // is using (srt_pt_group_accumulator_image)
+  std::array<GroupLane, kMaxLanes> lanes;
   size_t tile_floats = 0;               // per rank (srt_pt_group_set_params)
   size_t image_floats = 0;
   bool use_rccl = false;
@@ -80,7 +84,8 @@ struct srt_pt_group {
   std::vector<ncclComm_t> comms;
   uint32_t tile_w = 32, tile_h = 32;
   // the accumulator of a render kept on the devices (srt_pt_group_fold): per rank its tiles' state, the event behind its last
-  // fold and the one behind the last read of it (srt_pt_group_accumulator_image, on the display lane)
+  // fold and the one behind the last read of it (srt_pt_group_accumulator_image, on the display lane).  The vectors and events are
+  // made by srt_pt_create_multi, the buffers by srt_pt_group_set_params: folds and reads only use them
   std::vector<float*> d_acc; std::vector<size_t> acc_floats;
   std::vector<hipEvent_t> fold_done, image_done;
   std::vector<char> fold_recorded, image_recorded;
@@ -100,22 +105,20 @@ void free_lane_buffers(srt_pt_group* g, GroupLane& L) {
   L.tile_floats = L.image_floats = 0;
 }
 
-// A lane's streams and events (once) and its buffers (whenever srt_pt_group_set_params changed the sizes).
+bool lane_exists(const srt_pt_group* g, int lane) { return lane >= 0 && lane < kMaxLanes && !g->lanes[lane].streams.empty(); }
+
+// A lane's streams and events (once, in place) and its buffers (whenever srt_pt_group_set_params changed the sizes).
 int ensure_lane(srt_pt_group* g, int lane) {
   if (lane < 0 || lane >= kMaxLanes) return srt::fail(SRT_ERR_INVALID, "srt_pt_group: lane %d out of range [0, %d)", lane, kMaxLanes);
   const size_t n = g->ctx.size();
-  while ((int)g->lanes.size() <= lane) {
-    GroupLane L;
-    L.streams.assign(n, nullptr); L.events.assign(n, nullptr); L.d_tiles.assign(n, nullptr);
-    g->lanes.push_back(L);
-    GroupLane& N = g->lanes.back();
-    for (size_t r = 0; r < n; r++) {
-      SRT_HIP(hipSetDevice(g->devices[r]));
-      SRT_HIP(hipStreamCreateWithFlags(&N.streams[r], hipStreamNonBlocking));
-      SRT_HIP(hipEventCreateWithFlags(&N.events[r], hipEventDisableTiming));
-    }
-  }
   GroupLane& L = g->lanes[lane];
+  if (L.streams.empty()) { L.streams.assign(n, nullptr); L.events.assign(n, nullptr); L.d_tiles.assign(n, nullptr); }
+  for (size_t r = 0; r < n; r++) {
+    if (L.streams[r] && L.events[r]) continue;
+    SRT_HIP(hipSetDevice(g->devices[r]));
+    if (!L.streams[r]) SRT_HIP(hipStreamCreateWithFlags(&L.streams[r], hipStreamNonBlocking));
+    if (!L.events[r]) SRT_HIP(hipEventCreateWithFlags(&L.events[r], hipEventDisableTiming));
+  }
   if (L.tile_floats == g->tile_floats && L.image_floats == g->image_floats && L.d_image) return SRT_OK;
   for (size_t r = 0; r < n; r++)
     if (L.streams[r]) { SRT_HIP(hipSetDevice(g->devices[r])); SRT_HIP(hipStreamSynchronize(L.streams[r])); }
@@ -169,18 +172,10 @@ int exchange(srt_pt_group* g, GroupLane& L) {
 
 constexpr int kDisplayLane = kMaxLanes - 1;   // srt_pt_group_accumulator_image's own streams and exchange buffers
 
-// Every rank's accumulator state, sized for the current image / tiling; (re)allocated and zeroed when the size changed.
+// Every rank's accumulator state, sized for the current image / tiling; (re)allocated and zeroed when the size changed - by
+// srt_pt_group_set_params, so that a fold and a read of the accumulator from two threads find it in place.
 int ensure_accumulators(srt_pt_group* g) {
   const size_t n = g->ctx.size();
-  if (g->d_acc.size() != n) {
-    g->d_acc.assign(n, nullptr); g->acc_floats.assign(n, 0); g->fold_done.assign(n, nullptr); g->image_done.assign(n, nullptr);
-    g->fold_recorded.assign(n, 0); g->image_recorded.assign(n, 0);
-    for (size_t r = 0; r < n; r++) {
-      SRT_HIP(hipSetDevice(g->devices[r]));
-      SRT_HIP(hipEventCreateWithFlags(&g->fold_done[r], hipEventDisableTiming));
-      SRT_HIP(hipEventCreateWithFlags(&g->image_done[r], hipEventDisableTiming));
-    }
-  }
   for (size_t r = 0; r < n; r++) {
     size_t need = 0;
     const int st = srt_pt_accumulator_floats(g->ctx[r], &need);
@@ -210,10 +205,15 @@ int srt_pt_create_multi(const int* devices, int n, srt_pt_group** out) {
   if (!g) return srt::fail(SRT_ERR_INVALID, "out of host memory");
   g->devices.assign(devices, devices + n);
   g->ctx.assign(n, nullptr);
+  g->d_acc.assign(n, nullptr); g->acc_floats.assign(n, 0); g->fold_done.assign(n, nullptr); g->image_done.assign(n, nullptr);
+  g->fold_recorded.assign(n, 0); g->image_recorded.assign(n, 0);
   int st = SRT_OK;
   for (int r = 0; r < n && st == SRT_OK; r++) {
     st = srt_pt_create(devices[r], &g->ctx[r]);
     if (st == SRT_OK) st = srt_pt_set_tiling(g->ctx[r], g->tile_w, g->tile_h, (uint32_t)r, (uint32_t)n);
+    if (st == SRT_OK && (hipSetDevice(devices[r]) != hipSuccess || hipEventCreateWithFlags(&g->fold_done[r], hipEventDisableTiming) != hipSuccess ||
+                         hipEventCreateWithFlags(&g->image_done[r], hipEventDisableTiming) != hipSuccess))
+      st = srt::fail(SRT_ERR_HIP, "srt_pt_create_multi: hipEventCreate failed");
   }
   if (st == SRT_OK && n > 0) {
     // one RCCL communicator per rank when every rank has a device of its own; shared devices gather by copies
@@ -284,11 +284,14 @@ int srt_pt_group_set_params(srt_pt_group* g, uint32_t width, uint32_t height, ui
     if (st != SRT_OK) return st;
   }
   uint32_t local = 0, per_rank = 0, fpt = 0;
-  const int st = srt_pt_tile_info(g->ctx[0], &local, &per_rank, &fpt);
+  int st = srt_pt_tile_info(g->ctx[0], &local, &per_rank, &fpt);
   if (st != SRT_OK) return st;
   g->tile_floats = (size_t)per_rank * fpt;
   g->image_floats = (size_t)width * height * 3;
-  return ensure_lane(g, 0);
+  // lanes 0 and 1 (the render thread's) and the display lane sized now: later calls only use them
+  for (int lane : {0, 1, kDisplayLane})
+    if ((st = ensure_lane(g, lane)) != SRT_OK) return st;
+  return ensure_accumulators(g);
 }
 
 int srt_pt_group_render_epoch_lane(srt_pt_group* g, int lane, uint64_t seed, uint32_t sample_base, uint32_t samples, float** d_image_out, void** stream_out) {
@@ -414,7 +417,7 @@ int srt_pt_group_render_samples(srt_pt_group* g, int lane, uint64_t seed, uint32
 
 int srt_pt_group_wait_lane(srt_pt_group* g, int lane) {
   if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_wait_lane: NULL group");
-  if (lane < 0 || lane >= (int)g->lanes.size()) return SRT_OK;
+  if (!lane_exists(g, lane)) return SRT_OK;
   GroupLane& L = g->lanes[lane];
   for (size_t r = 0; r < g->ctx.size(); r++) {
     SRT_HIP(hipSetDevice(g->devices[r]));
@@ -427,7 +430,7 @@ int srt_pt_group_wait_lane(srt_pt_group* g, int lane) {
 
 int srt_pt_group_fold(srt_pt_group* g, int lane, uint32_t samples_per_epoch, uint32_t position, uint32_t total_samples, uint32_t accumulator_samples) {
   if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_fold: NULL group");
-  if (lane < 0 || lane >= (int)g->lanes.size() || lane == kDisplayLane) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_fold: nothing was rendered on lane %d", lane);
+  if (!lane_exists(g, lane) || lane == kDisplayLane) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_fold: nothing was rendered on lane %d", lane);
   int st = ensure_accumulators(g);
   if (st != SRT_OK) return st;
   GroupLane& L = g->lanes[lane];
@@ -497,7 +500,7 @@ int srt_pt_group_read_ray_log(srt_pt_group* g, int lane, srt_pt_logged_ray* out,
   if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_read_ray_log: NULL group");
   if (n_out) *n_out = 0;
   if (dropped) *dropped = 0;
-  if (lane < 0 || lane >= (int)g->lanes.size()) return SRT_OK;          // a lane that never rendered has logged nothing
+  if (!lane_exists(g, lane)) return SRT_OK;                            // a lane that never rendered has logged nothing
   GroupLane& L = g->lanes[lane];
   std::vector<srt_pt_logged_ray> all;
   size_t total_waiting = 0;

@@ -1449,7 +1449,9 @@ __global__ void pt_reduce_kernel(TileMap T, uint32_t w, uint32_t h, uint32_t sam
 // in order times 1 / count (a zero Spectrum when none is valid); the accumulator takes s += (mean - s) * (1.0f / k) with k the
 // epoch's 1-based number.  State per pixel slot p (8 floats): {acc rgb, -, sum rgb, count}: the epoch in progress is carried from
 // one launch of the render to the next.  pos = samples of the render in front of this launch, total = samples of the whole render
-// (its last epoch may be short), first_k = epochs the accumulator held before the render.
+// (its last epoch may be short), first_k = epochs the accumulator held before the render.  A fold at pos == 0 starts a render: the
+// epoch in progress starts empty, so that the partial epoch of a render that was cancelled (or ended off an epoch boundary) is
+// dropped as do_trace drops it and never leaks into the first epoch of an Add Samples render that continues the accumulator.
 __global__ void pt_fold_kernel(TileMap T, uint32_t w, uint32_t h, uint32_t samples, const float* __restrict__ sample_out, uint32_t spe,
                                uint32_t pos, uint32_t total, uint32_t first_k, float* __restrict__ state, const uint32_t* dev_cancel) {
   if (*dev_cancel != 0u) return;                         // the launch was cut short (srt_pt_cancel): nothing of it is folded
@@ -1463,6 +1465,7 @@ __global__ void pt_fold_kernel(TileMap T, uint32_t w, uint32_t h, uint32_t sampl
   float4 a = st[0], c = st[1];
   Spec acc = spec(a.x, a.y, a.z), sum = spec(c.x, c.y, c.z);
   uint32_t cnt = __float_as_uint(c.w);
+  if (pos == 0u) { sum = spec(0, 0, 0); cnt = 0u; }
   const float4* src = reinterpret_cast<const float4*>(sample_out) + p;   // [sample][pixel slot]
   for (uint32_t s = 0; s < samples; s++) {
     const float4 q = src[(size_t)s * npix];

@@ -459,6 +459,37 @@ def oracle_accumulate(acc, epoch, k):
     return acc
 
 
+def oracle_epoch_mt(o, seed, base, n, rows=None, threads=16):
+    """OraclePT.epoch split by rows over at most `threads` host threads (srt_oracle_pt_epoch_rows is safe for disjoint rows);
+    rows = (y0, y1) computes only those rows, the others stay zero."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    y0, y1 = rows or (0, o.h)
+    img = np.zeros((o.h, o.w, 3), np.float32)
+    step = max(1, -(-(y1 - y0) // threads))
+    with ThreadPoolExecutor(threads) as pool:
+        list(pool.map(lambda a: o.epoch(seed, base, n, a, min(a + step, y1), img), range(y0, y1, step)))
+    return img
+
+
+def oracle_running_means(epoch_of, total, spe, first_k=0, acc=None, shape=None):
+    """The reference's running mean (rays/pathtracer.cpp:195-231) of a render of `total` samples in epochs of `spe`:
+    [accumulator after 0, 1, 2, ... completed epochs], the epochs given by epoch_of(offset, count)."""
+    acc = np.zeros(shape, np.float32) if acc is None else acc.copy()
+    out = [acc.copy()]
+    k = first_k
+    for s in range(0, total, spe):
+        k += 1
+        oracle_accumulate(acc, epoch_of(s, min(spe, total - s)), k)
+        out.append(acc.copy())
+    return out
+
+
+def epochs_through(through, total, spe):
+    """Epochs of a render completed once `through` of its `total` samples are folded (the last one may be short)."""
+    return -(-total // spe) if through == total else through // spe
+
+
 # ------------------------------------------------------------------------------------------------
 # Host emulation of the device traversal headers (tests/host_emu): pt_device.h / pt_trace.h / pt_flat.h compiled
 # with g++ (same -ffp-contract=off) and run one lane at a time.  Checks the traversal LOGIC on the CPU; the HIP

@@ -211,6 +211,141 @@ def test_pathtracer_core_runs_the_reference_epoch_scheme(srt, devices):
     D.core_destroy(core)
 
 
+_CORE_EPOCHS = {}
+
+
+def _core_epoch(o, key, base, n, rows=None):
+    """The oracle's epoch (seed 11) of samples base .. base + n - 1, cached across the RenderCore tests below."""
+    k = key + (base, n, rows)
+    if k not in _CORE_EPOCHS:
+        _CORE_EPOCHS[k] = H.oracle_epoch_mt(o, 11, base, n, rows)
+    return _CORE_EPOCHS[k]
+
+
+_CORE_ORACLES = {}
+
+
+def _core_oracle(name, w, h, depth):
+    if (name, w, h, depth) not in _CORE_ORACLES:
+        _CORE_ORACLES[(name, w, h, depth)] = H.OraclePT(pt_scene(name), w, h, depth, True)
+    return _CORE_ORACLES[(name, w, h, depth)]
+
+
+def _core_setup(srt, devices, name, w, h, depth, n, threads):
+    D = H.pt_core_driver()
+    scene = pt_scene(name)
+    devs = (ctypes.c_int * len(devices))(*devices)
+    core = ctypes.c_void_p(D.core_create(devs, len(devices)))
+    D.core_set_threads(core, ctypes.c_size_t(threads))
+    D.core_set_params(core, ctypes.c_size_t(w), ctypes.c_size_t(h), ctypes.c_size_t(n), ctypes.c_size_t(depth))
+    for r in range(len(devices)):
+        _feed(srt, D.core_context(core, r), scene, w, h, depth)
+    D.core_set_seed(core, ctypes.c_ulonglong(11))
+    cam = scene["camera"]
+    iview = np.ascontiguousarray(cam["iview"], np.float32)
+    begin = lambda add: D.core_begin(core, H.P(iview), ctypes.c_float(cam["vfov"]), ctypes.c_float(cam["ar"]), int(add))
+    return D, core, begin
+
+
+def _core_image(D, core, w, h):
+    got = np.zeros((h, w, 3), np.float32)
+    D.core_copy_accumulator(core, H.P(got))
+    return got
+
+
+def _bits_mismatch(a, b):
+    return int((a.view(np.uint32) != b.view(np.uint32)).any(axis=2).sum())
+
+
+@pytest.mark.parametrize("devices", [[0], [0, 0, 0]])
+@pytest.mark.parametrize("n,threads", [(150, 1), (200, 2), (130, 13), (1037, 1), (2048, 1)])
+def test_pathtracer_core_epochs_span_launches(srt, devices, n, threads):
+    """RenderCore with an epoch size that does not divide the launch (64 samples): epochs, and the short last epoch, cross launch
+    boundaries, so the fold carries the epoch in progress from one launch to the next; then an Add Samples render that again
+    straddles launches.  2048 samples per pixel through the production path (at a small size)."""
+    name, depth = "cbox", 6
+    w, h = (24, 16) if n >= 2048 else (40, 20)          # [0, 0, 0]: rank 1 owns one tile (or none), rank 2 none
+    D, core, begin = _core_setup(srt, devices, name, w, h, depth, n, threads)
+    o, key = _core_oracle(name, w, h, depth), (name, w, h, depth)
+    begin(False)
+    D.core_wait(core)
+    spe = max(1, n // (threads * 10))                    # rays/pathtracer.cpp:252-253
+    want = H.oracle_running_means(lambda s, c: _core_epoch(o, key, s, c), n, spe, shape=(h, w, 3))
+    assert int(D.core_epochs_accumulated(core)) == len(want) - 1
+    got = _core_image(D, core, w, h)
+    assert np.array_equal(got.view(np.uint32), want[-1].view(np.uint32)), f"{_bits_mismatch(got, want[-1])} pixels differ"
+    more = 70                                            # Add Samples: launches of 64 + 6 from sample n
+    D.core_set_samples(core, ctypes.c_size_t(more))
+    begin(True)
+    D.core_wait(core)
+    spe2 = max(1, more // (threads * 10))
+    want2 = H.oracle_running_means(lambda s, c: _core_epoch(o, key, n + s, c), more, spe2, first_k=len(want) - 1, acc=want[-1])
+    assert int(D.core_epochs_accumulated(core)) == len(want) + len(want2) - 2
+    got = _core_image(D, core, w, h)
+    assert np.array_equal(got.view(np.uint32), want2[-1].view(np.uint32)), f"Add Samples: {_bits_mismatch(got, want2[-1])} pixels differ"
+    D.core_destroy(core)
+
+
+def test_pathtracer_core_cancel_then_add_samples(srt):
+    """Cancel a render part way (its launches end mid-epoch: spe 200, launches of 64), then "Add Samples": the accumulator holds
+    the running mean of the K epochs completed before the cancel, and the Add Samples render continues from there - the cancelled
+    render's partial epoch is dropped (rays/pathtracer.cpp:224), its samples are not averaged into the next render's first epoch.
+    The sample index continues at the cancelled render's full length, as begin() counts it.  Checked on 16 rows of the image."""
+    import time
+
+    name, w, h, depth, n, threads = "cbox", 256, 128, 6, 4000, 2
+    rows = (0, 16)
+    D, core, begin = _core_setup(srt, [0], name, w, h, depth, n, threads)
+    o, key = _core_oracle(name, w, h, depth), (name, w, h, depth)
+    spe = max(1, n // (threads * 10))
+    assert spe == 200
+    begin(False)
+    t0 = time.perf_counter()
+    while int(D.core_epochs_accumulated(core)) < 1 and time.perf_counter() - t0 < 60.0:
+        time.sleep(0.0005)
+    D.core_cancel(core)
+    K = int(D.core_epochs_accumulated(core))
+    print(f"cancelled after {K} of {n // spe} epochs")
+    assert 1 <= K < n // spe, f"the render was not cancelled part way (K = {K})"
+    assert not D.core_in_progress(core)
+    want = H.oracle_running_means(lambda s, c: _core_epoch(o, key, s, c, rows), K * spe, spe, shape=(h, w, 3))
+    got = _core_image(D, core, w, h)
+    y0, y1 = rows
+    assert np.array_equal(got[y0:y1].view(np.uint32), want[K][y0:y1].view(np.uint32)), \
+        f"after the cancel: {_bits_mismatch(got[y0:y1], want[K][y0:y1])} pixels differ from the mean of the first {K} epochs"
+    D.core_set_samples(core, ctypes.c_size_t(7))
+    begin(True)
+    D.core_wait(core)
+    want2 = H.oracle_running_means(lambda s, c: _core_epoch(o, key, n + s, c, rows), 7, 1, first_k=K, acc=want[K])
+    assert int(D.core_epochs_accumulated(core)) == K + 7
+    got = _core_image(D, core, w, h)
+    assert np.array_equal(got[y0:y1].view(np.uint32), want2[-1][y0:y1].view(np.uint32)), \
+        f"Add Samples after the cancel: {_bits_mismatch(got[y0:y1], want2[-1][y0:y1])} pixels differ (the cancelled partial epoch leaked in?)"
+    D.core_destroy(core)
+
+
+def test_pathtracer_core_first_display_from_another_thread(srt):
+    """The GUI thread's first tonemap() comes while the worker starts the render (and its second lane): the group's lanes must not
+    move under either thread.  One run, then the final image against the oracle."""
+    import threading
+
+    name, w, h, depth, n, threads = "cbox", 40, 20, 6, 150, 1
+    D, core, begin = _core_setup(srt, [0], name, w, h, depth, n, threads)
+    o, key = _core_oracle(name, w, h, depth), (name, w, h, depth)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    gui = threading.Thread(target=lambda: D.core_tonemap(core, H.P(rgba), ctypes.c_float(1.0)))
+    begin(False)
+    gui.start()
+    gui.join()
+    D.core_wait(core)
+    want = H.oracle_running_means(lambda s, c: _core_epoch(o, key, s, c), n, max(1, n // (threads * 10)), shape=(h, w, 3))
+    got = _core_image(D, core, w, h)
+    assert np.array_equal(got.view(np.uint32), want[-1].view(np.uint32)), f"{_bits_mismatch(got, want[-1])} pixels differ"
+    D.core_tonemap(core, H.P(rgba), ctypes.c_float(1.0))
+    assert np.array_equal(rgba, H.oracle_tonemap(want[-1], 1.0))
+    D.core_destroy(core)
+
+
 DROPIN_PT_FULL = os.path.join(H.ROOT, "integration", "_build", "libdropin_pt_full.so")
 
 
