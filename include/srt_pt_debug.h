@@ -71,6 +71,12 @@ int srt_pt_math_pow(srt_pt* pt, const float* x, const float* y, size_t n, float*
  * num2, den, x); out: four planes (num0/den, num1/den, num2/den, sqrt(x)).  shared_c2 != 0: a lane's three rays share
  * num2[3i].  Parity tests compare the planes with the host's correctly rounded `/` and sqrtf. */
 int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c2, float* out);
+/* The wave kernel's batch Triangle::hit (pt_device.h: tri_hitN<3>, inside / outside verdict from the numerators and det, only t
+ * divided) next to the plain per-ray tri_hit, lane i on its own triangle, origin and three rays.  in: 27 planes of `lanes`
+ * floats (p0 xyz, e1 xyz, e2 xyz, origin xyz, direction xyz of rays 0, 1, 2, dist_bounds.x of the three rays, dist_bounds.y of
+ * the three rays); out: 19 planes ({hit as 0 / 1, t, dist} of rays 0, 1, 2 from the batch form, the same nine from tri_hit, and
+ * 1 where the lane's wave held an ambiguous lane and computed u and v after all; a wave is 64 consecutive lanes). */
+int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_tonemap.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p]
     lib.srt_pt_tonemap_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p]
     lib.srt_pt_math_div_sqrt.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_int, c_void_p]
+    lib.srt_pt_math_tri_verdict.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_sync.argtypes = [c_void_p]
     lib.srt_pt_cancel.argtypes = [c_void_p]
     lib.srt_pt_cancel_requested.argtypes = [c_void_p]
@@ -491,6 +492,20 @@ class Pathtracer:
         out = np.zeros((4, n3), np.float32)
         self._check(self._lib, self._lib.srt_pt_math_div_sqrt(self._ctx, _p(planes), n3 // 3, int(bool(shared_c2)), _p(out)))
         return out[0], out[1], out[2], out[3]
+
+    def math_tri_verdict(self, tri, org, dirs, bounds):
+        """The wave kernel's batch Triangle::hit (tri_hitN<3>) and the plain tri_hit on n (triangle, origin, three rays) sets.
+        tri (n, 9) = p0, e1, e2; org (n, 3); dirs (n, 3, 3); bounds (n, 3, 2) = dist_bounds of each ray.  Returns
+        (batch, plain, ambiguous_waves): two dicts of (n, 3) arrays {"hit": bool, "t", "dist"} and the number of waves (64
+        consecutive sets) in which some lane was ambiguous, so that the wave computed u and v after all."""
+        tri, org, dirs, bounds = _f32(tri).reshape(-1, 9), _f32(org).reshape(-1, 3), _f32(dirs).reshape(-1, 9), _f32(bounds).reshape(-1, 3, 2)
+        n = len(tri)
+        assert len(org) == n and len(dirs) == n and len(bounds) == n and n > 0
+        planes = np.ascontiguousarray(np.concatenate([tri, org, dirs, bounds[:, :, 0], bounds[:, :, 1]], axis=1).T)
+        out = np.zeros((19, n), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_tri_verdict(self._ctx, _p(planes), n, _p(out)))
+        form = lambda b: {"hit": out[b:b + 9:3].T != 0, "t": out[b + 1:b + 9:3].T.copy(), "dist": out[b + 2:b + 9:3].T.copy()}
+        return form(0), form(9), int(np.count_nonzero(out[18, ::64]))
 
     def math_cos_sin(self, x):
         x = _f32(x)

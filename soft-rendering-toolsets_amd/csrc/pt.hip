@@ -294,6 +294,43 @@ __global__ void pt_div_sqrt_kernel(const float* __restrict__ in, size_t lanes, i
   }
 }
 
+// Triangle::hit of the wave kernel's fold (tri_hitN<3>: verdict from the numerators, only t divided) next to the plain per-ray
+// form (tri_hit), lane i on its own triangle, origin and three rays.  in: 27 planes of `lanes` floats (p0, e1, e2, origin, three
+// directions, then b0 and b1 of the three rays); out: 19 planes - {hit, t, dist} x 3 rays of the batch form, the same of
+// tri_hit, and "this lane's wave computed u and v after all" (an ambiguous lane in it).
+__global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t k = i < lanes ? i : lanes - 1;           // every lane of the last wave computes; the spares repeat the last lane
+  float v[27];
+#pragma unroll
+  for (int j = 0; j < 27; j++) v[j] = in[(size_t)j * lanes + k];
+  Tri g;
+#pragma unroll
+  for (int j = 0; j < 3; j++) { g.p0[j] = v[j]; g.e1[j] = v[3 + j]; g.e2[j] = v[6 + j]; }
+  const V3 org = v3(v[9], v[10], v[11]);
+  V3 d[3];
+  float b0[3], b1[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) { d[r] = v3(v[12 + 3 * r], v[13 + 3 * r], v[14 + 3 * r]); b0[r] = v[21 + r]; b1[r] = v[24 + r]; }
+  TriHitT hb[3];
+  bool fallback = false;
+  tri_hitN<3>(g, org, d, b0, b1, hb, &fallback);
+  if (i < lanes) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
+      const TriHit hp = tri_hit(g, ray);
+      out[(size_t)(3 * r) * lanes + i] = hb[r].hit ? 1.0f : 0.0f;
+      out[(size_t)(3 * r + 1) * lanes + i] = hb[r].t;
+      out[(size_t)(3 * r + 2) * lanes + i] = hb[r].dist;
+      out[(size_t)(9 + 3 * r) * lanes + i] = hp.hit ? 1.0f : 0.0f;
+      out[(size_t)(10 + 3 * r) * lanes + i] = hp.t;
+      out[(size_t)(11 + 3 * r) * lanes + i] = hp.dist;
+    }
+    out[(size_t)18 * lanes + i] = fallback ? 1.0f : 0.0f;
+  }
+}
+
 }  // namespace srt
 
 // ---------------------------------------------------------------------------------------------------
@@ -1687,6 +1724,11 @@ int srt_pt_math_pow(srt_pt* pt, const float* x, const float* y, size_t n, float*
 int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c2, float* out) {
   return math_round_trip(pt, "srt_pt_math_div_sqrt", {in}, 5 * 3 * lanes, {out}, 4 * 3 * lanes, [&](float* const* d, float* const* o) {
     pt_div_sqrt_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, shared_c2, o[0]); });
+}
+
+int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  return math_round_trip(pt, "srt_pt_math_tri_verdict", {in}, 27 * lanes, {out}, 19 * lanes, [&](float* const* d, float* const* o) {
+    pt_tri_verdict_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
 }
 
 

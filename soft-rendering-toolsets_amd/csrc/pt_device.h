@@ -78,12 +78,10 @@ SRT_DEV void sqrtN(const float* x, const bool* zero, float* o) {
 #pragma unroll
   for (int r = 0; r < N; r++) o[r] = sqrtf(x[r]);
 }
-// q[r][j] = n[r][j] / den[r].  SHARED_C2: the caller passes the same numerator in column 2 for all rays (the
-// numerator of t), which is exactly zero for an origin on the triangle's plane; such a lane takes the fast path as
-// well and v_div_fixup gives the signed zero the full sequence would.
+// The fast path's range verdict: every |operand| of the lane in [2^-40, 2^40] (a shared column 2 may also be exactly zero);
+// div_window is the same of the whole wave, one ballot.
 template <int N, bool SHARED_C2>
-SRT_DEV void divNx3(const float (*n)[3], const float* den, float (*q)[3]) {
-#if SRT_EXACT_FAST_PATHS
+SRT_DEV bool div_in_range(const float (*n)[3], const float* den) {
   const float lo = 0x1p-40f, hi = 0x1p40f;     // quotient exponents stay within +-80: no scaling case of v_div_scale
   float mn = fabsf(den[0]), mx = fabsf(den[0]);
 #pragma unroll
@@ -103,12 +101,27 @@ SRT_DEV void divNx3(const float (*n)[3], const float* den, float (*q)[3]) {
     mn = fminf(mn, c2); mx = fmaxf(mx, c2);
   }
   // (min / max skip a NaN operand: it stays a NaN through the refinement, as it would through the full sequence)
-  if (__ballot(!(mn >= lo && mx <= hi)) == 0ull) {
+  return mn >= lo && mx <= hi;
+}
+#if SRT_EXACT_FAST_PATHS
+template <int N, bool SHARED_C2>
+SRT_DEV bool div_window(const float (*n)[3], const float* den) { return __ballot(!div_in_range<N, SHARED_C2>(n, den)) == 0ull; }
+// 1 / den for the refinement: v_rcp (1 ulp) and one Newton step.
+SRT_DEV float rcp_refined(float den) {
+  const float rc = __builtin_amdgcn_rcpf(den);
+  return __builtin_fmaf(__builtin_fmaf(-den, rc, 1.0f), rc, rc);
+}
+#endif
+// q[r][j] = n[r][j] / den[r].  SHARED_C2: the caller passes the same numerator in column 2 for all rays (the
+// numerator of t), which is exactly zero for an origin on the triangle's plane; such a lane takes the fast path as
+// well and v_div_fixup gives the signed zero the full sequence would.
+template <int N, bool SHARED_C2>
+SRT_DEV void divNx3(const float (*n)[3], const float* den, float (*q)[3]) {
+#if SRT_EXACT_FAST_PATHS
+  if (div_window<N, SHARED_C2>(n, den)) {
 #pragma unroll
     for (int r = 0; r < N; r++) {
-      float rc = __builtin_amdgcn_rcpf(den[r]);
-      const float e = __builtin_fmaf(-den[r], rc, 1.0f);
-      rc = __builtin_fmaf(e, rc, rc);
+      const float rc = rcp_refined(den[r]);
 #pragma unroll
       for (int j = 0; j < 3; j++) q[r][j] = div_refine(n[r][j], den[r], rc);
       if (SHARED_C2) q[r][2] = __builtin_amdgcn_div_fixupf(q[r][2], den[r], n[r][2]);
@@ -513,15 +526,53 @@ SRT_DEV TriHit tri_hit(const Tri& g, const Ray& ray) {
   return h;
 }
 
-// Triangle::hit of one triangle for the N rays of a batch (shared origin): s, s x e2 and the numerator of t do
-// not depend on the direction; the 3 N quotients and the N distances go through divNx3 / sqrtN.
+// ---- Triangle::hit's inside / outside verdict from the numerators and det alone ----
+// The reference tests  outside = u < 0 || v < 0 || (1 - u - v) < 0 || t < 0  on the rounded quotients u = RN(nu / det),
+// v = RN(nv / det), t = RN(nt / det).  A caller that reads only {hit, dist, t} needs u and v for nothing else, and for all but a
+// vanishing share of (ray, triangle) pairs the first three tests follow exactly from nu, nv and det.  Precondition (div_window):
+// every operand is a NaN or has a magnitude in [2^-40, 2^40]; nt may also be exactly zero.  Write x = nu / det, y = nv / det
+// for the exact quotients and e = 2^-24 (the unit round-off; nothing here underflows: |x|, |y| >= 2^-80).
+//  * u < 0  <=>  nu * det < 0.  A non-zero quotient of magnitude >= 2^-80 never rounds to zero, so u has the sign of x; the
+//    product (magnitude in [2^-80, 2^80]) has it too.  A NaN makes both sides false.  The same for v.  (t is computed anyway
+//    and tested as it is.)
+//  * Given x, y > 0, the third test is  RN(RN(1 - u) - v) < 0  <=>  p < v  with p = RN(1 - u): the difference of two floats
+//    is a multiple of the smaller one's ulp, so it is zero or rounds to a non-zero float of its own sign.  Also
+//    |p - (1 - u)| <= e / 2 while u <= 1 (1 - u lies in [0, 1]), p <= 0 < v once u >= 1, u and v are within a factor
+//    (1 +- e) of x and y.  The test below compares s = |RN(nu + nv)| = |det| (x + y)(1 + d1), |d1| <= e, with
+//    RN(|det| (1 +- 2^-20)) = |det| (1 +- 2^-20)(1 + d2), |d2| <= e (the two constants are floats):
+//      s > RN(|det| (1 + 2^-20))  =>  x + y > (1 + 2^-20)(1 - e) / (1 + e) > 1 + 2^-21.  Then, for u < 1,
+//        p - v <= 1 - (x + y)(1 - e) + e / 2 < 1 - (1 + 2^-22) + 2^-25 < 0: outside, for certain.
+//      s < RN(|det| (1 - 2^-20))  =>  x + y < (1 - 2^-20)(1 + e) / (1 - e) < 1 - 2^-21, so u < 1 and
+//        p - v >= 1 - (x + y)(1 + e) - e / 2 > 2^-21 - 2^-24 - 2^-25 > 0: not outside, for certain.
+//    2^-20 leaves a factor 8 over what the errors need.  Between the two bounds the lane is AMBIGUOUS (about one pair in 10^6 of
+//    a rendered scene); a NaN among nu, nv, det fails both comparisons and lands there as well, unless u < 0 or v < 0 has
+//    already decided.  The caller then computes u and v and makes the reference's own comparisons.
+// Plain C++ (no device builtins): tests/host_emu runs the same function on the CPU.
+struct TriVerdict { bool outside, ambiguous; };
+SRT_DEV TriVerdict tri_verdict(float nu, float nv, float det) {
+  const bool neg = (nu * det < 0) | (nv * det < 0);
+  const float s = fabsf(nu + nv), a = fabsf(det);
+  const bool beyond = s > a * (1.0f + 0x1p-20f), within = s < a * (1.0f - 0x1p-20f);
+  TriVerdict v;
+  v.outside = neg | beyond;                // of the first three tests
+  v.ambiguous = !(neg | beyond | within);
+  return v;
+}
+
+// Triangle::hit of one triangle for the N rays of a batch (shared origin), for a caller that folds hits (Trace::min): hit,
+// distance and t, no barycentrics.  s, s x e2 and the numerator of t do not depend on the direction.  Inside div_window and
+// with no ambiguous lane in the wave (tri_verdict) only t is divided, through the shared-reciprocal refinement; with one, the
+// wave computes u and v as well and compares them as the reference does (*fallback, when given, is set: wave-uniform).
+// Outside the window, and with SRT_PLAIN_DIV_SQRT, everything is the compiler's own `/`.  The N distances go through sqrtN.
+struct TriHitT { bool hit; float dist, t; };
 template <int N>
-SRT_DEV void tri_hitN(const Tri& g, V3 org, const V3* d, const float* b0, const float* b1, TriHit* h) {
+SRT_DEV void tri_hitN(const Tri& g, V3 org, const V3* d, const float* b0, const float* b1, TriHitT* h, bool* fallback = nullptr) {
   const V3 e1 = v3p(g.e1), e2 = v3p(g.e2);
   const V3 s = org - v3p(g.p0);
   const V3 sxe2 = cross(s, e2);
   const float nt = -1.0f * dot(sxe2, e1);
-  float num[N][3], det[N], q[N][3], n2[N], nr[N];
+  float num[N][3], det[N], t[N], n2[N], nr[N];
+  bool outside[N];
 #pragma unroll
   for (int r = 0; r < N; r++) {
     const V3 e1xd = cross(e1, d[r]);
@@ -530,9 +581,38 @@ SRT_DEV void tri_hitN(const Tri& g, V3 org, const V3* d, const float* b0, const 
     num[r][1] = dot(e1xd, s);
     num[r][2] = nt;
   }
-  divNx3<N, true>(num, det, q);
+  bool decided = false;                         // wave-uniform
+#if SRT_EXACT_FAST_PATHS
+  // one ballot for both conditions: a lane out of the window or an ambiguous one sends the wave the long way
+  bool amb = !div_in_range<N, true>(num, det);
 #pragma unroll
-  for (int r = 0; r < N; r++) n2[r] = norm2(d[r] * q[r][2]);
+  for (int r = 0; r < N; r++) {
+    const TriVerdict v = tri_verdict(num[r][0], num[r][1], det[r]);
+    outside[r] = v.outside;
+    amb = amb | v.ambiguous;
+  }
+  if (__ballot(amb) == 0ull) {
+#pragma unroll
+    for (int r = 0; r < N; r++) {
+      t[r] = __builtin_amdgcn_div_fixupf(div_refine(nt, det[r], rcp_refined(det[r])), det[r], nt);
+      outside[r] = outside[r] | (t[r] < 0);
+    }
+    decided = true;
+  } else if (fallback) {
+    *fallback = div_window<N, true>(num, det);   // in the window: an ambiguous lane it was
+  }
+#endif
+  if (!decided) {
+    float q[N][3];
+    divNx3<N, true>(num, det, q);
+#pragma unroll
+    for (int r = 0; r < N; r++) {
+      t[r] = q[r][2];
+      outside[r] = (q[r][0] < 0) || (q[r][1] < 0) || ((1.0f - q[r][0] - q[r][1]) < 0) || (t[r] < 0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < N; r++) n2[r] = norm2(d[r] * t[r]);
   const bool on_plane = nt == 0.0f;             // t = +-0 for every ray: the distances are exactly +0
   bool zero[N];
 #pragma unroll
@@ -540,11 +620,10 @@ SRT_DEV void tri_hitN(const Tri& g, V3 org, const V3* d, const float* b0, const 
   sqrtN<N>(n2, zero, nr);
 #pragma unroll
   for (int r = 0; r < N; r++) {
-    h[r].u = q[r][0]; h[r].v = q[r][1]; h[r].t = q[r][2];
-    const bool outside = (h[r].u < 0) || (h[r].v < 0) || ((1.0f - h[r].u - h[r].v) < 0) || (h[r].t < 0);
+    h[r].t = t[r];
     h[r].dist = fabsf(nr[r]);
     const bool out_of_bounds = (h[r].dist < b0[r]) || (h[r].dist > b1[r]);
-    h[r].hit = (det[r] != 0) && !outside && !out_of_bounds;
+    h[r].hit = (det[r] != 0) & !outside[r] & !out_of_bounds;       // (no short-circuit: masks, not branches)
   }
 }
 
@@ -584,13 +663,12 @@ SRT_DEV void tri_hit_leaf4(const Tri* g, const Ray& ray, TriHit* h) { tri_hit_le
 // Sphere::hit (student/shapes.cpp:17-80).  The reference's unqualified sqrt(delta) is the double overload,
 // so the numerator sum and the quotient are fp64 before narrowing to t1/t2.  Straight-line form as above.
 struct SphHit { bool hit; float t; };
-SRT_DEV SphHit sphere_hit(float radius, const Ray& ray) {
-  SphHit h;
+// The delta > 0 branch (two roots): delta itself, "a root is valid" and the root the reference returns (0 without one).
+SRT_DEV float sphere_two_roots(float radius, const Ray& ray, bool& hit_two, float& t_two) {
   const float a = norm2(ray.d);
   const float b = 2.0f * dot(ray.o, ray.d);
   const float c = norm2(ray.o) - radius * radius;
   const float delta = b * b - 4.0f * a * c;
-  // delta > 0: two roots
   const double m2od = (double)((-2.0f) * dot(ray.o, ray.d));
   const double sq = sqrt((double)delta);
   const double den = (double)(2.0f * norm2(ray.d));
@@ -601,14 +679,45 @@ SRT_DEV SphHit sphere_hit(float radius, const Ray& ray) {
   const float d2 = fabsf(norm(ray.d * t2));
   v1 = v1 && !(d1 < ray.b0 || d1 > ray.b1);
   v2 = v2 && !(d2 < ray.b0 || d2 > ray.b1);
-  const float t_two = (v1 && v2) ? std_min(t1, t2) : (v1 ? t1 : t2);
-  const bool hit_two = v1 || v2;
-  // delta == 0: tangent, no validity checks in the reference
-  const float t_one = ((-2.0f) * dot(ray.o, ray.d)) / (2.0f * norm2(ray.d));
+  hit_two = v1 || v2;
+  t_two = hit_two ? ((v1 && v2) ? std_min(t1, t2) : (v1 ? t1 : t2)) : 0.0f;
+  return delta;
+}
+// delta == 0: tangent, no validity checks in the reference
+SRT_DEV float sphere_tangent_root(const Ray& ray) { return ((-2.0f) * dot(ray.o, ray.d)) / (2.0f * norm2(ray.d)); }
+SRT_DEV SphHit sphere_hit(float radius, const Ray& ray) {
+  SphHit h;
+  bool hit_two;
+  float t_two;
+  const float delta = sphere_two_roots(radius, ray, hit_two, t_two);
+  const float t_one = sphere_tangent_root(ray);
   const bool two = delta > 0, one = delta == 0;
   h.hit = two ? hit_two : one;
-  h.t = two ? (hit_two ? t_two : 0.0f) : (one ? t_one : 0.0f);
+  h.t = two ? t_two : (one ? t_one : 0.0f);
   return h;
+}
+// Sphere::hit for the N rays of a batch (shared origin), wave-uniformly: the tangent root (a full divide that only a lane with
+// delta == 0 reads) is computed when some lane of the wave has such a ray, which is next to never.
+template <int N>
+SRT_DEV void sphere_hitN(float radius, V3 org, const V3* d, const float* b0, const float* b1, SphHit* h) {
+  Ray ray[N];
+  bool one[N], any_one = false;
+#pragma unroll
+  for (int r = 0; r < N; r++) {
+    ray[r].o = org; ray[r].d = d[r]; ray[r].b0 = b0[r]; ray[r].b1 = b1[r];
+    bool hit_two;
+    float t_two;
+    const float delta = sphere_two_roots(radius, ray[r], hit_two, t_two);
+    const bool two = delta > 0;
+    one[r] = delta == 0;
+    any_one = any_one || one[r];
+    h[r].hit = two ? hit_two : one[r];
+    h[r].t = two ? t_two : 0.0f;
+  }
+  if (__ballot(any_one) != 0ull) {
+#pragma unroll
+    for (int r = 0; r < N; r++) h[r].t = one[r] ? sphere_tangent_root(ray[r]) : h[r].t;
+  }
 }
 
 // Mat4::rotate_to (lib/mat4.h:353-367): columns x, dir, z of the shading frame.

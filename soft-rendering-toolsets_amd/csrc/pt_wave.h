@@ -237,13 +237,12 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
   }
   V3 pos[NR];
   if (o.kind == OBJ_SPHERE) {
+    SphHit sh[NR];
+    sphere_hitN<NR>(o.radius, oorg, od, ob0, ob1, sh);
 #pragma unroll
     for (int r = 0; r < NR; r++) {
-      Ray ray;
-      ray.o = oorg; ray.d = od[r]; ray.b0 = ob0[r]; ray.b1 = ob1[r];
-      const SphHit sh = sphere_hit(o.radius, ray);
-      hit[r] = sh.hit; tri[r] = 0;
-      pos[r] = ray_at(ray, sh.t);
+      hit[r] = sh[r].hit; tri[r] = 0;
+      pos[r] = oorg + od[r] * sh[r].t;                // Ray::at
     }
     float n2[NR], nr[NR];
     bool miss[NR];                                    // no hit: t = 0, pos == origin
@@ -326,26 +325,29 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
     }
     return;                                              // world distances are final
   } else {                                            // one leaf of <= 4 triangles, or List<Triangle>: ordered fold
-    bool bh[NR];
+    // ret = Trace::min(ret, hit) per triangle.  A miss changes nothing: left_wins(l, ., false, .) == l, so either the left side
+    // is kept or both sides are misses and the fields already hold the default Trace (no hit => bd = bt = 0, true before the
+    // loop and kept by every step).  Only a hit that is not beaten (ldist < rdist is false on NaN: the right side wins) is
+    // taken: one mask and one select per field.  "hit so far" is carried as bn != 0, bn = winning triangle's index + 1: a flag
+    // of its own lives in a register across the loop and costs three more instructions per ray and triangle.
     float bd[NR], bt[NR];
-    uint32_t bi[NR];
+    uint32_t bn[NR];
 #pragma unroll
-    for (int r = 0; r < NR; r++) { bh[r] = false; bd[r] = 0.0f; bt[r] = 0.0f; bi[r] = 0u; }
+    for (int r = 0; r < NR; r++) { bd[r] = 0.0f; bt[r] = 0.0f; bn[r] = 0u; }
     for (uint32_t t = 0; t < o.ntri; t++) {
-      TriHit th[NR];
+      TriHitT th[NR];
       tri_hitN<NR>(S.tris[o.tri_base + t], oorg, od, ob0, ob1, th);
 #pragma unroll
       for (int r = 0; r < NR; r++) {
-        const bool keep = left_wins(bh[r], bd[r], th[r].hit, th[r].dist);   // ret = Trace::min(ret, hit)
-        bd[r] = keep ? bd[r] : (th[r].hit ? th[r].dist : 0.0f);
-        bt[r] = keep ? bt[r] : (th[r].hit ? th[r].t : 0.0f);
-        bi[r] = keep ? bi[r] : (th[r].hit ? o.tri_base + t : 0u);
-        bh[r] = keep ? bh[r] : th[r].hit;
+        const bool take = th[r].hit & !((bn[r] != 0u) & (bd[r] < th[r].dist));   // == th.hit && !left_wins(bh, bd, th.hit, th.dist)
+        bd[r] = take ? th[r].dist : bd[r];
+        bt[r] = take ? th[r].t : bt[r];
+        bn[r] = take ? o.tri_base + t + 1u : bn[r];
       }
     }
 #pragma unroll
     for (int r = 0; r < NR; r++) {
-      hit[r] = bh[r]; dist[r] = bd[r]; tri[r] = bi[r];
+      hit[r] = bn[r] != 0u; dist[r] = bd[r]; tri[r] = hit[r] ? bn[r] - 1u : 0u;
       pos[r] = v3(oorg.x + od[r].x * bt[r], oorg.y + od[r].y * bt[r], oorg.z + od[r].z * bt[r]);
     }
   }

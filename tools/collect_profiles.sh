@@ -4,6 +4,8 @@
 # Separate passes (kernel trace; FETCH_SIZE; WRITE_SIZE + L2 hit/miss; two SQ counter passes) as MI355X_MICROARCH.md prescribes:
 # counters are never combined with a trace.  tools/make_traffic.py turns the CSVs into profiles/<tag>_*.
 set -e
+# every GPU pass under its own time limit (STEP_TIMEOUT seconds); set -e ends the script at the first pass that fails or runs over
+rocprofv3() { timeout -k 10 "${STEP_TIMEOUT:-300}" rocprofv3 "$@"; }
 tag=${1:-r02_final}
 scene=${2:-cbox}
 root=$(pwd)
