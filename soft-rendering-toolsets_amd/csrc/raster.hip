@@ -59,7 +59,7 @@ struct RasterParams {
 };
 
 // Everything about one SRT_PRIM_IMAGE record that does not depend on the sample, prepared on the host at upload
-// (upload_stream): the parameters after rasterize_image's `x0 *= sample_rate` (float *= size_t), the mip level
+// (prepare_images): the parameters after rasterize_image's `x0 *= sample_rate` (float *= size_t), the mip level
 // arithmetic of sample_trilinear (it depends on the image extent only and uses the host's log2f, as the reference
 // does), the two mip levels involved, and the values the reference's float loops `for (float x = x0; x <= x1; x++)`
 // take: for every sample column / row of the target the (at most two) loop values that fill_sample's double->int
@@ -886,9 +886,8 @@ struct srt_raster {
   // `reserved` words of `pending` that hold device-side indices (a line's ordinal, an image's ImageAux) while that DMA runs, with
   // the caller's values: put back by settle_upload() once the copy has read them, before anything looks at `pending` again
   std::vector<std::pair<size_t, uint32_t>> patched;
-  srt_prim* d_prims = nullptr;
-  int4* d_bbox = nullptr;
-  size_t d_cap = 0;
+  srt_prim* d_prims = nullptr; size_t prims_cap = 0;
+  int4* d_bbox = nullptr; size_t bbox_cap = 0;
   uint2* d_lists = nullptr; size_t lists_cap = 0;      // coarse-bin lists, packed back to back (raster_bin_pass<2>), entries of {primitive, box}; kept across frames and streams
   uint32_t* d_counts = nullptr; size_t counts_cap = 0; // per coarse bin: entries, then (second half) list offsets
   uint32_t* d_super = nullptr; size_t super_cap = 0;   // super-bin lists (<= 64 x nprims) followed by their 64 counts
@@ -925,6 +924,14 @@ struct srt_raster {
   uint8_t* d_texels = nullptr; size_t texels_cap = 0;
   ImageAux* d_aux = nullptr; size_t aux_cap = 0;
   float* d_tabs = nullptr; size_t tabs_cap = 0;
+  // What the host prepares for a stream's SRT_PRIM_IMAGE and SRT_PRIM_LINE records (prepare_images); kept between uploads for its
+  // storage only - a redraw allocates nothing
+  struct ImagePrep {
+    std::vector<ImageAux> aux;                         // one per image record, in stream order
+    std::vector<float> tabs;                           // their loop-value tables (ImageAux::xtab / ytab)
+    std::vector<std::pair<size_t, uint32_t>> device_reserved;   // (record, the `reserved` word of its device copy)
+    uint32_t nlines = 0;
+  } prep;
 };
 
 namespace {
@@ -933,12 +940,18 @@ namespace {
 // Frames of large primitives used to be better off with 16-high tiles - half the (primitive, tile) pairs - while every pair cost
 // a turn of the ordered loop; since the pairs that cover nothing are dropped 64 at a time in the list scan that no longer holds
 // (stress SVG 1024^2 x 4: 1.40 ms with 8 rows, 1.54 with 16; BASELINE configs[1]: 0.116 / 0.139).  The image does not depend on it.
-uint32_t choose_tile_height(const srt_raster* r) {
-  const uint32_t sr = r->P.sr;
+uint32_t choose_tile_height(uint32_t sr) {
   if (sr > 16) return TS;
   if (sr > 8) return 16;
   if (const char* e = getenv("SRT_RASTER_TSY")) { const uint32_t v = (uint32_t)atoi(e); if ((v == 8 || v == 16 || v == 32) && sr <= v) return v; }   // experiments
   return 8;
+}
+
+// Tiles of (at most) `tsy` sample rows on the target in P: whole pixels per tile, as in x.
+void set_tile_height(RasterParams& P, uint32_t tsy) {
+  P.tile_py = tsy / P.sr;
+  P.tile_sy = P.tile_py * P.sr;
+  P.tiles_y = (P.h + P.tile_py - 1) / P.tile_py;
 }
 
 template <typename T>
@@ -951,6 +964,21 @@ int grow(T** buf, size_t* cap, size_t need) {
   return SRT_OK;
 }
 
+// A pinned host buffer of `cap` elements (`what`, for the error text) that keeps the first `keep` of the old one.  The caller has set
+// the device and has waited for every transfer that may still be reading the old buffer: it is freed here.
+template <typename T>
+int grow_pinned(T** buf, size_t* buf_cap, size_t keep, size_t cap, const char* what) {
+  T* grown = nullptr;
+  if (hipHostMalloc((void**)&grown, cap * sizeof(T), hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    return srt::fail(SRT_ERR_INVALID, "out of pinned host memory for %zu %s", cap, what);
+  }
+  if (keep) std::memcpy(grown, *buf, keep * sizeof(T));
+  if (*buf) (void)hipHostFree(*buf);
+  *buf = grown; *buf_cap = cap;
+  return SRT_OK;
+}
+
 // Before `pending` is read or rewritten on the host: the upload out of it has finished, its records are the caller's again.
 int settle_upload(srt_raster* r) {
   if (r->upload_pending) { SRT_HIP(hipEventSynchronize(r->upload_done)); r->upload_pending = false; }
@@ -959,66 +987,33 @@ int settle_upload(srt_raster* r) {
   return SRT_OK;
 }
 
-int upload_stream(srt_raster* r) {
-  { const int st = settle_upload(r); if (st != SRT_OK) return st; }
+// the same stream again (DrawSVG redraws on every event): nothing to upload, and the bin lists on the device stay valid
+bool same_stream_as_device(const srt_raster* r) {
   const size_t n = r->pending_n;
-  if (n > 0xFFFFFFFFull) return srt::fail(SRT_ERR_UNSUPPORTED, "more than 2^32-1 primitives in one frame");
-  {
-    const uint32_t tsy = choose_tile_height(r);
-    if (tsy / r->P.sr * r->P.sr != r->P.tile_sy) {
-      r->P.tile_py = tsy / r->P.sr;
-      r->P.tile_sy = r->P.tile_py * r->P.sr;
-      r->P.tiles_y = (r->P.h + r->P.tile_py - 1) / r->P.tile_py;
-      r->bins_valid = false;
-    }
-  }
-  // the same stream again (DrawSVG redraws on every event): nothing to upload, and the bin lists on the device stay valid
   bool has_image = false;
   for (size_t i = 0; i < n && !has_image; i++) has_image = r->pending[i].kind == SRT_PRIM_IMAGE;
-  // the texture set as srt_raster_clear_textures / srt_raster_add_texture left it: re-adding the levels the blob already held
-  // changes nothing (add_texture compared them); fewer or more textures than before do
-  if (r->rebuilding) { if (r->textures.size() != r->prev_textures.size()) r->tex_dirty = true; r->rebuilding = false; }
-  r->blob_kept = 0;
   // A stream without images does not care about the textures (tex_dirty stays set for the next stream that does); one with
   // images is the same frame only if its tables - target, textures - are the ones on the device.
-  if ((!has_image || (r->aux_valid && !r->tex_dirty)) && n == r->uploaded.size() && r->P.nprims == (uint32_t)n &&
-      (n == 0 || std::memcmp(r->pending, r->uploaded.data(), n * sizeof(srt_prim)) == 0)) {
-    r->dirty = false;
-    return SRT_OK;
-  }
-  if (n > r->d_cap) {
-    if (r->d_prims) SRT_HIP(hipFree(r->d_prims));
-    if (r->d_bbox) SRT_HIP(hipFree(r->d_bbox));
-    r->d_prims = nullptr; r->d_bbox = nullptr; r->d_cap = 0;
-    size_t cap = n + n / 2 + 64;
-    SRT_HIP(hipMalloc(&r->d_prims, cap * sizeof(srt_prim)));
-    SRT_HIP(hipMalloc(&r->d_bbox, cap * sizeof(int4)));
-    r->d_cap = cap;
-  }
-  // what d_prims is about to hold, as the caller wrote it (the next frame's stream is compared with this); dropped again on every
-  // failure below - without it the next frame just uploads
-  try { r->uploaded.assign(r->pending, r->pending + n); } catch (...) { r->uploaded.clear(); }
-  // SRT_PRIM_IMAGE records: per-image constants and loop-value tables (ImageAux); SRT_PRIM_LINE records: their ordinal.
-  // The device copy of such a record carries the index of its ImageAux / LineAux in `reserved`.
-  std::vector<ImageAux> aux;
-  std::vector<float> tabs;
-  std::vector<std::pair<size_t, uint32_t>>& patched = r->patched;   // (record, original reserved); empty here (settle_upload)
-  const RasterParams& P = r->P;
+  return (!has_image || (r->aux_valid && !r->tex_dirty)) && n == r->uploaded.size() && r->P.nprims == (uint32_t)n &&
+         (n == 0 || std::memcmp(r->pending, r->uploaded.data(), n * sizeof(srt_prim)) == 0);
+}
+
+// SRT_PRIM_IMAGE records: per-image constants and loop-value tables (ImageAux); SRT_PRIM_LINE records: their ordinal.
+// The device copy of such a record carries the index of its ImageAux / LineAux in `reserved`.  Host arithmetic only: the records
+// are read, not written, and nothing here knows the device.
+int prepare_images(const srt_prim* prims, size_t n, const std::vector<srt_raster::Tex>& textures, const RasterParams& P, srt_raster::ImagePrep* out) {
+  std::vector<ImageAux>& aux = out->aux;
+  std::vector<float>& tabs = out->tabs;
+  aux.clear(); tabs.clear(); out->device_reserved.clear();
   const float qnan = std::numeric_limits<float>::quiet_NaN();
   uint32_t nlines = 0;
   for (size_t i = 0; i < n; i++) {
-    srt_prim& p = r->pending[i];
-    if (p.kind == SRT_PRIM_LINE) {
-      patched.emplace_back(i, p.reserved);
-      p.reserved = nlines++;
-      continue;
-    }
+    const srt_prim& p = prims[i];
+    if (p.kind == SRT_PRIM_LINE) { out->device_reserved.emplace_back(i, nlines++); continue; }
     if (p.kind != SRT_PRIM_IMAGE) continue;
-    if (p.reserved >= r->textures.size()) {
-      r->uploaded.clear(); (void)settle_upload(r);
-      return srt::fail(SRT_ERR_INVALID, "primitive %zu refers to texture %u, %zu textures are loaded", i, p.reserved, r->textures.size());
-    }
-    const srt_raster::Tex& T = r->textures[p.reserved];
+    if (p.reserved >= textures.size())
+      return srt::fail(SRT_ERR_INVALID, "primitive %zu refers to texture %u, %zu textures are loaded", i, p.reserved, textures.size());
+    const srt_raster::Tex& T = textures[p.reserved];
     ImageAux A;
     std::memset(&A, 0, sizeof A);
     float x0 = p.v.tri[0], y0 = p.v.tri[1], x1 = p.v.tri[2], y1 = p.v.tri[3];
@@ -1048,79 +1043,111 @@ int upload_stream(srt_raster* r) {
     tabs.resize(tabs.size() + 2 * (size_t)P.ssw, qnan);
     A.ytab = (uint32_t)tabs.size();
     tabs.resize(tabs.size() + 2 * (size_t)P.ssh, qnan);
-    int rx = 0, ry = 0;
-    if (tabs.size() <= 0xFFFFFFFFull) {
-      A.bx0 = A.by0 = 1; A.bx1 = A.by1 = 0;
-      auto walk = [&](float lo, float hi, uint32_t extent, uint32_t tab, int32_t& b0, int32_t& b1) -> int {
-        bool any = false;
-        uint64_t guard = 0;
-        for (float x = lo; x <= hi; x++) {
-          if (x + 1 == x || ++guard > (1ull << 26)) return -1;       // the reference's loop would never end
-          if (!(x > -2147483648.0f && x < 2147483648.0f)) continue;  // (int)x is INT_MIN on x86: rejected by fill_sample
-          const int sx = (int)x;
-          if (sx < 0 || (uint32_t)sx >= extent) continue;
-          float* e = &tabs[tab + sx];
-          if (e[0] != e[0]) e[0] = x;
-          else if (e[extent] != e[extent]) e[extent] = x;
-          else return -2;
-          if (!any) { b0 = b1 = sx; any = true; }
-          b0 = sx < b0 ? sx : b0; b1 = sx > b1 ? sx : b1;
-        }
-        return any ? 1 : 0;
-      };
-      rx = walk(x0, x1, P.ssw, A.xtab, A.bx0, A.bx1);
-      ry = walk(y0, y1, P.ssh, A.ytab, A.by0, A.by1);
-    }
-    if (tabs.size() > 0xFFFFFFFFull || rx < 0 || ry < 0) {
-      r->uploaded.clear(); (void)settle_upload(r);
-      if (tabs.size() > 0xFFFFFFFFull) return srt::fail(SRT_ERR_UNSUPPORTED, "image tables exceed 2^32 entries");
+    if (tabs.size() > 0xFFFFFFFFull) return srt::fail(SRT_ERR_UNSUPPORTED, "image tables exceed 2^32 entries");
+    A.bx0 = A.by0 = 1; A.bx1 = A.by1 = 0;
+    auto walk = [&](float lo, float hi, uint32_t extent, uint32_t tab, int32_t& b0, int32_t& b1) -> int {
+      bool any = false;
+      uint64_t guard = 0;
+      for (float x = lo; x <= hi; x++) {
+        if (x + 1 == x || ++guard > (1ull << 26)) return -1;       // the reference's loop would never end
+        if (!(x > -2147483648.0f && x < 2147483648.0f)) continue;  // (int)x is INT_MIN on x86: rejected by fill_sample
+        const int sx = (int)x;
+        if (sx < 0 || (uint32_t)sx >= extent) continue;
+        float* e = &tabs[tab + sx];
+        if (e[0] != e[0]) e[0] = x;
+        else if (e[extent] != e[extent]) e[extent] = x;
+        else return -2;
+        if (!any) { b0 = b1 = sx; any = true; }
+        b0 = sx < b0 ? sx : b0; b1 = sx > b1 ? sx : b1;
+      }
+      return any ? 1 : 0;
+    };
+    const int rx = walk(x0, x1, P.ssw, A.xtab, A.bx0, A.bx1);
+    const int ry = walk(y0, y1, P.ssh, A.ytab, A.by0, A.by1);
+    if (rx < 0 || ry < 0)
       return srt::fail(SRT_ERR_UNSUPPORTED, "image primitive %zu: extent (%g, %g)-(%g, %g) samples is outside what the reference's float loops can walk",
                        i, (double)x0, (double)y0, (double)x1, (double)y1);
-    }
     if (rx == 0 || ry == 0) { A.bx0 = A.by0 = 1; A.bx1 = A.by1 = 0; }
-    patched.emplace_back(i, p.reserved);
-    p.reserved = (uint32_t)aux.size();
+    out->device_reserved.emplace_back(i, (uint32_t)aux.size());
     aux.push_back(A);
   }
   // (an intery table never holds more than one entry per line and pixel column / row of the target)
-  const bool lines_fit = (uint64_t)nlines * std::max(P.w, P.h) < (1ull << 32);
-  // one DMA transfer out of the pinned buffer; nobody waits for it here - the patched `reserved` words stay as they are until the
-  // host next touches `pending` (settle_upload; the wait per frame for this copy was 9 us of BASELINE configs[1]'s 0.32 ms redraw)
-  hipError_t up = hipSuccess;
-  if (n && lines_fit) {
-    up = hipMemcpyAsync(r->d_prims, r->pending, n * sizeof(srt_prim), hipMemcpyHostToDevice, r->stream);
-    if (up == hipSuccess) { up = hipEventRecord(r->upload_done, r->stream); r->upload_pending = up == hipSuccess; }
-    if (up != hipSuccess) (void)hipStreamSynchronize(r->stream);       // (an event that could not be recorded: wait the plain way)
-  }
-  if (up != hipSuccess || !lines_fit) { r->uploaded.clear(); (void)settle_upload(r); }
+  if ((uint64_t)nlines * std::max(P.w, P.h) >= (1ull << 32))
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%u lines on a %u x %u target: their tables could exceed 2^32 entries", nlines, P.w, P.h);
+  out->nlines = nlines;
+  return SRT_OK;
+}
+
+// The records: one DMA transfer out of the pinned buffer; nobody waits for it here - the patched `reserved` words stay as they are
+// until the host next touches `pending` (settle_upload; the wait per frame for this copy was 9 us of BASELINE configs[1]'s 0.32 ms redraw)
+int upload_prims(srt_raster* r) {
+  const size_t n = r->pending_n;
+  if (!n) return SRT_OK;
+  // the device's words into the records, the caller's into the list, which thereby becomes `patched` (empty until here: settle_upload)
+  for (auto& dr : r->prep.device_reserved) std::swap(r->pending[dr.first].reserved, dr.second);
+  r->patched.swap(r->prep.device_reserved);
+  hipError_t up = hipMemcpyAsync(r->d_prims, r->pending, n * sizeof(srt_prim), hipMemcpyHostToDevice, r->stream);
+  if (up == hipSuccess) { up = hipEventRecord(r->upload_done, r->stream); r->upload_pending = up == hipSuccess; }
+  if (up != hipSuccess) (void)hipStreamSynchronize(r->stream);       // (an event that could not be recorded: wait the plain way)
   SRT_HIP(up);
-  if (!lines_fit) return srt::fail(SRT_ERR_UNSUPPORTED, "%u lines on a %u x %u target: their tables could exceed 2^32 entries", nlines, P.w, P.h);
-  r->nlines = nlines;
-  r->has_images = !aux.empty();
-  if (nlines) {
-    int st = grow(&r->d_laux, &r->laux_cap, (size_t)nlines + nlines / 2);
-    if (st != SRT_OK) return st;
+  return SRT_OK;
+}
+
+// The images' constants and tables, and the texels: only what the device copy does not hold yet (nothing at all when the frame
+// re-added the textures of the last one), one DMA transfer out of the pinned blob, not waited for (add_texture waits before it
+// rewrites the blob)
+int upload_images(srt_raster* r) {
+  const srt_raster::ImagePrep& prep = r->prep;
+  int st;
+  if ((st = grow(&r->d_aux, &r->aux_cap, prep.aux.size())) != SRT_OK || (st = grow(&r->d_tabs, &r->tabs_cap, prep.tabs.size())) != SRT_OK) return st;
+  SRT_HIP(hipMemcpy(r->d_aux, prep.aux.data(), prep.aux.size() * sizeof(ImageAux), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(r->d_tabs, prep.tabs.data(), prep.tabs.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (r->texels_cap < r->blob_n || !r->d_texels) {
+    if ((st = grow(&r->d_texels, &r->texels_cap, r->blob_n ? r->blob_n + r->blob_n / 4 : 4)) != SRT_OK) return st;
+    r->device_blob_n = 0;
   }
-  if (!aux.empty()) {
-    int st;
-    if ((st = grow(&r->d_aux, &r->aux_cap, aux.size())) != SRT_OK || (st = grow(&r->d_tabs, &r->tabs_cap, tabs.size())) != SRT_OK) return st;
-    SRT_HIP(hipMemcpy(r->d_aux, aux.data(), aux.size() * sizeof(ImageAux), hipMemcpyHostToDevice));
-    SRT_HIP(hipMemcpy(r->d_tabs, tabs.data(), tabs.size() * sizeof(float), hipMemcpyHostToDevice));
-    // the texels: only what the device copy does not hold yet (nothing at all when the frame re-added the textures of the last one),
-    // one DMA transfer out of the pinned blob, not waited for (add_texture waits before it rewrites the blob)
-    if (r->texels_cap < r->blob_n || !r->d_texels) {
-      if ((st = grow(&r->d_texels, &r->texels_cap, r->blob_n ? r->blob_n + r->blob_n / 4 : 4)) != SRT_OK) return st;
-      r->device_blob_n = 0;
-    }
-    if (r->device_blob_n < r->blob_n) {
-      SRT_HIP(hipMemcpyAsync(r->d_texels + r->device_blob_n, r->texel_blob + r->device_blob_n, r->blob_n - r->device_blob_n, hipMemcpyHostToDevice, r->stream));
-      r->texel_bytes_uploaded += r->blob_n - r->device_blob_n;
-      r->device_blob_n = r->blob_n;
-      r->blob_upload_pending = true;
-    }
-    r->tex_dirty = false;                          // (only here: a stream without images leaves the flag for the next one with images)
+  if (r->device_blob_n < r->blob_n) {
+    SRT_HIP(hipMemcpyAsync(r->d_texels + r->device_blob_n, r->texel_blob + r->device_blob_n, r->blob_n - r->device_blob_n, hipMemcpyHostToDevice, r->stream));
+    r->texel_bytes_uploaded += r->blob_n - r->device_blob_n;
+    r->device_blob_n = r->blob_n;
+    r->blob_upload_pending = true;
   }
-  r->aux_valid = !aux.empty();
+  r->tex_dirty = false;                            // (only here: a stream without images leaves the flag for the next one with images)
+  return SRT_OK;
+}
+
+// `pending` to the device, unless the device holds it already.
+int upload_stream(srt_raster* r) {
+  int st = settle_upload(r);
+  if (st != SRT_OK) return st;
+  const size_t n = r->pending_n;
+  if (n > 0xFFFFFFFFull) return srt::fail(SRT_ERR_UNSUPPORTED, "more than 2^32-1 primitives in one frame");
+  const uint32_t tsy = choose_tile_height(r->P.sr);
+  if (tsy / r->P.sr * r->P.sr != r->P.tile_sy) { set_tile_height(r->P, tsy); r->bins_valid = false; }
+  // the texture set as srt_raster_clear_textures / srt_raster_add_texture left it: re-adding the levels the blob already held
+  // changes nothing (add_texture compared them); fewer or more textures than before do
+  if (r->rebuilding) { if (r->textures.size() != r->prev_textures.size()) r->tex_dirty = true; r->rebuilding = false; }
+  r->blob_kept = 0;
+  if (same_stream_as_device(r)) { r->dirty = false; return SRT_OK; }
+  if (n > r->prims_cap || n > r->bbox_cap) {
+    const size_t cap = n + n / 2 + 64;
+    if ((st = grow(&r->d_prims, &r->prims_cap, cap)) != SRT_OK || (st = grow(&r->d_bbox, &r->bbox_cap, cap)) != SRT_OK) return st;
+  }
+  // what d_prims is about to hold, as the caller wrote it (the next frame's stream is compared with this); dropped again on every
+  // failure below, with the records' own `reserved` words put back - without it the next frame just uploads
+  try { r->uploaded.assign(r->pending, r->pending + n); } catch (...) { r->uploaded.clear(); }
+  struct DropOnFailure {
+    srt_raster* r; bool done = false;
+    ~DropOnFailure() { if (!done) { r->uploaded.clear(); (void)settle_upload(r); } }
+  } guard{r};
+  srt_raster::ImagePrep& prep = r->prep;
+  if ((st = prepare_images(r->pending, n, r->textures, r->P, &prep)) != SRT_OK) return st;
+  if ((st = upload_prims(r)) != SRT_OK) return st;
+  if (prep.nlines && (st = grow(&r->d_laux, &r->laux_cap, (size_t)prep.nlines + prep.nlines / 2)) != SRT_OK) return st;
+  if (!prep.aux.empty() && (st = upload_images(r)) != SRT_OK) return st;
+  guard.done = true;
+  r->nlines = prep.nlines;
+  r->has_images = r->aux_valid = !prep.aux.empty();
   r->P.nprims = (uint32_t)n;
   r->dirty = false;
   r->bins_valid = false;                         // another stream: setup and binning run on its first frame
@@ -1137,6 +1164,24 @@ void set_grid(RasterParams& P, uint32_t c) {
   P.super_x = (P.coarse_x + P.super_bx - 1) / P.super_bx; P.super_y = (P.coarse_y + P.super_by - 1) / P.super_by;
   P.super_stride = P.nprims ? P.nprims : 1;
   P.packed_ok = (c * P.tile_s <= 256u && c * P.tile_sy <= 256u) ? 1u : 0u;
+}
+
+// Every instantiation of raster_tiles the library holds is named here and nowhere else; nullptr for any other combination.
+using TilesKernel = void (*)(RasterParams, const srt_prim*, const int4*, const uint32_t*, const uint32_t*, const uint32_t*, const ImageAux*, const float*,
+                             const uint8_t*, const LineAux*, const float*, uint32_t*, float4*, unsigned long long*, uint32_t*, uint32_t*);
+struct TilesEntry { bool stats; int tsy; bool img; TilesKernel kern; };
+template <bool STATS, int TSY, bool IMG>
+TilesEntry tiles_entry() { return {STATS, TSY, IMG, raster_tiles<STATS, TSY, IMG>}; }
+TilesKernel tiles_kernel(bool stats, int tsy, bool img) {
+  static const TilesEntry table[] = {
+      tiles_entry<false, 8, false>(), tiles_entry<false, 8, true>(), tiles_entry<false, 16, false>(), tiles_entry<false, 16, true>(),
+      tiles_entry<false, 32, false>(), tiles_entry<false, 32, true>(),
+      tiles_entry<true, 8, false>(), tiles_entry<true, 8, true>(), tiles_entry<true, 16, false>(), tiles_entry<true, 16, true>(),
+      tiles_entry<true, 32, false>(), tiles_entry<true, 32, true>(),   // (the counting build: srt_raster_stats)
+  };
+  for (const TilesEntry& e : table)
+    if (e.stats == stats && e.tsy == tsy && e.img == img) return e.kern;
+  return nullptr;
 }
 
 // Enqueue one frame of the current stream on `s`: raster_setup + the two ordered binning passes when the lists on the device
@@ -1178,17 +1223,13 @@ int launch_frame(srt_raster* r, hipStream_t s, bool dump_samples, bool stats) {
     r->bins_valid = true;
   }
   const uint32_t ntiles = P.tiles_x * P.tiles_y;
-  float4* so = dump_samples ? r->d_samples : nullptr;
-#define SRT_TILES2(STATS_, TSY_, IMG_, ST_)                                                                                 \
-  raster_tiles<STATS_, TSY_, IMG_><<<dim3((ntiles + (TSY_ == 32 ? 1 : kTileWavesPerBlock) - 1) / (TSY_ == 32 ? 1 : kTileWavesPerBlock)), dim3(WAVE * (TSY_ == 32 ? 1 : kTileWavesPerBlock)), 0, s>>>(P, r->d_prims, r->d_bbox, reinterpret_cast<const uint32_t*>(r->d_lists), r->d_counts, \
-                                                                 r->d_counts + (size_t)P.coarse_x * P.coarse_y, r->d_aux,       \
-                                                                 r->d_tabs, r->d_texels, r->d_laux, r->d_ltable, r->d_rgba, so, ST_, r->d_status, r->d_host_status)
-#define SRT_TILES(STATS_, TSY_, ST_) do { if (r->has_images) SRT_TILES2(STATS_, TSY_, true, ST_); else SRT_TILES2(STATS_, TSY_, false, ST_); } while (0)
   const int tsy = P.tile_sy > 16 ? 32 : (P.tile_sy > 8 ? 16 : 8);
-  if (stats) { if (tsy == 32) SRT_TILES(true, 32, r->d_stats); else if (tsy == 16) SRT_TILES(true, 16, r->d_stats); else SRT_TILES(true, 8, r->d_stats); }
-  else { if (tsy == 32) SRT_TILES(false, 32, nullptr); else if (tsy == 16) SRT_TILES(false, 16, nullptr); else SRT_TILES(false, 8, nullptr); }
-#undef SRT_TILES
-#undef SRT_TILES2
+  const TilesKernel kern = tiles_kernel(stats, tsy, r->has_images);
+  if (!kern) return srt::fail(SRT_ERR_STATE, "no tile kernel for %d-row tiles", tsy);
+  const uint32_t wpb = tsy == 32 ? 1 : kTileWavesPerBlock;
+  kern<<<dim3((ntiles + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s>>>(P, r->d_prims, r->d_bbox, reinterpret_cast<const uint32_t*>(r->d_lists), r->d_counts,
+                                                                  r->d_counts + (size_t)P.coarse_x * P.coarse_y, r->d_aux, r->d_tabs, r->d_texels, r->d_laux, r->d_ltable,
+                                                                  r->d_rgba, dump_samples ? r->d_samples : nullptr, stats ? r->d_stats : nullptr, r->d_status, r->d_host_status);
   SRT_HIP(hipGetLastError());
   r->resolved = true;
   return SRT_OK;
@@ -1228,22 +1269,28 @@ int check_frame(srt_raster* r) {
 constexpr int kMaxFrameAttempts = 14 * 2 + 4;
 
 // One frame, repeated while its storage has to grow (at most a few times, and only on the first frame of a stream that needs
-// more than every frame before it).  `sync_all`: the caller needs the frame complete on return; otherwise the function only
-// waits when the stream is new (its needs are unknown until a frame has reported them).
-int run_frame(srt_raster* r, hipStream_t s, bool dump_samples, bool stats, bool sync_all) {
+// more than every frame before it).  With `rgba8_out` the image is read back behind every attempt - frame and read-back are
+// enqueued together; one wait - and the frame is complete on return; without it the function only waits when the stream is new
+// (its needs are unknown until a frame has reported them).
+int run_frame(srt_raster* r, hipStream_t s, bool dump_samples, bool stats, uint8_t* rgba8_out = nullptr) {
   for (int attempt = 0; attempt < kMaxFrameAttempts; attempt++) {
     int st = launch_frame(r, s, dump_samples, stats);
     if (st != SRT_OK) return st;
-    if (r->verified && !sync_all) return SRT_OK;
-    if (!r->verified) {
-      SRT_HIP(hipStreamSynchronize(s));
-      st = check_frame(r);
-      if (st < 0) return st;
-      if (st == 1) continue;
-    }
-    return SRT_OK;
+    if (rgba8_out) SRT_HIP(hipMemcpyAsync(rgba8_out, r->d_rgba, (size_t)r->P.w * r->P.h * 4, hipMemcpyDeviceToHost, s));
+    if (r->verified && !rgba8_out) return SRT_OK;
+    SRT_HIP(hipStreamSynchronize(s));
+    st = check_frame(r);
+    if (st < 0) return st;
+    if (st == 0) return SRT_OK;
   }
   return srt::fail(SRT_ERR_STATE, "the frame's buffers kept growing");
+}
+
+// What every entry point that draws a frame starts with (`who`: its name in the error text): the stream in `pending` is on the device.
+int begin_frame(srt_raster* r, const char* who) {
+  if (!r->have_target) return srt::fail(SRT_ERR_STATE, "%s before srt_raster_set_target", who);
+  SRT_HIP(hipSetDevice(r->device));
+  return r->dirty ? upload_stream(r) : SRT_OK;
 }
 
 }  // namespace
@@ -1263,31 +1310,21 @@ int srt_raster_create(int device, srt_raster** out) {
   srt_raster* r = new (std::nothrow) srt_raster();
   if (!r) return srt::fail(SRT_ERR_INVALID, "out of host memory");
   r->device = device;
-  if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete r;
-    return srt::fail(SRT_ERR_HIP, "hipStreamCreate failed");
-  }
+  // (every failure below: srt_raster_destroy frees what the partly built context holds)
+  const auto give_up = [r](const char* what) { (void)srt_raster_destroy(r); return srt::fail(SRT_ERR_HIP, "%s", what); };
+  if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) return give_up("hipStreamCreate failed");
   if (hipMalloc(&r->d_stats, ST_COUNT * sizeof(unsigned long long)) != hipSuccess ||
       hipMalloc(&r->d_status, FS_COUNT * sizeof(uint32_t)) != hipSuccess ||
       hipMemset(r->d_status, 0, FS_COUNT * sizeof(uint32_t)) != hipSuccess ||
       hipHostMalloc((void**)&r->h_status, FS_COUNT * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&r->d_host_status, r->h_status, 0) != hipSuccess) {
-    (void)hipFree(r->d_stats); (void)hipFree(r->d_status);
-    (void)hipStreamDestroy(r->stream);
-    delete r;
-    return srt::fail(SRT_ERR_HIP, "hipMalloc(stats) failed");
-  }
+      hipHostGetDevicePointer((void**)&r->d_host_status, r->h_status, 0) != hipSuccess)
+    return give_up("hipMalloc(stats) failed");
   std::memset(r->h_status, 0, FS_COUNT * sizeof(uint32_t));
   // hipMemset is ordered on the NULL stream; the context's kernels run on a non-blocking stream that does not wait for it.  Without
   // this wait the first frame could read what the allocation held before (seen on a box whose memory had been used: a stale
   // "line cannot be walked" flag refused a stream without lines).
   (void)hipDeviceSynchronize();
-  if (hipEventCreateWithFlags(&r->upload_done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipFree(r->d_stats); (void)hipFree(r->d_status); (void)hipHostFree(r->h_status);
-    (void)hipStreamDestroy(r->stream);
-    delete r;
-    return srt::fail(SRT_ERR_HIP, "hipEventCreate failed");
-  }
+  if (hipEventCreateWithFlags(&r->upload_done, hipEventDisableTiming) != hipSuccess) return give_up("hipEventCreate failed");
   *out = r;
   return SRT_OK;
 }
@@ -1295,7 +1332,7 @@ int srt_raster_create(int device, srt_raster** out) {
 int srt_raster_destroy(srt_raster* r) {
   if (!r) return SRT_OK;
   (void)hipSetDevice(r->device);
-  (void)hipStreamSynchronize(r->stream);
+  if (r->stream) (void)hipStreamSynchronize(r->stream);   // (NULL stream / event: a context srt_raster_create gave up on)
   if (r->bound_out) (void)hipHostUnregister(r->bound_out);
   (void)hipFree(r->d_prims);
   (void)hipFree(r->d_bbox);
@@ -1315,7 +1352,7 @@ int srt_raster_destroy(srt_raster* r) {
   if (r->pending) (void)hipHostFree(r->pending);
   if (r->texel_blob) (void)hipHostFree(r->texel_blob);
   if (r->upload_done) (void)hipEventDestroy(r->upload_done);
-  (void)hipStreamDestroy(r->stream);
+  if (r->stream) (void)hipStreamDestroy(r->stream);
   (void)hipGetLastError();
   delete r;
   return SRT_OK;
@@ -1355,15 +1392,8 @@ int srt_raster_add_texture(srt_raster* r, uint32_t nlevels, const uint32_t* widt
     }
     if (r->blob_n + bytes > r->blob_cap) {
       SRT_HIP(hipSetDevice(r->device));
-      const size_t cap = std::max(total, (r->blob_n + bytes) * 2);
-      uint8_t* grown = nullptr;
-      if (hipHostMalloc((void**)&grown, cap, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return srt::fail(SRT_ERR_INVALID, "out of pinned host memory for %zu bytes of texels", cap);
-      }
-      if (r->blob_n) std::memcpy(grown, r->texel_blob, r->blob_n);
-      if (r->texel_blob) (void)hipHostFree(r->texel_blob);
-      r->texel_blob = grown; r->blob_cap = cap;
+      const int st = grow_pinned(&r->texel_blob, &r->blob_cap, r->blob_n, std::max(total, (r->blob_n + bytes) * 2), "bytes of texels");
+      if (st != SRT_OK) return st;
     }
     std::memcpy(r->texel_blob + r->blob_n, level_texels[k], bytes);
     r->blob_n += bytes;
@@ -1413,11 +1443,8 @@ int srt_raster_set_target(srt_raster* r, uint32_t width, uint32_t height, uint32
   P.ssw = width * sample_rate; P.ssh = height * sample_rate;
   P.tile_px = TS / sample_rate;
   P.tile_s = P.tile_px * sample_rate;
-  const uint32_t tsy = sample_rate <= 8 ? 8 : (sample_rate <= 16 ? 16 : TS);   // (re-decided per frame: choose_tile_height)
-  P.tile_py = tsy / sample_rate;
-  P.tile_sy = P.tile_py * sample_rate;
   P.tiles_x = (width + P.tile_px - 1) / P.tile_px;
-  P.tiles_y = (height + P.tile_py - 1) / P.tile_py;
+  set_tile_height(P, choose_tile_height(sample_rate));   // (re-decided per frame: upload_stream)
   if (realloc_px) {
     if (r->d_rgba) SRT_HIP(hipFree(r->d_rgba));
     r->d_rgba = nullptr; r->have_target = false;   // until the allocation below has succeeded
@@ -1454,15 +1481,8 @@ int srt_raster_submit(srt_raster* r, const srt_prim* prims, size_t n) {
   if (r->pending_n + n > r->pending_cap) {
     SRT_HIP(hipSetDevice(r->device));
     SRT_HIP(hipStreamSynchronize(r->stream));      // (an upload may still be reading the old buffer)
-    size_t cap = (r->pending_n + n) * 2 + 1024;
-    srt_prim* grown = nullptr;
-    if (hipHostMalloc((void**)&grown, cap * sizeof(srt_prim), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return srt::fail(SRT_ERR_INVALID, "out of pinned host memory for %zu primitives", cap);
-    }
-    if (r->pending_n) std::memcpy(grown, r->pending, r->pending_n * sizeof(srt_prim));
-    if (r->pending) (void)hipHostFree(r->pending);
-    r->pending = grown; r->pending_cap = cap;
+    const int st = grow_pinned(&r->pending, &r->pending_cap, r->pending_n, (r->pending_n + n) * 2 + 1024, "primitives");
+    if (st != SRT_OK) return st;
   }
   if (n) std::memcpy(r->pending + r->pending_n, prims, n * sizeof(srt_prim));
   r->pending_n += n;
@@ -1489,16 +1509,12 @@ int srt_raster_bind_output(srt_raster* r, uint8_t* host_rgba8, size_t bytes) {
 
 int srt_raster_resolve_device(srt_raster* r, void* stream, const uint8_t** d_rgba8_out) {
   if (!r) return srt::fail(SRT_ERR_INVALID, "srt_raster_resolve_device: NULL context");
-  if (!r->have_target) return srt::fail(SRT_ERR_STATE, "resolve before srt_raster_set_target");
-  SRT_HIP(hipSetDevice(r->device));
   hipStream_t s = (hipStream_t)stream;  // exactly the caller's stream; NULL is the HIP default stream
-  if (r->dirty) {
-    int st = upload_stream(r);
-    if (st != SRT_OK) return st;
-    if (s != r->stream) SRT_HIP(hipStreamSynchronize(r->stream));  // upload went on the context stream
-  }
-  int st = run_frame(r, s, false, false, false);
+  const bool upload = r->dirty;
+  int st = begin_frame(r, "resolve");
   if (st != SRT_OK) return st;
+  if (upload && s != r->stream) SRT_HIP(hipStreamSynchronize(r->stream));  // upload went on the context stream
+  if ((st = run_frame(r, s, false, false)) != SRT_OK) return st;
   if (d_rgba8_out) *d_rgba8_out = (const uint8_t*)r->d_rgba;
   return SRT_OK;
 }
@@ -1506,31 +1522,17 @@ int srt_raster_resolve_device(srt_raster* r, void* stream, const uint8_t** d_rgb
 int srt_raster_resolve(srt_raster* r, uint8_t* rgba8_out) {
   if (!rgba8_out) return srt::fail(SRT_ERR_INVALID, "srt_raster_resolve: output buffer is NULL");
   if (!r) return srt::fail(SRT_ERR_INVALID, "srt_raster_resolve: NULL context");
-  if (!r->have_target) return srt::fail(SRT_ERR_STATE, "resolve before srt_raster_set_target");
-  SRT_HIP(hipSetDevice(r->device));
-  if (r->dirty) { int st = upload_stream(r); if (st != SRT_OK) return st; }
-  // frame and read-back are enqueued together; one wait.  (A frame whose storage has to grow is repeated: run_frame.)
-  for (int attempt = 0; attempt < kMaxFrameAttempts; attempt++) {
-    int st = launch_frame(r, r->stream, false, false);
-    if (st != SRT_OK) return st;
-    SRT_HIP(hipMemcpyAsync(rgba8_out, r->d_rgba, (size_t)r->P.w * r->P.h * 4, hipMemcpyDeviceToHost, r->stream));
-    SRT_HIP(hipStreamSynchronize(r->stream));
-    st = check_frame(r);
-    if (st < 0) return st;
-    if (st == 0) return SRT_OK;
-  }
-  return srt::fail(SRT_ERR_STATE, "the frame's buffers kept growing");
+  const int st = begin_frame(r, "resolve");
+  return st != SRT_OK ? st : run_frame(r, r->stream, false, false, rgba8_out);
 }
 
 int srt_raster_read_samples(srt_raster* r, float* samples_out) {
   if (!r || !samples_out) return srt::fail(SRT_ERR_INVALID, "srt_raster_read_samples: NULL argument");
-  if (!r->have_target) return srt::fail(SRT_ERR_STATE, "read_samples before srt_raster_set_target");
-  SRT_HIP(hipSetDevice(r->device));
+  int st = begin_frame(r, "read_samples");
+  if (st != SRT_OK) return st;
   const size_t bytes = (size_t)r->P.ssw * r->P.ssh * sizeof(float4);
   if (!r->d_samples) SRT_HIP(hipMalloc(&r->d_samples, bytes));
-  if (r->dirty) { int st = upload_stream(r); if (st != SRT_OK) return st; }
-  int st = run_frame(r, r->stream, true, false, true);
-  if (st != SRT_OK) return st;
+  if ((st = run_frame(r, r->stream, true, false)) != SRT_OK) return st;
   SRT_HIP(hipMemcpyAsync(samples_out, r->d_samples, bytes, hipMemcpyDeviceToHost, r->stream));
   SRT_HIP(hipStreamSynchronize(r->stream));
   return SRT_OK;
@@ -1538,12 +1540,10 @@ int srt_raster_read_samples(srt_raster* r, float* samples_out) {
 
 int srt_raster_stats(srt_raster* r, srt_raster_stats_t* out) {
   if (!r || !out) return srt::fail(SRT_ERR_INVALID, "srt_raster_stats: NULL argument");
-  if (!r->have_target) return srt::fail(SRT_ERR_STATE, "stats before srt_raster_set_target");
-  SRT_HIP(hipSetDevice(r->device));
-  if (r->dirty) { int st = upload_stream(r); if (st != SRT_OK) return st; }
-  r->verified = false;                           // (the stats pass runs setup and binning again: its status is checked)
-  int st = run_frame(r, r->stream, false, true, true);
+  int st = begin_frame(r, "stats");
   if (st != SRT_OK) return st;
+  r->verified = false;                           // (the stats pass runs setup and binning again: its status is checked)
+  if ((st = run_frame(r, r->stream, false, true)) != SRT_OK) return st;
   unsigned long long h[ST_COUNT];
   SRT_HIP(hipMemcpyAsync(h, r->d_stats, sizeof h, hipMemcpyDeviceToHost, r->stream));
   SRT_HIP(hipStreamSynchronize(r->stream));

@@ -15,7 +15,7 @@ txt = open('/tmp/kres.log').read()
 for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
     name = b.split('\n')[0].split(' [')[0]
     d = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-    short = re.sub(r"\(.*", "", d).replace("void srt::", "").replace("void (anonymous namespace)::", "")
+    short = re.sub(r"\(.*", "", re.sub(r"^void ", "", d).replace("srt::", "").replace("(anonymous namespace)::", ""))
     if not re.search(sys.argv[1], short):
         continue
     g = lambda k: (re.search(re.escape(k) + r": (\d+)", b) or [0, -1])[1]
