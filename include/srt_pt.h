@@ -142,6 +142,8 @@ int srt_pt_group_clear_cancel(srt_pt_group* g);
  * that lane's streams). */
 int srt_pt_group_set_ray_log(srt_pt_group* g, uint32_t capacity);
 int srt_pt_group_read_ray_log(srt_pt_group* g, int lane, srt_pt_logged_ray* out, size_t cap, size_t* n_out, uint64_t* dropped);
+/* srt_pt_set_normal_colors (below) on every member. */
+int srt_pt_group_set_normal_colors(srt_pt_group* g, int on);
 /* Device time of the exchange step of srt_pt_group_render_epoch[_device] - from the moment rank 0's own tiles are rendered to the end of
  * the un-tiling kernel on rank 0's stream: the gather (RCCL, or copies between ranks that share a device) and what it waits for, i.e. the
  * slowest other rank - summed over the epochs since the previous call (HIP events; waits for them); then recording on / off.  A diagnostic
@@ -285,6 +287,27 @@ int srt_pt_clear_cancel(srt_pt* pt);
 int srt_pt_set_ray_log(srt_pt* pt, uint32_t capacity);   /* 0 (default): nothing is recorded */
 int srt_pt_read_ray_log(srt_pt* pt, srt_pt_logged_ray* out, size_t cap, size_t* n_out, uint64_t* dropped);
 int srt_pt_read_ray_log_stream(srt_pt* pt, void* stream, srt_pt_logged_ray* out, size_t cap, size_t* n_out, uint64_t* dropped);
+
+/* ---- the normal-colors debug view (debug_data.normal_colors, student/debug.h; "Pathtracer: use normal colors",
+ * student/debug.cpp:43) ---------------------------------------------------------------------------------------------------
+ * With the box ticked Pathtracer::trace returns {Spectrum::direction(result.normal), {}} right after scene.hit
+ * (student/pathtracer.cpp:199): a render is a first-hit view.  on != 0 reproduces it bit for bit.  A sample draws the two
+ * numbers of Rect(1,1).sample() (student/pathtracer.cpp:29-30), builds the camera ray and calls scene.hit ONCE: 2 RNG draws, 1
+ * ray, and the ray-log coin of :148 is never reached, so a ray log of any capacity stays empty.  A miss is
+ * env_light.evaluate(ray.dir) or zero, as in any render (:182-188).  A hit is Spectrum::direction(normal) (lib/spectrum.h:47-52:
+ * Vec3::normalize, lib/vec3.h:141-147, then absolute values; the to_linear() of :50 discards its result, so no sRGB curve is
+ * applied) BEFORE the emissive test: light sources show their normals too.  The normal is Trace::normal as Object::hit returns
+ * it - interpolated vertex normals for meshes, not unit length in general; a zero normal gives NaN in every channel and the
+ * sample is dropped as do_trace drops invalid samples (rays/pathtracer.cpp:219-222).
+ * While it is on, srt_pt_render_epoch[_device], srt_pt_render_samples_device (+ srt_pt_fold_epochs_device; under kernel mode 1
+ * as well, this kernel always keeps per-sample radiance), srt_pt_trace_samples and the group forms take one first-hit kernel
+ * (one lane per pixel and sample, no path state) for every scene srt_pt_scene_commit accepts, whatever srt_pt_set_kernel says;
+ * tiling, streams, cancel, srt_pt_sync and srt_pt_kernel_time behave as for any other form, srt_pt_ray_count counts one ray per
+ * camera sample and srt_pt_rays_elided stays 0.  srt_pt_hit, the particle step, tone mapping and the BVH dumps do not look at it.
+ * The reference reads its global on every trace call; here the switch is read when a launch is enqueued: a change takes effect
+ * at the next launch.  It needs no re-commit and may be called whenever nothing of the context is being enqueued (the rule of
+ * srt_pt_set_elision).  Default: off - every output is what it was without the switch. */
+int srt_pt_set_normal_colors(srt_pt* pt, int on);
 
 /* Rays (scene.hit calls) and camera samples traced by this context since the last reset. */
 int srt_pt_ray_count(srt_pt* pt, uint64_t* rays, uint64_t* camera_samples, int reset);

@@ -33,7 +33,7 @@ int srt_pt_set_kernel(srt_pt* pt, int mode);   /* modes 6 and 7: see below */
 int srt_pt_section_cycles(srt_pt* pt, uint64_t out[8], int reset);
 
 /* Device time of the dominant kernel of render_epoch[_device] (pt_wave_kernel / pt_unit_kernel / pt_epoch_kernel,
- * whichever the scene selects), measured with HIP events recorded on the launch stream around each launch.
+ * whichever the scene selects; pt_normals_kernel while srt_pt_set_normal_colors is on), measured with HIP events recorded on the launch stream around each launch.
  * Returns the sum over the launches recorded since the previous call (waits for them), then switches
  * recording on (enable != 0) or off.  Off by default. */
 int srt_pt_kernel_time(srt_pt* pt, int enable, double* total_ms, uint64_t* launches);
@@ -50,7 +50,8 @@ int srt_pt_stream_times(srt_pt* pt, int enable, double ms_out[4], uint64_t* gene
 int srt_pt_stream_counters(srt_pt* pt, uint64_t out[4], int reset);
 /* Which form render_epoch* takes for the committed scene under the current kernel mode: 0 persistent wave kernel with sweeps,
  * 1 the same with inline BVH<Triangle> walks, 2 persistent waves with the flattened walk, 3 streamed (every ray through the
- * ray-cast kernel), 4 streamed sweeps (BVH<Triangle> walks queued), -1 lane per sample, -2 lane per pixel. */
+ * ray-cast kernel), 4 streamed sweeps (BVH<Triangle> walks queued), -1 lane per sample, -2 lane per pixel; -3 while
+ * srt_pt_set_normal_colors is on: the first-hit kernel of the normal-colors view, whatever the scene and the kernel mode. */
 int srt_pt_kernel_form(srt_pt* pt, int* form);
 
 /* Traversal counters of the LAST srt_pt_trace_samples call (an instrumented launch):

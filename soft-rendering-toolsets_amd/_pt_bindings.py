@@ -81,6 +81,8 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_math_atan2.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_set_elision.argtypes = [c_void_p, c_int]
     lib.srt_pt_rays_elided.argtypes = [c_void_p, POINTER(c_uint64), c_int]
+    lib.srt_pt_set_normal_colors.argtypes = [c_void_p, c_int]
+    lib.srt_pt_group_set_normal_colors.argtypes = [c_void_p, c_int]
     lib.srt_pt_math_exp.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_pow.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_tonemap.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p]
@@ -394,7 +396,7 @@ class Pathtracer:
 
     def kernel_form(self) -> int:
         """Form render_epoch takes for the committed scene: 0 / 1 persistent sweeps (1: inline mesh walks), 2 flattened walk,
-        3 streamed, 4 streamed sweeps, -1 lane per sample, -2 lane per pixel."""
+        3 streamed, 4 streamed sweeps, -1 lane per sample, -2 lane per pixel; -3 while set_normal_colors is on."""
         f = c_int()
         self._check(self._lib, self._lib.srt_pt_kernel_form(self._ctx, ctypes.byref(f)))
         return int(f.value)
@@ -455,6 +457,11 @@ class Pathtracer:
     def set_elision(self, on: bool) -> None:
         """Let the wave kernel skip the provably dead BSDF-sampled direct ray (include/srt_pt.h); images stay bit-identical."""
         self._check(self._lib, self._lib.srt_pt_set_elision(self._ctx, int(bool(on))))
+
+    def set_normal_colors(self, on: bool) -> None:
+        """The reference's debug_data.normal_colors: every render call takes the first-hit kernel and a sample is
+        Spectrum::direction(normal) of the camera ray's hit (include/srt_pt.h).  Takes effect at the next launch."""
+        self._check(self._lib, self._lib.srt_pt_set_normal_colors(self._ctx, int(bool(on))))
 
     def rays_elided(self, reset: bool = False) -> int:
         n = c_uint64(0)
@@ -557,6 +564,10 @@ class PathtracerGroup:
     def set_elision(self, on: bool) -> None:
         for m in self.members:
             m.set_elision(on)
+
+    def set_normal_colors(self, on: bool) -> None:
+        """srt_pt_group_set_normal_colors: the normal-colors debug view on every member."""
+        self._check(self._lib, self._lib.srt_pt_group_set_normal_colors(self._g, int(bool(on))))
 
     def render_epoch(self, seed: int, sample_base: int, samples: int) -> np.ndarray:
         out = np.zeros((self.out_h, self.out_w, 3), np.float32)

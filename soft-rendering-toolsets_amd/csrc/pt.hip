@@ -109,8 +109,37 @@ __global__ __launch_bounds__(64, 8) void pt_unit_kernel(DScene S, TileMap T, uin
   if ((threadIdx.x & 63) == 0 && r) { atomicAdd(ray_counter, r); if (e) atomicAdd(ray_counter + 1, e); }
 }
 
-// Explicit (x, y, sample) triples; instrumented when COUNT.
-template <bool COUNT>
+// The normal-colors debug view (srt_pt_set_normal_colors; debug_data.normal_colors, student/pathtracer.cpp:199): a first-hit
+// kernel, one lane per (pixel, sample) unit - normal_sample() in pt_trace.h.  Unit u is sample u / npix of pixel slot u % npix:
+// npix is a multiple of 64, so the 64 lanes of a wave hold one 8x8 pixel block (unit_pixel) of one sample index - primary rays
+// of neighbouring pixels walk the same nodes - and write 64 consecutive float4 of pt_unit_kernel's [sample][pixel slot] layout,
+// which pt_reduce_kernel / pt_fold_kernel read unchanged.  Padding pixels of edge tiles write and count nothing.  Per-lane
+// traversal stacks only: no path slots, no records, no LDS.  8 waves/SIMD as pt_unit_kernel: a walk waits on memory.
+__global__ __launch_bounds__(64, 8) void pt_normals_kernel(DScene S, TileMap T, uint64_t seed, uint32_t sample_base, uint32_t npix,
+                                                        uint32_t total_units, float* __restrict__ sample_out,
+                                                        unsigned long long* __restrict__ ray_counter, const uint32_t* host_cancel, uint32_t* dev_cancel) {
+  if (blockIdx.x == 0u && threadIdx.x == 0u && cancel_requested(host_cancel)) atomicExch(dev_cancel, 1u);   // (as pt_epoch_kernel)
+  if (cancel_raised(dev_cancel)) return;
+  const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+  Counters cnt;
+  cnt.v[C_RAYS] = 0;
+  if (u < total_units) {
+    uint32_t x, y;
+    unit_pixel(T, u % npix, x, y);
+    if (x < S.w && y < S.h) {
+      Rng rng;
+      rng.key(seed, y * S.w + x, sample_base + u / npix);
+      const Spec p = normal_sample<false>(S, x, y, rng, cnt);
+      reinterpret_cast<float4*>(sample_out)[u] = make_float4(p.r, p.g, p.b, 0.0f);
+    }
+  }
+  unsigned long long r = cnt.v[C_RAYS];
+  for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off);
+  if ((threadIdx.x & 63) == 0 && r) atomicAdd(ray_counter, r);
+}
+
+// Explicit (x, y, sample) triples; instrumented when COUNT.  NORMALS: the normal-colors view (normal_sample) instead of a path.
+template <bool COUNT, bool NORMALS = false>
 __global__ __launch_bounds__(64) void pt_samples_kernel(DScene S, uint64_t seed, const uint32_t* __restrict__ xs,
                                                         const uint32_t* __restrict__ ys, const uint32_t* __restrict__ ss,
                                                         uint32_t n, float* __restrict__ rgb, uint32_t* __restrict__ draws,
@@ -121,7 +150,7 @@ __global__ __launch_bounds__(64) void pt_samples_kernel(DScene S, uint64_t seed,
   for (int k = 0; k < C_COUNT; k++) cnt.v[k] = 0;
   Rng rng;
   rng.key(seed, ys[i] * S.w + xs[i], ss[i]);
-  const Spec p = path_sample<COUNT>(S, xs[i], ys[i], rng, cnt);
+  const Spec p = NORMALS ? normal_sample<COUNT>(S, xs[i], ys[i], rng, cnt) : path_sample<COUNT>(S, xs[i], ys[i], rng, cnt);
   rgb[3 * i] = p.r; rgb[3 * i + 1] = p.g; rgb[3 * i + 2] = p.b;
   if (draws) draws[i] = rng.draws;
   if (COUNT) {
@@ -398,6 +427,7 @@ struct srt_pt {
   uint32_t* d_host_cancel = nullptr;        // its device address
   uint32_t ray_log_cap = 0;                 // srt_pt_set_ray_log: rays per stream and read; 0: Pathtracer::log_ray is not delivered
   int elide = 0;                            // srt_pt_set_elision
+  int normal_colors = 0;                    // srt_pt_set_normal_colors: read whenever a launch is enqueued
   unsigned long long last_counters[C_COUNT] = {0};
   uint64_t camera_samples = 0;
   // srt_pt_kernel_time: event pairs recorded around the dominant kernel's launches, on the launch stream
@@ -990,6 +1020,26 @@ int render_epoch_units(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t sample
   return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
 }
 
+// One epoch of the normal-colors view (srt_pt_set_normal_colors): pt_normals_kernel whatever the scene and srt_pt_set_kernel say -
+// it keeps per-sample radiance, so the reduction, the fold and the tile layout are those of every other form.
+int render_epoch_normals(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t sample_base, uint32_t samples, float* d_tiles_out) {
+  const TileMap& T = pt->tiles;
+  const uint32_t px = T.local_tiles * T.tile_w * T.tile_h;
+  int st;
+  srt_pt::EpochBuffers* Bp = nullptr;
+  if ((st = sample_buffers(pt, s, px, &Bp)) != SRT_OK) return st;
+  srt_pt::EpochBuffers& B = *Bp;
+  const DScene DS = device_scene(pt, &B);
+  auto stage = [](uint32_t, uint32_t) -> int { return SRT_OK; };
+  auto launch = [&](uint32_t first_sample, uint32_t n) -> int {
+    const uint64_t units = (uint64_t)px * n;               // (px is a multiple of 64: whole waves)
+    pt_normals_kernel<<<dim3((unsigned)((units + 63) / 64)), dim3(64), 0, s>>>(DS, T, seed, first_sample, px, (uint32_t)units, B.d_samples, pt->d_totals + C_COUNT,
+                                                                               pt->d_host_cancel, B.d_cancel);
+    return SRT_OK;
+  };
+  return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
+}
+
 }  // namespace
 
 namespace srt {
@@ -1275,8 +1325,11 @@ int render_device(srt_pt* pt, const char* what, void* stream, uint64_t seed, uin
   if (lanes * 64 > 0xffffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "more than 2^32 sample units per launch");
   if (lanes) {
     KernelForm K;
-    if ((st = resolve_form(pt, &K)) != SRT_OK) return st;
-    if (pt->kernel_mode != 1) {
+    if (pt->normal_colors) {                              // the debug view: one kernel for every scene and kernel mode
+      if ((st = render_epoch_normals(pt, s, seed, sample_base, samples, d_tiles_out)) != SRT_OK) return st;
+    } else if ((st = resolve_form(pt, &K)) != SRT_OK) {
+      return st;
+    } else if (pt->kernel_mode != 1) {
       st = K.trav >= 3 ? render_epoch_stream(pt, s, K, seed, sample_base, samples, d_tiles_out)
          : K.trav >= 0 ? render_epoch_wave(pt, s, K, seed, sample_base, samples, d_tiles_out)
                        : render_epoch_units(pt, s, seed, sample_base, samples, d_tiles_out);
@@ -1330,7 +1383,8 @@ int srt_pt_accumulator_floats(srt_pt* pt, size_t* nfloats) {
 
 int srt_pt_render_samples_device(srt_pt* pt, void* stream, uint64_t seed, uint32_t sample_base, uint32_t samples) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_render_samples_device: NULL context");
-  if (pt->kernel_mode == 1) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_render_samples_device: the lane-per-pixel kernel (mode 1) keeps no per-sample radiance");
+  if (pt->kernel_mode == 1 && !pt->normal_colors)        // (the normal-colors kernel always keeps per-sample radiance)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_render_samples_device: the lane-per-pixel kernel (mode 1) keeps no per-sample radiance");
   if (pt->w) {
     const uint32_t most = samples_per_launch(pt->tiles.local_tiles * pt->tiles.tile_w * pt->tiles.tile_h);
     if (samples == 0 || samples > most) return srt::fail(SRT_ERR_INVALID, "srt_pt_render_samples_device: 1..%u samples per launch (got %u)", most, samples);
@@ -1504,7 +1558,7 @@ int srt_pt_kernel_form(srt_pt* pt, int* form) {
   if (!pt || !form) return srt::fail(SRT_ERR_INVALID, "srt_pt_kernel_form: NULL argument");
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_kernel_form before srt_pt_scene_commit");
   const int t = wave_trav(pt);
-  *form = t >= 0 ? t : (pt->kernel_mode == 1 ? -2 : -1);
+  *form = pt->normal_colors ? -3 : (t >= 0 ? t : (pt->kernel_mode == 1 ? -2 : -1));
   return SRT_OK;
 }
 
@@ -1529,6 +1583,12 @@ int srt_pt_set_elision(srt_pt* pt, int on) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_elision: NULL context");
   pt->elide = on ? 1 : 0;
   pt->wave_blocks = 0;                                    // the launch configuration is re-derived for the other build
+  return SRT_OK;
+}
+
+int srt_pt_set_normal_colors(srt_pt* pt, int on) {
+  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_normal_colors: NULL context");
+  pt->normal_colors = on ? 1 : 0;
   return SRT_OK;
 }
 
@@ -1561,8 +1621,8 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
   SRT_HIP(hipMemcpyAsync(dy, ys, n * 4, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(ds, ss, n * 4, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemsetAsync(pt->d_totals, 0, C_COUNT * sizeof(unsigned long long), pt->stream));
-  pt_samples_kernel<true><<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pt->stream>>>(device_scene(pt), seed, dx, dy, ds, (uint32_t)n,
-                                                                                   drgb, dd, dr, pt->d_totals);
+  const auto kern = pt->normal_colors ? pt_samples_kernel<true, true> : pt_samples_kernel<true, false>;
+  kern<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pt->stream>>>(device_scene(pt), seed, dx, dy, ds, (uint32_t)n, drgb, dd, dr, pt->d_totals);
   SRT_HIP(hipGetLastError());
   SRT_HIP(hipMemcpyAsync(rgb_out, drgb, n * 12, hipMemcpyDeviceToHost, pt->stream));
   if (draws_out) SRT_HIP(hipMemcpyAsync(draws_out, dd, n * 4, hipMemcpyDeviceToHost, pt->stream));

@@ -783,6 +783,30 @@ SRT_DEV Spec path_sample(const DScene& S, uint32_t x, uint32_t y, Rng& rng, Coun
   return emissive_cam + L;
 }
 
+// Spectrum::direction (lib/spectrum.h:47-52): Vec3::normalize (lib/vec3.h:141-147: n = norm(), three divisions), then the
+// absolute values.  The `s.to_linear()` of :50 is the const member whose result is dropped: no sRGB curve.  A zero vector
+// gives 0 / 0 = NaN in every channel.
+SRT_DEV Spec spec_direction(V3 v) {
+  const float n = norm(v);
+  return spec(fabsf(v.x / n), fabsf(v.y / n), fabsf(v.z / n));
+}
+
+// Pathtracer::trace_pixel with debug_data.normal_colors set (student/pathtracer.cpp:14-40,174-199): the two draws of
+// Rect(1,1).sample(), the camera ray, ONE scene.hit; a miss sees the environment light as in any render, a hit returns
+// Spectrum::direction(normal) before the emissive test (the two-sided flip of :193 is absorbed by the absolute value).
+// Nothing else is drawn and the ray-log coin of :148 is never reached.  The RNG must already be keyed.
+template <bool COUNT>
+SRT_DEV Spec normal_sample(const DScene& S, uint32_t x, uint32_t y, Rng& rng, Counters& cnt) {
+  const float jx = rng.unit() * 1.0f;
+  const float jy = rng.unit() * 1.0f;
+  const Ray ray = camera_ray(S, ((float)x + jx) / (float)S.w, ((float)y + jy) / (float)S.h);
+  const Hit h = scene_hit<COUNT>(S, ray, cnt);
+  Spec first = spec(0, 0, 0);
+  if (!h.hit) { if (S.env_type != 0u) first = env_evaluate(S, ray.d); }
+  else first = spec_direction(surface_of(S, h, ray).normal);
+  return first + spec(0, 0, 0);      // `emissive + reflected` with reflected == {}
+}
+
 }  // namespace srt
 
 #endif

@@ -121,6 +121,7 @@ void RenderCore::begin(const float iview[16], float vert_fov_deg, float aspect_r
         samples_done = 0;
     }
     t_render0 = std::chrono::steady_clock::now();
+    check(srt_pt_group_set_normal_colors(group, normal_colors ? 1 : 0), "srt_pt_group_set_normal_colors");   // (no launch is being enqueued: cancel() joined the worker)
     for(srt_pt* m : members) check(srt_pt_set_camera(m, iview, vert_fov_deg, aspect_ratio), "srt_pt_set_camera");
     const size_t first = samples_done, first_epochs = accumulator_samples.load();
     samples_done += n_samples;

@@ -51,6 +51,9 @@ public:
     void set_samples(size_t samples) { n_samples = samples; }
     void set_seed(uint64_t s) { seed = s; }
     void set_threads(size_t n) { n_threads = n; }                  // the reference's hardware_concurrency(), which sets the epoch size
+    // debug_data.normal_colors (student/debug.h; student/pathtracer.cpp:199): the first-hit view.  Forwarded to the group by the next
+    // begin() (srt_pt_group_set_normal_colors) - the reference reads its global per trace call, a render here keeps what begin() saw.
+    void set_normal_colors(bool on) { normal_colors = on; }
 
     // begin_render minus the scene walk.  add_samples keeps the accumulator and continues the sample index.
     void begin(const float iview[16], float vert_fov_deg, float aspect_ratio, bool add_samples);
@@ -98,6 +101,7 @@ private:
     std::atomic<long long> build_ns{0}, render_ns{0};
     size_t out_w = 0, out_h = 0, n_samples = 0, max_depth = 0, n_threads = 0;
     uint64_t seed = 0;
+    bool normal_colors = false;
     int device0 = 0;
 };
 

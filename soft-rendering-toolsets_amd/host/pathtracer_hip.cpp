@@ -8,6 +8,7 @@
 #include "camera_iview.h"
 
 #include "../gui/render.h"
+#include "../student/debug.h"
 
 namespace PT {
 
@@ -217,6 +218,8 @@ void Pathtracer::begin_render(Scene& layout_scene, const Camera& cam, bool add_s
     // the matrix Camera::generate_ray itself uses (camera_iview.h): bit-identical camera rays, no header patch
     float iview[16];
     mat_to_array(srt_host::camera_iview(cam), iview);
+    // "Pathtracer: use normal colors" (student/debug.cpp:43): trace's early out at student/pathtracer.cpp:199, read once per render
+    core.set_normal_colors(debug_data.normal_colors);
     core.begin(iview, cam.get_fov(), cam.get_ar(), add_samples);
 }
 
