@@ -325,7 +325,146 @@ def pt_scene(name):
         s = scenes.cornell_box("cbox_lambertian")
         s["objects"] = s["objects"][:-1]   # no area light: sample_area_lights returns the zero vector -> NaN rays
         return s
+    if name in DEEP_CHAIN_TRIANGLES:
+        return deep_chain_scene(DEEP_CHAIN_TRIANGLES[name])
+    if name in DEEP_TLAS_SPHERES:
+        return deep_tlas_scene(*DEEP_TLAS_SPHERES[name])
     raise KeyError(name)
+
+
+# ------------------------------------------------------------------------------------------------
+# Skewed trees: scenes whose BVHs nest as deep as the traversal stacks allow (kMaxTlasDepth 24, kMaxBlasDepth 48)
+# ------------------------------------------------------------------------------------------------
+# BVH::build tries nine planes per axis at tenths of the node's extent and keeps the cheapest SAH split, so a tree gets deep only
+# when every split takes few primitives off a large rest WITHOUT shrinking the rest's box by much: 48 levels that each cut the
+# extent to a tenth would leave float32.  The chain: primitive i spans h_i * [-1, 2.2] along the chain axis with h_i = 0.4^i - the
+# centres 0.6 h_i are a geometric progression - and +-s_i = +-0.96^i across it.  The boxes nest around the origin.  In the node
+# that holds primitives j.. the planes lie at h_j * (-1 + 0.32 m): m = 1..3 are below every centre (an empty side costs n + 1),
+# m = 4 at 0.28 h_j has centre j (0.6 h_j) above it and every other centre (<= 0.24 h_j) below, m = 5 is centre j itself, m >= 6
+# are above all; the other two axes have every centre at 0.  So each level splits {j} off the rest at a cost of about
+# 0.96^2 (n - 1) + 2 < n + 1, every surface area is a finite positive number (the lateral extents carry it: 0.96^53 = 0.11), and
+# the interior nesting is n - max_leaf_size: n - 4 for triangles, n - 1 for objects.
+CHAIN_AXIAL, CHAIN_LATERAL = 0.4, 0.96
+DEEP_CHAIN_TRIANGLES = {"deep_mid": 20, "deep_max": 52, "deep_over": 53}       # max_blas_depth 16, 48 (= kMaxBlasDepth), 49
+DEEP_TLAS_SPHERES = {"deep_tlas": (21, "deep_mid"), "deep_tlas_over": (25, "deep_mid"),    # max_tlas_depth 22, 26 (kMaxTlasDepth = 24)
+                     "deep_both": (23, "deep_max", 4)}                                     # 24 and 48: both limits at once; 28 objects, which
+                                                                                           # the flattened walk still takes (<= 31)
+
+
+def chain_mesh(n, first=0):
+    """Triangles first .. first + n - 1 of the chain along z (indexed positions, triangles).  Seen along z they are copies of one
+    triangle around the origin, scaled by s_i; along z each one lies mostly in [-h_i, 0] with one corner at 2.2 h_i, so that a ray
+    coming down the axis from +z enters the boxes of the smaller triangles BEFORE it meets the larger ones (at about 0.28 h_i in the
+    middle): find_closest_hit's visit rule - far child iff its entry time < the nearer child's hit - then descends all the way."""
+    i = np.arange(first, first + n, dtype=np.float64)
+    h, s = CHAIN_AXIAL ** i, CHAIN_LATERAL ** i
+    v = np.stack([np.stack([-s, -s, -h], 1), np.stack([s, -0.3 * s, -0.8 * h], 1), np.stack([-0.2 * s, s, 2.2 * h], 1)], 1)
+    return v.reshape(-1, 3).astype(np.float32), np.arange(3 * n).reshape(n, 3)
+
+
+def _rows(m):
+    return np.ascontiguousarray(np.asarray(m, np.float32).reshape(4, 4).T.reshape(16))      # row-major text -> Mat4::data order
+
+
+DEEP_CHAIN_SCALE, DEEP_CHAIN_AT = 0.25, (0.0, 0.5, 0.0)
+
+
+def deep_chain_scene(n):
+    """The Cornell box with the n-triangle chain, a mirror, in place of the glass sphere (8 objects: every kernel form takes it), the
+    chain axis along the box's depth.  Two cameras on that axis.  "camera" sits AT the chain's origin - inside every box of the
+    mesh's tree - and looks out of the box along +z: every one of its rays finds both children of every node on the way down, the
+    closest triangle it meets is one of the SMALLEST (the leaf at the bottom of the tree), and what it then sees of the box
+    depends on that triangle's normal.  "camera_outside" stands in front of the box and looks down the axis: from there float32
+    entry times no longer tell the boxes below level ~17 apart, the visit rule's ties end those walks early."""
+    import srt_amd  # noqa: F401
+    from soft_rendering_toolsets_amd import scenes
+
+    s = scenes.cornell_box("cbox")
+    pos, tris = chain_mesh(n)
+    p, nr, ix = scenes.flat_mesh(pos, tris)
+    k, (tx, ty, tz) = DEEP_CHAIN_SCALE, DEEP_CHAIN_AT
+    s["objects"][6] = {"kind": "mesh", "pos": p, "nrm": nr, "idx": ix, "T": _rows([k, 0, 0, tx, 0, k, 0, ty, 0, 0, k, tz, 0, 0, 0, 1]),
+                       "material": 5, "is_light": False}
+    s["camera"] = {"iview": _rows([-1, 0, 0, tx, 0, 1, 0, ty, 0, 0, -1, tz, 0, 0, 0, 1]), "vfov": 70.0, "ar": 4.0 / 3.0}
+    s["camera_outside"] = {"iview": _rows([1, 0, 0, tx, 0, 1, 0, ty, 0, 0, 1, 1.05, 0, 0, 0, 1]), "vfov": 32.0, "ar": 4.0 / 3.0}
+    s["name"] = f"cbox+chain{n}"
+    s["chain_frame"] = [k, 0, 0, tx, 0, k, 0, ty, 0, 0, k, tz, 0, 0, 0, 1]
+    return s
+
+
+def deep_tlas_scene(k, chain="deep_mid", far=12):
+    """A BVH<Object> chain: k Lambertian spheres squeezed into discs by their transforms (box = h_i * [-1, 2.2] along z, +-s_i across),
+    the `chain` mesh scaled into the place of element k - the innermost one, so a walk that reaches it has the whole BVH<Object>
+    nesting on its stack and then adds the mesh's - and `far` Lambertian spheres in a row far off along y, which the root's
+    split takes away in one piece: k + 1 + far objects, nesting k + 1.  The camera sits AT the origin, inside
+    every box of both trees, so every camera ray finds both children of every node of the chain; the closest thing it meets is the
+    mesh, a mirror, and the reflected ray (bounds from 1e-5) ends on the inside of the first shell thicker than that.  A point light
+    at the origin lights it there - the shells closer to the light than the shadow ray's bounds do not block it - so the pixel's
+    value depends on which shell and which triangle the walks find.  (The uniform sphere light stays outside the shells.)"""
+    import srt_amd  # noqa: F401
+    from soft_rendering_toolsets_amd import scenes
+
+    mats = [scenes._mat(scenes.LAMBERTIAN, scenes.to_linear([0.8, 0.5, 0.3])), scenes._mat(scenes.MIRROR, [0.9, 0.9, 0.9]),
+            scenes._mat(scenes.LAMBERTIAN, scenes.to_linear([0.6, 0.7, 0.4])), scenes._mat(scenes.LAMBERTIAN, scenes.to_linear([0.3, 0.5, 0.9]))]
+    objs = []
+    for i in range(k):
+        h, s = CHAIN_AXIAL ** i, CHAIN_LATERAL ** i
+        objs.append({"kind": "sphere", "radius": 1.0, "T": _rows([s, 0, 0, 0, 0, s, 0, 0, 0, 0, 1.6 * h, 0.6 * h, 0, 0, 0, 1]), "material": 3 * (i % 2)})
+    pos, tris = chain_mesh(DEEP_CHAIN_TRIANGLES[chain])
+    p, nr, ix = scenes.flat_mesh(pos, tris)
+    h, s = CHAIN_AXIAL ** k, CHAIN_LATERAL ** k
+    objs.append({"kind": "mesh", "pos": p, "nrm": nr, "idx": ix, "T": _rows([s, 0, 0, 0, 0, s, 0, 0, 0, 0, h, 0, 0, 0, 0, 1]), "material": 1, "is_light": False})
+    for j in range(far):
+        objs.append({"kind": "sphere", "radius": 0.1, "T": _rows([1, 0, 0, 0.3 * j - 1.65, 0, 1, 0, 4.0, 0, 0, 1, 0, 0, 0, 0, 1]), "material": 2})
+    cam = {"iview": np.eye(4, dtype=np.float32).reshape(16), "vfov": 50.0, "ar": 4.0 / 3.0}
+    return {"name": f"tlas_chain{k}", "materials": mats, "objects": objs, "camera": cam, "chain_frame": np.eye(4).reshape(16),
+            "env": {"type": 1, "radiance": np.array([0.7, 0.8, 1.0], np.float32)},
+            "lights": [{"type": 1, "radiance": np.array([3.0, 3.0, 3.0], np.float32), "T": np.eye(4, dtype=np.float32).reshape(16)}]}
+
+
+def camera_rays(camera, w, h, jitters=((0.5, 0.5), (0.1, 0.2), (0.9, 0.3), (0.3, 0.9), (0.8, 0.8))):
+    """Camera::generate_ray (student/camera.cpp:7-34) for every pixel of a w x h image at fixed positions inside the pixel - the
+    renderer draws its positions from the sample's RNG, these stand in for them: (org, dirs, bounds) as scene.hit takes them."""
+    iv = np.asarray(camera["iview"], np.float32).reshape(4, 4).T.astype(np.float64)
+    sh = np.tan(np.radians(camera["vfov"]) / 2.0) * 2.0
+    sw = camera["ar"] * sh
+    xs, ys = np.meshgrid(np.arange(w), np.arange(h))
+    d = []
+    for jx, jy in jitters:
+        sx, sy = (xs.reshape(-1) + jx) / w, (ys.reshape(-1) + jy) / h
+        d.append(np.stack([sx * sw - 0.5 * sw, sy * sh - 0.5 * sh, -np.ones(w * h)], 1))
+    d = np.concatenate(d) @ iv[:3, :3].T
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    org = np.tile(iv[:3, 3], (len(d), 1))
+    b = np.zeros((len(d), 2), np.float32)
+    b[:, 1] = np.inf
+    return org.astype(np.float32), d.astype(np.float32), b
+
+
+def chain_rays(seed, n, scene):
+    """Rays aimed down the chain of a deep_* scene: from the camera's side, from behind, from inside the nest (the chain's origin:
+    every box contains it) and from points on the axis, towards points spread over the chain's cross-section on a log scale, so
+    that the small triangles get their share; a tenth exactly axial (zero components: 1 / dir = +-inf in BBox::hit), a third with
+    bounds that cut the walk short."""
+    rng = np.random.default_rng(seed)
+    T = np.asarray(scene["chain_frame"], np.float64).reshape(4, 4)      # chain coordinates -> world (row-major)
+    lat = np.exp(rng.uniform(np.log(1e-3), np.log(1.3), n)) * rng.choice([-1.0, 1.0], n)
+    target = np.stack([lat, np.exp(rng.uniform(np.log(1e-3), np.log(1.3), n)) * rng.choice([-1.0, 1.0], n),
+                       np.exp(rng.uniform(np.log(1e-12), np.log(2.0), n)) * rng.choice([-0.4, 1.0], n)], 1)
+    z0 = np.select([np.arange(n) % 4 == 0, np.arange(n) % 4 == 1, np.arange(n) % 4 == 2], [4.0, -3.0, 0.0],
+                   np.exp(rng.uniform(np.log(1e-9), np.log(2.0), n)))
+    org = np.stack([rng.normal(size=n) * 0.05 * (z0 != 0), rng.normal(size=n) * 0.05 * (z0 != 0), z0], 1)
+    k = n // 10
+    target[:k, :2] = org[:k, :2]                                       # axial
+    target[:k, 2] = np.where(org[:k, 2] == 0.0, rng.choice([-1.0, 1.0], k), 0.0)
+    to_world = lambda p: p @ T[:3, :3].T + T[:3, 3]
+    o, t = to_world(org), to_world(target)
+    d = t - o
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    b = np.zeros((n, 2), np.float32)
+    b[:, 0] = np.where(rng.random(n) < 0.5, 0.0, 1e-5)
+    b[:, 1] = np.where(rng.random(n) < 0.3, rng.random(n) * 1.5, np.finfo(np.float32).max)
+    return o.astype(np.float32), d.astype(np.float32), b
 
 
 def scene_digest(scene):

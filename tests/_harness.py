@@ -566,6 +566,16 @@ class EmuPT(_SceneFeeder):
         assert self.lib.emu_hit3(self.h_, P(org), P(dirs3), P(bounds), ctypes.c_size_t(len(org)), P(out)) == 0
         return out
 
+    def hit_depth(self, org, dirs, bounds):
+        """The flattened walk over a stack that counts: (deepest frame index each ray touched, -1 for none; its result as `hit`
+        reports it; (max_tlas_depth, max_blas_depth) of the host build)."""
+        org, dirs, bounds = _f32(org), _f32(dirs), _f32(bounds)
+        deepest = np.zeros(len(org), np.int32)
+        flat = np.zeros((len(org), 4), np.uint32)
+        tree = np.zeros(2, np.uint32)
+        assert self.lib.emu_hit_depth(self.h_, P(org), P(dirs), P(bounds), ctypes.c_size_t(len(org)), P(deepest), P(flat), P(tree)) == 0
+        return deepest, flat, (int(tree[0]), int(tree[1]))
+
     def close(self):
         self.lib.emu_destroy(self.h_)
 

@@ -15,6 +15,38 @@ struct Emu {
   DScene S;
 };
 
+// A stack that records the deepest frame index a walk touches.  Its array is larger than any tree the product accepts needs, so
+// a walk that outgrows the real stacks (kFlatStack frames per lane; depth - lds_frames spilled frames in the streamed ray-cast
+// kernel) shows up here as a number instead of a write past the end.
+constexpr int kCountingFrames = 256;
+struct CountingStack {
+  FlatFrame* p;
+  int* deepest;
+  FlatFrame load(int i) const { touch(i); return p[i]; }
+  void store(int i, const FlatFrame& f) const { touch(i); p[i] = f; }
+  void touch(int i) const {
+    if (i < 0 || i >= kCountingFrames) __builtin_trap();
+    if (i > *deepest) *deepest = i;
+  }
+};
+
+// flat_run (pt_flat.h) for one lane - the same steps in the same order - over any stack type.
+template <typename StackT>
+static void run_lane(FlatState& F, const StackT& stack, const DScene& S, V3 org, V3 d, float cb0, float cb1) {
+  while (F.mode != FM_DONE) {
+    while (F.mode == FM_NODE && F.cur >= 0) {
+      flat_interior(F, stack, S);
+      while (F.mode == FM_UNWIND && flat_plain_frame(F)) flat_pop(F, stack);
+    }
+    if (F.mode == FM_NODE && F.cur < 0) flat_leaf(F, S);
+    if (F.mode == FM_OBJECT) flat_object(F, S);
+    while (F.mode == FM_UNWIND) {
+      if (flat_plain_frame(F)) flat_pop(F, stack);
+      else flat_exit(F, S, org, d, d, d, cb0, cb1);
+    }
+  }
+}
+
 extern "C" {
 
 void* emu_create() { return new Emu(); }
@@ -75,6 +107,27 @@ int emu_hit(void* h, const float* org, const float* dir, const float* bounds, si
     flat_trace3(e->S, r.o, slot == 0 ? r.d : z, slot == 1 ? r.d : z, slot == 2 ? r.d : z, r.b0, r.b1, slot == 0, slot == 1,
                 slot == 2, res[0], res[1], res[2]);
     const Hit b = res[slot];
+    flat[4 * i] = b.hit; flat[4 * i + 1] = __float_as_uint(b.dist); flat[4 * i + 2] = b.obj; flat[4 * i + 3] = b.tri;
+  }
+  return 0;
+}
+
+// The flattened walk of every ray over the counting stack: deepest[i] = the largest frame index ray i touched (-1: none), flat =
+// its result as emu_hit reports it.  tree_depth = {max_tlas_depth, max_blas_depth} of the committed scene as the host builder
+// computed them (what srt_pt_scene_commit checks and render_epoch_stream sizes the ray-cast kernel's stack from).
+int emu_hit_depth(void* h, const float* org, const float* dir, const float* bounds, size_t n, int32_t* deepest, uint32_t* flat,
+                  uint32_t tree_depth[2]) {
+  Emu* e = (Emu*)h;
+  tree_depth[0] = e->built.flat.max_tlas_depth; tree_depth[1] = e->built.flat.max_blas_depth;
+  std::vector<FlatFrame> frames(kCountingFrames);
+  for (size_t i = 0; i < n; i++) {
+    const V3 o = v3p(org + 3 * i), d = v3p(dir + 3 * i);
+    deepest[i] = -1;
+    const CountingStack stack{frames.data(), deepest + i};
+    FlatState F;
+    flat_begin(F, e->S, o, d, d, d, bounds[2 * i], bounds[2 * i + 1], true, false, false);
+    run_lane(F, stack, e->S, o, d, bounds[2 * i], bounds[2 * i + 1]);
+    const Hit b = F.res0;
     flat[4 * i] = b.hit; flat[4 * i + 1] = __float_as_uint(b.dist); flat[4 * i + 2] = b.obj; flat[4 * i + 3] = b.tri;
   }
   return 0;

@@ -5,17 +5,27 @@ import numpy as np
 import pytest
 
 import _harness as H
-from _cases import pt_scene, random_rays
+from _cases import chain_rays, pt_scene, random_rays
 
 
 @pytest.mark.parametrize("name,use_bvh", [
     ("cbox", True), ("cbox", False), ("cbox_lambertian", True), ("cbox_blob512_glass", True), ("cbox_blob512_glass", False),
     ("cbox_blob2048_mirror", True), ("cbox_nolight", True),
+    # trees as deep as the stacks allow (tests/_cases.py): BVH<Triangle> nesting 16 and 48, BVH<Object> nesting 22 and 24
+    ("deep_mid", True), ("deep_max", True), ("deep_tlas", True), ("deep_both", True),
 ])
 def test_flat_walk_equals_nested_and_oracle(name, use_bvh):
     scene = pt_scene(name)
     emu = H.EmuPT(scene, use_bvh)
-    org, dirs, bounds = random_rays(11, 3000)
+    ray_sets = [random_rays(11, 3000)]
+    if name.startswith("deep_"):
+        ray_sets.append(chain_rays(7, 3000, scene))          # aimed down the chain: these walks fill the stacks
+    for org, dirs, bounds in ray_sets:
+        _check_walks(scene, emu, use_bvh, org, dirs, bounds)
+    emu.close()
+
+
+def _check_walks(scene, emu, use_bvh, org, dirs, bounds):
     o = H.OraclePT(scene, 8, 8, 8, use_bvh).hit(org, dirs, bounds)          # {hit, dist, pos, normal, material}
     for slot in range(3):
         nested, flat = emu.hit(org, dirs, bounds, slot)
@@ -29,4 +39,3 @@ def test_flat_walk_equals_nested_and_oracle(name, use_bvh):
     for s in range(3):
         want, _ = emu.hit(org[:n], np.ascontiguousarray(d3[:, 3 * s:3 * s + 3]), bounds[:n], 0)
         assert np.array_equal(got[:, s], want)
-    emu.close()

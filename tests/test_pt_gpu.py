@@ -774,7 +774,8 @@ def test_epochs_on_two_streams_overlap_safely(srt):
 
 
 @pytest.mark.parametrize("scene_name,min_prims", [("cbox_blob512_glass", 1), ("cbox_blob2048_mirror", 1), ("cbox_beast_glass", 16384),
-                                                  ("cbox_blob131072_glass", 16384)])
+                                                  ("cbox_blob131072_glass", 16384),
+                                                  ("deep_max", 1)])      # a skewed tree: one level per triangle, 48 = kMaxBlasDepth deep
 def test_device_bvh_build_equals_host_build(srt, scene_name, min_prims):
     """BVH::build on the GPU (csrc/pt_bvh_device.hip): node boxes, links and primitive order of every tree - the BVH<Object> too
     when min_prims = 1 - equal the host build's bit for bit (the host build equals the reference's: tests/test_pt_host.py and
@@ -804,6 +805,20 @@ def test_device_bvh_build_equals_host_build(srt, scene_name, min_prims):
         assert bits_equal(bh, bd) and np.array_equal(lh, ld) and np.array_equal(oh, od)
     org, d, b = random_rays(91, 1024)
     assert bits_equal(pt_h.hit(org, d, b), pt_d.hit(org, d, b))
+    if scene_name.startswith("deep_"):
+        # a generated scene without a reference-built fixture: the oracle's build stands in for it (tests/test_pt_stack_depth_host.py)
+        o = H.OraclePT(scene, 8, 8, 4, True)
+        checked = 0
+        for k in range(-1, len(scene["objects"])):
+            want = o.dump_bvh(k)
+            if want is not None:
+                bd, ld, od = pt_d.dump_bvh(k)
+                n = len(scene["objects"]) if k < 0 else len(want[0])
+                assert bits_equal(bd, want[0]) and np.array_equal(ld, want[1]) and np.array_equal(od[:n], want[2][:n])
+                checked += int(k >= 0 and len(want[0]) > 90)
+        assert checked == 1, "the chain's BVH<Triangle> was not compared"
+        pt_h.close(); pt_d.close()
+        return
     # ... and, directly, the REFERENCE build's node arrays of the same scene (the goldens of tests/golden/make_pt_golden.py)
     gpath = glob.glob(os.path.join(H.GOLDEN, f"pt_{scene_name}_*_bvh.npz"))
     assert gpath, scene_name
