@@ -161,6 +161,16 @@ int srt_pt_add_mesh(srt_pt* pt, const float* positions, const float* normals, ui
                     int is_area_light);
 /* Object(Shape(Sphere(radius)), id, material, T). */
 int srt_pt_add_sphere(srt_pt* pt, float radius, const float trans[16], uint32_t material);
+/* Object(<the Tri_Mesh of object `source_object`>.copy(), id, material, T) without the copy.  The reference's author names it at
+ * rays/pathtracer.cpp:76-77 ("We could also do instancing instead of duplicating the bvh for big meshes"); where it matters is
+ * :134-155, one Object per particle of a Scene_Particles, each with a byte copy of ONE built BVH<Triangle>.  source_object is the
+ * 0-based insertion index of an object added earlier in this scene by srt_pt_add_mesh (an area light is fine: its light-list copy
+ * stays what it is); a sphere, a sphere light, another instance, an index not yet added, a NULL trans or a material of kind
+ * DIFFUSE_LIGHT (every emissive object goes into the area-light list with triangles of its own, :105-116) are SRT_ERR_INVALID
+ * and leave the scene under construction usable.  The instance takes an insertion index and id like any object; its triangles,
+ * normals and BVH<Triangle> are the source's - built, stored and uploaded once - and everything the scene computes is bit for
+ * bit what srt_pt_add_mesh of the source's arrays would have given.  srt_pt_dump_bvh on it returns the shared arrays. */
+int srt_pt_add_instance(srt_pt* pt, uint32_t source_object, const float trans[16], uint32_t material);
 /* An emissive analytic sphere (a Scene_Object with a Shape and a diffuse_light material): rays intersect the sphere
  * (Sphere::hit), while the area-light list gets its triangle approximation obj.posed_mesh() as a Tri_Mesh without BVH
  * (rays/pathtracer.cpp:105-116).  positions / normals / indices = that mesh. */
@@ -192,6 +202,17 @@ int srt_pt_set_env_map(srt_pt* pt, uint32_t width, uint32_t height, const float*
 /* Builds every BVH<Triangle> (leaf size 4) and the BVH<Object> (leaf size 1) exactly as the reference
  * does — or the List<> forms when use_bvh == 0 — flattens them and uploads the scene. */
 int srt_pt_scene_commit(srt_pt* pt, int use_bvh);
+/* New transforms for n objects of the committed scene (insertion indices; meshes, instances and spheres; trans: 16 floats per
+ * object) without a rebuild: what a renderer of animations gets from the reference only by running build_scene again
+ * (rays/pathtracer.cpp:66-176, per frame).  Runs with nothing of the context in flight and waits for the device itself.  The
+ * listed Objects' itrans / has_trans / bbox are recomputed, the BVH<Object> is rebuilt (list order is kept when the scene was
+ * committed with use_bvh == 0) and the tables that follow object order are uploaded again; no BVH<Triangle> is rebuilt and no
+ * triangle, normal or BVH<Triangle> record is uploaded.  Afterwards the scene equals, bit for bit in everything it computes, a
+ * fresh srt_pt_scene_begin .. srt_pt_scene_commit of the same objects with the new transforms.  SRT_ERR_INVALID: an area light
+ * in the list (its light tables depend on its pose: commit again), a duplicate, an index out of range.  SRT_ERR_STATE: no
+ * committed scene.  New poses that make the reference's BVH<Object> build non-terminating or too deep for the traversal stacks
+ * fail as srt_pt_scene_commit does (SRT_ERR_UNSUPPORTED) - and the committed scene stays exactly as it was. */
+int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n);
 /* Where srt_pt_scene_commit runs BVH<Primitive>::build (student/bvh.inl:35-163): device != 0 (default) builds primitive sets of at
  * least min_primitives (default 16384) on the GPU, smaller ones and device == 0 on the host.  Both produce the reference's node
  * arrays and primitive order bit for bit (the candidate planes' std::partition sequence included); SRT_BVH_BUILDER=host in the

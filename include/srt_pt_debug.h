@@ -57,6 +57,12 @@ int srt_pt_kernel_form(srt_pt* pt, int* form);
 /* Traversal counters of the LAST srt_pt_trace_samples call (an instrumented launch):
  * {rays, box_tests, objects_entered, tri_tests, sphere_tests, tlas_nodes, blas_nodes, light_tri_tests}. */
 int srt_pt_counters(srt_pt* pt, uint64_t out[8]);
+/* What the scene holds and what it cost: {objects, triangle records stored, BVH<Triangle> nodes stored, BVH<Triangle> interior
+ * records stored, BVH<Triangle> builds performed by this context since creation, scene bytes resident on the device, scene bytes
+ * uploaded since creation, of those the triangle / normal / packed-triangle / BVH<Triangle>-record bytes}.  Lets a test state
+ * that srt_pt_add_instance shared and srt_pt_repose left the triangles alone.  Works on a host-only context (device = -1): the
+ * two byte figures of the device are then 0 and nothing is ever uploaded.  The first four are 0 before the first commit. */
+int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]);
 /* cosf/sinf of the kernel (SRT-MATH v2) for n host floats; parity tests compare them with glibc. */
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);
 /* The kernels' atan2f (glibc 2.35's algorithm restated; Spot_Light::sample) evaluated on the device. */

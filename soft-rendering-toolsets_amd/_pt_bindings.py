@@ -26,6 +26,8 @@ class SrtCancelled(Exception):
 
 _HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
+SCENE_COUNT_NAMES = ("objects", "triangles", "blas_nodes", "blas_records", "blas_builds", "device_bytes", "uploaded_bytes",
+                     "uploaded_triangle_bytes")
 COUNTER_NAMES = ("rays", "box_tests", "objects_entered", "tri_tests", "sphere_tests", "tlas_nodes", "blas_nodes",
                  "light_tri_tests")
 
@@ -51,7 +53,10 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_add_sphere_light.argtypes = [c_void_p, c_float, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32]
     lib.srt_pt_add_light.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]
     lib.srt_pt_add_sphere.argtypes = [c_void_p, c_float, c_void_p, c_uint32]
+    lib.srt_pt_add_instance.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32]
     lib.srt_pt_scene_commit.argtypes = [c_void_p, c_int]
+    lib.srt_pt_repose.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_scene_counts.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_set_bvh_builder.argtypes = [c_void_p, c_int, c_uint32]
     lib.srt_pt_set_stream_slots.argtypes = [c_void_p, c_uint32]
     lib.srt_pt_set_camera.argtypes = [c_void_p, c_void_p, c_float, c_float]
@@ -205,6 +210,8 @@ class Pathtracer:
                 idx = np.ascontiguousarray(o["idx"], np.uint32)
                 self._check(L, L.srt_pt_add_mesh(self._ctx, _p(pos), _p(nrm), len(pos), _p(idx), len(idx), _p(T),
                                                  int(o["material"]), int(bool(o["is_light"]))))
+            elif o["kind"] == "instance":      # {"kind": "instance", "of": insertion index of a mesh, "T", "material"} (scenes.share_meshes)
+                self._check(L, L.srt_pt_add_instance(self._ctx, int(o["of"]), _p(T), int(o["material"])))
             elif o.get("light_mesh") is not None:   # emissive sphere
                 lm = o["light_mesh"]
                 pos, nrm, idx = _f32(lm["pos"]), _f32(lm["nrm"]), np.ascontiguousarray(lm["idx"], np.uint32)
@@ -223,6 +230,21 @@ class Pathtracer:
             rad, ab, T = _f32(l["radiance"]), _f32(l.get("angle_bounds", (0.0, 0.0))), _f32(l["T"])
             self._check(L, L.srt_pt_add_light(self._ctx, int(l["type"]), _p(rad), _p(ab), _p(T)))
         self._check(L, L.srt_pt_scene_commit(self._ctx, int(self.scene_use_bvh)))
+
+    def repose(self, indices, Ts) -> None:
+        """srt_pt_repose: new transforms (16 floats each, column-major) for the objects with these insertion indices of the
+        committed scene - no BVH<Triangle> is rebuilt, no triangle uploaded."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        T = _f32(Ts).reshape(-1, 16)
+        if len(T) != len(idx):
+            raise ValueError(f"{len(idx)} objects but {len(T)} transforms")
+        self._check(self._lib, self._lib.srt_pt_repose(self._ctx, _p(idx), _p(T), len(idx)))
+
+    def scene_counts(self) -> dict:
+        """srt_pt_scene_counts: what the scene stores, the BVH<Triangle> builds so far and the bytes uploaded (SCENE_COUNT_NAMES)."""
+        out = np.zeros(8, np.uint64)
+        self._check(self._lib, self._lib.srt_pt_scene_counts(self._ctx, _p(out)))
+        return dict(zip(SCENE_COUNT_NAMES, (int(v) for v in out)))
 
     def set_camera(self, camera: dict) -> None:
         iv = _f32(camera["iview"])
@@ -552,6 +574,14 @@ class PathtracerGroup:
     def build_scene(self, scene) -> None:
         for m in self.members:
             m.build_scene(scene)
+
+    def repose(self, indices, Ts) -> None:
+        for m in self.members:
+            m.repose(indices, Ts)
+
+    def scene_counts(self) -> list:
+        """Every member's Pathtracer.scene_counts(), by rank (the scene is replicated)."""
+        return [m.scene_counts() for m in self.members]
 
     def set_camera(self, camera) -> None:
         for m in self.members:

@@ -438,16 +438,22 @@ struct srt_pt {
   bool stream_timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> stream_timed[4];   // {logic (resolve), compaction, ray cast, probe}
   uint64_t stream_generations = 0;
+  // srt_pt_scene_counts: since creation
+  uint64_t blas_builds = 0, bytes_uploaded = 0, tri_bytes_uploaded = 0;
 };
 
 namespace {
 
+// The one exit of scene data to the device.  tri_class: triangle, normal, packed-triangle or BLAS-record bytes - what an
+// instance shares and srt_pt_repose leaves alone (srt_pt_scene_counts tells them apart).
 template <typename T>
-int upload(T** dst, const std::vector<T>& src) {
+int upload(srt_pt* pt, T** dst, const std::vector<T>& src, bool tri_class = false) {
   if (*dst) { SRT_HIP(hipFree(*dst)); *dst = nullptr; }
   const size_t n = src.empty() ? 1 : src.size();
   SRT_HIP(hipMalloc(dst, n * sizeof(T)));
   if (!src.empty()) SRT_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += src.size() * sizeof(T);
+  if (tri_class) pt->tri_bytes_uploaded += src.size() * sizeof(T);
   return SRT_OK;
 }
 
@@ -1157,6 +1163,26 @@ int srt_pt_add_mesh(srt_pt* pt, const float* positions, const float* normals, ui
   return SRT_OK;
 }
 
+int srt_pt_add_instance(srt_pt* pt, uint32_t source_object, const float trans[16], uint32_t material) {
+  if (!pt || !trans) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: NULL argument");
+  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
+  if (source_object >= pt->inputs.size()) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: object %u is not added yet (%zu objects so far)", source_object, pt->inputs.size());
+  const ObjectInput& src = pt->inputs[source_object];
+  if (src.kind != OBJ_MESH || src.source >= 0)
+    return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: object %u is %s, not a mesh added by srt_pt_add_mesh", source_object,
+                     src.kind != OBJ_MESH ? "a sphere" : "an instance");
+  if (material >= pt->materials.size()) return srt::fail(SRT_ERR_INVALID, "material %u not defined", material);
+  if (pt->materials[material].type == SRT_MAT_DIFFUSE_LIGHT)
+    return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: an emissive object needs triangles of its own in the area-light list; add it with srt_pt_add_mesh");
+  ObjectInput o;
+  o.kind = OBJ_MESH;
+  std::memcpy(&o.trans, trans, sizeof(Mat4));
+  o.material = material;
+  o.source = (int32_t)source_object;
+  pt->inputs.push_back(std::move(o));
+  return SRT_OK;
+}
+
 int srt_pt_add_sphere(srt_pt* pt, float radius, const float trans[16], uint32_t material) {
   if (!pt || !trans) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_sphere: NULL argument");
   if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
@@ -1229,6 +1255,7 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   else set_device_bvh_builder(nullptr, 0);
   const std::string err = build_scene(pt->inputs, pt->materials, use_bvh != 0, &pt->built);
   set_device_bvh_builder(nullptr, 0);
+  pt->blas_builds += pt->built.blas_builds;
   if (!err.empty()) return srt::fail(SRT_ERR_UNSUPPORTED, "%s", err.c_str());
   pt->built.flat.delta_lights = pt->delta_lights;
   const FlatScene& F = pt->built.flat;
@@ -1239,16 +1266,78 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
     SRT_HIP(hipSetDevice(pt->device));
     SRT_HIP(hipStreamSynchronize(pt->stream));
     int st;
-    if ((st = upload(&pt->d_nodes, F.nodes)) || (st = upload(&pt->d_tris, F.tris)) || (st = upload(&pt->d_nrm, F.tri_nrm)) ||
-        (st = upload(&pt->d_tri_packed, F.tri_packed)) ||
-        (st = upload(&pt->d_objects, F.objects)) || (st = upload(&pt->d_lights, F.lights)) ||
-        (st = upload(&pt->d_ltris, F.light_tris)) || (st = upload(&pt->d_mats, F.materials)) ||
-        (st = upload(&pt->d_wave, F.wave_tlas)) || (st = upload(&pt->d_blas, F.blas_recs)) || (st = upload(&pt->d_wave_lazy, F.wave_lazy)) ||
-        (st = upload(&pt->d_dlights, F.delta_lights)) || (st = upload(&pt->d_env_map, pt->env_map)))
+    if ((st = upload(pt, &pt->d_nodes, F.nodes)) || (st = upload(pt, &pt->d_tris, F.tris, true)) || (st = upload(pt, &pt->d_nrm, F.tri_nrm, true)) ||
+        (st = upload(pt, &pt->d_tri_packed, F.tri_packed, true)) ||
+        (st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_lights, F.lights)) ||
+        (st = upload(pt, &pt->d_ltris, F.light_tris)) || (st = upload(pt, &pt->d_mats, F.materials)) ||
+        (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_blas, F.blas_recs, true)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)) ||
+        (st = upload(pt, &pt->d_dlights, F.delta_lights)) || (st = upload(pt, &pt->d_env_map, pt->env_map)))
       return st;
   }
   pt->committed = true;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  return SRT_OK;
+}
+
+int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
+  if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose: NULL argument");
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_repose before srt_pt_scene_commit");
+  const char* be = getenv("SRT_BVH_BUILDER");               // the BVH<Object> build goes where srt_pt_scene_commit's does
+  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
+  if (pt->device >= 0 && bmode != 0) { SRT_HIP(hipSetDevice(pt->device)); set_device_bvh_builder(build_bvh_device, pt->bvh_device_min); }
+  else set_device_bvh_builder(nullptr, 0);
+  ReposedTop top;
+  bool bad_argument = false;
+  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
+  std::vector<Mat4> T(n);
+  if (n) std::memcpy(T.data(), trans, (size_t)n * sizeof(Mat4));
+  const std::string err = prepare_repose(pt->built, objects, T.data(), n, &top, &bad_argument);
+  set_device_bvh_builder(nullptr, 0);
+  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "srt_pt_repose: %s", err.c_str());
+  if ((int)top.max_tlas_depth > kMaxTlasDepth)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)",
+                     top.max_tlas_depth, kMaxTlasDepth, pt->built.flat.max_blas_depth, kMaxBlasDepth);
+  // from here on nothing fails on the host side: the new tables replace the old ones
+  const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
+  if (pt->device >= 0) {
+    SRT_HIP(hipSetDevice(pt->device));
+    SRT_HIP(hipStreamSynchronize(pt->stream));
+    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old tables
+  }
+  apply_repose(&pt->built, &top);
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  if (pt->device >= 0) {
+    const FlatScene& F = pt->built.flat;
+    int st;
+    if (F.tlas_nodes == old_tlas_nodes) {                 // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
+      if (F.tlas_nodes) SRT_HIP(hipMemcpy(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice));
+      pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
+    } else if ((st = upload(pt, &pt->d_nodes, F.nodes))) {
+      return st;
+    }
+    if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
+      return st;
+  }
+  return SRT_OK;
+}
+
+int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]) {
+  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_counts: NULL argument");
+  const FlatScene& F = pt->built.flat;
+  const bool have = pt->committed;
+  out[0] = have ? F.objects.size() : 0;
+  out[1] = have ? F.tris.size() : 0;
+  out[2] = have ? F.nodes.size() - F.tlas_nodes : 0;
+  out[3] = have ? F.blas_recs.size() : 0;
+  out[4] = pt->blas_builds;
+  out[5] = 0;
+  if (have && pt->device >= 0)
+    out[5] = F.nodes.size() * sizeof(Node) + F.tris.size() * sizeof(Tri) + F.tri_nrm.size() * sizeof(TriNrm) + F.tri_packed.size() * sizeof(float) +
+             F.objects.size() * sizeof(Object) + F.lights.size() * sizeof(Light) + F.light_tris.size() * sizeof(LightTri) +
+             F.materials.size() * sizeof(Material) + F.wave_tlas.size() * sizeof(WaveInterior) + F.blas_recs.size() * sizeof(WaveInterior) +
+             F.wave_lazy.size() * sizeof(uint32_t) + F.delta_lights.size() * sizeof(DeltaLight) + pt->env_map.size() * sizeof(float);
+  out[6] = pt->bytes_uploaded;
+  out[7] = pt->tri_bytes_uploaded;
   return SRT_OK;
 }
 
@@ -1701,9 +1790,10 @@ long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_
   const ObjectInput* in = nullptr;
   if (which >= 0) {
     if ((size_t)which >= pt->built.tlas.prim.size()) return srt::fail(SRT_ERR_INVALID, "object slot %d out of range", which);
-    const uint32_t obj = pt->built.tlas.prim[which];
+    uint32_t obj = pt->built.tlas.prim[which];
     in = &pt->built.inputs[obj];
     if (in->kind != OBJ_MESH) return srt::fail(SRT_ERR_INVALID, "object slot %d is not a mesh", which);
+    if (in->source >= 0) { obj = (uint32_t)in->source; in = &pt->built.inputs[obj]; }   // an instance: the shared arrays
     b = &pt->built.blas[obj];
   }
   for (size_t i = 0; i < b->nodes.size() && i < cap; i++) {

@@ -155,13 +155,123 @@ void mat_point(const Mat4& m, const float v[3], float out[3]) {
   out[0] = o[0] / o[3]; out[1] = o[1] / o[3]; out[2] = o[2] / o[3];
 }
 
-void append_nodes(const HostBVH& b, FlatScene* f) {
+void append_nodes(const HostBVH& b, std::vector<Node>* out) {
   for (const HostNode& h : b.nodes) {
     Node n;
     for (int i = 0; i < 3; i++) { n.mn[i] = h.mn[i]; n.mx[i] = h.mx[i]; }
     if (h.l == h.r) { n.left = h.start; n.count = LEAF_BIT | h.size; }
     else { n.left = h.l; n.count = 0; }
-    f->nodes.push_back(n);
+    out->push_back(n);
+  }
+}
+
+// One record per interior node of `b`, in node order (parents first): both child boxes and the child references.  A leaf
+// child's reference is ~leaf_code(leaf).
+template <class LeafCode>
+void append_records(const HostBVH& b, LeafCode leaf_code, std::vector<WaveInterior>* out) {
+  const std::vector<HostNode>& N = b.nodes;
+  std::vector<int32_t> rank(N.size(), -1);
+  int32_t q = 0;
+  for (size_t n = 0; n < N.size(); n++)
+    if (N[n].l != N[n].r) rank[n] = q++;
+  for (size_t n = 0; n < N.size(); n++) {
+    if (N[n].l == N[n].r) continue;
+    WaveInterior wi;
+    const HostNode& a = N[N[n].l];
+    const HostNode& c = N[N[n].r];
+    for (int i = 0; i < 3; i++) { wi.boxl[i] = a.mn[i]; wi.boxl[3 + i] = a.mx[i]; wi.boxr[i] = c.mn[i]; wi.boxr[3 + i] = c.mx[i]; }
+    wi.l_ref = (a.l != a.r) ? rank[N[n].l] : ~(int32_t)leaf_code(a);
+    wi.r_ref = (c.l != c.r) ? rank[N[n].r] : ~(int32_t)leaf_code(c);
+    wi.l_cnt = a.size;
+    wi.r_cnt = c.size;
+    out->push_back(wi);
+  }
+}
+
+// The pose-dependent half of build_scene, shared with prepare_repose: Object ctor values and Object::bbox per object, the
+// BVH<Object> (leaf size 1) or List<Object> over them, its flattened nodes and its sweep records.
+struct Top {
+  std::vector<Mat4> itrans;
+  std::vector<bool> has_trans;
+  HostBVH tlas;
+  std::vector<Node> nodes;
+  std::vector<WaveInterior> wave;
+  uint32_t depth = 0;
+};
+bool build_top(const std::vector<Mat4>& trans, const std::vector<float>& local_boxes, bool use_bvh, Top* T) {
+  const uint32_t nobj = (uint32_t)trans.size();
+  T->itrans.resize(nobj);
+  T->has_trans.resize(nobj);
+  std::vector<Box> obj_boxes(nobj);
+  for (uint32_t i = 0; i < nobj; i++) {
+    T->itrans[i] = mat_inverse(trans[i]);            // Object ctor, rays/object.h:18-21
+    T->has_trans[i] = mat_ne_identity(trans[i]);
+    Box ob;
+    for (int a = 0; a < 3; a++) { ob.mn[a] = local_boxes[6 * i + a]; ob.mx[a] = local_boxes[6 * i + 3 + a]; }
+    if (T->has_trans[i]) ob.transform(trans[i]);     // Object::bbox, rays/object.h:51-55
+    obj_boxes[i] = ob;
+  }
+  if (use_bvh) {
+    if (!build_bvh(obj_boxes, 1, &T->tlas)) return false;
+    append_nodes(T->tlas, &T->nodes);
+    T->depth = interior_depth(T->tlas);
+    // interior-node sweep order for the wave-uniform kernel: a leaf child is ~first object slot
+    append_records(T->tlas, [](const HostNode& leaf) { return leaf.start; }, &T->wave);
+  } else {
+    T->tlas.nodes.clear();
+    T->tlas.prim.resize(nobj);
+    for (uint32_t i = 0; i < nobj; i++) T->tlas.prim[i] = i;
+  }
+  return true;
+}
+
+// The object records in BVH<Object> primitive order (insertion order in list mode): an instance's record carries its
+// source's ranges and its own transform pair and material.
+void make_objects(const std::vector<ObjectInput>& inputs, const std::vector<Mat4>& trans, const Top& T, const std::vector<MeshStore>& store,
+                  uint32_t tlas_nodes, bool use_bvh, std::vector<Object>* objects, std::vector<uint32_t>* lazy_objects) {
+  objects->clear();
+  lazy_objects->clear();
+  for (uint32_t slot = 0; slot < (uint32_t)inputs.size(); slot++) {
+    const uint32_t i = T.tlas.prim[slot];
+    const ObjectInput& in = inputs[i];
+    Object o;
+    std::memset(&o, 0, sizeof o);
+    o.kind = in.kind;
+    o.has_trans = T.has_trans[i] ? 1u : 0u;
+    o.material = (int32_t)in.material;
+    o.use_bvh = (in.kind == OBJ_MESH && use_bvh) ? 1u : 0u;
+    o.radius = in.radius;
+    o.id = i + 1;
+    o.trans = trans[i];
+    o.itrans = T.itrans[i];
+    if (in.kind == OBJ_MESH) {
+      const MeshStore& m = store[i];
+      o.tri_base = m.tri_base; o.ntri = m.ntri;
+      if (use_bvh) { o.node_base = tlas_nodes + m.node_off; o.nnodes = m.nnodes; o.rec_base = m.rec_base; o.nrec = m.nrec; }
+    }
+    if (o.kind == OBJ_MESH && o.use_bvh != 0u && o.nrec > 0u) {
+      // a mesh with a real BVH<Triangle>: its ordinal among those (the streamed sweeps queue its walks per ordinal)
+      o.use_bvh |= (uint32_t)lazy_objects->size() << 8;
+      lazy_objects->push_back(slot);
+    }
+    objects->push_back(o);
+  }
+}
+
+// Which children of the top-level records hold a mesh with a real BVH<Triangle> somewhere below (children come after
+// their parent in sweep order, so one backward pass does it).
+void make_wave_lazy(const std::vector<WaveInterior>& wave, const std::vector<Object>& objects, std::vector<uint32_t>* wave_lazy) {
+  wave_lazy->assign(wave.size(), 0u);
+  for (size_t q = wave.size(); q-- > 0;) {
+    const WaveInterior& w = wave[q];
+    auto child_has = [&](int32_t ref, uint32_t cnt) {
+      if (ref >= 0) return (*wave_lazy)[(size_t)ref] != 0u;
+      const uint32_t first = (uint32_t)~ref;
+      for (uint32_t k = first; k < first + cnt && k < objects.size(); k++)
+        if (objects[k].kind == OBJ_MESH && objects[k].use_bvh != 0u && objects[k].nrec > 0u) return true;
+      return false;
+    };
+    (*wave_lazy)[q] = (child_has(w.l_ref, w.l_cnt) ? 1u : 0u) | (child_has(w.r_ref, w.r_cnt) ? 2u : 0u);
   }
 }
 
@@ -273,6 +383,11 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
   for (uint32_t i = 0; i < nobj; i++) {
     const ObjectInput& in = objects[i];
     if (in.material >= materials.size()) return "object " + std::to_string(i) + " references an unknown material";
+    if (in.source >= 0) {
+      if (in.kind != OBJ_MESH || in.is_light || (uint32_t)in.source >= i || objects[in.source].kind != OBJ_MESH || objects[in.source].source >= 0)
+        return "object " + std::to_string(i) + " is not an instance of a mesh added before it";
+      continue;
+    }
     if (in.kind == OBJ_MESH || (in.is_light && !in.mesh.idx.empty())) {   // a mesh, or an emissive shape's light mesh
       if (in.mesh.idx.empty() || in.mesh.idx.size() % 3) return "mesh " + std::to_string(i) + " has no triangles";
       for (uint32_t v : in.mesh.idx)
@@ -280,20 +395,21 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
     }
   }
 
-  // Per-mesh BVH<Triangle> (Tri_Mesh::build, student/tri_mesh.cpp:145-170, leaf size 4) and object boxes.
+  // Per-mesh BVH<Triangle> (Tri_Mesh::build, student/tri_mesh.cpp:145-170, leaf size 4) and object-space boxes.  An instance
+  // (rays/pathtracer.cpp:134-155 without mesh.copy()) takes its source's box: the copy's BVH has the same root.
   B.blas.resize(nobj);
-  std::vector<Box> obj_boxes(nobj);
-  std::vector<Mat4> itrans(nobj);
-  std::vector<bool> has_trans(nobj);
+  B.local_boxes.assign(6 * (size_t)nobj, 0.0f);
+  std::vector<Mat4> trans(nobj);
   for (uint32_t i = 0; i < nobj; i++) {
     const ObjectInput& in = objects[i];
-    itrans[i] = mat_inverse(in.trans);            // Object ctor, rays/object.h:18-21
-    has_trans[i] = mat_ne_identity(in.trans);
+    trans[i] = in.trans;
     Box ob;
     if (in.kind == OBJ_SPHERE) {                  // Sphere::bbox, student/shapes.cpp:9-15
       const float lo[3] = {-in.radius, -in.radius, -in.radius}, hi[3] = {in.radius, in.radius, in.radius};
       ob.enclose(lo);
       ob.enclose(hi);
+    } else if (in.source >= 0) {
+      for (int a = 0; a < 3; a++) { ob.mn[a] = B.local_boxes[6 * (size_t)in.source + a]; ob.mx[a] = B.local_boxes[6 * (size_t)in.source + 3 + a]; }
     } else {
       const uint32_t ntri = (uint32_t)in.mesh.idx.size() / 3;
       std::vector<Box> tb(ntri);
@@ -301,6 +417,7 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
         tb[t] = triangle_box(&in.mesh.pos[3 * in.mesh.idx[3 * t]], &in.mesh.pos[3 * in.mesh.idx[3 * t + 1]],
                              &in.mesh.pos[3 * in.mesh.idx[3 * t + 2]]);
       if (use_bvh) {
+        B.blas_builds++;
         if (!build_bvh(tb, 4, &B.blas[i]))
           return "BVH<Triangle> build of object " + std::to_string(i) +
                  " does not terminate (coincident centroids); the reference loops forever on this mesh";
@@ -310,42 +427,18 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
         for (const Box& b : tb) ob.enclose(b);  // List<Triangle>::bbox
       }
     }
-    if (has_trans[i]) ob.transform(in.trans);     // Object::bbox, rays/object.h:51-55
-    obj_boxes[i] = ob;
+    for (int a = 0; a < 3; a++) { B.local_boxes[6 * (size_t)i + a] = ob.mn[a]; B.local_boxes[6 * (size_t)i + 3 + a] = ob.mx[a]; }
   }
 
-  // BVH<Object> (leaf size 1) or List<Object>.
-  if (use_bvh) {
-    if (!build_bvh(obj_boxes, 1, &B.tlas)) return "BVH<Object> build does not terminate (coincident object centroids)";
-  } else {
-    B.tlas.nodes.clear();
-    B.tlas.prim.resize(nobj);
-    for (uint32_t i = 0; i < nobj; i++) B.tlas.prim[i] = i;
-  }
-
-  // Flatten.
-  if (use_bvh) append_nodes(B.tlas, &F);
+  // BVH<Object> (leaf size 1) or List<Object>, flattened.
+  Top T;
+  if (!build_top(trans, B.local_boxes, use_bvh, &T)) return "BVH<Object> build does not terminate (coincident object centroids)";
+  B.tlas = T.tlas;
+  F.nodes = T.nodes;
   F.tlas_nodes = (uint32_t)F.nodes.size();
-  F.max_tlas_depth = use_bvh ? interior_depth(B.tlas) : 0;
-  if (use_bvh) {  // interior-node sweep order for the wave-uniform kernel
-    const std::vector<HostNode>& N = B.tlas.nodes;
-    std::vector<int32_t> rank(N.size(), -1);
-    int32_t q = 0;
-    for (size_t n = 0; n < N.size(); n++)
-      if (N[n].l != N[n].r) rank[n] = q++;
-    for (size_t n = 0; n < N.size(); n++) {
-      if (N[n].l == N[n].r) continue;
-      WaveInterior wi;
-      const HostNode& a = N[N[n].l];
-      const HostNode& b = N[N[n].r];
-      for (int i = 0; i < 3; i++) { wi.boxl[i] = a.mn[i]; wi.boxl[3 + i] = a.mx[i]; wi.boxr[i] = b.mn[i]; wi.boxr[3 + i] = b.mx[i]; }
-      wi.l_ref = (a.l != a.r) ? rank[N[n].l] : ~(int32_t)a.start;
-      wi.r_ref = (b.l != b.r) ? rank[N[n].r] : ~(int32_t)b.start;
-      wi.l_cnt = a.size;
-      wi.r_cnt = b.size;
-      F.wave_tlas.push_back(wi);
-    }
-  }
+  F.max_tlas_depth = T.depth;
+  F.wave_tlas = T.wave;
+
   auto append_triangles = [&](const MeshInput& m, const std::vector<uint32_t>* order) {
     const uint32_t ntri = (uint32_t)m.idx.size() / 3;
     for (uint32_t k = 0; k < ntri; k++) {
@@ -372,80 +465,39 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
       for (int a = 0; a < 3; a++) F.tri_packed.push_back(g.e2[a]);
     }
   };
+  // Every mesh is stored once, where object order first reaches it or one of its instances.
+  B.store.assign(nobj, MeshStore());
+  std::vector<bool> stored(nobj, false);
   for (uint32_t slot = 0; slot < nobj; slot++) {
     const uint32_t i = B.tlas.prim[slot];
-    const ObjectInput& in = objects[i];
-    Object o;
-    std::memset(&o, 0, sizeof o);
-    o.kind = in.kind;
-    o.has_trans = has_trans[i] ? 1u : 0u;
-    o.material = (int32_t)in.material;
-    o.use_bvh = (in.kind == OBJ_MESH && use_bvh) ? 1u : 0u;
-    o.radius = in.radius;
-    o.id = i + 1;
-    o.trans = in.trans;
-    o.itrans = itrans[i];
-    if (in.kind == OBJ_MESH) {
-      o.tri_base = (uint32_t)F.tris.size();
-      o.ntri = (uint32_t)in.mesh.idx.size() / 3;
+    if (objects[i].kind != OBJ_MESH) continue;
+    const uint32_t src = objects[i].source >= 0 ? (uint32_t)objects[i].source : i;
+    if (!stored[src]) {
+      stored[src] = true;
+      const ObjectInput& in = objects[src];
+      MeshStore& m = B.store[src];
+      m.tri_base = (uint32_t)F.tris.size();
+      m.ntri = (uint32_t)in.mesh.idx.size() / 3;
       if (use_bvh) {
-        o.node_base = (uint32_t)F.nodes.size();
-        o.nnodes = (uint32_t)B.blas[i].nodes.size();
-        append_nodes(B.blas[i], &F);
-        F.max_blas_depth = std::max(F.max_blas_depth, interior_depth(B.blas[i]));
-        {  // interior records of this BLAS
-          const std::vector<HostNode>& N = B.blas[i].nodes;
-          std::vector<int32_t> rank(N.size(), -1);
-          int32_t q = 0;
-          for (size_t n = 0; n < N.size(); n++)
-            if (N[n].l != N[n].r) rank[n] = q++;
-          o.rec_base = (uint32_t)F.blas_recs.size();
-          o.nrec = (uint32_t)q;
-          auto ref_of = [&](uint32_t child) -> int32_t {
-            const HostNode& c = N[child];
-            if (c.l != c.r) return rank[child];
-            return ~(int32_t)((c.start << 3) | (c.size & 7u));
-          };
-          for (size_t n = 0; n < N.size(); n++) {
-            if (N[n].l == N[n].r) continue;
-            WaveInterior wi;
-            const HostNode& a = N[N[n].l];
-            const HostNode& b = N[N[n].r];
-            for (int k = 0; k < 3; k++) { wi.boxl[k] = a.mn[k]; wi.boxl[3 + k] = a.mx[k]; wi.boxr[k] = b.mn[k]; wi.boxr[3 + k] = b.mx[k]; }
-            wi.l_ref = ref_of(N[n].l);
-            wi.r_ref = ref_of(N[n].r);
-            wi.l_cnt = a.size;
-            wi.r_cnt = b.size;
-            F.blas_recs.push_back(wi);
-          }
-        }
-        append_triangles(in.mesh, &B.blas[i].prim);
+        m.node_off = (uint32_t)F.nodes.size() - F.tlas_nodes;
+        m.nnodes = (uint32_t)B.blas[src].nodes.size();
+        append_nodes(B.blas[src], &F.nodes);
+        F.max_blas_depth = std::max(F.max_blas_depth, interior_depth(B.blas[src]));
+        // interior records of this BLAS: a leaf child is ~((first triangle slot << 3) | triangle count)
+        m.rec_base = (uint32_t)F.blas_recs.size();
+        append_records(B.blas[src], [](const HostNode& leaf) { return (leaf.start << 3) | (leaf.size & 7u); }, &F.blas_recs);
+        m.nrec = (uint32_t)F.blas_recs.size() - m.rec_base;
+        append_triangles(in.mesh, &B.blas[src].prim);
       } else {
         append_triangles(in.mesh, nullptr);
       }
     }
-    if (o.kind == OBJ_MESH && o.use_bvh != 0u && o.nrec > 0u) {
-      // a mesh with a real BVH<Triangle>: its ordinal among those (the streamed sweeps queue its walks per ordinal)
-      o.use_bvh |= (uint32_t)F.lazy_objects.size() << 8;
-      F.lazy_objects.push_back(slot);
-    }
-    F.objects.push_back(o);
+    B.store[i] = B.store[src];
   }
-
-  // Which children of the top-level records hold a mesh with a real BVH<Triangle> somewhere below (children come after
-  // their parent in sweep order, so one backward pass does it).
-  F.wave_lazy.assign(F.wave_tlas.size(), 0u);
-  for (size_t q = F.wave_tlas.size(); q-- > 0;) {
-    const WaveInterior& w = F.wave_tlas[q];
-    auto child_has = [&](int32_t ref, uint32_t cnt) {
-      if (ref >= 0) return F.wave_lazy[(size_t)ref] != 0u;
-      const uint32_t first = (uint32_t)~ref;
-      for (uint32_t k = first; k < first + cnt && k < F.objects.size(); k++)
-        if (F.objects[k].kind == OBJ_MESH && F.objects[k].use_bvh != 0u && F.objects[k].nrec > 0u) return true;
-      return false;
-    };
-    F.wave_lazy[q] = (child_has(w.l_ref, w.l_cnt) ? 1u : 0u) | (child_has(w.r_ref, w.r_cnt) ? 2u : 0u);
-  }
+  make_objects(objects, trans, T, B.store, F.tlas_nodes, use_bvh, &F.objects, &F.lazy_objects);
+  make_wave_lazy(F.wave_tlas, F.objects, &F.wave_lazy);
+  const std::vector<Mat4>& itrans = T.itrans;
+  const std::vector<bool>& has_trans = T.has_trans;
 
   // Area lights: List<Object> of Tri_Mesh(mesh, false) in insertion order (rays/pathtracer.cpp:105-116,163).
   F.light_tri_first = (uint32_t)F.tris.size();
@@ -487,6 +539,54 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
     F.lights.push_back(L);
   }
   return "";
+}
+
+std::string prepare_repose(const BuiltScene& B, const uint32_t* objects, const Mat4* new_trans, uint32_t n, ReposedTop* out,
+                           bool* bad_argument) {
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  *bad_argument = true;
+  std::vector<Mat4> trans(nobj);
+  for (uint32_t i = 0; i < nobj; i++) trans[i] = B.inputs[i].trans;
+  std::vector<bool> seen(nobj, false);
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t i = objects[k];
+    if (i >= nobj) return "object " + std::to_string(i) + " is out of range (the scene has " + std::to_string(nobj) + " objects)";
+    if (seen[i]) return "object " + std::to_string(i) + " is listed twice";
+    if (B.inputs[i].is_light) return "object " + std::to_string(i) + " is an area light: its light tables depend on its pose, commit the scene again";
+    seen[i] = true;
+    trans[i] = new_trans[k];
+  }
+  *bad_argument = false;
+  Top T;
+  if (!build_top(trans, B.local_boxes, B.flat.use_bvh, &T)) return "BVH<Object> build does not terminate (coincident object centroids)";
+  out->listed.assign(objects, objects + n);
+  out->trans.assign(new_trans, new_trans + n);
+  make_objects(B.inputs, trans, T, B.store, (uint32_t)T.nodes.size(), B.flat.use_bvh, &out->objects, &out->lazy_objects);
+  make_wave_lazy(T.wave, out->objects, &out->wave_lazy);
+  out->tlas.nodes.swap(T.tlas.nodes);
+  out->tlas.prim.swap(T.tlas.prim);
+  out->tlas_nodes.swap(T.nodes);
+  out->wave_tlas.swap(T.wave);
+  out->max_tlas_depth = T.depth;
+  return "";
+}
+
+void apply_repose(BuiltScene* built, ReposedTop* top) {
+  BuiltScene& B = *built;
+  FlatScene& F = B.flat;
+  for (size_t k = 0; k < top->listed.size(); k++) B.inputs[top->listed[k]].trans = top->trans[k];
+  // the BVH<Triangle> nodes stay behind the BVH<Object>'s, however many those are now
+  std::vector<Node> nodes(top->tlas_nodes);
+  nodes.insert(nodes.end(), F.nodes.begin() + F.tlas_nodes, F.nodes.end());
+  F.nodes.swap(nodes);
+  F.tlas_nodes = (uint32_t)top->tlas_nodes.size();
+  F.max_tlas_depth = top->max_tlas_depth;
+  F.wave_tlas.swap(top->wave_tlas);
+  F.wave_lazy.swap(top->wave_lazy);
+  F.lazy_objects.swap(top->lazy_objects);
+  F.objects.swap(top->objects);
+  B.tlas.nodes.swap(top->tlas.nodes);
+  B.tlas.prim.swap(top->tlas.prim);
 }
 
 }  // namespace srt

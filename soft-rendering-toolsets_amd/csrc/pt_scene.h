@@ -134,17 +134,40 @@ struct ObjectInput {
   bool is_light = false;
   float radius = 0.f;
   MeshInput mesh;
+  // >= 0: an instance (srt_pt_add_instance) of the mesh object with this insertion index - Object(<its Tri_Mesh>.copy(), ..) of
+  // rays/pathtracer.cpp:134-155 without the copy: `mesh` stays empty, the triangles and the BVH<Triangle> are the source's
+  int32_t source = -1;
 };
 
 // Host BVH kept for srt_pt_dump_bvh (reference Node layout: bbox + start,size,l,r).
 struct HostNode { float mn[3], mx[3]; uint32_t start, size, l, r; };
 struct HostBVH { std::vector<HostNode> nodes; std::vector<uint32_t> prim; };
 
+// Where a mesh lives in the flattened arrays.  BLAS nodes are counted from the end of the TLAS nodes (node_off), so that a
+// re-posed scene, whose BVH<Object> may have another number of nodes, leaves them where they are.
+struct MeshStore { uint32_t tri_base = 0, ntri = 0, node_off = 0, nnodes = 0, rec_base = 0, nrec = 0; };
+
 struct BuiltScene {
   FlatScene flat;
   HostBVH tlas;                 // prim = object insertion indices
-  std::vector<HostBVH> blas;    // per object in insertion order (empty for spheres / list mode)
+  std::vector<HostBVH> blas;    // per object in insertion order (empty for spheres / instances / list mode)
   std::vector<ObjectInput> inputs;
+  std::vector<float> local_boxes;   // six floats per object in insertion order: the object-space box Object::bbox poses
+  std::vector<MeshStore> store;     // per object in insertion order: an instance's is its source's
+  uint64_t blas_builds = 0;         // BVH<Triangle> builds this build_scene performed (one per mesh that is not an instance)
+};
+
+// What srt_pt_repose derives for new poses of a committed scene, built next to it: the BVH<Object> and everything that follows
+// from object order.  prepare_repose leaves `built` untouched; apply_repose moves the tables in (it cannot fail).
+struct ReposedTop {
+  std::vector<uint32_t> listed;     // insertion indices ..
+  std::vector<Mat4> trans;          // .. and their new transforms
+  HostBVH tlas;
+  std::vector<Node> tlas_nodes;
+  uint32_t max_tlas_depth = 0;
+  std::vector<WaveInterior> wave_tlas;
+  std::vector<uint32_t> wave_lazy, lazy_objects;
+  std::vector<Object> objects;
 };
 
 // BVH<Primitive>::build for large primitive sets on the device (pt_bvh_device.hip; same arrays as the host build, bit for
@@ -162,6 +185,14 @@ bool mat_ne_identity(const Mat4& m);
 // Returns "" on success, otherwise an error message (e.g. the reference's non-terminating BVH build).
 std::string build_scene(const std::vector<ObjectInput>& objects, const std::vector<Material>& materials, bool use_bvh,
                         BuiltScene* out);
+
+// New transforms for `n` objects of a built scene (insertion indices; meshes, instances and spheres - not area lights): itrans /
+// has_trans / posed box of those, the BVH<Object> (or list order) and the tables that follow from it.  No BVH<Triangle> is
+// rebuilt and no triangle moves.  Returns "" or an error message; *bad_argument tells a refused list (duplicate, out of range,
+// a light) from a BVH<Object> build that does not terminate.
+std::string prepare_repose(const BuiltScene& built, const uint32_t* objects, const Mat4* trans, uint32_t n, ReposedTop* out,
+                           bool* bad_argument);
+void apply_repose(BuiltScene* built, ReposedTop* top);
 
 Camera make_camera(const float iview[16], float vert_fov_deg, float aspect_ratio);
 

@@ -85,6 +85,7 @@ void Pathtracer::build_scene(Scene& layout_scene) {
 void Pathtracer::feed_scene(srt_pt* ctx, Scene& layout_scene) {
     check(srt_pt_scene_begin(ctx), "srt_pt_scene_begin");
     bool warned = false;
+    uint32_t n_objects = 0;   // objects added so far: the insertion index srt_pt_add_instance names its source by
     layout_scene.for_items([&, this](Scene_Item& item) {
         if(item.is<Scene_Object>()) {
             Scene_Object& obj = item.get<Scene_Object>();
@@ -119,6 +120,7 @@ void Pathtracer::feed_scene(srt_pt* ctx, Scene& layout_scene) {
                 check(srt_pt_add_mesh(ctx, pos.data(), nrm.data(), (uint32_t)mesh.verts().size(), idxs.data(),
                                       (uint32_t)idxs.size(), T, idx, light ? 1 : 0),
                       "srt_pt_add_mesh");
+                n_objects++;
             };
             if(obj.is_shape()) {
                 const float radius = obj.opt.shape.get<PT::Sphere>().radius;
@@ -135,8 +137,10 @@ void Pathtracer::feed_scene(srt_pt* ctx, Scene& layout_scene) {
                     check(srt_pt_add_sphere_light(ctx, radius, T, idx, pos.data(), nrm.data(), (uint32_t)mesh.verts().size(),
                                                   idxs.data(), (uint32_t)idxs.size()),
                           "srt_pt_add_sphere_light");
+                    n_objects++;
                 } else {
                     check(srt_pt_add_sphere(ctx, radius, T, idx), "srt_pt_add_sphere");
+                    n_objects++;
                 }
             } else {
                 add_mesh(obj.posed_mesh(), is_light);
@@ -179,8 +183,9 @@ void Pathtracer::feed_scene(srt_pt* ctx, Scene& layout_scene) {
                 break;
             }
         } else if(item.is<Scene_Particles>()) {
-            // build_scene, rays/pathtracer.cpp:134-156: one Lambertian copy of the particle mesh per particle,
-            // posed by translate(p.pos) * scale(opt.scale)
+            // build_scene, rays/pathtracer.cpp:134-156: one Lambertian Object per particle, posed by translate(p.pos) *
+            // scale(opt.scale), each with mesh.copy() of ONE built BVH<Triangle> - here the first particle carries the mesh and
+            // every further one is an instance of it (the instancing :76-77 leaves "for the future"): same image, one BVH
             Scene_Particles& particles = item.get<Scene_Particles>();
             srt_pt_material mat;
             std::memset(&mat, 0, sizeof mat);
@@ -196,12 +201,20 @@ void Pathtracer::feed_scene(srt_pt* ctx, Scene& layout_scene) {
                 nrm.insert(nrm.end(), {v.norm.x, v.norm.y, v.norm.z});
             }
             const auto& idxs = mesh.indices();
+            const uint32_t none = ~0u;
+            uint32_t first = none;
             for(const Scene_Particles::Particle& p : particles.get_particles()) {
                 float T[16];
                 mat_to_array(Mat4::translate(p.pos) * Mat4::scale(Vec3{particles.opt.scale}), T);
-                check(srt_pt_add_mesh(ctx, pos.data(), nrm.data(), (uint32_t)mesh.verts().size(), idxs.data(),
-                                      (uint32_t)idxs.size(), T, idx, 0),
-                      "srt_pt_add_mesh");
+                if(first == none) {
+                    check(srt_pt_add_mesh(ctx, pos.data(), nrm.data(), (uint32_t)mesh.verts().size(), idxs.data(),
+                                          (uint32_t)idxs.size(), T, idx, 0),
+                          "srt_pt_add_mesh");
+                    first = n_objects;
+                } else {
+                    check(srt_pt_add_instance(ctx, first, T, idx), "srt_pt_add_instance");
+                }
+                n_objects++;
             }
         }
     });

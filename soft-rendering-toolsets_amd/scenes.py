@@ -202,3 +202,25 @@ def _flat_mesh_fast(positions, triangles):
     pos = np.stack([v0, v1, v2], axis=1).reshape(-1, 3).astype(F)
     nrm = np.repeat(n, 3, axis=0).astype(F)
     return pos, nrm, np.arange(len(pos), dtype=np.uint32)
+
+
+def share_meshes(description: dict) -> dict:
+    """A copy of the scene description in which every non-light mesh object whose pos / nrm / idx arrays are byte-equal to an
+    earlier non-light mesh object's is {"kind": "instance", "of": <that object's index>, "T", "material"}: the one Object per
+    particle of rays/pathtracer.cpp:134-155 without the mesh.copy().  Lights are left alone (an emissive object needs triangles
+    of its own in the area-light list), instances already there stay, and so does the order of objects; idempotent."""
+    out = dict(description)
+    objs, first = [], {}
+    mats = description["materials"]
+    for k, o in enumerate(description["objects"]):
+        if o["kind"] == "mesh" and not o.get("is_light") and int(mats[int(o["material"])]["type"]) != DIFFUSE_LIGHT:
+            pos, nrm = np.ascontiguousarray(o["pos"], F), np.ascontiguousarray(o["nrm"], F)
+            idx = np.ascontiguousarray(o["idx"], np.uint32)
+            key = (pos.shape, pos.tobytes(), nrm.tobytes(), idx.tobytes())
+            src = first.setdefault(key, k)
+            if src != k:
+                objs.append({"kind": "instance", "of": src, "T": o["T"], "material": o["material"]})
+                continue
+        objs.append(o)
+    out["objects"] = objs
+    return out
