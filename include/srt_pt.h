@@ -213,6 +213,35 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh);
  * committed scene.  New poses that make the reference's BVH<Object> build non-terminating or too deep for the traversal stacks
  * fail as srt_pt_scene_commit does (SRT_ERR_UNSUPPORTED) - and the committed scene stays exactly as it was. */
 int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n);
+/* New vertex arrays for ONE mesh of the committed scene without committing again: what a renderer of deforming meshes (a skinned
+ * skeleton, cloth, a caller's own kernel) gets from the reference only by running build_scene again on Scene_Object::posed_mesh()
+ * (rays/pathtracer.cpp:66-176, per frame).  `object` is the insertion index of an object added by srt_pt_add_mesh; positions /
+ * normals are nverts * 3 floats and nverts is what the mesh was added with; the index buffer, material, transform and instance
+ * relations stay.  Runs with nothing of the context in flight and waits for the device itself.  Exactly one BVH<Triangle> (leaf
+ * size 4) is built - on the host or the device by the rule of srt_pt_set_bvh_builder / SRT_BVH_BUILDER; none when the scene was
+ * committed with use_bvh == 0: the triangles then stay in index order and the object's box is List<Triangle>::bbox - and the
+ * mesh's triangle, normal and packed-triangle records are rewritten in place by a kernel from the 24 B per vertex that go up (and
+ * 4 B per triangle of primitive order after a host build); no other mesh's are touched or uploaded.  The mesh's BVH<Triangle>
+ * nodes and interior records may be more or fewer than before: the ranges stored behind them are re-packed and uploaded again
+ * when they move, left alone when they do not.  Every instance of the mesh follows (its triangles and BVH<Triangle> are the
+ * source's, its object-space box the new root box), so the BVH<Object> is rebuilt and the tables that follow object order are
+ * replaced as in srt_pt_repose.  Afterwards the scene equals, bit for bit in everything it computes, a fresh srt_pt_scene_begin
+ * .. srt_pt_scene_commit of the same objects with the new arrays; only storage and counters may differ.  SRT_ERR_STATE: no
+ * committed scene.  SRT_ERR_INVALID: a NULL argument, an index out of range, a sphere or sphere light, an instance (the message
+ * names its source: update that), an area light (its light-list copy and light tables depend on the vertices: commit again),
+ * nverts differing from the committed count.  Arrays that make the reference's BVH<Triangle> or BVH<Object> build non-terminating
+ * or too deep for the traversal stacks fail as srt_pt_scene_commit does (SRT_ERR_UNSUPPORTED).  In every failing case the
+ * committed scene stays exactly as it was, on the host and on the device: everything is built aside and checked before the
+ * first write.  (A HIP failure after that point - out of device memory while the tables are replaced - is SRT_ERR_HIP and leaves
+ * the context without a committed scene: commit again.)  The builder's workspace and the vertex staging are kept between calls;
+ * like srt_pt_repose the call allocates the three tables of object order anew, and the node / record arrays too when the mesh's
+ * node / record count changed.  Works on a host-only context (device = -1). */
+int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts);
+/* The same with the two arrays in device memory (a skinning kernel's output): copies and kernels are enqueued on `stream`
+ * (a hipStream_t; NULL: the null stream), which the call synchronises where the host needs a verdict and before it returns.  The
+ * arrays are copied back once (24 B per vertex) so that the host's record of the scene stays true; with the host builder, or a
+ * mesh below the device builder's threshold, the triangle boxes are computed from that copy. */
+int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts);
 /* Where srt_pt_scene_commit runs BVH<Primitive>::build (student/bvh.inl:35-163): device != 0 (default) builds primitive sets of at
  * least min_primitives (default 16384) on the GPU, smaller ones and device == 0 on the host.  Both produce the reference's node
  * arrays and primitive order bit for bit (the candidate planes' std::partition sequence included); SRT_BVH_BUILDER=host in the

@@ -61,7 +61,12 @@ int srt_pt_counters(srt_pt* pt, uint64_t out[8]);
  * records stored, BVH<Triangle> builds performed by this context since creation, scene bytes resident on the device, scene bytes
  * uploaded since creation, of those the triangle / normal / packed-triangle / BVH<Triangle>-record bytes}.  Lets a test state
  * that srt_pt_add_instance shared and srt_pt_repose left the triangles alone.  Works on a host-only context (device = -1): the
- * two byte figures of the device are then 0 and nothing is ever uploaded.  The first four are 0 before the first commit. */
+ * two byte figures of the device are then 0 and nothing is ever uploaded.  The first four are 0 before the first commit.
+ * The resident bytes include the index buffers srt_pt_update_mesh's kernels read (12 B per triangle of every mesh that is neither
+ * an instance nor an area light).  A successful srt_pt_update_mesh[_device] adds exactly 1 to the builds (nothing in a scene
+ * committed without BVHs, where nothing is built) and to the two upload figures the bytes it actually copied from host to device:
+ * the vertex arrays (host form), the primitive order of a host build, the nodes and records that are new or moved, the tables of
+ * object order - the records its kernel writes on the device are not uploads.  A refused update adds nothing to the builds. */
 int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]);
 /* cosf/sinf of the kernel (SRT-MATH v2) for n host floats; parity tests compare them with glibc. */
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);

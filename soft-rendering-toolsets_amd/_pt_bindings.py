@@ -56,6 +56,8 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_add_instance.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32]
     lib.srt_pt_scene_commit.argtypes = [c_void_p, c_int]
     lib.srt_pt_repose.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_update_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_update_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_scene_counts.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_set_bvh_builder.argtypes = [c_void_p, c_int, c_uint32]
     lib.srt_pt_set_stream_slots.argtypes = [c_void_p, c_uint32]
@@ -239,6 +241,18 @@ class Pathtracer:
         if len(T) != len(idx):
             raise ValueError(f"{len(idx)} objects but {len(T)} transforms")
         self._check(self._lib, self._lib.srt_pt_repose(self._ctx, _p(idx), _p(T), len(idx)))
+
+    def update_mesh(self, index: int, pos, nrm) -> None:
+        """srt_pt_update_mesh: new vertex positions and normals ((nverts, 3) each, the count the mesh was added with) for the mesh
+        object with this insertion index of the committed scene - one BVH<Triangle> is rebuilt, no other mesh is touched."""
+        pos, nrm = _f32(pos).reshape(-1, 3), _f32(nrm).reshape(-1, 3)
+        if len(pos) != len(nrm):
+            raise ValueError(f"{len(pos)} positions but {len(nrm)} normals")
+        self._check(self._lib, self._lib.srt_pt_update_mesh(self._ctx, int(index), _p(pos), _p(nrm), len(pos)))
+
+    def update_mesh_device(self, index: int, d_pos_ptr: int, d_nrm_ptr: int, nverts: int, stream: int = 0) -> None:
+        """srt_pt_update_mesh_device: the same from two device arrays of nverts * 3 floats (e.g. tensor.data_ptr())."""
+        self._check(self._lib, self._lib.srt_pt_update_mesh_device(self._ctx, c_void_p(stream), int(index), c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr), int(nverts)))
 
     def scene_counts(self) -> dict:
         """srt_pt_scene_counts: what the scene stores, the BVH<Triangle> builds so far and the bytes uploaded (SCENE_COUNT_NAMES)."""
@@ -578,6 +592,10 @@ class PathtracerGroup:
     def repose(self, indices, Ts) -> None:
         for m in self.members:
             m.repose(indices, Ts)
+
+    def update_mesh(self, index: int, pos, nrm) -> None:
+        for m in self.members:
+            m.update_mesh(index, pos, nrm)
 
     def scene_counts(self) -> list:
         """Every member's Pathtracer.scene_counts(), by rank (the scene is replicated)."""

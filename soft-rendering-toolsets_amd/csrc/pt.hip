@@ -24,6 +24,7 @@
 #include <map>
 #include <vector>
 
+#include "pt_bvh_device.h"
 #include "pt_device.h"
 #include "pt_scene.h"
 #include "srt_common.h"
@@ -440,6 +441,13 @@ struct srt_pt {
   uint64_t stream_generations = 0;
   // srt_pt_scene_counts: since creation
   uint64_t blas_builds = 0, bytes_uploaded = 0, tri_bytes_uploaded = 0;
+  // srt_pt_update_mesh: the index buffers of the meshes that can be updated (no instance, no area light), resident from commit on, one
+  // after the other; the device builder's workspace; and the staging of the host form's vertex arrays.  Grown on demand, kept.
+  uint32_t* d_idx = nullptr; size_t idx_words = 0;
+  std::vector<size_t> idx_off;              // per object in insertion order: first word of its index buffer in d_idx (SIZE_MAX: none)
+  BvhWorkspace bvh_ws;
+  float* d_vpos = nullptr; size_t vpos_floats = 0;
+  float* d_vnrm = nullptr; size_t vnrm_floats = 0;
 };
 
 namespace {
@@ -1103,6 +1111,8 @@ int srt_pt_destroy(srt_pt* pt) {
     (void)hipFree(pt->d_nodes); (void)hipFree(pt->d_tris); (void)hipFree(pt->d_tri_packed); (void)hipFree(pt->d_nrm); (void)hipFree(pt->d_objects);
     (void)hipFree(pt->d_lights); (void)hipFree(pt->d_ltris); (void)hipFree(pt->d_mats); (void)hipFree(pt->d_wave); (void)hipFree(pt->d_blas); (void)hipFree(pt->d_wave_lazy); (void)hipFree(pt->d_dlights); (void)hipFree(pt->d_env_map);
     (void)hipFree(pt->d_tile_buf); (void)hipFree(pt->d_image); (void)hipFree(pt->d_totals);
+    (void)hipFree(pt->d_idx); (void)hipFree(pt->d_vpos); (void)hipFree(pt->d_vnrm);
+    bvh_workspace_free(&pt->bvh_ws);
     if (pt->h_fault) (void)hipHostFree(pt->h_fault);
     if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);
     for (auto& kv : pt->epoch_buffers) {
@@ -1273,10 +1283,171 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
         (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_blas, F.blas_recs, true)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)) ||
         (st = upload(pt, &pt->d_dlights, F.delta_lights)) || (st = upload(pt, &pt->d_env_map, pt->env_map)))
       return st;
+    // the index buffers srt_pt_update_mesh's kernels read (12 B per triangle)
+    std::vector<uint32_t> idx;
+    pt->idx_off.assign(pt->built.inputs.size(), SIZE_MAX);
+    for (size_t i = 0; i < pt->built.inputs.size(); i++) {
+      const ObjectInput& in = pt->built.inputs[i];
+      if (in.kind != OBJ_MESH || in.source >= 0 || in.is_light) continue;
+      pt->idx_off[i] = idx.size();
+      idx.insert(idx.end(), in.mesh.idx.begin(), in.mesh.idx.end());
+    }
+    pt->idx_words = idx.size();
+    if ((st = upload(pt, &pt->d_idx, idx))) return st;
   }
   pt->committed = true;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   return SRT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Device side of a mesh update whose verdict is in (srt_pt_update_mesh): the node and record arrays after the scene layer
+// re-packed them.  [0, keep) of the old array has not moved and [from, size) of the new one is new or has moved; with another
+// total length the array is allocated anew, the part that stays is copied on the device and only the rest comes from the host.
+template <typename T>
+int upload_tail(srt_pt* pt, hipStream_t s, T** dst, size_t old_size, const std::vector<T>& src, size_t keep_from, size_t keep_to, size_t keep_n,
+                size_t up_from, size_t up_to, bool tri_class) {
+  // old[keep_from, keep_from + keep_n) -> new[keep_to, ..);  src[up_from, up_to) -> new[up_from, up_to)
+  if (src.size() != old_size || keep_from != keep_to) {
+    T* fresh = nullptr;
+    SRT_HIP(hipMalloc(&fresh, (src.empty() ? 1 : src.size()) * sizeof(T)));
+    if ((keep_n && hipMemcpyAsync(fresh + keep_to, *dst + keep_from, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipFree(fresh);
+      return srt::fail(SRT_ERR_HIP, "srt_pt_update_mesh: device copy failed");
+    }
+    (void)hipFree(*dst);
+    *dst = fresh;
+  }
+  if (up_to > up_from) {
+    SRT_HIP(hipMemcpyAsync(*dst + up_from, src.data() + up_from, (up_to - up_from) * sizeof(T), hipMemcpyHostToDevice, s));
+    pt->bytes_uploaded += (up_to - up_from) * sizeof(T);
+    if (tri_class) pt->tri_bytes_uploaded += (up_to - up_from) * sizeof(T);
+  }
+  return SRT_OK;
+}
+
+// The device writes of a mesh update, after apply_mesh_update: the record kernel over the mesh's triangle range, the nodes and
+// records that are new or moved, the tables of object order.  `old`: the mesh's storage before.
+int write_updated_mesh(srt_pt* pt, hipStream_t s, uint32_t object, const MeshStore& old, size_t old_tlas, size_t old_nodes, size_t old_recs,
+                       const float* d_pos, const float* d_nrm, const uint32_t* d_mesh_idx) {
+  const FlatScene& F = pt->built.flat;
+  const bool use_bvh = F.use_bvh;
+  const MeshStore now = pt->built.store[object];
+  const uint32_t ntri = now.ntri;
+  launch_mesh_records(s, d_pos, d_nrm, d_mesh_idx, use_bvh ? pt->bvh_ws.d_prim : nullptr, ntri, pt->d_tris + now.tri_base, pt->d_nrm + now.tri_base,
+                      pt->d_tri_packed + 9 * (size_t)now.tri_base);
+  int st;
+  if (use_bvh) {
+    // nodes: the BVH<Object>'s and the mesh's are new; the BVH<Triangle>s in front stay, those behind move when the mesh's count changed
+    const bool same_nodes = now.nnodes == old.nnodes, same_recs = now.nrec == old.nrec;
+    const size_t at = (size_t)F.tlas_nodes + now.node_off;
+    if ((st = upload_tail(pt, s, &pt->d_nodes, old_nodes, F.nodes, old_tlas, F.tlas_nodes, old.node_off, at,
+                          same_nodes && F.tlas_nodes == old_tlas ? at + now.nnodes : F.nodes.size(), false)))
+      return st;
+    if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
+    pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
+    if ((st = upload_tail(pt, s, &pt->d_blas, old_recs, F.blas_recs, 0, 0, old.rec_base, now.rec_base,
+                          same_recs ? (size_t)now.rec_base + now.nrec : F.blas_recs.size(), true)))
+      return st;
+  }
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
+    return st;
+  return SRT_OK;
+}
+
+
+// srt_pt_update_mesh / srt_pt_update_mesh_device.  h_*: the host form's arrays; d_*: the device form's (then `s` is the caller's stream).
+int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* h_pos, const float* h_nrm, const float* d_pos,
+                const float* d_nrm, uint32_t nverts) {
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
+  const std::string refused = check_mesh_update(pt->built, object, nverts);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  const bool on_device = pt->device >= 0;
+  if (!on_device && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
+  const bool use_bvh = pt->built.flat.use_bvh;
+  const MeshStore old = pt->built.store[object];
+  const uint32_t ntri = old.ntri;
+  const size_t vfloats = 3 * (size_t)nverts;
+  std::vector<float> back_pos, back_nrm;
+  if (on_device) {
+    SRT_HIP(hipSetDevice(pt->device));
+    SRT_HIP(hipStreamSynchronize(pt->stream));
+    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old arrays
+    if (h_pos) {                                          // 24 B per vertex up, into the staging (nothing of the live scene yet)
+      int st;
+      if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
+      // (blocking copies: the caller's arrays are not read after this call returns, whichever way it returns)
+      SRT_HIP(hipMemcpy(pt->d_vpos, h_pos, vfloats * sizeof(float), hipMemcpyHostToDevice));
+      SRT_HIP(hipMemcpy(pt->d_vnrm, h_nrm, vfloats * sizeof(float), hipMemcpyHostToDevice));
+      pt->bytes_uploaded += 2 * vfloats * sizeof(float);
+      d_pos = pt->d_vpos; d_nrm = pt->d_vnrm;
+    } else {                                              // 24 B per vertex back: BuiltScene::inputs and the host mirrors stay true
+      back_pos.resize(vfloats); back_nrm.resize(vfloats);
+      SRT_HIP(hipMemcpyAsync(back_pos.data(), d_pos, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+      SRT_HIP(hipMemcpyAsync(back_nrm.data(), d_nrm, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+      SRT_HIP(hipStreamSynchronize(s));
+      h_pos = back_pos.data(); h_nrm = back_nrm.data();
+    }
+  }
+  // the one BVH<Triangle> build goes where srt_pt_scene_commit's would: a mesh at or above the device builder's threshold is
+  // built there, from boxes computed there; anything else on the host
+  const char* be = getenv("SRT_BVH_BUILDER");
+  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
+  const uint32_t* d_mesh_idx = on_device ? pt->d_idx + pt->idx_off[object] : nullptr;
+  HostBVH device_tree;
+  const bool device_wanted = on_device && use_bvh && bmode != 0 && ntri >= pt->bvh_device_min && ntri > 4u;
+  bool device_built = false;
+  if (device_wanted && bvh_workspace_reserve(&pt->bvh_ws, ntri, false)) {
+    launch_mesh_boxes(s, d_pos, d_mesh_idx, ntri, pt->bvh_ws.d_boxes);
+    device_built = build_bvh_device_core(&pt->bvh_ws, s, ntri, 4, &device_tree);
+  }
+  // The BVH<Object> build goes where srt_pt_repose's does.  A device build of the mesh that failed - no termination, or no
+  // memory - is not tried a second time through the wrapper: the host builds give the verdict.
+  if (on_device && bmode != 0 && !(device_wanted && !device_built)) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
+  else set_device_bvh_builder(nullptr, 0);
+  MeshUpdate U;
+  bool bad_argument = false;
+  const std::string err = prepare_mesh_update(pt->built, object, h_pos, h_nrm, nverts, device_built ? &device_tree : nullptr, &U, &bad_argument);
+  set_device_bvh_builder(nullptr, 0);
+  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str());
+  if ((int)U.top.max_tlas_depth > kMaxTlasDepth || (int)U.max_blas_depth > kMaxBlasDepth)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)",
+                     U.top.max_tlas_depth, kMaxTlasDepth, U.max_blas_depth, kMaxBlasDepth);
+  if (on_device && use_bvh && !device_built) {            // a host build: its primitive order goes up, 4 B per triangle
+    if (!bvh_workspace_reserve(&pt->bvh_ws, ntri, true)) return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+    SRT_HIP(hipMemcpy(pt->bvh_ws.d_prim, U.blas.prim.data(), (size_t)ntri * 4, hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)ntri * 4;
+  }
+  // the verdict is in: from here on the new arrays replace the old ones, on the host and then on the device
+  const size_t old_tlas = pt->built.flat.tlas_nodes, old_nodes = pt->built.flat.nodes.size(), old_recs = pt->built.flat.blas_recs.size();
+  apply_mesh_update(&pt->built, &U);
+  if (use_bvh) pt->blas_builds++;
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  if (!on_device) return SRT_OK;
+  // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
+  const int st = write_updated_mesh(pt, s, object, old, old_tlas, old_nodes, old_recs, d_pos, d_nrm, d_mesh_idx);
+  if (st != SRT_OK) pt->committed = false;
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
+  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh: NULL argument");
+  return update_mesh(pt, "srt_pt_update_mesh", pt->stream, object, positions, normals, nullptr, nullptr, nverts);
+}
+
+int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
+  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh_device: NULL argument");
+  return update_mesh(pt, "srt_pt_update_mesh_device", (hipStream_t)stream, object, nullptr, nullptr, d_positions, d_normals, nverts);
 }
 
 int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
@@ -1335,7 +1506,8 @@ int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]) {
     out[5] = F.nodes.size() * sizeof(Node) + F.tris.size() * sizeof(Tri) + F.tri_nrm.size() * sizeof(TriNrm) + F.tri_packed.size() * sizeof(float) +
              F.objects.size() * sizeof(Object) + F.lights.size() * sizeof(Light) + F.light_tris.size() * sizeof(LightTri) +
              F.materials.size() * sizeof(Material) + F.wave_tlas.size() * sizeof(WaveInterior) + F.blas_recs.size() * sizeof(WaveInterior) +
-             F.wave_lazy.size() * sizeof(uint32_t) + F.delta_lights.size() * sizeof(DeltaLight) + pt->env_map.size() * sizeof(float);
+             F.wave_lazy.size() * sizeof(uint32_t) + F.delta_lights.size() * sizeof(DeltaLight) + pt->env_map.size() * sizeof(float) +
+             pt->idx_words * sizeof(uint32_t);
   out[6] = pt->bytes_uploaded;
   out[7] = pt->tri_bytes_uploaded;
   return SRT_OK;

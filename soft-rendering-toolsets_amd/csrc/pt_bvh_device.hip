@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "pt_bvh_device.h"
 #include "pt_scene.h"
 #include "srt_common.h"
 
@@ -236,35 +237,62 @@ __global__ void bvh_root(DNode* __restrict__ nodes, uint32_t* __restrict__ prim,
 
 }  // namespace
 
-// The device builder behind build_bvh (pt_scene.cpp) for large primitive sets.  `boxes6`: n x {mn[3], mx[3]} on the host.
-// Returns false when the build does not terminate (as the host build does) or a HIP call fails (out->nodes is then empty and
-// the caller falls back to reporting the host builder's verdict).
-bool build_bvh_device(const float* boxes6, uint32_t n, uint32_t max_leaf, HostBVH* out) {
+bool bvh_workspace_reserve(BvhWorkspace* ws, uint32_t n, bool prim_only) {
   bool ok = true;
+  if (n > ws->prims) {
+    (void)hipFree(ws->d_prim); ws->d_prim = nullptr; ws->prims = 0;
+    BVH_HIP(hipMalloc(&ws->d_prim, (size_t)n * 4));
+    ws->prims = n;
+  }
+  if (!prim_only && n > ws->build_prims) {
+    const size_t node_cap = 8ull * n + 64 + 2 * (size_t)n + 8;
+    (void)hipFree(ws->d_boxes); (void)hipFree(ws->d_nodes); (void)hipFree(ws->d_l); (void)hipFree(ws->d_r); (void)hipFree(ws->d_child); (void)hipFree(ws->d_ns);
+    ws->d_boxes = nullptr; ws->d_nodes = nullptr; ws->d_l = ws->d_r = ws->d_child = ws->d_ns = nullptr; ws->build_prims = 0;
+    BVH_HIP(hipMalloc(&ws->d_boxes, (size_t)n * sizeof(DBox)));
+    BVH_HIP(hipMalloc(&ws->d_nodes, node_cap * sizeof(DNode)));
+    BVH_HIP(hipMalloc(&ws->d_l, (size_t)n * 4)); BVH_HIP(hipMalloc(&ws->d_r, (size_t)n * 4));
+    BVH_HIP(hipMalloc(&ws->d_child, node_cap * 4)); BVH_HIP(hipMalloc(&ws->d_ns, 4));
+    ws->build_prims = n;
+  }
+done:
+  if (!ok) {
+    bvh_workspace_free(ws);
+    (void)hipGetLastError();
+  }
+  return ok;
+}
+
+void bvh_workspace_free(BvhWorkspace* ws) {
+  (void)hipFree(ws->d_boxes); (void)hipFree(ws->d_nodes); (void)hipFree(ws->d_prim); (void)hipFree(ws->d_l); (void)hipFree(ws->d_r); (void)hipFree(ws->d_child); (void)hipFree(ws->d_ns);
+  *ws = BvhWorkspace();
+}
+
+// The build itself, over boxes that are on the device already (uploaded by build_bvh_device, or computed there by
+// srt_pt_update_mesh): the root, then one plan + one split launch and one blocking read-back per level.
+bool build_bvh_device_core(BvhWorkspace* ws, void* stream, uint32_t n, uint32_t max_leaf, HostBVH* out) {
+  bool ok = true;
+  hipStream_t s = (hipStream_t)stream;
   const size_t node_limit = 8ull * n + 64;
   const size_t node_cap = node_limit + 2 * (size_t)n + 8;
-  DBox* d_boxes = nullptr; DNode* d_nodes = nullptr;
-  uint32_t *d_prim = nullptr, *d_l = nullptr, *d_r = nullptr, *d_child = nullptr, *d_ns = nullptr;
+  const DBox* d_boxes = (const DBox*)ws->d_boxes; DNode* d_nodes = (DNode*)ws->d_nodes;
+  uint32_t *d_prim = ws->d_prim, *d_l = ws->d_l, *d_r = ws->d_r, *d_child = ws->d_child, *d_ns = ws->d_ns;
   size_t total = 1;
   uint32_t first = 0, count = 1, levels = 0;
   out->nodes.clear(); out->prim.clear();
-  BVH_HIP(hipMalloc(&d_boxes, (size_t)n * sizeof(DBox)));
-  BVH_HIP(hipMalloc(&d_nodes, node_cap * sizeof(DNode)));
-  BVH_HIP(hipMalloc(&d_prim, (size_t)n * 4)); BVH_HIP(hipMalloc(&d_l, (size_t)n * 4)); BVH_HIP(hipMalloc(&d_r, (size_t)n * 4));
-  BVH_HIP(hipMalloc(&d_child, node_cap * 4)); BVH_HIP(hipMalloc(&d_ns, 4));
-  BVH_HIP(hipMemcpy(d_boxes, boxes6, (size_t)n * sizeof(DBox), hipMemcpyHostToDevice));
-  bvh_root<<<dim3(1), dim3(1024)>>>(d_nodes, d_prim, d_boxes, n);
+  if (n == 0 || n > ws->build_prims || n > ws->prims) return false;
+  bvh_root<<<dim3(1), dim3(1024), 0, s>>>(d_nodes, d_prim, d_boxes, n);
   while (count) {
     // One launch + one blocking read-back per level.  A usable tree is at most 48 levels deep (kMaxBlasDepth; deeper ones are
     // refused at commit), while a degenerate input - every centre equal - peels one primitive per level: leave those to the
     // host builder's verdict instead of ~4n round trips.
     if (++levels > 512u) { ok = false; goto done; }
     uint32_t nsplit = 0;
-    bvh_level_plan<<<dim3(1), dim3(1024)>>>(d_nodes, first, count, max_leaf, (uint32_t)total, d_child, d_ns);
+    bvh_level_plan<<<dim3(1), dim3(1024), 0, s>>>(d_nodes, first, count, max_leaf, (uint32_t)total, d_child, d_ns);
     // block size by the level's width (a proxy for its node sizes): a slice of k primitives is walked k / block steps per pass
     const uint32_t threads = (first == 0 || count <= 64u) ? 1024u : (count <= 4096u ? 256u : 64u);
-    bvh_level_split<<<dim3(count), dim3(threads)>>>(d_nodes, first, d_child, d_prim, d_boxes, d_l, d_r);
-    BVH_HIP(hipMemcpy(&nsplit, d_ns, 4, hipMemcpyDeviceToHost));
+    bvh_level_split<<<dim3(count), dim3(threads), 0, s>>>(d_nodes, first, d_child, d_prim, d_boxes, d_l, d_r);
+    BVH_HIP(hipMemcpyAsync(&nsplit, d_ns, 4, hipMemcpyDeviceToHost, s));
+    BVH_HIP(hipStreamSynchronize(s));
     BVH_HIP(hipGetLastError());
     // the host build gives up when a node is about to split with more than node_limit nodes in the array; the level's last
     // splitting node sees the most (the reference would never return from such a build)
@@ -276,14 +304,28 @@ bool build_bvh_device(const float* boxes6, uint32_t n, uint32_t max_leaf, HostBV
   }
   out->nodes.resize(total);
   out->prim.resize(n);
-  BVH_HIP(hipMemcpy(out->nodes.data(), d_nodes, total * sizeof(DNode), hipMemcpyDeviceToHost));
-  BVH_HIP(hipMemcpy(out->prim.data(), d_prim, (size_t)n * 4, hipMemcpyDeviceToHost));
+  BVH_HIP(hipMemcpyAsync(out->nodes.data(), d_nodes, total * sizeof(DNode), hipMemcpyDeviceToHost, s));
+  BVH_HIP(hipMemcpyAsync(out->prim.data(), d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  BVH_HIP(hipStreamSynchronize(s));
 done:
-  (void)hipFree(d_boxes); (void)hipFree(d_nodes); (void)hipFree(d_prim); (void)hipFree(d_l); (void)hipFree(d_r); (void)hipFree(d_child); (void)hipFree(d_ns);
   if (!ok) {
     out->nodes.clear(); out->prim.clear();
-    (void)hipGetLastError();   // the caller falls back to the host build: a failed hipMalloc here must not surface as the error of a later, unrelated launch
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();   // the caller falls back to the host build: a failure here must not surface as the error of a later, unrelated launch
   }
+  return ok;
+}
+
+// The device builder behind build_bvh (pt_scene.cpp) for large primitive sets.  `boxes6`: n x {mn[3], mx[3]} on the host.
+// Returns false when the build does not terminate (as the host build does) or a HIP call fails (out->nodes is then empty and
+// the caller falls back to reporting the host builder's verdict).  A workspace of its own per build, on the null stream.
+bool build_bvh_device(const float* boxes6, uint32_t n, uint32_t max_leaf, HostBVH* out) {
+  BvhWorkspace ws;
+  out->nodes.clear(); out->prim.clear();
+  bool ok = bvh_workspace_reserve(&ws, n, false) && hipMemcpy(ws.d_boxes, boxes6, (size_t)n * sizeof(DBox), hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && build_bvh_device_core(&ws, nullptr, n, max_leaf, out);
+  bvh_workspace_free(&ws);
+  if (!ok) (void)hipGetLastError();
   return ok;
 }
 

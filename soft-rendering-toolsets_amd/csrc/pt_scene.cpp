@@ -275,6 +275,38 @@ void make_wave_lazy(const std::vector<WaveInterior>& wave, const std::vector<Obj
   }
 }
 
+// The triangle records of mesh `m` in `order` (index order without one), appended to the three arrays.
+void append_triangles(const MeshInput& m, const std::vector<uint32_t>* order, std::vector<Tri>* tris, std::vector<TriNrm>* tri_nrm,
+                      std::vector<float>* tri_packed) {
+  const uint32_t ntri = (uint32_t)m.idx.size() / 3;
+  for (uint32_t k = 0; k < ntri; k++) {
+    const uint32_t t = order ? (*order)[k] : k;
+    const float* p0 = &m.pos[3 * m.idx[3 * t]];
+    const float* p1 = &m.pos[3 * m.idx[3 * t + 1]];
+    const float* p2 = &m.pos[3 * m.idx[3 * t + 2]];
+    Tri g;
+    TriNrm nn;
+    std::memset(&g, 0, sizeof g);
+    std::memset(&nn, 0, sizeof nn);
+    for (int a = 0; a < 3; a++) {
+      g.p0[a] = p0[a];
+      g.e1[a] = p1[a] - p0[a];  // p0p1, student/tri_mesh.cpp:60
+      g.e2[a] = p2[a] - p0[a];  // p0p2
+      nn.n0[a] = m.nrm[3 * m.idx[3 * t] + a];
+      nn.n1[a] = m.nrm[3 * m.idx[3 * t + 1] + a];
+      nn.n2[a] = m.nrm[3 * m.idx[3 * t + 2] + a];
+    }
+    tris->push_back(g);
+    tri_nrm->push_back(nn);
+    for (int a = 0; a < 3; a++) tri_packed->push_back(g.p0[a]);
+    for (int a = 0; a < 3; a++) tri_packed->push_back(g.e1[a]);
+    for (int a = 0; a < 3; a++) tri_packed->push_back(g.e2[a]);
+  }
+}
+
+// A leaf child of a BVH<Triangle> interior record: ~((first triangle slot << 3) | triangle count)
+uint32_t blas_leaf_code(const HostNode& leaf) { return (leaf.start << 3) | (leaf.size & 7u); }
+
 // Term tables of Mat4::inverse / Mat4::det: digit pairs are (col,row); the order of terms and of the
 // factors inside a term fixes the fp32 rounding, so it is data (lib/mat4.h:206-231, 296-343).
 const char* const kInverseTerms[16] = {
@@ -439,32 +471,6 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
   F.max_tlas_depth = T.depth;
   F.wave_tlas = T.wave;
 
-  auto append_triangles = [&](const MeshInput& m, const std::vector<uint32_t>* order) {
-    const uint32_t ntri = (uint32_t)m.idx.size() / 3;
-    for (uint32_t k = 0; k < ntri; k++) {
-      const uint32_t t = order ? (*order)[k] : k;
-      const float* p0 = &m.pos[3 * m.idx[3 * t]];
-      const float* p1 = &m.pos[3 * m.idx[3 * t + 1]];
-      const float* p2 = &m.pos[3 * m.idx[3 * t + 2]];
-      Tri g;
-      TriNrm nn;
-      std::memset(&g, 0, sizeof g);
-      std::memset(&nn, 0, sizeof nn);
-      for (int a = 0; a < 3; a++) {
-        g.p0[a] = p0[a];
-        g.e1[a] = p1[a] - p0[a];  // p0p1, student/tri_mesh.cpp:60
-        g.e2[a] = p2[a] - p0[a];  // p0p2
-        nn.n0[a] = m.nrm[3 * m.idx[3 * t] + a];
-        nn.n1[a] = m.nrm[3 * m.idx[3 * t + 1] + a];
-        nn.n2[a] = m.nrm[3 * m.idx[3 * t + 2] + a];
-      }
-      F.tris.push_back(g);
-      F.tri_nrm.push_back(nn);
-      for (int a = 0; a < 3; a++) F.tri_packed.push_back(g.p0[a]);
-      for (int a = 0; a < 3; a++) F.tri_packed.push_back(g.e1[a]);
-      for (int a = 0; a < 3; a++) F.tri_packed.push_back(g.e2[a]);
-    }
-  };
   // Every mesh is stored once, where object order first reaches it or one of its instances.
   B.store.assign(nobj, MeshStore());
   std::vector<bool> stored(nobj, false);
@@ -485,11 +491,11 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
         F.max_blas_depth = std::max(F.max_blas_depth, interior_depth(B.blas[src]));
         // interior records of this BLAS: a leaf child is ~((first triangle slot << 3) | triangle count)
         m.rec_base = (uint32_t)F.blas_recs.size();
-        append_records(B.blas[src], [](const HostNode& leaf) { return (leaf.start << 3) | (leaf.size & 7u); }, &F.blas_recs);
+        append_records(B.blas[src], blas_leaf_code, &F.blas_recs);
         m.nrec = (uint32_t)F.blas_recs.size() - m.rec_base;
-        append_triangles(in.mesh, &B.blas[src].prim);
+        append_triangles(in.mesh, &B.blas[src].prim, &F.tris, &F.tri_nrm, &F.tri_packed);
       } else {
-        append_triangles(in.mesh, nullptr);
+        append_triangles(in.mesh, nullptr, &F.tris, &F.tri_nrm, &F.tri_packed);
       }
     }
     B.store[i] = B.store[src];
@@ -520,7 +526,7 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
       L.pdfT = mat_mul(id, in.trans);
       L.pdfiT = mat_mul(itrans[i], id);
     }
-    append_triangles(in.mesh, nullptr);
+    append_triangles(in.mesh, nullptr, &F.tris, &F.tri_nrm, &F.tri_packed);
     for (uint32_t t = 0; t < L.ntri; t++) {
       LightTri lt;
       std::memset(&lt, 0, sizeof lt);
@@ -587,6 +593,142 @@ void apply_repose(BuiltScene* built, ReposedTop* top) {
   F.objects.swap(top->objects);
   B.tlas.nodes.swap(top->tlas.nodes);
   B.tlas.prim.swap(top->tlas.prim);
+}
+
+std::string check_mesh_update(const BuiltScene& B, uint32_t object, uint32_t nverts) {
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  if (object >= nobj) return "object " + std::to_string(object) + " is out of range (the scene has " + std::to_string(nobj) + " objects)";
+  const ObjectInput& in = B.inputs[object];
+  if (in.kind != OBJ_MESH) return "object " + std::to_string(object) + " is a sphere, not a mesh added by srt_pt_add_mesh";
+  if (in.source >= 0)
+    return "object " + std::to_string(object) + " is an instance: update its source, object " + std::to_string(in.source) + ", and every instance follows";
+  if (in.is_light)
+    return "object " + std::to_string(object) + " is an area light: its light-list copy and light tables depend on its vertices, commit the scene again";
+  if ((size_t)nverts * 3 != in.mesh.pos.size())
+    return "object " + std::to_string(object) + " was added with " + std::to_string(in.mesh.pos.size() / 3) + " vertices, not " + std::to_string(nverts);
+  return "";
+}
+
+std::string prepare_mesh_update(const BuiltScene& B, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                                HostBVH* prebuilt, MeshUpdate* out, bool* bad_argument) {
+  *bad_argument = true;
+  const std::string refused = check_mesh_update(B, object, nverts);
+  if (!refused.empty()) return refused;
+  *bad_argument = false;
+  const bool use_bvh = B.flat.use_bvh;
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  MeshUpdate& U = *out;
+  U = MeshUpdate();
+  U.object = object;
+  U.pos.assign(pos, pos + 3 * (size_t)nverts);
+  U.nrm.assign(nrm, nrm + 3 * (size_t)nverts);
+  MeshInput m;                                     // the mesh as a fresh commit would be given it (the arrays are moved back out below)
+  m.pos.swap(U.pos); m.nrm.swap(U.nrm);
+  m.idx = B.inputs[object].mesh.idx;
+  const uint32_t ntri = (uint32_t)m.idx.size() / 3;
+
+  // Tri_Mesh::build (leaf size 4) or List<Triangle>, and the object-space box, as build_scene has them
+  Box ob;
+  if (use_bvh && prebuilt) {
+    U.blas.nodes.swap(prebuilt->nodes);
+    U.blas.prim.swap(prebuilt->prim);
+  } else {
+    std::vector<Box> tb(ntri);
+    for (uint32_t t = 0; t < ntri; t++)
+      tb[t] = triangle_box(&m.pos[3 * m.idx[3 * t]], &m.pos[3 * m.idx[3 * t + 1]], &m.pos[3 * m.idx[3 * t + 2]]);
+    if (use_bvh) {
+      if (!build_bvh(tb, 4, &U.blas))
+        return "BVH<Triangle> build of object " + std::to_string(object) +
+               " does not terminate (coincident centroids); the reference loops forever on this mesh";
+    } else {
+      for (const Box& b : tb) ob.enclose(b);  // List<Triangle>::bbox
+    }
+  }
+  if (use_bvh) {
+    const HostNode& root = U.blas.nodes[0];
+    for (int a = 0; a < 3; a++) { ob.mn[a] = root.mn[a]; ob.mx[a] = root.mx[a]; }
+    append_nodes(U.blas, &U.nodes);
+    append_records(U.blas, blas_leaf_code, &U.recs);
+    append_triangles(m, &U.blas.prim, &U.tris, &U.tri_nrm, &U.tri_packed);
+  } else {
+    append_triangles(m, nullptr, &U.tris, &U.tri_nrm, &U.tri_packed);
+  }
+  m.pos.swap(U.pos); m.nrm.swap(U.nrm);
+
+  // the mesh and its instances take the new box and the new range lengths; what is stored behind the mesh moves by the difference
+  // (a mesh has at least one node, so node_off orders the stored meshes)
+  U.local_boxes = B.local_boxes;
+  U.store = B.store;
+  const MeshStore old = B.store[object];
+  const int64_t dn = (int64_t)U.nodes.size() - (int64_t)old.nnodes, dr = (int64_t)U.recs.size() - (int64_t)old.nrec;
+  U.max_blas_depth = interior_depth(U.blas);
+  for (uint32_t i = 0; i < nobj; i++) {
+    const ObjectInput& in = B.inputs[i];
+    if (in.kind != OBJ_MESH) continue;
+    if (i == object || in.source == (int32_t)object) {
+      for (int a = 0; a < 3; a++) { U.local_boxes[6 * (size_t)i + a] = ob.mn[a]; U.local_boxes[6 * (size_t)i + 3 + a] = ob.mx[a]; }
+      U.store[i].nnodes = (uint32_t)U.nodes.size();
+      U.store[i].nrec = (uint32_t)U.recs.size();
+    } else if (use_bvh && U.store[i].node_off > old.node_off) {
+      U.store[i].node_off = (uint32_t)((int64_t)U.store[i].node_off + dn);
+      U.store[i].rec_base = (uint32_t)((int64_t)U.store[i].rec_base + dr);
+    }
+    if (i != object && in.source < 0) U.max_blas_depth = std::max(U.max_blas_depth, interior_depth(B.blas[i]));
+  }
+
+  std::vector<Mat4> trans(nobj);
+  for (uint32_t i = 0; i < nobj; i++) trans[i] = B.inputs[i].trans;
+  Top T;
+  if (!build_top(trans, U.local_boxes, use_bvh, &T)) return "BVH<Object> build does not terminate (coincident object centroids)";
+  ReposedTop& R = U.top;
+  make_objects(B.inputs, trans, T, U.store, (uint32_t)T.nodes.size(), use_bvh, &R.objects, &R.lazy_objects);
+  make_wave_lazy(T.wave, R.objects, &R.wave_lazy);
+  R.tlas.nodes.swap(T.tlas.nodes);
+  R.tlas.prim.swap(T.tlas.prim);
+  R.tlas_nodes.swap(T.nodes);
+  R.wave_tlas.swap(T.wave);
+  R.max_tlas_depth = T.depth;
+  return "";
+}
+
+void apply_mesh_update(BuiltScene* built, MeshUpdate* update) {
+  BuiltScene& B = *built;
+  FlatScene& F = B.flat;
+  MeshUpdate& U = *update;
+  const MeshStore old = B.store[U.object];
+  B.inputs[U.object].mesh.pos.swap(U.pos);
+  B.inputs[U.object].mesh.nrm.swap(U.nrm);
+  B.blas[U.object].nodes.swap(U.blas.nodes);
+  B.blas[U.object].prim.swap(U.blas.prim);
+  B.local_boxes.swap(U.local_boxes);
+  B.store.swap(U.store);
+  // the triangle range stays where it is
+  std::copy(U.tris.begin(), U.tris.end(), F.tris.begin() + old.tri_base);
+  std::copy(U.tri_nrm.begin(), U.tri_nrm.end(), F.tri_nrm.begin() + old.tri_base);
+  std::copy(U.tri_packed.begin(), U.tri_packed.end(), F.tri_packed.begin() + 9 * (size_t)old.tri_base);
+  if (F.use_bvh) {
+    // records: [ .. the mesh's .. what lies behind ]
+    std::vector<WaveInterior> recs(F.blas_recs.begin(), F.blas_recs.begin() + old.rec_base);
+    recs.insert(recs.end(), U.recs.begin(), U.recs.end());
+    recs.insert(recs.end(), F.blas_recs.begin() + old.rec_base + old.nrec, F.blas_recs.end());
+    F.blas_recs.swap(recs);
+    // nodes: [ new BVH<Object> | BVH<Triangle>s in front | the mesh's | those behind ]
+    const size_t at = (size_t)F.tlas_nodes + old.node_off;
+    std::vector<Node> nodes(U.top.tlas_nodes);
+    nodes.insert(nodes.end(), F.nodes.begin() + F.tlas_nodes, F.nodes.begin() + at);
+    nodes.insert(nodes.end(), U.nodes.begin(), U.nodes.end());
+    nodes.insert(nodes.end(), F.nodes.begin() + at + old.nnodes, F.nodes.end());
+    F.nodes.swap(nodes);
+  }
+  F.tlas_nodes = (uint32_t)U.top.tlas_nodes.size();
+  F.max_tlas_depth = U.top.max_tlas_depth;
+  F.max_blas_depth = U.max_blas_depth;
+  F.wave_tlas.swap(U.top.wave_tlas);
+  F.wave_lazy.swap(U.top.wave_lazy);
+  F.lazy_objects.swap(U.top.lazy_objects);
+  F.objects.swap(U.top.objects);
+  B.tlas.nodes.swap(U.top.tlas.nodes);
+  B.tlas.prim.swap(U.top.tlas.prim);
 }
 
 }  // namespace srt

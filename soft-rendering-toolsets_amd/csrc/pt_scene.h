@@ -194,6 +194,38 @@ std::string prepare_repose(const BuiltScene& built, const uint32_t* objects, con
                            bool* bad_argument);
 void apply_repose(BuiltScene* built, ReposedTop* top);
 
+// What srt_pt_update_mesh derives for new vertex arrays of ONE mesh of a built scene (an object added by srt_pt_add_mesh: not an
+// instance, a sphere or an area light; same vertex count, same index buffer), built next to the scene: the mesh's
+// BVH<Triangle> (leaf size 4; none in list mode), its flattened nodes, interior records and triangle records, the object-space
+// box of the mesh and of its instances, and - because those boxes changed - the BVH<Object> and the tables that follow object
+// order, as prepare_repose derives them.  The triangle range of the mesh never moves (the triangle count is fixed); its node
+// and record ranges may have another length, and the ranges stored behind them are re-packed: `store` holds every object's new
+// offsets.  prepare_mesh_update leaves `built` untouched; apply_mesh_update moves everything in (it cannot fail).
+struct MeshUpdate {
+  uint32_t object = 0;
+  std::vector<float> pos, nrm;
+  HostBVH blas;
+  std::vector<Node> nodes;            // the mesh's BVH<Triangle>, flattened
+  std::vector<WaveInterior> recs;     // its interior records
+  std::vector<Tri> tris;              // its triangle range, in the new primitive order
+  std::vector<TriNrm> tri_nrm;
+  std::vector<float> tri_packed;
+  std::vector<float> local_boxes;     // of every object
+  std::vector<MeshStore> store;       // of every object
+  uint32_t max_blas_depth = 0;        // over all stored meshes
+  ReposedTop top;                     // (listed / trans stay empty: no pose changes)
+};
+// "" or why `object` of `built` cannot take new arrays of nverts vertices (out of range, a sphere, an instance, an area light,
+// another vertex count).
+std::string check_mesh_update(const BuiltScene& built, uint32_t object, uint32_t nverts);
+// pos / nrm: 3 floats per vertex.  `prebuilt`: the BVH<Triangle> of the new arrays where the caller has built it already (on the
+// device, from boxes computed there; bit-equal to the host build; its arrays are moved from) - otherwise it is built here, by
+// build_scene's rule.  Returns ""
+// or an error message; *bad_argument tells a refused argument (check_mesh_update) from a build that does not terminate.
+std::string prepare_mesh_update(const BuiltScene& built, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                                HostBVH* prebuilt, MeshUpdate* out, bool* bad_argument);
+void apply_mesh_update(BuiltScene* built, MeshUpdate* update);
+
 Camera make_camera(const float iview[16], float vert_fov_deg, float aspect_ratio);
 
 // Delta_Light ctor: itrans = T.inverse(), has_trans = T != I.

@@ -224,3 +224,19 @@ def share_meshes(description: dict) -> dict:
         objs.append(o)
     out["objects"] = objs
     return out
+
+
+def with_vertices(description: dict, index: int, pos, nrm) -> dict:
+    """The description with new vertex positions and normals for mesh object `index` (same vertex count, same idx): what a fresh
+    commit after Pathtracer.update_mesh(index, pos, nrm) is given.  Instances of the object keep pointing at it."""
+    o = description["objects"][int(index)]
+    if o["kind"] != "mesh":
+        raise ValueError(f"object {index} is {o['kind']!r}, not a mesh")
+    pos, nrm = np.ascontiguousarray(pos, F).reshape(-1, 3), np.ascontiguousarray(nrm, F).reshape(-1, 3)
+    if len(pos) != len(o["pos"]) or len(nrm) != len(o["pos"]):
+        raise ValueError(f"object {index} has {len(o['pos'])} vertices, not {len(pos)} / {len(nrm)}")
+    out = dict(description)
+    objs = list(description["objects"])
+    objs[int(index)] = dict(o, pos=pos, nrm=nrm)
+    out["objects"] = objs
+    return out
