@@ -242,6 +242,60 @@ int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, cons
  * arrays are copied back once (24 B per vertex) so that the host's record of the scene stays true; with the host builder, or a
  * mesh below the device builder's threshold, the triangle boxes are computed from that copy. */
 int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts);
+
+/* ---- Skinning: Skeleton::find_joints and Skeleton::skin on the device ----
+ * What Scene_Object::sync_anim_mesh (scene/object.cpp:106-129) does on the CPU per frame - Skeleton::find_joints
+ * (student/skeleton.cpp:219-256), Skeleton::skin (:258-307) and, without smooth normals, the flat-normal loop (:114-126) - as
+ * kernels whose output feeds srt_pt_update_mesh_device: a frame of a skinned mesh sends 64 B per joint up and nothing else.
+ * A skin is bound to one context and to one object of its committed scene added by srt_pt_add_mesh.  Results equal the
+ * reference's bit for bit (x86-64, no contraction); where the reference yields NaN (a vertex ON a bone has distance 0 and
+ * weight inf / inf) so do the kernels, up to the NaN's sign and payload.
+ * Limits (SRT_ERR_UNSUPPORTED beyond): at most 4096 joints per skin, and nverts * njoints <= 2^31 (the map's offsets are
+ * 32-bit).  Destroy a context's skins before the context. */
+typedef struct srt_pt_skin srt_pt_skin; /* opaque */
+/* One joint: `bind` is Skeleton::joint_to_bind(j) in Mat4::data order (column-major), extent and radius are Joint::extent and
+ * Joint::radius.  The caller lists the joints in the order Skeleton::for_joints visits them; that order is part of the result: a
+ * vertex's influence list, and so the order of its float sums, follows it. */
+typedef struct srt_pt_skin_joint {
+    float bind[16];
+    float extent[3];
+    float radius;
+} srt_pt_skin_joint;
+/* find_joints.  Needs a committed scene (SRT_ERR_STATE).  `object`, and SRT_ERR_INVALID with its messages for a NULL argument,
+ * an index out of range, a sphere, an instance, an area light and nverts differing from the committed count, are as for
+ * srt_pt_update_mesh; njoints == 0 is SRT_ERR_INVALID too.  bind_positions / bind_normals (nverts * 3 floats each) are the
+ * object's bind-pose mesh - the committed vertices may already be a posed frame - and stay on the device with the skin.  The host
+ * computes Mat4::inverse(bind) (lib/mat4.h:299-351, the `/= det()` included) once per joint; kernels build the vertex -> joints
+ * map as CSR (count, exclusive scan, fill; a vertex's joints in ascending index) with the reference's capsule test per (vertex,
+ * joint) - inverse * pos through Vec4::project, closest_on_line_segment (:195-217) as written, norm() <= radius - and store each
+ * influence's weight (1.0f / distance) / sum_of_inv_dis (:280-299), summed in list order: weights do not depend on the pose, so
+ * computing them once is what the reference recomputes per frame.  Waits for the device.  A host-only context (device = -1)
+ * validates the arguments and returns SRT_ERR_UNSUPPORTED: skinning has no CPU path. */
+int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions, const float* bind_normals, uint32_t nverts,
+                       const srt_pt_skin_joint* joints, uint32_t njoints, srt_pt_skin** skin);
+/* Waits for the device, frees the skin.  NULL is fine. */
+int srt_pt_skin_destroy(srt_pt_skin* skin);
+/* out = {vertices, joints, influences in the map, triangles}. */
+int srt_pt_skin_counts(srt_pt_skin* skin, uint32_t out[4]);
+/* The map, copied back for inspection: offsets[nverts + 1]; joints[k] and weights[k] for k in [offsets[v], offsets[v + 1]) are
+ * vertex v's influences.  cap: what joints / weights hold; below the influence count is SRT_ERR_INVALID. */
+int srt_pt_skin_map(srt_pt_skin* skin, uint32_t* offsets, uint32_t* joints, float* weights, uint32_t cap);
+/* skin.  posed: njoints * 16 host floats, Skeleton::joint_to_posed(j) in the joints' order, read before the call returns.  The host
+ * forms M_j = posed_j * inverse_bind_j with Mat4::operator*'s loop (lib/mat4.h:136-147) and uploads 64 B per joint; one lane per
+ * vertex sums w_ij * (M_j * pos) in list order (M * Vec3: v0 col0 + v1 col1 + v2 col2 + 1.0f col3, then project()); a vertex
+ * with no joint keeps its bind position (:293).  flat_normals == 0: the normals are the bind normals (skin does not touch them);
+ * != 0: those of sync_anim_mesh without smooth normals (:114-126) - a vertex gets cross(v1 - v0, v2 - v0).unit() of the LAST
+ * triangle in index order that names it, its bind normal when none does.  The two outputs are device arrays of nverts * 3 floats.
+ * Enqueues on `stream` (a hipStream_t; NULL: the null stream) and returns: no synchronisation.  Calls on one skin use one stream
+ * at a time. */
+int srt_pt_skin_vertices_device(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals, float* d_positions_out, float* d_normals_out);
+/* The same into host arrays, through the skin's staging on the context's stream; waits. */
+int srt_pt_skin_vertices(srt_pt_skin* skin, const float* posed, int flat_normals, float* positions_out, float* normals_out);
+/* Skins into the skin's staging on `stream`, then srt_pt_update_mesh_device(pt, stream, object, staging, nverts): preconditions,
+ * errors and "the committed scene stays as it was on failure" are exactly that call's for those arrays. */
+int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
+/* Every call on a skin but destroy and counts returns SRT_ERR_STATE once its context's scene was begun or committed again (the
+ * skin is stale: destroy it, create another), and SRT_ERR_INVALID for a NULL argument. */
 /* Where srt_pt_scene_commit runs BVH<Primitive>::build (student/bvh.inl:35-163): device != 0 (default) builds primitive sets of at
  * least min_primitives (default 16384) on the GPU, smaller ones and device == 0 on the host.  Both produce the reference's node
  * arrays and primitive order bit for bit (the candidate planes' std::partition sequence included); SRT_BVH_BUILDER=host in the

@@ -58,6 +58,13 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_repose.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_update_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_update_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_skin_create.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]
+    lib.srt_pt_skin_destroy.argtypes = [c_void_p]
+    lib.srt_pt_skin_counts.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_skin_map.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_skin_vertices_device.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.srt_pt_skin_vertices.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.srt_pt_skin_pose.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
     lib.srt_pt_scene_counts.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_set_bvh_builder.argtypes = [c_void_p, c_int, c_uint32]
     lib.srt_pt_set_stream_slots.argtypes = [c_void_p, c_uint32]
@@ -132,6 +139,100 @@ def _p(a):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+SKIN_JOINT_DTYPE = np.dtype([("bind", np.float32, 16), ("extent", np.float32, 3), ("radius", np.float32)])   # srt_pt_skin_joint
+
+
+def skin_joints(joints) -> np.ndarray:
+    """srt_pt_skin_joint records from an array of SKIN_JOINT_DTYPE or a sequence of (bind16, extent3, radius) / dicts with those keys,
+    in Skeleton::for_joints order."""
+    if isinstance(joints, np.ndarray) and joints.dtype == SKIN_JOINT_DTYPE:
+        return np.ascontiguousarray(joints)
+    out = np.zeros(len(joints), SKIN_JOINT_DTYPE)
+    for k, j in enumerate(joints):
+        bind, extent, radius = (j["bind"], j["extent"], j["radius"]) if isinstance(j, dict) else j
+        out[k] = (_f32(bind).reshape(16), _f32(extent).reshape(3), np.float32(radius))
+    return out
+
+
+class Skin:
+    """srt_pt_skin: Skeleton::find_joints done once at creation (Pathtracer.create_skin), Skeleton::skin per call.  `posed` is
+    (njoints, 16): Skeleton::joint_to_posed(j) in Mat4::data order, in the joints' order."""
+
+    def __init__(self, pt, handle, nverts: int, njoints: int):
+        self._pt, self._lib, self._check = pt, pt._lib, pt._check
+        self._h = handle
+        self.nverts, self.njoints = nverts, njoints
+
+    def _posed(self, posed):
+        posed = _f32(posed).reshape(-1, 16)
+        if len(posed) != self.njoints:
+            raise ValueError(f"{len(posed)} posed matrices for {self.njoints} joints")
+        return posed
+
+    def counts(self) -> dict:
+        out = np.zeros(4, np.uint32)
+        self._check(self._lib, self._lib.srt_pt_skin_counts(self._h, _p(out)))
+        return dict(zip(("vertices", "joints", "influences", "triangles"), (int(v) for v in out)))
+
+    def map(self):
+        """(offsets[nverts + 1], joints[n], weights[n]): vertex v's influences are [offsets[v], offsets[v + 1])."""
+        n = self.counts()["influences"]
+        off, jidx, w = np.zeros(self.nverts + 1, np.uint32), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32)
+        self._check(self._lib, self._lib.srt_pt_skin_map(self._h, _p(off), _p(jidx), _p(w), n))
+        return off, jidx[:n], w[:n]
+
+    def vertices(self, posed, flat_normals: bool = False):
+        """srt_pt_skin_vertices: the skinned (positions, normals), (nverts, 3) each."""
+        posed = self._posed(posed)
+        pos, nrm = np.zeros((self.nverts, 3), np.float32), np.zeros((self.nverts, 3), np.float32)
+        self._check(self._lib, self._lib.srt_pt_skin_vertices(self._h, _p(posed), int(bool(flat_normals)), _p(pos), _p(nrm)))
+        return pos, nrm
+
+    def vertices_device(self, posed, d_pos_ptr: int, d_nrm_ptr: int, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_vertices_device: the same into two device arrays of nverts * 3 floats; only enqueues."""
+        posed = self._posed(posed)
+        self._check(self._lib, self._lib.srt_pt_skin_vertices_device(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals)),
+                                                                     c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr)))
+
+    def pose(self, posed, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose: skin, then srt_pt_update_mesh_device with the result - the committed mesh takes the pose."""
+        posed = self._posed(posed)
+        self._check(self._lib, self._lib.srt_pt_skin_pose(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals))))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.srt_pt_skin_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self._pt._ctx:                # (a skin is destroyed before its context; after it, there is nothing left to free safely)
+                self.close()
+        except Exception:
+            pass
+
+
+class SkinGroup:
+    """PathtracerGroup.create_skin: one Skin per rank (the scene is replicated), posed together."""
+
+    def __init__(self, skins):
+        self.skins = skins
+
+    def map(self):
+        return self.skins[0].map()
+
+    def vertices(self, posed, flat_normals: bool = False):
+        return self.skins[0].vertices(posed, flat_normals)
+
+    def pose(self, posed, flat_normals: bool = False) -> None:
+        for k in self.skins:
+            k.pose(posed, flat_normals)
+
+    def close(self) -> None:
+        for k in self.skins:
+            k.close()
 
 
 class Scene:
@@ -253,6 +354,17 @@ class Pathtracer:
     def update_mesh_device(self, index: int, d_pos_ptr: int, d_nrm_ptr: int, nverts: int, stream: int = 0) -> None:
         """srt_pt_update_mesh_device: the same from two device arrays of nverts * 3 floats (e.g. tensor.data_ptr())."""
         self._check(self._lib, self._lib.srt_pt_update_mesh_device(self._ctx, c_void_p(stream), int(index), c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr), int(nverts)))
+
+    def create_skin(self, index: int, bind_pos, bind_nrm, joints) -> Skin:
+        """srt_pt_skin_create: Skeleton::find_joints for the mesh object with this insertion index of the committed scene, from its
+        bind-pose arrays ((nverts, 3) each) and its joints (skin_joints(..)) in Skeleton::for_joints order."""
+        pos, nrm = _f32(bind_pos).reshape(-1, 3), _f32(bind_nrm).reshape(-1, 3)
+        if len(pos) != len(nrm):
+            raise ValueError(f"{len(pos)} positions but {len(nrm)} normals")
+        J = skin_joints(joints)
+        h = c_void_p()
+        self._check(self._lib, self._lib.srt_pt_skin_create(self._ctx, int(index), _p(pos), _p(nrm), len(pos), _p(J), len(J), ctypes.byref(h)))
+        return Skin(self, h, len(pos), len(J))
 
     def scene_counts(self) -> dict:
         """srt_pt_scene_counts: what the scene stores, the BVH<Triangle> builds so far and the bytes uploaded (SCENE_COUNT_NAMES)."""
@@ -596,6 +708,18 @@ class PathtracerGroup:
     def update_mesh(self, index: int, pos, nrm) -> None:
         for m in self.members:
             m.update_mesh(index, pos, nrm)
+
+    def create_skin(self, index: int, bind_pos, bind_nrm, joints) -> SkinGroup:
+        """One skin per rank; SkinGroup.pose poses each rank, as update_mesh updates each."""
+        skins = []
+        try:
+            for m in self.members:
+                skins.append(m.create_skin(index, bind_pos, bind_nrm, joints))
+        except Exception:
+            for k in skins:
+                k.close()
+            raise
+        return SkinGroup(skins)
 
     def scene_counts(self) -> list:
         """Every member's Pathtracer.scene_counts(), by rank (the scene is replicated)."""

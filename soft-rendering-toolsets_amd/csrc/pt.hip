@@ -27,6 +27,7 @@
 #include "pt_bvh_device.h"
 #include "pt_device.h"
 #include "pt_scene.h"
+#include "pt_skin.h"
 #include "srt_common.h"
 #include "srt_pt.h"
 #include "srt_pt_debug.h"
@@ -448,6 +449,8 @@ struct srt_pt {
   BvhWorkspace bvh_ws;
   float* d_vpos = nullptr; size_t vpos_floats = 0;
   float* d_vnrm = nullptr; size_t vnrm_floats = 0;
+  // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
+  uint64_t scene_generation = 0;
 };
 
 namespace {
@@ -1137,6 +1140,7 @@ int srt_pt_scene_begin(srt_pt* pt) {
   pt->env_type = 0;
   pt->env_map.clear(); pt->env_w = pt->env_h = 0;
   pt->committed = false;
+  pt->scene_generation++;
   return SRT_OK;
 }
 
@@ -1296,6 +1300,7 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
     if ((st = upload(pt, &pt->d_idx, idx))) return st;
   }
   pt->committed = true;
+  pt->scene_generation++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   return SRT_OK;
 }
@@ -1449,6 +1454,194 @@ int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const f
   if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh_device: NULL argument");
   return update_mesh(pt, "srt_pt_update_mesh_device", (hipStream_t)stream, object, nullptr, nullptr, d_positions, d_normals, nverts);
 }
+
+}  // extern "C"
+
+// ---- srt_pt_skin: Skeleton::find_joints once, Skeleton::skin per frame (pt_skin.h, pt_skin.hip) ----
+struct srt_pt_skin {
+  srt_pt* pt = nullptr;
+  uint64_t generation = 0;                  // pt->scene_generation at creation
+  uint32_t object = 0, nverts = 0, ntri = 0, njoints = 0, ninf = 0;
+  std::vector<float> inv;                   // Mat4::inverse(joint_to_bind(j)), 16 floats per joint
+  std::vector<float> mats;                  // the frame's posed_j * inverse_j on their way up
+  float *d_pos = nullptr, *d_nrm = nullptr;             // the bind-pose mesh
+  float *d_inv = nullptr, *d_cap = nullptr, *d_mats = nullptr;
+  uint32_t *d_off = nullptr, *d_jidx = nullptr, *d_last = nullptr;
+  float* d_w = nullptr;
+  float *d_pos_out = nullptr, *d_nrm_out = nullptr;     // srt_pt_skin_pose's staging
+};
+
+namespace {
+
+void skin_free(srt_pt_skin* k) {
+  if (k->pt && k->pt->device >= 0) (void)hipSetDevice(k->pt->device);
+  for (void* p : {(void*)k->d_pos, (void*)k->d_nrm, (void*)k->d_inv, (void*)k->d_cap, (void*)k->d_mats, (void*)k->d_off, (void*)k->d_jidx, (void*)k->d_last,
+                  (void*)k->d_w, (void*)k->d_pos_out, (void*)k->d_nrm_out})
+    if (p) (void)hipFree(p);
+  delete k;
+}
+
+// The device side of srt_pt_skin_create; on failure the caller frees what is there.
+int skin_build(srt_pt_skin* k, const float* bind_positions, const float* bind_normals, const srt_pt_skin_joint* joints) {
+  srt_pt* pt = k->pt;
+  const size_t vfloats = 3 * (size_t)k->nverts;
+  std::vector<float> cap(4 * (size_t)k->njoints);
+  for (uint32_t j = 0; j < k->njoints; j++) {
+    skin_mat4_inverse(joints[j].bind, &k->inv[16 * (size_t)j]);
+    for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = joints[j].extent[a];
+    cap[4 * (size_t)j + 3] = joints[j].radius;
+  }
+  SRT_HIP(hipSetDevice(pt->device));
+  hipStream_t s = pt->stream;
+  const uint32_t nblocks = (k->nverts + 255u) / 256u;
+  SRT_HIP(hipMalloc(&k->d_pos, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_nrm, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_pos_out, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_nrm_out, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_inv, k->inv.size() * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_mats, k->inv.size() * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_cap, cap.size() * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_off, ((size_t)k->nverts + 1) * sizeof(uint32_t)));
+  SRT_HIP(hipMalloc(&k->d_last, (size_t)k->nverts * sizeof(uint32_t)));
+  SRT_HIP(hipMemcpy(k->d_pos, bind_positions, vfloats * sizeof(float), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(k->d_nrm, bind_normals, vfloats * sizeof(float), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(k->d_inv, k->inv.data(), k->inv.size() * sizeof(float), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(k->d_cap, cap.data(), cap.size() * sizeof(float), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += (2 * vfloats + k->inv.size() + cap.size()) * sizeof(float);
+  // count, scan, fill; the counts and the block sums live only here
+  uint32_t *d_counts = nullptr, *d_sums = nullptr;
+  SRT_HIP(hipMalloc(&d_counts, (size_t)k->nverts * sizeof(uint32_t)));
+  int st = SRT_OK;
+  if (hipMalloc(&d_sums, (size_t)nblocks * sizeof(uint32_t)) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: out of device memory");
+  uint32_t total = 0;
+  if (st == SRT_OK) {
+    launch_skin_count(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, d_counts);
+    launch_skin_scan(s, d_counts, k->nverts, k->d_off, d_sums);
+    if (hipMemcpyAsync(&total, k->d_off + k->nverts, sizeof total, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
+        hipGetLastError() != hipSuccess)
+      st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: the find_joints kernels failed");
+  }
+  (void)hipFree(d_counts); (void)hipFree(d_sums);
+  if (st != SRT_OK) return st;
+  k->ninf = total;
+  SRT_HIP(hipMalloc(&k->d_jidx, (total ? (size_t)total : 1) * sizeof(uint32_t)));
+  SRT_HIP(hipMalloc(&k->d_w, (total ? (size_t)total : 1) * sizeof(float)));
+  launch_skin_fill(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, k->d_off, k->d_jidx, k->d_w);
+  SRT_HIP(hipMemsetAsync(k->d_last, 0, (size_t)k->nverts * sizeof(uint32_t), s));
+  launch_skin_last_triangle(s, pt->d_idx + pt->idx_off[k->object], k->ntri, k->nverts, k->d_last);
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int skin_usable(const srt_pt_skin* k, const char* what) {
+  if (!k) return srt::fail(SRT_ERR_INVALID, "%s: NULL skin", what);
+  if (!k->pt->committed || k->generation != k->pt->scene_generation)
+    return srt::fail(SRT_ERR_STATE, "%s: the skin is stale - its context's scene was begun or committed again after srt_pt_skin_create", what);
+  return SRT_OK;
+}
+
+// Enqueues the frame's matrices and the skinning kernels on s.
+int skin_enqueue(srt_pt_skin* k, hipStream_t s, const float* posed, int flat_normals, float* d_pos_out, float* d_nrm_out) {
+  SRT_HIP(hipSetDevice(k->pt->device));
+  for (uint32_t j = 0; j < k->njoints; j++) skin_mat4_mul(posed + 16 * (size_t)j, &k->inv[16 * (size_t)j], &k->mats[16 * (size_t)j]);
+  SRT_HIP(hipMemcpyAsync(k->d_mats, k->mats.data(), k->mats.size() * sizeof(float), hipMemcpyHostToDevice, s));   // 64 B per joint
+  k->pt->bytes_uploaded += k->mats.size() * sizeof(float);
+  launch_skin_vertices(s, k->d_pos, k->d_nrm, k->nverts, k->d_mats, k->njoints, k->d_off, k->d_jidx, k->d_w, d_pos_out, flat_normals ? nullptr : d_nrm_out);
+  if (flat_normals)
+    launch_skin_flat_normals(s, d_pos_out, k->d_nrm, k->pt->d_idx + k->pt->idx_off[k->object], k->ntri, k->d_last, k->nverts, d_nrm_out);
+  return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions, const float* bind_normals, uint32_t nverts,
+                       const srt_pt_skin_joint* joints, uint32_t njoints, srt_pt_skin** skin) {
+  if (skin) *skin = nullptr;
+  if (!pt || !bind_positions || !bind_normals || !joints || !skin) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: NULL argument");
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_skin_create before srt_pt_scene_commit");
+  const std::string refused = check_mesh_update(pt->built, object, nverts);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: %s", refused.c_str());
+  if (njoints == 0) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: a skin needs at least one joint");
+  if (njoints > kSkinMaxJoints || (uint64_t)nverts * njoints > kSkinMaxPairs)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_skin_create: %u joints on %u vertices (at most %u joints and 2^31 vertex-joint pairs)", njoints, nverts,
+                     kSkinMaxJoints);
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_skin_create: skinning runs on the device only; this context is host-only and there is no CPU path");
+  srt_pt_skin* k = new (std::nothrow) srt_pt_skin;
+  if (!k) return srt::fail(SRT_ERR_INVALID, "out of host memory");
+  k->pt = pt; k->generation = pt->scene_generation; k->object = object; k->nverts = nverts; k->njoints = njoints;
+  k->ntri = pt->built.store[object].ntri;
+  k->inv.resize(16 * (size_t)njoints);
+  k->mats.resize(16 * (size_t)njoints);
+  const int st = skin_build(k, bind_positions, bind_normals, joints);
+  if (st != SRT_OK) { skin_free(k); return st; }
+  *skin = k;
+  return SRT_OK;
+}
+
+int srt_pt_skin_destroy(srt_pt_skin* skin) {
+  if (!skin) return SRT_OK;
+  if (skin->pt->device >= 0) { (void)hipSetDevice(skin->pt->device); (void)hipDeviceSynchronize(); }
+  skin_free(skin);
+  return SRT_OK;
+}
+
+int srt_pt_skin_counts(srt_pt_skin* skin, uint32_t out[4]) {
+  if (!skin || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_counts: NULL argument");
+  out[0] = skin->nverts; out[1] = skin->njoints; out[2] = skin->ninf; out[3] = skin->ntri;
+  return SRT_OK;
+}
+
+int srt_pt_skin_map(srt_pt_skin* skin, uint32_t* offsets, uint32_t* joints, float* weights, uint32_t cap) {
+  if (!skin || !offsets || !joints || !weights) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_map: NULL argument");
+  int st = skin_usable(skin, "srt_pt_skin_map");
+  if (st != SRT_OK) return st;
+  if (cap < skin->ninf) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_map: the map has %u influences, the arrays hold %u", skin->ninf, cap);
+  SRT_HIP(hipSetDevice(skin->pt->device));
+  SRT_HIP(hipMemcpy(offsets, skin->d_off, ((size_t)skin->nverts + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (skin->ninf) {
+    SRT_HIP(hipMemcpy(joints, skin->d_jidx, (size_t)skin->ninf * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SRT_HIP(hipMemcpy(weights, skin->d_w, (size_t)skin->ninf * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return SRT_OK;
+}
+
+int srt_pt_skin_vertices_device(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals, float* d_positions_out, float* d_normals_out) {
+  if (!skin || !posed || !d_positions_out || !d_normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices_device: NULL argument");
+  const int st = skin_usable(skin, "srt_pt_skin_vertices_device");
+  if (st != SRT_OK) return st;
+  return skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, d_positions_out, d_normals_out);
+}
+
+int srt_pt_skin_vertices(srt_pt_skin* skin, const float* posed, int flat_normals, float* positions_out, float* normals_out) {
+  if (!skin || !posed || !positions_out || !normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices: NULL argument");
+  int st = skin_usable(skin, "srt_pt_skin_vertices");
+  if (st != SRT_OK) return st;
+  hipStream_t s = skin->pt->stream;
+  if ((st = skin_enqueue(skin, s, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
+  const size_t bytes = 3 * (size_t)skin->nverts * sizeof(float);
+  SRT_HIP(hipMemcpyAsync(positions_out, skin->d_pos_out, bytes, hipMemcpyDeviceToHost, s));
+  SRT_HIP(hipMemcpyAsync(normals_out, skin->d_nrm_out, bytes, hipMemcpyDeviceToHost, s));
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
+  if (!skin || !posed) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_pose: NULL argument");
+  int st = skin_usable(skin, "srt_pt_skin_pose");
+  if (st != SRT_OK) return st;
+  // (the staging is read by nothing of the context: writing it before srt_pt_update_mesh_device's verdict changes no scene)
+  if ((st = skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
+  return update_mesh(skin->pt, "srt_pt_skin_pose", (hipStream_t)stream, skin->object, nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
   if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose: NULL argument");
