@@ -243,6 +243,41 @@ int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, cons
  * mesh below the device builder's threshold, the triangle boxes are computed from that copy. */
 int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts);
 
+/* New vertex arrays for one mesh WITHOUT rebuilding its BVH<Triangle>: a refit, what every renderer of animations does for a mesh
+ * whose connectivity stays while its vertices move.  Arguments, preconditions, refusals and their messages are
+ * srt_pt_update_mesh's, plus one: a non-finite position coordinate is SRT_ERR_INVALID.  For finite vertices the mesh's
+ * BVH<Triangle> keeps its node links {start, size, l, r} and its primitive order; every leaf box becomes the BBox::enclose fold of
+ * Triangle::bbox (student/tri_mesh.cpp:7-30, the +1.0f of a flat axis included) over its triangles, every interior box the enclose
+ * of its two children's.  BVH<Primitive>::build forms every node box as such min / max folds of its primitives' boxes
+ * (student/bvh.inl:73-75, 119-123), exact and independent of order, so a refit with the committed vertices gives the committed
+ * boxes back - as values: where a bound is a zero that some triangles carry as +0 and others as -0 the fold's order picks the
+ * sign, and the build's order inside a node is its partition's; no slab test can tell the two zeros apart.  Results are those
+ * of the reference's BVH<Triangle>::hit (student/bvh.inl:166-276) and Triangle::hit on that tree.
+ * The triangle, normal and packed-triangle records are rewritten in place in the kept order, the mesh's nodes and interior
+ * records take the new boxes in place; counts never change, nothing is re-packed or reallocated, and no other mesh's storage is
+ * touched.  The object-space box of the mesh and of each of its instances becomes the new root box; the BVH<Object> and the
+ * tables of object order are replaced as in srt_pt_repose.  A device context refits on the device whatever
+ * srt_pt_set_bvh_builder says (pt_mesh_update.hip: triangle boxes, leaves, the interior levels deepest first) and reads the node
+ * boxes back, 24 B per node, so that srt_pt_dump_bvh stays true; the tables the kernels need (primitive order, level lists,
+ * record children) go up at the mesh's first refit and are dropped when srt_pt_update_mesh rebuilds the mesh or the scene is
+ * committed again.  A host-only context (device = -1) refits on the host: that code (refit_boxes, pt_scene.cpp) is the
+ * definition the device is held to.  A BVH<Object> build that does not terminate or comes out too deep is SRT_ERR_UNSUPPORTED.
+ * In every failing case the committed scene stays exactly as it was, on the host and on the device: the new boxes are computed
+ * aside and the top half is built aside before the first write to a live array.  With a scene committed with use_bvh == 0 there
+ * is no tree and the call does what srt_pt_update_mesh does.  A later srt_pt_update_mesh on a refitted mesh rebuilds it (the
+ * scene then equals a fresh commit); a skin created before a refit stays valid.  A refitted tree is valid but may be worse than
+ * a rebuilt one: srt_pt_mesh_tree_cost tells. */
+int srt_pt_refit_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts);
+/* The same with the two arrays in device memory: copies and kernels are enqueued on `stream` (a hipStream_t; NULL: the null
+ * stream), which the call synchronises where the host needs a verdict (the arrays come back once, 24 B per vertex, and are
+ * checked there; the root box comes back with the node boxes) and before it returns. */
+int srt_pt_refit_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts);
+/* SAH cost of the mesh's current BVH<Triangle>, on the host in double from the host node boxes: the sum over interior nodes of
+ * SA(n) / SA(root) plus the sum over leaves of size(n) * SA(n) / SA(root), SA = 2 (xy + yz + zx) of a box's extents.  What a
+ * caller compares before and after refits to decide when to rebuild with srt_pt_update_mesh.  Refusals as for srt_pt_refit_mesh;
+ * SRT_ERR_UNSUPPORTED for a scene committed with use_bvh == 0. */
+int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost);
+
 /* ---- Skinning: Skeleton::find_joints and Skeleton::skin on the device ----
  * What Scene_Object::sync_anim_mesh (scene/object.cpp:106-129) does on the CPU per frame - Skeleton::find_joints
  * (student/skeleton.cpp:219-256), Skeleton::skin (:258-307) and, without smooth normals, the flat-normal loop (:114-126) - as
@@ -294,6 +329,8 @@ int srt_pt_skin_vertices(srt_pt_skin* skin, const float* posed, int flat_normals
 /* Skins into the skin's staging on `stream`, then srt_pt_update_mesh_device(pt, stream, object, staging, nverts): preconditions,
  * errors and "the committed scene stays as it was on failure" are exactly that call's for those arrays. */
 int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
+/* The same with srt_pt_refit_mesh_device in place of the update: skin -> staging -> refit, no BVH<Triangle> build. */
+int srt_pt_skin_pose_refit(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
 /* Every call on a skin but destroy and counts returns SRT_ERR_STATE once its context's scene was begun or committed again (the
  * skin is stale: destroy it, create another), and SRT_ERR_INVALID for a NULL argument. */
 /* Where srt_pt_scene_commit runs BVH<Primitive>::build (student/bvh.inl:35-163): device != 0 (default) builds primitive sets of at

@@ -68,6 +68,13 @@ int srt_pt_counters(srt_pt* pt, uint64_t out[8]);
  * the vertex arrays (host form), the primitive order of a host build, the nodes and records that are new or moved, the tables of
  * object order - the records its kernel writes on the device are not uploads.  A refused update adds nothing to the builds. */
 int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]);
+/* The trailing counter of the same family, in a call of its own so that out[8] above keeps its size for existing callers: the
+ * successful srt_pt_refit_mesh[_device] / srt_pt_skin_pose_refit calls since creation.  A refit adds nothing to the builds and
+ * nothing to the triangle-class upload figure (its kernels write the records); to the uploads it adds the vertex arrays (host
+ * form), the BVH<Object> nodes and the tables of object order, and at a mesh's first refit its refit tables (4 B per triangle,
+ * 8 B per node and per interior record, the level offsets).  A refused refit adds nothing to any figure: the vertices it had
+ * staged are not counted at all, and tables it made stay resident and are counted with the mesh's first refit that succeeds. */
+int srt_pt_refit_count(srt_pt* pt, uint64_t* refits);
 /* cosf/sinf of the kernel (SRT-MATH v2) for n host floats; parity tests compare them with glibc. */
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);
 /* The kernels' atan2f (glibc 2.35's algorithm restated; Spot_Light::sample) evaluated on the device. */

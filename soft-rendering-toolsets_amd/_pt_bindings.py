@@ -27,7 +27,7 @@ class SrtCancelled(Exception):
 _HIP_MEMCPY_D2H = 2   # hipMemcpyDeviceToHost
 
 SCENE_COUNT_NAMES = ("objects", "triangles", "blas_nodes", "blas_records", "blas_builds", "device_bytes", "uploaded_bytes",
-                     "uploaded_triangle_bytes")
+                     "uploaded_triangle_bytes", "refits")
 COUNTER_NAMES = ("rays", "box_tests", "objects_entered", "tri_tests", "sphere_tests", "tlas_nodes", "blas_nodes",
                  "light_tri_tests")
 
@@ -58,6 +58,11 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_repose.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_update_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_update_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_refit_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_refit_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_skin_pose_refit.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
+    lib.srt_pt_mesh_tree_cost.argtypes = [c_void_p, c_uint32, POINTER(ctypes.c_double)]
+    lib.srt_pt_refit_count.argtypes = [c_void_p, POINTER(c_uint64)]
     lib.srt_pt_skin_create.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]
     lib.srt_pt_skin_destroy.argtypes = [c_void_p]
     lib.srt_pt_skin_counts.argtypes = [c_void_p, c_void_p]
@@ -201,6 +206,11 @@ class Skin:
         posed = self._posed(posed)
         self._check(self._lib, self._lib.srt_pt_skin_pose(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals))))
 
+    def pose_refit(self, posed, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose_refit: skin, then srt_pt_refit_mesh_device with the result - the committed mesh takes the pose and keeps its tree."""
+        posed = self._posed(posed)
+        self._check(self._lib, self._lib.srt_pt_skin_pose_refit(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals))))
+
     def close(self) -> None:
         if self._h:
             self._lib.srt_pt_skin_destroy(self._h)
@@ -229,6 +239,10 @@ class SkinGroup:
     def pose(self, posed, flat_normals: bool = False) -> None:
         for k in self.skins:
             k.pose(posed, flat_normals)
+
+    def pose_refit(self, posed, flat_normals: bool = False) -> None:
+        for k in self.skins:
+            k.pose_refit(posed, flat_normals)
 
     def close(self) -> None:
         for k in self.skins:
@@ -355,6 +369,24 @@ class Pathtracer:
         """srt_pt_update_mesh_device: the same from two device arrays of nverts * 3 floats (e.g. tensor.data_ptr())."""
         self._check(self._lib, self._lib.srt_pt_update_mesh_device(self._ctx, c_void_p(stream), int(index), c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr), int(nverts)))
 
+    def refit_mesh(self, index: int, pos, nrm) -> None:
+        """srt_pt_refit_mesh: new vertex positions and normals for the mesh object with this insertion index, its BVH<Triangle> kept:
+        same links and primitive order, new boxes - no build (in a scene without BVHs: update_mesh)."""
+        pos, nrm = _f32(pos).reshape(-1, 3), _f32(nrm).reshape(-1, 3)
+        if len(pos) != len(nrm):
+            raise ValueError(f"{len(pos)} positions but {len(nrm)} normals")
+        self._check(self._lib, self._lib.srt_pt_refit_mesh(self._ctx, int(index), _p(pos), _p(nrm), len(pos)))
+
+    def refit_mesh_device(self, index: int, d_pos_ptr: int, d_nrm_ptr: int, nverts: int, stream: int = 0) -> None:
+        """srt_pt_refit_mesh_device: the same from two device arrays of nverts * 3 floats (e.g. tensor.data_ptr())."""
+        self._check(self._lib, self._lib.srt_pt_refit_mesh_device(self._ctx, c_void_p(stream), int(index), c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr), int(nverts)))
+
+    def mesh_tree_cost(self, index: int) -> float:
+        """srt_pt_mesh_tree_cost: SAH cost of the mesh's current BVH<Triangle> - compare before and after refits to decide when to rebuild."""
+        c = ctypes.c_double()
+        self._check(self._lib, self._lib.srt_pt_mesh_tree_cost(self._ctx, int(index), ctypes.byref(c)))
+        return float(c.value)
+
     def create_skin(self, index: int, bind_pos, bind_nrm, joints) -> Skin:
         """srt_pt_skin_create: Skeleton::find_joints for the mesh object with this insertion index of the committed scene, from its
         bind-pose arrays ((nverts, 3) each) and its joints (skin_joints(..)) in Skeleton::for_joints order."""
@@ -367,10 +399,13 @@ class Pathtracer:
         return Skin(self, h, len(pos), len(J))
 
     def scene_counts(self) -> dict:
-        """srt_pt_scene_counts: what the scene stores, the BVH<Triangle> builds so far and the bytes uploaded (SCENE_COUNT_NAMES)."""
+        """srt_pt_scene_counts: what the scene stores, the BVH<Triangle> builds so far and the bytes uploaded, and srt_pt_refit_count's
+        refits (SCENE_COUNT_NAMES)."""
         out = np.zeros(8, np.uint64)
         self._check(self._lib, self._lib.srt_pt_scene_counts(self._ctx, _p(out)))
-        return dict(zip(SCENE_COUNT_NAMES, (int(v) for v in out)))
+        refits = c_uint64()
+        self._check(self._lib, self._lib.srt_pt_refit_count(self._ctx, ctypes.byref(refits)))
+        return dict(zip(SCENE_COUNT_NAMES, [int(v) for v in out] + [int(refits.value)]))
 
     def set_camera(self, camera: dict) -> None:
         iv = _f32(camera["iview"])
@@ -708,6 +743,10 @@ class PathtracerGroup:
     def update_mesh(self, index: int, pos, nrm) -> None:
         for m in self.members:
             m.update_mesh(index, pos, nrm)
+
+    def refit_mesh(self, index: int, pos, nrm) -> None:
+        for m in self.members:
+            m.refit_mesh(index, pos, nrm)
 
     def create_skin(self, index: int, bind_pos, bind_nrm, joints) -> SkinGroup:
         """One skin per rank; SkinGroup.pose poses each rank, as update_mesh updates each."""

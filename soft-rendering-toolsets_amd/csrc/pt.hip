@@ -449,6 +449,10 @@ struct srt_pt {
   BvhWorkspace bvh_ws;
   float* d_vpos = nullptr; size_t vpos_floats = 0;
   float* d_vnrm = nullptr; size_t vnrm_floats = 0;
+  // srt_pt_refit_mesh: per refitted mesh (insertion index) what its kernels keep on the device, from the first refit until the mesh
+  // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
+  std::map<uint32_t, RefitTables> refit_tables;
+  uint64_t refits = 0;
   // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
   uint64_t scene_generation = 0;
 };
@@ -466,6 +470,20 @@ int upload(srt_pt* pt, T** dst, const std::vector<T>& src, bool tri_class = fals
   pt->bytes_uploaded += src.size() * sizeof(T);
   if (tri_class) pt->tri_bytes_uploaded += src.size() * sizeof(T);
   return SRT_OK;
+}
+
+void free_refit_tables(RefitTables* T) {
+  for (void* p : {(void*)T->d_prim, T->d_leaves, T->d_list, T->d_children, (void*)T->d_level_off, (void*)T->d_tri_boxes, (void*)T->d_node_boxes})
+    if (p) (void)hipFree(p);
+  *T = RefitTables();
+}
+
+// The refit tables of `object` (UINT32_MAX: of every mesh): its tree is about to be replaced.
+void drop_refit_tables(srt_pt* pt, uint32_t object) {
+  for (auto it = pt->refit_tables.begin(); it != pt->refit_tables.end();) {
+    if (object == UINT32_MAX || it->first == object) { free_refit_tables(&it->second); it = pt->refit_tables.erase(it); }
+    else ++it;
+  }
 }
 
 int need_device(srt_pt* pt, const char* what) {
@@ -1116,6 +1134,7 @@ int srt_pt_destroy(srt_pt* pt) {
     (void)hipFree(pt->d_tile_buf); (void)hipFree(pt->d_image); (void)hipFree(pt->d_totals);
     (void)hipFree(pt->d_idx); (void)hipFree(pt->d_vpos); (void)hipFree(pt->d_vnrm);
     bvh_workspace_free(&pt->bvh_ws);
+    drop_refit_tables(pt, UINT32_MAX);
     if (pt->h_fault) (void)hipHostFree(pt->h_fault);
     if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);
     for (auto& kv : pt->epoch_buffers) {
@@ -1265,7 +1284,8 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   // BVH<Triangle> builds of big meshes run on the device (pt_bvh_device.hip: identical arrays); srt_pt_set_bvh_builder
   const char* be = getenv("SRT_BVH_BUILDER");
   const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  if (pt->device >= 0 && bmode != 0) { SRT_HIP(hipSetDevice(pt->device)); set_device_bvh_builder(build_bvh_device, pt->bvh_device_min); }
+  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_refit_tables(pt, UINT32_MAX); }   // they describe trees that are about to go
+  if (pt->device >= 0 && bmode != 0) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
   else set_device_bvh_builder(nullptr, 0);
   const std::string err = build_scene(pt->inputs, pt->materials, use_bvh != 0, &pt->built);
   set_device_bvh_builder(nullptr, 0);
@@ -1432,11 +1452,162 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
   // the verdict is in: from here on the new arrays replace the old ones, on the host and then on the device
   const size_t old_tlas = pt->built.flat.tlas_nodes, old_nodes = pt->built.flat.nodes.size(), old_recs = pt->built.flat.blas_recs.size();
   apply_mesh_update(&pt->built, &U);
+  if (on_device) drop_refit_tables(pt, object);           // the refit tables describe the tree that was just replaced
   if (use_bvh) pt->blas_builds++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
   // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
   const int st = write_updated_mesh(pt, s, object, old, old_tlas, old_nodes, old_recs, d_pos, d_nrm, d_mesh_idx);
+  if (st != SRT_OK) pt->committed = false;
+  return st;
+}
+
+// The device tables of a mesh's refits, from its host tree: made at the first refit after a commit or a rebuild.
+int make_refit_tables(srt_pt* pt, uint32_t object, RefitTables* T) {
+  const HostBVH& tree = pt->built.blas[object];
+  const uint32_t nn = (uint32_t)tree.nodes.size(), ntri = (uint32_t)tree.prim.size();
+  // a node's level: children lie behind their parent (level order, student/bvh.inl:144-145), so one forward pass does it
+  std::vector<uint32_t> level(nn, 0u);
+  uint32_t levels = 0;
+  for (uint32_t n = 0; n < nn; n++) {
+    const HostNode& h = tree.nodes[n];
+    if (h.l == h.r) {
+      // the leaf table packs (first slot << 3) | count, and the kernels trust it: refuse here what they could not take
+      if (h.size > 7u || h.start >= (1u << 29) || (uint64_t)h.start + h.size > ntri)
+        return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_refit_mesh: leaf %u of object %u holds %u primitives from slot %u (at most 7, below 2^29, inside the mesh)", n,
+                         object, h.size, h.start);
+      continue;
+    }
+    if (h.l <= n || h.r != h.l + 1u || h.r >= nn) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_refit_mesh: the tree of object %u is not in level order", object);
+    level[h.l] = level[h.r] = level[n] + 1u;
+    levels = std::max(levels, level[n] + 1u);
+  }
+  for (uint32_t t : tree.prim)
+    if (t >= ntri) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_refit_mesh: the primitive order of object %u names triangle %u of %u", object, t, ntri);
+  std::vector<uint2> leaves, list, children;
+  std::vector<uint32_t> off(levels + 1u, 0u);
+  for (uint32_t n = 0; n < nn; n++) {
+    const HostNode& h = tree.nodes[n];
+    if (h.l == h.r) leaves.push_back(make_uint2(n, (h.start << 3) | (h.size & 7u)));
+    else { off[level[n] + 1u]++; children.push_back(make_uint2(h.l, h.r)); }     // records are numbered in node order (append_records)
+  }
+  for (uint32_t l = 0; l < levels; l++) off[l + 1u] += off[l];
+  list.resize(children.size());
+  std::vector<uint32_t> at(off.begin(), off.end() - 1);
+  for (uint32_t n = 0; n < nn; n++)
+    if (tree.nodes[n].l != tree.nodes[n].r) list[at[level[n]]++] = make_uint2(n, tree.nodes[n].l);
+  T->ntri = ntri; T->nnodes = nn; T->nleaves = (uint32_t)leaves.size(); T->nrec = (uint32_t)children.size();
+  T->level_off = off;
+  const char* ll = getenv("SRT_REFIT_LEVEL_LAUNCHES");
+  T->level_launches = ll && atoi(ll) != 0;
+  auto up = [&](auto** dst, const auto& src) -> bool {
+    using E = typename std::remove_reference<decltype(src)>::type::value_type;
+    if (hipMalloc((void**)dst, (src.empty() ? 1 : src.size()) * sizeof(E)) != hipSuccess) return false;
+    if (!src.empty() && hipMemcpy(*dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice) != hipSuccess) return false;
+    T->uncounted_bytes += src.size() * sizeof(E);
+    return true;
+  };
+  if (!up(&T->d_prim, tree.prim) || !up(&T->d_leaves, leaves) || !up(&T->d_list, list) || !up(&T->d_children, children) || !up(&T->d_level_off, off) ||
+      hipMalloc(&T->d_tri_boxes, (size_t)ntri * 6 * sizeof(float)) != hipSuccess || hipMalloc(&T->d_node_boxes, (size_t)nn * 6 * sizeof(float)) != hipSuccess) {
+    free_refit_tables(T);
+    return srt::fail(SRT_ERR_HIP, "srt_pt_refit_mesh: out of device memory");
+  }
+  return SRT_OK;
+}
+
+// srt_pt_refit_mesh / srt_pt_refit_mesh_device / srt_pt_skin_pose_refit.  h_*: the host form's arrays; d_*: the device form's.
+int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* h_pos, const float* h_nrm, const float* d_pos,
+               const float* d_nrm, uint32_t nverts) {
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
+  const std::string refused = check_mesh_update(pt->built, object, nverts);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (!pt->built.flat.use_bvh) return update_mesh(pt, what, s, object, h_pos, h_nrm, d_pos, d_nrm, nverts);   // a list has no tree: the update
+  const bool on_device = pt->device >= 0;
+  if (!on_device && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
+  const MeshStore m = pt->built.store[object];
+  const size_t vfloats = 3 * (size_t)nverts;
+  std::vector<float> back_pos, back_nrm, node_boxes;
+  RefitTables* T = nullptr;
+  uint64_t staged_bytes = 0;
+  if (on_device) {
+    SRT_HIP(hipSetDevice(pt->device));
+    SRT_HIP(hipStreamSynchronize(pt->stream));
+    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old arrays
+    if (h_pos) {                                          // 24 B per vertex up, into the staging (nothing of the live scene yet)
+      for (size_t k = 0; k < vfloats; k++)
+        if (!std::isfinite(h_pos[k])) return srt::fail(SRT_ERR_INVALID, "%s: vertex %zu of the new positions has a non-finite coordinate", what, k / 3);
+      int st;
+      if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
+      SRT_HIP(hipMemcpy(pt->d_vpos, h_pos, vfloats * sizeof(float), hipMemcpyHostToDevice));
+      SRT_HIP(hipMemcpy(pt->d_vnrm, h_nrm, vfloats * sizeof(float), hipMemcpyHostToDevice));
+      staged_bytes = 2 * vfloats * sizeof(float);         // (counted with the verdict: a refused refit adds nothing to the figures)
+      d_pos = pt->d_vpos; d_nrm = pt->d_vnrm;
+    }
+    auto it = pt->refit_tables.find(object);
+    if (it == pt->refit_tables.end()) {
+      RefitTables fresh;
+      const int st = make_refit_tables(pt, object, &fresh);
+      if (st != SRT_OK) return st;
+      it = pt->refit_tables.emplace(object, fresh).first;
+    }
+    T = &it->second;
+    // the new boxes, aside: triangle boxes, leaves, levels.  They come back (24 B per node) with the arrays of the device form
+    // (24 B per vertex): the host checks those, takes the root box and keeps its own tree true.
+    launch_mesh_boxes(s, d_pos, pt->d_idx + pt->idx_off[object], m.ntri, T->d_tri_boxes);
+    launch_refit_boxes(s, *T, T->d_node_boxes);
+    node_boxes.resize(6 * (size_t)T->nnodes);
+    SRT_HIP(hipMemcpyAsync(node_boxes.data(), T->d_node_boxes, node_boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!h_pos) {
+      back_pos.resize(vfloats); back_nrm.resize(vfloats);
+      SRT_HIP(hipMemcpyAsync(back_pos.data(), d_pos, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+      SRT_HIP(hipMemcpyAsync(back_nrm.data(), d_nrm, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    if (!h_pos) { h_pos = back_pos.data(); h_nrm = back_nrm.data(); }
+  }
+  // the BVH<Object> build goes where srt_pt_repose's does
+  const char* be = getenv("SRT_BVH_BUILDER");
+  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
+  if (on_device && bmode != 0) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
+  else set_device_bvh_builder(nullptr, 0);
+  MeshRefit R;
+  bool bad_argument = false;
+  const std::string err = prepare_mesh_refit(pt->built, object, h_pos, h_nrm, nverts, on_device ? node_boxes.data() : nullptr, &R, &bad_argument);
+  set_device_bvh_builder(nullptr, 0);
+  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str());
+  if ((int)R.top.max_tlas_depth > kMaxTlasDepth)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)", R.top.max_tlas_depth, kMaxTlasDepth,
+                     pt->built.flat.max_blas_depth, kMaxBlasDepth);
+  // the verdict is in: from here on the new boxes and records replace the old ones in place, on the host and then on the device
+  const size_t old_tlas = pt->built.flat.tlas_nodes;
+  apply_mesh_refit(&pt->built, &R);
+  pt->refits++;
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  if (!on_device) return SRT_OK;
+  pt->bytes_uploaded += staged_bytes + T->uncounted_bytes;   // the vertices of the host form; the tables, at the mesh's first successful refit
+  T->uncounted_bytes = 0;
+  // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
+  const FlatScene& F = pt->built.flat;
+  auto write = [&]() -> int {
+    int st;
+    if (F.tlas_nodes == old_tlas) {                       // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
+      if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
+      pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
+    } else {
+      SRT_HIP(hipStreamSynchronize(s));
+      if ((st = upload(pt, &pt->d_nodes, F.nodes))) return st;
+    }
+    launch_refit_write(s, *T, T->d_node_boxes, pt->d_nodes + F.tlas_nodes + m.node_off, pt->d_blas + m.rec_base);
+    launch_mesh_records(s, d_pos, d_nrm, pt->d_idx + pt->idx_off[object], T->d_prim, m.ntri, pt->d_tris + m.tri_base, pt->d_nrm + m.tri_base,
+                        pt->d_tri_packed + 9 * (size_t)m.tri_base);
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
+      return st;
+    return SRT_OK;
+  };
+  const int st = write();
   if (st != SRT_OK) pt->committed = false;
   return st;
 }
@@ -1453,6 +1624,32 @@ int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, cons
 int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
   if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh_device: NULL argument");
   return update_mesh(pt, "srt_pt_update_mesh_device", (hipStream_t)stream, object, nullptr, nullptr, d_positions, d_normals, nverts);
+}
+
+int srt_pt_refit_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
+  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh: NULL argument");
+  return refit_mesh(pt, "srt_pt_refit_mesh", pt->stream, object, positions, normals, nullptr, nullptr, nverts);
+}
+
+int srt_pt_refit_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
+  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh_device: NULL argument");
+  return refit_mesh(pt, "srt_pt_refit_mesh_device", (hipStream_t)stream, object, nullptr, nullptr, d_positions, d_normals, nverts);
+}
+
+int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost) {
+  if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: NULL argument");
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_mesh_tree_cost before srt_pt_scene_commit");
+  const std::string refused = check_mesh_update(pt->built, object, (uint32_t)(object < pt->built.inputs.size() ? pt->built.inputs[object].mesh.pos.size() / 3 : 0));
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: %s", refused.c_str());
+  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_mesh_tree_cost: the scene was committed without BVHs, the mesh has no tree");
+  *cost = tree_cost(pt->built.blas[object]);
+  return SRT_OK;
+}
+
+int srt_pt_refit_count(srt_pt* pt, uint64_t* refits) {
+  if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_count: NULL argument");
+  *refits = pt->refits;
+  return SRT_OK;
 }
 
 }  // extern "C"
@@ -1637,6 +1834,15 @@ int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int fl
   // (the staging is read by nothing of the context: writing it before srt_pt_update_mesh_device's verdict changes no scene)
   if ((st = skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
   return update_mesh(skin->pt, "srt_pt_skin_pose", (hipStream_t)stream, skin->object, nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
+}
+
+int srt_pt_skin_pose_refit(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
+  if (!skin || !posed) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_pose_refit: NULL argument");
+  int st = skin_usable(skin, "srt_pt_skin_pose_refit");
+  if (st != SRT_OK) return st;
+  // (the staging is read by nothing of the context: writing it before srt_pt_refit_mesh_device's verdict changes no scene)
+  if ((st = skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
+  return refit_mesh(skin->pt, "srt_pt_skin_pose_refit", (hipStream_t)stream, skin->object, nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
 }
 
 }  // extern "C"

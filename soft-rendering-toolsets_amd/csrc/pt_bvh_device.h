@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "pt_scene.h"
 
@@ -36,6 +37,26 @@ void launch_mesh_boxes(void* stream, const float* d_pos, const uint32_t* d_idx, 
 // and d_packed[9 k ..] - the caller passes the three arrays offset to the mesh's first slot.
 void launch_mesh_records(void* stream, const float* d_pos, const float* d_nrm_in, const uint32_t* d_idx, const uint32_t* d_prim, uint32_t ntri,
                          Tri* d_tris, TriNrm* d_nrm, float* d_packed);
+
+// What a refit of one mesh (srt_pt_refit_mesh) keeps on the device, made from the host tree at the mesh's first refit and
+// dropped when the mesh is rebuilt or the scene committed again: the primitive order (4 B per triangle), the leaves as {node,
+// (first slot << 3) | count}, the interior nodes as {node, left child} sorted by level with the level offsets, the interior
+// records' {left node, right node} (8 B each), and the two box arrays the kernels work in.
+struct RefitTables {
+  uint32_t ntri = 0, nnodes = 0, nleaves = 0, nrec = 0;
+  uint32_t* d_prim = nullptr;
+  void *d_leaves = nullptr, *d_list = nullptr, *d_children = nullptr;   // uint2 each (typed in pt_mesh_update.hip)
+  uint32_t* d_level_off = nullptr;
+  std::vector<uint32_t> level_off;       // levels + 1 offsets into d_list (level 0: the root)
+  float *d_tri_boxes = nullptr, *d_node_boxes = nullptr;
+  uint64_t uncounted_bytes = 0;          // what went up for these tables and is not in the context's upload figure yet (a refused refit adds nothing)
+  int level_launches = 0;                // != 0: one launch per level even where a run of levels fits one workgroup (measurements)
+};
+// Leaf boxes from T.d_tri_boxes (launch_mesh_boxes' output, by original triangle), then the interior levels, deepest first, into
+// d_node_boxes6 (six floats per node).  Only enqueues.
+void launch_refit_boxes(void* stream, const RefitTables& T, float* d_node_boxes6);
+// The boxes into the mesh's live nodes (d_mesh_nodes: its first Node) and interior records (d_mesh_recs: its first record).
+void launch_refit_write(void* stream, const RefitTables& T, const float* d_node_boxes6, Node* d_mesh_nodes, WaveInterior* d_mesh_recs);
 
 }  // namespace srt
 

@@ -60,6 +60,18 @@ __device__ __forceinline__ void mesh_triangle_record(const float* __restrict__ p
   nn->n0[3] = nn->n1[3] = nn->n2[3] = 0.0f;
 }
 
+// BBox::enclose(BBox) (lib/bbox.h) as Box::enclose of pt_scene.cpp states it: std::min(mn, b) / std::max(mx, b) per axis, the
+// kept bound first - so the device refit and refit_boxes agree on the sign of a zero bound as well.
+__device__ __forceinline__ void box_enclose(float box6[6], const float other6[6]) {
+  for (int a = 0; a < 3; a++) {
+    if (other6[a] < box6[a]) box6[a] = other6[a];
+    if (box6[3 + a] < other6[3 + a]) box6[3 + a] = other6[3 + a];
+  }
+}
+__device__ __forceinline__ void box_empty(float box6[6]) {   // BBox(), lib/bbox.h:17
+  for (int a = 0; a < 3; a++) { box6[a] = 3.402823466e+38f; box6[3 + a] = -3.402823466e+38f; }
+}
+
 }  // namespace srt
 
 #endif

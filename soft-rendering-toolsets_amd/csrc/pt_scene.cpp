@@ -731,4 +731,110 @@ void apply_mesh_update(BuiltScene* built, MeshUpdate* update) {
   B.tlas.prim.swap(U.top.tlas.prim);
 }
 
+void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32_t>& idx, std::vector<float>* boxes6) {
+  const size_t nn = tree.nodes.size();
+  std::vector<Box> nb(nn);
+  for (size_t n = nn; n-- > 0;) {
+    const HostNode& nd = tree.nodes[n];
+    Box b;
+    if (nd.l == nd.r) {
+      for (uint32_t k = nd.start; k < nd.start + nd.size; k++) {
+        const uint32_t t = tree.prim[k];
+        b.enclose(triangle_box(&pos[3 * (size_t)idx[3 * (size_t)t]], &pos[3 * (size_t)idx[3 * (size_t)t + 1]], &pos[3 * (size_t)idx[3 * (size_t)t + 2]]));
+      }
+    } else {
+      b.enclose(nb[nd.l]);
+      b.enclose(nb[nd.r]);
+    }
+    nb[n] = b;
+  }
+  boxes6->resize(6 * nn);
+  for (size_t n = 0; n < nn; n++)
+    for (int a = 0; a < 3; a++) { (*boxes6)[6 * n + a] = nb[n].mn[a]; (*boxes6)[6 * n + 3 + a] = nb[n].mx[a]; }
+}
+
+std::string prepare_mesh_refit(const BuiltScene& B, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                               const float* node_boxes, MeshRefit* out, bool* bad_argument) {
+  *bad_argument = true;
+  const std::string refused = check_mesh_update(B, object, nverts);
+  if (!refused.empty()) return refused;
+  if (!B.flat.use_bvh) return "the scene was committed without BVHs: there is no tree to refit";
+  for (size_t k = 0; k < 3 * (size_t)nverts; k++)
+    if (!std::isfinite(pos[k]))
+      return "vertex " + std::to_string(k / 3) + " of the new positions has a non-finite coordinate";
+  *bad_argument = false;
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  MeshRefit& R = *out;
+  R = MeshRefit();
+  R.object = object;
+  R.pos.assign(pos, pos + 3 * (size_t)nverts);
+  R.nrm.assign(nrm, nrm + 3 * (size_t)nverts);
+  const HostBVH& tree = B.blas[object];
+  if (node_boxes) R.boxes.assign(node_boxes, node_boxes + 6 * tree.nodes.size());
+  else refit_boxes(tree, pos, B.inputs[object].mesh.idx, &R.boxes);
+  // the mesh and its instances take the new root box; storage does not move
+  R.local_boxes = B.local_boxes;
+  for (uint32_t i = 0; i < nobj; i++)
+    if (i == object || (B.inputs[i].kind == OBJ_MESH && B.inputs[i].source == (int32_t)object))
+      for (int a = 0; a < 6; a++) R.local_boxes[6 * (size_t)i + a] = R.boxes[a];
+  std::vector<Mat4> trans(nobj);
+  for (uint32_t i = 0; i < nobj; i++) trans[i] = B.inputs[i].trans;
+  Top T;
+  if (!build_top(trans, R.local_boxes, true, &T)) return "BVH<Object> build does not terminate (coincident object centroids)";
+  ReposedTop& P = R.top;
+  make_objects(B.inputs, trans, T, B.store, (uint32_t)T.nodes.size(), true, &P.objects, &P.lazy_objects);
+  make_wave_lazy(T.wave, P.objects, &P.wave_lazy);
+  P.tlas.nodes.swap(T.tlas.nodes);
+  P.tlas.prim.swap(T.tlas.prim);
+  P.tlas_nodes.swap(T.nodes);
+  P.wave_tlas.swap(T.wave);
+  P.max_tlas_depth = T.depth;
+  return "";
+}
+
+void apply_mesh_refit(BuiltScene* built, MeshRefit* refit) {
+  BuiltScene& B = *built;
+  FlatScene& F = B.flat;
+  MeshRefit& R = *refit;
+  const MeshStore m = B.store[R.object];
+  MeshInput& mesh = B.inputs[R.object].mesh;
+  mesh.pos.swap(R.pos);
+  mesh.nrm.swap(R.nrm);
+  B.local_boxes.swap(R.local_boxes);
+  apply_repose(built, &R.top);                     // the BVH<Object> and the tables of object order; the BVH<Triangle> nodes stay behind it
+  HostBVH& tree = B.blas[R.object];
+  for (size_t n = 0; n < tree.nodes.size(); n++) {
+    HostNode& h = tree.nodes[n];
+    Node& f = F.nodes[(size_t)F.tlas_nodes + m.node_off + n];
+    for (int a = 0; a < 3; a++) { h.mn[a] = f.mn[a] = R.boxes[6 * n + a]; h.mx[a] = f.mx[a] = R.boxes[6 * n + 3 + a]; }
+  }
+  // interior records in node order, as append_records numbers them: both child boxes, nothing else
+  size_t q = m.rec_base;
+  for (const HostNode& h : tree.nodes) {
+    if (h.l == h.r) continue;
+    WaveInterior& wi = F.blas_recs[q++];
+    for (int a = 0; a < 6; a++) { wi.boxl[a] = R.boxes[6 * (size_t)h.l + a]; wi.boxr[a] = R.boxes[6 * (size_t)h.r + a]; }
+  }
+  // triangle records in the kept primitive order
+  std::vector<Tri> tris;
+  std::vector<TriNrm> tri_nrm;
+  std::vector<float> packed;
+  append_triangles(mesh, &tree.prim, &tris, &tri_nrm, &packed);
+  std::copy(tris.begin(), tris.end(), F.tris.begin() + m.tri_base);
+  std::copy(tri_nrm.begin(), tri_nrm.end(), F.tri_nrm.begin() + m.tri_base);
+  std::copy(packed.begin(), packed.end(), F.tri_packed.begin() + 9 * (size_t)m.tri_base);
+}
+
+double tree_cost(const HostBVH& tree) {
+  if (tree.nodes.empty()) return 0.0;
+  auto area = [](const HostNode& h) {
+    const double x = (double)h.mx[0] - (double)h.mn[0], y = (double)h.mx[1] - (double)h.mn[1], z = (double)h.mx[2] - (double)h.mn[2];
+    return 2.0 * (x * y + y * z + z * x);
+  };
+  const double root = area(tree.nodes[0]);
+  double cost = 0.0;
+  for (const HostNode& h : tree.nodes) cost += (h.l == h.r ? (double)h.size : 1.0) * (area(h) / root);
+  return cost;
+}
+
 }  // namespace srt

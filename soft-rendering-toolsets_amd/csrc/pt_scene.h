@@ -226,6 +226,34 @@ std::string prepare_mesh_update(const BuiltScene& built, uint32_t object, const 
                                 HostBVH* prebuilt, MeshUpdate* out, bool* bad_argument);
 void apply_mesh_update(BuiltScene* built, MeshUpdate* update);
 
+// What srt_pt_refit_mesh derives for new vertex arrays of one mesh of a scene built with BVHs (the same objects
+// check_mesh_update admits), built next to the scene: the mesh's BVH<Triangle> keeps its links and its primitive order and takes
+// new boxes - a leaf's is the BBox::enclose fold of Triangle::bbox over its triangles in primitive order, an interior node's the
+// enclose of its left and then its right child's (children lie behind their parent, so one backward pass does it) - which is how
+// BVH<Primitive>::build forms every node box (student/bvh.inl:73-75, 119-123), so the committed vertices give the committed
+// boxes back (as values: the sign of a zero bound that occurs as +0 and as -0 follows the fold's order).  Node, record and
+// triangle counts stay; the object-space box of the mesh and of its instances becomes the new root box, and the BVH<Object> and the tables of object order follow as in prepare_repose.  prepare_mesh_refit leaves `built`
+// untouched; apply_mesh_refit writes everything in place (it cannot fail).
+struct MeshRefit {
+  uint32_t object = 0;
+  std::vector<float> pos, nrm;
+  std::vector<float> boxes;           // six floats {mn, mx} per node of the mesh's BVH<Triangle>
+  std::vector<float> local_boxes;     // of every object
+  ReposedTop top;                     // (listed / trans stay empty: no pose changes)
+};
+// The refitted boxes alone: six floats per node of `tree` over the triangles of (pos, idx).
+void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32_t>& idx, std::vector<float>* boxes6);
+// pos / nrm: 3 floats per vertex.  `node_boxes`: the refitted boxes where the caller has them already (from the device kernels,
+// pt_mesh_update.hip; six floats per node) - otherwise refit_boxes computes them here.  Returns "" or an error message;
+// *bad_argument tells a refused argument (check_mesh_update, a non-finite coordinate, a scene without BVHs) from a BVH<Object> build that
+// does not terminate.
+std::string prepare_mesh_refit(const BuiltScene& built, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                               const float* node_boxes, MeshRefit* out, bool* bad_argument);
+void apply_mesh_refit(BuiltScene* built, MeshRefit* refit);
+// SAH cost of a BVH (what a caller compares before and after refits to decide when to rebuild), in double from the node boxes:
+// sum over interior nodes of SA(n) / SA(root) + sum over leaves of size(n) * SA(n) / SA(root), SA = 2 (xy + yz + zx) of the extents.
+double tree_cost(const HostBVH& tree);
+
 Camera make_camera(const float iview[16], float vert_fov_deg, float aspect_ratio);
 
 // Delta_Light ctor: itrans = T.inverse(), has_trans = T != I.
