@@ -213,6 +213,31 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh);
  * committed scene.  New poses that make the reference's BVH<Object> build non-terminating or too deep for the traversal stacks
  * fail as srt_pt_scene_commit does (SRT_ERR_UNSUPPORTED) - and the committed scene stays exactly as it was. */
 int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n);
+/* The same with the transforms in device memory (a simulation's output: a rigid-body kernel, a torch op,
+ * srt_pt_particle_transforms_device): `objects` is a host array of n insertion indices as above, d_trans holds n * 16 floats in
+ * Mat4::data order and is read on `stream` (a hipStream_t; NULL: the null stream) behind whatever the caller enqueued there.
+ * Preconditions, refusals, their status codes and their messages are srt_pt_repose's, checked on the host before anything is
+ * enqueued; a host-only context (device = -1) validates and then returns SRT_ERR_UNSUPPORTED.  A kernel computes what the poses
+ * decide - itrans, has_trans and the posed box of the listed objects, one lane each - and those values come back once (156 B per
+ * listed object) so that the host's record of the scene stays true: srt_pt_dump_bvh and every later srt_pt_repose /
+ * srt_pt_update_mesh / srt_pt_refit_mesh see the new poses.  The BVH<Object> is built by the rule of srt_pt_set_bvh_builder /
+ * SRT_BVH_BUILDER: on the device, over the posed boxes where the kernel left them, for a scene of at least min_primitives
+ * objects; otherwise on the host, over the boxes read back (24 B per object).  The object records are rewritten in place by a
+ * kernel - no record is uploaded: the order of a host-built tree (4 B per slot) and the mesh ordinals (4 B per slot, when a mesh
+ * has a real BVH<Triangle>) go up with the nodes and sweep tables srt_pt_repose uploads, and the context's first device repose
+ * after a commit sends 24 B of object-space box per object.  Afterwards the scene equals, bit for bit in everything it computes,
+ * what srt_pt_repose of the same matrices gives; only storage and the upload counter may differ.  In every refused case the
+ * committed scene stays exactly as it was, on the host and on the device: the kernels write tables of their own, and the tree
+ * and the tables of object order are built aside and checked before the first write to a live array, which comes after the wait
+ * srt_pt_repose makes.  (A HIP failure after that point is SRT_ERR_HIP and leaves the context without a committed scene: commit
+ * again.)  Copies and kernels go on `stream`, which the call synchronises where the host needs a verdict and before it returns. */
+int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n);
+/* One lane per particle: d_trans_out[16 k ..] = Mat4::translate(pos_k) * Mat4::scale(Vec3{scale}), the T of
+ * rays/pathtracer.cpp:149, bit-equal to Mat4::operator* (zero signs included).  d_pos holds 3 floats per particle - the layout
+ * srt_pt_particles_step_device updates in place - so that step -> transforms -> srt_pt_repose_device -> render has no host data
+ * in it.  Only enqueues on `stream`; does not synchronise.  The population is fixed: n is the number of particle objects the
+ * scene was committed with.  Spawning and removing particles stays with the caller and needs a commit, as before. */
+int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out);
 /* New vertex arrays for ONE mesh of the committed scene without committing again: what a renderer of deforming meshes (a skinned
  * skeleton, cloth, a caller's own kernel) gets from the reference only by running build_scene again on Scene_Object::posed_mesh()
  * (rays/pathtracer.cpp:66-176, per frame).  `object` is the insertion index of an object added by srt_pt_add_mesh; positions /

@@ -56,6 +56,8 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_add_instance.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32]
     lib.srt_pt_scene_commit.argtypes = [c_void_p, c_int]
     lib.srt_pt_repose.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_repose_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_particle_transforms_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_void_p]
     lib.srt_pt_update_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_update_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_refit_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
@@ -356,6 +358,17 @@ class Pathtracer:
         if len(T) != len(idx):
             raise ValueError(f"{len(idx)} objects but {len(T)} transforms")
         self._check(self._lib, self._lib.srt_pt_repose(self._ctx, _p(idx), _p(T), len(idx)))
+
+    def repose_device(self, indices, d_trans_ptr: int, stream: int = 0) -> None:
+        """srt_pt_repose_device: the same from a device array of len(indices) * 16 floats (e.g. tensor.data_ptr()), read on `stream`."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self._lib, self._lib.srt_pt_repose_device(self._ctx, c_void_p(stream), _p(idx), c_void_p(d_trans_ptr), len(idx)))
+
+    def particle_transforms_device(self, d_pos_ptr: int, n: int, scale: float, d_trans_ptr: int, stream: int = 0) -> None:
+        """srt_pt_particle_transforms_device: translate(pos_k) * scale(scale) for n particles, device array (n, 3) -> device array
+        (n, 16); only enqueued on `stream`."""
+        self._check(self._lib, self._lib.srt_pt_particle_transforms_device(self._ctx, c_void_p(stream), c_void_p(d_pos_ptr), int(n), float(scale),
+                                                                           c_void_p(d_trans_ptr)))
 
     def update_mesh(self, index: int, pos, nrm) -> None:
         """srt_pt_update_mesh: new vertex positions and normals ((nverts, 3) each, the count the mesh was added with) for the mesh
@@ -739,6 +752,15 @@ class PathtracerGroup:
     def repose(self, indices, Ts) -> None:
         for m in self.members:
             m.repose(indices, Ts)
+
+    def repose_device(self, indices, d_trans_ptrs, stream: int = 0) -> None:
+        """srt_pt_repose_device on every rank: one device pointer per rank, each on its rank's device (ranks that share a device may
+        share the array)."""
+        ptrs = list(d_trans_ptrs)
+        if len(ptrs) != len(self.members):
+            raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
+        for m, ptr in zip(self.members, ptrs):
+            m.repose_device(indices, ptr, stream)
 
     def update_mesh(self, index: int, pos, nrm) -> None:
         for m in self.members:

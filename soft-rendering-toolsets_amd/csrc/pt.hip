@@ -26,6 +26,7 @@
 
 #include "pt_bvh_device.h"
 #include "pt_device.h"
+#include "pt_pose.h"
 #include "pt_scene.h"
 #include "pt_skin.h"
 #include "srt_common.h"
@@ -453,6 +454,15 @@ struct srt_pt {
   // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
   std::map<uint32_t, RefitTables> refit_tables;
   uint64_t refits = 0;
+  // srt_pt_repose_device: what its kernels keep on the device between calls - every object's record by insertion index, its
+  // object-space box and its posed box - made at the first device repose after a commit (drop_pose_tables: a commit, a mesh update
+  // or refit and a host repose change what they mirror; so does a device repose that is refused).  The per-call arrays (the list,
+  // the read-back staging, the mesh ordinals per slot) are grown on demand and kept.
+  Object* d_pose_records = nullptr; float* d_local_boxes = nullptr; float* d_posed_boxes = nullptr;
+  bool pose_tables = false;
+  uint32_t* d_pose_list = nullptr; size_t pose_list_n = 0;
+  PoseOut* d_pose_out = nullptr; size_t pose_out_n = 0;
+  uint32_t* d_slot_ordinal = nullptr; size_t slot_ordinal_n = 0;
   // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
   uint64_t scene_generation = 0;
 };
@@ -484,6 +494,13 @@ void drop_refit_tables(srt_pt* pt, uint32_t object) {
     if (object == UINT32_MAX || it->first == object) { free_refit_tables(&it->second); it = pt->refit_tables.erase(it); }
     else ++it;
   }
+}
+
+void drop_pose_tables(srt_pt* pt) {
+  for (void* p : {(void*)pt->d_pose_records, (void*)pt->d_local_boxes, (void*)pt->d_posed_boxes})
+    if (p) (void)hipFree(p);
+  pt->d_pose_records = nullptr; pt->d_local_boxes = pt->d_posed_boxes = nullptr;
+  pt->pose_tables = false;
 }
 
 int need_device(srt_pt* pt, const char* what) {
@@ -1135,6 +1152,8 @@ int srt_pt_destroy(srt_pt* pt) {
     (void)hipFree(pt->d_idx); (void)hipFree(pt->d_vpos); (void)hipFree(pt->d_vnrm);
     bvh_workspace_free(&pt->bvh_ws);
     drop_refit_tables(pt, UINT32_MAX);
+    drop_pose_tables(pt);
+    (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal);
     if (pt->h_fault) (void)hipHostFree(pt->h_fault);
     if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);
     for (auto& kv : pt->epoch_buffers) {
@@ -1284,7 +1303,7 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   // BVH<Triangle> builds of big meshes run on the device (pt_bvh_device.hip: identical arrays); srt_pt_set_bvh_builder
   const char* be = getenv("SRT_BVH_BUILDER");
   const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_refit_tables(pt, UINT32_MAX); }   // they describe trees that are about to go
+  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_refit_tables(pt, UINT32_MAX); drop_pose_tables(pt); }   // they describe trees and records that are about to go
   if (pt->device >= 0 && bmode != 0) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
   else set_device_bvh_builder(nullptr, 0);
   const std::string err = build_scene(pt->inputs, pt->materials, use_bvh != 0, &pt->built);
@@ -1452,7 +1471,7 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
   // the verdict is in: from here on the new arrays replace the old ones, on the host and then on the device
   const size_t old_tlas = pt->built.flat.tlas_nodes, old_nodes = pt->built.flat.nodes.size(), old_recs = pt->built.flat.blas_recs.size();
   apply_mesh_update(&pt->built, &U);
-  if (on_device) drop_refit_tables(pt, object);           // the refit tables describe the tree that was just replaced
+  if (on_device) { drop_refit_tables(pt, object); drop_pose_tables(pt); }   // they describe the tree and the boxes that were just replaced
   if (use_bvh) pt->blas_builds++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
@@ -1585,6 +1604,7 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
   pt->refits++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
+  drop_pose_tables(pt);                                   // the object-space boxes changed
   pt->bytes_uploaded += staged_bytes + T->uncounted_bytes;   // the vertices of the host form; the tables, at the mesh's first successful refit
   T->uncounted_bytes = 0;
   // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
@@ -1877,6 +1897,7 @@ int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint3
   apply_repose(&pt->built, &top);
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (pt->device >= 0) {
+    drop_pose_tables(pt);                                 // srt_pt_repose_device's tables mirror the poses that were just replaced
     const FlatScene& F = pt->built.flat;
     int st;
     if (F.tlas_nodes == old_tlas_nodes) {                 // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
@@ -1888,6 +1909,150 @@ int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint3
     if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
       return st;
   }
+  return SRT_OK;
+}
+
+int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
+  const char* what = "srt_pt_repose_device";
+  if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
+  const std::string refused = check_repose_list(pt->built, objects, n);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose takes host matrices)", what);
+  SRT_HIP(hipSetDevice(pt->device));
+  hipStream_t s = (hipStream_t)stream;
+  const bool use_bvh = pt->built.flat.use_bvh;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
+  int st;
+  uint64_t staged_bytes = 0;                              // (counted with the verdict: a refused repose adds nothing to the figures)
+  // The tables the kernels work in, at the first device repose after a commit: the records by insertion index come from the live
+  // records (a kernel; nothing goes up), the posed boxes from them and the object-space boxes (24 B per object up).
+  if (!pt->pose_tables) {
+    drop_pose_tables(pt);
+    if (hipMalloc(&pt->d_pose_records, (size_t)nobj * sizeof(Object)) != hipSuccess || hipMalloc(&pt->d_local_boxes, (size_t)nobj * 6 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&pt->d_posed_boxes, (size_t)nobj * 6 * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      drop_pose_tables(pt);
+      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+    }
+    // (blocking copy, then kernels on `s` that read what the last commit or repose left in d_objects: all of it done by now)
+    SRT_HIP(hipMemcpy(pt->d_local_boxes, pt->built.local_boxes.data(), (size_t)nobj * 6 * sizeof(float), hipMemcpyHostToDevice));
+    staged_bytes += (uint64_t)nobj * 6 * sizeof(float);
+    launch_pose_tables(s, pt->d_objects, nobj, pt->built.flat.tlas_nodes, pt->d_pose_records, pt->d_local_boxes, pt->d_posed_boxes);
+    pt->pose_tables = true;
+  }
+  // From here to the verdict only these tables and the staging are written; a refusal drops the tables (the next call makes them
+  // again from the committed records, which are not touched).
+  auto refuse = [&](int status) { drop_pose_tables(pt); return status; };
+  std::vector<PoseOut> posed(n);
+  std::vector<float> boxes;
+  if (n) {
+    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n))) return refuse(st);
+    if (hipMemcpyAsync(pt->d_pose_list, objects, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
+    staged_bytes += (uint64_t)n * 4;
+    launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
+    if (hipMemcpyAsync(posed.data(), pt->d_pose_out, (size_t)n * sizeof(PoseOut), hipMemcpyDeviceToHost, s) != hipSuccess)
+      return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
+  }
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: the pose kernel failed", what));
+  // The BVH<Object> build goes where srt_pt_repose's does: on the device, over the boxes where they are, for a scene at or above
+  // the device builder's threshold; anything else - and a device build that failed: the host build gives the verdict - on the host,
+  // over the boxes read back (24 B per object).
+  const char* be = getenv("SRT_BVH_BUILDER");
+  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
+  HostBVH device_tree;
+  bool device_built = false;
+  if (use_bvh && bmode != 0 && nobj >= pt->bvh_device_min && nobj > 1u && bvh_workspace_reserve(&pt->bvh_ws, nobj, false)) {
+    BvhWorkspace view = pt->bvh_ws;                       // the context's workspace with the posed boxes in the place of its own
+    view.d_boxes = pt->d_posed_boxes;
+    device_built = build_bvh_device_core(&view, s, nobj, 1, &device_tree);
+  }
+  if (use_bvh && !device_built) {
+    boxes.resize((size_t)nobj * 6);
+    if (hipMemcpyAsync(boxes.data(), pt->d_posed_boxes, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
+  }
+  std::vector<Mat4> trans(n), itrans(n);
+  std::vector<uint32_t> has_trans(n);
+  for (uint32_t k = 0; k < n; k++) {
+    std::memcpy(&trans[k], posed[k].trans, sizeof(Mat4));
+    std::memcpy(&itrans[k], posed[k].itrans, sizeof(Mat4));
+    has_trans[k] = posed[k].has_trans;
+    // (with a device-built tree the posed box has served already; the host's record holds it in the tree's leaves)
+  }
+  SuppliedPoses P;
+  P.trans = trans.data(); P.itrans = itrans.data(); P.has_trans = has_trans.data();
+  P.boxes6 = boxes.empty() ? nullptr : boxes.data();
+  P.prebuilt = device_built ? &device_tree : nullptr;
+  set_device_bvh_builder(nullptr, 0);
+  ReposedTop top;
+  bool bad_argument = false;
+  const std::string err = prepare_repose_supplied(pt->built, objects, n, P, &top, &bad_argument);
+  if (!err.empty()) return refuse(srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str()));
+  if ((int)top.max_tlas_depth > kMaxTlasDepth)
+    return refuse(srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)", top.max_tlas_depth, kMaxTlasDepth,
+                            pt->built.flat.max_blas_depth, kMaxBlasDepth));
+  // the primitive order and the mesh ordinals per slot, still aside: a host build's order goes up (4 B per slot), a device build's
+  // is where the record kernel reads it; the ordinals (bits 8 and up of use_bvh) are the host's
+  const uint32_t* d_prim = nullptr;
+  const uint32_t* d_ordinal = nullptr;
+  std::vector<uint32_t> ordinal;
+  if (use_bvh) {
+    if (!device_built) {
+      if (!bvh_workspace_reserve(&pt->bvh_ws, nobj, true)) return refuse(srt::fail(SRT_ERR_HIP, "%s: out of device memory", what));
+      if (hipMemcpyAsync(pt->bvh_ws.d_prim, top.tlas.prim.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
+      staged_bytes += (uint64_t)nobj * 4;
+    }
+    d_prim = pt->bvh_ws.d_prim;
+    if (!top.lazy_objects.empty()) {
+      ordinal.assign(nobj, 0u);
+      for (size_t q = 0; q < top.lazy_objects.size(); q++) ordinal[top.lazy_objects[q]] = (uint32_t)q << 8;
+      if ((st = ensure(&pt->d_slot_ordinal, &pt->slot_ordinal_n, (size_t)nobj))) return refuse(st);
+      if (hipMemcpyAsync(pt->d_slot_ordinal, ordinal.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+        return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
+      staged_bytes += (uint64_t)nobj * 4;
+      d_ordinal = pt->d_slot_ordinal;
+    }
+  }
+  // the verdict is in; nothing of the context may be in flight while the live arrays change
+  const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
+  if (hipStreamSynchronize(s) != hipSuccess || hipStreamSynchronize(pt->stream) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return refuse(srt::fail(SRT_ERR_HIP, "%s: synchronisation failed", what));
+  apply_repose(&pt->built, &top);
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->bytes_uploaded += staged_bytes;
+  // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
+  const FlatScene& F = pt->built.flat;
+  auto write = [&]() -> int {
+    int w;
+    if (F.tlas_nodes == old_tlas_nodes) {                 // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
+      if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
+      pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
+    } else if ((w = upload(pt, &pt->d_nodes, F.nodes))) {
+      return w;
+    }
+    // the records in place (the object count never changes): gathered on the device by the new order
+    launch_pose_records(s, pt->d_pose_records, d_prim, d_ordinal, nobj, F.tlas_nodes, pt->d_objects);
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    if ((w = upload(pt, &pt->d_wave, F.wave_tlas)) || (w = upload(pt, &pt->d_wave_lazy, F.wave_lazy))) return w;
+    return SRT_OK;
+  };
+  st = write();
+  if (st != SRT_OK) { pt->committed = false; drop_pose_tables(pt); }
+  return st;
+}
+
+int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {
+  int st = need_device(pt, "srt_pt_particle_transforms_device");
+  if (st != SRT_OK) return st;
+  if (n == 0) return SRT_OK;
+  if (!d_pos || !d_trans_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_particle_transforms_device: NULL argument");
+  launch_particle_transforms(stream, d_pos, n, scale, d_trans_out);
+  SRT_HIP(hipGetLastError());
   return SRT_OK;
 }
 

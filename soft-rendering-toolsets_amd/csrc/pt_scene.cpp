@@ -198,21 +198,27 @@ struct Top {
   std::vector<WaveInterior> wave;
   uint32_t depth = 0;
 };
-bool build_top(const std::vector<Mat4>& trans, const std::vector<float>& local_boxes, bool use_bvh, Top* T) {
+// The Object ctor values and Object::bbox of every object: what a pose decides.
+void pose_objects(const std::vector<Mat4>& trans, const std::vector<float>& local_boxes, Top* T, std::vector<Box>* obj_boxes) {
   const uint32_t nobj = (uint32_t)trans.size();
   T->itrans.resize(nobj);
   T->has_trans.resize(nobj);
-  std::vector<Box> obj_boxes(nobj);
+  obj_boxes->resize(nobj);
   for (uint32_t i = 0; i < nobj; i++) {
     T->itrans[i] = mat_inverse(trans[i]);            // Object ctor, rays/object.h:18-21
     T->has_trans[i] = mat_ne_identity(trans[i]);
     Box ob;
     for (int a = 0; a < 3; a++) { ob.mn[a] = local_boxes[6 * i + a]; ob.mx[a] = local_boxes[6 * i + 3 + a]; }
     if (T->has_trans[i]) ob.transform(trans[i]);     // Object::bbox, rays/object.h:51-55
-    obj_boxes[i] = ob;
+    (*obj_boxes)[i] = ob;
   }
+}
+// The BVH<Object> (leaf size 1) or List<Object> over the posed boxes, flattened.  `prebuilt`: the tree where the caller has built
+// it already (on the device, bit-equal to the host build; its arrays are moved from) - then obj_boxes is not read.
+bool tree_top(const std::vector<Box>& obj_boxes, uint32_t nobj, bool use_bvh, HostBVH* prebuilt, Top* T) {
   if (use_bvh) {
-    if (!build_bvh(obj_boxes, 1, &T->tlas)) return false;
+    if (prebuilt) { T->tlas.nodes.swap(prebuilt->nodes); T->tlas.prim.swap(prebuilt->prim); }
+    else if (!build_bvh(obj_boxes, 1, &T->tlas)) return false;
     append_nodes(T->tlas, &T->nodes);
     T->depth = interior_depth(T->tlas);
     // interior-node sweep order for the wave-uniform kernel: a leaf child is ~first object slot
@@ -223,6 +229,11 @@ bool build_top(const std::vector<Mat4>& trans, const std::vector<float>& local_b
     for (uint32_t i = 0; i < nobj; i++) T->tlas.prim[i] = i;
   }
   return true;
+}
+bool build_top(const std::vector<Mat4>& trans, const std::vector<float>& local_boxes, bool use_bvh, Top* T) {
+  std::vector<Box> obj_boxes;
+  pose_objects(trans, local_boxes, T, &obj_boxes);
+  return tree_top(obj_boxes, (uint32_t)trans.size(), use_bvh, nullptr, T);
 }
 
 // The object records in BVH<Object> primitive order (insertion order in list mode): an instance's record carries its
@@ -547,12 +558,8 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
   return "";
 }
 
-std::string prepare_repose(const BuiltScene& B, const uint32_t* objects, const Mat4* new_trans, uint32_t n, ReposedTop* out,
-                           bool* bad_argument) {
+std::string check_repose_list(const BuiltScene& B, const uint32_t* objects, uint32_t n) {
   const uint32_t nobj = (uint32_t)B.inputs.size();
-  *bad_argument = true;
-  std::vector<Mat4> trans(nobj);
-  for (uint32_t i = 0; i < nobj; i++) trans[i] = B.inputs[i].trans;
   std::vector<bool> seen(nobj, false);
   for (uint32_t k = 0; k < n; k++) {
     const uint32_t i = objects[k];
@@ -560,21 +567,87 @@ std::string prepare_repose(const BuiltScene& B, const uint32_t* objects, const M
     if (seen[i]) return "object " + std::to_string(i) + " is listed twice";
     if (B.inputs[i].is_light) return "object " + std::to_string(i) + " is an area light: its light tables depend on its pose, commit the scene again";
     seen[i] = true;
-    trans[i] = new_trans[k];
   }
+  return "";
+}
+
+namespace {
+
+// The tables of object order from a finished Top, moved into *out.
+void finish_repose(const BuiltScene& B, const std::vector<Mat4>& trans, Top* T, ReposedTop* out) {
+  make_objects(B.inputs, trans, *T, B.store, (uint32_t)T->nodes.size(), B.flat.use_bvh, &out->objects, &out->lazy_objects);
+  make_wave_lazy(T->wave, out->objects, &out->wave_lazy);
+  out->tlas.nodes.swap(T->tlas.nodes);
+  out->tlas.prim.swap(T->tlas.prim);
+  out->tlas_nodes.swap(T->nodes);
+  out->wave_tlas.swap(T->wave);
+  out->max_tlas_depth = T->depth;
+}
+
+}  // namespace
+
+std::string prepare_repose(const BuiltScene& B, const uint32_t* objects, const Mat4* new_trans, uint32_t n, ReposedTop* out,
+                           bool* bad_argument) {
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  *bad_argument = true;
+  const std::string refused = check_repose_list(B, objects, n);
+  if (!refused.empty()) return refused;
+  std::vector<Mat4> trans(nobj);
+  for (uint32_t i = 0; i < nobj; i++) trans[i] = B.inputs[i].trans;
+  for (uint32_t k = 0; k < n; k++) trans[objects[k]] = new_trans[k];
   *bad_argument = false;
   Top T;
   if (!build_top(trans, B.local_boxes, B.flat.use_bvh, &T)) return "BVH<Object> build does not terminate (coincident object centroids)";
   out->listed.assign(objects, objects + n);
   out->trans.assign(new_trans, new_trans + n);
-  make_objects(B.inputs, trans, T, B.store, (uint32_t)T.nodes.size(), B.flat.use_bvh, &out->objects, &out->lazy_objects);
-  make_wave_lazy(T.wave, out->objects, &out->wave_lazy);
-  out->tlas.nodes.swap(T.tlas.nodes);
-  out->tlas.prim.swap(T.tlas.prim);
-  out->tlas_nodes.swap(T.nodes);
-  out->wave_tlas.swap(T.wave);
-  out->max_tlas_depth = T.depth;
+  finish_repose(B, trans, &T, out);
   return "";
+}
+
+std::string prepare_repose_supplied(const BuiltScene& B, const uint32_t* objects, uint32_t n, const SuppliedPoses& P, ReposedTop* out,
+                                    bool* bad_argument) {
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  *bad_argument = true;
+  const std::string refused = check_repose_list(B, objects, n);
+  if (!refused.empty()) return refused;
+  if (B.flat.use_bvh && !P.prebuilt && !P.boxes6) return "a scene with BVHs needs the posed boxes or the BVH<Object> built from them";
+  *bad_argument = false;
+  // the objects that are not listed keep what the committed records hold (their id is the insertion index + 1)
+  Top T;
+  std::vector<Mat4> trans(nobj);
+  T.itrans.resize(nobj);
+  T.has_trans.resize(nobj);
+  for (const Object& o : B.flat.objects) {
+    const uint32_t i = o.id - 1u;
+    trans[i] = B.inputs[i].trans;
+    T.itrans[i] = o.itrans;
+    T.has_trans[i] = o.has_trans != 0u;
+  }
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t i = objects[k];
+    trans[i] = P.trans[k];
+    T.itrans[i] = P.itrans[k];
+    T.has_trans[i] = P.has_trans[k] != 0u;
+  }
+  std::vector<Box> obj_boxes;
+  if (B.flat.use_bvh && !P.prebuilt) {
+    obj_boxes.resize(nobj);
+    std::memcpy(static_cast<void*>(obj_boxes.data()), P.boxes6, (size_t)nobj * sizeof(Box));
+  }
+  if (!tree_top(obj_boxes, nobj, B.flat.use_bvh, P.prebuilt, &T)) return "BVH<Object> build does not terminate (coincident object centroids)";
+  out->listed.assign(objects, objects + n);
+  out->trans.assign(P.trans, P.trans + n);
+  finish_repose(B, trans, &T, out);
+  return "";
+}
+
+void posed_values(const Mat4& trans, const float local_box6[6], Mat4* itrans, uint32_t* has_trans, float box6[6]) {
+  *itrans = mat_inverse(trans);
+  *has_trans = mat_ne_identity(trans) ? 1u : 0u;
+  Box ob;
+  for (int a = 0; a < 3; a++) { ob.mn[a] = local_box6[a]; ob.mx[a] = local_box6[3 + a]; }
+  if (*has_trans) ob.transform(trans);
+  for (int a = 0; a < 3; a++) { box6[a] = ob.mn[a]; box6[3 + a] = ob.mx[a]; }
 }
 
 void apply_repose(BuiltScene* built, ReposedTop* top) {

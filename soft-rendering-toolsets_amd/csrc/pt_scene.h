@@ -193,6 +193,25 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
 std::string prepare_repose(const BuiltScene& built, const uint32_t* objects, const Mat4* trans, uint32_t n, ReposedTop* out,
                            bool* bad_argument);
 void apply_repose(BuiltScene* built, ReposedTop* top);
+// srt_pt_repose's refusals alone: "" or why the list cannot be re-posed (out of range, a duplicate, an area light).
+std::string check_repose_list(const BuiltScene& built, const uint32_t* objects, uint32_t n);
+// prepare_repose with the pose-dependent values supplied by the caller instead of computed (srt_pt_repose_device: a kernel
+// computed them, pt_pose.h): trans / itrans / has_trans of the n listed objects in list order, and either the posed boxes of ALL
+// objects in insertion order (six floats each; the BVH<Object> is then built here, by build_scene's rule) or the BVH<Object> the
+// caller built over them (moved from).  A list scene needs neither.  The objects that are not listed keep the values of their
+// committed records.  mat_inverse, mat_ne_identity and Box::transform stay the definition the supplied values are held to
+// (posed_values states them for one object); nothing here recomputes them.
+struct SuppliedPoses {
+  const Mat4* trans = nullptr;
+  const Mat4* itrans = nullptr;
+  const uint32_t* has_trans = nullptr;
+  const float* boxes6 = nullptr;
+  HostBVH* prebuilt = nullptr;
+};
+std::string prepare_repose_supplied(const BuiltScene& built, const uint32_t* objects, uint32_t n, const SuppliedPoses& poses, ReposedTop* out,
+                                    bool* bad_argument);
+// What the Object ctor and Object::bbox make of one transform and one object-space box (rays/object.h:18-21, 51-55).
+void posed_values(const Mat4& trans, const float local_box6[6], Mat4* itrans, uint32_t* has_trans, float box6[6]);
 
 // What srt_pt_update_mesh derives for new vertex arrays of ONE mesh of a built scene (an object added by srt_pt_add_mesh: not an
 // instance, a sphere or an area light; same vertex count, same index buffer), built next to the scene: the mesh's
