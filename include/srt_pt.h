@@ -144,6 +144,8 @@ int srt_pt_group_set_ray_log(srt_pt_group* g, uint32_t capacity);
 int srt_pt_group_read_ray_log(srt_pt_group* g, int lane, srt_pt_logged_ray* out, size_t cap, size_t* n_out, uint64_t* dropped);
 /* srt_pt_set_normal_colors (below) on every member. */
 int srt_pt_group_set_normal_colors(srt_pt_group* g, int on);
+/* srt_pt_set_dynamic_lights (below) on every member. */
+int srt_pt_group_set_dynamic_lights(srt_pt_group* g, int on);
 /* Device time of the exchange step of srt_pt_group_render_epoch[_device] - from the moment rank 0's own tiles are rendered to the end of
  * the un-tiling kernel on rank 0's stream: the gather (RCCL, or copies between ranks that share a device) and what it waits for, i.e. the
  * slowest other rank - summed over the epochs since the previous call (HIP events; waits for them); then recording on / off.  A diagnostic
@@ -209,10 +211,32 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh);
  * committed with use_bvh == 0) and the tables that follow object order are uploaded again; no BVH<Triangle> is rebuilt and no
  * triangle, normal or BVH<Triangle> record is uploaded.  Afterwards the scene equals, bit for bit in everything it computes, a
  * fresh srt_pt_scene_begin .. srt_pt_scene_commit of the same objects with the new transforms.  SRT_ERR_INVALID: an area light
- * in the list (its light tables depend on its pose: commit again), a duplicate, an index out of range.  SRT_ERR_STATE: no
+ * in the list (its light tables depend on its pose: commit again) unless srt_pt_set_dynamic_lights, a duplicate, an index out of range.  SRT_ERR_STATE: no
  * committed scene.  New poses that make the reference's BVH<Object> build non-terminating or too deep for the traversal stacks
  * fail as srt_pt_scene_commit does (SRT_ERR_UNSUPPORTED) - and the committed scene stays exactly as it was. */
 int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n);
+/* Area lights in srt_pt_repose[_device], srt_pt_update_mesh[_device], srt_pt_refit_mesh[_device] and srt_pt_skin_create.  Default:
+ * off - those calls refuse an area light with the status and message they always had, and no output of any call changes.  While
+ * it is on:
+ *   srt_pt_repose[_device] take emissive meshes (is_area_light) and emissive spheres (srt_pt_add_sphere_light) in their list: next to
+ *   the object record, the BVH<Object> and the tables of object order, each listed light's record in the light list - has_trans,
+ *   trans, itrans and Object::pdf's pair T = I * trans, iT = itrans * I (rays/object.h:90-94; identities when trans == I) - and the
+ *   2 / |cross(T v1 - T v0, T v2 - T v0)| factor of Triangle::pdf (student/tri_mesh.cpp:137) of each of its triangles take the
+ *   values a fresh commit with the new transform gives them; the object-space corners and the light-list triangle copies stay.
+ *   srt_pt_update_mesh[_device] / srt_pt_refit_mesh[_device] take an emissive MESH (a sphere light stays refused as a sphere): the
+ *   object's triangles and BVH<Triangle> go the way any mesh's go, and the light-list copy (Tri_Mesh(mesh, false), index order)
+ *   and the light's per-triangle sample corners and factors are rewritten in place; no count changes.
+ *   srt_pt_skin_create takes an emissive mesh; srt_pt_skin_pose[_refit] go through the two calls above, and fail with their refusal
+ *   if the switch has been cleared since.
+ * After a successful call the scene computes, bit for bit, what a fresh commit of the same description computes; a zero-area
+ * light triangle (factor inf) and a singular pose (infinities, NaNs) are what a fresh commit gives too, not refusals.  In every
+ * failing case the committed scene stays exactly as it was, light tables included: no live light array is written before the
+ * verdict.  The device forms write the light tables with kernels after their verdict and their wait (pt_light_update.hip) and
+ * upload no light record; the host forms upload the listed lights' records (272 B per light, 64 B per light triangle, and after
+ * new vertices 132 B per triangle of the light-list copy).  An emissive mesh's index buffer (12 B per triangle) is resident from
+ * the commit when the switch was on by then, otherwise from the light's first update, refit or skin.  May be set or cleared
+ * whenever nothing of the context is being enqueued (the rule of srt_pt_set_elision), before or after srt_pt_scene_commit. */
+int srt_pt_set_dynamic_lights(srt_pt* pt, int on);
 /* The same with the transforms in device memory (a simulation's output: a rigid-body kernel, a torch op,
  * srt_pt_particle_transforms_device): `objects` is a host array of n insertion indices as above, d_trans holds n * 16 floats in
  * Mat4::data order and is read on `stream` (a hipStream_t; NULL: the null stream) behind whatever the caller enqueued there.
@@ -253,8 +277,8 @@ int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_p
  * replaced as in srt_pt_repose.  Afterwards the scene equals, bit for bit in everything it computes, a fresh srt_pt_scene_begin
  * .. srt_pt_scene_commit of the same objects with the new arrays; only storage and counters may differ.  SRT_ERR_STATE: no
  * committed scene.  SRT_ERR_INVALID: a NULL argument, an index out of range, a sphere or sphere light, an instance (the message
- * names its source: update that), an area light (its light-list copy and light tables depend on the vertices: commit again),
- * nverts differing from the committed count.  Arrays that make the reference's BVH<Triangle> or BVH<Object> build non-terminating
+ * names its source: update that), an area light (its light-list copy and light tables depend on the vertices: commit again)
+ * unless srt_pt_set_dynamic_lights, nverts differing from the committed count.  Arrays that make the reference's BVH<Triangle> or BVH<Object> build non-terminating
  * or too deep for the traversal stacks fail as srt_pt_scene_commit does (SRT_ERR_UNSUPPORTED).  In every failing case the
  * committed scene stays exactly as it was, on the host and on the device: everything is built aside and checked before the
  * first write.  (A HIP failure after that point - out of device memory while the tables are replaced - is SRT_ERR_HIP and leaves
@@ -291,7 +315,8 @@ int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const f
  * aside and the top half is built aside before the first write to a live array.  With a scene committed with use_bvh == 0 there
  * is no tree and the call does what srt_pt_update_mesh does.  A later srt_pt_update_mesh on a refitted mesh rebuilds it (the
  * scene then equals a fresh commit); a skin created before a refit stays valid.  A refitted tree is valid but may be worse than
- * a rebuilt one: srt_pt_mesh_tree_cost tells. */
+ * a rebuilt one: srt_pt_mesh_tree_cost tells.  The refusals are srt_pt_update_mesh's: an area light is refused unless
+ * srt_pt_set_dynamic_lights. */
 int srt_pt_refit_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts);
 /* The same with the two arrays in device memory: copies and kernels are enqueued on `stream` (a hipStream_t; NULL: the null
  * stream), which the call synchronises where the host needs a verdict (the arrays come back once, 24 B per vertex, and are
@@ -322,8 +347,8 @@ typedef struct srt_pt_skin_joint {
     float radius;
 } srt_pt_skin_joint;
 /* find_joints.  Needs a committed scene (SRT_ERR_STATE).  `object`, and SRT_ERR_INVALID with its messages for a NULL argument,
- * an index out of range, a sphere, an instance, an area light and nverts differing from the committed count, are as for
- * srt_pt_update_mesh; njoints == 0 is SRT_ERR_INVALID too.  bind_positions / bind_normals (nverts * 3 floats each) are the
+ * an index out of range, a sphere, an instance, an area light (unless srt_pt_set_dynamic_lights) and nverts differing from the
+ * committed count, are as for srt_pt_update_mesh; njoints == 0 is SRT_ERR_INVALID too.  bind_positions / bind_normals (nverts * 3 floats each) are the
  * object's bind-pose mesh - the committed vertices may already be a posed frame - and stay on the device with the skin.  The host
  * computes Mat4::inverse(bind) (lib/mat4.h:299-351, the `/= det()` included) once per joint; kernels build the vertex -> joints
  * map as CSR (count, exclusive scan, fill; a vertex's joints in ascending index) with the reference's capsule test per (vertex,

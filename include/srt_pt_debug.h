@@ -63,7 +63,7 @@ int srt_pt_counters(srt_pt* pt, uint64_t out[8]);
  * that srt_pt_add_instance shared and srt_pt_repose left the triangles alone.  Works on a host-only context (device = -1): the
  * two byte figures of the device are then 0 and nothing is ever uploaded.  The first four are 0 before the first commit.
  * The resident bytes include the index buffers srt_pt_update_mesh's kernels read (12 B per triangle of every mesh that is neither
- * an instance nor an area light).  A successful srt_pt_update_mesh[_device] adds exactly 1 to the builds (nothing in a scene
+ * an instance nor an area light; under srt_pt_set_dynamic_lights an emissive mesh's too, from the commit or from its first update).  A successful srt_pt_update_mesh[_device] adds exactly 1 to the builds (nothing in a scene
  * committed without BVHs, where nothing is built) and to the two upload figures the bytes it actually copied from host to device:
  * the vertex arrays (host form), the primitive order of a host build, the nodes and records that are new or moved, the tables of
  * object order - the records its kernel writes on the device are not uploads.  A refused update adds nothing to the builds. */
@@ -75,6 +75,14 @@ int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]);
  * 8 B per node and per interior record, the level offsets).  A refused refit adds nothing to any figure: the vertices it had
  * staged are not counted at all, and tables it made stay resident and are counted with the mesh's first refit that succeeds. */
 int srt_pt_refit_count(srt_pt* pt, uint64_t* refits);
+/* The area-light tables of the committed scene (what srt_pt_set_dynamic_lights keeps true).  Returns the number of lights, or a
+ * negative status.  Per light li < cap_lights: heads[4 li ..] = {has_trans, first light triangle (tri_base - first light triangle
+ * of the scene), triangle count, insertion index of the object}, mats[64 li ..] = trans, itrans, pdfT, pdfiT.  Per light triangle
+ * t < cap_tris (every light's, in light order): tris[31 t ..] = v0 v1 v2 (four floats each, the padding included), area_term, then
+ * p0 e1 e2 and n0 n1 n2 of the light-list copy (three floats each).  from_device == 0 reads the host's mirror; from_device != 0
+ * waits for the device and reads the device arrays back (SRT_ERR_UNSUPPORTED on a host-only context).  The arrays may be NULL
+ * where their capacity is 0. */
+long srt_pt_dump_lights(srt_pt* pt, int from_device, uint32_t* heads, float* mats, size_t cap_lights, float* tris, size_t cap_tris);
 /* cosf/sinf of the kernel (SRT-MATH v2) for n host floats; parity tests compare them with glibc. */
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);
 /* The kernels' atan2f (glibc 2.35's algorithm restated; Spot_Light::sample) evaluated on the device. */

@@ -104,6 +104,10 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_rays_elided.argtypes = [c_void_p, POINTER(c_uint64), c_int]
     lib.srt_pt_set_normal_colors.argtypes = [c_void_p, c_int]
     lib.srt_pt_group_set_normal_colors.argtypes = [c_void_p, c_int]
+    lib.srt_pt_set_dynamic_lights.argtypes = [c_void_p, c_int]
+    lib.srt_pt_group_set_dynamic_lights.argtypes = [c_void_p, c_int]
+    lib.srt_pt_dump_lights.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
+    lib.srt_pt_dump_lights.restype = c_long
     lib.srt_pt_math_exp.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_pow.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_tonemap.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p]
@@ -659,6 +663,30 @@ class Pathtracer:
         Spectrum::direction(normal) of the camera ray's hit (include/srt_pt.h).  Takes effect at the next launch."""
         self._check(self._lib, self._lib.srt_pt_set_normal_colors(self._ctx, int(bool(on))))
 
+    def set_dynamic_lights(self, on: bool) -> None:
+        """srt_pt_set_dynamic_lights: repose / update_mesh / refit_mesh / create_skin (and their device forms) accept area lights and
+        keep the light tables what a fresh commit would make them.  Off by default; before or after build_scene."""
+        self._check(self._lib, self._lib.srt_pt_set_dynamic_lights(self._ctx, int(bool(on))))
+
+    def dump_lights(self, from_device: bool = False) -> dict:
+        """srt_pt_dump_lights: {"heads": uint32 (lights, 4) = has_trans, first light triangle, triangle count, insertion index;
+        "mats": float32 (lights, 4, 16) = trans, itrans, pdfT, pdfiT; "tris": float32 (light triangles, 31) = v0 v1 v2 (four floats
+        each), area_term, p0 e1 e2, n0 n1 n2} from the host's mirror or read back from the device."""
+        def call(heads, mats, nl, tris, nt):
+            n = self._lib.srt_pt_dump_lights(self._ctx, int(bool(from_device)), _p(heads) if nl else None, _p(mats) if nl else None, nl,
+                                             _p(tris) if nt else None, nt)
+            if n < 0:
+                raise self._SrtError(int(n), self._lib.srt_last_error().decode())
+            return int(n)
+
+        nl = call(None, None, 0, None, 0)
+        heads, mats = np.zeros((nl, 4), np.uint32), np.zeros((nl, 4, 16), np.float32)
+        call(heads, mats, nl, None, 0)
+        nt = int(heads[:, 2].sum())
+        tris = np.zeros((nt, 31), np.float32)
+        call(heads, mats, nl, tris, nt)
+        return {"heads": heads, "mats": mats, "tris": tris}
+
     def rays_elided(self, reset: bool = False) -> int:
         n = c_uint64(0)
         self._check(self._lib, self._lib.srt_pt_rays_elided(self._ctx, ctypes.byref(n), int(reset)))
@@ -801,6 +829,10 @@ class PathtracerGroup:
     def set_normal_colors(self, on: bool) -> None:
         """srt_pt_group_set_normal_colors: the normal-colors debug view on every member."""
         self._check(self._lib, self._lib.srt_pt_group_set_normal_colors(self._g, int(bool(on))))
+
+    def set_dynamic_lights(self, on: bool) -> None:
+        """srt_pt_group_set_dynamic_lights: area lights in repose / update_mesh / refit_mesh / create_skin on every member."""
+        self._check(self._lib, self._lib.srt_pt_group_set_dynamic_lights(self._g, int(bool(on))))
 
     def render_epoch(self, seed: int, sample_base: int, samples: int) -> np.ndarray:
         out = np.zeros((self.out_h, self.out_w, 3), np.float32)

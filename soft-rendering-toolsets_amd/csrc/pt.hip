@@ -26,6 +26,7 @@
 
 #include "pt_bvh_device.h"
 #include "pt_device.h"
+#include "pt_light_update.h"
 #include "pt_pose.h"
 #include "pt_scene.h"
 #include "pt_skin.h"
@@ -463,6 +464,11 @@ struct srt_pt {
   uint32_t* d_pose_list = nullptr; size_t pose_list_n = 0;
   PoseOut* d_pose_out = nullptr; size_t pose_out_n = 0;
   uint32_t* d_slot_ordinal = nullptr; size_t slot_ordinal_n = 0;
+  // srt_pt_set_dynamic_lights (the switch itself is built.dynamic_lights): srt_pt_repose_device's table of the listed lights
+  // ({position in the list, light} pairs), grown on demand and kept; and the bytes of index buffers that went up for a light's
+  // first update or refit (ensure_mesh_idx) and are counted with the verdict
+  uint32_t* d_light_list = nullptr; size_t light_list_n = 0;
+  uint64_t idx_uncounted = 0;
   // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
   uint64_t scene_generation = 0;
 };
@@ -1153,7 +1159,7 @@ int srt_pt_destroy(srt_pt* pt) {
     bvh_workspace_free(&pt->bvh_ws);
     drop_refit_tables(pt, UINT32_MAX);
     drop_pose_tables(pt);
-    (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal);
+    (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal); (void)hipFree(pt->d_light_list);
     if (pt->h_fault) (void)hipHostFree(pt->h_fault);
     if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);
     for (auto& kv : pt->epoch_buffers) {
@@ -1331,11 +1337,12 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
     pt->idx_off.assign(pt->built.inputs.size(), SIZE_MAX);
     for (size_t i = 0; i < pt->built.inputs.size(); i++) {
       const ObjectInput& in = pt->built.inputs[i];
-      if (in.kind != OBJ_MESH || in.source >= 0 || in.is_light) continue;
+      if (in.kind != OBJ_MESH || in.source >= 0 || (in.is_light && !pt->built.dynamic_lights)) continue;   // (a light's goes up later when the switch is set later: ensure_mesh_idx)
       pt->idx_off[i] = idx.size();
       idx.insert(idx.end(), in.mesh.idx.begin(), in.mesh.idx.end());
     }
     pt->idx_words = idx.size();
+    pt->idx_uncounted = 0;
     if ((st = upload(pt, &pt->d_idx, idx))) return st;
   }
   pt->committed = true;
@@ -1347,6 +1354,63 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
 }  // extern "C"
 
 namespace {
+
+// The index buffer of mesh `object` on the device.  Every mesh that can be updated has its own from the commit on; an emissive
+// mesh has it from the commit only when srt_pt_set_dynamic_lights was on by then - otherwise it is appended here, at the light's
+// first update, refit or skin.  Nothing a render kernel reads; the caller has waited for whatever reads d_idx.
+int ensure_mesh_idx(srt_pt* pt, uint32_t object) {
+  if (pt->idx_off[object] != SIZE_MAX) return SRT_OK;
+  const std::vector<uint32_t>& idx = pt->built.inputs[object].mesh.idx;
+  uint32_t* fresh = nullptr;
+  SRT_HIP(hipMalloc(&fresh, (pt->idx_words + idx.size()) * sizeof(uint32_t)));
+  if ((pt->idx_words && hipMemcpy(fresh, pt->d_idx, pt->idx_words * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess) ||
+      hipMemcpy(fresh + pt->idx_words, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(fresh);
+    return srt::fail(SRT_ERR_HIP, "index buffer of object %u: device copy failed", object);
+  }
+  if (pt->d_idx) (void)hipFree(pt->d_idx);
+  pt->d_idx = fresh;
+  pt->idx_off[object] = pt->idx_words;
+  pt->idx_words += idx.size();
+  pt->idx_uncounted += idx.size() * sizeof(uint32_t);
+  return SRT_OK;
+}
+
+// Host forms of the dynamic-light calls (srt_pt_repose, srt_pt_update_mesh, srt_pt_refit_mesh): the light's record and its
+// LightTri records from the host mirror, and - after new vertices - its light-list triangle copies.  The device forms run the
+// kernels of pt_light_update.hip instead and upload none of this.
+int upload_light(srt_pt* pt, uint32_t li, bool triangles) {
+  const FlatScene& F = pt->built.flat;
+  const Light& L = F.lights[li];
+  const size_t lt = (size_t)(L.tri_base - F.light_tri_first), n = L.ntri;
+  SRT_HIP(hipMemcpy(pt->d_lights + li, &L, sizeof(Light), hipMemcpyHostToDevice));
+  if (n) SRT_HIP(hipMemcpy(pt->d_ltris + lt, &F.light_tris[lt], n * sizeof(LightTri), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += sizeof(Light) + n * sizeof(LightTri);
+  if (triangles && n) {
+    SRT_HIP(hipMemcpy(pt->d_tris + L.tri_base, &F.tris[L.tri_base], n * sizeof(Tri), hipMemcpyHostToDevice));
+    SRT_HIP(hipMemcpy(pt->d_nrm + L.tri_base, &F.tri_nrm[L.tri_base], n * sizeof(TriNrm), hipMemcpyHostToDevice));
+    SRT_HIP(hipMemcpy(pt->d_tri_packed + 9 * (size_t)L.tri_base, &F.tri_packed[9 * (size_t)L.tri_base], 9 * n * sizeof(float), hipMemcpyHostToDevice));
+    const uint64_t bytes = n * (sizeof(Tri) + sizeof(TriNrm) + 9 * sizeof(float));
+    pt->bytes_uploaded += bytes;
+    pt->tri_bytes_uploaded += bytes;
+  }
+  return SRT_OK;
+}
+
+// The light tables of an emissive mesh after new vertices (the verdict is in, the host mirror is true, nothing is in flight):
+// the device forms rewrite them with the kernel from the arrays where they are, the host forms upload them.
+int write_light_mesh_device(srt_pt* pt, hipStream_t s, uint32_t object, bool device_form, const float* d_pos, const float* d_nrm) {
+  const int32_t li = light_of(pt->built, object);
+  if (li < 0) return SRT_OK;
+  if (!device_form) return upload_light(pt, (uint32_t)li, true);
+  const FlatScene& F = pt->built.flat;
+  const Light& L = F.lights[(size_t)li];
+  launch_light_triangles(s, d_pos, d_nrm, pt->d_idx + pt->idx_off[object], L.ntri, pt->d_lights + li, pt->d_tris + L.tri_base, pt->d_nrm + L.tri_base,
+                         pt->d_tri_packed + 9 * (size_t)L.tri_base, pt->d_ltris + (L.tri_base - F.light_tri_first));
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
 
 // Device side of a mesh update whose verdict is in (srt_pt_update_mesh): the node and record arrays after the scene layer
 // re-packed them.  [0, keep) of the old array has not moved and [from, size) of the new one is new or has moved; with another
@@ -1415,6 +1479,7 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
   const bool on_device = pt->device >= 0;
   if (!on_device && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
   const bool use_bvh = pt->built.flat.use_bvh;
+  const bool device_form = h_pos == nullptr;
   const MeshStore old = pt->built.store[object];
   const uint32_t ntri = old.ntri;
   const size_t vfloats = 3 * (size_t)nverts;
@@ -1423,6 +1488,8 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
     SRT_HIP(hipSetDevice(pt->device));
     SRT_HIP(hipStreamSynchronize(pt->stream));
     SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old arrays
+    const int ist = ensure_mesh_idx(pt, object);          // (an emissive mesh's first update under srt_pt_set_dynamic_lights)
+    if (ist != SRT_OK) return ist;
     if (h_pos) {                                          // 24 B per vertex up, into the staging (nothing of the live scene yet)
       int st;
       if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
@@ -1475,8 +1542,11 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
   if (use_bvh) pt->blas_builds++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
+  pt->bytes_uploaded += pt->idx_uncounted;
+  pt->idx_uncounted = 0;
   // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
-  const int st = write_updated_mesh(pt, s, object, old, old_tlas, old_nodes, old_recs, d_pos, d_nrm, d_mesh_idx);
+  int st = write_updated_mesh(pt, s, object, old, old_tlas, old_nodes, old_recs, d_pos, d_nrm, d_mesh_idx);
+  if (st == SRT_OK) st = write_light_mesh_device(pt, s, object, device_form, d_pos, d_nrm);
   if (st != SRT_OK) pt->committed = false;
   return st;
 }
@@ -1544,6 +1614,7 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
   const bool on_device = pt->device >= 0;
   if (!on_device && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
   const MeshStore m = pt->built.store[object];
+  const bool device_form = h_pos == nullptr;
   const size_t vfloats = 3 * (size_t)nverts;
   std::vector<float> back_pos, back_nrm, node_boxes;
   RefitTables* T = nullptr;
@@ -1552,6 +1623,8 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
     SRT_HIP(hipSetDevice(pt->device));
     SRT_HIP(hipStreamSynchronize(pt->stream));
     SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old arrays
+    const int ist = ensure_mesh_idx(pt, object);          // (an emissive mesh's first refit under srt_pt_set_dynamic_lights)
+    if (ist != SRT_OK) return ist;
     if (h_pos) {                                          // 24 B per vertex up, into the staging (nothing of the live scene yet)
       for (size_t k = 0; k < vfloats; k++)
         if (!std::isfinite(h_pos[k])) return srt::fail(SRT_ERR_INVALID, "%s: vertex %zu of the new positions has a non-finite coordinate", what, k / 3);
@@ -1605,8 +1678,9 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
   drop_pose_tables(pt);                                   // the object-space boxes changed
-  pt->bytes_uploaded += staged_bytes + T->uncounted_bytes;   // the vertices of the host form; the tables, at the mesh's first successful refit
+  pt->bytes_uploaded += staged_bytes + T->uncounted_bytes + pt->idx_uncounted;   // the vertices of the host form; the tables, at the mesh's first successful refit
   T->uncounted_bytes = 0;
+  pt->idx_uncounted = 0;
   // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
   const FlatScene& F = pt->built.flat;
   auto write = [&]() -> int {
@@ -1627,7 +1701,8 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
       return st;
     return SRT_OK;
   };
-  const int st = write();
+  int st = write();
+  if (st == SRT_OK) st = write_light_mesh_device(pt, s, object, device_form, d_pos, d_nrm);
   if (st != SRT_OK) pt->committed = false;
   return st;
 }
@@ -1793,7 +1868,13 @@ int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions,
   k->ntri = pt->built.store[object].ntri;
   k->inv.resize(16 * (size_t)njoints);
   k->mats.resize(16 * (size_t)njoints);
-  const int st = skin_build(k, bind_positions, bind_normals, joints);
+  int st = SRT_OK;
+  if (pt->idx_off[object] == SIZE_MAX) {                  // an emissive mesh under srt_pt_set_dynamic_lights: its index buffer goes up now
+    if (hipSetDevice(pt->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: synchronisation failed");
+    else st = ensure_mesh_idx(pt, object);
+    if (st == SRT_OK) { pt->bytes_uploaded += pt->idx_uncounted; pt->idx_uncounted = 0; }
+  }
+  if (st == SRT_OK) st = skin_build(k, bind_positions, bind_normals, joints);
   if (st != SRT_OK) { skin_free(k); return st; }
   *skin = k;
   return SRT_OK;
@@ -1908,6 +1989,10 @@ int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint3
     }
     if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
       return st;
+    for (uint32_t k = 0; k < n; k++) {                    // listed area lights (srt_pt_set_dynamic_lights): their records, as the host mirror has them now
+      const int32_t li = light_of(pt->built, objects[k]);
+      if (li >= 0 && (st = upload_light(pt, (uint32_t)li, false))) { pt->committed = false; return st; }
+    }
   }
   return SRT_OK;
 }
@@ -2017,6 +2102,22 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
       d_ordinal = pt->d_slot_ordinal;
     }
   }
+  // the listed area lights (srt_pt_set_dynamic_lights), still aside: {position in the list, light} pairs for the light kernels
+  std::vector<uint32_t> light_list;
+  uint32_t light_max_ntri = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const int32_t li = light_of(pt->built, objects[k]);
+    if (li < 0) continue;
+    light_list.push_back(k);
+    light_list.push_back((uint32_t)li);
+    light_max_ntri = std::max(light_max_ntri, pt->built.flat.lights[(size_t)li].ntri);
+  }
+  if (!light_list.empty()) {
+    if ((st = ensure(&pt->d_light_list, &pt->light_list_n, light_list.size()))) return refuse(st);
+    if (hipMemcpyAsync(pt->d_light_list, light_list.data(), light_list.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+      return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
+    staged_bytes += (uint64_t)light_list.size() * 4;
+  }
   // the verdict is in; nothing of the context may be in flight while the live arrays change
   const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
   if (hipStreamSynchronize(s) != hipSuccess || hipStreamSynchronize(pt->stream) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
@@ -2036,6 +2137,13 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
     }
     // the records in place (the object count never changes): gathered on the device by the new order
     launch_pose_records(s, pt->d_pose_records, d_prim, d_ordinal, nobj, F.tlas_nodes, pt->d_objects);
+    if (!light_list.empty()) {
+      // the listed lights' records from the pose kernel's output where it lies, then their area terms under the new pdfT: no upload
+      const uint32_t nl = (uint32_t)(light_list.size() / 2);
+      launch_light_records(s, pt->d_light_list, nl, pt->d_pose_out, n, pt->d_lights, (uint32_t)F.lights.size());
+      launch_light_area_terms(s, pt->d_light_list, nl, light_max_ntri, pt->d_lights, (uint32_t)F.lights.size(), F.light_tri_first, pt->d_ltris,
+                              (uint32_t)F.light_tris.size());
+    }
     SRT_HIP(hipStreamSynchronize(s));
     SRT_HIP(hipGetLastError());
     if ((w = upload(pt, &pt->d_wave, F.wave_tlas)) || (w = upload(pt, &pt->d_wave_lazy, F.wave_lazy))) return w;
@@ -2411,6 +2519,12 @@ int srt_pt_set_elision(srt_pt* pt, int on) {
   return SRT_OK;
 }
 
+int srt_pt_set_dynamic_lights(srt_pt* pt, int on) {
+  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_dynamic_lights: NULL context");
+  pt->built.dynamic_lights = on != 0;
+  return SRT_OK;
+}
+
 int srt_pt_set_normal_colors(srt_pt* pt, int on) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_normal_colors: NULL context");
   pt->normal_colors = on ? 1 : 0;
@@ -2540,6 +2654,49 @@ long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_
   if (order)
     for (size_t i = 0; i < b->prim.size(); i++) order[i] = in ? in->mesh.idx[3 * b->prim[i]] : b->prim[i] + 1;
   return (long)b->nodes.size();
+}
+
+long srt_pt_dump_lights(srt_pt* pt, int from_device, uint32_t* heads, float* mats, size_t cap_lights, float* tris, size_t cap_tris) {
+  if (!pt || (cap_lights && (!heads || !mats)) || (cap_tris && !tris)) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_lights: NULL argument");
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_lights before srt_pt_scene_commit");
+  if (from_device && pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_dump_lights: this context is host-only, there are no device arrays to read (from_device = 0 reads the host's)");
+  const FlatScene& F = pt->built.flat;
+  const size_t nl = F.lights.size(), nt = F.light_tris.size();
+  std::vector<Light> lights(F.lights);
+  std::vector<LightTri> ltris(F.light_tris);
+  std::vector<Tri> tr(F.tris.begin() + F.light_tri_first, F.tris.end());
+  std::vector<TriNrm> tn(F.tri_nrm.begin() + F.light_tri_first, F.tri_nrm.end());
+  if (tr.size() != nt || tn.size() != nt) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_lights: the light tables disagree about their triangle count");
+  if (from_device) {
+    SRT_HIP(hipSetDevice(pt->device));
+    SRT_HIP(hipDeviceSynchronize());
+    if (nl) SRT_HIP(hipMemcpy(lights.data(), pt->d_lights, nl * sizeof(Light), hipMemcpyDeviceToHost));
+    if (nt) {
+      SRT_HIP(hipMemcpy(ltris.data(), pt->d_ltris, nt * sizeof(LightTri), hipMemcpyDeviceToHost));
+      SRT_HIP(hipMemcpy(tr.data(), pt->d_tris + F.light_tri_first, nt * sizeof(Tri), hipMemcpyDeviceToHost));
+      SRT_HIP(hipMemcpy(tn.data(), pt->d_nrm + F.light_tri_first, nt * sizeof(TriNrm), hipMemcpyDeviceToHost));
+    }
+  }
+  size_t li = 0;
+  for (size_t i = 0; i < pt->built.inputs.size() && li < nl; i++) {
+    if (light_of(pt->built, (uint32_t)i) < 0) continue;
+    if (li < cap_lights) {
+      const Light& L = lights[li];
+      heads[4 * li] = L.has_trans; heads[4 * li + 1] = L.tri_base - F.light_tri_first; heads[4 * li + 2] = L.ntri; heads[4 * li + 3] = (uint32_t)i;
+      std::memcpy(mats + 64 * li, &L.trans, 64 * sizeof(float));   // trans, itrans, pdfT, pdfiT
+    }
+    li++;
+  }
+  for (size_t t = 0; t < nt && t < cap_tris; t++) {
+    float* o = tris + 31 * t;
+    std::memcpy(o, &ltris[t], 13 * sizeof(float));                 // v0 v1 v2 (four floats each, padding included), area_term
+    for (int a = 0; a < 3; a++) {
+      o[13 + a] = tr[t].p0[a]; o[16 + a] = tr[t].e1[a]; o[19 + a] = tr[t].e2[a];
+      o[22 + a] = tn[t].n0[a]; o[25 + a] = tn[t].n1[a]; o[28 + a] = tn[t].n2[a];
+    }
+  }
+  return (long)nl;
 }
 
 int srt_pt_counters(srt_pt* pt, uint64_t out[8]) {

@@ -496,6 +496,12 @@ int srt_pt_group_set_normal_colors(srt_pt_group* g, int on) {
   return SRT_OK;
 }
 
+int srt_pt_group_set_dynamic_lights(srt_pt_group* g, int on) {
+  if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_set_dynamic_lights: NULL group");
+  for (srt_pt* c : g->ctx) { const int st = srt_pt_set_dynamic_lights(c, on); if (st != SRT_OK) return st; }
+  return SRT_OK;
+}
+
 int srt_pt_group_set_ray_log(srt_pt_group* g, uint32_t capacity) {
   if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_set_ray_log: NULL group");
   for (srt_pt* c : g->ctx) { const int st = srt_pt_set_ray_log(c, capacity); if (st != SRT_OK) return st; }

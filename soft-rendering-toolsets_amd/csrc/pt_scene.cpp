@@ -410,10 +410,68 @@ Camera make_camera(const float iview[16], float vert_fov_deg, float aspect_ratio
   return c;
 }
 
+void light_record(const Mat4& trans, const Mat4& itrans, bool has_trans, Light* L) {
+  L->has_trans = has_trans ? 1u : 0u;
+  L->trans = trans;
+  L->itrans = itrans;
+  const Mat4 id = mat_identity();
+  L->pdfT = id;
+  L->pdfiT = id;
+  if (has_trans) {  // Object::pdf, rays/object.h:90-94
+    L->pdfT = mat_mul(id, trans);
+    L->pdfiT = mat_mul(itrans, id);
+  }
+}
+
+float light_area_term(const Mat4& pdfT, const float v0[3], const float v1[3], const float v2[3]) {
+  const float* v[3] = {v0, v1, v2};
+  float w[3][3];
+  for (int k = 0; k < 3; k++) mat_point(pdfT, v[k], w[k]);
+  // a = 2.0f / cross(v_1 - v_0, v_2 - v_0).norm()   (student/tri_mesh.cpp:137)
+  const float ax = w[1][0] - w[0][0], ay = w[1][1] - w[0][1], az = w[1][2] - w[0][2];
+  const float bx = w[2][0] - w[0][0], by = w[2][1] - w[0][1], bz = w[2][2] - w[0][2];
+  const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+  return 2.0f / std::sqrt(cx * cx + cy * cy + cz * cz);
+}
+
+LightTri light_tri_record(const Mat4& pdfT, const MeshInput& mesh, uint32_t t) {
+  LightTri lt;
+  std::memset(&lt, 0, sizeof lt);
+  const float* v[3] = {&mesh.pos[3 * (size_t)mesh.idx[3 * (size_t)t]], &mesh.pos[3 * (size_t)mesh.idx[3 * (size_t)t + 1]],
+                       &mesh.pos[3 * (size_t)mesh.idx[3 * (size_t)t + 2]]};
+  for (int a = 0; a < 3; a++) { lt.v0[a] = v[0][a]; lt.v1[a] = v[1][a]; lt.v2[a] = v[2][a]; }
+  lt.area_term = light_area_term(pdfT, v[0], v[1], v[2]);
+  return lt;
+}
+
+int32_t light_of(const BuiltScene& B, uint32_t object) {
+  if (object >= B.inputs.size() || !B.inputs[object].is_light || B.inputs[object].mesh.idx.empty()) return -1;
+  int32_t li = 0;   // lights are made in insertion order, one per emissive object that carries a mesh
+  for (uint32_t i = 0; i < object; i++)
+    if (B.inputs[i].is_light && !B.inputs[i].mesh.idx.empty()) li++;
+  return (size_t)li < B.flat.lights.size() ? li : -1;
+}
+
+void write_light_mesh(BuiltScene* built, uint32_t light, uint32_t object) {
+  FlatScene& F = built->flat;
+  const Light& L = F.lights[light];
+  const MeshInput& mesh = built->inputs[object].mesh;
+  std::vector<Tri> tris;
+  std::vector<TriNrm> tri_nrm;
+  std::vector<float> packed;
+  append_triangles(mesh, nullptr, &tris, &tri_nrm, &packed);
+  std::copy(tris.begin(), tris.end(), F.tris.begin() + L.tri_base);
+  std::copy(tri_nrm.begin(), tri_nrm.end(), F.tri_nrm.begin() + L.tri_base);
+  std::copy(packed.begin(), packed.end(), F.tri_packed.begin() + 9 * (size_t)L.tri_base);
+  for (uint32_t t = 0; t < L.ntri; t++) F.light_tris[(size_t)(L.tri_base - F.light_tri_first) + t] = light_tri_record(L.pdfT, mesh, t);
+}
+
 std::string build_scene(const std::vector<ObjectInput>& objects, const std::vector<Material>& materials, bool use_bvh,
                         BuiltScene* out) {
   BuiltScene& B = *out;
+  const bool dynamic_lights = B.dynamic_lights;
   B = BuiltScene();
+  B.dynamic_lights = dynamic_lights;
   B.inputs = objects;
   FlatScene& F = B.flat;
   F.use_bvh = use_bvh;
@@ -525,34 +583,11 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
     if (!in.is_light || in.mesh.idx.empty()) continue;
     Light L;
     std::memset(&L, 0, sizeof L);
-    L.has_trans = has_trans[i] ? 1u : 0u;
     L.tri_base = (uint32_t)F.tris.size();
     L.ntri = (uint32_t)in.mesh.idx.size() / 3;
-    L.trans = in.trans;
-    L.itrans = itrans[i];
-    const Mat4 id = mat_identity();
-    L.pdfT = id;
-    L.pdfiT = id;
-    if (has_trans[i]) {  // Object::pdf, rays/object.h:90-94
-      L.pdfT = mat_mul(id, in.trans);
-      L.pdfiT = mat_mul(itrans[i], id);
-    }
+    light_record(in.trans, itrans[i], has_trans[i], &L);
     append_triangles(in.mesh, nullptr, &F.tris, &F.tri_nrm, &F.tri_packed);
-    for (uint32_t t = 0; t < L.ntri; t++) {
-      LightTri lt;
-      std::memset(&lt, 0, sizeof lt);
-      const float* v[3] = {&in.mesh.pos[3 * in.mesh.idx[3 * t]], &in.mesh.pos[3 * in.mesh.idx[3 * t + 1]],
-                           &in.mesh.pos[3 * in.mesh.idx[3 * t + 2]]};
-      float w[3][3];
-      for (int k = 0; k < 3; k++) mat_point(L.pdfT, v[k], w[k]);
-      for (int a = 0; a < 3; a++) { lt.v0[a] = v[0][a]; lt.v1[a] = v[1][a]; lt.v2[a] = v[2][a]; }
-      // a = 2.0f / cross(v_1 - v_0, v_2 - v_0).norm()   (student/tri_mesh.cpp:137)
-      const float ax = w[1][0] - w[0][0], ay = w[1][1] - w[0][1], az = w[1][2] - w[0][2];
-      const float bx = w[2][0] - w[0][0], by = w[2][1] - w[0][1], bz = w[2][2] - w[0][2];
-      const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-      lt.area_term = 2.0f / std::sqrt(cx * cx + cy * cy + cz * cz);
-      F.light_tris.push_back(lt);
-    }
+    for (uint32_t t = 0; t < L.ntri; t++) F.light_tris.push_back(light_tri_record(L.pdfT, in.mesh, t));
     F.lights.push_back(L);
   }
   return "";
@@ -565,7 +600,8 @@ std::string check_repose_list(const BuiltScene& B, const uint32_t* objects, uint
     const uint32_t i = objects[k];
     if (i >= nobj) return "object " + std::to_string(i) + " is out of range (the scene has " + std::to_string(nobj) + " objects)";
     if (seen[i]) return "object " + std::to_string(i) + " is listed twice";
-    if (B.inputs[i].is_light) return "object " + std::to_string(i) + " is an area light: its light tables depend on its pose, commit the scene again";
+    if (B.inputs[i].is_light && !B.dynamic_lights)
+      return "object " + std::to_string(i) + " is an area light: its light tables depend on its pose, commit the scene again";
     seen[i] = true;
   }
   return "";
@@ -666,6 +702,22 @@ void apply_repose(BuiltScene* built, ReposedTop* top) {
   F.objects.swap(top->objects);
   B.tlas.nodes.swap(top->tlas.nodes);
   B.tlas.prim.swap(top->tlas.prim);
+  // a listed area light (BuiltScene::dynamic_lights): its Light record from the pose values its new object record carries, and
+  // the area terms of its triangles under the new pdfT; the object-space corners and the light-list triangle copies stay
+  for (size_t k = 0; k < top->listed.size(); k++) {
+    const int32_t li = light_of(B, top->listed[k]);
+    if (li < 0) continue;
+    for (const Object& o : F.objects) {
+      if (o.id != top->listed[k] + 1u) continue;
+      Light& L = F.lights[(size_t)li];
+      light_record(o.trans, o.itrans, o.has_trans != 0u, &L);
+      for (uint32_t t = 0; t < L.ntri; t++) {
+        LightTri& lt = F.light_tris[(size_t)(L.tri_base - F.light_tri_first) + t];
+        lt.area_term = light_area_term(L.pdfT, lt.v0, lt.v1, lt.v2);
+      }
+      break;
+    }
+  }
 }
 
 std::string check_mesh_update(const BuiltScene& B, uint32_t object, uint32_t nverts) {
@@ -675,7 +727,7 @@ std::string check_mesh_update(const BuiltScene& B, uint32_t object, uint32_t nve
   if (in.kind != OBJ_MESH) return "object " + std::to_string(object) + " is a sphere, not a mesh added by srt_pt_add_mesh";
   if (in.source >= 0)
     return "object " + std::to_string(object) + " is an instance: update its source, object " + std::to_string(in.source) + ", and every instance follows";
-  if (in.is_light)
+  if (in.is_light && !B.dynamic_lights)
     return "object " + std::to_string(object) + " is an area light: its light-list copy and light tables depend on its vertices, commit the scene again";
   if ((size_t)nverts * 3 != in.mesh.pos.size())
     return "object " + std::to_string(object) + " was added with " + std::to_string(in.mesh.pos.size() / 3) + " vertices, not " + std::to_string(nverts);
@@ -802,6 +854,8 @@ void apply_mesh_update(BuiltScene* built, MeshUpdate* update) {
   F.objects.swap(U.top.objects);
   B.tlas.nodes.swap(U.top.tlas.nodes);
   B.tlas.prim.swap(U.top.tlas.prim);
+  const int32_t li = light_of(B, U.object);          // an emissive mesh (BuiltScene::dynamic_lights): its light-list copy and LightTri records
+  if (li >= 0) write_light_mesh(built, (uint32_t)li, U.object);
 }
 
 void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32_t>& idx, std::vector<float>* boxes6) {
@@ -896,6 +950,8 @@ void apply_mesh_refit(BuiltScene* built, MeshRefit* refit) {
   std::copy(tris.begin(), tris.end(), F.tris.begin() + m.tri_base);
   std::copy(tri_nrm.begin(), tri_nrm.end(), F.tri_nrm.begin() + m.tri_base);
   std::copy(packed.begin(), packed.end(), F.tri_packed.begin() + 9 * (size_t)m.tri_base);
+  const int32_t li = light_of(B, R.object);          // an emissive mesh (BuiltScene::dynamic_lights): its light-list copy and LightTri records
+  if (li >= 0) write_light_mesh(built, (uint32_t)li, R.object);
 }
 
 double tree_cost(const HostBVH& tree) {

@@ -155,6 +155,9 @@ struct BuiltScene {
   std::vector<float> local_boxes;   // six floats per object in insertion order: the object-space box Object::bbox poses
   std::vector<MeshStore> store;     // per object in insertion order: an instance's is its source's
   uint64_t blas_builds = 0;         // BVH<Triangle> builds this build_scene performed (one per mesh that is not an instance)
+  // srt_pt_set_dynamic_lights: check_repose_list / check_mesh_update admit area lights, and the apply_* functions keep the light
+  // tables true (light_record, light_area_term, write_light_mesh below).  build_scene keeps the switch of the scene it replaces.
+  bool dynamic_lights = false;
 };
 
 // What srt_pt_repose derives for new poses of a committed scene, built next to it: the BVH<Object> and everything that follows
@@ -186,7 +189,22 @@ bool mat_ne_identity(const Mat4& m);
 std::string build_scene(const std::vector<ObjectInput>& objects, const std::vector<Material>& materials, bool use_bvh,
                         BuiltScene* out);
 
-// New transforms for `n` objects of a built scene (insertion indices; meshes, instances and spheres - not area lights): itrans /
+// What build_scene computes per area light, factored out so that a re-posed or deformed light takes the values a fresh commit
+// would give it.  light_record: has_trans, trans, itrans and Object::pdf's pair pdfT = I * trans, pdfiT = itrans * I (identities
+// when !has_trans; rays/object.h:90-94) - tri_base / ntri / pad are left alone.  light_area_term: 2 / |cross(T v1 - T v0, T v2 - T v0)|
+// of Triangle::pdf (student/tri_mesh.cpp:137), T applied as Mat4 * Vec3 with the perspective divide; a zero-area triangle gives inf.
+// light_tri_record: the whole LightTri of triangle t of `mesh` (corners, zeroed padding, area term under pdfT).
+void light_record(const Mat4& trans, const Mat4& itrans, bool has_trans, Light* L);
+float light_area_term(const Mat4& pdfT, const float v0[3], const float v1[3], const float v2[3]);
+LightTri light_tri_record(const Mat4& pdfT, const MeshInput& mesh, uint32_t t);
+// The index of object `object` (insertion index) in FlatScene::lights, -1 when it has no light record.
+int32_t light_of(const BuiltScene& built, uint32_t object);
+// The light-list copy of light `light` (its mesh in index order: Tri, TriNrm and packed records at its tri_base) and its LightTri
+// records, rewritten in place from built->inputs and the light's current pdfT.  Counts and light_tri_first stay.
+void write_light_mesh(BuiltScene* built, uint32_t light, uint32_t object);
+
+// New transforms for `n` objects of a built scene (insertion indices; meshes, instances and spheres - area lights only while
+// BuiltScene::dynamic_lights is set: apply_repose then gives each listed light its new Light record and area terms): itrans /
 // has_trans / posed box of those, the BVH<Object> (or list order) and the tables that follow from it.  No BVH<Triangle> is
 // rebuilt and no triangle moves.  Returns "" or an error message; *bad_argument tells a refused list (duplicate, out of range,
 // a light) from a BVH<Object> build that does not terminate.
