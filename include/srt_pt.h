@@ -256,11 +256,61 @@ int srt_pt_set_dynamic_lights(srt_pt* pt, int on);
  * srt_pt_repose makes.  (A HIP failure after that point is SRT_ERR_HIP and leaves the context without a committed scene: commit
  * again.)  Copies and kernels go on `stream`, which the call synchronises where the host needs a verdict and before it returns. */
 int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n);
+/* New transforms for n objects WITHOUT rebuilding the BVH<Object>: the tree keeps its node links {start, size, l, r} and its
+ * primitive order and takes new boxes - every leaf the BBox::enclose fold, from BBox(), of Object::bbox of its objects in
+ * primitive order (0 or 1), every interior node the enclose of its left child's box and then its right child's, which is how
+ * BVH<Primitive>::build forms node boxes (student/bvh.inl:73-75, 119-123).  A refit with the committed poses therefore gives the
+ * committed boxes back, as values (the zero-sign caveat of srt_pt_refit_mesh applies).  The listed objects get the itrans,
+ * has_trans and posed box the Object ctor and Object::bbox give them; results are those of the reference's BVH<Object>::hit and
+ * Object::hit on that tree - the closest hit does not depend on the tree except at exact ties, the cost of finding it does:
+ * srt_pt_scene_tree_cost tells when a rebuild (srt_pt_repose[_device]) pays.  Arguments, preconditions, refusals, status codes
+ * and messages are srt_pt_repose's (an area light is refused unless srt_pt_set_dynamic_lights is on; a listed light then takes
+ * the record and area terms srt_pt_repose gives it).  Non-finite matrices are not refused, by either form: the scene computes
+ * what the definition (prepare_top_refit / apply_top_refit, pt_scene.h) computes from them.  Counts, object slots, node_base,
+ * ordinals, the lazy tables, the depth of the tree, the kernel form and every BVH<Triangle> stay.  A scene committed with
+ * use_bvh == 0 has no tree: the listed records alone are rewritten.  A host-only context runs the definition and nothing else.
+ * On a device context the call waits as srt_pt_repose waits, then uploads what changed and nothing else: the top-level nodes
+ * (32 B each), the sweep records (64 B each), the listed object records (176 B each) and the listed lights' records - no table
+ * of object order. */
+int srt_pt_repose_refit(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n);
+/* The same from device transforms (d_trans: n * 16 floats, read on `stream`), ENQUEUE-ONLY.  The list is validated on the host
+ * before anything is enqueued (a host-only context validates and then returns SRT_ERR_UNSUPPORTED); after that the call cannot
+ * fail for a reason the scene gives - depth, node count, record count, object order, kernel form and stack sizes are those of
+ * the committed tree, so there is no verdict to wait for - and it only enqueues on `stream` and returns: no
+ * hipStreamSynchronize, no hipDeviceSynchronize, nothing copied to the host.  On `stream`, in order: the pose kernel of
+ * srt_pt_repose_device; the leaves from the posed boxes through the primitive order; the interior levels, deepest first; the
+ * boxes into the live top-level nodes and sweep records; the listed objects' trans / itrans / has_trans into their live
+ * records; the listed lights' records and area terms.  Box arithmetic is compares and loads only.
+ *   Blocking work: the FIRST call after a commit, and after any call that replaces the BVH<Object> (srt_pt_repose[_device],
+ * srt_pt_update_mesh*, srt_pt_refit_mesh*, the skin poses), allocates and uploads its tables - the pose tables it shares with
+ * srt_pt_repose_device (24 B per object) and the tree's refit tables (about 28 B per object, plus 4 B per level of the tree for
+ * the level offsets) - counted once.  A steady-state
+ * call uploads the list (4 B per listed object, 8 B more per listed light) through pinned memory, and nothing at all when the
+ * list equals the previous call's.  A list longer than any before grows device arrays, which waits, once.
+ *   Ordering: the new arrays are visible to whatever is enqueued on `stream` behind the call.  Epochs on other streams, and a
+ * later enqueue-only call on another stream, are ordered by the caller with events (the rule of the epoch folds): nothing in
+ * flight elsewhere may read the scene while the refit writes it.  The enqueue-only *_device render calls do not settle.
+ *   The host's record of the scene LAGS after this call and settles on demand: every entry point that is not itself
+ * enqueue-only first waits for an event recorded behind the last such call, reads back the records by insertion index (176 B
+ * per object) and the top-level boxes (24 B per node) once - however many calls are pending - and applies them to its own
+ * record (the lights' through its own arithmetic).  That covers srt_pt_sync, srt_pt_dump_bvh, srt_pt_dump_lights,
+ * srt_pt_scene_tree_cost, srt_pt_scene_counts, srt_pt_repose[_device], srt_pt_repose_refit, srt_pt_update_mesh*,
+ * srt_pt_refit_mesh*, the skin poses, srt_pt_hit, srt_pt_trace_samples, srt_pt_particles_step and srt_pt_render_epoch (host
+ * forms); srt_pt_scene_begin, srt_pt_scene_commit and srt_pt_destroy wait and discard what is pending (no read-back).  What the
+ * context keeps while it lags is one flag and at most one list entry per object, however many calls are pending.  A HIP error
+ * found while settling, or after the call has begun to enqueue, is SRT_ERR_HIP and leaves the context without a committed
+ * scene and with nothing pending: commit again. */
+int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n);
+/* tree_cost (the SAH figure of srt_pt_mesh_tree_cost) of the BVH<Object> as it is now, after settling: what a caller of
+ * srt_pt_repose_refit[_device] watches to decide when to pay for a rebuild with srt_pt_repose_device.  SRT_ERR_UNSUPPORTED for a
+ * scene committed without BVHs, SRT_ERR_STATE without a commit. */
+int srt_pt_scene_tree_cost(srt_pt* pt, double* cost);
 /* One lane per particle: d_trans_out[16 k ..] = Mat4::translate(pos_k) * Mat4::scale(Vec3{scale}), the T of
  * rays/pathtracer.cpp:149, bit-equal to Mat4::operator* (zero signs included).  d_pos holds 3 floats per particle - the layout
  * srt_pt_particles_step_device updates in place - so that step -> transforms -> srt_pt_repose_device -> render has no host data
- * in it.  Only enqueues on `stream`; does not synchronise.  The population is fixed: n is the number of particle objects the
- * scene was committed with.  Spawning and removing particles stays with the caller and needs a commit, as before. */
+ * in it (and with srt_pt_repose_refit_device in the place of srt_pt_repose_device, no host wait either).  Only enqueues on
+ * `stream`; does not synchronise.  The population is fixed: n is the number of particle objects the scene was committed with.
+ * Spawning and removing particles stays with the caller and needs a commit, as before. */
 int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out);
 /* New vertex arrays for ONE mesh of the committed scene without committing again: what a renderer of deforming meshes (a skinned
  * skeleton, cloth, a caller's own kernel) gets from the reference only by running build_scene again on Scene_Object::posed_mesh()

@@ -75,6 +75,13 @@ int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]);
  * 8 B per node and per interior record, the level offsets).  A refused refit adds nothing to any figure: the vertices it had
  * staged are not counted at all, and tables it made stay resident and are counted with the mesh's first refit that succeeds. */
 int srt_pt_refit_count(srt_pt* pt, uint64_t* refits);
+/* The same for the BVH<Object>: the successful srt_pt_repose_refit[_device] calls since creation.  Settles first, so device-form
+ * calls whose results the host has not read back yet are counted.  A top-level refit adds nothing to the builds or the
+ * triangle-class figure; to the uploads it adds what srt_pt_repose_refit[_device] document. */
+int srt_pt_top_refit_count(srt_pt* pt, uint64_t* refits);
+/* What the host's record lags by, WITHOUT settling: out[0] = the srt_pt_repose_refit_device calls not applied yet, out[1] = the
+ * entries of the set of objects they listed - at most the scene's object count, however many calls are pending. */
+int srt_pt_top_refit_pending(srt_pt* pt, uint64_t out[2]);
 /* The area-light tables of the committed scene (what srt_pt_set_dynamic_lights keeps true).  Returns the number of lights, or a
  * negative status.  Per light li < cap_lights: heads[4 li ..] = {has_trans, first light triangle (tri_base - first light triangle
  * of the scene), triangle count, insertion index of the object}, mats[64 li ..] = trans, itrans, pdfT, pdfiT.  Per light triangle

@@ -63,6 +63,11 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_refit_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_refit_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_skin_pose_refit.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
+    lib.srt_pt_repose_refit.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_repose_refit_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_scene_tree_cost.argtypes = [c_void_p, POINTER(ctypes.c_double)]
+    lib.srt_pt_top_refit_count.argtypes = [c_void_p, POINTER(c_uint64)]
+    lib.srt_pt_top_refit_pending.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_mesh_tree_cost.argtypes = [c_void_p, c_uint32, POINTER(ctypes.c_double)]
     lib.srt_pt_refit_count.argtypes = [c_void_p, POINTER(c_uint64)]
     lib.srt_pt_skin_create.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]
@@ -368,6 +373,40 @@ class Pathtracer:
         idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
         self._check(self._lib, self._lib.srt_pt_repose_device(self._ctx, c_void_p(stream), _p(idx), c_void_p(d_trans_ptr), len(idx)))
 
+    def repose_refit(self, indices, Ts) -> None:
+        """srt_pt_repose_refit: new transforms for these objects with the BVH<Object> kept - same links and object order, new boxes;
+        no build, no table of object order uploaded.  scene_tree_cost() tells when a rebuild (repose / repose_device) pays."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        T = _f32(Ts).reshape(-1, 16)
+        if len(T) != len(idx):
+            raise ValueError(f"{len(idx)} objects but {len(T)} transforms")
+        self._check(self._lib, self._lib.srt_pt_repose_refit(self._ctx, _p(idx), _p(T), len(idx)))
+
+    def repose_refit_device(self, indices, d_trans_ptr: int, stream: int = 0) -> None:
+        """srt_pt_repose_refit_device: the same from a device array of len(indices) * 16 floats, only enqueued on `stream`: no wait,
+        no read-back.  The host's record settles at the next call that is not enqueue-only (dump_bvh, hit, sync, ...)."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self._lib, self._lib.srt_pt_repose_refit_device(self._ctx, c_void_p(stream), _p(idx), c_void_p(d_trans_ptr), len(idx)))
+
+    def scene_tree_cost(self) -> float:
+        """srt_pt_scene_tree_cost: SAH cost of the current BVH<Object> (after settling)."""
+        c = ctypes.c_double()
+        self._check(self._lib, self._lib.srt_pt_scene_tree_cost(self._ctx, ctypes.byref(c)))
+        return float(c.value)
+
+    def top_refit_pending(self):
+        """srt_pt_top_refit_pending: (device-form refits the host has not applied yet, entries of the set of objects they listed);
+        does not settle."""
+        out = np.zeros(2, np.uint64)
+        self._check(self._lib, self._lib.srt_pt_top_refit_pending(self._ctx, _p(out)))
+        return int(out[0]), int(out[1])
+
+    def top_refit_count(self) -> int:
+        """srt_pt_top_refit_count: the successful repose_refit / repose_refit_device calls since creation (after settling)."""
+        r = c_uint64()
+        self._check(self._lib, self._lib.srt_pt_top_refit_count(self._ctx, ctypes.byref(r)))
+        return int(r.value)
+
     def particle_transforms_device(self, d_pos_ptr: int, n: int, scale: float, d_trans_ptr: int, stream: int = 0) -> None:
         """srt_pt_particle_transforms_device: translate(pos_k) * scale(scale) for n particles, device array (n, 3) -> device array
         (n, 16); only enqueued on `stream`."""
@@ -633,6 +672,12 @@ class Pathtracer:
         self._check(self._lib, self._lib.srt_pt_particles_step(self._ctx, _p(pos), _p(vel), _p(age), len(age), float(dt), float(radius), _p(alive)))
         return pos, vel, age, alive
 
+    def particles_step_device(self, d_pos_ptr: int, d_vel_ptr: int, d_age_ptr: int, n: int, dt: float, radius: float, d_alive_ptr: int, stream: int = 0) -> None:
+        """srt_pt_particles_step_device: the same in place on device arrays ((n, 3), (n, 3), (n,) float32 and (n,) uint8); only
+        enqueued on `stream`."""
+        self._check(self._lib, self._lib.srt_pt_particles_step_device(self._ctx, c_void_p(stream), c_void_p(d_pos_ptr), c_void_p(d_vel_ptr), c_void_p(d_age_ptr),
+                                                                      int(n), float(dt), float(radius), c_void_p(d_alive_ptr)))
+
     def dump_bvh(self, which: int, cap: int = 1 << 22):
         boxes = np.zeros((cap, 6), np.float32)
         links = np.zeros((cap, 4), np.uint32)
@@ -789,6 +834,22 @@ class PathtracerGroup:
             raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
         for m, ptr in zip(self.members, ptrs):
             m.repose_device(indices, ptr, stream)
+
+    def repose_refit(self, indices, Ts) -> None:
+        for m in self.members:
+            m.repose_refit(indices, Ts)
+
+    def repose_refit_device(self, indices, d_trans_ptrs, stream: int = 0) -> None:
+        """srt_pt_repose_refit_device on every rank: one device pointer per rank, as repose_device.  The group's lanes render on
+        streams of their own, which nothing orders behind `stream`: each member is settled (srt_pt_sync) before this returns, so the
+        group form waits for the refit.  A caller that wants the enqueue-only loop drives the members and their streams itself."""
+        ptrs = list(d_trans_ptrs)
+        if len(ptrs) != len(self.members):
+            raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
+        for m, ptr in zip(self.members, ptrs):
+            m.repose_refit_device(indices, ptr, stream)
+        for m in self.members:
+            m._check(m._lib, m._lib.srt_pt_sync(m._ctx))
 
     def update_mesh(self, index: int, pos, nrm) -> None:
         for m in self.members:

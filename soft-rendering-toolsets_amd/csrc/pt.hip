@@ -471,6 +471,25 @@ struct srt_pt {
   uint64_t idx_uncounted = 0;
   // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
   uint64_t scene_generation = 0;
+  // srt_pt_repose_refit[_device]: the BVH<Object>'s refit tables (RefitTables of pt_bvh_device.h; d_tri_boxes stays NULL - the posed
+  // boxes of the pose tables stand in its place) and the slot of every object, made at the first device-form refit of a tree and
+  // dropped wherever the tree is replaced (drop_top_tables).  top_list: what d_pose_list (and d_light_list) hold when the last call
+  // that wrote them was a device-form refit - a call with the same list uploads nothing.  pinned: host staging of the lists, one
+  // buffer per list still on its way (its event tells), so that a call never waits for the one before.
+  RefitTables top_tables; bool have_top_tables = false;
+  uint32_t* d_slot_of = nullptr;
+  std::vector<uint32_t> top_list; bool top_list_valid = false;
+  uint32_t top_lights = 0, top_light_max_ntri = 0;        // of top_list: listed lights, and the largest triangle count among them
+  struct PinnedList { uint32_t* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
+  std::vector<PinnedList> pinned;
+  // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of objects
+  // they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls are
+  // pending), and the event recorded behind the last of them.
+  uint64_t top_pending = 0;
+  std::vector<uint8_t> top_pending_flag;
+  std::vector<uint32_t> top_pending_objects;
+  hipEvent_t top_event = nullptr;
+  uint64_t top_refits = 0;                  // srt_pt_top_refit_count
 };
 
 namespace {
@@ -500,6 +519,17 @@ void drop_refit_tables(srt_pt* pt, uint32_t object) {
     if (object == UINT32_MAX || it->first == object) { free_refit_tables(&it->second); it = pt->refit_tables.erase(it); }
     else ++it;
   }
+}
+
+// The BVH<Object> is about to be replaced (or d_pose_list to be overwritten by another call: then only the list is forgotten).
+void forget_top_list(srt_pt* pt) { pt->top_list_valid = false; pt->top_list.clear(); }
+void drop_top_tables(srt_pt* pt) {
+  pt->top_tables.d_tri_boxes = nullptr;                   // (the pose tables' posed boxes: drop_pose_tables frees them)
+  if (pt->have_top_tables) free_refit_tables(&pt->top_tables);
+  pt->have_top_tables = false;
+  if (pt->d_slot_of) (void)hipFree(pt->d_slot_of);
+  pt->d_slot_of = nullptr;
+  forget_top_list(pt);
 }
 
 void drop_pose_tables(srt_pt* pt) {
@@ -532,6 +562,51 @@ int need_ready(srt_pt* pt, const char* what) {
   if (!pt->have_cam) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_camera", what);
   if (!pt->w || !pt->h) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_params", what);
   return SRT_OK;
+}
+
+// The host's record catches up with the device after srt_pt_repose_refit_device calls: one wait for the event behind the last of
+// them, one read-back (176 B per object: the records by insertion index; 24 B per node: the top-level boxes), and the scene
+// layer's own apply_top_refit - the lights' records come from the host's light_record / light_area_term.  Every entry point that
+// is not itself enqueue-only calls this first; with nothing pending it does nothing.
+void discard_pending(srt_pt* pt);
+int settle(srt_pt* pt) {
+  if (!pt || !pt->top_pending) return SRT_OK;
+  if (!pt->committed) { discard_pending(pt); return SRT_OK; }   // (a failure took the scene away: there is no record to bring up to date)
+  const uint64_t calls = pt->top_pending;
+  pt->top_pending = 0;
+  std::vector<uint32_t> objects;
+  objects.swap(pt->top_pending_objects);
+  for (uint32_t i : objects) pt->top_pending_flag[i] = 0;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  const bool use_bvh = pt->built.flat.use_bvh;
+  std::vector<Object> records(nobj);
+  TopRefit R;
+  if (use_bvh) R.boxes.resize(6 * (size_t)pt->top_tables.nnodes);
+  if (hipSetDevice(pt->device) != hipSuccess || hipEventSynchronize(pt->top_event) != hipSuccess ||
+      (nobj && hipMemcpy(records.data(), pt->d_pose_records, (size_t)nobj * sizeof(Object), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (!R.boxes.empty() && hipMemcpy(R.boxes.data(), pt->top_tables.d_node_boxes, R.boxes.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
+    pt->committed = false;
+    return srt::fail(SRT_ERR_HIP, "settling srt_pt_repose_refit_device: %s; the scene has to be committed again", hipGetErrorString(hipGetLastError()));
+  }
+  for (uint32_t i : objects) {                            // (every object once: top_pending_flag)
+    R.listed.push_back(i);
+    R.trans.push_back(records[i].trans);
+    R.itrans.push_back(records[i].itrans);
+    R.has_trans.push_back(records[i].has_trans);
+  }
+  apply_top_refit(&pt->built, &R);
+  pt->top_refits += calls;
+  return SRT_OK;
+}
+
+// srt_pt_scene_begin, srt_pt_scene_commit, srt_pt_destroy: what is pending describes a scene that goes; wait for it and forget it.
+void discard_pending(srt_pt* pt) {
+  if (!pt->top_pending) return;
+  if (hipSetDevice(pt->device) == hipSuccess) (void)hipEventSynchronize(pt->top_event);
+  pt->top_refits += pt->top_pending;                      // (they ran; only their read-back is not worth making any more)
+  pt->top_pending = 0;
+  for (uint32_t i : pt->top_pending_objects) pt->top_pending_flag[i] = 0;
+  pt->top_pending_objects.clear();
 }
 
 // srt_pt_set_elision asked for it and the BSDF-sampled direct ray of every continuous bounce is provably dead in this scene:
@@ -1143,6 +1218,7 @@ int srt_pt_destroy(srt_pt* pt) {
   if (!pt) return SRT_OK;
   if (pt->device >= 0) {
     (void)hipSetDevice(pt->device);
+    discard_pending(pt);
     (void)hipStreamSynchronize(pt->stream);
     if (pt->d_cast_stats) {                               // SRT_CAST_STATS=1 (diagnostic): the sums, on stderr
       unsigned long long h[CS_COUNT];
@@ -1159,6 +1235,9 @@ int srt_pt_destroy(srt_pt* pt) {
     bvh_workspace_free(&pt->bvh_ws);
     drop_refit_tables(pt, UINT32_MAX);
     drop_pose_tables(pt);
+    drop_top_tables(pt);
+    for (auto& pl : pt->pinned) { (void)hipHostFree(pl.h); (void)hipEventDestroy(pl.done); }
+    if (pt->top_event) (void)hipEventDestroy(pt->top_event);
     (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal); (void)hipFree(pt->d_light_list);
     if (pt->h_fault) (void)hipHostFree(pt->h_fault);
     if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);
@@ -1178,6 +1257,7 @@ int srt_pt_destroy(srt_pt* pt) {
 
 int srt_pt_scene_begin(srt_pt* pt) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_begin: NULL context");
+  discard_pending(pt);
   pt->inputs.clear();
   pt->materials.clear();
   pt->delta_lights.clear();
@@ -1309,7 +1389,8 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   // BVH<Triangle> builds of big meshes run on the device (pt_bvh_device.hip: identical arrays); srt_pt_set_bvh_builder
   const char* be = getenv("SRT_BVH_BUILDER");
   const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_refit_tables(pt, UINT32_MAX); drop_pose_tables(pt); }   // they describe trees and records that are about to go
+  discard_pending(pt);
+  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_refit_tables(pt, UINT32_MAX); drop_pose_tables(pt); drop_top_tables(pt); }   // they describe trees and records that are about to go
   if (pt->device >= 0 && bmode != 0) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
   else set_device_bvh_builder(nullptr, 0);
   const std::string err = build_scene(pt->inputs, pt->materials, use_bvh != 0, &pt->built);
@@ -1473,6 +1554,7 @@ int write_updated_mesh(srt_pt* pt, hipStream_t s, uint32_t object, const MeshSto
 // srt_pt_update_mesh / srt_pt_update_mesh_device.  h_*: the host form's arrays; d_*: the device form's (then `s` is the caller's stream).
 int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* h_pos, const float* h_nrm, const float* d_pos,
                 const float* d_nrm, uint32_t nverts) {
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
   const std::string refused = check_mesh_update(pt->built, object, nverts);
   if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
@@ -1538,7 +1620,7 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
   // the verdict is in: from here on the new arrays replace the old ones, on the host and then on the device
   const size_t old_tlas = pt->built.flat.tlas_nodes, old_nodes = pt->built.flat.nodes.size(), old_recs = pt->built.flat.blas_recs.size();
   apply_mesh_update(&pt->built, &U);
-  if (on_device) { drop_refit_tables(pt, object); drop_pose_tables(pt); }   // they describe the tree and the boxes that were just replaced
+  if (on_device) { drop_refit_tables(pt, object); drop_pose_tables(pt); drop_top_tables(pt); }   // they describe the tree and the boxes that were just replaced
   if (use_bvh) pt->blas_builds++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
@@ -1551,9 +1633,13 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, co
   return st;
 }
 
-// The device tables of a mesh's refits, from its host tree: made at the first refit after a commit or a rebuild.
-int make_refit_tables(srt_pt* pt, uint32_t object, RefitTables* T) {
-  const HostBVH& tree = pt->built.blas[object];
+// The device tables of a tree's refits, from the host tree: made at the first refit after a commit or a rebuild.  `tree`: a mesh's
+// BVH<Triangle> (object: its insertion index) or the BVH<Object> (object == UINT32_MAX; its primitives are the objects, whose
+// boxes the pose tables hold already: no box array of their own is made).
+int make_refit_tables(const HostBVH& tree, const char* what, uint32_t object, RefitTables* T) {
+  const bool top = object == UINT32_MAX;
+  const std::string whose = top ? std::string("the BVH<Object>") : "object " + std::to_string(object);
+  const char* const inside = top ? "scene" : "mesh";
   const uint32_t nn = (uint32_t)tree.nodes.size(), ntri = (uint32_t)tree.prim.size();
   // a node's level: children lie behind their parent (level order, student/bvh.inl:144-145), so one forward pass does it
   std::vector<uint32_t> level(nn, 0u);
@@ -1563,16 +1649,16 @@ int make_refit_tables(srt_pt* pt, uint32_t object, RefitTables* T) {
     if (h.l == h.r) {
       // the leaf table packs (first slot << 3) | count, and the kernels trust it: refuse here what they could not take
       if (h.size > 7u || h.start >= (1u << 29) || (uint64_t)h.start + h.size > ntri)
-        return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_refit_mesh: leaf %u of object %u holds %u primitives from slot %u (at most 7, below 2^29, inside the mesh)", n,
-                         object, h.size, h.start);
+        return srt::fail(SRT_ERR_UNSUPPORTED, "%s: leaf %u of %s holds %u primitives from slot %u (at most 7, below 2^29, inside the %s)", what, n,
+                         whose.c_str(), h.size, h.start, inside);
       continue;
     }
-    if (h.l <= n || h.r != h.l + 1u || h.r >= nn) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_refit_mesh: the tree of object %u is not in level order", object);
+    if (h.l <= n || h.r != h.l + 1u || h.r >= nn) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the tree of %s is not in level order", what, whose.c_str());
     level[h.l] = level[h.r] = level[n] + 1u;
     levels = std::max(levels, level[n] + 1u);
   }
   for (uint32_t t : tree.prim)
-    if (t >= ntri) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_refit_mesh: the primitive order of object %u names triangle %u of %u", object, t, ntri);
+    if (t >= ntri) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the primitive order of %s names %s %u of %u", what, whose.c_str(), top ? "object" : "triangle", t, ntri);
   std::vector<uint2> leaves, list, children;
   std::vector<uint32_t> off(levels + 1u, 0u);
   for (uint32_t n = 0; n < nn; n++) {
@@ -1597,9 +1683,10 @@ int make_refit_tables(srt_pt* pt, uint32_t object, RefitTables* T) {
     return true;
   };
   if (!up(&T->d_prim, tree.prim) || !up(&T->d_leaves, leaves) || !up(&T->d_list, list) || !up(&T->d_children, children) || !up(&T->d_level_off, off) ||
-      hipMalloc(&T->d_tri_boxes, (size_t)ntri * 6 * sizeof(float)) != hipSuccess || hipMalloc(&T->d_node_boxes, (size_t)nn * 6 * sizeof(float)) != hipSuccess) {
+      (!top && hipMalloc(&T->d_tri_boxes, (size_t)ntri * 6 * sizeof(float)) != hipSuccess) ||
+      hipMalloc(&T->d_node_boxes, (size_t)(nn ? nn : 1) * 6 * sizeof(float)) != hipSuccess) {
     free_refit_tables(T);
-    return srt::fail(SRT_ERR_HIP, "srt_pt_refit_mesh: out of device memory");
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
   }
   return SRT_OK;
 }
@@ -1607,6 +1694,7 @@ int make_refit_tables(srt_pt* pt, uint32_t object, RefitTables* T) {
 // srt_pt_refit_mesh / srt_pt_refit_mesh_device / srt_pt_skin_pose_refit.  h_*: the host form's arrays; d_*: the device form's.
 int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* h_pos, const float* h_nrm, const float* d_pos,
                const float* d_nrm, uint32_t nverts) {
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
   const std::string refused = check_mesh_update(pt->built, object, nverts);
   if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
@@ -1638,7 +1726,7 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
     auto it = pt->refit_tables.find(object);
     if (it == pt->refit_tables.end()) {
       RefitTables fresh;
-      const int st = make_refit_tables(pt, object, &fresh);
+      const int st = make_refit_tables(pt->built.blas[object], "srt_pt_refit_mesh", object, &fresh);
       if (st != SRT_OK) return st;
       it = pt->refit_tables.emplace(object, fresh).first;
     }
@@ -1678,6 +1766,7 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, con
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (!on_device) return SRT_OK;
   drop_pose_tables(pt);                                   // the object-space boxes changed
+  drop_top_tables(pt);                                    // the BVH<Object> was rebuilt
   pt->bytes_uploaded += staged_bytes + T->uncounted_bytes + pt->idx_uncounted;   // the vertices of the host form; the tables, at the mesh's first successful refit
   T->uncounted_bytes = 0;
   pt->idx_uncounted = 0;
@@ -1952,6 +2041,7 @@ extern "C" {
 
 int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
   if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_repose before srt_pt_scene_commit");
   const char* be = getenv("SRT_BVH_BUILDER");               // the BVH<Object> build goes where srt_pt_scene_commit's does
   const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
@@ -1979,6 +2069,7 @@ int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint3
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   if (pt->device >= 0) {
     drop_pose_tables(pt);                                 // srt_pt_repose_device's tables mirror the poses that were just replaced
+    drop_top_tables(pt);                                  // srt_pt_repose_refit_device's describe the tree that was just replaced
     const FlatScene& F = pt->built.flat;
     int st;
     if (F.tlas_nodes == old_tlas_nodes) {                 // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
@@ -2000,12 +2091,14 @@ int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint3
 int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
   const char* what = "srt_pt_repose_device";
   if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
   const std::string refused = check_repose_list(pt->built, objects, n);
   if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
   if (pt->device < 0)
     return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose takes host matrices)", what);
   SRT_HIP(hipSetDevice(pt->device));
+  forget_top_list(pt);                                    // d_pose_list and d_light_list are about to hold this call's lists
   hipStream_t s = (hipStream_t)stream;
   const bool use_bvh = pt->built.flat.use_bvh;
   const uint32_t nobj = (uint32_t)pt->built.inputs.size();
@@ -2123,6 +2216,7 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
   if (hipStreamSynchronize(s) != hipSuccess || hipStreamSynchronize(pt->stream) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return refuse(srt::fail(SRT_ERR_HIP, "%s: synchronisation failed", what));
   apply_repose(&pt->built, &top);
+  drop_top_tables(pt);                                    // srt_pt_repose_refit_device's describe the tree that was just replaced
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
   pt->bytes_uploaded += staged_bytes;
   // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
@@ -2154,6 +2248,228 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
   return st;
 }
 
+}  // extern "C"
+
+namespace {
+
+// A pinned staging buffer of at least `words` words whose last copy has left it (or a new one).
+int pinned_list(srt_pt* pt, size_t words, srt_pt::PinnedList** out) {
+  for (auto& pl : pt->pinned) {
+    if (pl.words < words) continue;
+    const hipError_t left = hipEventQuery(pl.done);
+    (void)hipGetLastError();                              // (hipErrorNotReady of a query is no error: not left behind for the launch check)
+    if (left == hipSuccess) { *out = &pl; return SRT_OK; }
+  }
+  srt_pt::PinnedList pl;
+  pl.words = std::max<size_t>(words, 1024);
+  if (hipHostMalloc((void**)&pl.h, pl.words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return srt::fail(SRT_ERR_HIP, "out of pinned host memory");
+  if (hipEventCreateWithFlags(&pl.done, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(pl.h); return srt::fail(SRT_ERR_HIP, "event creation failed"); }
+  pt->pinned.push_back(pl);
+  *out = &pt->pinned.back();
+  return SRT_OK;
+}
+
+// srt_pt_repose_refit's device side after apply_top_refit: the arrays that changed, from the host's record.
+int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n) {
+  const FlatScene& F = pt->built.flat;
+  if (F.use_bvh) {
+    if (F.tlas_nodes) SRT_HIP(hipMemcpy(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice));
+    if (!F.wave_tlas.empty()) SRT_HIP(hipMemcpy(pt->d_wave, F.wave_tlas.data(), F.wave_tlas.size() * sizeof(WaveInterior), hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node) + F.wave_tlas.size() * sizeof(WaveInterior);
+  }
+  // the listed records, one copy per run of neighbouring slots (a pool that moves as a whole is a handful of runs)
+  std::vector<uint32_t> slot_of(pt->built.tlas.prim.size()), slots(n);
+  for (size_t k = 0; k < slot_of.size(); k++) slot_of[pt->built.tlas.prim[k]] = (uint32_t)k;
+  for (uint32_t k = 0; k < n; k++) slots[k] = slot_of[objects[k]];
+  std::sort(slots.begin(), slots.end());
+  for (uint32_t k = 0; k < n;) {
+    uint32_t e = k + 1;
+    while (e < n && slots[e] == slots[e - 1] + 1u) e++;
+    SRT_HIP(hipMemcpy(pt->d_objects + slots[k], &F.objects[slots[k]], (size_t)(e - k) * sizeof(Object), hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)(e - k) * sizeof(Object);
+    k = e;
+  }
+  for (uint32_t k = 0; k < n; k++) {
+    const int32_t li = pt->built.inputs[objects[k]].is_light ? light_of(pt->built, objects[k]) : -1;
+    int st;
+    if (li >= 0 && (st = upload_light(pt, (uint32_t)li, false))) return st;
+  }
+  return SRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srt_pt_repose_refit(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
+  if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose_refit: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_repose_refit before srt_pt_scene_commit");
+  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
+  std::vector<Mat4> T(n);
+  if (n) std::memcpy(T.data(), trans, (size_t)n * sizeof(Mat4));
+  TopRefit R;
+  const std::string err = prepare_top_refit(pt->built, objects, T.data(), n, &R);
+  if (!err.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose_refit: %s", err.c_str());
+  // nothing fails on the host side from here on: the new boxes and records replace the old ones in place
+  if (pt->device >= 0) {
+    SRT_HIP(hipSetDevice(pt->device));
+    SRT_HIP(hipStreamSynchronize(pt->stream));
+    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old boxes
+  }
+  apply_top_refit(&pt->built, &R);
+  pt->top_refits++;
+  if (pt->device >= 0) {
+    drop_pose_tables(pt);                                 // they mirror the poses that were just replaced (the tree's tables stay: the tree did)
+    const int st = write_top_refit(pt, objects, n);
+    if (st != SRT_OK) { pt->committed = false; return st; }
+  }
+  return SRT_OK;
+}
+
+int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
+  const char* what = "srt_pt_repose_refit_device";
+  if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
+  const std::string refused = check_repose_list(pt->built, objects, n);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose_refit takes host matrices)", what);
+  SRT_HIP(hipSetDevice(pt->device));
+  hipStream_t s = (hipStream_t)stream;
+  const FlatScene& F = pt->built.flat;
+  const bool use_bvh = F.use_bvh;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  int st;
+  // First call after a commit or after a call that replaced the BVH<Object> (blocking, counted once): the pose tables as
+  // srt_pt_repose_device makes them (24 B per object up), the tree's refit tables (about 28 B per object up) and the slot of
+  // every object (a kernel).  Nothing is pending then - every call that drops these tables settles first.
+  if (!pt->pose_tables) {
+    drop_pose_tables(pt);
+    if (hipMalloc(&pt->d_pose_records, (size_t)(nobj ? nobj : 1) * sizeof(Object)) != hipSuccess ||
+        hipMalloc(&pt->d_local_boxes, (size_t)(nobj ? nobj : 1) * 6 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&pt->d_posed_boxes, (size_t)(nobj ? nobj : 1) * 6 * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      drop_pose_tables(pt);
+      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+    }
+    if (nobj) SRT_HIP(hipMemcpy(pt->d_local_boxes, pt->built.local_boxes.data(), (size_t)nobj * 6 * sizeof(float), hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)nobj * 6 * sizeof(float);
+    launch_pose_tables(s, pt->d_objects, nobj, F.tlas_nodes, pt->d_pose_records, pt->d_local_boxes, pt->d_posed_boxes);
+    pt->pose_tables = true;
+  }
+  if (use_bvh && !pt->have_top_tables) {
+    drop_top_tables(pt);
+    RefitTables fresh;
+    if ((st = make_refit_tables(pt->built.tlas, what, UINT32_MAX, &fresh)) != SRT_OK) return st;
+    pt->top_tables = fresh;
+    pt->have_top_tables = true;
+    pt->bytes_uploaded += fresh.uncounted_bytes;
+    pt->top_tables.uncounted_bytes = 0;
+    if (hipMalloc(&pt->d_slot_of, (size_t)(nobj ? nobj : 1) * sizeof(uint32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      drop_top_tables(pt);
+      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+    }
+    launch_top_slots(s, pt->top_tables.d_prim, nobj, pt->d_slot_of);
+  }
+  // A HIP failure from here on may leave tables, lists or live arrays half written: the scene is no longer committed, what was
+  // pending is forgotten (settle() has no record to bring up to date) and the tables go; the scene has to be committed again.
+  auto broken = [&](int status) {
+    pt->committed = false;
+    if (hipSetDevice(pt->device) == hipSuccess) (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    pt->top_pending = 0;
+    for (uint32_t i : pt->top_pending_objects) pt->top_pending_flag[i] = 0;
+    pt->top_pending_objects.clear();
+    drop_pose_tables(pt);
+    drop_top_tables(pt);
+    return status;
+  };
+  auto hip_broken = [&](hipError_t e, const char* step) { return broken(srt::fail(SRT_ERR_HIP, "%s: %s failed (%s); the scene has to be committed again", what, step, hipGetErrorString(e))); };
+  hipError_t he;
+  // The list (4 B per listed object, 8 B more per listed light), through pinned memory so that the copy is only enqueued - unless
+  // the device holds this very list already.
+  if (n && !(pt->top_list_valid && pt->top_list.size() == n && std::memcmp(pt->top_list.data(), objects, (size_t)n * 4) == 0)) {
+    std::vector<uint32_t> light_list;
+    uint32_t light_max_ntri = 0;
+    for (uint32_t k = 0; k < n; k++) {
+      const int32_t li = pt->built.inputs[objects[k]].is_light ? light_of(pt->built, objects[k]) : -1;   // (light_of counts the lights in front)
+      if (li < 0) continue;
+      light_list.push_back(k);
+      light_list.push_back((uint32_t)li);
+      light_max_ntri = std::max(light_max_ntri, F.lights[(size_t)li].ntri);
+    }
+    forget_top_list(pt);
+    // (growing one of these arrays frees the old one, which waits for what reads it: first calls and longer lists only)
+    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n)) ||
+        (!light_list.empty() && (st = ensure(&pt->d_light_list, &pt->light_list_n, light_list.size()))))
+      return broken(st);
+    srt_pt::PinnedList* pl = nullptr;
+    if ((st = pinned_list(pt, (size_t)n + light_list.size(), &pl)) != SRT_OK) return broken(st);
+    std::memcpy(pl->h, objects, (size_t)n * 4);
+    if (!light_list.empty()) std::memcpy(pl->h + n, light_list.data(), light_list.size() * 4);
+    if ((he = hipMemcpyAsync(pt->d_pose_list, pl->h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_broken(he, "the copy of the list");
+    if (!light_list.empty() && (he = hipMemcpyAsync(pt->d_light_list, pl->h + n, light_list.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
+      return hip_broken(he, "the copy of the light list");
+    if ((he = hipEventRecord(pl->done, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
+    pt->bytes_uploaded += (uint64_t)n * 4 + light_list.size() * 4;
+    pt->top_list.assign(objects, objects + n);
+    pt->top_lights = (uint32_t)(light_list.size() / 2);
+    pt->top_light_max_ntri = light_max_ntri;
+    pt->top_list_valid = true;
+  }
+  if (!pt->top_event && (he = hipEventCreateWithFlags(&pt->top_event, hipEventDisableTiming)) != hipSuccess) return hip_broken(he, "hipEventCreate");
+  // Everything below only enqueues on `s`: the poses, the leaves through the tree's primitive order, the levels deepest first, the
+  // boxes into the live nodes and sweep records, the listed records' matrices, the listed lights.  No verdict is needed: depth,
+  // counts, order, kernel form and stack sizes are those of the committed tree.
+  if (n) launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
+  if (use_bvh) {
+    pt->top_tables.d_tri_boxes = pt->d_posed_boxes;       // the tree's primitives are the objects: their boxes are the pose tables' (not owned)
+    launch_refit_boxes(s, pt->top_tables, pt->top_tables.d_node_boxes);
+    launch_refit_write(s, pt->top_tables, pt->top_tables.d_node_boxes, pt->d_nodes, pt->d_wave);
+  }
+  if (n) {
+    launch_top_objects(s, pt->d_pose_list, n, nobj, use_bvh ? pt->d_slot_of : nullptr, pt->d_pose_records, pt->d_objects);
+    if (pt->top_lights) {
+      launch_light_records(s, pt->d_light_list, pt->top_lights, pt->d_pose_out, n, pt->d_lights, (uint32_t)F.lights.size());
+      launch_light_area_terms(s, pt->d_light_list, pt->top_lights, pt->top_light_max_ntri, pt->d_lights, (uint32_t)F.lights.size(), F.light_tri_first, pt->d_ltris,
+                              (uint32_t)F.light_tris.size());
+    }
+  }
+  if ((he = hipGetLastError()) != hipSuccess) return hip_broken(he, "a launch");
+  if ((he = hipEventRecord(pt->top_event, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
+  // the host's record is behind from here until settle(): one more call, and the objects it listed that no pending call had listed
+  pt->top_pending++;
+  if (pt->top_pending_flag.size() != nobj) pt->top_pending_flag.assign(nobj, 0);   // (nothing is pending across a commit)
+  for (uint32_t k = 0; k < n; k++)
+    if (!pt->top_pending_flag[objects[k]]) { pt->top_pending_flag[objects[k]] = 1; pt->top_pending_objects.push_back(objects[k]); }
+  return SRT_OK;
+}
+
+int srt_pt_scene_tree_cost(srt_pt* pt, double* cost) {
+  if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_tree_cost: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
+  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_scene_tree_cost before srt_pt_scene_commit");
+  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_scene_tree_cost: the scene was committed without BVHs, it has no tree");
+  *cost = tree_cost(pt->built.tlas);
+  return SRT_OK;
+}
+
+int srt_pt_top_refit_pending(srt_pt* pt, uint64_t out[2]) {
+  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_top_refit_pending: NULL argument");
+  out[0] = pt->top_pending;
+  out[1] = pt->top_pending_objects.size();
+  return SRT_OK;
+}
+
+int srt_pt_top_refit_count(srt_pt* pt, uint64_t* refits) {
+  if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_top_refit_count: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
+  *refits = pt->top_refits;
+  return SRT_OK;
+}
+
 int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {
   int st = need_device(pt, "srt_pt_particle_transforms_device");
   if (st != SRT_OK) return st;
@@ -2166,6 +2482,7 @@ int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_p
 
 int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]) {
   if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_counts: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   const FlatScene& F = pt->built.flat;
   const bool have = pt->committed;
   out[0] = have ? F.objects.size() : 0;
@@ -2382,6 +2699,7 @@ int srt_pt_accumulate_device(srt_pt* pt, void* stream, float* d_accumulator, con
 int srt_pt_render_epoch(srt_pt* pt, uint64_t seed, uint32_t sample_base, uint32_t samples, float* rgb_out) {
   int st = need_ready(pt, "srt_pt_render_epoch");
   if (st != SRT_OK) return st;
+  if ((st = settle(pt)) != SRT_OK) return st;
   if (!rgb_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_render_epoch: output is NULL");
   const TileMap& T = pt->tiles;
   const size_t per_tile = (size_t)T.tile_w * T.tile_h * 3;
@@ -2546,6 +2864,7 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
                          float* rgb_out, uint32_t* draws_out, uint32_t* rays_out) {
   int st = need_ready(pt, "srt_pt_trace_samples");
   if (st != SRT_OK) return st;
+  if ((st = settle(pt)) != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!xs || !ys || !ss || !rgb_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_trace_samples: NULL argument");
   if (n > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "too many samples in one call");
@@ -2574,6 +2893,7 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
 int srt_pt_hit(srt_pt* pt, const float* origins, const float* dirs, const float* bounds, size_t n, float* out9) {
   int st = need_device(pt, "srt_pt_hit");
   if (st != SRT_OK) return st;
+  if ((st = settle(pt)) != SRT_OK) return st;
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_hit before srt_pt_scene_commit");
   if (n == 0) return SRT_OK;
   if (!origins || !dirs || !bounds || !out9) return srt::fail(SRT_ERR_INVALID, "srt_pt_hit: NULL argument");
@@ -2613,6 +2933,7 @@ int srt_pt_particles_step_device(srt_pt* pt, void* stream, float* d_pos, float* 
 int srt_pt_particles_step(srt_pt* pt, float* pos, float* vel, float* age, size_t n, float dt, float radius, uint8_t* alive) {
   int st = need_device(pt, "srt_pt_particles_step");
   if (st != SRT_OK) return st;
+  if ((st = settle(pt)) != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!pos || !vel || !age || !alive) return srt::fail(SRT_ERR_INVALID, "srt_pt_particles_step: NULL argument");
   float *dp = nullptr, *dv = nullptr, *da = nullptr;
@@ -2634,6 +2955,7 @@ int srt_pt_particles_step(srt_pt* pt, float* pos, float* vel, float* age, size_t
 
 long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_t cap, uint32_t* order) {
   if (!pt || !boxes || !links) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_bvh: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_bvh before srt_pt_scene_commit");
   if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_STATE, "scene was committed without BVHs");
   const HostBVH* b = &pt->built.tlas;
@@ -2658,6 +2980,7 @@ long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_
 
 long srt_pt_dump_lights(srt_pt* pt, int from_device, uint32_t* heads, float* mats, size_t cap_lights, float* tris, size_t cap_tris) {
   if (!pt || (cap_lights && (!heads || !mats)) || (cap_tris && !tris)) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_lights: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_lights before srt_pt_scene_commit");
   if (from_device && pt->device < 0)
     return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_dump_lights: this context is host-only, there are no device arrays to read (from_device = 0 reads the host's)");
@@ -2880,6 +3203,7 @@ int srt_pt_read_ray_log(srt_pt* pt, srt_pt_logged_ray* out, size_t cap, size_t* 
 int srt_pt_sync(srt_pt* pt) {
   int st = need_device(pt, "srt_pt_sync");
   if (st != SRT_OK) return st;
+  if ((st = settle(pt)) != SRT_OK) return st;
   SRT_HIP(hipStreamSynchronize(pt->stream));
   return check_stream_fault(pt, "srt_pt_sync");
 }

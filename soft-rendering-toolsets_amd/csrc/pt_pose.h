@@ -116,6 +116,13 @@ void launch_pose_objects(void* stream, const uint32_t* d_listed, const float* d_
 // tlas_nodes again and its mesh ordinal d_ordinal[k] (already shifted to bits 8 and up; none when NULL).
 void launch_pose_records(void* stream, const Object* d_by_index, const uint32_t* d_prim, const uint32_t* d_ordinal, uint32_t nobj, uint32_t tlas_nodes,
                          Object* d_objects);
+// srt_pt_repose_refit_device: d_slot_of[d_prim[slot]] = slot for the nobj slots of the BVH<Object>'s primitive order (made once per tree,
+// on the device: nothing goes up for it).
+void launch_top_slots(void* stream, const uint32_t* d_prim, uint32_t nobj, uint32_t* d_slot_of);
+// The n listed objects' trans, itrans and has_trans from d_by_index (where launch_pose_objects left them) into their live records
+// d_objects[d_slot_of[i]] (slot i when d_slot_of is NULL: a list scene).  Copies only; no other field of a live record is written.
+void launch_top_objects(void* stream, const uint32_t* d_listed, uint32_t n, uint32_t nobj, const uint32_t* d_slot_of, const Object* d_by_index,
+                        Object* d_objects);
 // One lane per particle: d_trans_out[16 k ..] = translate(d_pos[3 k ..]) * scale(scale).
 void launch_particle_transforms(void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out);
 

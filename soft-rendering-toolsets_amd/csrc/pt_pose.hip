@@ -98,6 +98,29 @@ __global__ __launch_bounds__(256) void pose_records_kernel(const Object* __restr
   reinterpret_cast<uint4*>(live + slot)[q] = v;
 }
 
+// srt_pt_repose_refit_device.  One lane per slot: the slot of every object (insertion index), from the tree's primitive order.
+__global__ __launch_bounds__(256) void top_slots_kernel(const uint32_t* __restrict__ prim, uint32_t nobj, uint32_t* __restrict__ slot_of) {
+  const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= nobj) return;
+  const uint32_t i = prim[slot];
+  if (i < nobj) slot_of[i] = slot;                               // (a permutation of [0, nobj) by construction; never a store outside the table)
+}
+
+// lane = 9 k + q: listed object k's matrices (the last eight quads of its record by insertion index, where the pose kernel left
+// them) into its live record, q == 8: its has_trans word.  Nothing else of the live record is touched.
+__global__ __launch_bounds__(256) void top_objects_kernel(const uint32_t* __restrict__ listed, uint32_t n, uint32_t nobj, const uint32_t* __restrict__ slot_of,
+                                                          const Object* __restrict__ by_index, Object* __restrict__ live) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)n * 9u) return;
+  const uint32_t k = (uint32_t)(t / 9u), q = (uint32_t)(t % 9u);
+  const uint32_t i = listed[k];
+  if (i >= nobj) return;                                         // (the list was checked on the host before anything was enqueued)
+  const uint32_t slot = slot_of ? slot_of[i] : i;
+  if (slot >= nobj) return;
+  if (q < 8u) reinterpret_cast<uint4*>(live + slot)[3u + q] = reinterpret_cast<const uint4*>(by_index + i)[3u + q];
+  else live[slot].has_trans = by_index[i].has_trans;
+}
+
 __global__ __launch_bounds__(256) void particle_transforms_kernel(const float* __restrict__ pos, uint32_t n, float scale, float* __restrict__ out) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
@@ -129,6 +152,17 @@ void launch_pose_records(void* stream, const Object* d_by_index, const uint32_t*
                          Object* d_objects) {
   if (!nobj) return;
   pose_records_kernel<<<dim3(blocks_for((size_t)nobj * kQuads)), dim3(256), 0, (hipStream_t)stream>>>(d_by_index, d_prim, d_ordinal, nobj, tlas_nodes, d_objects);
+}
+
+void launch_top_slots(void* stream, const uint32_t* d_prim, uint32_t nobj, uint32_t* d_slot_of) {
+  if (!nobj) return;
+  top_slots_kernel<<<dim3(blocks_for(nobj)), dim3(256), 0, (hipStream_t)stream>>>(d_prim, nobj, d_slot_of);
+}
+
+void launch_top_objects(void* stream, const uint32_t* d_listed, uint32_t n, uint32_t nobj, const uint32_t* d_slot_of, const Object* d_by_index,
+                        Object* d_objects) {
+  if (!n) return;
+  top_objects_kernel<<<dim3(blocks_for((size_t)n * 9u)), dim3(256), 0, (hipStream_t)stream>>>(d_listed, n, nobj, d_slot_of, d_by_index, d_objects);
 }
 
 void launch_particle_transforms(void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {

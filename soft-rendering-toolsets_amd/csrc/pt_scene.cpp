@@ -954,6 +954,96 @@ void apply_mesh_refit(BuiltScene* built, MeshRefit* refit) {
   if (li >= 0) write_light_mesh(built, (uint32_t)li, R.object);
 }
 
+void top_refit_boxes(const HostBVH& tree, const float* posed, std::vector<float>* boxes6) {
+  const size_t nn = tree.nodes.size();
+  std::vector<Box> nb(nn);
+  for (size_t n = nn; n-- > 0;) {                    // children lie behind their parent: one backward pass
+    const HostNode& nd = tree.nodes[n];
+    Box b;
+    if (nd.l == nd.r) {
+      for (uint32_t k = nd.start; k < nd.start + nd.size; k++) {
+        Box ob;
+        for (int a = 0; a < 3; a++) { ob.mn[a] = posed[6 * (size_t)tree.prim[k] + a]; ob.mx[a] = posed[6 * (size_t)tree.prim[k] + 3 + a]; }
+        b.enclose(ob);
+      }
+    } else {
+      b.enclose(nb[nd.l]);
+      b.enclose(nb[nd.r]);
+    }
+    nb[n] = b;
+  }
+  boxes6->resize(6 * nn);
+  for (size_t n = 0; n < nn; n++)
+    for (int a = 0; a < 3; a++) { (*boxes6)[6 * n + a] = nb[n].mn[a]; (*boxes6)[6 * n + 3 + a] = nb[n].mx[a]; }
+}
+
+std::string prepare_top_refit(const BuiltScene& B, const uint32_t* objects, const Mat4* new_trans, uint32_t n, TopRefit* out) {
+  const std::string refused = check_repose_list(B, objects, n);
+  if (!refused.empty()) return refused;
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  TopRefit& R = *out;
+  R = TopRefit();
+  R.listed.assign(objects, objects + n);
+  R.trans.assign(new_trans, new_trans + n);
+  R.itrans.resize(n);
+  R.has_trans.resize(n);
+  // Object::bbox of every object: the listed ones under their new transforms, the others under the committed ones
+  std::vector<float> posed(6 * (size_t)nobj);
+  std::vector<bool> listed(nobj, false);
+  for (uint32_t k = 0; k < n; k++) {
+    listed[objects[k]] = true;
+    posed_values(new_trans[k], &B.local_boxes[6 * (size_t)objects[k]], &R.itrans[k], &R.has_trans[k], &posed[6 * (size_t)objects[k]]);
+  }
+  if (!B.flat.use_bvh) return "";
+  for (uint32_t i = 0; i < nobj; i++) {
+    if (listed[i]) continue;
+    Mat4 itrans;
+    uint32_t has_trans;
+    posed_values(B.inputs[i].trans, &B.local_boxes[6 * (size_t)i], &itrans, &has_trans, &posed[6 * (size_t)i]);
+  }
+  top_refit_boxes(B.tlas, posed.data(), &R.boxes);
+  return "";
+}
+
+void apply_top_refit(BuiltScene* built, TopRefit* refit) {
+  BuiltScene& B = *built;
+  FlatScene& F = B.flat;
+  TopRefit& R = *refit;
+  std::vector<uint32_t> slot_of(B.tlas.prim.size());
+  for (size_t s = 0; s < B.tlas.prim.size(); s++) slot_of[B.tlas.prim[s]] = (uint32_t)s;
+  for (size_t k = 0; k < R.listed.size(); k++) {
+    const uint32_t i = R.listed[k];
+    B.inputs[i].trans = R.trans[k];
+    Object& o = F.objects[slot_of[i]];
+    o.trans = R.trans[k];
+    o.itrans = R.itrans[k];
+    o.has_trans = R.has_trans[k];
+    // a listed area light (BuiltScene::dynamic_lights): its record and area terms, as apply_repose gives them
+    const int32_t li = B.inputs[i].is_light ? light_of(B, i) : -1;
+    if (li < 0) continue;
+    Light& L = F.lights[(size_t)li];
+    light_record(o.trans, o.itrans, o.has_trans != 0u, &L);
+    for (uint32_t t = 0; t < L.ntri; t++) {
+      LightTri& lt = F.light_tris[(size_t)(L.tri_base - F.light_tri_first) + t];
+      lt.area_term = light_area_term(L.pdfT, lt.v0, lt.v1, lt.v2);
+    }
+  }
+  if (!F.use_bvh) return;
+  HostBVH& tree = B.tlas;
+  for (size_t n = 0; n < tree.nodes.size(); n++) {
+    HostNode& h = tree.nodes[n];
+    Node& f = F.nodes[n];
+    for (int a = 0; a < 3; a++) { h.mn[a] = f.mn[a] = R.boxes[6 * n + a]; h.mx[a] = f.mx[a] = R.boxes[6 * n + 3 + a]; }
+  }
+  // sweep records in node order, as append_records numbers them: both child boxes, nothing else
+  size_t q = 0;
+  for (const HostNode& h : tree.nodes) {
+    if (h.l == h.r) continue;
+    WaveInterior& wi = F.wave_tlas[q++];
+    for (int a = 0; a < 6; a++) { wi.boxl[a] = R.boxes[6 * (size_t)h.l + a]; wi.boxr[a] = R.boxes[6 * (size_t)h.r + a]; }
+  }
+}
+
 double tree_cost(const HostBVH& tree) {
   if (tree.nodes.empty()) return 0.0;
   auto area = [](const HostNode& h) {

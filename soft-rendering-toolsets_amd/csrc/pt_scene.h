@@ -287,6 +287,26 @@ void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32
 std::string prepare_mesh_refit(const BuiltScene& built, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
                                const float* node_boxes, MeshRefit* out, bool* bad_argument);
 void apply_mesh_refit(BuiltScene* built, MeshRefit* refit);
+// What srt_pt_repose_refit derives for new poses of a committed scene: the BVH<Object> keeps its links {start, size, l, r} and its
+// primitive order and takes new boxes, as a mesh's tree does in prepare_mesh_refit - a leaf's is the BBox::enclose fold, from
+// BBox(), of Object::bbox of its objects in primitive order (a leaf holds 0 or 1), an interior node's the enclose of its left and
+// then its right child's (student/bvh.inl:73-75, 119-123) - so the committed poses give the committed boxes back, as values (the
+// zero-sign caveat of prepare_mesh_refit applies).  The listed objects take the Object ctor's values (posed_values); counts, object
+// slots, node_base, ordinals, wave_lazy, lazy_objects, max_tlas_depth and every BVH<Triangle> stay.  Non-finite matrices are not
+// refused.  A list scene has no tree: `boxes` stays empty and only the listed records change.  This is what the device kernels of
+// srt_pt_repose_refit_device are held to, bit for bit.  prepare_top_refit leaves `built` untouched and can refuse the list only
+// (check_repose_list); apply_top_refit writes in place (it cannot fail): inputs' transforms, the listed records of flat.objects,
+// the boxes of tlas, flat.nodes[0 .. tlas_nodes) and flat.wave_tlas, and a listed light's record and area terms.
+struct TopRefit {
+  std::vector<uint32_t> listed;       // insertion indices ..
+  std::vector<Mat4> trans, itrans;    // .. their new transforms, the inverses ..
+  std::vector<uint32_t> has_trans;    // .. and trans != I
+  std::vector<float> boxes;           // six floats {mn, mx} per node of the BVH<Object>
+};
+// The refitted boxes alone: six floats per node of `tree` over the posed boxes of all objects (six floats each, by insertion index).
+void top_refit_boxes(const HostBVH& tree, const float* posed_boxes6, std::vector<float>* boxes6);
+std::string prepare_top_refit(const BuiltScene& built, const uint32_t* objects, const Mat4* trans, uint32_t n, TopRefit* out);
+void apply_top_refit(BuiltScene* built, TopRefit* refit);
 // SAH cost of a BVH (what a caller compares before and after refits to decide when to rebuild), in double from the node boxes:
 // sum over interior nodes of SA(n) / SA(root) + sum over leaves of size(n) * SA(n) / SA(root), SA = 2 (xy + yz + zx) of the extents.
 double tree_cost(const HostBVH& tree);
