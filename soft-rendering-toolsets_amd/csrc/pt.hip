@@ -21,17 +21,10 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <map>
 #include <vector>
 
-#include "pt_bvh_device.h"
+#include "pt_context.h"
 #include "pt_device.h"
-#include "pt_light_update.h"
-#include "pt_pose.h"
-#include "pt_scene.h"
-#include "pt_skin.h"
-#include "srt_common.h"
-#include "srt_pt.h"
 #include "srt_pt_debug.h"
 #include "pt_internal.h"
 
@@ -371,180 +364,7 @@ __global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes
 // ---------------------------------------------------------------------------------------------------
 using namespace srt;
 
-struct srt_pt {
-  int device = -1;            // -1: host-only context (scene assembly / BVH inspection, no rendering)
-  hipStream_t stream = nullptr;
-  std::vector<ObjectInput> inputs;
-  std::vector<Material> materials;
-  BuiltScene built;
-  bool committed = false;
-  Camera cam{};
-  bool have_cam = false;
-  uint32_t w = 0, h = 0, max_depth = 8;
-  TileMap tiles{32, 32, 0, 0, 0, 1, 0};
-  uint32_t tiles_per_rank = 0;
-  // device copies
-  Node* d_nodes = nullptr; Tri* d_tris = nullptr; TriNrm* d_nrm = nullptr; Object* d_objects = nullptr;
-  float* d_tri_packed = nullptr;                                 // the triangle records without padding (pt_scene.h): what the cast kernel reads
-  Light* d_lights = nullptr; LightTri* d_ltris = nullptr; Material* d_mats = nullptr;
-  WaveInterior* d_wave = nullptr; WaveInterior* d_blas = nullptr; uint32_t* d_wave_lazy = nullptr;
-  DeltaLight* d_dlights = nullptr;
-  std::vector<DeltaLight> delta_lights;   // srt_pt_add_light, in call order
-  uint32_t env_type = 0; float env_radiance[3] = {0, 0, 0};   // srt_pt_set_env_light
-  std::vector<float> env_map; uint32_t env_w = 0, env_h = 0; float* d_env_map = nullptr;   // srt_pt_set_env_map
-  float* d_tile_buf = nullptr; size_t tile_buf_floats = 0;
-  float* d_image = nullptr; size_t image_floats = 0;
-  int kernel_mode = 0;        // srt_pt_set_kernel: 0 auto, 1 per-lane (lane per pixel), 2 wave-uniform, 3 wave-uniform with section stamps, 4 per-lane (lane per
-                              // sample), 5 flattened per-lane walk, 6 streamed (logic + ray-cast kernels), 7 streamed sweeps; wave_trav() picks the form
-  // Scratch of one epoch in flight.  One set per stream the caller renders on: epochs launched on different streams
-  // may overlap on the device (the next epoch's blocks fill the CUs the previous launch's tail leaves idle).
-  struct EpochBuffers {
-    float* d_samples = nullptr; size_t samples_floats = 0;   // per-sample radiance
-    float* d_records = nullptr; size_t records_floats = 0;   // wave kernel: per-bounce records
-    float* d_running = nullptr; size_t running_floats = 0;   // (sum, count) across the launches of one epoch
-    unsigned long long* d_queue = nullptr;                   // wave kernel: queue head (+ section stamps)
-    // streamed form (pt_stream.h): saved path state, ray queue, hits, counters
-    uint32_t* d_state = nullptr; size_t state_words = 0;
-    float4* d_ray_o = nullptr; size_t ray_o_n = 0;
-    float4* d_ray_d = nullptr; size_t ray_d_n = 0;
-    uint32_t* d_ray_id = nullptr; size_t ray_id_n = 0;
-    uint2* d_hits = nullptr; size_t hits_n = 0;
-    StreamCounters* d_sc = nullptr;
-    unsigned long long* d_block_counters = nullptr; size_t block_counters_n = 0;
-    uint32_t* d_cast_spill = nullptr; size_t cast_spill_words = 0;   // the ray-cast kernel's traversal frames beyond those in LDS
-    uint32_t* d_cancel = nullptr;                                     // srt_pt_cancel as the kernels of this stream have seen it (sticky until srt_pt_clear_cancel)
-    uint32_t* d_ray_log = nullptr; uint32_t ray_log_cap = 0;          // srt_pt_set_ray_log: this stream's ring (pt_trace.h: log_ray_event)
-    uint32_t* d_alive_list = nullptr; size_t alive_list_n = 0;          // streamed forms: the alive slots the next generation works from
-    uint32_t last_samples = 0, last_npix = 0;                         // what d_samples holds: samples per pixel and pixel slots of the last launch
-  };
-  std::map<hipStream_t, EpochBuffers> epoch_buffers;
-  int wave_blocks = 0; size_t wave_lds = 0; int wave_mode = -1; const void* wave_kern = nullptr;
-  const void* cast_kern = nullptr; uint32_t cast_lds_frames = 0;                                 // traversal frames per lane kept in LDS (the deeper ones: d_cast_spill)
-  int cast_blocks = 0, cast_threads = 0; size_t cast_lds = 0; uint32_t cast_depth = 0;   // pt_cast_kernel's launch shape (0: not derived yet)
-  int bvh_builder = 1; uint32_t bvh_device_min = 16384;         // srt_pt_set_bvh_builder: device build for sets of >= this many primitives
-  uint32_t stream_slots = 0;                                    // srt_pt_set_stream_slots (0: default)
-  unsigned long long* d_cast_stats = nullptr;                   // SRT_CAST_STATS=1: the STATS build of pt_cast_kernel adds into these
-  unsigned long long* d_totals = nullptr;   // C_COUNT instrumented totals + 4 slots: rays of the epoch kernels, rays elided, streamed forms: entries queued, alive slot-generations
-  uint32_t* h_fault = nullptr;              // pinned, device-visible: bit 0 = a streamed launch ended with unfinished units (sticky until reported)
-  uint32_t* d_fault = nullptr;              // its device address
-  uint32_t* h_cancel = nullptr;             // pinned, device-visible: srt_pt_cancel's flag (any host thread may set it)
-  uint32_t* d_host_cancel = nullptr;        // its device address
-  uint32_t ray_log_cap = 0;                 // srt_pt_set_ray_log: rays per stream and read; 0: Pathtracer::log_ray is not delivered
-  int elide = 0;                            // srt_pt_set_elision
-  int normal_colors = 0;                    // srt_pt_set_normal_colors: read whenever a launch is enqueued
-  unsigned long long last_counters[C_COUNT] = {0};
-  uint64_t camera_samples = 0;
-  // srt_pt_kernel_time: event pairs recorded around the dominant kernel's launches, on the launch stream
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;   // pending (recorded, not yet read)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> spare;
-  // srt_pt_stream_times: per-kernel event pairs of the streamed form {logic, compaction, ray cast}
-  bool stream_timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> stream_timed[4];   // {logic (resolve), compaction, ray cast, probe}
-  uint64_t stream_generations = 0;
-  // srt_pt_scene_counts: since creation
-  uint64_t blas_builds = 0, bytes_uploaded = 0, tri_bytes_uploaded = 0;
-  // srt_pt_update_mesh: the index buffers of the meshes that can be updated (no instance, no area light), resident from commit on, one
-  // after the other; the device builder's workspace; and the staging of the host form's vertex arrays.  Grown on demand, kept.
-  uint32_t* d_idx = nullptr; size_t idx_words = 0;
-  std::vector<size_t> idx_off;              // per object in insertion order: first word of its index buffer in d_idx (SIZE_MAX: none)
-  BvhWorkspace bvh_ws;
-  float* d_vpos = nullptr; size_t vpos_floats = 0;
-  float* d_vnrm = nullptr; size_t vnrm_floats = 0;
-  // srt_pt_refit_mesh: per refitted mesh (insertion index) what its kernels keep on the device, from the first refit until the mesh
-  // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
-  std::map<uint32_t, RefitTables> refit_tables;
-  uint64_t refits = 0;
-  // srt_pt_repose_device: what its kernels keep on the device between calls - every object's record by insertion index, its
-  // object-space box and its posed box - made at the first device repose after a commit (drop_pose_tables: a commit, a mesh update
-  // or refit and a host repose change what they mirror; so does a device repose that is refused).  The per-call arrays (the list,
-  // the read-back staging, the mesh ordinals per slot) are grown on demand and kept.
-  Object* d_pose_records = nullptr; float* d_local_boxes = nullptr; float* d_posed_boxes = nullptr;
-  bool pose_tables = false;
-  uint32_t* d_pose_list = nullptr; size_t pose_list_n = 0;
-  PoseOut* d_pose_out = nullptr; size_t pose_out_n = 0;
-  uint32_t* d_slot_ordinal = nullptr; size_t slot_ordinal_n = 0;
-  // srt_pt_set_dynamic_lights (the switch itself is built.dynamic_lights): srt_pt_repose_device's table of the listed lights
-  // ({position in the list, light} pairs), grown on demand and kept; and the bytes of index buffers that went up for a light's
-  // first update or refit (ensure_mesh_idx) and are counted with the verdict
-  uint32_t* d_light_list = nullptr; size_t light_list_n = 0;
-  uint64_t idx_uncounted = 0;
-  // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
-  uint64_t scene_generation = 0;
-  // srt_pt_repose_refit[_device]: the BVH<Object>'s refit tables (RefitTables of pt_bvh_device.h; d_tri_boxes stays NULL - the posed
-  // boxes of the pose tables stand in its place) and the slot of every object, made at the first device-form refit of a tree and
-  // dropped wherever the tree is replaced (drop_top_tables).  top_list: what d_pose_list (and d_light_list) hold when the last call
-  // that wrote them was a device-form refit - a call with the same list uploads nothing.  pinned: host staging of the lists, one
-  // buffer per list still on its way (its event tells), so that a call never waits for the one before.
-  RefitTables top_tables; bool have_top_tables = false;
-  uint32_t* d_slot_of = nullptr;
-  std::vector<uint32_t> top_list; bool top_list_valid = false;
-  uint32_t top_lights = 0, top_light_max_ntri = 0;        // of top_list: listed lights, and the largest triangle count among them
-  struct PinnedList { uint32_t* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
-  std::vector<PinnedList> pinned;
-  // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of objects
-  // they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls are
-  // pending), and the event recorded behind the last of them.
-  uint64_t top_pending = 0;
-  std::vector<uint8_t> top_pending_flag;
-  std::vector<uint32_t> top_pending_objects;
-  hipEvent_t top_event = nullptr;
-  uint64_t top_refits = 0;                  // srt_pt_top_refit_count
-};
-
 namespace {
-
-// The one exit of scene data to the device.  tri_class: triangle, normal, packed-triangle or BLAS-record bytes - what an
-// instance shares and srt_pt_repose leaves alone (srt_pt_scene_counts tells them apart).
-template <typename T>
-int upload(srt_pt* pt, T** dst, const std::vector<T>& src, bool tri_class = false) {
-  if (*dst) { SRT_HIP(hipFree(*dst)); *dst = nullptr; }
-  const size_t n = src.empty() ? 1 : src.size();
-  SRT_HIP(hipMalloc(dst, n * sizeof(T)));
-  if (!src.empty()) SRT_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  pt->bytes_uploaded += src.size() * sizeof(T);
-  if (tri_class) pt->tri_bytes_uploaded += src.size() * sizeof(T);
-  return SRT_OK;
-}
-
-void free_refit_tables(RefitTables* T) {
-  for (void* p : {(void*)T->d_prim, T->d_leaves, T->d_list, T->d_children, (void*)T->d_level_off, (void*)T->d_tri_boxes, (void*)T->d_node_boxes})
-    if (p) (void)hipFree(p);
-  *T = RefitTables();
-}
-
-// The refit tables of `object` (UINT32_MAX: of every mesh): its tree is about to be replaced.
-void drop_refit_tables(srt_pt* pt, uint32_t object) {
-  for (auto it = pt->refit_tables.begin(); it != pt->refit_tables.end();) {
-    if (object == UINT32_MAX || it->first == object) { free_refit_tables(&it->second); it = pt->refit_tables.erase(it); }
-    else ++it;
-  }
-}
-
-// The BVH<Object> is about to be replaced (or d_pose_list to be overwritten by another call: then only the list is forgotten).
-void forget_top_list(srt_pt* pt) { pt->top_list_valid = false; pt->top_list.clear(); }
-void drop_top_tables(srt_pt* pt) {
-  pt->top_tables.d_tri_boxes = nullptr;                   // (the pose tables' posed boxes: drop_pose_tables frees them)
-  if (pt->have_top_tables) free_refit_tables(&pt->top_tables);
-  pt->have_top_tables = false;
-  if (pt->d_slot_of) (void)hipFree(pt->d_slot_of);
-  pt->d_slot_of = nullptr;
-  forget_top_list(pt);
-}
-
-void drop_pose_tables(srt_pt* pt) {
-  for (void* p : {(void*)pt->d_pose_records, (void*)pt->d_local_boxes, (void*)pt->d_posed_boxes})
-    if (p) (void)hipFree(p);
-  pt->d_pose_records = nullptr; pt->d_local_boxes = pt->d_posed_boxes = nullptr;
-  pt->pose_tables = false;
-}
-
-int need_device(srt_pt* pt, const char* what) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "%s: NULL context", what);
-  if (pt->device < 0) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only and there is no CPU fallback", what);
-  SRT_HIP(hipSetDevice(pt->device));
-  return SRT_OK;
-}
 
 // After a synchronisation: did a streamed launch end with unfinished units (pt_stream_finish_kernel)?  Reported once.
 int check_stream_fault(srt_pt* pt, const char* what) {
@@ -558,55 +378,10 @@ int check_stream_fault(srt_pt* pt, const char* what) {
 int need_ready(srt_pt* pt, const char* what) {
   int st = need_device(pt, what);
   if (st != SRT_OK) return st;
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
+  if (!pt->committed) return not_committed(what);
   if (!pt->have_cam) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_camera", what);
   if (!pt->w || !pt->h) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_params", what);
   return SRT_OK;
-}
-
-// The host's record catches up with the device after srt_pt_repose_refit_device calls: one wait for the event behind the last of
-// them, one read-back (176 B per object: the records by insertion index; 24 B per node: the top-level boxes), and the scene
-// layer's own apply_top_refit - the lights' records come from the host's light_record / light_area_term.  Every entry point that
-// is not itself enqueue-only calls this first; with nothing pending it does nothing.
-void discard_pending(srt_pt* pt);
-int settle(srt_pt* pt) {
-  if (!pt || !pt->top_pending) return SRT_OK;
-  if (!pt->committed) { discard_pending(pt); return SRT_OK; }   // (a failure took the scene away: there is no record to bring up to date)
-  const uint64_t calls = pt->top_pending;
-  pt->top_pending = 0;
-  std::vector<uint32_t> objects;
-  objects.swap(pt->top_pending_objects);
-  for (uint32_t i : objects) pt->top_pending_flag[i] = 0;
-  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
-  const bool use_bvh = pt->built.flat.use_bvh;
-  std::vector<Object> records(nobj);
-  TopRefit R;
-  if (use_bvh) R.boxes.resize(6 * (size_t)pt->top_tables.nnodes);
-  if (hipSetDevice(pt->device) != hipSuccess || hipEventSynchronize(pt->top_event) != hipSuccess ||
-      (nobj && hipMemcpy(records.data(), pt->d_pose_records, (size_t)nobj * sizeof(Object), hipMemcpyDeviceToHost) != hipSuccess) ||
-      (!R.boxes.empty() && hipMemcpy(R.boxes.data(), pt->top_tables.d_node_boxes, R.boxes.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
-    pt->committed = false;
-    return srt::fail(SRT_ERR_HIP, "settling srt_pt_repose_refit_device: %s; the scene has to be committed again", hipGetErrorString(hipGetLastError()));
-  }
-  for (uint32_t i : objects) {                            // (every object once: top_pending_flag)
-    R.listed.push_back(i);
-    R.trans.push_back(records[i].trans);
-    R.itrans.push_back(records[i].itrans);
-    R.has_trans.push_back(records[i].has_trans);
-  }
-  apply_top_refit(&pt->built, &R);
-  pt->top_refits += calls;
-  return SRT_OK;
-}
-
-// srt_pt_scene_begin, srt_pt_scene_commit, srt_pt_destroy: what is pending describes a scene that goes; wait for it and forget it.
-void discard_pending(srt_pt* pt) {
-  if (!pt->top_pending) return;
-  if (hipSetDevice(pt->device) == hipSuccess) (void)hipEventSynchronize(pt->top_event);
-  pt->top_refits += pt->top_pending;                      // (they ran; only their read-back is not worth making any more)
-  pt->top_pending = 0;
-  for (uint32_t i : pt->top_pending_objects) pt->top_pending_flag[i] = 0;
-  pt->top_pending_objects.clear();
 }
 
 // srt_pt_set_elision asked for it and the BSDF-sampled direct ray of every continuous bounce is provably dead in this scene:
@@ -650,19 +425,6 @@ void update_tiling(srt_pt* pt) {
   const uint32_t ntiles = T.tiles_x * T.tiles_y;
   pt->tiles_per_rank = (ntiles + T.world - 1) / T.world;
   T.local_tiles = (ntiles > T.rank) ? (ntiles - T.rank + T.world - 1) / T.world : 0;
-}
-
-}  // namespace
-
-namespace {
-
-template <typename T>
-int ensure(T** buf, size_t* have, size_t need) {
-  if (*have >= need && *buf) return SRT_OK;
-  if (*buf) { SRT_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
-  SRT_HIP(hipMalloc(buf, need * sizeof(T)));
-  *have = need;
-  return SRT_OK;
 }
 
 // The scratch set of stream `s` (created on first use), with what every kernel form needs: the stream's sticky cancel word and,
@@ -1176,6 +938,13 @@ int render_epoch_normals(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t samp
 }  // namespace
 
 namespace srt {
+int need_device(srt_pt* pt, const char* what) {
+  if (!pt) return srt::fail(SRT_ERR_INVALID, "%s: NULL context", what);
+  if (pt->device < 0) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only and there is no CPU fallback", what);
+  SRT_HIP(hipSetDevice(pt->device));
+  return SRT_OK;
+}
+
 int pt_check_fault(srt_pt* pt, const char* what) { return pt ? check_stream_fault(pt, what) : SRT_OK; }
 }  // namespace srt
 
@@ -1233,9 +1002,7 @@ int srt_pt_destroy(srt_pt* pt) {
     (void)hipFree(pt->d_tile_buf); (void)hipFree(pt->d_image); (void)hipFree(pt->d_totals);
     (void)hipFree(pt->d_idx); (void)hipFree(pt->d_vpos); (void)hipFree(pt->d_vnrm);
     bvh_workspace_free(&pt->bvh_ws);
-    drop_refit_tables(pt, UINT32_MAX);
-    drop_pose_tables(pt);
-    drop_top_tables(pt);
+    drop_update_tables(pt, UINT32_MAX);
     for (auto& pl : pt->pinned) { (void)hipHostFree(pl.h); (void)hipEventDestroy(pl.done); }
     if (pt->top_event) (void)hipEventDestroy(pt->top_event);
     (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal); (void)hipFree(pt->d_light_list);
@@ -1386,26 +1153,21 @@ int srt_pt_set_env_map(srt_pt* pt, uint32_t width, uint32_t height, const float*
 
 int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_commit: NULL context");
-  // BVH<Triangle> builds of big meshes run on the device (pt_bvh_device.hip: identical arrays); srt_pt_set_bvh_builder
-  const char* be = getenv("SRT_BVH_BUILDER");
-  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
   discard_pending(pt);
-  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_refit_tables(pt, UINT32_MAX); drop_pose_tables(pt); drop_top_tables(pt); }   // they describe trees and records that are about to go
-  if (pt->device >= 0 && bmode != 0) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
-  else set_device_bvh_builder(nullptr, 0);
+  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_update_tables(pt, UINT32_MAX); }   // they describe trees and records that are about to go
+  pt->committed = false;    // build_scene replaces the host's record, the uploads below the device's: no scene until the last has gone through
+  // BVH<Triangle> builds of big meshes run on the device (pt_bvh_device.hip: identical arrays); srt_pt_set_bvh_builder
+  const DeviceBuilderScope builder(pt, device_builds(pt));
   const std::string err = build_scene(pt->inputs, pt->materials, use_bvh != 0, &pt->built);
-  set_device_bvh_builder(nullptr, 0);
   pt->blas_builds += pt->built.blas_builds;
   if (!err.empty()) return srt::fail(SRT_ERR_UNSUPPORTED, "%s", err.c_str());
   pt->built.flat.delta_lights = pt->delta_lights;
   const FlatScene& F = pt->built.flat;
-  if ((int)F.max_tlas_depth > kMaxTlasDepth || (int)F.max_blas_depth > kMaxBlasDepth)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)",
-                     F.max_tlas_depth, kMaxTlasDepth, F.max_blas_depth, kMaxBlasDepth);
+  int st;
+  if ((st = check_depth(F.max_tlas_depth, F.max_blas_depth))) return st;
   if (pt->device >= 0) {
     SRT_HIP(hipSetDevice(pt->device));
     SRT_HIP(hipStreamSynchronize(pt->stream));
-    int st;
     if ((st = upload(pt, &pt->d_nodes, F.nodes)) || (st = upload(pt, &pt->d_tris, F.tris, true)) || (st = upload(pt, &pt->d_nrm, F.tri_nrm, true)) ||
         (st = upload(pt, &pt->d_tri_packed, F.tri_packed, true)) ||
         (st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_lights, F.lights)) ||
@@ -1413,7 +1175,7 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
         (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_blas, F.blas_recs, true)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)) ||
         (st = upload(pt, &pt->d_dlights, F.delta_lights)) || (st = upload(pt, &pt->d_env_map, pt->env_map)))
       return st;
-    // the index buffers srt_pt_update_mesh's kernels read (12 B per triangle)
+    // the index buffers the kernels of pt_mesh_update.hip read (12 B per triangle)
     std::vector<uint32_t> idx;
     pt->idx_off.assign(pt->built.inputs.size(), SIZE_MAX);
     for (size_t i = 0; i < pt->built.inputs.size(); i++) {
@@ -1429,1076 +1191,6 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   pt->committed = true;
   pt->scene_generation++;
   pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
-  return SRT_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The index buffer of mesh `object` on the device.  Every mesh that can be updated has its own from the commit on; an emissive
-// mesh has it from the commit only when srt_pt_set_dynamic_lights was on by then - otherwise it is appended here, at the light's
-// first update, refit or skin.  Nothing a render kernel reads; the caller has waited for whatever reads d_idx.
-int ensure_mesh_idx(srt_pt* pt, uint32_t object) {
-  if (pt->idx_off[object] != SIZE_MAX) return SRT_OK;
-  const std::vector<uint32_t>& idx = pt->built.inputs[object].mesh.idx;
-  uint32_t* fresh = nullptr;
-  SRT_HIP(hipMalloc(&fresh, (pt->idx_words + idx.size()) * sizeof(uint32_t)));
-  if ((pt->idx_words && hipMemcpy(fresh, pt->d_idx, pt->idx_words * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess) ||
-      hipMemcpy(fresh + pt->idx_words, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(fresh);
-    return srt::fail(SRT_ERR_HIP, "index buffer of object %u: device copy failed", object);
-  }
-  if (pt->d_idx) (void)hipFree(pt->d_idx);
-  pt->d_idx = fresh;
-  pt->idx_off[object] = pt->idx_words;
-  pt->idx_words += idx.size();
-  pt->idx_uncounted += idx.size() * sizeof(uint32_t);
-  return SRT_OK;
-}
-
-// Host forms of the dynamic-light calls (srt_pt_repose, srt_pt_update_mesh, srt_pt_refit_mesh): the light's record and its
-// LightTri records from the host mirror, and - after new vertices - its light-list triangle copies.  The device forms run the
-// kernels of pt_light_update.hip instead and upload none of this.
-int upload_light(srt_pt* pt, uint32_t li, bool triangles) {
-  const FlatScene& F = pt->built.flat;
-  const Light& L = F.lights[li];
-  const size_t lt = (size_t)(L.tri_base - F.light_tri_first), n = L.ntri;
-  SRT_HIP(hipMemcpy(pt->d_lights + li, &L, sizeof(Light), hipMemcpyHostToDevice));
-  if (n) SRT_HIP(hipMemcpy(pt->d_ltris + lt, &F.light_tris[lt], n * sizeof(LightTri), hipMemcpyHostToDevice));
-  pt->bytes_uploaded += sizeof(Light) + n * sizeof(LightTri);
-  if (triangles && n) {
-    SRT_HIP(hipMemcpy(pt->d_tris + L.tri_base, &F.tris[L.tri_base], n * sizeof(Tri), hipMemcpyHostToDevice));
-    SRT_HIP(hipMemcpy(pt->d_nrm + L.tri_base, &F.tri_nrm[L.tri_base], n * sizeof(TriNrm), hipMemcpyHostToDevice));
-    SRT_HIP(hipMemcpy(pt->d_tri_packed + 9 * (size_t)L.tri_base, &F.tri_packed[9 * (size_t)L.tri_base], 9 * n * sizeof(float), hipMemcpyHostToDevice));
-    const uint64_t bytes = n * (sizeof(Tri) + sizeof(TriNrm) + 9 * sizeof(float));
-    pt->bytes_uploaded += bytes;
-    pt->tri_bytes_uploaded += bytes;
-  }
-  return SRT_OK;
-}
-
-// The light tables of an emissive mesh after new vertices (the verdict is in, the host mirror is true, nothing is in flight):
-// the device forms rewrite them with the kernel from the arrays where they are, the host forms upload them.
-int write_light_mesh_device(srt_pt* pt, hipStream_t s, uint32_t object, bool device_form, const float* d_pos, const float* d_nrm) {
-  const int32_t li = light_of(pt->built, object);
-  if (li < 0) return SRT_OK;
-  if (!device_form) return upload_light(pt, (uint32_t)li, true);
-  const FlatScene& F = pt->built.flat;
-  const Light& L = F.lights[(size_t)li];
-  launch_light_triangles(s, d_pos, d_nrm, pt->d_idx + pt->idx_off[object], L.ntri, pt->d_lights + li, pt->d_tris + L.tri_base, pt->d_nrm + L.tri_base,
-                         pt->d_tri_packed + 9 * (size_t)L.tri_base, pt->d_ltris + (L.tri_base - F.light_tri_first));
-  SRT_HIP(hipStreamSynchronize(s));
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-// Device side of a mesh update whose verdict is in (srt_pt_update_mesh): the node and record arrays after the scene layer
-// re-packed them.  [0, keep) of the old array has not moved and [from, size) of the new one is new or has moved; with another
-// total length the array is allocated anew, the part that stays is copied on the device and only the rest comes from the host.
-template <typename T>
-int upload_tail(srt_pt* pt, hipStream_t s, T** dst, size_t old_size, const std::vector<T>& src, size_t keep_from, size_t keep_to, size_t keep_n,
-                size_t up_from, size_t up_to, bool tri_class) {
-  // old[keep_from, keep_from + keep_n) -> new[keep_to, ..);  src[up_from, up_to) -> new[up_from, up_to)
-  if (src.size() != old_size || keep_from != keep_to) {
-    T* fresh = nullptr;
-    SRT_HIP(hipMalloc(&fresh, (src.empty() ? 1 : src.size()) * sizeof(T)));
-    if ((keep_n && hipMemcpyAsync(fresh + keep_to, *dst + keep_from, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipFree(fresh);
-      return srt::fail(SRT_ERR_HIP, "srt_pt_update_mesh: device copy failed");
-    }
-    (void)hipFree(*dst);
-    *dst = fresh;
-  }
-  if (up_to > up_from) {
-    SRT_HIP(hipMemcpyAsync(*dst + up_from, src.data() + up_from, (up_to - up_from) * sizeof(T), hipMemcpyHostToDevice, s));
-    pt->bytes_uploaded += (up_to - up_from) * sizeof(T);
-    if (tri_class) pt->tri_bytes_uploaded += (up_to - up_from) * sizeof(T);
-  }
-  return SRT_OK;
-}
-
-// The device writes of a mesh update, after apply_mesh_update: the record kernel over the mesh's triangle range, the nodes and
-// records that are new or moved, the tables of object order.  `old`: the mesh's storage before.
-int write_updated_mesh(srt_pt* pt, hipStream_t s, uint32_t object, const MeshStore& old, size_t old_tlas, size_t old_nodes, size_t old_recs,
-                       const float* d_pos, const float* d_nrm, const uint32_t* d_mesh_idx) {
-  const FlatScene& F = pt->built.flat;
-  const bool use_bvh = F.use_bvh;
-  const MeshStore now = pt->built.store[object];
-  const uint32_t ntri = now.ntri;
-  launch_mesh_records(s, d_pos, d_nrm, d_mesh_idx, use_bvh ? pt->bvh_ws.d_prim : nullptr, ntri, pt->d_tris + now.tri_base, pt->d_nrm + now.tri_base,
-                      pt->d_tri_packed + 9 * (size_t)now.tri_base);
-  int st;
-  if (use_bvh) {
-    // nodes: the BVH<Object>'s and the mesh's are new; the BVH<Triangle>s in front stay, those behind move when the mesh's count changed
-    const bool same_nodes = now.nnodes == old.nnodes, same_recs = now.nrec == old.nrec;
-    const size_t at = (size_t)F.tlas_nodes + now.node_off;
-    if ((st = upload_tail(pt, s, &pt->d_nodes, old_nodes, F.nodes, old_tlas, F.tlas_nodes, old.node_off, at,
-                          same_nodes && F.tlas_nodes == old_tlas ? at + now.nnodes : F.nodes.size(), false)))
-      return st;
-    if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
-    pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
-    if ((st = upload_tail(pt, s, &pt->d_blas, old_recs, F.blas_recs, 0, 0, old.rec_base, now.rec_base,
-                          same_recs ? (size_t)now.rec_base + now.nrec : F.blas_recs.size(), true)))
-      return st;
-  }
-  SRT_HIP(hipStreamSynchronize(s));
-  SRT_HIP(hipGetLastError());
-  if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
-    return st;
-  return SRT_OK;
-}
-
-
-// srt_pt_update_mesh / srt_pt_update_mesh_device.  h_*: the host form's arrays; d_*: the device form's (then `s` is the caller's stream).
-int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* h_pos, const float* h_nrm, const float* d_pos,
-                const float* d_nrm, uint32_t nverts) {
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
-  const std::string refused = check_mesh_update(pt->built, object, nverts);
-  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
-  const bool on_device = pt->device >= 0;
-  if (!on_device && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
-  const bool use_bvh = pt->built.flat.use_bvh;
-  const bool device_form = h_pos == nullptr;
-  const MeshStore old = pt->built.store[object];
-  const uint32_t ntri = old.ntri;
-  const size_t vfloats = 3 * (size_t)nverts;
-  std::vector<float> back_pos, back_nrm;
-  if (on_device) {
-    SRT_HIP(hipSetDevice(pt->device));
-    SRT_HIP(hipStreamSynchronize(pt->stream));
-    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old arrays
-    const int ist = ensure_mesh_idx(pt, object);          // (an emissive mesh's first update under srt_pt_set_dynamic_lights)
-    if (ist != SRT_OK) return ist;
-    if (h_pos) {                                          // 24 B per vertex up, into the staging (nothing of the live scene yet)
-      int st;
-      if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
-      // (blocking copies: the caller's arrays are not read after this call returns, whichever way it returns)
-      SRT_HIP(hipMemcpy(pt->d_vpos, h_pos, vfloats * sizeof(float), hipMemcpyHostToDevice));
-      SRT_HIP(hipMemcpy(pt->d_vnrm, h_nrm, vfloats * sizeof(float), hipMemcpyHostToDevice));
-      pt->bytes_uploaded += 2 * vfloats * sizeof(float);
-      d_pos = pt->d_vpos; d_nrm = pt->d_vnrm;
-    } else {                                              // 24 B per vertex back: BuiltScene::inputs and the host mirrors stay true
-      back_pos.resize(vfloats); back_nrm.resize(vfloats);
-      SRT_HIP(hipMemcpyAsync(back_pos.data(), d_pos, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
-      SRT_HIP(hipMemcpyAsync(back_nrm.data(), d_nrm, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
-      SRT_HIP(hipStreamSynchronize(s));
-      h_pos = back_pos.data(); h_nrm = back_nrm.data();
-    }
-  }
-  // the one BVH<Triangle> build goes where srt_pt_scene_commit's would: a mesh at or above the device builder's threshold is
-  // built there, from boxes computed there; anything else on the host
-  const char* be = getenv("SRT_BVH_BUILDER");
-  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  const uint32_t* d_mesh_idx = on_device ? pt->d_idx + pt->idx_off[object] : nullptr;
-  HostBVH device_tree;
-  const bool device_wanted = on_device && use_bvh && bmode != 0 && ntri >= pt->bvh_device_min && ntri > 4u;
-  bool device_built = false;
-  if (device_wanted && bvh_workspace_reserve(&pt->bvh_ws, ntri, false)) {
-    launch_mesh_boxes(s, d_pos, d_mesh_idx, ntri, pt->bvh_ws.d_boxes);
-    device_built = build_bvh_device_core(&pt->bvh_ws, s, ntri, 4, &device_tree);
-  }
-  // The BVH<Object> build goes where srt_pt_repose's does.  A device build of the mesh that failed - no termination, or no
-  // memory - is not tried a second time through the wrapper: the host builds give the verdict.
-  if (on_device && bmode != 0 && !(device_wanted && !device_built)) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
-  else set_device_bvh_builder(nullptr, 0);
-  MeshUpdate U;
-  bool bad_argument = false;
-  const std::string err = prepare_mesh_update(pt->built, object, h_pos, h_nrm, nverts, device_built ? &device_tree : nullptr, &U, &bad_argument);
-  set_device_bvh_builder(nullptr, 0);
-  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str());
-  if ((int)U.top.max_tlas_depth > kMaxTlasDepth || (int)U.max_blas_depth > kMaxBlasDepth)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)",
-                     U.top.max_tlas_depth, kMaxTlasDepth, U.max_blas_depth, kMaxBlasDepth);
-  if (on_device && use_bvh && !device_built) {            // a host build: its primitive order goes up, 4 B per triangle
-    if (!bvh_workspace_reserve(&pt->bvh_ws, ntri, true)) return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
-    SRT_HIP(hipMemcpy(pt->bvh_ws.d_prim, U.blas.prim.data(), (size_t)ntri * 4, hipMemcpyHostToDevice));
-    pt->bytes_uploaded += (uint64_t)ntri * 4;
-  }
-  // the verdict is in: from here on the new arrays replace the old ones, on the host and then on the device
-  const size_t old_tlas = pt->built.flat.tlas_nodes, old_nodes = pt->built.flat.nodes.size(), old_recs = pt->built.flat.blas_recs.size();
-  apply_mesh_update(&pt->built, &U);
-  if (on_device) { drop_refit_tables(pt, object); drop_pose_tables(pt); drop_top_tables(pt); }   // they describe the tree and the boxes that were just replaced
-  if (use_bvh) pt->blas_builds++;
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
-  if (!on_device) return SRT_OK;
-  pt->bytes_uploaded += pt->idx_uncounted;
-  pt->idx_uncounted = 0;
-  // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
-  int st = write_updated_mesh(pt, s, object, old, old_tlas, old_nodes, old_recs, d_pos, d_nrm, d_mesh_idx);
-  if (st == SRT_OK) st = write_light_mesh_device(pt, s, object, device_form, d_pos, d_nrm);
-  if (st != SRT_OK) pt->committed = false;
-  return st;
-}
-
-// The device tables of a tree's refits, from the host tree: made at the first refit after a commit or a rebuild.  `tree`: a mesh's
-// BVH<Triangle> (object: its insertion index) or the BVH<Object> (object == UINT32_MAX; its primitives are the objects, whose
-// boxes the pose tables hold already: no box array of their own is made).
-int make_refit_tables(const HostBVH& tree, const char* what, uint32_t object, RefitTables* T) {
-  const bool top = object == UINT32_MAX;
-  const std::string whose = top ? std::string("the BVH<Object>") : "object " + std::to_string(object);
-  const char* const inside = top ? "scene" : "mesh";
-  const uint32_t nn = (uint32_t)tree.nodes.size(), ntri = (uint32_t)tree.prim.size();
-  // a node's level: children lie behind their parent (level order, student/bvh.inl:144-145), so one forward pass does it
-  std::vector<uint32_t> level(nn, 0u);
-  uint32_t levels = 0;
-  for (uint32_t n = 0; n < nn; n++) {
-    const HostNode& h = tree.nodes[n];
-    if (h.l == h.r) {
-      // the leaf table packs (first slot << 3) | count, and the kernels trust it: refuse here what they could not take
-      if (h.size > 7u || h.start >= (1u << 29) || (uint64_t)h.start + h.size > ntri)
-        return srt::fail(SRT_ERR_UNSUPPORTED, "%s: leaf %u of %s holds %u primitives from slot %u (at most 7, below 2^29, inside the %s)", what, n,
-                         whose.c_str(), h.size, h.start, inside);
-      continue;
-    }
-    if (h.l <= n || h.r != h.l + 1u || h.r >= nn) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the tree of %s is not in level order", what, whose.c_str());
-    level[h.l] = level[h.r] = level[n] + 1u;
-    levels = std::max(levels, level[n] + 1u);
-  }
-  for (uint32_t t : tree.prim)
-    if (t >= ntri) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the primitive order of %s names %s %u of %u", what, whose.c_str(), top ? "object" : "triangle", t, ntri);
-  std::vector<uint2> leaves, list, children;
-  std::vector<uint32_t> off(levels + 1u, 0u);
-  for (uint32_t n = 0; n < nn; n++) {
-    const HostNode& h = tree.nodes[n];
-    if (h.l == h.r) leaves.push_back(make_uint2(n, (h.start << 3) | (h.size & 7u)));
-    else { off[level[n] + 1u]++; children.push_back(make_uint2(h.l, h.r)); }     // records are numbered in node order (append_records)
-  }
-  for (uint32_t l = 0; l < levels; l++) off[l + 1u] += off[l];
-  list.resize(children.size());
-  std::vector<uint32_t> at(off.begin(), off.end() - 1);
-  for (uint32_t n = 0; n < nn; n++)
-    if (tree.nodes[n].l != tree.nodes[n].r) list[at[level[n]]++] = make_uint2(n, tree.nodes[n].l);
-  T->ntri = ntri; T->nnodes = nn; T->nleaves = (uint32_t)leaves.size(); T->nrec = (uint32_t)children.size();
-  T->level_off = off;
-  const char* ll = getenv("SRT_REFIT_LEVEL_LAUNCHES");
-  T->level_launches = ll && atoi(ll) != 0;
-  auto up = [&](auto** dst, const auto& src) -> bool {
-    using E = typename std::remove_reference<decltype(src)>::type::value_type;
-    if (hipMalloc((void**)dst, (src.empty() ? 1 : src.size()) * sizeof(E)) != hipSuccess) return false;
-    if (!src.empty() && hipMemcpy(*dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice) != hipSuccess) return false;
-    T->uncounted_bytes += src.size() * sizeof(E);
-    return true;
-  };
-  if (!up(&T->d_prim, tree.prim) || !up(&T->d_leaves, leaves) || !up(&T->d_list, list) || !up(&T->d_children, children) || !up(&T->d_level_off, off) ||
-      (!top && hipMalloc(&T->d_tri_boxes, (size_t)ntri * 6 * sizeof(float)) != hipSuccess) ||
-      hipMalloc(&T->d_node_boxes, (size_t)(nn ? nn : 1) * 6 * sizeof(float)) != hipSuccess) {
-    free_refit_tables(T);
-    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
-  }
-  return SRT_OK;
-}
-
-// srt_pt_refit_mesh / srt_pt_refit_mesh_device / srt_pt_skin_pose_refit.  h_*: the host form's arrays; d_*: the device form's.
-int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* h_pos, const float* h_nrm, const float* d_pos,
-               const float* d_nrm, uint32_t nverts) {
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
-  const std::string refused = check_mesh_update(pt->built, object, nverts);
-  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
-  if (!pt->built.flat.use_bvh) return update_mesh(pt, what, s, object, h_pos, h_nrm, d_pos, d_nrm, nverts);   // a list has no tree: the update
-  const bool on_device = pt->device >= 0;
-  if (!on_device && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
-  const MeshStore m = pt->built.store[object];
-  const bool device_form = h_pos == nullptr;
-  const size_t vfloats = 3 * (size_t)nverts;
-  std::vector<float> back_pos, back_nrm, node_boxes;
-  RefitTables* T = nullptr;
-  uint64_t staged_bytes = 0;
-  if (on_device) {
-    SRT_HIP(hipSetDevice(pt->device));
-    SRT_HIP(hipStreamSynchronize(pt->stream));
-    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old arrays
-    const int ist = ensure_mesh_idx(pt, object);          // (an emissive mesh's first refit under srt_pt_set_dynamic_lights)
-    if (ist != SRT_OK) return ist;
-    if (h_pos) {                                          // 24 B per vertex up, into the staging (nothing of the live scene yet)
-      for (size_t k = 0; k < vfloats; k++)
-        if (!std::isfinite(h_pos[k])) return srt::fail(SRT_ERR_INVALID, "%s: vertex %zu of the new positions has a non-finite coordinate", what, k / 3);
-      int st;
-      if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
-      SRT_HIP(hipMemcpy(pt->d_vpos, h_pos, vfloats * sizeof(float), hipMemcpyHostToDevice));
-      SRT_HIP(hipMemcpy(pt->d_vnrm, h_nrm, vfloats * sizeof(float), hipMemcpyHostToDevice));
-      staged_bytes = 2 * vfloats * sizeof(float);         // (counted with the verdict: a refused refit adds nothing to the figures)
-      d_pos = pt->d_vpos; d_nrm = pt->d_vnrm;
-    }
-    auto it = pt->refit_tables.find(object);
-    if (it == pt->refit_tables.end()) {
-      RefitTables fresh;
-      const int st = make_refit_tables(pt->built.blas[object], "srt_pt_refit_mesh", object, &fresh);
-      if (st != SRT_OK) return st;
-      it = pt->refit_tables.emplace(object, fresh).first;
-    }
-    T = &it->second;
-    // the new boxes, aside: triangle boxes, leaves, levels.  They come back (24 B per node) with the arrays of the device form
-    // (24 B per vertex): the host checks those, takes the root box and keeps its own tree true.
-    launch_mesh_boxes(s, d_pos, pt->d_idx + pt->idx_off[object], m.ntri, T->d_tri_boxes);
-    launch_refit_boxes(s, *T, T->d_node_boxes);
-    node_boxes.resize(6 * (size_t)T->nnodes);
-    SRT_HIP(hipMemcpyAsync(node_boxes.data(), T->d_node_boxes, node_boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (!h_pos) {
-      back_pos.resize(vfloats); back_nrm.resize(vfloats);
-      SRT_HIP(hipMemcpyAsync(back_pos.data(), d_pos, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
-      SRT_HIP(hipMemcpyAsync(back_nrm.data(), d_nrm, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    SRT_HIP(hipStreamSynchronize(s));
-    SRT_HIP(hipGetLastError());
-    if (!h_pos) { h_pos = back_pos.data(); h_nrm = back_nrm.data(); }
-  }
-  // the BVH<Object> build goes where srt_pt_repose's does
-  const char* be = getenv("SRT_BVH_BUILDER");
-  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  if (on_device && bmode != 0) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
-  else set_device_bvh_builder(nullptr, 0);
-  MeshRefit R;
-  bool bad_argument = false;
-  const std::string err = prepare_mesh_refit(pt->built, object, h_pos, h_nrm, nverts, on_device ? node_boxes.data() : nullptr, &R, &bad_argument);
-  set_device_bvh_builder(nullptr, 0);
-  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str());
-  if ((int)R.top.max_tlas_depth > kMaxTlasDepth)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)", R.top.max_tlas_depth, kMaxTlasDepth,
-                     pt->built.flat.max_blas_depth, kMaxBlasDepth);
-  // the verdict is in: from here on the new boxes and records replace the old ones in place, on the host and then on the device
-  const size_t old_tlas = pt->built.flat.tlas_nodes;
-  apply_mesh_refit(&pt->built, &R);
-  pt->refits++;
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
-  if (!on_device) return SRT_OK;
-  drop_pose_tables(pt);                                   // the object-space boxes changed
-  drop_top_tables(pt);                                    // the BVH<Object> was rebuilt
-  pt->bytes_uploaded += staged_bytes + T->uncounted_bytes + pt->idx_uncounted;   // the vertices of the host form; the tables, at the mesh's first successful refit
-  T->uncounted_bytes = 0;
-  pt->idx_uncounted = 0;
-  // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
-  const FlatScene& F = pt->built.flat;
-  auto write = [&]() -> int {
-    int st;
-    if (F.tlas_nodes == old_tlas) {                       // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
-      if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
-      pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
-    } else {
-      SRT_HIP(hipStreamSynchronize(s));
-      if ((st = upload(pt, &pt->d_nodes, F.nodes))) return st;
-    }
-    launch_refit_write(s, *T, T->d_node_boxes, pt->d_nodes + F.tlas_nodes + m.node_off, pt->d_blas + m.rec_base);
-    launch_mesh_records(s, d_pos, d_nrm, pt->d_idx + pt->idx_off[object], T->d_prim, m.ntri, pt->d_tris + m.tri_base, pt->d_nrm + m.tri_base,
-                        pt->d_tri_packed + 9 * (size_t)m.tri_base);
-    SRT_HIP(hipStreamSynchronize(s));
-    SRT_HIP(hipGetLastError());
-    if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
-      return st;
-    return SRT_OK;
-  };
-  int st = write();
-  if (st == SRT_OK) st = write_light_mesh_device(pt, s, object, device_form, d_pos, d_nrm);
-  if (st != SRT_OK) pt->committed = false;
-  return st;
-}
-
-}  // namespace
-
-extern "C" {
-
-int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
-  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh: NULL argument");
-  return update_mesh(pt, "srt_pt_update_mesh", pt->stream, object, positions, normals, nullptr, nullptr, nverts);
-}
-
-int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
-  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh_device: NULL argument");
-  return update_mesh(pt, "srt_pt_update_mesh_device", (hipStream_t)stream, object, nullptr, nullptr, d_positions, d_normals, nverts);
-}
-
-int srt_pt_refit_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
-  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh: NULL argument");
-  return refit_mesh(pt, "srt_pt_refit_mesh", pt->stream, object, positions, normals, nullptr, nullptr, nverts);
-}
-
-int srt_pt_refit_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
-  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh_device: NULL argument");
-  return refit_mesh(pt, "srt_pt_refit_mesh_device", (hipStream_t)stream, object, nullptr, nullptr, d_positions, d_normals, nverts);
-}
-
-int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost) {
-  if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: NULL argument");
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_mesh_tree_cost before srt_pt_scene_commit");
-  const std::string refused = check_mesh_update(pt->built, object, (uint32_t)(object < pt->built.inputs.size() ? pt->built.inputs[object].mesh.pos.size() / 3 : 0));
-  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: %s", refused.c_str());
-  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_mesh_tree_cost: the scene was committed without BVHs, the mesh has no tree");
-  *cost = tree_cost(pt->built.blas[object]);
-  return SRT_OK;
-}
-
-int srt_pt_refit_count(srt_pt* pt, uint64_t* refits) {
-  if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_count: NULL argument");
-  *refits = pt->refits;
-  return SRT_OK;
-}
-
-}  // extern "C"
-
-// ---- srt_pt_skin: Skeleton::find_joints once, Skeleton::skin per frame (pt_skin.h, pt_skin.hip) ----
-struct srt_pt_skin {
-  srt_pt* pt = nullptr;
-  uint64_t generation = 0;                  // pt->scene_generation at creation
-  uint32_t object = 0, nverts = 0, ntri = 0, njoints = 0, ninf = 0;
-  std::vector<float> inv;                   // Mat4::inverse(joint_to_bind(j)), 16 floats per joint
-  std::vector<float> mats;                  // the frame's posed_j * inverse_j on their way up
-  float *d_pos = nullptr, *d_nrm = nullptr;             // the bind-pose mesh
-  float *d_inv = nullptr, *d_cap = nullptr, *d_mats = nullptr;
-  uint32_t *d_off = nullptr, *d_jidx = nullptr, *d_last = nullptr;
-  float* d_w = nullptr;
-  float *d_pos_out = nullptr, *d_nrm_out = nullptr;     // srt_pt_skin_pose's staging
-};
-
-namespace {
-
-void skin_free(srt_pt_skin* k) {
-  if (k->pt && k->pt->device >= 0) (void)hipSetDevice(k->pt->device);
-  for (void* p : {(void*)k->d_pos, (void*)k->d_nrm, (void*)k->d_inv, (void*)k->d_cap, (void*)k->d_mats, (void*)k->d_off, (void*)k->d_jidx, (void*)k->d_last,
-                  (void*)k->d_w, (void*)k->d_pos_out, (void*)k->d_nrm_out})
-    if (p) (void)hipFree(p);
-  delete k;
-}
-
-// The device side of srt_pt_skin_create; on failure the caller frees what is there.
-int skin_build(srt_pt_skin* k, const float* bind_positions, const float* bind_normals, const srt_pt_skin_joint* joints) {
-  srt_pt* pt = k->pt;
-  const size_t vfloats = 3 * (size_t)k->nverts;
-  std::vector<float> cap(4 * (size_t)k->njoints);
-  for (uint32_t j = 0; j < k->njoints; j++) {
-    skin_mat4_inverse(joints[j].bind, &k->inv[16 * (size_t)j]);
-    for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = joints[j].extent[a];
-    cap[4 * (size_t)j + 3] = joints[j].radius;
-  }
-  SRT_HIP(hipSetDevice(pt->device));
-  hipStream_t s = pt->stream;
-  const uint32_t nblocks = (k->nverts + 255u) / 256u;
-  SRT_HIP(hipMalloc(&k->d_pos, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_nrm, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_pos_out, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_nrm_out, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_inv, k->inv.size() * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_mats, k->inv.size() * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_cap, cap.size() * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_off, ((size_t)k->nverts + 1) * sizeof(uint32_t)));
-  SRT_HIP(hipMalloc(&k->d_last, (size_t)k->nverts * sizeof(uint32_t)));
-  SRT_HIP(hipMemcpy(k->d_pos, bind_positions, vfloats * sizeof(float), hipMemcpyHostToDevice));
-  SRT_HIP(hipMemcpy(k->d_nrm, bind_normals, vfloats * sizeof(float), hipMemcpyHostToDevice));
-  SRT_HIP(hipMemcpy(k->d_inv, k->inv.data(), k->inv.size() * sizeof(float), hipMemcpyHostToDevice));
-  SRT_HIP(hipMemcpy(k->d_cap, cap.data(), cap.size() * sizeof(float), hipMemcpyHostToDevice));
-  pt->bytes_uploaded += (2 * vfloats + k->inv.size() + cap.size()) * sizeof(float);
-  // count, scan, fill; the counts and the block sums live only here
-  uint32_t *d_counts = nullptr, *d_sums = nullptr;
-  SRT_HIP(hipMalloc(&d_counts, (size_t)k->nverts * sizeof(uint32_t)));
-  int st = SRT_OK;
-  if (hipMalloc(&d_sums, (size_t)nblocks * sizeof(uint32_t)) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: out of device memory");
-  uint32_t total = 0;
-  if (st == SRT_OK) {
-    launch_skin_count(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, d_counts);
-    launch_skin_scan(s, d_counts, k->nverts, k->d_off, d_sums);
-    if (hipMemcpyAsync(&total, k->d_off + k->nverts, sizeof total, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
-        hipGetLastError() != hipSuccess)
-      st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: the find_joints kernels failed");
-  }
-  (void)hipFree(d_counts); (void)hipFree(d_sums);
-  if (st != SRT_OK) return st;
-  k->ninf = total;
-  SRT_HIP(hipMalloc(&k->d_jidx, (total ? (size_t)total : 1) * sizeof(uint32_t)));
-  SRT_HIP(hipMalloc(&k->d_w, (total ? (size_t)total : 1) * sizeof(float)));
-  launch_skin_fill(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, k->d_off, k->d_jidx, k->d_w);
-  SRT_HIP(hipMemsetAsync(k->d_last, 0, (size_t)k->nverts * sizeof(uint32_t), s));
-  launch_skin_last_triangle(s, pt->d_idx + pt->idx_off[k->object], k->ntri, k->nverts, k->d_last);
-  SRT_HIP(hipStreamSynchronize(s));
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int skin_usable(const srt_pt_skin* k, const char* what) {
-  if (!k) return srt::fail(SRT_ERR_INVALID, "%s: NULL skin", what);
-  if (!k->pt->committed || k->generation != k->pt->scene_generation)
-    return srt::fail(SRT_ERR_STATE, "%s: the skin is stale - its context's scene was begun or committed again after srt_pt_skin_create", what);
-  return SRT_OK;
-}
-
-// Enqueues the frame's matrices and the skinning kernels on s.
-int skin_enqueue(srt_pt_skin* k, hipStream_t s, const float* posed, int flat_normals, float* d_pos_out, float* d_nrm_out) {
-  SRT_HIP(hipSetDevice(k->pt->device));
-  for (uint32_t j = 0; j < k->njoints; j++) skin_mat4_mul(posed + 16 * (size_t)j, &k->inv[16 * (size_t)j], &k->mats[16 * (size_t)j]);
-  SRT_HIP(hipMemcpyAsync(k->d_mats, k->mats.data(), k->mats.size() * sizeof(float), hipMemcpyHostToDevice, s));   // 64 B per joint
-  k->pt->bytes_uploaded += k->mats.size() * sizeof(float);
-  launch_skin_vertices(s, k->d_pos, k->d_nrm, k->nverts, k->d_mats, k->njoints, k->d_off, k->d_jidx, k->d_w, d_pos_out, flat_normals ? nullptr : d_nrm_out);
-  if (flat_normals)
-    launch_skin_flat_normals(s, d_pos_out, k->d_nrm, k->pt->d_idx + k->pt->idx_off[k->object], k->ntri, k->d_last, k->nverts, d_nrm_out);
-  return SRT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions, const float* bind_normals, uint32_t nverts,
-                       const srt_pt_skin_joint* joints, uint32_t njoints, srt_pt_skin** skin) {
-  if (skin) *skin = nullptr;
-  if (!pt || !bind_positions || !bind_normals || !joints || !skin) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: NULL argument");
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_skin_create before srt_pt_scene_commit");
-  const std::string refused = check_mesh_update(pt->built, object, nverts);
-  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: %s", refused.c_str());
-  if (njoints == 0) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: a skin needs at least one joint");
-  if (njoints > kSkinMaxJoints || (uint64_t)nverts * njoints > kSkinMaxPairs)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_skin_create: %u joints on %u vertices (at most %u joints and 2^31 vertex-joint pairs)", njoints, nverts,
-                     kSkinMaxJoints);
-  if (pt->device < 0)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_skin_create: skinning runs on the device only; this context is host-only and there is no CPU path");
-  srt_pt_skin* k = new (std::nothrow) srt_pt_skin;
-  if (!k) return srt::fail(SRT_ERR_INVALID, "out of host memory");
-  k->pt = pt; k->generation = pt->scene_generation; k->object = object; k->nverts = nverts; k->njoints = njoints;
-  k->ntri = pt->built.store[object].ntri;
-  k->inv.resize(16 * (size_t)njoints);
-  k->mats.resize(16 * (size_t)njoints);
-  int st = SRT_OK;
-  if (pt->idx_off[object] == SIZE_MAX) {                  // an emissive mesh under srt_pt_set_dynamic_lights: its index buffer goes up now
-    if (hipSetDevice(pt->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: synchronisation failed");
-    else st = ensure_mesh_idx(pt, object);
-    if (st == SRT_OK) { pt->bytes_uploaded += pt->idx_uncounted; pt->idx_uncounted = 0; }
-  }
-  if (st == SRT_OK) st = skin_build(k, bind_positions, bind_normals, joints);
-  if (st != SRT_OK) { skin_free(k); return st; }
-  *skin = k;
-  return SRT_OK;
-}
-
-int srt_pt_skin_destroy(srt_pt_skin* skin) {
-  if (!skin) return SRT_OK;
-  if (skin->pt->device >= 0) { (void)hipSetDevice(skin->pt->device); (void)hipDeviceSynchronize(); }
-  skin_free(skin);
-  return SRT_OK;
-}
-
-int srt_pt_skin_counts(srt_pt_skin* skin, uint32_t out[4]) {
-  if (!skin || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_counts: NULL argument");
-  out[0] = skin->nverts; out[1] = skin->njoints; out[2] = skin->ninf; out[3] = skin->ntri;
-  return SRT_OK;
-}
-
-int srt_pt_skin_map(srt_pt_skin* skin, uint32_t* offsets, uint32_t* joints, float* weights, uint32_t cap) {
-  if (!skin || !offsets || !joints || !weights) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_map: NULL argument");
-  int st = skin_usable(skin, "srt_pt_skin_map");
-  if (st != SRT_OK) return st;
-  if (cap < skin->ninf) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_map: the map has %u influences, the arrays hold %u", skin->ninf, cap);
-  SRT_HIP(hipSetDevice(skin->pt->device));
-  SRT_HIP(hipMemcpy(offsets, skin->d_off, ((size_t)skin->nverts + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (skin->ninf) {
-    SRT_HIP(hipMemcpy(joints, skin->d_jidx, (size_t)skin->ninf * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SRT_HIP(hipMemcpy(weights, skin->d_w, (size_t)skin->ninf * sizeof(float), hipMemcpyDeviceToHost));
-  }
-  return SRT_OK;
-}
-
-int srt_pt_skin_vertices_device(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals, float* d_positions_out, float* d_normals_out) {
-  if (!skin || !posed || !d_positions_out || !d_normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices_device: NULL argument");
-  const int st = skin_usable(skin, "srt_pt_skin_vertices_device");
-  if (st != SRT_OK) return st;
-  return skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, d_positions_out, d_normals_out);
-}
-
-int srt_pt_skin_vertices(srt_pt_skin* skin, const float* posed, int flat_normals, float* positions_out, float* normals_out) {
-  if (!skin || !posed || !positions_out || !normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices: NULL argument");
-  int st = skin_usable(skin, "srt_pt_skin_vertices");
-  if (st != SRT_OK) return st;
-  hipStream_t s = skin->pt->stream;
-  if ((st = skin_enqueue(skin, s, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
-  const size_t bytes = 3 * (size_t)skin->nverts * sizeof(float);
-  SRT_HIP(hipMemcpyAsync(positions_out, skin->d_pos_out, bytes, hipMemcpyDeviceToHost, s));
-  SRT_HIP(hipMemcpyAsync(normals_out, skin->d_nrm_out, bytes, hipMemcpyDeviceToHost, s));
-  SRT_HIP(hipStreamSynchronize(s));
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
-  if (!skin || !posed) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_pose: NULL argument");
-  int st = skin_usable(skin, "srt_pt_skin_pose");
-  if (st != SRT_OK) return st;
-  // (the staging is read by nothing of the context: writing it before srt_pt_update_mesh_device's verdict changes no scene)
-  if ((st = skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
-  return update_mesh(skin->pt, "srt_pt_skin_pose", (hipStream_t)stream, skin->object, nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
-}
-
-int srt_pt_skin_pose_refit(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
-  if (!skin || !posed) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_pose_refit: NULL argument");
-  int st = skin_usable(skin, "srt_pt_skin_pose_refit");
-  if (st != SRT_OK) return st;
-  // (the staging is read by nothing of the context: writing it before srt_pt_refit_mesh_device's verdict changes no scene)
-  if ((st = skin_enqueue(skin, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out))) return st;
-  return refit_mesh(skin->pt, "srt_pt_skin_pose_refit", (hipStream_t)stream, skin->object, nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
-  if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_repose before srt_pt_scene_commit");
-  const char* be = getenv("SRT_BVH_BUILDER");               // the BVH<Object> build goes where srt_pt_scene_commit's does
-  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  if (pt->device >= 0 && bmode != 0) { SRT_HIP(hipSetDevice(pt->device)); set_device_bvh_builder(build_bvh_device, pt->bvh_device_min); }
-  else set_device_bvh_builder(nullptr, 0);
-  ReposedTop top;
-  bool bad_argument = false;
-  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
-  std::vector<Mat4> T(n);
-  if (n) std::memcpy(T.data(), trans, (size_t)n * sizeof(Mat4));
-  const std::string err = prepare_repose(pt->built, objects, T.data(), n, &top, &bad_argument);
-  set_device_bvh_builder(nullptr, 0);
-  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "srt_pt_repose: %s", err.c_str());
-  if ((int)top.max_tlas_depth > kMaxTlasDepth)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)",
-                     top.max_tlas_depth, kMaxTlasDepth, pt->built.flat.max_blas_depth, kMaxBlasDepth);
-  // from here on nothing fails on the host side: the new tables replace the old ones
-  const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
-  if (pt->device >= 0) {
-    SRT_HIP(hipSetDevice(pt->device));
-    SRT_HIP(hipStreamSynchronize(pt->stream));
-    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old tables
-  }
-  apply_repose(&pt->built, &top);
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
-  if (pt->device >= 0) {
-    drop_pose_tables(pt);                                 // srt_pt_repose_device's tables mirror the poses that were just replaced
-    drop_top_tables(pt);                                  // srt_pt_repose_refit_device's describe the tree that was just replaced
-    const FlatScene& F = pt->built.flat;
-    int st;
-    if (F.tlas_nodes == old_tlas_nodes) {                 // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
-      if (F.tlas_nodes) SRT_HIP(hipMemcpy(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice));
-      pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
-    } else if ((st = upload(pt, &pt->d_nodes, F.nodes))) {
-      return st;
-    }
-    if ((st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)))
-      return st;
-    for (uint32_t k = 0; k < n; k++) {                    // listed area lights (srt_pt_set_dynamic_lights): their records, as the host mirror has them now
-      const int32_t li = light_of(pt->built, objects[k]);
-      if (li >= 0 && (st = upload_light(pt, (uint32_t)li, false))) { pt->committed = false; return st; }
-    }
-  }
-  return SRT_OK;
-}
-
-int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
-  const char* what = "srt_pt_repose_device";
-  if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
-  const std::string refused = check_repose_list(pt->built, objects, n);
-  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
-  if (pt->device < 0)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose takes host matrices)", what);
-  SRT_HIP(hipSetDevice(pt->device));
-  forget_top_list(pt);                                    // d_pose_list and d_light_list are about to hold this call's lists
-  hipStream_t s = (hipStream_t)stream;
-  const bool use_bvh = pt->built.flat.use_bvh;
-  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
-  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
-  int st;
-  uint64_t staged_bytes = 0;                              // (counted with the verdict: a refused repose adds nothing to the figures)
-  // The tables the kernels work in, at the first device repose after a commit: the records by insertion index come from the live
-  // records (a kernel; nothing goes up), the posed boxes from them and the object-space boxes (24 B per object up).
-  if (!pt->pose_tables) {
-    drop_pose_tables(pt);
-    if (hipMalloc(&pt->d_pose_records, (size_t)nobj * sizeof(Object)) != hipSuccess || hipMalloc(&pt->d_local_boxes, (size_t)nobj * 6 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&pt->d_posed_boxes, (size_t)nobj * 6 * sizeof(float)) != hipSuccess) {
-      (void)hipGetLastError();
-      drop_pose_tables(pt);
-      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
-    }
-    // (blocking copy, then kernels on `s` that read what the last commit or repose left in d_objects: all of it done by now)
-    SRT_HIP(hipMemcpy(pt->d_local_boxes, pt->built.local_boxes.data(), (size_t)nobj * 6 * sizeof(float), hipMemcpyHostToDevice));
-    staged_bytes += (uint64_t)nobj * 6 * sizeof(float);
-    launch_pose_tables(s, pt->d_objects, nobj, pt->built.flat.tlas_nodes, pt->d_pose_records, pt->d_local_boxes, pt->d_posed_boxes);
-    pt->pose_tables = true;
-  }
-  // From here to the verdict only these tables and the staging are written; a refusal drops the tables (the next call makes them
-  // again from the committed records, which are not touched).
-  auto refuse = [&](int status) { drop_pose_tables(pt); return status; };
-  std::vector<PoseOut> posed(n);
-  std::vector<float> boxes;
-  if (n) {
-    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n))) return refuse(st);
-    if (hipMemcpyAsync(pt->d_pose_list, objects, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
-    staged_bytes += (uint64_t)n * 4;
-    launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
-    if (hipMemcpyAsync(posed.data(), pt->d_pose_out, (size_t)n * sizeof(PoseOut), hipMemcpyDeviceToHost, s) != hipSuccess)
-      return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
-  }
-  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: the pose kernel failed", what));
-  // The BVH<Object> build goes where srt_pt_repose's does: on the device, over the boxes where they are, for a scene at or above
-  // the device builder's threshold; anything else - and a device build that failed: the host build gives the verdict - on the host,
-  // over the boxes read back (24 B per object).
-  const char* be = getenv("SRT_BVH_BUILDER");
-  const int bmode = be ? (strcmp(be, "host") == 0 ? 0 : 1) : pt->bvh_builder;
-  HostBVH device_tree;
-  bool device_built = false;
-  if (use_bvh && bmode != 0 && nobj >= pt->bvh_device_min && nobj > 1u && bvh_workspace_reserve(&pt->bvh_ws, nobj, false)) {
-    BvhWorkspace view = pt->bvh_ws;                       // the context's workspace with the posed boxes in the place of its own
-    view.d_boxes = pt->d_posed_boxes;
-    device_built = build_bvh_device_core(&view, s, nobj, 1, &device_tree);
-  }
-  if (use_bvh && !device_built) {
-    boxes.resize((size_t)nobj * 6);
-    if (hipMemcpyAsync(boxes.data(), pt->d_posed_boxes, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
-  }
-  std::vector<Mat4> trans(n), itrans(n);
-  std::vector<uint32_t> has_trans(n);
-  for (uint32_t k = 0; k < n; k++) {
-    std::memcpy(&trans[k], posed[k].trans, sizeof(Mat4));
-    std::memcpy(&itrans[k], posed[k].itrans, sizeof(Mat4));
-    has_trans[k] = posed[k].has_trans;
-    // (with a device-built tree the posed box has served already; the host's record holds it in the tree's leaves)
-  }
-  SuppliedPoses P;
-  P.trans = trans.data(); P.itrans = itrans.data(); P.has_trans = has_trans.data();
-  P.boxes6 = boxes.empty() ? nullptr : boxes.data();
-  P.prebuilt = device_built ? &device_tree : nullptr;
-  set_device_bvh_builder(nullptr, 0);
-  ReposedTop top;
-  bool bad_argument = false;
-  const std::string err = prepare_repose_supplied(pt->built, objects, n, P, &top, &bad_argument);
-  if (!err.empty()) return refuse(srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str()));
-  if ((int)top.max_tlas_depth > kMaxTlasDepth)
-    return refuse(srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)", top.max_tlas_depth, kMaxTlasDepth,
-                            pt->built.flat.max_blas_depth, kMaxBlasDepth));
-  // the primitive order and the mesh ordinals per slot, still aside: a host build's order goes up (4 B per slot), a device build's
-  // is where the record kernel reads it; the ordinals (bits 8 and up of use_bvh) are the host's
-  const uint32_t* d_prim = nullptr;
-  const uint32_t* d_ordinal = nullptr;
-  std::vector<uint32_t> ordinal;
-  if (use_bvh) {
-    if (!device_built) {
-      if (!bvh_workspace_reserve(&pt->bvh_ws, nobj, true)) return refuse(srt::fail(SRT_ERR_HIP, "%s: out of device memory", what));
-      if (hipMemcpyAsync(pt->bvh_ws.d_prim, top.tlas.prim.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
-      staged_bytes += (uint64_t)nobj * 4;
-    }
-    d_prim = pt->bvh_ws.d_prim;
-    if (!top.lazy_objects.empty()) {
-      ordinal.assign(nobj, 0u);
-      for (size_t q = 0; q < top.lazy_objects.size(); q++) ordinal[top.lazy_objects[q]] = (uint32_t)q << 8;
-      if ((st = ensure(&pt->d_slot_ordinal, &pt->slot_ordinal_n, (size_t)nobj))) return refuse(st);
-      if (hipMemcpyAsync(pt->d_slot_ordinal, ordinal.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-        return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
-      staged_bytes += (uint64_t)nobj * 4;
-      d_ordinal = pt->d_slot_ordinal;
-    }
-  }
-  // the listed area lights (srt_pt_set_dynamic_lights), still aside: {position in the list, light} pairs for the light kernels
-  std::vector<uint32_t> light_list;
-  uint32_t light_max_ntri = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    const int32_t li = light_of(pt->built, objects[k]);
-    if (li < 0) continue;
-    light_list.push_back(k);
-    light_list.push_back((uint32_t)li);
-    light_max_ntri = std::max(light_max_ntri, pt->built.flat.lights[(size_t)li].ntri);
-  }
-  if (!light_list.empty()) {
-    if ((st = ensure(&pt->d_light_list, &pt->light_list_n, light_list.size()))) return refuse(st);
-    if (hipMemcpyAsync(pt->d_light_list, light_list.data(), light_list.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess)
-      return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what));
-    staged_bytes += (uint64_t)light_list.size() * 4;
-  }
-  // the verdict is in; nothing of the context may be in flight while the live arrays change
-  const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
-  if (hipStreamSynchronize(s) != hipSuccess || hipStreamSynchronize(pt->stream) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return refuse(srt::fail(SRT_ERR_HIP, "%s: synchronisation failed", what));
-  apply_repose(&pt->built, &top);
-  drop_top_tables(pt);                                    // srt_pt_repose_refit_device's describe the tree that was just replaced
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
-  pt->bytes_uploaded += staged_bytes;
-  // A HIP failure from here on leaves the device arrays behind the host's: the scene is no longer committed and has to be committed again.
-  const FlatScene& F = pt->built.flat;
-  auto write = [&]() -> int {
-    int w;
-    if (F.tlas_nodes == old_tlas_nodes) {                 // the BVH<Triangle> nodes behind the BVH<Object>'s have not moved
-      if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
-      pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
-    } else if ((w = upload(pt, &pt->d_nodes, F.nodes))) {
-      return w;
-    }
-    // the records in place (the object count never changes): gathered on the device by the new order
-    launch_pose_records(s, pt->d_pose_records, d_prim, d_ordinal, nobj, F.tlas_nodes, pt->d_objects);
-    if (!light_list.empty()) {
-      // the listed lights' records from the pose kernel's output where it lies, then their area terms under the new pdfT: no upload
-      const uint32_t nl = (uint32_t)(light_list.size() / 2);
-      launch_light_records(s, pt->d_light_list, nl, pt->d_pose_out, n, pt->d_lights, (uint32_t)F.lights.size());
-      launch_light_area_terms(s, pt->d_light_list, nl, light_max_ntri, pt->d_lights, (uint32_t)F.lights.size(), F.light_tri_first, pt->d_ltris,
-                              (uint32_t)F.light_tris.size());
-    }
-    SRT_HIP(hipStreamSynchronize(s));
-    SRT_HIP(hipGetLastError());
-    if ((w = upload(pt, &pt->d_wave, F.wave_tlas)) || (w = upload(pt, &pt->d_wave_lazy, F.wave_lazy))) return w;
-    return SRT_OK;
-  };
-  st = write();
-  if (st != SRT_OK) { pt->committed = false; drop_pose_tables(pt); }
-  return st;
-}
-
-}  // extern "C"
-
-namespace {
-
-// A pinned staging buffer of at least `words` words whose last copy has left it (or a new one).
-int pinned_list(srt_pt* pt, size_t words, srt_pt::PinnedList** out) {
-  for (auto& pl : pt->pinned) {
-    if (pl.words < words) continue;
-    const hipError_t left = hipEventQuery(pl.done);
-    (void)hipGetLastError();                              // (hipErrorNotReady of a query is no error: not left behind for the launch check)
-    if (left == hipSuccess) { *out = &pl; return SRT_OK; }
-  }
-  srt_pt::PinnedList pl;
-  pl.words = std::max<size_t>(words, 1024);
-  if (hipHostMalloc((void**)&pl.h, pl.words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return srt::fail(SRT_ERR_HIP, "out of pinned host memory");
-  if (hipEventCreateWithFlags(&pl.done, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(pl.h); return srt::fail(SRT_ERR_HIP, "event creation failed"); }
-  pt->pinned.push_back(pl);
-  *out = &pt->pinned.back();
-  return SRT_OK;
-}
-
-// srt_pt_repose_refit's device side after apply_top_refit: the arrays that changed, from the host's record.
-int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n) {
-  const FlatScene& F = pt->built.flat;
-  if (F.use_bvh) {
-    if (F.tlas_nodes) SRT_HIP(hipMemcpy(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice));
-    if (!F.wave_tlas.empty()) SRT_HIP(hipMemcpy(pt->d_wave, F.wave_tlas.data(), F.wave_tlas.size() * sizeof(WaveInterior), hipMemcpyHostToDevice));
-    pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node) + F.wave_tlas.size() * sizeof(WaveInterior);
-  }
-  // the listed records, one copy per run of neighbouring slots (a pool that moves as a whole is a handful of runs)
-  std::vector<uint32_t> slot_of(pt->built.tlas.prim.size()), slots(n);
-  for (size_t k = 0; k < slot_of.size(); k++) slot_of[pt->built.tlas.prim[k]] = (uint32_t)k;
-  for (uint32_t k = 0; k < n; k++) slots[k] = slot_of[objects[k]];
-  std::sort(slots.begin(), slots.end());
-  for (uint32_t k = 0; k < n;) {
-    uint32_t e = k + 1;
-    while (e < n && slots[e] == slots[e - 1] + 1u) e++;
-    SRT_HIP(hipMemcpy(pt->d_objects + slots[k], &F.objects[slots[k]], (size_t)(e - k) * sizeof(Object), hipMemcpyHostToDevice));
-    pt->bytes_uploaded += (uint64_t)(e - k) * sizeof(Object);
-    k = e;
-  }
-  for (uint32_t k = 0; k < n; k++) {
-    const int32_t li = pt->built.inputs[objects[k]].is_light ? light_of(pt->built, objects[k]) : -1;
-    int st;
-    if (li >= 0 && (st = upload_light(pt, (uint32_t)li, false))) return st;
-  }
-  return SRT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int srt_pt_repose_refit(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
-  if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose_refit: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_repose_refit before srt_pt_scene_commit");
-  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
-  std::vector<Mat4> T(n);
-  if (n) std::memcpy(T.data(), trans, (size_t)n * sizeof(Mat4));
-  TopRefit R;
-  const std::string err = prepare_top_refit(pt->built, objects, T.data(), n, &R);
-  if (!err.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose_refit: %s", err.c_str());
-  // nothing fails on the host side from here on: the new boxes and records replace the old ones in place
-  if (pt->device >= 0) {
-    SRT_HIP(hipSetDevice(pt->device));
-    SRT_HIP(hipStreamSynchronize(pt->stream));
-    SRT_HIP(hipDeviceSynchronize());                      // epochs the caller enqueued on streams of its own read the old boxes
-  }
-  apply_top_refit(&pt->built, &R);
-  pt->top_refits++;
-  if (pt->device >= 0) {
-    drop_pose_tables(pt);                                 // they mirror the poses that were just replaced (the tree's tables stay: the tree did)
-    const int st = write_top_refit(pt, objects, n);
-    if (st != SRT_OK) { pt->committed = false; return st; }
-  }
-  return SRT_OK;
-}
-
-int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
-  const char* what = "srt_pt_repose_refit_device";
-  if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what);
-  const std::string refused = check_repose_list(pt->built, objects, n);
-  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
-  if (pt->device < 0)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose_refit takes host matrices)", what);
-  SRT_HIP(hipSetDevice(pt->device));
-  hipStream_t s = (hipStream_t)stream;
-  const FlatScene& F = pt->built.flat;
-  const bool use_bvh = F.use_bvh;
-  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
-  int st;
-  // First call after a commit or after a call that replaced the BVH<Object> (blocking, counted once): the pose tables as
-  // srt_pt_repose_device makes them (24 B per object up), the tree's refit tables (about 28 B per object up) and the slot of
-  // every object (a kernel).  Nothing is pending then - every call that drops these tables settles first.
-  if (!pt->pose_tables) {
-    drop_pose_tables(pt);
-    if (hipMalloc(&pt->d_pose_records, (size_t)(nobj ? nobj : 1) * sizeof(Object)) != hipSuccess ||
-        hipMalloc(&pt->d_local_boxes, (size_t)(nobj ? nobj : 1) * 6 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&pt->d_posed_boxes, (size_t)(nobj ? nobj : 1) * 6 * sizeof(float)) != hipSuccess) {
-      (void)hipGetLastError();
-      drop_pose_tables(pt);
-      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
-    }
-    if (nobj) SRT_HIP(hipMemcpy(pt->d_local_boxes, pt->built.local_boxes.data(), (size_t)nobj * 6 * sizeof(float), hipMemcpyHostToDevice));
-    pt->bytes_uploaded += (uint64_t)nobj * 6 * sizeof(float);
-    launch_pose_tables(s, pt->d_objects, nobj, F.tlas_nodes, pt->d_pose_records, pt->d_local_boxes, pt->d_posed_boxes);
-    pt->pose_tables = true;
-  }
-  if (use_bvh && !pt->have_top_tables) {
-    drop_top_tables(pt);
-    RefitTables fresh;
-    if ((st = make_refit_tables(pt->built.tlas, what, UINT32_MAX, &fresh)) != SRT_OK) return st;
-    pt->top_tables = fresh;
-    pt->have_top_tables = true;
-    pt->bytes_uploaded += fresh.uncounted_bytes;
-    pt->top_tables.uncounted_bytes = 0;
-    if (hipMalloc(&pt->d_slot_of, (size_t)(nobj ? nobj : 1) * sizeof(uint32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      drop_top_tables(pt);
-      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
-    }
-    launch_top_slots(s, pt->top_tables.d_prim, nobj, pt->d_slot_of);
-  }
-  // A HIP failure from here on may leave tables, lists or live arrays half written: the scene is no longer committed, what was
-  // pending is forgotten (settle() has no record to bring up to date) and the tables go; the scene has to be committed again.
-  auto broken = [&](int status) {
-    pt->committed = false;
-    if (hipSetDevice(pt->device) == hipSuccess) (void)hipDeviceSynchronize();
-    (void)hipGetLastError();
-    pt->top_pending = 0;
-    for (uint32_t i : pt->top_pending_objects) pt->top_pending_flag[i] = 0;
-    pt->top_pending_objects.clear();
-    drop_pose_tables(pt);
-    drop_top_tables(pt);
-    return status;
-  };
-  auto hip_broken = [&](hipError_t e, const char* step) { return broken(srt::fail(SRT_ERR_HIP, "%s: %s failed (%s); the scene has to be committed again", what, step, hipGetErrorString(e))); };
-  hipError_t he;
-  // The list (4 B per listed object, 8 B more per listed light), through pinned memory so that the copy is only enqueued - unless
-  // the device holds this very list already.
-  if (n && !(pt->top_list_valid && pt->top_list.size() == n && std::memcmp(pt->top_list.data(), objects, (size_t)n * 4) == 0)) {
-    std::vector<uint32_t> light_list;
-    uint32_t light_max_ntri = 0;
-    for (uint32_t k = 0; k < n; k++) {
-      const int32_t li = pt->built.inputs[objects[k]].is_light ? light_of(pt->built, objects[k]) : -1;   // (light_of counts the lights in front)
-      if (li < 0) continue;
-      light_list.push_back(k);
-      light_list.push_back((uint32_t)li);
-      light_max_ntri = std::max(light_max_ntri, F.lights[(size_t)li].ntri);
-    }
-    forget_top_list(pt);
-    // (growing one of these arrays frees the old one, which waits for what reads it: first calls and longer lists only)
-    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n)) ||
-        (!light_list.empty() && (st = ensure(&pt->d_light_list, &pt->light_list_n, light_list.size()))))
-      return broken(st);
-    srt_pt::PinnedList* pl = nullptr;
-    if ((st = pinned_list(pt, (size_t)n + light_list.size(), &pl)) != SRT_OK) return broken(st);
-    std::memcpy(pl->h, objects, (size_t)n * 4);
-    if (!light_list.empty()) std::memcpy(pl->h + n, light_list.data(), light_list.size() * 4);
-    if ((he = hipMemcpyAsync(pt->d_pose_list, pl->h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_broken(he, "the copy of the list");
-    if (!light_list.empty() && (he = hipMemcpyAsync(pt->d_light_list, pl->h + n, light_list.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-      return hip_broken(he, "the copy of the light list");
-    if ((he = hipEventRecord(pl->done, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
-    pt->bytes_uploaded += (uint64_t)n * 4 + light_list.size() * 4;
-    pt->top_list.assign(objects, objects + n);
-    pt->top_lights = (uint32_t)(light_list.size() / 2);
-    pt->top_light_max_ntri = light_max_ntri;
-    pt->top_list_valid = true;
-  }
-  if (!pt->top_event && (he = hipEventCreateWithFlags(&pt->top_event, hipEventDisableTiming)) != hipSuccess) return hip_broken(he, "hipEventCreate");
-  // Everything below only enqueues on `s`: the poses, the leaves through the tree's primitive order, the levels deepest first, the
-  // boxes into the live nodes and sweep records, the listed records' matrices, the listed lights.  No verdict is needed: depth,
-  // counts, order, kernel form and stack sizes are those of the committed tree.
-  if (n) launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
-  if (use_bvh) {
-    pt->top_tables.d_tri_boxes = pt->d_posed_boxes;       // the tree's primitives are the objects: their boxes are the pose tables' (not owned)
-    launch_refit_boxes(s, pt->top_tables, pt->top_tables.d_node_boxes);
-    launch_refit_write(s, pt->top_tables, pt->top_tables.d_node_boxes, pt->d_nodes, pt->d_wave);
-  }
-  if (n) {
-    launch_top_objects(s, pt->d_pose_list, n, nobj, use_bvh ? pt->d_slot_of : nullptr, pt->d_pose_records, pt->d_objects);
-    if (pt->top_lights) {
-      launch_light_records(s, pt->d_light_list, pt->top_lights, pt->d_pose_out, n, pt->d_lights, (uint32_t)F.lights.size());
-      launch_light_area_terms(s, pt->d_light_list, pt->top_lights, pt->top_light_max_ntri, pt->d_lights, (uint32_t)F.lights.size(), F.light_tri_first, pt->d_ltris,
-                              (uint32_t)F.light_tris.size());
-    }
-  }
-  if ((he = hipGetLastError()) != hipSuccess) return hip_broken(he, "a launch");
-  if ((he = hipEventRecord(pt->top_event, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
-  // the host's record is behind from here until settle(): one more call, and the objects it listed that no pending call had listed
-  pt->top_pending++;
-  if (pt->top_pending_flag.size() != nobj) pt->top_pending_flag.assign(nobj, 0);   // (nothing is pending across a commit)
-  for (uint32_t k = 0; k < n; k++)
-    if (!pt->top_pending_flag[objects[k]]) { pt->top_pending_flag[objects[k]] = 1; pt->top_pending_objects.push_back(objects[k]); }
-  return SRT_OK;
-}
-
-int srt_pt_scene_tree_cost(srt_pt* pt, double* cost) {
-  if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_tree_cost: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_scene_tree_cost before srt_pt_scene_commit");
-  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_scene_tree_cost: the scene was committed without BVHs, it has no tree");
-  *cost = tree_cost(pt->built.tlas);
-  return SRT_OK;
-}
-
-int srt_pt_top_refit_pending(srt_pt* pt, uint64_t out[2]) {
-  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_top_refit_pending: NULL argument");
-  out[0] = pt->top_pending;
-  out[1] = pt->top_pending_objects.size();
-  return SRT_OK;
-}
-
-int srt_pt_top_refit_count(srt_pt* pt, uint64_t* refits) {
-  if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_top_refit_count: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  *refits = pt->top_refits;
-  return SRT_OK;
-}
-
-int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {
-  int st = need_device(pt, "srt_pt_particle_transforms_device");
-  if (st != SRT_OK) return st;
-  if (n == 0) return SRT_OK;
-  if (!d_pos || !d_trans_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_particle_transforms_device: NULL argument");
-  launch_particle_transforms(stream, d_pos, n, scale, d_trans_out);
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]) {
-  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_counts: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  const FlatScene& F = pt->built.flat;
-  const bool have = pt->committed;
-  out[0] = have ? F.objects.size() : 0;
-  out[1] = have ? F.tris.size() : 0;
-  out[2] = have ? F.nodes.size() - F.tlas_nodes : 0;
-  out[3] = have ? F.blas_recs.size() : 0;
-  out[4] = pt->blas_builds;
-  out[5] = 0;
-  if (have && pt->device >= 0)
-    out[5] = F.nodes.size() * sizeof(Node) + F.tris.size() * sizeof(Tri) + F.tri_nrm.size() * sizeof(TriNrm) + F.tri_packed.size() * sizeof(float) +
-             F.objects.size() * sizeof(Object) + F.lights.size() * sizeof(Light) + F.light_tris.size() * sizeof(LightTri) +
-             F.materials.size() * sizeof(Material) + F.wave_tlas.size() * sizeof(WaveInterior) + F.blas_recs.size() * sizeof(WaveInterior) +
-             F.wave_lazy.size() * sizeof(uint32_t) + F.delta_lights.size() * sizeof(DeltaLight) + pt->env_map.size() * sizeof(float) +
-             pt->idx_words * sizeof(uint32_t);
-  out[6] = pt->bytes_uploaded;
-  out[7] = pt->tri_bytes_uploaded;
   return SRT_OK;
 }
 
@@ -2807,7 +1499,7 @@ int srt_pt_stream_counters(srt_pt* pt, uint64_t out[4], int reset) {
 
 int srt_pt_kernel_form(srt_pt* pt, int* form) {
   if (!pt || !form) return srt::fail(SRT_ERR_INVALID, "srt_pt_kernel_form: NULL argument");
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_kernel_form before srt_pt_scene_commit");
+  if (!pt->committed) return not_committed("srt_pt_kernel_form");
   const int t = wave_trav(pt);
   *form = pt->normal_colors ? -3 : (t >= 0 ? t : (pt->kernel_mode == 1 ? -2 : -1));
   return SRT_OK;
@@ -2893,8 +1585,7 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
 int srt_pt_hit(srt_pt* pt, const float* origins, const float* dirs, const float* bounds, size_t n, float* out9) {
   int st = need_device(pt, "srt_pt_hit");
   if (st != SRT_OK) return st;
-  if ((st = settle(pt)) != SRT_OK) return st;
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_hit before srt_pt_scene_commit");
+  if ((st = need_committed(pt, "srt_pt_hit")) != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!origins || !dirs || !bounds || !out9) return srt::fail(SRT_ERR_INVALID, "srt_pt_hit: NULL argument");
   float *dorg = nullptr, *ddir = nullptr, *db = nullptr, *dout = nullptr;
@@ -2920,7 +1611,7 @@ int srt_pt_particles_step_device(srt_pt* pt, void* stream, float* d_pos, float* 
                                  uint8_t* d_alive) {
   int st = need_device(pt, "srt_pt_particles_step_device");
   if (st != SRT_OK) return st;
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_particles_step before srt_pt_scene_commit");
+  if (!pt->committed) return not_committed("srt_pt_particles_step");
   if (n == 0) return SRT_OK;
   if (!d_pos || !d_vel || !d_age || !d_alive) return srt::fail(SRT_ERR_INVALID, "srt_pt_particles_step: NULL argument");
   if (n > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "too many particles in one call");
@@ -2955,8 +1646,7 @@ int srt_pt_particles_step(srt_pt* pt, float* pos, float* vel, float* age, size_t
 
 long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_t cap, uint32_t* order) {
   if (!pt || !boxes || !links) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_bvh: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_bvh before srt_pt_scene_commit");
+  { const int ready = need_committed(pt, "srt_pt_dump_bvh"); if (ready != SRT_OK) return ready; }
   if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_STATE, "scene was committed without BVHs");
   const HostBVH* b = &pt->built.tlas;
   const ObjectInput* in = nullptr;
@@ -2980,8 +1670,7 @@ long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_
 
 long srt_pt_dump_lights(srt_pt* pt, int from_device, uint32_t* heads, float* mats, size_t cap_lights, float* tris, size_t cap_tris) {
   if (!pt || (cap_lights && (!heads || !mats)) || (cap_tris && !tris)) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_lights: NULL argument");
-  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
-  if (!pt->committed) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_lights before srt_pt_scene_commit");
+  { const int ready = need_committed(pt, "srt_pt_dump_lights"); if (ready != SRT_OK) return ready; }
   if (from_device && pt->device < 0)
     return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_dump_lights: this context is host-only, there are no device arrays to read (from_device = 0 reads the host's)");
   const FlatScene& F = pt->built.flat;

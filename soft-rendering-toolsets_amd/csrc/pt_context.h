@@ -1,0 +1,198 @@
+// The path tracer's context (struct srt_pt) and the helpers its two translation units share: pt.hip (kernels, render paths, create /
+// begin / add / commit / destroy) and pt_update.cpp (host code only: what changes or queries a committed scene).  No header that
+// defines a non-template __global__ may be included here (pt_stream.h and pt_wave.h do): both units would define its kernels.
+#ifndef SRT_PT_CONTEXT_H
+#define SRT_PT_CONTEXT_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <map>
+#include <utility>
+#include <vector>
+
+#include "pt_bvh_device.h"
+#include "pt_pose.h"
+#include "pt_scene.h"
+#include "srt_common.h"
+#include "srt_pt.h"
+
+namespace srt {
+struct StreamCounters;   // pt_stream.h
+}
+
+struct srt_pt {
+  int device = -1;            // -1: host-only context (scene assembly / BVH inspection, no rendering)
+  hipStream_t stream = nullptr;
+  std::vector<srt::ObjectInput> inputs;
+  std::vector<srt::Material> materials;
+  srt::BuiltScene built;
+  bool committed = false;
+  srt::Camera cam{};
+  bool have_cam = false;
+  uint32_t w = 0, h = 0, max_depth = 8;
+  srt::TileMap tiles{32, 32, 0, 0, 0, 1, 0};
+  uint32_t tiles_per_rank = 0;
+  // device copies
+  srt::Node* d_nodes = nullptr; srt::Tri* d_tris = nullptr; srt::TriNrm* d_nrm = nullptr; srt::Object* d_objects = nullptr;
+  float* d_tri_packed = nullptr;                                 // the triangle records without padding (pt_scene.h): what the cast kernel reads
+  srt::Light* d_lights = nullptr; srt::LightTri* d_ltris = nullptr; srt::Material* d_mats = nullptr;
+  srt::WaveInterior* d_wave = nullptr; srt::WaveInterior* d_blas = nullptr; uint32_t* d_wave_lazy = nullptr;
+  srt::DeltaLight* d_dlights = nullptr;
+  std::vector<srt::DeltaLight> delta_lights;   // srt_pt_add_light, in call order
+  uint32_t env_type = 0; float env_radiance[3] = {0, 0, 0};   // srt_pt_set_env_light
+  std::vector<float> env_map; uint32_t env_w = 0, env_h = 0; float* d_env_map = nullptr;   // srt_pt_set_env_map
+  float* d_tile_buf = nullptr; size_t tile_buf_floats = 0;
+  float* d_image = nullptr; size_t image_floats = 0;
+  int kernel_mode = 0;        // srt_pt_set_kernel: 0 auto, 1 per-lane (lane per pixel), 2 wave-uniform, 3 wave-uniform with section stamps, 4 per-lane (lane per
+                              // sample), 5 flattened per-lane walk, 6 streamed (logic + ray-cast kernels), 7 streamed sweeps; wave_trav() picks the form
+  // Scratch of one epoch in flight.  One set per stream the caller renders on: epochs launched on different streams
+  // may overlap on the device (the next epoch's blocks fill the CUs the previous launch's tail leaves idle).
+  struct EpochBuffers {
+    float* d_samples = nullptr; size_t samples_floats = 0;   // per-sample radiance
+    float* d_records = nullptr; size_t records_floats = 0;   // wave kernel: per-bounce records
+    float* d_running = nullptr; size_t running_floats = 0;   // (sum, count) across the launches of one epoch
+    unsigned long long* d_queue = nullptr;                   // wave kernel: queue head (+ section stamps)
+    // streamed form (pt_stream.h): saved path state, ray queue, hits, counters
+    uint32_t* d_state = nullptr; size_t state_words = 0;
+    float4* d_ray_o = nullptr; size_t ray_o_n = 0;
+    float4* d_ray_d = nullptr; size_t ray_d_n = 0;
+    uint32_t* d_ray_id = nullptr; size_t ray_id_n = 0;
+    uint2* d_hits = nullptr; size_t hits_n = 0;
+    srt::StreamCounters* d_sc = nullptr;
+    unsigned long long* d_block_counters = nullptr; size_t block_counters_n = 0;
+    uint32_t* d_cast_spill = nullptr; size_t cast_spill_words = 0;   // the ray-cast kernel's traversal frames beyond those in LDS
+    uint32_t* d_cancel = nullptr;                                     // srt_pt_cancel as the kernels of this stream have seen it (sticky until srt_pt_clear_cancel)
+    uint32_t* d_ray_log = nullptr; uint32_t ray_log_cap = 0;          // srt_pt_set_ray_log: this stream's ring (pt_trace.h: log_ray_event)
+    uint32_t* d_alive_list = nullptr; size_t alive_list_n = 0;          // streamed forms: the alive slots the next generation works from
+    uint32_t last_samples = 0, last_npix = 0;                         // what d_samples holds: samples per pixel and pixel slots of the last launch
+  };
+  std::map<hipStream_t, EpochBuffers> epoch_buffers;
+  int wave_blocks = 0; size_t wave_lds = 0; int wave_mode = -1; const void* wave_kern = nullptr;
+  const void* cast_kern = nullptr; uint32_t cast_lds_frames = 0;                                 // traversal frames per lane kept in LDS (the deeper ones: d_cast_spill)
+  int cast_blocks = 0, cast_threads = 0; size_t cast_lds = 0; uint32_t cast_depth = 0;   // pt_cast_kernel's launch shape (0: not derived yet)
+  int bvh_builder = 1; uint32_t bvh_device_min = 16384;         // srt_pt_set_bvh_builder: device build for sets of >= this many primitives
+  uint32_t stream_slots = 0;                                    // srt_pt_set_stream_slots (0: default)
+  unsigned long long* d_cast_stats = nullptr;                   // SRT_CAST_STATS=1: the STATS build of pt_cast_kernel adds into these
+  unsigned long long* d_totals = nullptr;   // C_COUNT instrumented totals + 4 slots: rays of the epoch kernels, rays elided, streamed forms: entries queued, alive slot-generations
+  uint32_t* h_fault = nullptr;              // pinned, device-visible: bit 0 = a streamed launch ended with unfinished units (sticky until reported)
+  uint32_t* d_fault = nullptr;              // its device address
+  uint32_t* h_cancel = nullptr;             // pinned, device-visible: srt_pt_cancel's flag (any host thread may set it)
+  uint32_t* d_host_cancel = nullptr;        // its device address
+  uint32_t ray_log_cap = 0;                 // srt_pt_set_ray_log: rays per stream and read; 0: Pathtracer::log_ray is not delivered
+  int elide = 0;                            // srt_pt_set_elision
+  int normal_colors = 0;                    // srt_pt_set_normal_colors: read whenever a launch is enqueued
+  unsigned long long last_counters[srt::C_COUNT] = {0};
+  uint64_t camera_samples = 0;
+  // srt_pt_kernel_time: event pairs recorded around the dominant kernel's launches, on the launch stream
+  bool timing = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;   // pending (recorded, not yet read)
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> spare;
+  // srt_pt_stream_times: per-kernel event pairs of the streamed form {logic, compaction, ray cast}
+  bool stream_timing = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> stream_timed[4];   // {logic (resolve), compaction, ray cast, probe}
+  uint64_t stream_generations = 0;
+  // srt_pt_scene_counts: since creation
+  uint64_t blas_builds = 0, bytes_uploaded = 0, tri_bytes_uploaded = 0;
+  // srt_pt_update_mesh: the index buffers of the meshes that can be updated (no instance, no area light), resident from commit on, one
+  // after the other; the device builder's workspace; and the staging of the host form's vertex arrays.  Grown on demand, kept.
+  uint32_t* d_idx = nullptr; size_t idx_words = 0;
+  std::vector<size_t> idx_off;              // per object in insertion order: first word of its index buffer in d_idx (SIZE_MAX: none)
+  srt::BvhWorkspace bvh_ws;
+  float* d_vpos = nullptr; size_t vpos_floats = 0;
+  float* d_vnrm = nullptr; size_t vnrm_floats = 0;
+  // srt_pt_refit_mesh: per refitted mesh (insertion index) what its kernels keep on the device, from the first refit until the mesh
+  // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
+  std::map<uint32_t, srt::RefitTables> refit_tables;
+  uint64_t refits = 0;
+  // srt_pt_repose_device: what its kernels keep on the device between calls - every object's record by insertion index, its
+  // object-space box and its posed box - made at the first device repose after a commit (drop_pose_tables: a commit, a mesh update
+  // or refit and a host repose change what they mirror; so does a device repose that is refused).  The per-call arrays (the list,
+  // the read-back staging, the mesh ordinals per slot) are grown on demand and kept.
+  srt::Object* d_pose_records = nullptr; float* d_local_boxes = nullptr; float* d_posed_boxes = nullptr;
+  bool pose_tables = false;
+  uint32_t* d_pose_list = nullptr; size_t pose_list_n = 0;
+  srt::PoseOut* d_pose_out = nullptr; size_t pose_out_n = 0;
+  uint32_t* d_slot_ordinal = nullptr; size_t slot_ordinal_n = 0;
+  // srt_pt_set_dynamic_lights (the switch itself is built.dynamic_lights): srt_pt_repose_device's table of the listed lights
+  // ({position in the list, light} pairs), grown on demand and kept; and the bytes of index buffers that went up for a light's
+  // first update or refit (ensure_mesh_idx) and are counted with the verdict
+  uint32_t* d_light_list = nullptr; size_t light_list_n = 0;
+  uint64_t idx_uncounted = 0;
+  // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
+  uint64_t scene_generation = 0;
+  // srt_pt_repose_refit[_device]: the BVH<Object>'s refit tables (RefitTables of pt_bvh_device.h; d_tri_boxes stays NULL - the posed
+  // boxes of the pose tables stand in its place) and the slot of every object, made at the first device-form refit of a tree and
+  // dropped wherever the tree is replaced (drop_top_tables).  top_list: what d_pose_list (and d_light_list) hold when the last call
+  // that wrote them was a device-form refit - a call with the same list uploads nothing.  pinned: host staging of the lists, one
+  // buffer per list still on its way (its event tells), so that a call never waits for the one before.
+  srt::RefitTables top_tables; bool have_top_tables = false;
+  uint32_t* d_slot_of = nullptr;
+  std::vector<uint32_t> top_list; bool top_list_valid = false;
+  uint32_t top_lights = 0, top_light_max_ntri = 0;        // of top_list: listed lights, and the largest triangle count among them
+  struct PinnedList { uint32_t* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
+  std::vector<PinnedList> pinned;
+  // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of objects
+  // they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls are
+  // pending), and the event recorded behind the last of them.
+  uint64_t top_pending = 0;
+  std::vector<uint8_t> top_pending_flag;
+  std::vector<uint32_t> top_pending_objects;
+  hipEvent_t top_event = nullptr;
+  uint64_t top_refits = 0;                  // srt_pt_top_refit_count
+};
+
+namespace srt {
+
+// The one exit of scene data to the device.  tri_class: triangle, normal, packed-triangle or BLAS-record bytes - what an
+// instance shares and srt_pt_repose leaves alone (srt_pt_scene_counts tells them apart).
+template <typename T>
+inline int upload(srt_pt* pt, T** dst, const std::vector<T>& src, bool tri_class = false) {
+  if (*dst) { SRT_HIP(hipFree(*dst)); *dst = nullptr; }
+  const size_t n = src.empty() ? 1 : src.size();
+  SRT_HIP(hipMalloc(dst, n * sizeof(T)));
+  if (!src.empty()) SRT_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += src.size() * sizeof(T);
+  if (tri_class) pt->tri_bytes_uploaded += src.size() * sizeof(T);
+  return SRT_OK;
+}
+
+// A device array of at least `need` elements: grown (never shrunk) by freeing and allocating anew; what it held is gone then.
+template <typename T>
+inline int ensure(T** buf, size_t* have, size_t need) {
+  if (*have >= need && *buf) return SRT_OK;
+  if (*buf) { SRT_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
+  SRT_HIP(hipMalloc(buf, need * sizeof(T)));
+  *have = need;
+  return SRT_OK;
+}
+
+int need_device(srt_pt* pt, const char* what);            // (pt.hip; everything below: pt_update.cpp)
+// settle(): the host's record catches up with the device after srt_pt_repose_refit_device calls - every entry point that is not itself
+// enqueue-only calls it first (need_committed: and refuses, with not_committed's text, a scene that is not committed); discard_pending():
+// what is pending describes a scene that goes.
+int settle(srt_pt* pt);
+void discard_pending(srt_pt* pt);
+int not_committed(const char* what);
+int need_committed(srt_pt* pt, const char* what);
+// The device tables about the tree of mesh `object` (UINT32_MAX: of every mesh), the poses and the BVH<Object>: about to be replaced.
+void drop_update_tables(srt_pt* pt, uint32_t object);
+// BVH builds of sets at or above the context's threshold go to pt_bvh_device.hip: the context has a device and neither SRT_BVH_BUILDER=host
+// nor srt_pt_set_bvh_builder says otherwise.  While a scope with `on` lives, the scene layer's builds do; it leaves the host builder behind.
+bool device_builds(const srt_pt* pt);
+struct DeviceBuilderScope {
+  DeviceBuilderScope(const srt_pt* pt, bool on);
+  ~DeviceBuilderScope();
+};
+// SRT_OK, or the refusal of trees deeper than the traversal stacks.
+int check_depth(uint32_t tlas_depth, uint32_t blas_depth);
+// Every device write that follows a replaced host mirror (apply_* of pt_scene.h, build_scene) returns through here: after a failed
+// one the device arrays are behind the host's, so the scene is no longer committed and has to be committed again.
+inline int written(srt_pt* pt, int status) {
+  if (status != SRT_OK) pt->committed = false;
+  return status;
+}
+
+}  // namespace srt
+
+#endif

@@ -98,6 +98,15 @@ struct Camera {
   float screen_h, screen_w;  // tanf(Radians(fov) / 2) * 1 * 2 and ar * that (student/camera.cpp:17-18), host libm
 };
 
+// Image-tile shard of one rank: tiles t with t % world == rank, numbered row-major.
+struct TileMap { uint32_t tile_w, tile_h, tiles_x, tiles_y, rank, world, local_tiles; };
+
+enum { C_RAYS = 0, C_BOX, C_OBJ, C_TRI, C_SPH, C_TLAS, C_BLAS, C_LTRI, C_COUNT };   // what the instrumented kernels count (Counters, pt_trace.h)
+
+// What the host refuses at commit and at every update: trees deeper than the kernels' traversal stacks (pt_trace.h)
+constexpr int kMaxTlasDepth = 24;   // interior-node nesting the traversal stacks can hold
+constexpr int kMaxBlasDepth = 48;
+
 struct FlatScene {
   bool use_bvh = true;
   std::vector<Node> nodes;        // [0, tlas_nodes) = BVH<Object>

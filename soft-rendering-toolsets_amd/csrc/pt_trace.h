@@ -10,8 +10,6 @@
 
 namespace srt {
 
-constexpr int kMaxTlasDepth = 24;   // interior-node nesting the traversal stacks can hold
-constexpr int kMaxBlasDepth = 48;
 constexpr int kMaxPathDepth = 16;   // max_depth supported by the per-bounce record stack
 
 struct DScene {
@@ -57,10 +55,6 @@ SRT_DEV void log_ray_event(uint32_t* ring, uint32_t cap, float px, float py, flo
   }
 }
 
-// Image-tile shard of one rank: tiles t with t % world == rank, numbered row-major.
-struct TileMap { uint32_t tile_w, tile_h, tiles_x, tiles_y, rank, world, local_tiles; };
-
-enum { C_RAYS = 0, C_BOX, C_OBJ, C_TRI, C_SPH, C_TLAS, C_BLAS, C_LTRI, C_COUNT };
 struct Counters { uint32_t v[C_COUNT]; uint32_t elided = 0; };   // elided: rays counted in v[C_RAYS] but not traced
 
 // Result of a closest-hit query, as ids (the payload of the winner is recomputed on demand).

@@ -1,0 +1,1111 @@
+// The path tracer's host side after srt_pt_scene_commit: what changes or queries a committed scene - new vertices (srt_pt_update_mesh,
+// srt_pt_refit_mesh), skinning (srt_pt_skin*), new poses (srt_pt_repose*) and the figures about them.  Host code only: the kernels are in
+// pt_mesh_update.hip, pt_pose.hip, pt_light_update.hip, pt_skin.hip and pt_bvh_device.hip, the context and what pt.hip shares in pt_context.h.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "pt_context.h"
+#include "pt_light_update.h"
+#include "pt_mesh_update.h"
+#include "pt_skin.h"
+#include "srt_pt_debug.h"
+
+using namespace srt;
+
+// ---- srt_pt_skin: Skeleton::find_joints once, Skeleton::skin per frame (pt_skin.h, pt_skin.hip) ----
+struct srt_pt_skin {
+  srt_pt* pt = nullptr;
+  uint64_t generation = 0;                  // pt->scene_generation at creation
+  uint32_t object = 0, nverts = 0, ntri = 0, njoints = 0, ninf = 0;
+  std::vector<float> inv;                   // Mat4::inverse(joint_to_bind(j)), 16 floats per joint
+  std::vector<float> mats;                  // the frame's posed_j * inverse_j on their way up
+  float *d_pos = nullptr, *d_nrm = nullptr;             // the bind-pose mesh
+  float *d_inv = nullptr, *d_cap = nullptr, *d_mats = nullptr;
+  uint32_t *d_off = nullptr, *d_jidx = nullptr, *d_last = nullptr;
+  float* d_w = nullptr;
+  float *d_pos_out = nullptr, *d_nrm_out = nullptr;     // srt_pt_skin_pose's staging
+};
+
+namespace {
+
+void free_refit_tables(RefitTables* T) {
+  for (void* p : {(void*)T->d_prim, T->d_leaves, T->d_list, T->d_children, (void*)T->d_level_off, (void*)T->d_tri_boxes, (void*)T->d_node_boxes})
+    if (p) (void)hipFree(p);
+  *T = RefitTables();
+}
+
+// The refit tables of `object` (UINT32_MAX: of every mesh): its tree is about to be replaced.
+void drop_refit_tables(srt_pt* pt, uint32_t object) {
+  for (auto it = pt->refit_tables.begin(); it != pt->refit_tables.end();) {
+    if (object == UINT32_MAX || it->first == object) { free_refit_tables(&it->second); it = pt->refit_tables.erase(it); }
+    else ++it;
+  }
+}
+
+// The BVH<Object> is about to be replaced (or d_pose_list to be overwritten by another call: then only the list is forgotten).
+void forget_top_list(srt_pt* pt) { pt->top_list_valid = false; pt->top_list.clear(); }
+void drop_top_tables(srt_pt* pt) {
+  pt->top_tables.d_tri_boxes = nullptr;                   // (the pose tables' posed boxes: drop_pose_tables frees them)
+  if (pt->have_top_tables) free_refit_tables(&pt->top_tables);
+  pt->have_top_tables = false;
+  if (pt->d_slot_of) (void)hipFree(pt->d_slot_of);
+  pt->d_slot_of = nullptr;
+  forget_top_list(pt);
+}
+
+void drop_pose_tables(srt_pt* pt) {
+  for (void* p : {(void*)pt->d_pose_records, (void*)pt->d_local_boxes, (void*)pt->d_posed_boxes})
+    if (p) (void)hipFree(p);
+  pt->d_pose_records = nullptr; pt->d_local_boxes = pt->d_posed_boxes = nullptr;
+  pt->pose_tables = false;
+}
+
+// No srt_pt_repose_refit_device call is waiting for settle() any more.
+void forget_pending(srt_pt* pt) {
+  pt->top_pending = 0;
+  for (uint32_t i : pt->top_pending_objects) pt->top_pending_flag[i] = 0;
+  pt->top_pending_objects.clear();
+}
+
+// Nothing is in flight any more: epochs the caller enqueued on streams of its own read the arrays that are about to change.
+hipError_t quiesce(srt_pt* pt) {
+  hipError_t e;
+  if ((e = hipSetDevice(pt->device)) != hipSuccess || (e = hipStreamSynchronize(pt->stream)) != hipSuccess) return e;
+  return hipDeviceSynchronize();
+}
+
+// The index buffer of mesh `object` on the device.  Every mesh that can be updated has its own from the commit on; an emissive
+// mesh has it from the commit only when srt_pt_set_dynamic_lights was on by then - otherwise it is appended here, at the light's
+// first update, refit or skin.  Nothing a render kernel reads; the caller has waited for whatever reads d_idx.
+int ensure_mesh_idx(srt_pt* pt, uint32_t object) {
+  if (pt->idx_off[object] != SIZE_MAX) return SRT_OK;
+  const std::vector<uint32_t>& idx = pt->built.inputs[object].mesh.idx;
+  uint32_t* fresh = nullptr;
+  SRT_HIP(hipMalloc(&fresh, (pt->idx_words + idx.size()) * sizeof(uint32_t)));
+  if ((pt->idx_words && hipMemcpy(fresh, pt->d_idx, pt->idx_words * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess) ||
+      hipMemcpy(fresh + pt->idx_words, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(fresh);
+    return srt::fail(SRT_ERR_HIP, "index buffer of object %u: device copy failed", object);
+  }
+  if (pt->d_idx) (void)hipFree(pt->d_idx);
+  pt->d_idx = fresh;
+  pt->idx_off[object] = pt->idx_words;
+  pt->idx_words += idx.size();
+  pt->idx_uncounted += idx.size() * sizeof(uint32_t);
+  return SRT_OK;
+}
+
+// Host forms of the dynamic-light calls (srt_pt_repose, srt_pt_update_mesh, srt_pt_refit_mesh): the light's record and its
+// LightTri records from the host mirror, and - after new vertices - its light-list triangle copies.  The device forms run the
+// kernels of pt_light_update.hip instead and upload none of this.
+int upload_light(srt_pt* pt, uint32_t li, bool triangles) {
+  const FlatScene& F = pt->built.flat;
+  const Light& L = F.lights[li];
+  const size_t lt = (size_t)(L.tri_base - F.light_tri_first), n = L.ntri;
+  SRT_HIP(hipMemcpy(pt->d_lights + li, &L, sizeof(Light), hipMemcpyHostToDevice));
+  if (n) SRT_HIP(hipMemcpy(pt->d_ltris + lt, &F.light_tris[lt], n * sizeof(LightTri), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += sizeof(Light) + n * sizeof(LightTri);
+  if (triangles && n) {
+    SRT_HIP(hipMemcpy(pt->d_tris + L.tri_base, &F.tris[L.tri_base], n * sizeof(Tri), hipMemcpyHostToDevice));
+    SRT_HIP(hipMemcpy(pt->d_nrm + L.tri_base, &F.tri_nrm[L.tri_base], n * sizeof(TriNrm), hipMemcpyHostToDevice));
+    SRT_HIP(hipMemcpy(pt->d_tri_packed + 9 * (size_t)L.tri_base, &F.tri_packed[9 * (size_t)L.tri_base], 9 * n * sizeof(float), hipMemcpyHostToDevice));
+    const uint64_t bytes = n * (sizeof(Tri) + sizeof(TriNrm) + 9 * sizeof(float));
+    pt->bytes_uploaded += bytes;
+    pt->tri_bytes_uploaded += bytes;
+  }
+  return SRT_OK;
+}
+
+// The light tables of an emissive mesh after new vertices (the verdict is in, the host mirror is true, nothing is in flight):
+// the device forms rewrite them with the kernel from the arrays where they are, the host forms upload them.
+int write_light_mesh_device(srt_pt* pt, hipStream_t s, uint32_t object, bool device_form, const float* d_pos, const float* d_nrm) {
+  const int32_t li = light_of(pt->built, object);
+  if (li < 0) return SRT_OK;
+  if (!device_form) return upload_light(pt, (uint32_t)li, true);
+  const FlatScene& F = pt->built.flat;
+  const Light& L = F.lights[(size_t)li];
+  launch_light_triangles(s, d_pos, d_nrm, pt->d_idx + pt->idx_off[object], L.ntri, pt->d_lights + li, pt->d_tris + L.tri_base, pt->d_nrm + L.tri_base,
+                         pt->d_tri_packed + 9 * (size_t)L.tri_base, pt->d_ltris + (L.tri_base - F.light_tri_first));
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+// The BVH<Object>'s nodes after the scene layer replaced them.  With their count unchanged the BVH<Triangle> nodes behind them have
+// not moved: the first tlas_nodes nodes are copied in place, enqueued on `s`.  Otherwise all of d_nodes goes up anew, once what
+// `s` holds is done with the old array.
+int write_top_level(srt_pt* pt, hipStream_t s, size_t old_tlas_nodes) {
+  const FlatScene& F = pt->built.flat;
+  if (F.tlas_nodes != old_tlas_nodes) {
+    SRT_HIP(hipStreamSynchronize(s));
+    return upload(pt, &pt->d_nodes, F.nodes);
+  }
+  if (F.tlas_nodes) SRT_HIP(hipMemcpyAsync(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice, s));
+  pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node);
+  return SRT_OK;
+}
+
+// The tables in object order after the scene layer replaced them: the sweep records, which of their children hold a real
+// BVH<Triangle> and - unless a kernel has gathered them in place - the object records.  Nothing may be reading the old ones.
+int upload_object_tables(srt_pt* pt, bool records = true) {
+  const FlatScene& F = pt->built.flat;
+  int st;
+  if ((records && (st = upload(pt, &pt->d_objects, F.objects))) || (st = upload(pt, &pt->d_wave, F.wave_tlas))) return st;
+  return upload(pt, &pt->d_wave_lazy, F.wave_lazy);
+}
+
+// Device side of a mesh update whose verdict is in (srt_pt_update_mesh): the node and record arrays after the scene layer
+// re-packed them.  [0, keep) of the old array has not moved and [from, size) of the new one is new or has moved; with another
+// total length the array is allocated anew, the part that stays is copied on the device and only the rest comes from the host.
+template <typename T>
+int upload_tail(srt_pt* pt, hipStream_t s, T** dst, size_t old_size, const std::vector<T>& src, size_t keep_from, size_t keep_to, size_t keep_n,
+                size_t up_from, size_t up_to, bool tri_class) {
+  // old[keep_from, keep_from + keep_n) -> new[keep_to, ..);  src[up_from, up_to) -> new[up_from, up_to)
+  if (src.size() != old_size || keep_from != keep_to) {
+    T* fresh = nullptr;
+    SRT_HIP(hipMalloc(&fresh, (src.empty() ? 1 : src.size()) * sizeof(T)));
+    if ((keep_n && hipMemcpyAsync(fresh + keep_to, *dst + keep_from, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipFree(fresh);
+      return srt::fail(SRT_ERR_HIP, "srt_pt_update_mesh: device copy failed");
+    }
+    (void)hipFree(*dst);
+    *dst = fresh;
+  }
+  if (up_to > up_from) {
+    SRT_HIP(hipMemcpyAsync(*dst + up_from, src.data() + up_from, (up_to - up_from) * sizeof(T), hipMemcpyHostToDevice, s));
+    pt->bytes_uploaded += (up_to - up_from) * sizeof(T);
+    if (tri_class) pt->tri_bytes_uploaded += (up_to - up_from) * sizeof(T);
+  }
+  return SRT_OK;
+}
+
+// What srt_pt_update_mesh and srt_pt_refit_mesh refuse before they touch anything, in this order.
+int check_mesh_call(srt_pt* pt, const char* what, uint32_t object, uint32_t nverts, const float* h_pos) {
+  const int ready = need_committed(pt, what);
+  if (ready != SRT_OK) return ready;
+  const std::string refused = check_mesh_update(pt->built, object, nverts);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (pt->device < 0 && !h_pos) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only", what);
+  return SRT_OK;
+}
+
+// The new vertex arrays of a mesh on both sides.  h_*: the host form's arrays; d_*: the device form's (h_* NULL), read back into back_*.
+struct MeshVertices { const float *h_pos, *h_nrm, *d_pos, *d_nrm; std::vector<float> back_pos, back_nrm; };
+
+// The head of a mesh update or refit on a device: nothing is in flight, the mesh's index buffer is there (an emissive mesh's goes up
+// at its first call under srt_pt_set_dynamic_lights) and the arrays are on both sides, 24 B per vertex.  The host form's go up into
+// the staging - nothing of the live scene yet; blocking: the caller's arrays are not read after the call, however it returns -
+// and *staged_bytes says how much, for the caller to count.  The device form's come back, so that BuiltScene::inputs and the host
+// mirrors stay true: the copies are enqueued on `s`, V->h_* hold them once the caller has synchronised `s`.
+int stage_vertices(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, uint32_t nverts, bool refuse_non_finite, MeshVertices* V,
+                   uint64_t* staged_bytes) {
+  const size_t vfloats = 3 * (size_t)nverts;
+  SRT_HIP(quiesce(pt));
+  int st;
+  if ((st = ensure_mesh_idx(pt, object))) return st;
+  if (V->h_pos) {
+    if (refuse_non_finite)
+      for (size_t k = 0; k < vfloats; k++)
+        if (!std::isfinite(V->h_pos[k])) return srt::fail(SRT_ERR_INVALID, "%s: vertex %zu of the new positions has a non-finite coordinate", what, k / 3);
+    if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
+    SRT_HIP(hipMemcpy(pt->d_vpos, V->h_pos, vfloats * sizeof(float), hipMemcpyHostToDevice));
+    SRT_HIP(hipMemcpy(pt->d_vnrm, V->h_nrm, vfloats * sizeof(float), hipMemcpyHostToDevice));
+    *staged_bytes = 2 * vfloats * sizeof(float);
+    V->d_pos = pt->d_vpos; V->d_nrm = pt->d_vnrm;
+  } else {
+    V->back_pos.resize(vfloats); V->back_nrm.resize(vfloats);
+    SRT_HIP(hipMemcpyAsync(V->back_pos.data(), V->d_pos, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+    SRT_HIP(hipMemcpyAsync(V->back_nrm.data(), V->d_nrm, vfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+    V->h_pos = V->back_pos.data(); V->h_nrm = V->back_nrm.data();
+  }
+  return SRT_OK;
+}
+
+// srt_pt_update_mesh / srt_pt_update_mesh_device (then `s` is the caller's stream).
+int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, MeshVertices V, uint32_t nverts) {
+  int st;
+  if ((st = check_mesh_call(pt, what, object, nverts, V.h_pos))) return st;
+  const bool on_device = pt->device >= 0;
+  const bool use_bvh = pt->built.flat.use_bvh;
+  const bool device_form = V.h_pos == nullptr;
+  const MeshStore old = pt->built.store[object];
+  const uint32_t ntri = old.ntri;
+  if (on_device) {
+    uint64_t staged_bytes = 0;
+    if ((st = stage_vertices(pt, what, s, object, nverts, false, &V, &staged_bytes))) return st;
+    pt->bytes_uploaded += staged_bytes;                   // (whatever the verdict)
+    if (device_form) SRT_HIP(hipStreamSynchronize(s));
+  }
+  // the one BVH<Triangle> build goes where srt_pt_scene_commit's would: a mesh at or above the device builder's threshold is
+  // built there, from boxes computed there; anything else on the host
+  const bool device_builder = device_builds(pt);
+  const uint32_t* d_mesh_idx = on_device ? pt->d_idx + pt->idx_off[object] : nullptr;
+  HostBVH device_tree;
+  const bool device_wanted = device_builder && use_bvh && ntri >= pt->bvh_device_min && ntri > 4u;
+  bool device_built = false;
+  if (device_wanted && bvh_workspace_reserve(&pt->bvh_ws, ntri, false)) {
+    launch_mesh_boxes(s, V.d_pos, d_mesh_idx, ntri, pt->bvh_ws.d_boxes);
+    device_built = build_bvh_device_core(&pt->bvh_ws, s, ntri, 4, &device_tree);
+  }
+  // The BVH<Object> build goes where srt_pt_repose's does.  A device build of the mesh that failed - no termination, or no
+  // memory - is not tried a second time through the wrapper: the host builds give the verdict.
+  const DeviceBuilderScope builder(pt, device_builder && !(device_wanted && !device_built));
+  MeshUpdate U;
+  bool bad_argument = false;
+  const std::string err = prepare_mesh_update(pt->built, object, V.h_pos, V.h_nrm, nverts, device_built ? &device_tree : nullptr, &U, &bad_argument);
+  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str());
+  if ((st = check_depth(U.top.max_tlas_depth, U.max_blas_depth))) return st;
+  if (on_device && use_bvh && !device_built) {            // a host build: its primitive order goes up, 4 B per triangle
+    if (!bvh_workspace_reserve(&pt->bvh_ws, ntri, true)) return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+    SRT_HIP(hipMemcpy(pt->bvh_ws.d_prim, U.blas.prim.data(), (size_t)ntri * 4, hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)ntri * 4;
+  }
+  // the verdict is in: from here on the new arrays replace the old ones, on the host and then on the device
+  const size_t old_tlas = pt->built.flat.tlas_nodes, old_nodes = pt->built.flat.nodes.size(), old_recs = pt->built.flat.blas_recs.size();
+  apply_mesh_update(&pt->built, &U);
+  if (on_device) drop_update_tables(pt, object);          // they describe the tree and the boxes that were just replaced
+  if (use_bvh) pt->blas_builds++;
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  if (!on_device) return SRT_OK;
+  pt->bytes_uploaded += pt->idx_uncounted;
+  pt->idx_uncounted = 0;
+  // the record kernel over the mesh's triangle range, the nodes and records that are new or moved, the tables of object order
+  auto write = [&]() -> int {
+    const FlatScene& F = pt->built.flat;
+    const MeshStore now = pt->built.store[object];
+    launch_mesh_records(s, V.d_pos, V.d_nrm, d_mesh_idx, use_bvh ? pt->bvh_ws.d_prim : nullptr, ntri, pt->d_tris + now.tri_base, pt->d_nrm + now.tri_base,
+                        pt->d_tri_packed + 9 * (size_t)now.tri_base);
+    int w;
+    if (use_bvh) {
+      // nodes: the BVH<Object>'s and the mesh's are new; the BVH<Triangle>s in front stay, those behind move when the mesh's count changed
+      const bool same_nodes = now.nnodes == old.nnodes, same_recs = now.nrec == old.nrec;
+      const size_t at = (size_t)F.tlas_nodes + now.node_off;
+      if ((w = upload_tail(pt, s, &pt->d_nodes, old_nodes, F.nodes, old_tlas, F.tlas_nodes, old.node_off, at,
+                           same_nodes && F.tlas_nodes == old_tlas ? at + now.nnodes : F.nodes.size(), false)) ||
+          (w = write_top_level(pt, s, F.tlas_nodes)) ||     // (upload_tail has laid d_nodes out anew: the BVH<Object>'s nodes go in place, whatever their count was)
+          (w = upload_tail(pt, s, &pt->d_blas, old_recs, F.blas_recs, 0, 0, old.rec_base, now.rec_base,
+                           same_recs ? (size_t)now.rec_base + now.nrec : F.blas_recs.size(), true)))
+        return w;
+    }
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    if ((w = upload_object_tables(pt))) return w;
+    return write_light_mesh_device(pt, s, object, device_form, V.d_pos, V.d_nrm);
+  };
+  return written(pt, write());
+}
+
+// The device tables of a tree's refits, from the host tree: made at the first refit after a commit or a rebuild.  `tree`: a mesh's
+// BVH<Triangle> (object: its insertion index) or the BVH<Object> (object == UINT32_MAX; its primitives are the objects, whose
+// boxes the pose tables hold already: no box array of their own is made).
+int make_refit_tables(const HostBVH& tree, const char* what, uint32_t object, RefitTables* T) {
+  const bool top = object == UINT32_MAX;
+  const std::string whose = top ? std::string("the BVH<Object>") : "object " + std::to_string(object);
+  const char* const inside = top ? "scene" : "mesh";
+  const uint32_t nn = (uint32_t)tree.nodes.size(), ntri = (uint32_t)tree.prim.size();
+  // a node's level: children lie behind their parent (level order, student/bvh.inl:144-145), so one forward pass does it
+  std::vector<uint32_t> level(nn, 0u);
+  uint32_t levels = 0;
+  for (uint32_t n = 0; n < nn; n++) {
+    const HostNode& h = tree.nodes[n];
+    if (h.l == h.r) {
+      // the leaf table packs (first slot << 3) | count, and the kernels trust it: refuse here what they could not take
+      if (h.size > 7u || h.start >= (1u << 29) || (uint64_t)h.start + h.size > ntri)
+        return srt::fail(SRT_ERR_UNSUPPORTED, "%s: leaf %u of %s holds %u primitives from slot %u (at most 7, below 2^29, inside the %s)", what, n,
+                         whose.c_str(), h.size, h.start, inside);
+      continue;
+    }
+    if (h.l <= n || h.r != h.l + 1u || h.r >= nn) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the tree of %s is not in level order", what, whose.c_str());
+    level[h.l] = level[h.r] = level[n] + 1u;
+    levels = std::max(levels, level[n] + 1u);
+  }
+  for (uint32_t t : tree.prim)
+    if (t >= ntri) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the primitive order of %s names %s %u of %u", what, whose.c_str(), top ? "object" : "triangle", t, ntri);
+  std::vector<uint2> leaves, list, children;
+  std::vector<uint32_t> off(levels + 1u, 0u);
+  for (uint32_t n = 0; n < nn; n++) {
+    const HostNode& h = tree.nodes[n];
+    if (h.l == h.r) leaves.push_back(make_uint2(n, (h.start << 3) | (h.size & 7u)));
+    else { off[level[n] + 1u]++; children.push_back(make_uint2(h.l, h.r)); }     // records are numbered in node order (append_records)
+  }
+  for (uint32_t l = 0; l < levels; l++) off[l + 1u] += off[l];
+  list.resize(children.size());
+  std::vector<uint32_t> at(off.begin(), off.end() - 1);
+  for (uint32_t n = 0; n < nn; n++)
+    if (tree.nodes[n].l != tree.nodes[n].r) list[at[level[n]]++] = make_uint2(n, tree.nodes[n].l);
+  T->ntri = ntri; T->nnodes = nn; T->nleaves = (uint32_t)leaves.size(); T->nrec = (uint32_t)children.size();
+  T->level_off = off;
+  const char* ll = getenv("SRT_REFIT_LEVEL_LAUNCHES");
+  T->level_launches = ll && atoi(ll) != 0;
+  auto up = [&](auto** dst, const auto& src) -> bool {
+    using E = typename std::remove_reference<decltype(src)>::type::value_type;
+    if (hipMalloc((void**)dst, (src.empty() ? 1 : src.size()) * sizeof(E)) != hipSuccess) return false;
+    if (!src.empty() && hipMemcpy(*dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice) != hipSuccess) return false;
+    T->uncounted_bytes += src.size() * sizeof(E);
+    return true;
+  };
+  if (!up(&T->d_prim, tree.prim) || !up(&T->d_leaves, leaves) || !up(&T->d_list, list) || !up(&T->d_children, children) || !up(&T->d_level_off, off) ||
+      (!top && hipMalloc(&T->d_tri_boxes, (size_t)ntri * 6 * sizeof(float)) != hipSuccess) ||
+      hipMalloc(&T->d_node_boxes, (size_t)(nn ? nn : 1) * 6 * sizeof(float)) != hipSuccess) {
+    free_refit_tables(T);
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+  }
+  return SRT_OK;
+}
+
+// srt_pt_refit_mesh / srt_pt_refit_mesh_device / srt_pt_skin_pose_refit.
+int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, MeshVertices V, uint32_t nverts) {
+  int st;
+  if ((st = check_mesh_call(pt, what, object, nverts, V.h_pos))) return st;
+  if (!pt->built.flat.use_bvh) return update_mesh(pt, what, s, object, V, nverts);   // a list has no tree: the update
+  const bool on_device = pt->device >= 0;
+  const MeshStore m = pt->built.store[object];
+  const bool device_form = V.h_pos == nullptr;
+  std::vector<float> node_boxes;
+  RefitTables* T = nullptr;
+  uint64_t staged_bytes = 0;                              // (counted with the verdict: a refused refit adds nothing to the figures)
+  if (on_device) {
+    if ((st = stage_vertices(pt, what, s, object, nverts, true, &V, &staged_bytes))) return st;
+    auto it = pt->refit_tables.find(object);
+    if (it == pt->refit_tables.end()) {
+      RefitTables fresh;
+      if ((st = make_refit_tables(pt->built.blas[object], "srt_pt_refit_mesh", object, &fresh)) != SRT_OK) { (void)hipStreamSynchronize(s); return st; }   // (the read-back is on s)
+      it = pt->refit_tables.emplace(object, fresh).first;
+    }
+    T = &it->second;
+    // the new boxes, aside: triangle boxes, leaves, levels.  They come back (24 B per node) with the arrays of the device form
+    // (24 B per vertex): the host checks those, takes the root box and keeps its own tree true.
+    launch_mesh_boxes(s, V.d_pos, pt->d_idx + pt->idx_off[object], m.ntri, T->d_tri_boxes);
+    launch_refit_boxes(s, *T, T->d_node_boxes);
+    node_boxes.resize(6 * (size_t)T->nnodes);
+    SRT_HIP(hipMemcpyAsync(node_boxes.data(), T->d_node_boxes, node_boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+  }
+  const DeviceBuilderScope builder(pt, device_builds(pt));   // the BVH<Object> build goes where srt_pt_repose's does
+  MeshRefit R;
+  bool bad_argument = false;
+  const std::string err = prepare_mesh_refit(pt->built, object, V.h_pos, V.h_nrm, nverts, on_device ? node_boxes.data() : nullptr, &R, &bad_argument);
+  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str());
+  if ((st = check_depth(R.top.max_tlas_depth, pt->built.flat.max_blas_depth))) return st;
+  // the verdict is in: from here on the new boxes and records replace the old ones in place, on the host and then on the device
+  const size_t old_tlas = pt->built.flat.tlas_nodes;
+  apply_mesh_refit(&pt->built, &R);
+  pt->refits++;
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  if (!on_device) return SRT_OK;
+  drop_pose_tables(pt);                                   // the object-space boxes changed
+  drop_top_tables(pt);                                    // the BVH<Object> was rebuilt
+  pt->bytes_uploaded += staged_bytes + T->uncounted_bytes + pt->idx_uncounted;   // the vertices of the host form; the tables, at the mesh's first successful refit
+  T->uncounted_bytes = 0;
+  pt->idx_uncounted = 0;
+  auto write = [&]() -> int {
+    int w;
+    if ((w = write_top_level(pt, s, old_tlas))) return w;
+    launch_refit_write(s, *T, T->d_node_boxes, pt->d_nodes + pt->built.flat.tlas_nodes + m.node_off, pt->d_blas + m.rec_base);
+    launch_mesh_records(s, V.d_pos, V.d_nrm, pt->d_idx + pt->idx_off[object], T->d_prim, m.ntri, pt->d_tris + m.tri_base, pt->d_nrm + m.tri_base,
+                        pt->d_tri_packed + 9 * (size_t)m.tri_base);
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    if ((w = upload_object_tables(pt))) return w;
+    return write_light_mesh_device(pt, s, object, device_form, V.d_pos, V.d_nrm);
+  };
+  return written(pt, write());
+}
+
+void skin_free(srt_pt_skin* k) {
+  if (k->pt && k->pt->device >= 0) (void)hipSetDevice(k->pt->device);
+  for (void* p : {(void*)k->d_pos, (void*)k->d_nrm, (void*)k->d_inv, (void*)k->d_cap, (void*)k->d_mats, (void*)k->d_off, (void*)k->d_jidx, (void*)k->d_last,
+                  (void*)k->d_w, (void*)k->d_pos_out, (void*)k->d_nrm_out})
+    if (p) (void)hipFree(p);
+  delete k;
+}
+
+// The device side of srt_pt_skin_create; on failure the caller frees what is there.
+int skin_build(srt_pt_skin* k, const float* bind_positions, const float* bind_normals, const srt_pt_skin_joint* joints) {
+  srt_pt* pt = k->pt;
+  const size_t vfloats = 3 * (size_t)k->nverts;
+  std::vector<float> cap(4 * (size_t)k->njoints);
+  for (uint32_t j = 0; j < k->njoints; j++) {
+    skin_mat4_inverse(joints[j].bind, &k->inv[16 * (size_t)j]);
+    for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = joints[j].extent[a];
+    cap[4 * (size_t)j + 3] = joints[j].radius;
+  }
+  SRT_HIP(hipSetDevice(pt->device));
+  hipStream_t s = pt->stream;
+  const uint32_t nblocks = (k->nverts + 255u) / 256u;
+  SRT_HIP(hipMalloc(&k->d_pos, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_nrm, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_pos_out, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_nrm_out, vfloats * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_inv, k->inv.size() * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_mats, k->inv.size() * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_cap, cap.size() * sizeof(float)));
+  SRT_HIP(hipMalloc(&k->d_off, ((size_t)k->nverts + 1) * sizeof(uint32_t)));
+  SRT_HIP(hipMalloc(&k->d_last, (size_t)k->nverts * sizeof(uint32_t)));
+  SRT_HIP(hipMemcpy(k->d_pos, bind_positions, vfloats * sizeof(float), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(k->d_nrm, bind_normals, vfloats * sizeof(float), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(k->d_inv, k->inv.data(), k->inv.size() * sizeof(float), hipMemcpyHostToDevice));
+  SRT_HIP(hipMemcpy(k->d_cap, cap.data(), cap.size() * sizeof(float), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += (2 * vfloats + k->inv.size() + cap.size()) * sizeof(float);
+  // count, scan, fill; the counts and the block sums live only here
+  uint32_t *d_counts = nullptr, *d_sums = nullptr;
+  SRT_HIP(hipMalloc(&d_counts, (size_t)k->nverts * sizeof(uint32_t)));
+  int st = SRT_OK;
+  if (hipMalloc(&d_sums, (size_t)nblocks * sizeof(uint32_t)) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: out of device memory");
+  uint32_t total = 0;
+  if (st == SRT_OK) {
+    launch_skin_count(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, d_counts);
+    launch_skin_scan(s, d_counts, k->nverts, k->d_off, d_sums);
+    if (hipMemcpyAsync(&total, k->d_off + k->nverts, sizeof total, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
+        hipGetLastError() != hipSuccess)
+      st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: the find_joints kernels failed");
+  }
+  (void)hipFree(d_counts); (void)hipFree(d_sums);
+  if (st != SRT_OK) return st;
+  k->ninf = total;
+  SRT_HIP(hipMalloc(&k->d_jidx, (total ? (size_t)total : 1) * sizeof(uint32_t)));
+  SRT_HIP(hipMalloc(&k->d_w, (total ? (size_t)total : 1) * sizeof(float)));
+  launch_skin_fill(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, k->d_off, k->d_jidx, k->d_w);
+  SRT_HIP(hipMemsetAsync(k->d_last, 0, (size_t)k->nverts * sizeof(uint32_t), s));
+  launch_skin_last_triangle(s, pt->d_idx + pt->idx_off[k->object], k->ntri, k->nverts, k->d_last);
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int skin_usable(const srt_pt_skin* k, const char* what) {
+  if (!k) return srt::fail(SRT_ERR_INVALID, "%s: NULL skin", what);
+  if (!k->pt->committed || k->generation != k->pt->scene_generation)
+    return srt::fail(SRT_ERR_STATE, "%s: the skin is stale - its context's scene was begun or committed again after srt_pt_skin_create", what);
+  return SRT_OK;
+}
+
+// Enqueues the frame's matrices and the skinning kernels on s, for a skin that is usable.
+int skin_enqueue(srt_pt_skin* k, const char* what, hipStream_t s, const float* posed, int flat_normals, float* d_pos_out, float* d_nrm_out) {
+  const int usable = skin_usable(k, what);
+  if (usable != SRT_OK) return usable;
+  SRT_HIP(hipSetDevice(k->pt->device));
+  for (uint32_t j = 0; j < k->njoints; j++) skin_mat4_mul(posed + 16 * (size_t)j, &k->inv[16 * (size_t)j], &k->mats[16 * (size_t)j]);
+  SRT_HIP(hipMemcpyAsync(k->d_mats, k->mats.data(), k->mats.size() * sizeof(float), hipMemcpyHostToDevice, s));   // 64 B per joint
+  k->pt->bytes_uploaded += k->mats.size() * sizeof(float);
+  launch_skin_vertices(s, k->d_pos, k->d_nrm, k->nverts, k->d_mats, k->njoints, k->d_off, k->d_jidx, k->d_w, d_pos_out, flat_normals ? nullptr : d_nrm_out);
+  if (flat_normals)
+    launch_skin_flat_normals(s, d_pos_out, k->d_nrm, k->pt->d_idx + k->pt->idx_off[k->object], k->ntri, k->d_last, k->nverts, d_nrm_out);
+  return SRT_OK;
+}
+
+// srt_pt_skin_pose / srt_pt_skin_pose_refit: the frame's vertices into the skin's staging, then update_mesh or refit_mesh from there.
+// (The staging is read by nothing of the context: writing it before the verdict changes no scene.)
+int skin_pose(srt_pt_skin* skin, const char* what, void* stream, const float* posed, int flat_normals, decltype(update_mesh)* mesh_call) {
+  if (!skin || !posed) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_enqueue(skin, what, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out);
+  if (st != SRT_OK) return st;
+  return mesh_call(skin->pt, what, (hipStream_t)stream, skin->object, {nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, {}, {}}, skin->nverts);
+}
+
+std::vector<Mat4> matrices(const float* trans, uint32_t n) {
+  static_assert(sizeof(Mat4) == 16 * sizeof(float), "Mat4 is sixteen floats");
+  std::vector<Mat4> T(n);
+  if (n) std::memcpy(T.data(), trans, (size_t)n * sizeof(Mat4));
+  return T;
+}
+
+// The listed area lights (srt_pt_set_dynamic_lights): {position in the list, light} pairs as the light kernels take them, and the largest triangle count.
+struct ListedLights { std::vector<uint32_t> pairs; uint32_t max_ntri = 0; };
+ListedLights listed_lights(const BuiltScene& built, const uint32_t* objects, uint32_t n) {
+  ListedLights L;
+  for (uint32_t k = 0; k < n; k++) {
+    const int32_t li = built.inputs[objects[k]].is_light ? light_of(built, objects[k]) : -1;   // (light_of counts the lights in front)
+    if (li < 0) continue;
+    L.pairs.push_back(k);
+    L.pairs.push_back((uint32_t)li);
+    L.max_ntri = std::max(L.max_ntri, built.flat.lights[(size_t)li].ntri);
+  }
+  return L;
+}
+
+// Host forms: the listed lights' records as the host mirror has them now.
+int upload_listed_lights(srt_pt* pt, const uint32_t* objects, uint32_t n) {
+  const ListedLights L = listed_lights(pt->built, objects, n);
+  int st = SRT_OK;
+  for (size_t q = 1; q < L.pairs.size() && st == SRT_OK; q += 2) st = upload_light(pt, L.pairs[q], false);
+  return st;
+}
+
+// Device forms: the records of the `nl` lights in d_light_list from the pose kernel's output where it lies (d_pose_out, `n` poses),
+// then their area terms under the new pdfT.  No upload.
+void launch_listed_lights(srt_pt* pt, hipStream_t s, uint32_t nl, uint32_t max_ntri, uint32_t n) {
+  const FlatScene& F = pt->built.flat;
+  launch_light_records(s, pt->d_light_list, nl, pt->d_pose_out, n, pt->d_lights, (uint32_t)F.lights.size());
+  launch_light_area_terms(s, pt->d_light_list, nl, max_ntri, pt->d_lights, (uint32_t)F.lights.size(), F.light_tri_first, pt->d_ltris, (uint32_t)F.light_tris.size());
+}
+
+// The tables the pose kernels work in, made at the first device-form repose after a commit or after a call that dropped them: the
+// records by insertion index come from the live records (a kernel on `s`; nothing goes up), the posed boxes from them and the
+// object-space boxes (24 B per object up, added to *bytes).
+int ensure_pose_tables(srt_pt* pt, hipStream_t s, const char* what, uint64_t* bytes) {
+  if (pt->pose_tables) return SRT_OK;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  const size_t room = nobj ? nobj : 1;
+  drop_pose_tables(pt);
+  if (hipMalloc(&pt->d_pose_records, room * sizeof(Object)) != hipSuccess || hipMalloc(&pt->d_local_boxes, room * 6 * sizeof(float)) != hipSuccess ||
+      hipMalloc(&pt->d_posed_boxes, room * 6 * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    drop_pose_tables(pt);
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+  }
+  // (blocking copy, then kernels on `s` that read what the last commit or repose left in d_objects: all of it done by now)
+  if (nobj) SRT_HIP(hipMemcpy(pt->d_local_boxes, pt->built.local_boxes.data(), (size_t)nobj * 6 * sizeof(float), hipMemcpyHostToDevice));
+  *bytes += (uint64_t)nobj * 6 * sizeof(float);
+  launch_pose_tables(s, pt->d_objects, nobj, pt->built.flat.tlas_nodes, pt->d_pose_records, pt->d_local_boxes, pt->d_posed_boxes);
+  pt->pose_tables = true;
+  return SRT_OK;
+}
+
+// A pinned staging buffer of at least `words` words whose last copy has left it (or a new one).
+int pinned_list(srt_pt* pt, size_t words, srt_pt::PinnedList** out) {
+  for (auto& pl : pt->pinned) {
+    if (pl.words < words) continue;
+    const hipError_t left = hipEventQuery(pl.done);
+    (void)hipGetLastError();                              // (hipErrorNotReady of a query is no error: not left behind for the launch check)
+    if (left == hipSuccess) { *out = &pl; return SRT_OK; }
+  }
+  srt_pt::PinnedList pl;
+  pl.words = std::max<size_t>(words, 1024);
+  if (hipHostMalloc((void**)&pl.h, pl.words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return srt::fail(SRT_ERR_HIP, "out of pinned host memory");
+  if (hipEventCreateWithFlags(&pl.done, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(pl.h); return srt::fail(SRT_ERR_HIP, "event creation failed"); }
+  pt->pinned.push_back(pl);
+  *out = &pt->pinned.back();
+  return SRT_OK;
+}
+
+// srt_pt_repose_refit's device side after apply_top_refit: the arrays that changed, from the host's record.
+int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n) {
+  const FlatScene& F = pt->built.flat;
+  if (F.use_bvh) {
+    if (F.tlas_nodes) SRT_HIP(hipMemcpy(pt->d_nodes, F.nodes.data(), (size_t)F.tlas_nodes * sizeof(Node), hipMemcpyHostToDevice));
+    if (!F.wave_tlas.empty()) SRT_HIP(hipMemcpy(pt->d_wave, F.wave_tlas.data(), F.wave_tlas.size() * sizeof(WaveInterior), hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)F.tlas_nodes * sizeof(Node) + F.wave_tlas.size() * sizeof(WaveInterior);
+  }
+  // the listed records, one copy per run of neighbouring slots (a pool that moves as a whole is a handful of runs)
+  std::vector<uint32_t> slot_of(pt->built.tlas.prim.size()), slots(n);
+  for (size_t k = 0; k < slot_of.size(); k++) slot_of[pt->built.tlas.prim[k]] = (uint32_t)k;
+  for (uint32_t k = 0; k < n; k++) slots[k] = slot_of[objects[k]];
+  std::sort(slots.begin(), slots.end());
+  for (uint32_t k = 0; k < n;) {
+    uint32_t e = k + 1;
+    while (e < n && slots[e] == slots[e - 1] + 1u) e++;
+    SRT_HIP(hipMemcpy(pt->d_objects + slots[k], &F.objects[slots[k]], (size_t)(e - k) * sizeof(Object), hipMemcpyHostToDevice));
+    pt->bytes_uploaded += (uint64_t)(e - k) * sizeof(Object);
+    k = e;
+  }
+  return upload_listed_lights(pt, objects, n);
+}
+
+}  // namespace
+
+namespace srt {
+
+void drop_update_tables(srt_pt* pt, uint32_t object) { drop_refit_tables(pt, object); drop_pose_tables(pt); drop_top_tables(pt); }
+
+// The host's record catches up with the device after srt_pt_repose_refit_device calls: one wait for the event behind the last of
+// them, one read-back (176 B per object: the records by insertion index; 24 B per node: the top-level boxes), and the scene
+// layer's own apply_top_refit - the lights' records come from the host's light_record / light_area_term.  With nothing pending it
+// does nothing.
+int settle(srt_pt* pt) {
+  if (!pt || !pt->top_pending) return SRT_OK;
+  if (!pt->committed) { discard_pending(pt); return SRT_OK; }   // (a failure took the scene away: there is no record to bring up to date)
+  const uint64_t calls = pt->top_pending;
+  std::vector<uint32_t> objects = pt->top_pending_objects;
+  forget_pending(pt);
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  const bool use_bvh = pt->built.flat.use_bvh;
+  std::vector<Object> records(nobj);
+  TopRefit R;
+  if (use_bvh) R.boxes.resize(6 * (size_t)pt->top_tables.nnodes);
+  if (hipSetDevice(pt->device) != hipSuccess || hipEventSynchronize(pt->top_event) != hipSuccess ||
+      (nobj && hipMemcpy(records.data(), pt->d_pose_records, (size_t)nobj * sizeof(Object), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (!R.boxes.empty() && hipMemcpy(R.boxes.data(), pt->top_tables.d_node_boxes, R.boxes.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
+    pt->committed = false;
+    return srt::fail(SRT_ERR_HIP, "settling srt_pt_repose_refit_device: %s; the scene has to be committed again", hipGetErrorString(hipGetLastError()));
+  }
+  for (uint32_t i : objects) {                            // (every object once: top_pending_flag)
+    R.listed.push_back(i);
+    R.trans.push_back(records[i].trans);
+    R.itrans.push_back(records[i].itrans);
+    R.has_trans.push_back(records[i].has_trans);
+  }
+  apply_top_refit(&pt->built, &R);
+  pt->top_refits += calls;
+  return SRT_OK;
+}
+
+// srt_pt_scene_begin, srt_pt_scene_commit, srt_pt_destroy: wait for what is pending and forget it.
+void discard_pending(srt_pt* pt) {
+  if (!pt->top_pending) return;
+  if (hipSetDevice(pt->device) == hipSuccess) (void)hipEventSynchronize(pt->top_event);
+  pt->top_refits += pt->top_pending;                      // (they ran; only their read-back is not worth making any more)
+  forget_pending(pt);
+}
+
+int not_committed(const char* what) { return srt::fail(SRT_ERR_STATE, "%s before srt_pt_scene_commit", what); }
+int need_committed(srt_pt* pt, const char* what) {
+  const int settled = settle(pt);
+  return settled != SRT_OK ? settled : pt->committed ? SRT_OK : not_committed(what);
+}
+
+bool device_builds(const srt_pt* pt) {
+  const char* be = getenv("SRT_BVH_BUILDER");
+  return pt->device >= 0 && (be ? strcmp(be, "host") != 0 : pt->bvh_builder != 0);
+}
+
+DeviceBuilderScope::DeviceBuilderScope(const srt_pt* pt, bool on) {
+  if (on) set_device_bvh_builder(build_bvh_device, pt->bvh_device_min);
+  else set_device_bvh_builder(nullptr, 0);
+}
+DeviceBuilderScope::~DeviceBuilderScope() { set_device_bvh_builder(nullptr, 0); }
+
+// (Calls that replace only the BVH<Object> pass the committed BVH<Triangle> depth, which is within the limit.)
+int check_depth(uint32_t tlas_depth, uint32_t blas_depth) {
+  if ((int)tlas_depth <= kMaxTlasDepth && (int)blas_depth <= kMaxBlasDepth) return SRT_OK;
+  return srt::fail(SRT_ERR_UNSUPPORTED, "BVH too deep for the traversal stacks (TLAS %u > %d or BLAS %u > %d)", tlas_depth, kMaxTlasDepth, blas_depth, kMaxBlasDepth);
+}
+
+}  // namespace srt
+
+extern "C" {
+
+int srt_pt_update_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
+  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh: NULL argument");
+  return update_mesh(pt, "srt_pt_update_mesh", pt->stream, object, {positions, normals, nullptr, nullptr, {}, {}}, nverts);
+}
+
+int srt_pt_update_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
+  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_update_mesh_device: NULL argument");
+  return update_mesh(pt, "srt_pt_update_mesh_device", (hipStream_t)stream, object, {nullptr, nullptr, d_positions, d_normals, {}, {}}, nverts);
+}
+
+int srt_pt_refit_mesh(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
+  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh: NULL argument");
+  return refit_mesh(pt, "srt_pt_refit_mesh", pt->stream, object, {positions, normals, nullptr, nullptr, {}, {}}, nverts);
+}
+
+int srt_pt_refit_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
+  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh_device: NULL argument");
+  return refit_mesh(pt, "srt_pt_refit_mesh_device", (hipStream_t)stream, object, {nullptr, nullptr, d_positions, d_normals, {}, {}}, nverts);
+}
+
+int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost) {
+  if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: NULL argument");
+  if (!pt->committed) return not_committed("srt_pt_mesh_tree_cost");
+  const std::string refused = check_mesh_update(pt->built, object, (uint32_t)(object < pt->built.inputs.size() ? pt->built.inputs[object].mesh.pos.size() / 3 : 0));
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: %s", refused.c_str());
+  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_mesh_tree_cost: the scene was committed without BVHs, the mesh has no tree");
+  *cost = tree_cost(pt->built.blas[object]);
+  return SRT_OK;
+}
+
+int srt_pt_refit_count(srt_pt* pt, uint64_t* refits) {
+  if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_count: NULL argument");
+  *refits = pt->refits;
+  return SRT_OK;
+}
+
+int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions, const float* bind_normals, uint32_t nverts,
+                       const srt_pt_skin_joint* joints, uint32_t njoints, srt_pt_skin** skin) {
+  if (skin) *skin = nullptr;
+  if (!pt || !bind_positions || !bind_normals || !joints || !skin) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: NULL argument");
+  if (!pt->committed) return not_committed("srt_pt_skin_create");
+  const std::string refused = check_mesh_update(pt->built, object, nverts);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: %s", refused.c_str());
+  if (njoints == 0) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_create: a skin needs at least one joint");
+  if (njoints > kSkinMaxJoints || (uint64_t)nverts * njoints > kSkinMaxPairs)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_skin_create: %u joints on %u vertices (at most %u joints and 2^31 vertex-joint pairs)", njoints, nverts,
+                     kSkinMaxJoints);
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_skin_create: skinning runs on the device only; this context is host-only and there is no CPU path");
+  srt_pt_skin* k = new (std::nothrow) srt_pt_skin;
+  if (!k) return srt::fail(SRT_ERR_INVALID, "out of host memory");
+  k->pt = pt; k->generation = pt->scene_generation; k->object = object; k->nverts = nverts; k->njoints = njoints;
+  k->ntri = pt->built.store[object].ntri;
+  k->inv.resize(16 * (size_t)njoints);
+  k->mats.resize(16 * (size_t)njoints);
+  int st = SRT_OK;
+  if (pt->idx_off[object] == SIZE_MAX) {                  // an emissive mesh under srt_pt_set_dynamic_lights: its index buffer goes up now
+    if (quiesce(pt) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: synchronisation failed");
+    else st = ensure_mesh_idx(pt, object);
+    if (st == SRT_OK) { pt->bytes_uploaded += pt->idx_uncounted; pt->idx_uncounted = 0; }
+  }
+  if (st == SRT_OK) st = skin_build(k, bind_positions, bind_normals, joints);
+  if (st != SRT_OK) { skin_free(k); return st; }
+  *skin = k;
+  return SRT_OK;
+}
+
+int srt_pt_skin_destroy(srt_pt_skin* skin) {
+  if (!skin) return SRT_OK;
+  if (skin->pt->device >= 0) (void)quiesce(skin->pt);
+  skin_free(skin);
+  return SRT_OK;
+}
+
+int srt_pt_skin_counts(srt_pt_skin* skin, uint32_t out[4]) {
+  if (!skin || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_counts: NULL argument");
+  out[0] = skin->nverts; out[1] = skin->njoints; out[2] = skin->ninf; out[3] = skin->ntri;
+  return SRT_OK;
+}
+
+int srt_pt_skin_map(srt_pt_skin* skin, uint32_t* offsets, uint32_t* joints, float* weights, uint32_t cap) {
+  if (!skin || !offsets || !joints || !weights) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_map: NULL argument");
+  int st = skin_usable(skin, "srt_pt_skin_map");
+  if (st != SRT_OK) return st;
+  if (cap < skin->ninf) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_map: the map has %u influences, the arrays hold %u", skin->ninf, cap);
+  SRT_HIP(hipSetDevice(skin->pt->device));
+  SRT_HIP(hipMemcpy(offsets, skin->d_off, ((size_t)skin->nverts + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (skin->ninf) {
+    SRT_HIP(hipMemcpy(joints, skin->d_jidx, (size_t)skin->ninf * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SRT_HIP(hipMemcpy(weights, skin->d_w, (size_t)skin->ninf * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return SRT_OK;
+}
+
+int srt_pt_skin_vertices_device(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals, float* d_positions_out, float* d_normals_out) {
+  if (!skin || !posed || !d_positions_out || !d_normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices_device: NULL argument");
+  return skin_enqueue(skin, "srt_pt_skin_vertices_device", (hipStream_t)stream, posed, flat_normals, d_positions_out, d_normals_out);
+}
+
+int srt_pt_skin_vertices(srt_pt_skin* skin, const float* posed, int flat_normals, float* positions_out, float* normals_out) {
+  if (!skin || !posed || !positions_out || !normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices: NULL argument");
+  hipStream_t s = skin->pt->stream;
+  const int st = skin_enqueue(skin, "srt_pt_skin_vertices", s, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out);
+  if (st != SRT_OK) return st;
+  const size_t bytes = 3 * (size_t)skin->nverts * sizeof(float);
+  SRT_HIP(hipMemcpyAsync(positions_out, skin->d_pos_out, bytes, hipMemcpyDeviceToHost, s));
+  SRT_HIP(hipMemcpyAsync(normals_out, skin->d_nrm_out, bytes, hipMemcpyDeviceToHost, s));
+  SRT_HIP(hipStreamSynchronize(s));
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
+  return skin_pose(skin, "srt_pt_skin_pose", stream, posed, flat_normals, update_mesh);
+}
+
+int srt_pt_skin_pose_refit(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
+  return skin_pose(skin, "srt_pt_skin_pose_refit", stream, posed, flat_normals, refit_mesh);
+}
+
+int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
+  if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose: NULL argument");
+  int st;
+  if ((st = need_committed(pt, "srt_pt_repose"))) return st;
+  const bool on_device = pt->device >= 0;
+  if (on_device) SRT_HIP(hipSetDevice(pt->device));
+  const DeviceBuilderScope builder(pt, device_builds(pt));   // the BVH<Object> build goes where srt_pt_scene_commit's does
+  ReposedTop top;
+  bool bad_argument = false;
+  const std::string err = prepare_repose(pt->built, objects, matrices(trans, n).data(), n, &top, &bad_argument);
+  if (!err.empty()) return srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "srt_pt_repose: %s", err.c_str());
+  if ((st = check_depth(top.max_tlas_depth, pt->built.flat.max_blas_depth))) return st;
+  // from here on nothing fails on the host side: the new tables replace the old ones
+  const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
+  if (on_device) SRT_HIP(quiesce(pt));
+  apply_repose(&pt->built, &top);
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  if (!on_device) return SRT_OK;
+  drop_pose_tables(pt);                                   // srt_pt_repose_device's tables mirror the poses that were just replaced
+  drop_top_tables(pt);                                    // srt_pt_repose_refit_device's describe the tree that was just replaced
+  auto write = [&]() -> int {
+    int w;
+    if ((w = write_top_level(pt, pt->stream, old_tlas_nodes))) return w;
+    SRT_HIP(hipStreamSynchronize(pt->stream));            // (a host form returns with its copies complete)
+    if ((w = upload_object_tables(pt))) return w;
+    return upload_listed_lights(pt, objects, n);
+  };
+  return written(pt, write());
+}
+
+int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
+  const char* what = "srt_pt_repose_device";
+  if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st;
+  if ((st = need_committed(pt, what))) return st;
+  const std::string refused = check_repose_list(pt->built, objects, n);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose takes host matrices)", what);
+  SRT_HIP(hipSetDevice(pt->device));
+  forget_top_list(pt);                                    // d_pose_list and d_light_list are about to hold this call's lists
+  hipStream_t s = (hipStream_t)stream;
+  const bool use_bvh = pt->built.flat.use_bvh;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  uint64_t staged_bytes = 0;                              // (counted with the verdict: a refused repose adds nothing to the figures)
+  if ((st = ensure_pose_tables(pt, s, what, &staged_bytes))) return st;
+  // From here to the verdict only these tables and the staging are written; a refusal drops the tables (the next call makes them
+  // again from the committed records, which are not touched).
+  auto refuse = [&](int status) { drop_pose_tables(pt); return status; };
+  auto copy_failed = [&] { return refuse(srt::fail(SRT_ERR_HIP, "%s: copy failed", what)); };
+  std::vector<PoseOut> posed(n);
+  std::vector<float> boxes;
+  if (n) {
+    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n))) return refuse(st);
+    if (hipMemcpyAsync(pt->d_pose_list, objects, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
+    staged_bytes += (uint64_t)n * 4;
+    launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
+    if (hipMemcpyAsync(posed.data(), pt->d_pose_out, (size_t)n * sizeof(PoseOut), hipMemcpyDeviceToHost, s) != hipSuccess) return copy_failed();
+  }
+  if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: the pose kernel failed", what));
+  // The BVH<Object> build goes where srt_pt_repose's does: on the device, over the boxes where they are, for a scene at or above
+  // the device builder's threshold; anything else - and a device build that failed: the host build gives the verdict - on the host,
+  // over the boxes read back (24 B per object).
+  HostBVH device_tree;
+  bool device_built = false;
+  if (use_bvh && device_builds(pt) && nobj >= pt->bvh_device_min && nobj > 1u && bvh_workspace_reserve(&pt->bvh_ws, nobj, false)) {
+    BvhWorkspace view = pt->bvh_ws;                       // the context's workspace with the posed boxes in the place of its own
+    view.d_boxes = pt->d_posed_boxes;
+    device_built = build_bvh_device_core(&view, s, nobj, 1, &device_tree);
+  }
+  if (use_bvh && !device_built) {
+    boxes.resize((size_t)nobj * 6);
+    if (hipMemcpyAsync(boxes.data(), pt->d_posed_boxes, boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return copy_failed();
+  }
+  std::vector<Mat4> trans(n), itrans(n);
+  std::vector<uint32_t> has_trans(n);
+  for (uint32_t k = 0; k < n; k++) {
+    std::memcpy(&trans[k], posed[k].trans, sizeof(Mat4));
+    std::memcpy(&itrans[k], posed[k].itrans, sizeof(Mat4));
+    has_trans[k] = posed[k].has_trans;
+    // (with a device-built tree the posed box has served already; the host's record holds it in the tree's leaves)
+  }
+  SuppliedPoses P;
+  P.trans = trans.data(); P.itrans = itrans.data(); P.has_trans = has_trans.data();
+  P.boxes6 = boxes.empty() ? nullptr : boxes.data();
+  P.prebuilt = device_built ? &device_tree : nullptr;
+  const DeviceBuilderScope builder(pt, false);            // (the tree is supplied, or built on the host)
+  ReposedTop top;
+  bool bad_argument = false;
+  const std::string err = prepare_repose_supplied(pt->built, objects, n, P, &top, &bad_argument);
+  if (!err.empty()) return refuse(srt::fail(bad_argument ? SRT_ERR_INVALID : SRT_ERR_UNSUPPORTED, "%s: %s", what, err.c_str()));
+  if ((st = check_depth(top.max_tlas_depth, pt->built.flat.max_blas_depth))) return refuse(st);
+  // the primitive order and the mesh ordinals per slot, still aside: a host build's order goes up (4 B per slot), a device build's
+  // is where the record kernel reads it; the ordinals (bits 8 and up of use_bvh) are the host's
+  const uint32_t *d_prim = nullptr, *d_ordinal = nullptr;
+  std::vector<uint32_t> ordinal;
+  if (use_bvh) {
+    if (!device_built) {
+      if (!bvh_workspace_reserve(&pt->bvh_ws, nobj, true)) return refuse(srt::fail(SRT_ERR_HIP, "%s: out of device memory", what));
+      if (hipMemcpyAsync(pt->bvh_ws.d_prim, top.tlas.prim.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
+      staged_bytes += (uint64_t)nobj * 4;
+    }
+    d_prim = pt->bvh_ws.d_prim;
+    if (!top.lazy_objects.empty()) {
+      ordinal.assign(nobj, 0u);
+      for (size_t q = 0; q < top.lazy_objects.size(); q++) ordinal[top.lazy_objects[q]] = (uint32_t)q << 8;
+      if ((st = ensure(&pt->d_slot_ordinal, &pt->slot_ordinal_n, (size_t)nobj))) return refuse(st);
+      if (hipMemcpyAsync(pt->d_slot_ordinal, ordinal.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
+      staged_bytes += (uint64_t)nobj * 4;
+      d_ordinal = pt->d_slot_ordinal;
+    }
+  }
+  // the listed area lights (srt_pt_set_dynamic_lights), still aside
+  const ListedLights lights = listed_lights(pt->built, objects, n);
+  if (!lights.pairs.empty()) {
+    if ((st = ensure(&pt->d_light_list, &pt->light_list_n, lights.pairs.size()))) return refuse(st);
+    if (hipMemcpyAsync(pt->d_light_list, lights.pairs.data(), lights.pairs.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
+    staged_bytes += (uint64_t)lights.pairs.size() * 4;
+  }
+  // the verdict is in; nothing of the context may be in flight while the live arrays change
+  const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
+  if (hipStreamSynchronize(s) != hipSuccess || quiesce(pt) != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: synchronisation failed", what));
+  apply_repose(&pt->built, &top);
+  drop_top_tables(pt);                                    // srt_pt_repose_refit_device's describe the tree that was just replaced
+  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->bytes_uploaded += staged_bytes;
+  auto write = [&]() -> int {
+    int w;
+    if ((w = write_top_level(pt, s, old_tlas_nodes))) return w;
+    // the records in place (the object count never changes): gathered on the device by the new order
+    launch_pose_records(s, pt->d_pose_records, d_prim, d_ordinal, nobj, pt->built.flat.tlas_nodes, pt->d_objects);
+    if (!lights.pairs.empty()) launch_listed_lights(pt, s, (uint32_t)(lights.pairs.size() / 2), lights.max_ntri, n);
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    return upload_object_tables(pt, false);
+  };
+  st = written(pt, write());
+  if (st != SRT_OK) drop_pose_tables(pt);
+  return st;
+}
+
+int srt_pt_repose_refit(srt_pt* pt, const uint32_t* objects, const float* trans, uint32_t n) {
+  if (!pt || (n && (!objects || !trans))) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose_refit: NULL argument");
+  int st;
+  if ((st = need_committed(pt, "srt_pt_repose_refit"))) return st;
+  TopRefit R;
+  const std::string err = prepare_top_refit(pt->built, objects, matrices(trans, n).data(), n, &R);
+  if (!err.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_repose_refit: %s", err.c_str());
+  // nothing fails on the host side from here on: the new boxes and records replace the old ones in place
+  if (pt->device >= 0) SRT_HIP(quiesce(pt));
+  apply_top_refit(&pt->built, &R);
+  pt->top_refits++;
+  if (pt->device < 0) return SRT_OK;
+  drop_pose_tables(pt);                                   // they mirror the poses that were just replaced (the tree's tables stay: the tree did)
+  return written(pt, write_top_refit(pt, objects, n));
+}
+
+int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects, const float* d_trans, uint32_t n) {
+  const char* what = "srt_pt_repose_refit_device";
+  if (!pt || (n && (!objects || !d_trans))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (!pt->committed) return not_committed(what);         // (no settle(): this call only adds to what is pending)
+  const std::string refused = check_repose_list(pt->built, objects, n);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose_refit takes host matrices)", what);
+  SRT_HIP(hipSetDevice(pt->device));
+  hipStream_t s = (hipStream_t)stream;
+  const FlatScene& F = pt->built.flat;
+  const bool use_bvh = F.use_bvh;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  int st;
+  // First call after a commit or after a call that replaced the BVH<Object> (blocking, counted once): the pose tables as
+  // srt_pt_repose_device makes them (24 B per object up), the tree's refit tables (about 28 B per object up) and the slot of
+  // every object (a kernel).  Nothing is pending then - every call that drops these tables settles first.
+  if ((st = ensure_pose_tables(pt, s, what, &pt->bytes_uploaded))) return st;
+  if (use_bvh && !pt->have_top_tables) {
+    drop_top_tables(pt);
+    RefitTables fresh;
+    if ((st = make_refit_tables(pt->built.tlas, what, UINT32_MAX, &fresh)) != SRT_OK) return st;
+    pt->top_tables = fresh;
+    pt->have_top_tables = true;
+    pt->bytes_uploaded += fresh.uncounted_bytes;
+    pt->top_tables.uncounted_bytes = 0;
+    if (hipMalloc(&pt->d_slot_of, (size_t)(nobj ? nobj : 1) * sizeof(uint32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      drop_top_tables(pt);
+      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+    }
+    launch_top_slots(s, pt->top_tables.d_prim, nobj, pt->d_slot_of);
+  }
+  // A HIP failure from here on may leave tables, lists or live arrays half written: the scene is no longer committed, what was
+  // pending is forgotten (settle() has no record to bring up to date) and the tables go; the scene has to be committed again.
+  auto broken = [&](int status) {
+    pt->committed = false;
+    if (hipSetDevice(pt->device) == hipSuccess) (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    forget_pending(pt);
+    drop_pose_tables(pt);
+    drop_top_tables(pt);
+    return status;
+  };
+  auto hip_broken = [&](hipError_t e, const char* step) { return broken(srt::fail(SRT_ERR_HIP, "%s: %s failed (%s); the scene has to be committed again", what, step, hipGetErrorString(e))); };
+  hipError_t he;
+  // The list (4 B per listed object, 8 B more per listed light), through pinned memory so that the copy is only enqueued - unless
+  // the device holds this very list already.
+  if (n && !(pt->top_list_valid && pt->top_list.size() == n && std::memcmp(pt->top_list.data(), objects, (size_t)n * 4) == 0)) {
+    const ListedLights lights = listed_lights(pt->built, objects, n);
+    forget_top_list(pt);
+    // (growing one of these arrays frees the old one, which waits for what reads it: first calls and longer lists only)
+    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n)) ||
+        (!lights.pairs.empty() && (st = ensure(&pt->d_light_list, &pt->light_list_n, lights.pairs.size()))))
+      return broken(st);
+    srt_pt::PinnedList* pl = nullptr;
+    if ((st = pinned_list(pt, (size_t)n + lights.pairs.size(), &pl)) != SRT_OK) return broken(st);
+    std::memcpy(pl->h, objects, (size_t)n * 4);
+    if (!lights.pairs.empty()) std::memcpy(pl->h + n, lights.pairs.data(), lights.pairs.size() * 4);
+    if ((he = hipMemcpyAsync(pt->d_pose_list, pl->h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_broken(he, "the copy of the list");
+    if (!lights.pairs.empty() && (he = hipMemcpyAsync(pt->d_light_list, pl->h + n, lights.pairs.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
+      return hip_broken(he, "the copy of the light list");
+    if ((he = hipEventRecord(pl->done, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
+    pt->bytes_uploaded += (uint64_t)n * 4 + lights.pairs.size() * 4;
+    pt->top_list.assign(objects, objects + n);
+    pt->top_lights = (uint32_t)(lights.pairs.size() / 2);
+    pt->top_light_max_ntri = lights.max_ntri;
+    pt->top_list_valid = true;
+  }
+  if (!pt->top_event && (he = hipEventCreateWithFlags(&pt->top_event, hipEventDisableTiming)) != hipSuccess) return hip_broken(he, "hipEventCreate");
+  // Everything below only enqueues on `s`: the poses, the leaves through the tree's primitive order, the levels deepest first, the
+  // boxes into the live nodes and sweep records, the listed records' matrices, the listed lights.  No verdict is needed: depth,
+  // counts, order, kernel form and stack sizes are those of the committed tree.
+  if (n) launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
+  if (use_bvh) {
+    pt->top_tables.d_tri_boxes = pt->d_posed_boxes;       // the tree's primitives are the objects: their boxes are the pose tables' (not owned)
+    launch_refit_boxes(s, pt->top_tables, pt->top_tables.d_node_boxes);
+    launch_refit_write(s, pt->top_tables, pt->top_tables.d_node_boxes, pt->d_nodes, pt->d_wave);
+  }
+  if (n) {
+    launch_top_objects(s, pt->d_pose_list, n, nobj, use_bvh ? pt->d_slot_of : nullptr, pt->d_pose_records, pt->d_objects);
+    if (pt->top_lights) launch_listed_lights(pt, s, pt->top_lights, pt->top_light_max_ntri, n);
+  }
+  if ((he = hipGetLastError()) != hipSuccess) return hip_broken(he, "a launch");
+  if ((he = hipEventRecord(pt->top_event, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
+  // the host's record is behind from here until settle(): one more call, and the objects it listed that no pending call had listed
+  pt->top_pending++;
+  if (pt->top_pending_flag.size() != nobj) pt->top_pending_flag.assign(nobj, 0);   // (nothing is pending across a commit)
+  for (uint32_t k = 0; k < n; k++)
+    if (!pt->top_pending_flag[objects[k]]) { pt->top_pending_flag[objects[k]] = 1; pt->top_pending_objects.push_back(objects[k]); }
+  return SRT_OK;
+}
+
+int srt_pt_scene_tree_cost(srt_pt* pt, double* cost) {
+  if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_tree_cost: NULL argument");
+  { const int ready = need_committed(pt, "srt_pt_scene_tree_cost"); if (ready != SRT_OK) return ready; }
+  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_scene_tree_cost: the scene was committed without BVHs, it has no tree");
+  *cost = tree_cost(pt->built.tlas);
+  return SRT_OK;
+}
+
+int srt_pt_top_refit_pending(srt_pt* pt, uint64_t out[2]) {
+  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_top_refit_pending: NULL argument");
+  out[0] = pt->top_pending;
+  out[1] = pt->top_pending_objects.size();
+  return SRT_OK;
+}
+
+int srt_pt_top_refit_count(srt_pt* pt, uint64_t* refits) {
+  if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_top_refit_count: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
+  *refits = pt->top_refits;
+  return SRT_OK;
+}
+
+int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {
+  int st = need_device(pt, "srt_pt_particle_transforms_device");
+  if (st != SRT_OK) return st;
+  if (n == 0) return SRT_OK;
+  if (!d_pos || !d_trans_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_particle_transforms_device: NULL argument");
+  launch_particle_transforms(stream, d_pos, n, scale, d_trans_out);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]) {
+  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_counts: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
+  const FlatScene& F = pt->built.flat;
+  const bool have = pt->committed;
+  out[0] = have ? F.objects.size() : 0;
+  out[1] = have ? F.tris.size() : 0;
+  out[2] = have ? F.nodes.size() - F.tlas_nodes : 0;
+  out[3] = have ? F.blas_recs.size() : 0;
+  out[4] = pt->blas_builds;
+  out[5] = 0;
+  if (have && pt->device >= 0)
+    out[5] = F.nodes.size() * sizeof(Node) + F.tris.size() * sizeof(Tri) + F.tri_nrm.size() * sizeof(TriNrm) + F.tri_packed.size() * sizeof(float) +
+             F.objects.size() * sizeof(Object) + F.lights.size() * sizeof(Light) + F.light_tris.size() * sizeof(LightTri) +
+             F.materials.size() * sizeof(Material) + F.wave_tlas.size() * sizeof(WaveInterior) + F.blas_recs.size() * sizeof(WaveInterior) +
+             F.wave_lazy.size() * sizeof(uint32_t) + F.delta_lights.size() * sizeof(DeltaLight) + pt->env_map.size() * sizeof(float) +
+             pt->idx_words * sizeof(uint32_t);
+  out[6] = pt->bytes_uploaded;
+  out[7] = pt->tri_bytes_uploaded;
+  return SRT_OK;
+}
+
+}  // extern "C"
+
