@@ -431,8 +431,80 @@ int srt_pt_skin_vertices(srt_pt_skin* skin, const float* posed, int flat_normals
 int srt_pt_skin_pose(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
 /* The same with srt_pt_refit_mesh_device in place of the update: skin -> staging -> refit, no BVH<Triangle> build. */
 int srt_pt_skin_pose_refit(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
+/* A RIG for the skin: the hierarchy and the joints' keys, so that a frame's matrices are computed on the device from one float.
+ * What Skeleton::set_time (scene/skeleton.cpp:47-63) and Joint::joint_to_posed (student/skeleton.cpp:26-52) under
+ * Skeleton::joint_to_posed (:106-115) do on the CPU per frame.  Joints are the skin's, in its order: parent[j] is -1 for a root or
+ * the index of a joint in front of j (parents come first, as Skeleton::for_joints visits them); base is Skeleton::base_pos;
+ * rest_pose holds 3 Euler angles (degrees) per joint - Joint::pose, which set_time leaves alone for a joint without keys;
+ * knot_offsets has njoints + 1 entries from 0, joint j's keys being [knot_offsets[j], knot_offsets[j + 1]) of knot_times (strictly
+ * ascending per joint, finite) and knot_quats (xyzw, 4 floats per key, not checked: the rig computes what the reference computes
+ * from them).  Extents are those srt_pt_skin_create took.  SRT_ERR_INVALID: a NULL argument, a parent out of order, offsets that
+ * do not start at 0 or descend, times that do not ascend strictly or are not finite; the skin keeps the rig it had.  Waits for the
+ * device, then uploads the tables once (4 B + 12 B per joint, 12 B of base, the offsets, 20 B per key); a second call replaces
+ * the rig. */
+int srt_pt_skin_set_rig(srt_pt_skin* skin, const int32_t* parent, const float base[3], const float* rest_pose, const uint32_t* knot_offsets,
+                        const float* knot_times, const float* knot_quats);
+/* Skeleton::joint_to_posed(j) for every joint after Skeleton::set_time(t), njoints * 16 floats in Mat4::data order: a keyed joint's
+ * pose is Spline<Quat>::at(t) (geometry/spline.inl:4-15: strict test before the first key, the last value from the last key on,
+ * slerp of lib/quat.h:177-189 in between) through Quat::to_euler (lib/quat.h:124-135, lib/mat4.h:163-199); then from
+ * iter = Mat4::euler(pose_j), for every ancestor from the parent to the root iter = translate(extent) * iter and iter = euler(pose) *
+ * iter; translate(base) in front.  Bit-equal to the reference (x86-64, glibc 2.35's sinf / cosf / acosf / atan2f / hypotf restated;
+ * the sin / cos restatement is valid below 6875 degrees).  The host form runs pt_anim.h compiled for the host - the definition the
+ * kernels are held to - and touches no device.  The device form enqueues two kernels on `stream` (one lane per joint: the poses,
+ * then each joint's own chain, in the reference's order) and returns.  SRT_ERR_STATE without a rig.  The host form only reads
+ * the skin and may run next to other calls; the device forms here and below share the skin's per-joint scratch and its device
+ * matrices with srt_pt_skin_vertices_device / srt_pt_skin_pose*: device-form calls on one skin use one stream at a time, and
+ * srt_pt_skin_set_rig runs with none of them in flight on another thread. */
+int srt_pt_skin_posed(srt_pt_skin* skin, float t, float* posed_out);
+int srt_pt_skin_posed_device(srt_pt_skin* skin, void* stream, float t, float* d_posed_out);
+/* srt_pt_skin_vertices_device, srt_pt_skin_pose and srt_pt_skin_pose_refit with the matrices of time t from the rig: the joint
+ * kernels write M_j = joint_to_posed(j) * inverse_bind_j (Mat4::operator*'s loop) straight into the skin's device matrices, the
+ * skinning kernels read them behind on the same stream.  Nothing is read from host memory and nothing goes up; waits, refusals
+ * and "the committed scene stays as it was on failure" are those of the calls that take `posed`.  SRT_ERR_STATE without a rig. */
+int srt_pt_skin_vertices_at_device(srt_pt_skin* skin, void* stream, float t, int flat_normals, float* d_positions_out, float* d_normals_out);
+int srt_pt_skin_pose_at(srt_pt_skin* skin, void* stream, float t, int flat_normals);
+int srt_pt_skin_pose_refit_at(srt_pt_skin* skin, void* stream, float t, int flat_normals);
 /* Every call on a skin but destroy and counts returns SRT_ERR_STATE once its context's scene was begun or committed again (the
  * skin is stale: destroy it, create another), and SRT_ERR_INVALID for a NULL argument. */
+/* ---- Timelines: the Animate mode's keyframes evaluated on the device ----
+ * What Scene_Object::set_time (scene/object.cpp:68-72) does on the CPU per frame and object: Anim_Pose::at(t) (scene/pose.cpp:54-57)
+ * - Spline<Vec3>::at for position and scale as the fork wrote it (student/spline.inl:5-72: T() without knots, the end values at
+ * and beyond the ends, a missing neighbour mirrored in time and value, tangents ((k2 - p0) / (t2 - t0)) * interval, the Hermite sum
+ * left to right), Spline<Quat>::at for the rotation (geometry/spline.inl:4-15, slerp of lib/quat.h:177-189), Quat::to_euler
+ * (lib/quat.h:124-135, lib/mat4.h:163-199) - and Pose::transform() = translate * euler * scale (scene/pose.cpp:4-10,
+ * lib/mat4.h:382-418, Mat4::rotate's general-axis expressions as written).  The keys do not change between frames: they go up once,
+ * and a frame sends one float.  Results equal the reference's bit for bit (x86-64, no contraction, glibc 2.35's sinf / cosf /
+ * acosf / atan2f / hypotf restated; the sin / cos restatement is valid below 6875 degrees, which to_euler's angles never
+ * reach); where the reference yields NaN (a zero quaternion) so do these, up to the NaN's sign and payload.
+ * A timeline is bound to one context and its committed scene and goes stale as a skin does: every call but destroy returns
+ * SRT_ERR_STATE once the scene was begun or committed again.  Destroy a context's timelines before the context. */
+typedef struct srt_pt_timeline srt_pt_timeline; /* opaque */
+/* `objects`: nobjects insertion indices under srt_pt_repose's rules (meshes, instances, spheres; an area light only under
+ * srt_pt_set_dynamic_lights; no duplicate).  track_offsets has 3 * nobjects + 1 entries from 0: object k's position, rotation
+ * and scale tracks are the knots [track_offsets[3 k + i], track_offsets[3 k + i + 1]) of knot_times and knot_values (4 floats per
+ * knot: xyz_ for position and scale, xyzw for the rotation).  An empty track gives T(): a zero position, Quat(), a ZERO scale.
+ * SRT_ERR_STATE: no committed scene.  SRT_ERR_INVALID: a NULL argument; srt_pt_repose's refusals with their messages; offsets that
+ * do not start at 0 or descend; times of a track that do not ascend strictly or are not finite; an object whose three tracks are
+ * all empty (Splines::any() is false for it: the reference would not move it).  Knot values are not checked: the scene computes
+ * what the reference computes from them.  The scene is not touched.  Uploads the tables once (12 B per object, 20 B per knot). */
+int srt_pt_timeline_create(srt_pt* pt, const uint32_t* objects, uint32_t nobjects, const uint32_t* track_offsets, const float* knot_times,
+                           const float* knot_values, srt_pt_timeline** timeline);
+/* Waits for the device, frees the timeline.  NULL is fine. */
+int srt_pt_timeline_destroy(srt_pt_timeline* timeline);
+/* trans_out[16 k ..] = Pose::transform() of object k's Anim_Pose::at(t), Mat4::data order.  The host form: pt_anim.h compiled for the
+ * host, the definition the kernel is held to; works on a host-only context and touches no device. */
+int srt_pt_timeline_transforms(srt_pt_timeline* timeline, float t, float* trans_out);
+/* The same into a device array of nobjects * 16 floats: one kernel (one lane per object: three binary searches, the splines, the
+ * Euler angles, the products) enqueued on `stream` (a hipStream_t; NULL: the null stream); no wait, nothing uploaded.  A host-only
+ * context validates and then returns SRT_ERR_UNSUPPORTED. */
+int srt_pt_timeline_transforms_device(srt_pt_timeline* timeline, void* stream, float t, float* d_trans_out);
+/* The transforms of time t into the timeline's own device buffer, then srt_pt_repose_refit_device(pt, stream, the timeline's list,
+ * that buffer): ENQUEUE-ONLY under that call's contract, with its first-call work, its ordering rules and the lagging host record.
+ * In the steady state nothing is uploaded at all: the list repeats.  Calls on one timeline use one stream at a time. */
+int srt_pt_timeline_repose_refit(srt_pt_timeline* timeline, void* stream, float t);
+/* The same with srt_pt_repose_device, the rebuild: what a caller uses when srt_pt_scene_tree_cost says a refitted tree has
+ * degraded.  Waits as that call waits. */
+int srt_pt_timeline_repose(srt_pt_timeline* timeline, void* stream, float t);
 /* Where srt_pt_scene_commit runs BVH<Primitive>::build (student/bvh.inl:35-163): device != 0 (default) builds primitive sets of at
  * least min_primitives (default 16384) on the GPU, smaller ones and device == 0 on the host.  Both produce the reference's node
  * arrays and primitive order bit for bit (the candidate planes' std::partition sequence included); SRT_BVH_BUILDER=host in the

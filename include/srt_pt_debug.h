@@ -96,6 +96,14 @@ int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, fl
 int srt_pt_math_atan2(srt_pt* pt, const float* y, const float* x, size_t n, float* out);
 /* The kernels' acosf (glibc 2.35's algorithm restated; Samplers::Hemisphere::Uniform) evaluated on the device. */
 int srt_pt_math_acos(srt_pt* pt, const float* x, size_t n, float* out);
+/* The timelines' hypotf (glibc 2.35's __hypotf restated: evaluated in fp64; Mat4::to_euler, lib/mat4.h:177) evaluated on the device. */
+int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, float* out);
+/* What srt_pt_skin_set_rig validates and srt_pt_skin_posed computes, without a skin or a context (a host-only context has no skins):
+ * Skeleton::set_time(t) and Skeleton::joint_to_posed (student/skeleton.cpp:26-52, 106-115) of a rig given as srt_pt_skin_set_rig
+ * takes it, with the joints' extents (3 floats each) in the place of the skin's.  euler_out (3 floats per joint, may be NULL) takes
+ * Joint::pose after set_time, posed_out 16 floats per joint.  SRT_ERR_INVALID as for srt_pt_skin_set_rig. */
+int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* extents, const float base[3], const float* rest_pose,
+                          const uint32_t* knot_offsets, const float* knot_times, const float* knot_quats, float t, float* euler_out, float* posed_out);
 
 /* The epilogue's expf / powf (glibc 2.35's algorithms restated, FMA build) evaluated on the device. */
 int srt_pt_math_exp(srt_pt* pt, const float* x, size_t n, float* out);

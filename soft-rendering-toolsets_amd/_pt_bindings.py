@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from ctypes import POINTER, c_float, c_int, c_long, c_size_t, c_uint32, c_uint64, c_void_p
 
 import numpy as np
@@ -77,6 +78,20 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_skin_vertices_device.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.srt_pt_skin_vertices.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.srt_pt_skin_pose.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
+    lib.srt_pt_skin_set_rig.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_skin_posed.argtypes = [c_void_p, c_float, c_void_p]
+    lib.srt_pt_skin_posed_device.argtypes = [c_void_p, c_void_p, c_float, c_void_p]
+    lib.srt_pt_skin_vertices_at_device.argtypes = [c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p]
+    lib.srt_pt_skin_pose_at.argtypes = [c_void_p, c_void_p, c_float, c_int]
+    lib.srt_pt_skin_pose_refit_at.argtypes = [c_void_p, c_void_p, c_float, c_int]
+    lib.srt_pt_rig_posed_host.argtypes = [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]
+    lib.srt_pt_math_hypot.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_timeline_create.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_timeline_destroy.argtypes = [c_void_p]
+    lib.srt_pt_timeline_transforms.argtypes = [c_void_p, c_float, c_void_p]
+    lib.srt_pt_timeline_transforms_device.argtypes = [c_void_p, c_void_p, c_float, c_void_p]
+    lib.srt_pt_timeline_repose_refit.argtypes = [c_void_p, c_void_p, c_float]
+    lib.srt_pt_timeline_repose.argtypes = [c_void_p, c_void_p, c_float]
     lib.srt_pt_scene_counts.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_set_bvh_builder.argtypes = [c_void_p, c_int, c_uint32]
     lib.srt_pt_set_stream_slots.argtypes = [c_void_p, c_uint32]
@@ -222,6 +237,44 @@ class Skin:
         posed = self._posed(posed)
         self._check(self._lib, self._lib.srt_pt_skin_pose_refit(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals))))
 
+    def set_rig(self, parent, base, rest_pose, knot_offsets, knot_times, knot_quats) -> None:
+        """srt_pt_skin_set_rig: the hierarchy (parent[j] < j or -1, the joints in the skin's order), Skeleton::base_pos, the rest pose
+        (3 Euler angles in degrees per joint) and the joints' keys as CSR (knot_offsets[njoints + 1], times, xyzw quaternions).
+        Uploaded once; posed_at / pose_at / pose_refit_at then take a time."""
+        parent = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        rest, off = _f32(rest_pose).reshape(-1, 3), np.ascontiguousarray(knot_offsets, np.uint32).reshape(-1)
+        times, quats = _f32(knot_times).reshape(-1), _f32(knot_quats).reshape(-1, 4)
+        if len(parent) != self.njoints or len(rest) != self.njoints or len(off) != self.njoints + 1:
+            raise ValueError(f"{len(parent)} parents, {len(rest)} rest poses and {len(off)} offsets for {self.njoints} joints")
+        if len(times) != len(quats) or (len(off) and int(off.max()) > len(times)):
+            raise ValueError(f"{len(times)} knot times, {len(quats)} quaternions, offsets up to {int(off.max())}")
+        if len(times) == 0:
+            times, quats = np.zeros(1, np.float32), np.zeros((1, 4), np.float32)
+        self._check(self._lib, self._lib.srt_pt_skin_set_rig(self._h, _p(parent), _p(_f32(base).reshape(3)), _p(rest), _p(off), _p(times), _p(quats)))
+
+    def posed_at(self, t: float) -> np.ndarray:
+        """srt_pt_skin_posed: Skeleton::joint_to_posed of every joint after Skeleton::set_time(t), (njoints, 16), computed on the host."""
+        out = np.zeros((self.njoints, 16), np.float32)
+        self._check(self._lib, self._lib.srt_pt_skin_posed(self._h, float(t), _p(out)))
+        return out
+
+    def posed_at_device(self, t: float, d_posed_ptr: int, stream: int = 0) -> None:
+        """srt_pt_skin_posed_device: the same by the joint kernels into a device array of njoints * 16 floats; only enqueues."""
+        self._check(self._lib, self._lib.srt_pt_skin_posed_device(self._h, c_void_p(stream), float(t), c_void_p(d_posed_ptr)))
+
+    def vertices_at_device(self, t: float, d_pos_ptr: int, d_nrm_ptr: int, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_vertices_at_device: vertices_device with the matrices of time t from the rig; nothing goes up."""
+        self._check(self._lib, self._lib.srt_pt_skin_vertices_at_device(self._h, c_void_p(stream), float(t), int(bool(flat_normals)), c_void_p(d_pos_ptr),
+                                                                        c_void_p(d_nrm_ptr)))
+
+    def pose_at(self, t: float, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose_at: pose() with the matrices of time t computed on the device from the rig."""
+        self._check(self._lib, self._lib.srt_pt_skin_pose_at(self._h, c_void_p(stream), float(t), int(bool(flat_normals))))
+
+    def pose_refit_at(self, t: float, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose_refit_at: pose_refit() with the matrices of time t computed on the device from the rig."""
+        self._check(self._lib, self._lib.srt_pt_skin_pose_refit_at(self._h, c_void_p(stream), float(t), int(bool(flat_normals))))
+
     def close(self) -> None:
         if self._h:
             self._lib.srt_pt_skin_destroy(self._h)
@@ -255,9 +308,114 @@ class SkinGroup:
         for k in self.skins:
             k.pose_refit(posed, flat_normals)
 
+    def set_rig(self, parent, base, rest_pose, knot_offsets, knot_times, knot_quats) -> None:
+        for k in self.skins:
+            k.set_rig(parent, base, rest_pose, knot_offsets, knot_times, knot_quats)
+
+    def posed_at(self, t: float) -> np.ndarray:
+        return self.skins[0].posed_at(t)
+
+    def pose_at(self, t: float, flat_normals: bool = False) -> None:
+        """Every rank's skin takes the pose of the same time t."""
+        for k in self.skins:
+            k.pose_at(t, flat_normals)
+
+    def pose_refit_at(self, t: float, flat_normals: bool = False) -> None:
+        for k in self.skins:
+            k.pose_refit_at(t, flat_normals)
+
     def close(self) -> None:
         for k in self.skins:
             k.close()
+
+
+def timeline_tracks(tracks):
+    """(track_offsets, knot_times, knot_values) from either that triple or a sequence with one entry per object, each
+    (position, rotation, scale) with a track given as (times, values) or None: values (n, 3) for position and scale, (n, 4) xyzw
+    quaternions for the rotation."""
+    if isinstance(tracks, tuple) and len(tracks) == 3 and isinstance(tracks[0], np.ndarray) and tracks[0].ndim == 1 and tracks[0].dtype.kind in "ui":
+        off, times, values = tracks
+        return np.ascontiguousarray(off, np.uint32), _f32(times).reshape(-1), _f32(values).reshape(-1, 4)
+    off, times, values = [0], [], []
+    for obj in tracks:
+        if len(obj) != 3:
+            raise ValueError("an object has three tracks: position, rotation, scale")
+        for track in obj:
+            if track is not None:
+                ts, vs = track
+                vs = _f32(vs).reshape(len(ts), -1)
+                times.extend(float(t) for t in ts)
+                values.extend(np.concatenate([v, np.zeros(4 - len(v), np.float32)]) for v in vs)
+            off.append(len(times))
+    return np.array(off, np.uint32), np.array(times, np.float32), np.array(values, np.float32).reshape(-1, 4)
+
+
+class Timeline:
+    """srt_pt_timeline (Pathtracer.create_timeline): the Animate mode's keys of some objects of the committed scene, on the device.
+    A frame is one float: transforms(t) / transforms_device(t) evaluate Anim_Pose::at(t) and Pose::transform() per object,
+    repose_refit(t) / repose(t) hand the result to srt_pt_repose_refit_device / srt_pt_repose_device where it lies.  Closing the
+    Pathtracer closes the timelines it created; close() after that does nothing."""
+
+    def __init__(self, pt, handle, objects):
+        self._pt, self._lib, self._check = pt, pt._lib, pt._check
+        self._h = handle
+        self.objects = objects
+
+    def transforms(self, t: float) -> np.ndarray:
+        """srt_pt_timeline_transforms: (nobjects, 16), computed on the host (works on a host-only context)."""
+        out = np.zeros((len(self.objects), 16), np.float32)
+        self._check(self._lib, self._lib.srt_pt_timeline_transforms(self._h, float(t), _p(out)))
+        return out
+
+    def transforms_device(self, t: float, d_trans_ptr: int, stream: int = 0) -> None:
+        """srt_pt_timeline_transforms_device: the same by the kernel into a device array of nobjects * 16 floats; only enqueues."""
+        self._check(self._lib, self._lib.srt_pt_timeline_transforms_device(self._h, c_void_p(stream), float(t), c_void_p(d_trans_ptr)))
+
+    def repose_refit(self, t: float, stream: int = 0) -> None:
+        """srt_pt_timeline_repose_refit: the poses of time t, then the BVH<Object> refitted in place - enqueue-only, nothing uploaded in
+        the steady state."""
+        self._check(self._lib, self._lib.srt_pt_timeline_repose_refit(self._h, c_void_p(stream), float(t)))
+
+    def repose(self, t: float, stream: int = 0) -> None:
+        """srt_pt_timeline_repose: the poses of time t, then the BVH<Object> rebuilt (srt_pt_repose_device)."""
+        self._check(self._lib, self._lib.srt_pt_timeline_repose(self._h, c_void_p(stream), float(t)))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.srt_pt_timeline_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self._pt._ctx:                # (Pathtracer.close() has closed the timelines it made: after it there is nothing left to free)
+                self.close()
+        except Exception:
+            pass
+
+
+class TimelineGroup:
+    """PathtracerGroup.create_timeline: one Timeline per rank (the scene is replicated); all ranks get the same t."""
+
+    def __init__(self, timelines):
+        self.timelines = timelines
+
+    def transforms(self, t: float) -> np.ndarray:
+        return self.timelines[0].transforms(t)
+
+    def repose_refit(self, t: float, stream: int = 0) -> None:
+        """Timeline.repose_refit on every rank; like PathtracerGroup.repose_refit_device each member is settled before this returns."""
+        for tl in self.timelines:
+            tl.repose_refit(t, stream)
+        for tl in self.timelines:
+            tl._check(tl._lib, tl._lib.srt_pt_sync(tl._pt._ctx))
+
+    def repose(self, t: float, stream: int = 0) -> None:
+        for tl in self.timelines:
+            tl.repose(t, stream)
+
+    def close(self) -> None:
+        for tl in self.timelines:
+            tl.close()
 
 
 class Scene:
@@ -300,9 +458,15 @@ class Pathtracer:
         self.total_epochs = self.completed_epochs = 0
         self.seed = 0
         self._sample_cursor = 0
+        self._timelines = []                             # weak references: close() destroys the live ones before the context goes
 
     def close(self) -> None:
         if self._ctx:
+            for ref in self._timelines:
+                tl = ref()
+                if tl is not None:
+                    tl.close()
+            self._timelines = []
             if not self._borrowed:
                 self._lib.srt_pt_destroy(self._ctx)
             self._ctx = c_void_p()
@@ -453,6 +617,29 @@ class Pathtracer:
         h = c_void_p()
         self._check(self._lib, self._lib.srt_pt_skin_create(self._ctx, int(index), _p(pos), _p(nrm), len(pos), _p(J), len(J), ctypes.byref(h)))
         return Skin(self, h, len(pos), len(J))
+
+    def create_timeline(self, objects, tracks) -> Timeline:
+        """srt_pt_timeline_create: keys for the objects with these insertion indices of the committed scene (timeline_tracks(..) says
+        how `tracks` may be given); the tables go up once."""
+        idx = np.ascontiguousarray(objects, np.uint32).reshape(-1)
+        off, times, values = timeline_tracks(tracks)
+        if len(off) != 3 * len(idx) + 1 or len(times) != len(values) or int(off.max()) > len(times):
+            raise ValueError(f"{len(idx)} objects, {len(off)} offsets up to {int(off.max())}, {len(times)} knot times, {len(values)} knot values")
+        if len(times) == 0:
+            times, values = np.zeros(1, np.float32), np.zeros((1, 4), np.float32)
+        h = c_void_p()
+        self._check(self._lib, self._lib.srt_pt_timeline_create(self._ctx, _p(idx if len(idx) else np.zeros(1, np.uint32)), len(idx), _p(off), _p(times), _p(values),
+                                                                ctypes.byref(h)))
+        tl = Timeline(self, h, idx)
+        self._timelines = [r for r in self._timelines if r() is not None] + [weakref.ref(tl)]
+        return tl
+
+    def math_hypot(self, x, y):
+        """srt_pt_math_hypot: the kernels' hypotf on the device."""
+        x, y = _f32(x).reshape(-1), _f32(y).reshape(-1)
+        out = np.zeros(len(x), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_hypot(self._ctx, _p(x), _p(y), len(x), _p(out)))
+        return out
 
     def scene_counts(self) -> dict:
         """srt_pt_scene_counts: what the scene stores, the BVH<Triangle> builds so far and the bytes uploaded, and srt_pt_refit_count's
@@ -870,6 +1057,18 @@ class PathtracerGroup:
                 k.close()
             raise
         return SkinGroup(skins)
+
+    def create_timeline(self, objects, tracks) -> TimelineGroup:
+        """One timeline per rank; TimelineGroup.repose_refit / repose give every rank the same t."""
+        made = []
+        try:
+            for m in self.members:
+                made.append(m.create_timeline(objects, tracks))
+        except Exception:
+            for tl in made:
+                tl.close()
+            raise
+        return TimelineGroup(made)
 
     def scene_counts(self) -> list:
         """Every member's Pathtracer.scene_counts(), by rank (the scene is replicated)."""

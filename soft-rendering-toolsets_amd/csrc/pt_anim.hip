@@ -1,0 +1,78 @@
+// The Animate mode's timeline on the device: the launches around the per-object and per-joint functions of pt_anim.h.  One lane
+// per object or joint.  The kernels are small and latency-bound - a lane's work is three binary searches over its own knots, a
+// handful of transcendentals and a few 4 x 4 products from registers - and their point is that the frame's transforms are made
+// where the refit reads them: nothing here waits for the host or reads host memory.  Knot tables are CSR, read at per-lane
+// indices; every index a lane forms lies inside its own tracks [offsets[i], offsets[i + 1]), which the host validated against the
+// table sizes before the upload.  The chain of a joint is walked by its own lane, parent by parent, in the reference's order: a
+// parallel prefix over the hierarchy would re-associate float matrix products, which do not associate.
+#include <hip/hip_runtime.h>
+
+#include "pt_anim.h"
+
+namespace srt {
+namespace {
+
+constexpr uint32_t kBlock = 64;           // one wave per block: a rig has a few dozen joints, a timeline a few thousand objects
+
+__global__ __launch_bounds__(kBlock) void anim_pose_kernel(const uint32_t* __restrict__ track_offsets, const float* __restrict__ times,
+                                                          const float* __restrict__ values, uint32_t nobjects, float t, float* __restrict__ trans_out) {
+  const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nobjects) return;
+  float m[16];
+  anim_object_transform(track_offsets, times, values, k, t, nullptr, m);
+  for (int i = 0; i < 16; i++) trans_out[16 * (size_t)k + i] = m[i];
+}
+
+__global__ __launch_bounds__(kBlock) void anim_joint_local_kernel(const float* __restrict__ rest_pose, const uint32_t* __restrict__ knot_offsets,
+                                                                 const float* __restrict__ times, const float* __restrict__ quats, uint32_t njoints, float t,
+                                                                 float* __restrict__ local) {
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= njoints) return;
+  float m[16];
+  anim_mat4_euler(anim_joint_pose(rest_pose, knot_offsets, times, quats, j, t), m);
+  for (int i = 0; i < 16; i++) local[16 * (size_t)j + i] = m[i];
+}
+
+__global__ __launch_bounds__(kBlock) void anim_joint_chain_kernel(const int32_t* __restrict__ parent, const float* __restrict__ cap,
+                                                                 const float* __restrict__ base, const float* __restrict__ local, uint32_t njoints,
+                                                                 const float* __restrict__ inv, float* __restrict__ mats, float* __restrict__ posed_out) {
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= njoints) return;
+  float posed[16], m[16];
+  anim_joint_to_posed(parent, cap, base, local, njoints, j, posed);
+  if (mats) {
+    skin_mat4_mul(posed, inv + 16 * (size_t)j, m);                   // M_j = joint_to_posed(j) * inverse(joint_to_bind(j))
+    for (int i = 0; i < 16; i++) mats[16 * (size_t)j + i] = m[i];
+  }
+  if (posed_out)
+    for (int i = 0; i < 16; i++) posed_out[16 * (size_t)j + i] = posed[i];
+}
+
+__global__ __launch_bounds__(256) void anim_hypot_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = srt_hypotf(x[i], y[i]);
+}
+
+dim3 grid_for(uint32_t n) { return dim3((n + kBlock - 1u) / kBlock); }
+
+}  // namespace
+
+void launch_anim_pose(void* stream, const uint32_t* d_track_offsets, const float* d_times, const float* d_values, uint32_t nobjects, float t, float* d_trans_out) {
+  if (!nobjects) return;
+  anim_pose_kernel<<<grid_for(nobjects), dim3(kBlock), 0, (hipStream_t)stream>>>(d_track_offsets, d_times, d_values, nobjects, t, d_trans_out);
+}
+
+void launch_anim_joints(void* stream, const int32_t* d_parent, const float* d_cap, const float* d_base, const float* d_rest_pose, const uint32_t* d_knot_offsets,
+                        const float* d_times, const float* d_quats, uint32_t njoints, float t, float* d_local, const float* d_inv, float* d_mats,
+                        float* d_posed_out) {
+  if (!njoints) return;
+  anim_joint_local_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_rest_pose, d_knot_offsets, d_times, d_quats, njoints, t, d_local);
+  anim_joint_chain_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_parent, d_cap, d_base, d_local, njoints, d_inv, d_mats, d_posed_out);
+}
+
+void launch_anim_hypot(void* stream, const float* d_x, const float* d_y, size_t n, float* d_out) {
+  if (!n) return;
+  anim_hypot_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(d_x, d_y, n, d_out);
+}
+
+}  // namespace srt

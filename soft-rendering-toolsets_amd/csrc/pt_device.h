@@ -223,11 +223,16 @@ struct Rng {
   SRT_DEV bool coin(float p) { return unit() < p; }
 };
 
+// The SRT-MATH functions below are host functions too (SRT_HD): pt_anim.h evaluates timelines with them on both sides.  f2u / u2f
+// are the bit casts for both compilers.
+#define SRT_HD __host__ __device__ __forceinline__
+SRT_HD uint32_t f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+SRT_HD float u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 // ---------------------------------------------------------------------------------------------------
 // SRT-MATH v2: glibc 2.35 sinf/cosf (sysdeps/ieee754/flt-32/{s_sinf,s_cosf}.c, sincosf.h, sincosf_data.c)
 // evaluated in fp64 without FMA.  Valid for |x| < 120 (the renderer uses [0, 2pi] and [-1, 1]).
 // ---------------------------------------------------------------------------------------------------
-SRT_DEV float sincos_poly(double x, double x2, bool negated_cos_table, int n) {
+SRT_HD float sincos_poly(double x, double x2, bool negated_cos_table, int n) {
   const double sgn = negated_cos_table ? -1.0 : 1.0;  // table[1] negates the cosine coefficients only
   if ((n & 1) == 0) {
     const double x3 = x * x2;
@@ -244,9 +249,9 @@ SRT_DEV float sincos_poly(double x, double x2, bool negated_cos_table, int n) {
     return (float)(c + x6 * c2);
   }
 }
-SRT_DEV float srt_sincosf(float y, int want_cos) {
+SRT_HD float srt_sincosf(float y, int want_cos) {
   double x = (double)y;
-  const uint32_t top = (__float_as_uint(y) >> 20) & 0x7ffu;
+  const uint32_t top = (f2u(y) >> 20) & 0x7ffu;
   if (top < 0x3f4u) {                      // abstop12(y) < abstop12(pi/4 = 0x1.921FB6p-1f)
     if (top < 0x398u) return want_cos ? 1.0f : y;   // |y| < 2^-12
     return sincos_poly(x, x * x, false, want_cos);
@@ -259,12 +264,12 @@ SRT_DEV float srt_sincosf(float y, int want_cos) {
     const double s = (q == 1 || q == 2) ? -1.0 : 1.0;
     return sincos_poly(x * s, x * x, (n & 2) != 0, n ^ want_cos);
   }
-  return __uint_as_float(0x7fc00000u);
+  return u2f(0x7fc00000u);
 }
 // cosf(y) and sinf(y) together: both glibc routines reduce y the same way, so the reduction is shared.
-SRT_DEV void srt_sincosf2(float y, float& c, float& s) {
+SRT_HD void srt_sincosf2(float y, float& c, float& s) {
   double x = (double)y;
-  const uint32_t top = (__float_as_uint(y) >> 20) & 0x7ffu;
+  const uint32_t top = (f2u(y) >> 20) & 0x7ffu;
   if (top < 0x3f4u) {
     if (top < 0x398u) { c = 1.0f; s = y; return; }
     const double x2 = x * x;
@@ -283,17 +288,17 @@ SRT_DEV void srt_sincosf2(float y, float& c, float& s) {
     s = sincos_poly(xs, x2, (n & 2) != 0, n);
     return;
   }
-  c = s = __uint_as_float(0x7fc00000u);
+  c = s = u2f(0x7fc00000u);
 }
 // ---------------------------------------------------------------------------------------------------
 // SRT-MATH v2, atan2f: glibc 2.35 __ieee754_atan2f / __atanf (sysdeps/ieee754/flt-32/e_atan2f.c, s_atanf.c — the
 // fdlibm float code), fp32 throughout, no FMA.  Bit-identical to the host libm on 2e8 arguments (random bit
 // patterns and the renderer's range); used by Spot_Light::sample (rays/light.cpp:22).
 // ---------------------------------------------------------------------------------------------------
-SRT_DEV float srt_atanf(float x) {
+SRT_HD float srt_atanf(float x) {
   const float atanhi[4] = {4.6364760399e-01f, 7.8539812565e-01f, 9.8279368877e-01f, 1.5707962513e+00f};
   const float atanlo[4] = {5.0121582440e-09f, 3.7748947079e-08f, 3.4473217170e-08f, 7.5497894159e-08f};
-  const int32_t hx = (int32_t)__float_as_uint(x), ix = hx & 0x7fffffff;
+  const int32_t hx = (int32_t)f2u(x), ix = hx & 0x7fffffff;
   if (ix >= 0x4c000000) {                              // |x| >= 2^25
     if (ix > 0x7f800000) return x + x;                 // NaN
     return (hx > 0) ? (atanhi[3] + atanlo[3]) : (-atanhi[3] - atanlo[3]);
@@ -324,11 +329,11 @@ SRT_DEV float srt_atanf(float x) {
   return (hx < 0) ? -r : r;
 }
 
-SRT_DEV float srt_atan2f(float y, float x) {
+SRT_HD float srt_atan2f(float y, float x) {
   const float tiny = 1.0e-30f, pi_o_4 = 7.8539818525e-01f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f,
               pi_lo = -8.7422776573e-08f;
-  const int32_t hx = (int32_t)__float_as_uint(x), ix = hx & 0x7fffffff;
-  const int32_t hy = (int32_t)__float_as_uint(y), iy = hy & 0x7fffffff;
+  const int32_t hx = (int32_t)f2u(x), ix = hx & 0x7fffffff;
+  const int32_t hy = (int32_t)f2u(y), iy = hy & 0x7fffffff;
   if (ix > 0x7f800000 || iy > 0x7f800000) return x + y;   // NaN
   if (hx == 0x3f800000) return srt_atanf(y);               // x = 1
   const int32_t m = ((hy >> 31) & 1) | ((hx >> 30) & 2);   // 2 * sign(x) + sign(y)
@@ -346,16 +351,16 @@ SRT_DEV float srt_atan2f(float y, float x) {
   else if (hx < 0 && k < -60) z = 0.0f;                    // |y| / x < -2^60
   else z = srt_atanf(fabsf(y / x));
   if (m == 0) return z;
-  if (m == 1) return __uint_as_float(__float_as_uint(z) ^ 0x80000000u);
+  if (m == 1) return u2f(f2u(z) ^ 0x80000000u);
   if (m == 2) return pi - (z - pi_lo);
   return (z - pi_lo) - pi;
 }
 
 // SRT-MATH v2, acosf: glibc 2.35 __ieee754_acosf (sysdeps/ieee754/flt-32/e_acosf.c, fdlibm's float code), fp32, no FMA.
 // Bit-identical to the host libm on 7e8 arguments covering [-1, 1]; used by Samplers::Hemisphere::Uniform.
-SRT_DEV float srt_acosf(float x) {
+SRT_HD float srt_acosf(float x) {
   const float pi = 3.1415925026e+00f, pio2_hi = 1.5707962513e+00f, pio2_lo = 7.5497894159e-08f;
-  const int32_t hx = (int32_t)__float_as_uint(x), ix = hx & 0x7fffffff;
+  const int32_t hx = (int32_t)f2u(x), ix = hx & 0x7fffffff;
   if (ix == 0x3f800000) return (hx > 0) ? 0.0f : pi + 2.0f * pio2_lo;
   if (ix > 0x3f800000) return (x - x) / (x - x);
   if (ix < 0x3f000000 && ix <= 0x23000000) return pio2_hi + pio2_lo;       // |x| < 2^-57
@@ -370,7 +375,7 @@ SRT_DEV float srt_acosf(float x) {
     const float w = r * s - pio2_lo;
     return pi - 2.0f * (s + w);
   }
-  const float df = __uint_as_float(__float_as_uint(s) & 0xfffff000u);     // x > 0.5
+  const float df = u2f(f2u(s) & 0xfffff000u);     // x > 0.5
   const float c = (z - df * df) / (s + df);
   const float w = r * s + c;
   return 2.0f * (df + w);

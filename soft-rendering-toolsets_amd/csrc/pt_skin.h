@@ -65,7 +65,7 @@ inline void skin_mat4_inverse(const float* m, float* r) {
 
 // Mat4::operator* (lib/mat4.h:136-147), ret = a * b: ret[i][j] = sum over k, from 0.0f, of b[i][k] * a[k][j] - the loop runs
 // over the RIGHT operand's column i and the left operand's row j.
-inline void skin_mat4_mul(const float* a, const float* b, float* ret) {
+__host__ __device__ inline void skin_mat4_mul(const float* a, const float* b, float* ret) {
   for (int i = 0; i < 4; i++)
     for (int j = 0; j < 4; j++) {
       float s = 0.0f;

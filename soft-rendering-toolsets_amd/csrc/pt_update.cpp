@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "pt_anim.h"
 #include "pt_context.h"
 #include "pt_light_update.h"
 #include "pt_mesh_update.h"
@@ -29,6 +30,25 @@ struct srt_pt_skin {
   uint32_t *d_off = nullptr, *d_jidx = nullptr, *d_last = nullptr;
   float* d_w = nullptr;
   float *d_pos_out = nullptr, *d_nrm_out = nullptr;     // srt_pt_skin_pose's staging
+  // srt_pt_skin_set_rig: the hierarchy and the joints' keys, on both sides; d_local: Mat4::euler(pose) per joint, the frame's
+  bool rigged = false;
+  std::vector<int32_t> parent;
+  std::vector<float> cap, rest_pose, knot_times, knot_quats;   // cap: {extent, radius} per joint, from srt_pt_skin_create
+  std::vector<uint32_t> knot_offsets;
+  float base[3] = {0.0f, 0.0f, 0.0f};
+  int32_t* d_parent = nullptr;
+  uint32_t* d_knot_offsets = nullptr;
+  float *d_base = nullptr, *d_rest_pose = nullptr, *d_knot_times = nullptr, *d_knot_quats = nullptr, *d_local = nullptr;
+};
+
+// ---- srt_pt_timeline: Anim_Pose::at(t) and Pose::transform() of listed objects (pt_anim.h, pt_anim.hip) ----
+struct srt_pt_timeline {
+  srt_pt* pt = nullptr;
+  uint64_t generation = 0;                  // pt->scene_generation at creation
+  std::vector<uint32_t> objects, track_offsets;           // insertion indices; 3 tracks per object, CSR
+  std::vector<float> knot_times, knot_values;
+  uint32_t* d_track_offsets = nullptr;
+  float *d_knot_times = nullptr, *d_knot_values = nullptr, *d_trans = nullptr;   // d_trans: the frame's transforms, 16 floats per object
 };
 
 namespace {
@@ -419,11 +439,21 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Mes
   return written(pt, write());
 }
 
+void skin_free_rig(srt_pt_skin* k) {
+  for (void* p : {(void*)k->d_parent, (void*)k->d_knot_offsets, (void*)k->d_base, (void*)k->d_rest_pose, (void*)k->d_knot_times, (void*)k->d_knot_quats,
+                  (void*)k->d_local})
+    if (p) (void)hipFree(p);
+  k->d_parent = nullptr; k->d_knot_offsets = nullptr;
+  k->d_base = k->d_rest_pose = k->d_knot_times = k->d_knot_quats = k->d_local = nullptr;
+  k->rigged = false;
+}
+
 void skin_free(srt_pt_skin* k) {
   if (k->pt && k->pt->device >= 0) (void)hipSetDevice(k->pt->device);
   for (void* p : {(void*)k->d_pos, (void*)k->d_nrm, (void*)k->d_inv, (void*)k->d_cap, (void*)k->d_mats, (void*)k->d_off, (void*)k->d_jidx, (void*)k->d_last,
                   (void*)k->d_w, (void*)k->d_pos_out, (void*)k->d_nrm_out})
     if (p) (void)hipFree(p);
+  skin_free_rig(k);
   delete k;
 }
 
@@ -431,7 +461,8 @@ void skin_free(srt_pt_skin* k) {
 int skin_build(srt_pt_skin* k, const float* bind_positions, const float* bind_normals, const srt_pt_skin_joint* joints) {
   srt_pt* pt = k->pt;
   const size_t vfloats = 3 * (size_t)k->nverts;
-  std::vector<float> cap(4 * (size_t)k->njoints);
+  std::vector<float>& cap = k->cap;
+  cap.resize(4 * (size_t)k->njoints);
   for (uint32_t j = 0; j < k->njoints; j++) {
     skin_mat4_inverse(joints[j].bind, &k->inv[16 * (size_t)j]);
     for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = joints[j].extent[a];
@@ -487,6 +518,13 @@ int skin_usable(const srt_pt_skin* k, const char* what) {
   return SRT_OK;
 }
 
+// The skinning kernels on s, behind whatever wrote the frame's matrices into d_mats there.
+void skin_launch(srt_pt_skin* k, hipStream_t s, int flat_normals, float* d_pos_out, float* d_nrm_out) {
+  launch_skin_vertices(s, k->d_pos, k->d_nrm, k->nverts, k->d_mats, k->njoints, k->d_off, k->d_jidx, k->d_w, d_pos_out, flat_normals ? nullptr : d_nrm_out);
+  if (flat_normals)
+    launch_skin_flat_normals(s, d_pos_out, k->d_nrm, k->pt->d_idx + k->pt->idx_off[k->object], k->ntri, k->d_last, k->nverts, d_nrm_out);
+}
+
 // Enqueues the frame's matrices and the skinning kernels on s, for a skin that is usable.
 int skin_enqueue(srt_pt_skin* k, const char* what, hipStream_t s, const float* posed, int flat_normals, float* d_pos_out, float* d_nrm_out) {
   const int usable = skin_usable(k, what);
@@ -495,9 +533,31 @@ int skin_enqueue(srt_pt_skin* k, const char* what, hipStream_t s, const float* p
   for (uint32_t j = 0; j < k->njoints; j++) skin_mat4_mul(posed + 16 * (size_t)j, &k->inv[16 * (size_t)j], &k->mats[16 * (size_t)j]);
   SRT_HIP(hipMemcpyAsync(k->d_mats, k->mats.data(), k->mats.size() * sizeof(float), hipMemcpyHostToDevice, s));   // 64 B per joint
   k->pt->bytes_uploaded += k->mats.size() * sizeof(float);
-  launch_skin_vertices(s, k->d_pos, k->d_nrm, k->nverts, k->d_mats, k->njoints, k->d_off, k->d_jidx, k->d_w, d_pos_out, flat_normals ? nullptr : d_nrm_out);
-  if (flat_normals)
-    launch_skin_flat_normals(s, d_pos_out, k->d_nrm, k->pt->d_idx + k->pt->idx_off[k->object], k->ntri, k->d_last, k->nverts, d_nrm_out);
+  skin_launch(k, s, flat_normals, d_pos_out, d_nrm_out);
+  return SRT_OK;
+}
+
+int skin_rigged(const srt_pt_skin* k, const char* what) {
+  const int usable = skin_usable(k, what);
+  if (usable != SRT_OK) return usable;
+  if (!k->rigged) return srt::fail(SRT_ERR_STATE, "%s: the skin has no rig (srt_pt_skin_set_rig)", what);
+  return SRT_OK;
+}
+
+// The joint kernels for time t on s: Mat4::euler(pose) per joint, then the chains - into the skin's matrices (to_mats) and / or d_posed_out.
+void rig_launch(srt_pt_skin* k, hipStream_t s, float t, bool to_mats, float* d_posed_out) {
+  launch_anim_joints(s, k->d_parent, k->d_cap, k->d_base, k->d_rest_pose, k->d_knot_offsets, k->d_knot_times, k->d_knot_quats, k->njoints, t, k->d_local,
+                     k->d_inv, to_mats ? k->d_mats : nullptr, d_posed_out);
+}
+
+// The same with the matrices from the rig at time t: the joint kernels write them where the skinning kernels read them; nothing goes up.
+int skin_enqueue_at(srt_pt_skin* k, const char* what, hipStream_t s, float t, int flat_normals, float* d_pos_out, float* d_nrm_out) {
+  const int rigged = skin_rigged(k, what);
+  if (rigged != SRT_OK) return rigged;
+  SRT_HIP(hipSetDevice(k->pt->device));
+  rig_launch(k, s, t, true, nullptr);
+  skin_launch(k, s, flat_normals, d_pos_out, d_nrm_out);
+  SRT_HIP(hipGetLastError());
   return SRT_OK;
 }
 
@@ -508,6 +568,56 @@ int skin_pose(srt_pt_skin* skin, const char* what, void* stream, const float* po
   const int st = skin_enqueue(skin, what, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out);
   if (st != SRT_OK) return st;
   return mesh_call(skin->pt, what, (hipStream_t)stream, skin->object, {nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, {}, {}}, skin->nverts);
+}
+
+int skin_pose_at(srt_pt_skin* skin, const char* what, void* stream, float t, int flat_normals, decltype(update_mesh)* mesh_call) {
+  if (!skin) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_enqueue_at(skin, what, (hipStream_t)stream, t, flat_normals, skin->d_pos_out, skin->d_nrm_out);
+  if (st != SRT_OK) return st;
+  return mesh_call(skin->pt, what, (hipStream_t)stream, skin->object, {nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, {}, {}}, skin->nverts);
+}
+
+// A device copy of n elements made once (blocking), counted as uploaded.
+template <typename T>
+int upload_table(srt_pt* pt, T** dst, const T* src, size_t n) {
+  SRT_HIP(hipMalloc((void**)dst, (n ? n : 1) * sizeof(T)));
+  if (n) SRT_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+  pt->bytes_uploaded += n * sizeof(T);
+  return SRT_OK;
+}
+
+void timeline_free(srt_pt_timeline* tl) {
+  if (tl->pt && tl->pt->device >= 0) (void)hipSetDevice(tl->pt->device);
+  for (void* p : {(void*)tl->d_track_offsets, (void*)tl->d_knot_times, (void*)tl->d_knot_values, (void*)tl->d_trans})
+    if (p) (void)hipFree(p);
+  delete tl;
+}
+
+int timeline_usable(const srt_pt_timeline* tl, const char* what) {
+  if (!tl) return srt::fail(SRT_ERR_INVALID, "%s: NULL timeline", what);
+  if (!tl->pt->committed || tl->generation != tl->pt->scene_generation)
+    return srt::fail(SRT_ERR_STATE, "%s: the timeline is stale - its context's scene was begun or committed again after srt_pt_timeline_create", what);
+  return SRT_OK;
+}
+
+// Usable, on a device context, and the transforms of time t enqueued on s into the timeline's own buffer.
+int timeline_enqueue(srt_pt_timeline* tl, const char* what, hipStream_t s, float t, float* d_out) {
+  const int usable = timeline_usable(tl, what);
+  if (usable != SRT_OK) return usable;
+  if (tl->pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the kernels run on the device only; this context is host-only (srt_pt_timeline_transforms is the host form)", what);
+  SRT_HIP(hipSetDevice(tl->pt->device));
+  launch_anim_pose(s, tl->d_track_offsets, tl->d_knot_times, tl->d_knot_values, (uint32_t)tl->objects.size(), t, d_out);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+// What srt_pt_skin_set_rig refuses about its arrays, as a message (empty: nothing).
+std::string check_rig(uint32_t njoints, const int32_t* parent, const uint32_t* knot_offsets, const float* knot_times) {
+  for (uint32_t j = 0; j < njoints; j++)
+    if (parent[j] < -1 || parent[j] >= (int32_t)j)
+      return "joint " + std::to_string(j) + " has parent " + std::to_string(parent[j]) + " (-1, or a joint in front of it: parents come first, as Skeleton::for_joints visits them)";
+  return anim_check_tracks(knot_offsets, njoints, 1, knot_times, false, "joint");
 }
 
 std::vector<Mat4> matrices(const float* trans, uint32_t n) {
@@ -1051,6 +1161,173 @@ int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects
   for (uint32_t k = 0; k < n; k++)
     if (!pt->top_pending_flag[objects[k]]) { pt->top_pending_flag[objects[k]] = 1; pt->top_pending_objects.push_back(objects[k]); }
   return SRT_OK;
+}
+
+int srt_pt_skin_set_rig(srt_pt_skin* skin, const int32_t* parent, const float base[3], const float* rest_pose, const uint32_t* knot_offsets,
+                        const float* knot_times, const float* knot_quats) {
+  const char* what = "srt_pt_skin_set_rig";
+  if (!skin || !parent || !base || !rest_pose || !knot_offsets || !knot_times || !knot_quats) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st = skin_usable(skin, what);
+  if (st != SRT_OK) return st;
+  const uint32_t nj = skin->njoints;
+  const std::string refused = check_rig(nj, parent, knot_offsets, knot_times);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  srt_pt* pt = skin->pt;
+  SRT_HIP(quiesce(pt));                                   // (a rig set before may still be read)
+  skin_free_rig(skin);
+  const size_t nk = knot_offsets[nj];
+  skin->parent.assign(parent, parent + nj);
+  skin->rest_pose.assign(rest_pose, rest_pose + 3 * (size_t)nj);
+  skin->knot_offsets.assign(knot_offsets, knot_offsets + nj + 1);
+  skin->knot_times.assign(knot_times, knot_times + nk);
+  skin->knot_quats.assign(knot_quats, knot_quats + 4 * nk);
+  std::memcpy(skin->base, base, sizeof skin->base);
+  if ((st = upload_table(pt, &skin->d_parent, skin->parent.data(), nj)) || (st = upload_table(pt, &skin->d_base, skin->base, 3)) ||
+      (st = upload_table(pt, &skin->d_rest_pose, skin->rest_pose.data(), skin->rest_pose.size())) ||
+      (st = upload_table(pt, &skin->d_knot_offsets, skin->knot_offsets.data(), skin->knot_offsets.size())) ||
+      (st = upload_table(pt, &skin->d_knot_times, skin->knot_times.data(), nk)) || (st = upload_table(pt, &skin->d_knot_quats, skin->knot_quats.data(), 4 * nk))) {
+    skin_free_rig(skin);
+    return st;
+  }
+  if (hipMalloc(&skin->d_local, 16 * (size_t)nj * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    skin_free_rig(skin);
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+  }
+  skin->rigged = true;
+  return SRT_OK;
+}
+
+int srt_pt_skin_posed(srt_pt_skin* skin, float t, float* posed_out) {
+  if (!skin || !posed_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_posed: NULL argument");
+  const int st = skin_rigged(skin, "srt_pt_skin_posed");
+  if (st != SRT_OK) return st;
+  std::vector<float> local(16 * (size_t)skin->njoints);   // Mat4::euler(pose) per joint: the call's own, so the host form only reads the skin
+  anim_rig_posed_host(skin->parent.data(), skin->cap.data(), skin->base, skin->rest_pose.data(), skin->knot_offsets.data(), skin->knot_times.data(),
+                      skin->knot_quats.data(), skin->njoints, t, nullptr, local.data(), posed_out);
+  return SRT_OK;
+}
+
+int srt_pt_skin_posed_device(srt_pt_skin* skin, void* stream, float t, float* d_posed_out) {
+  if (!skin || !d_posed_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_posed_device: NULL argument");
+  const int st = skin_rigged(skin, "srt_pt_skin_posed_device");
+  if (st != SRT_OK) return st;
+  SRT_HIP(hipSetDevice(skin->pt->device));
+  rig_launch(skin, (hipStream_t)stream, t, false, d_posed_out);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_skin_vertices_at_device(srt_pt_skin* skin, void* stream, float t, int flat_normals, float* d_positions_out, float* d_normals_out) {
+  if (!skin || !d_positions_out || !d_normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices_at_device: NULL argument");
+  return skin_enqueue_at(skin, "srt_pt_skin_vertices_at_device", (hipStream_t)stream, t, flat_normals, d_positions_out, d_normals_out);
+}
+
+int srt_pt_skin_pose_at(srt_pt_skin* skin, void* stream, float t, int flat_normals) {
+  return skin_pose_at(skin, "srt_pt_skin_pose_at", stream, t, flat_normals, update_mesh);
+}
+
+int srt_pt_skin_pose_refit_at(srt_pt_skin* skin, void* stream, float t, int flat_normals) {
+  return skin_pose_at(skin, "srt_pt_skin_pose_refit_at", stream, t, flat_normals, refit_mesh);
+}
+
+int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* extents, const float base[3], const float* rest_pose,
+                          const uint32_t* knot_offsets, const float* knot_times, const float* knot_quats, float t, float* euler_out, float* posed_out) {
+  const char* what = "srt_pt_rig_posed_host";
+  if (!parent || !extents || !base || !rest_pose || !knot_offsets || !knot_times || !knot_quats || !posed_out) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const std::string refused = check_rig(njoints, parent, knot_offsets, knot_times);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  std::vector<float> cap(4 * (size_t)njoints, 0.0f), local(16 * (size_t)njoints);
+  for (uint32_t j = 0; j < njoints; j++)
+    for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = extents[3 * (size_t)j + a];
+  anim_rig_posed_host(parent, cap.data(), base, rest_pose, knot_offsets, knot_times, knot_quats, njoints, t, euler_out, local.data(), posed_out);
+  return SRT_OK;
+}
+
+int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, float* out) {
+  int st = need_device(pt, "srt_pt_math_hypot");
+  if (st != SRT_OK) return st;
+  if (n == 0) return SRT_OK;
+  if (!x || !y || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_hypot: NULL argument");
+  float* d = nullptr;
+  SRT_HIP(hipMalloc(&d, 3 * n * sizeof(float)));
+  hipError_t e = hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + n, y, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_anim_hypot(pt->stream, d, d + n, n, d + 2 * n);
+    e = hipMemcpyAsync(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost, pt->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(pt->stream);
+  (void)hipFree(d);
+  SRT_HIP(e);
+  return SRT_OK;
+}
+
+int srt_pt_timeline_create(srt_pt* pt, const uint32_t* objects, uint32_t nobjects, const uint32_t* track_offsets, const float* knot_times,
+                           const float* knot_values, srt_pt_timeline** timeline) {
+  const char* what = "srt_pt_timeline_create";
+  if (timeline) *timeline = nullptr;
+  if (!pt || !objects || !track_offsets || !knot_times || !knot_values || !timeline) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st;
+  if ((st = need_committed(pt, what))) return st;
+  std::string refused = check_repose_list(pt->built, objects, nobjects);
+  if (refused.empty()) refused = anim_check_tracks(track_offsets, nobjects, 3, knot_times, true, "object");
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  srt_pt_timeline* tl = new (std::nothrow) srt_pt_timeline;
+  if (!tl) return srt::fail(SRT_ERR_INVALID, "out of host memory");
+  const size_t nk = track_offsets[3 * (size_t)nobjects];
+  tl->pt = pt; tl->generation = pt->scene_generation;
+  tl->objects.assign(objects, objects + nobjects);
+  tl->track_offsets.assign(track_offsets, track_offsets + 3 * (size_t)nobjects + 1);
+  tl->knot_times.assign(knot_times, knot_times + nk);
+  tl->knot_values.assign(knot_values, knot_values + 4 * nk);
+  if (pt->device >= 0) {
+    auto up = [&]() -> int {
+      SRT_HIP(hipSetDevice(pt->device));
+      int w;
+      if ((w = upload_table(pt, &tl->d_track_offsets, tl->track_offsets.data(), tl->track_offsets.size())) ||
+          (w = upload_table(pt, &tl->d_knot_times, tl->knot_times.data(), nk)) || (w = upload_table(pt, &tl->d_knot_values, tl->knot_values.data(), 4 * nk)))
+        return w;
+      SRT_HIP(hipMalloc(&tl->d_trans, (nobjects ? (size_t)nobjects : 1) * 16 * sizeof(float)));
+      return SRT_OK;
+    };
+    if ((st = up()) != SRT_OK) { timeline_free(tl); return st; }
+  }
+  *timeline = tl;
+  return SRT_OK;
+}
+
+int srt_pt_timeline_destroy(srt_pt_timeline* timeline) {
+  if (!timeline) return SRT_OK;
+  if (timeline->pt->device >= 0) (void)quiesce(timeline->pt);
+  timeline_free(timeline);
+  return SRT_OK;
+}
+
+int srt_pt_timeline_transforms(srt_pt_timeline* timeline, float t, float* trans_out) {
+  if (!timeline || !trans_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_timeline_transforms: NULL argument");
+  const int st = timeline_usable(timeline, "srt_pt_timeline_transforms");
+  if (st != SRT_OK) return st;
+  for (uint32_t k = 0; k < (uint32_t)timeline->objects.size(); k++)
+    anim_object_transform(timeline->track_offsets.data(), timeline->knot_times.data(), timeline->knot_values.data(), k, t, nullptr, trans_out + 16 * (size_t)k);
+  return SRT_OK;
+}
+
+int srt_pt_timeline_transforms_device(srt_pt_timeline* timeline, void* stream, float t, float* d_trans_out) {
+  if (!timeline || !d_trans_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_timeline_transforms_device: NULL argument");
+  return timeline_enqueue(timeline, "srt_pt_timeline_transforms_device", (hipStream_t)stream, t, d_trans_out);
+}
+
+int srt_pt_timeline_repose_refit(srt_pt_timeline* timeline, void* stream, float t) {
+  const int st = timeline_enqueue(timeline, "srt_pt_timeline_repose_refit", (hipStream_t)stream, t, timeline ? timeline->d_trans : nullptr);
+  if (st != SRT_OK) return st;
+  return srt_pt_repose_refit_device(timeline->pt, stream, timeline->objects.data(), timeline->d_trans, (uint32_t)timeline->objects.size());
+}
+
+int srt_pt_timeline_repose(srt_pt_timeline* timeline, void* stream, float t) {
+  const int st = timeline_enqueue(timeline, "srt_pt_timeline_repose", (hipStream_t)stream, t, timeline ? timeline->d_trans : nullptr);
+  if (st != SRT_OK) return st;
+  return srt_pt_repose_device(timeline->pt, stream, timeline->objects.data(), timeline->d_trans, (uint32_t)timeline->objects.size());
 }
 
 int srt_pt_scene_tree_cost(srt_pt* pt, double* cost) {
