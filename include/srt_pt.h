@@ -505,6 +505,85 @@ int srt_pt_timeline_repose_refit(srt_pt_timeline* timeline, void* stream, float 
 /* The same with srt_pt_repose_device, the rebuild: what a caller uses when srt_pt_scene_tree_cost says a refitted tree has
  * degraded.  Waits as that call waits. */
 int srt_pt_timeline_repose(srt_pt_timeline* timeline, void* stream, float t);
+/* ---- New shading values for a committed scene: materials, delta lights, the environment's radiance ----
+ * What the reference changes per frame besides poses: Scene_Object::set_time's material.anim.at(time, material.opt)
+ * (scene/object.cpp:71, Material::Anim_Material::at, scene/material.cpp:44-52) and Scene_Light::set_time (scene/light.cpp:30-38:
+ * lanim.at(time, opt), Anim_Light::at :139-144, and pose = anim.at(time)).  The kernels read materials and delta lights at trace time;
+ * trees, light lists, kernel forms and stack sizes depend only on a material's TYPE and on the NUMBER of lights, so new values need
+ * no commit.  The three calls below follow srt_pt_repose's discipline: they settle a lagging host record first, validate everything
+ * before the first write, run with nothing of the context in flight and wait as srt_pt_repose waits, upload only the listed records
+ * (32 B per material, 160 B per light, counted in srt_pt_scene_counts) and work on a host-only context.  After a successful call the
+ * scene computes, bit for bit, what a fresh commit with those values computes; after a refused one it is exactly what it was, on
+ * both sides.  No count, tree, light-list entry, kernel form or stack size changes.  (The values srt_pt_add_material / srt_pt_add_light
+ * collected stay what they were: a commit without a srt_pt_scene_begin builds from those, as it does after srt_pt_repose.)
+ * SRT_ERR_STATE: no committed scene.  SRT_ERR_INVALID: a NULL argument, an index out of range, an index listed twice, and what each
+ * call says below.
+ *
+ * materials[i]: indices srt_pt_add_material returned.  m[i].type must equal the committed type - the type decides area-light
+ * membership, the instancing refusal and the elision proof - otherwise SRT_ERR_INVALID with a message naming both types.  Values are
+ * taken as srt_pt_add_material takes them: a Lambertian `a` is divided by PI_F (rays/bsdf.h:26) as at a commit. */
+int srt_pt_update_materials(srt_pt* pt, const uint32_t* materials, const srt_pt_material* m, uint32_t n);
+/* lights[i]: the 0-based call order of srt_pt_add_light; the type stays.  radiance: 3 floats per light, angle_bounds: 2 per light
+ * (may be NULL when no listed light is a spot light), trans: 16 per light.  Each record is what srt_pt_add_light makes of the new
+ * values (Delta_Light, rays/light.h:57-96): itrans = Mat4::inverse(trans), has_trans = trans != Mat4::I. */
+int srt_pt_update_lights(srt_pt* pt, const uint32_t* lights, const float* radiance, const float* angle_bounds, const float* trans, uint32_t n);
+/* A new radiance for an SRT_ENV_SPHERE / SRT_ENV_HEMISPHERE environment light; SRT_ERR_INVALID for SRT_ENV_NONE / SRT_ENV_MAP.  The
+ * radiance is a launch parameter, like the camera: it is stored, nothing is uploaded or waited for, and it takes effect at the next launch. */
+int srt_pt_update_env_light(srt_pt* pt, const float radiance[3]);
+
+/* ---- Shading timelines: the Animate mode's material and light keys, evaluated on the device ----
+ * The keys of listed materials and delta lights (and of the environment light) as srt_pt_timeline_create takes an object's: a CSR of
+ * knots, 4 floats per knot.  Tracks, in order: per material six - albedo, reflectance, transmittance, emissive (xyz_), intensity,
+ * ior (x___), the order of Anim_Material::at's tuple (scene/material.cpp:44-52); then per light six - spectrum (xyz_), intensity
+ * (x___), angle_bounds (xy__) (Anim_Light::at, scene/light.cpp:139-144), then the Anim_Pose triple position / rotation (xyzw) /
+ * scale; then, with env != 0, two - spectrum and intensity of the environment light.  track_offsets has one entry per track plus one,
+ * from 0.
+ *   Semantics are the reference's.  Spline<Spectrum>, Spline<Vec2> and Spline<float> are the fork's Spline<T>::at
+ * (student/spline.inl:5-72) channel by channel (lib/spectrum.h:84-102,136-138, lib/vec2.h:83-107,175-177).  A material takes all six
+ * options from at(t): an empty track gives T() - a zero Spectrum, a 0.0f intensity or ior (geometry/spline.h:99-101) - so emissive
+ * keys without an intensity key give a black light, as in the reference.  A light's option triple and its pose triple are
+ * independent (Scene_Light::set_time, scene/light.cpp:30-38): a triple without a key leaves the scene's values in place.  From the
+ * options the record is what Pathtracer::build_scene / build_lights make (rays/pathtracer.cpp:26-64,93-117), by committed type:
+ * Lambertian a = albedo.to_linear() / PI_F (Spectrum::to_linear, lib/spectrum.h:54-60, both branches); Mirror a = reflectance; Glass
+ * a = transmittance, b = reflectance, ior; Refract a = transmittance, ior; Diffuse light a = emissive * intensity
+ * (Material::emissive, scene/material.cpp:34-36); a light's radiance = spectrum * intensity (scene/light.cpp:98-100), angle_bounds,
+ * trans = Pose::transform() of Anim_Pose::at(t), itrans, has_trans.  Fields a material type does not read are written as zeros.
+ *   to_linear: the host form uses libm's powf, as the reference does; the kernel uses the SRT-MATH restatement of glibc 2.35's powf,
+ * whose argument (f + 0.055f) / 1.055f with f > 0.04045f is a positive normal number for every finite albedo.  A non-finite albedo
+ * channel yields the same on both sides: NaN stays NaN and -inf stays -inf (the f / 12.92f branch), +inf gives +inf (the kernel
+ * answers it before its powf, which takes normal arguments only).
+ * SRT_ERR_STATE: no committed scene.  SRT_ERR_INVALID: a NULL argument (materials / lights may be NULL where their count is 0);
+ * nothing listed; an index out of range or listed twice; env != 0 without a sphere / hemisphere environment light; the refusals of
+ * srt_pt_timeline_create about offsets and times, with its messages; a material whose six tracks are all empty, a light whose two
+ * triples are both empty, an environment whose two tracks are empty (Splines::any() is false).  Knot values are not checked.  The
+ * scene is not touched.  Uploads the tables once.  A shading timeline goes stale as a timeline does (SRT_ERR_STATE from every call
+ * but destroy once the scene was begun or committed again) and is destroyed before its context. */
+typedef struct srt_pt_shading_timeline srt_pt_shading_timeline; /* opaque */
+int srt_pt_shading_timeline_create(srt_pt* pt, const uint32_t* materials, uint32_t nmaterials, const uint32_t* lights, uint32_t nlights, int env,
+                                   const uint32_t* track_offsets, const float* knot_times, const float* knot_values, srt_pt_shading_timeline** out);
+/* Waits for the device, frees the timeline.  NULL is fine. */
+int srt_pt_shading_timeline_destroy(srt_pt_shading_timeline* timeline);
+/* The host form: the functions of pt_anim.h compiled for the host, the definition the kernel is held to.  materials_out[k]: material
+ * k of the list as srt_pt_update_materials takes it (a Lambertian `a` is albedo.to_linear(), not yet divided); lights_out: 21 floats
+ * per light - radiance3, angle_bounds2, trans16, a triple without a key giving the scene's values; env_out: the environment's
+ * radiance.  An array may be NULL where the timeline lists nothing for it.  Launches nothing and works on a host-only context (a
+ * lagging host record is settled first: the values a light keeps are read from it). */
+int srt_pt_shading_timeline_values(srt_pt_shading_timeline* timeline, float t, srt_pt_material* materials_out, float* lights_out, float env_out[3]);
+/* The values of time t through srt_pt_update_materials, srt_pt_update_lights and srt_pt_update_env_light: the host form of apply. */
+int srt_pt_shading_timeline_update(srt_pt_shading_timeline* timeline, float t);
+/* The device form, ENQUEUE-ONLY: validates on the host and enqueues one kernel on `stream` (a hipStream_t; NULL: the null stream) -
+ * one lane per item, materials first, then lights - which writes the listed records of the live material and delta-light tables in
+ * place.  No synchronisation, no read-back, and in the steady state nothing uploaded: the tables went up at create.  A light's
+ * itrans / has_trans come from the arithmetic srt_pt_repose_device gives an object's.  The environment's three floats are one item
+ * and no scene memory: they are evaluated on the host inside the call, by the same function of pt_anim.h a kernel would run, and
+ * stored as the launch parameter.  Results equal the host form's bit for bit.
+ *   Ordering is srt_pt_repose_refit_device's: the new values are visible to whatever is enqueued on `stream` behind the call; epochs
+ * on other streams are ordered by the caller with events.  The host's record LAGS after the call and settles under that call's rule:
+ * every entry point that is not enqueue-only waits for an event recorded behind the last apply and reads the material and / or
+ * delta-light table back once (32 B / 160 B per record).  While the material record lags, srt_pt_set_elision's proof is not
+ * attempted: the image is bit-identical either way, only the cost differs, and srt_pt_rays_elided shows it.  A host-only context
+ * validates and returns SRT_ERR_UNSUPPORTED.  A HIP error is SRT_ERR_HIP and leaves the context without a committed scene. */
+int srt_pt_shading_timeline_apply(srt_pt_shading_timeline* timeline, void* stream, float t);
 /* Where srt_pt_scene_commit runs BVH<Primitive>::build (student/bvh.inl:35-163): device != 0 (default) builds primitive sets of at
  * least min_primitives (default 16384) on the GPU, smaller ones and device == 0 on the host.  Both produce the reference's node
  * arrays and primitive order bit for bit (the candidate planes' std::partition sequence included); SRT_BVH_BUILDER=host in the

@@ -90,6 +90,15 @@ int srt_pt_top_refit_pending(srt_pt* pt, uint64_t out[2]);
  * waits for the device and reads the device arrays back (SRT_ERR_UNSUPPORTED on a host-only context).  The arrays may be NULL
  * where their capacity is 0. */
 long srt_pt_dump_lights(srt_pt* pt, int from_device, uint32_t* heads, float* mats, size_t cap_lights, float* tris, size_t cap_tris);
+/* The shading tables of the committed scene (what srt_pt_update_materials / srt_pt_update_lights / srt_pt_update_env_light and the
+ * shading timelines write).  counts = {materials, delta lights}.  Per material k < cap_materials: the record the kernels read (a
+ * Lambertian `a` already divided by PI_F, rays/bsdf.h:26).  Per delta light j < cap_lights: light_heads[2 j ..] = {type, has_trans},
+ * light_values[37 j ..] = radiance3, angle_bounds2, trans16, itrans16.  env_type / env_radiance (may be NULL): the environment light;
+ * the radiance is a launch parameter and the same on both sides.  from_device == 0 reads the host's record (after settling);
+ * from_device != 0 waits for the device and reads the device tables back (SRT_ERR_UNSUPPORTED on a host-only context).  The arrays
+ * may be NULL where their capacity is 0. */
+int srt_pt_dump_shading(srt_pt* pt, int from_device, uint32_t counts[2], srt_pt_material* materials, size_t cap_materials, uint32_t* light_heads,
+                        float* light_values, size_t cap_lights, uint32_t* env_type, float env_radiance[3]);
 /* cosf/sinf of the kernel (SRT-MATH v2) for n host floats; parity tests compare them with glibc. */
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);
 /* The kernels' atan2f (glibc 2.35's algorithm restated; Spot_Light::sample) evaluated on the device. */

@@ -92,6 +92,15 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_timeline_transforms_device.argtypes = [c_void_p, c_void_p, c_float, c_void_p]
     lib.srt_pt_timeline_repose_refit.argtypes = [c_void_p, c_void_p, c_float]
     lib.srt_pt_timeline_repose.argtypes = [c_void_p, c_void_p, c_float]
+    lib.srt_pt_update_materials.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_update_lights.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_update_env_light.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_shading_timeline_create.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_shading_timeline_destroy.argtypes = [c_void_p]
+    lib.srt_pt_shading_timeline_values.argtypes = [c_void_p, c_float, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_shading_timeline_update.argtypes = [c_void_p, c_float]
+    lib.srt_pt_shading_timeline_apply.argtypes = [c_void_p, c_void_p, c_float]
+    lib.srt_pt_dump_shading.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.srt_pt_scene_counts.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_set_bvh_builder.argtypes = [c_void_p, c_int, c_uint32]
     lib.srt_pt_set_stream_slots.argtypes = [c_void_p, c_uint32]
@@ -418,6 +427,103 @@ class TimelineGroup:
             tl.close()
 
 
+MATERIAL_DTYPE = np.dtype([("type", np.uint32), ("a", np.float32, 3), ("b", np.float32, 3), ("ior", np.float32)])   # srt_pt_material
+
+
+def material_records(materials) -> np.ndarray:
+    """srt_pt_material records from an array of MATERIAL_DTYPE or a sequence of dicts with type / a / b / ior (the scene descriptions' form)."""
+    if isinstance(materials, np.ndarray) and materials.dtype == MATERIAL_DTYPE:
+        return np.ascontiguousarray(materials).reshape(-1)
+    out = np.zeros(len(materials), MATERIAL_DTYPE)
+    for k, m in enumerate(materials):
+        out[k] = (int(m["type"]), _f32(m["a"]), _f32(m.get("b", (0, 0, 0))), float(m.get("ior", 0.0)))
+    return out
+
+
+def shading_tracks(tracks):
+    """(track_offsets, knot_times, knot_values) from either that triple or a flat sequence of tracks in the order of
+    srt_pt_shading_timeline_create - six per material, six per light, two of the environment - each (times, values) or None, values
+    (n, 1 .. 4)."""
+    if isinstance(tracks, tuple) and len(tracks) == 3 and isinstance(tracks[0], np.ndarray) and tracks[0].ndim == 1 and tracks[0].dtype.kind in "ui":
+        off, times, values = tracks
+        return np.ascontiguousarray(off, np.uint32), _f32(times).reshape(-1), _f32(values).reshape(-1, 4)
+    off, times, values = [0], [], []
+    for track in tracks:
+        if track is not None:
+            ts, vs = track
+            vs = _f32(vs).reshape(len(ts), -1)
+            times.extend(float(t) for t in ts)
+            values.extend(np.concatenate([v, np.zeros(4 - len(v), np.float32)]) for v in vs)
+        off.append(len(times))
+    return np.array(off, np.uint32), np.array(times, np.float32), np.array(values, np.float32).reshape(-1, 4)
+
+
+class ShadingTimeline:
+    """srt_pt_shading_timeline (Pathtracer.create_shading_timeline): the Animate mode's keys of some materials and delta lights of the
+    committed scene (and of its environment light), on the device.  values(t) is the host form, update(t) hands it to
+    update_materials / update_lights / update_env_light, apply(t) is the kernel: enqueue-only, nothing uploaded.  Closing the
+    Pathtracer closes the timelines it created; close() after that does nothing."""
+
+    def __init__(self, pt, handle, materials, lights, env):
+        self._pt, self._lib, self._check = pt, pt._lib, pt._check
+        self._h = handle
+        self.materials, self.lights, self.env = materials, lights, bool(env)
+
+    def values(self, t: float) -> dict:
+        """srt_pt_shading_timeline_values: {"materials": MATERIAL_DTYPE (nmaterials) as update_materials takes them, "lights":
+        float32 (nlights, 21) = radiance3, angle_bounds2, trans16, "env": float32 (3) or None}, computed on the host."""
+        mats, lights, env = np.zeros(len(self.materials), MATERIAL_DTYPE), np.zeros((len(self.lights), 21), np.float32), np.zeros(3, np.float32)
+        self._check(self._lib, self._lib.srt_pt_shading_timeline_values(self._h, float(t), _p(mats) if len(mats) else None, _p(lights) if len(lights) else None,
+                                                                        _p(env) if self.env else None))
+        return {"materials": mats, "lights": lights, "env": env if self.env else None}
+
+    def update(self, t: float) -> None:
+        """srt_pt_shading_timeline_update: the host form - values(t) through the update calls (waits, uploads the listed records)."""
+        self._check(self._lib, self._lib.srt_pt_shading_timeline_update(self._h, float(t)))
+
+    def apply(self, t: float, stream: int = 0) -> None:
+        """srt_pt_shading_timeline_apply: one kernel on `stream` writes the listed records in place - enqueue-only, nothing uploaded."""
+        self._check(self._lib, self._lib.srt_pt_shading_timeline_apply(self._h, c_void_p(stream), float(t)))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.srt_pt_shading_timeline_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self._pt._ctx:                # (Pathtracer.close() has closed the timelines it made: after it there is nothing left to free)
+                self.close()
+        except Exception:
+            pass
+
+
+class ShadingTimelineGroup:
+    """PathtracerGroup.create_shading_timeline: one ShadingTimeline per rank (the scene is replicated); all ranks get the same t."""
+
+    def __init__(self, timelines):
+        self.timelines = timelines
+
+    def values(self, t: float) -> dict:
+        return self.timelines[0].values(t)
+
+    def update(self, t: float) -> None:
+        for tl in self.timelines:
+            tl.update(t)
+
+    def apply(self, t: float, stream: int = 0) -> None:
+        """ShadingTimeline.apply on every rank; like TimelineGroup.repose_refit each member is settled before this returns (the
+        group's lanes render on streams of their own, which nothing orders behind `stream`)."""
+        for tl in self.timelines:
+            tl.apply(t, stream)
+        for tl in self.timelines:
+            tl._check(tl._lib, tl._lib.srt_pt_sync(tl._pt._ctx))
+
+    def close(self) -> None:
+        for tl in self.timelines:
+            tl.close()
+
+
 class Scene:
     """A scene description (see scenes.py): materials, objects, camera — the inputs of build_scene."""
 
@@ -631,6 +737,64 @@ class Pathtracer:
         self._check(self._lib, self._lib.srt_pt_timeline_create(self._ctx, _p(idx if len(idx) else np.zeros(1, np.uint32)), len(idx), _p(off), _p(times), _p(values),
                                                                 ctypes.byref(h)))
         tl = Timeline(self, h, idx)
+        self._timelines = [r for r in self._timelines if r() is not None] + [weakref.ref(tl)]
+        return tl
+
+    def update_materials(self, indices, materials) -> None:
+        """srt_pt_update_materials: new values (material_records(..): the form build_scene takes) for the materials with these indices
+        of the committed scene; the types stay.  No commit: 32 B per material go up."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        recs = material_records(materials)
+        if len(recs) != len(idx):
+            raise ValueError(f"{len(idx)} indices but {len(recs)} materials")
+        self._check(self._lib, self._lib.srt_pt_update_materials(self._ctx, _p(idx), _p(recs), len(idx)))
+
+    def update_lights(self, indices, radiance, angle_bounds, Ts) -> None:
+        """srt_pt_update_lights: new radiance (n, 3), angle_bounds (n, 2) or None, and transforms (n, 16) for the delta lights with
+        these indices (the order of the scene's "lights"); the types stay.  No commit: 160 B per light go up."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        rad, T = _f32(radiance).reshape(-1, 3), _f32(Ts).reshape(-1, 16)
+        ab = None if angle_bounds is None else _f32(angle_bounds).reshape(-1, 2)
+        if len(rad) != len(idx) or len(T) != len(idx) or (ab is not None and len(ab) != len(idx)):
+            raise ValueError(f"{len(idx)} lights but {len(rad)} radiances, {len(T)} transforms")
+        self._check(self._lib, self._lib.srt_pt_update_lights(self._ctx, _p(idx), _p(rad), None if ab is None else _p(ab), _p(T), len(idx)))
+
+    def update_env_light(self, radiance) -> None:
+        """srt_pt_update_env_light: a new radiance for a sphere / hemisphere environment light, in effect from the next launch."""
+        rad = _f32(radiance).reshape(3)
+        self._check(self._lib, self._lib.srt_pt_update_env_light(self._ctx, _p(rad)))
+
+    def dump_shading(self, from_device: bool = False) -> dict:
+        """srt_pt_dump_shading: {"materials": MATERIAL_DTYPE records as the kernels read them, "light_heads": uint32 (lights, 2) = type,
+        has_trans, "lights": float32 (lights, 37) = radiance3, angle_bounds2, trans16, itrans16, "env_type", "env_radiance"} from the
+        host's record or read back from the device."""
+        counts, env_type, env = np.zeros(2, np.uint32), c_uint32(0), np.zeros(3, np.float32)
+
+        def call(mats, heads, values):
+            self._check(self._lib, self._lib.srt_pt_dump_shading(self._ctx, int(bool(from_device)), _p(counts), _p(mats) if len(mats) else None, len(mats),
+                                                                 _p(heads) if len(heads) else None, _p(values) if len(heads) else None, len(heads),
+                                                                 ctypes.byref(env_type), _p(env)))
+
+        call(np.zeros(0, MATERIAL_DTYPE), np.zeros((0, 2), np.uint32), np.zeros((0, 37), np.float32))
+        mats, heads, values = np.zeros(int(counts[0]), MATERIAL_DTYPE), np.zeros((int(counts[1]), 2), np.uint32), np.zeros((int(counts[1]), 37), np.float32)
+        call(mats, heads, values)
+        return {"materials": mats, "light_heads": heads, "lights": values, "env_type": int(env_type.value), "env_radiance": env}
+
+    def create_shading_timeline(self, materials, lights, env, tracks) -> ShadingTimeline:
+        """srt_pt_shading_timeline_create: keys for the materials and delta lights with these indices of the committed scene and, with
+        env, for its environment light (shading_tracks(..) says how `tracks` may be given); the tables go up once."""
+        mats, lts = np.ascontiguousarray(materials, np.uint32).reshape(-1), np.ascontiguousarray(lights, np.uint32).reshape(-1)
+        off, times, values = shading_tracks(tracks)
+        want = 6 * len(mats) + 6 * len(lts) + (2 if env else 0) + 1
+        if len(off) != want or len(times) != len(values) or int(off.max()) > len(times):
+            raise ValueError(f"{len(mats)} materials, {len(lts)} lights, env {bool(env)}: {want} offsets expected, {len(off)} given up to {int(off.max())}, "
+                             f"{len(times)} knot times, {len(values)} knot values")
+        if len(times) == 0:
+            times, values = np.zeros(1, np.float32), np.zeros((1, 4), np.float32)
+        h = c_void_p()
+        self._check(self._lib, self._lib.srt_pt_shading_timeline_create(self._ctx, _p(mats) if len(mats) else None, len(mats), _p(lts) if len(lts) else None, len(lts),
+                                                                        int(bool(env)), _p(off), _p(times), _p(values), ctypes.byref(h)))
+        tl = ShadingTimeline(self, h, mats, lts, env)
         self._timelines = [r for r in self._timelines if r() is not None] + [weakref.ref(tl)]
         return tl
 
@@ -1069,6 +1233,34 @@ class PathtracerGroup:
                 tl.close()
             raise
         return TimelineGroup(made)
+
+    def update_materials(self, indices, materials) -> None:
+        for m in self.members:
+            m.update_materials(indices, materials)
+
+    def update_lights(self, indices, radiance, angle_bounds, Ts) -> None:
+        for m in self.members:
+            m.update_lights(indices, radiance, angle_bounds, Ts)
+
+    def update_env_light(self, radiance) -> None:
+        for m in self.members:
+            m.update_env_light(radiance)
+
+    def dump_shading(self, from_device: bool = False) -> list:
+        """Every member's Pathtracer.dump_shading(), by rank."""
+        return [m.dump_shading(from_device) for m in self.members]
+
+    def create_shading_timeline(self, materials, lights, env, tracks) -> ShadingTimelineGroup:
+        """One shading timeline per rank; ShadingTimelineGroup.update / apply give every rank the same t."""
+        made = []
+        try:
+            for m in self.members:
+                made.append(m.create_shading_timeline(materials, lights, env, tracks))
+        except Exception:
+            for tl in made:
+                tl.close()
+            raise
+        return ShadingTimelineGroup(made)
 
     def scene_counts(self) -> list:
         """Every member's Pathtracer.scene_counts(), by rank (the scene is replicated)."""

@@ -390,6 +390,7 @@ int need_ready(srt_pt* pt, const char* what) {
 bool elision_provable(const srt_pt* pt) {
   const FlatScene& F = pt->built.flat;
   if (!pt->elide || !F.delta_lights.empty() || pt->env_type != 0) return false;
+  if (pt->shade_pending_mats) return false;               // srt_pt_shading_timeline_apply: F.materials lags the device until settle()
   for (const Material& m : F.materials) {
     if (m.type == 3u && !(0.2126f * m.a[0] + 0.7152f * m.a[1] + 0.0722f * m.a[2] > 0.0f)) return false;
     // the dead term is emission x albedo x cos x 1/pdf with 1/pdf <= pi / cos(1): finite as long as the factors are moderate
@@ -1005,6 +1006,7 @@ int srt_pt_destroy(srt_pt* pt) {
     drop_update_tables(pt, UINT32_MAX);
     for (auto& pl : pt->pinned) { (void)hipHostFree(pl.h); (void)hipEventDestroy(pl.done); }
     if (pt->top_event) (void)hipEventDestroy(pt->top_event);
+    if (pt->shade_event) (void)hipEventDestroy(pt->shade_event);
     (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal); (void)hipFree(pt->d_light_list);
     if (pt->h_fault) (void)hipHostFree(pt->h_fault);
     if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);

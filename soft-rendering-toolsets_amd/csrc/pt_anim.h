@@ -27,6 +27,7 @@
 #include <string>
 
 #include "pt_device.h"
+#include "pt_scene.h"
 #include "pt_skin.h"
 
 namespace srt {
@@ -256,6 +257,99 @@ SRT_ANIM_FN void anim_joint_to_posed(const int32_t* parent, const float* cap, co
   skin_mat4_mul(tr, iter, posed);
 }
 
+// ---- shading timelines: Material::Anim_Material::at (scene/material.cpp:44-52), Scene_Light::Anim_Light::at (scene/light.cpp:139-144)
+// and Scene_Light::set_time (:30-38) ----
+// Spline<Spectrum>, Spline<Vec2> and Spline<float> are the fork's Spline<T>::at (student/spline.inl:5-72) over types whose operators
+// work channel by channel with one rounding each and true divisions (lib/spectrum.h:84-102,136-138, lib/vec2.h:83-107,175-177): they
+// are anim_spline_vec3 on components padded with zeros (xyz_, xy__, x___), and an empty track gives T() - a zero Spectrum, 0.0f.
+//
+// Spectrum::to_linear (lib/spectrum.h:54-60), both branches.  The host form calls libm's powf, as the reference does; the device
+// form calls srt_powf (SRT-MATH v2, glibc 2.35's powf restated), whose argument (f + 0.055f) / 1.055f with f > 0.04045f is a positive
+// normal number for every finite f.  Non-finite channels: NaN takes the division and stays NaN, -inf takes the division and stays
+// -inf, and +inf - the one input outside srt_powf's domain - is answered here with libm's +inf, so both forms agree on every input.
+SRT_ANIM_FN float anim_to_linear(float f) {
+  if (f > 0.04045f) {
+    const float x = (f + 0.055f) / 1.055f;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (f2u(x) == 0x7f800000u) return x;
+    return srt_powf(x, 2.4f);
+#else
+    return powf(x, 2.4f);
+#endif
+  }
+  return f / 12.92f;
+}
+
+// Material::Options after Anim_Material::at(t): the tuple's order - albedo, reflectance, transmittance, emissive, intensity, ior.
+struct AnimMaterialOptions { AnimV3 albedo, reflectance, transmittance, emissive; float intensity, ior; };
+
+// o: the seven offsets of one material's six tracks.
+SRT_ANIM_FN AnimMaterialOptions anim_material_options(const uint32_t* o, const float* times, const float* values, float t) {
+  AnimMaterialOptions p;
+  p.albedo = anim_spline_vec3(times, values, o[0], o[1], t);
+  p.reflectance = anim_spline_vec3(times, values, o[1], o[2], t);
+  p.transmittance = anim_spline_vec3(times, values, o[2], o[3], t);
+  p.emissive = anim_spline_vec3(times, values, o[3], o[4], t);
+  p.intensity = anim_spline_vec3(times, values, o[4], o[5], t).x;
+  p.ior = anim_spline_vec3(times, values, o[5], o[6], t).x;
+  return p;
+}
+
+// The material as srt_pt_add_material takes it, from the options, as Pathtracer::build_scene maps them to BSDFs (rays/pathtracer.cpp:93-117):
+// Lambertian a = albedo.to_linear(); Mirror a = reflectance; Glass a = transmittance, b = reflectance, ior; Diffuse light a =
+// Material::emissive() = emissive * intensity (scene/material.cpp:34-36); Refract a = transmittance, ior.  Fields a type does not
+// read are zero.  `type` is the committed SRT_MAT_* type.
+SRT_ANIM_FN void anim_material_values(uint32_t type, const AnimMaterialOptions& p, float a[3], float b[3], float* ior) {
+  AnimV3 va = {0.0f, 0.0f, 0.0f}, vb = {0.0f, 0.0f, 0.0f};
+  *ior = 0.0f;
+  if (type == 0u) va = {anim_to_linear(p.albedo.x), anim_to_linear(p.albedo.y), anim_to_linear(p.albedo.z)};
+  else if (type == 1u) va = p.reflectance;
+  else if (type == 2u) { va = p.transmittance; vb = p.reflectance; *ior = p.ior; }
+  else if (type == 3u) va = p.emissive * p.intensity;
+  else { va = p.transmittance; *ior = p.ior; }
+  a[0] = va.x; a[1] = va.y; a[2] = va.z;
+  b[0] = vb.x; b[1] = vb.y; b[2] = vb.z;
+}
+
+// The record the kernels read, from the material as srt_pt_add_material takes it: BSDF_Lambertian(albedo) : albedo(albedo / PI_F)
+// (rays/bsdf.h:26), which build_scene of pt_scene.cpp applies at the commit.
+SRT_ANIM_FN void anim_material_store(Material* m) {
+  if (m->type == 0u)
+    for (int i = 0; i < 3; i++) m->a[i] = m->a[i] / kPi;
+}
+
+// Material k of a shading timeline at time t, as srt_pt_add_material takes it (the type is the committed one and is not written).
+SRT_ANIM_FN void anim_material_item(const uint32_t* track_offsets, const float* times, const float* values, uint32_t k, float t, Material* m) {
+  const AnimMaterialOptions p = anim_material_options(track_offsets + 6 * (size_t)k, times, values, t);
+  anim_material_values(m->type, p, m->a, m->b, &m->ior);
+}
+
+// Scene_Light::set_time for one light.  o: the seven offsets of its six tracks - spectrum, intensity, angle_bounds, then the Anim_Pose
+// triple.  The option triple and the pose triple are independent: one without a key leaves its outputs untouched (options /
+// pose say which were written).  radiance = Scene_Light::radiance() = spectrum * intensity (scene/light.cpp:98-100); trans =
+// Pose::transform() of Anim_Pose::at(t).
+struct AnimLightOut { bool options, pose; float radiance[3], angle_bounds[2], trans[16]; };
+SRT_ANIM_FN void anim_light_item(const uint32_t* o, const float* times, const float* values, float t, AnimLightOut* out) {
+  out->options = o[3] > o[0];
+  out->pose = o[6] > o[3];
+  if (out->options) {
+    const AnimV3 spectrum = anim_spline_vec3(times, values, o[0], o[1], t);
+    const float intensity = anim_spline_vec3(times, values, o[1], o[2], t).x;
+    const AnimV3 bounds = anim_spline_vec3(times, values, o[2], o[3], t);
+    const AnimV3 r = spectrum * intensity;
+    out->radiance[0] = r.x; out->radiance[1] = r.y; out->radiance[2] = r.z;
+    out->angle_bounds[0] = bounds.x; out->angle_bounds[1] = bounds.y;
+  }
+  if (out->pose) anim_object_transform(o + 3, times, values, 0u, t, nullptr, out->trans);
+}
+
+// The environment light's radiance: o: the three offsets of its two tracks (spectrum, intensity).  One item, evaluated on the host by
+// every form - the radiance is a launch parameter (DScene::env_radiance), not scene memory; this is the function a kernel would run.
+SRT_ANIM_FN void anim_env_item(const uint32_t* o, const float* times, const float* values, float t, float radiance[3]) {
+  const AnimV3 r = anim_spline_vec3(times, values, o[0], o[1], t) * anim_spline_vec3(times, values, o[1], o[2], t).x;
+  radiance[0] = r.x; radiance[1] = r.y; radiance[2] = r.z;
+}
+
 // What srt_pt_timeline_create and srt_pt_skin_set_rig refuse about their knot tables, as a message (empty: nothing).  offsets holds
 // nitems * per_item + 1 entries - per_item tracks per object or joint - from 0, never descending; the times of one track ascend
 // strictly and are finite; with refuse_empty_items an item whose tracks are all empty is refused (Splines::any() is false for it:
@@ -299,6 +393,12 @@ void launch_anim_pose(void* stream, const uint32_t* d_track_offsets, const float
 void launch_anim_joints(void* stream, const int32_t* d_parent, const float* d_cap, const float* d_base, const float* d_rest_pose, const uint32_t* d_knot_offsets,
                         const float* d_times, const float* d_quats, uint32_t njoints, float t, float* d_local, const float* d_inv, float* d_mats,
                         float* d_posed_out);
+// srt_pt_shading_timeline_apply: one lane per item, materials first, then lights.  Lane k < nmaterials writes a, b and ior of
+// d_mats[d_materials[k]] (anim_material_item, anim_material_store; the type is read from the record and stays); lane nmaterials + j
+// writes radiance and angle_bounds (option keys) and trans, itrans, has_trans (pose keys) of d_dlights[d_lights[j]].  The track
+// offsets are those of the timeline: 6 per material, then 6 per light.  The caller has checked every index against the tables.
+void launch_anim_shading(void* stream, const uint32_t* d_track_offsets, const float* d_times, const float* d_values, const uint32_t* d_materials,
+                         uint32_t nmaterials, const uint32_t* d_lights, uint32_t nlights, float t, Material* d_mats, DeltaLight* d_dlights);
 // d_out[i] = srt_hypotf(d_x[i], d_y[i]) (srt_pt_math_hypot)
 void launch_anim_hypot(void* stream, const float* d_x, const float* d_y, size_t n, float* d_out);
 

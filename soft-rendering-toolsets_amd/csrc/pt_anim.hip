@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_anim.h"
+#include "pt_pose.h"
 
 namespace srt {
 namespace {
@@ -48,6 +49,42 @@ __global__ __launch_bounds__(kBlock) void anim_joint_chain_kernel(const int32_t*
     for (int i = 0; i < 16; i++) posed_out[16 * (size_t)j + i] = posed[i];
 }
 
+// srt_pt_shading_timeline_apply.  Materials first, then lights: a wave at the boundary runs both branches once, every other wave
+// one.  A lane reads and writes its own record only (the host refused duplicate indices), at an index the host checked against
+// the table; the matrices of a light take the arithmetic launch_pose_objects gives an object's (pose_inverse, pose_ne_identity).
+__global__ __launch_bounds__(kBlock) void anim_shading_kernel(const uint32_t* __restrict__ track_offsets, const float* __restrict__ times,
+                                                             const float* __restrict__ values, const uint32_t* __restrict__ materials, uint32_t nmaterials,
+                                                             const uint32_t* __restrict__ lights, uint32_t nlights, float t, Material* __restrict__ mats,
+                                                             DeltaLight* __restrict__ dlights) {
+  const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+  if (k < nmaterials) {
+    Material* dst = mats + materials[k];
+    Material m;
+    m.type = dst->type;
+    anim_material_item(track_offsets, times, values, k, t, &m);
+    anim_material_store(&m);
+    for (int i = 0; i < 3; i++) { dst->a[i] = m.a[i]; dst->b[i] = m.b[i]; }
+    dst->ior = m.ior;
+    return;
+  }
+  const uint32_t j = k - nmaterials;
+  if (j >= nlights) return;
+  DeltaLight* dst = dlights + lights[j];
+  AnimLightOut out;
+  anim_light_item(track_offsets + 6 * (size_t)nmaterials + 6 * (size_t)j, times, values, t, &out);
+  if (out.options) {
+    for (int i = 0; i < 3; i++) dst->radiance[i] = out.radiance[i];
+    dst->angle_bounds[0] = out.angle_bounds[0]; dst->angle_bounds[1] = out.angle_bounds[1];
+  }
+  if (out.pose) {
+    float inv[16];
+    pose_inverse(out.trans, inv);
+    for (int c = 0; c < 4; c++)
+      for (int r = 0; r < 4; r++) { dst->trans.c[c][r] = out.trans[4 * c + r]; dst->itrans.c[c][r] = inv[4 * c + r]; }
+    dst->has_trans = pose_ne_identity(out.trans) ? 1u : 0u;
+  }
+}
+
 __global__ __launch_bounds__(256) void anim_hypot_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = srt_hypotf(x[i], y[i]);
@@ -68,6 +105,13 @@ void launch_anim_joints(void* stream, const int32_t* d_parent, const float* d_ca
   if (!njoints) return;
   anim_joint_local_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_rest_pose, d_knot_offsets, d_times, d_quats, njoints, t, d_local);
   anim_joint_chain_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_parent, d_cap, d_base, d_local, njoints, d_inv, d_mats, d_posed_out);
+}
+
+void launch_anim_shading(void* stream, const uint32_t* d_track_offsets, const float* d_times, const float* d_values, const uint32_t* d_materials,
+                         uint32_t nmaterials, const uint32_t* d_lights, uint32_t nlights, float t, Material* d_mats, DeltaLight* d_dlights) {
+  if (!(nmaterials + nlights)) return;
+  anim_shading_kernel<<<grid_for(nmaterials + nlights), dim3(kBlock), 0, (hipStream_t)stream>>>(d_track_offsets, d_times, d_values, d_materials, nmaterials,
+                                                                                             d_lights, nlights, t, d_mats, d_dlights);
 }
 
 void launch_anim_hypot(void* stream, const float* d_x, const float* d_y, size_t n, float* d_out) {

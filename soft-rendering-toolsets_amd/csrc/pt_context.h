@@ -140,6 +140,11 @@ struct srt_pt {
   std::vector<uint32_t> top_pending_objects;
   hipEvent_t top_event = nullptr;
   uint64_t top_refits = 0;                  // srt_pt_top_refit_count
+  // srt_pt_shading_timeline_apply: the host's record of the materials / delta lights lags the device from a call that wrote them until
+  // settle() reads d_mats / d_dlights back, behind the event recorded after the last such call.  While the materials lag,
+  // elision_provable (pt.hip) proves nothing.
+  bool shade_pending_mats = false, shade_pending_lights = false;
+  hipEvent_t shade_event = nullptr;
 };
 
 namespace srt {
