@@ -203,6 +203,9 @@ def pt_scene(name):
     import srt_amd  # noqa: F401  (loads the package under its importable name)
     from soft_rendering_toolsets_amd import scenes
 
+    if "@" in name:                                   # a world off unit scale, e.g. "cbox@geom:14" (tests/_scale_cases.py)
+        from _scale_cases import scaled_scene
+        return scaled_scene(name)
     if name in ("cbox", "cbox_lambertian"):
         return scenes.cornell_box(name)
     if name == "cbox_blob512_glass":
@@ -694,4 +697,23 @@ def random_pt_scene(seed):
         elif seed >= 200000 and rng.random() < 0.5:          # image environment map (Env_Map)
             eh, ew = int(rng.integers(2, 24)), int(rng.integers(2, 40))
             scene["env"] = {"type": 3, "image": np.ascontiguousarray(rng.uniform(0.0, 1.5, (eh, ew, 3)), np.float32)}
+    # seeds >= 300000 also draw a world off unit scale (tests/_scale_cases.py): with a small probability a projective bottom row
+    # on one object, then a translation (up to 16, or up to 2000), a factor that is no power of two, and a power of two in the
+    # geometry or in the pose from the bands in which the exact-division windows of csrc/pt_device.h are crossed
+    if seed >= 300000:
+        import _scale_cases as SC
+
+        k, w2 = int(rng.integers(0, len(objs))), rng.random() < 0.5
+        row = (0.0, 0.0, 0.0, 2.0) if w2 else tuple(np.append(rng.uniform(-0.25, 0.25, 3), 1.0))
+        if rng.random() < 0.15:
+            scene = SC.projective(scene, (k,), (row,))
+        far = rng.random() < 0.5
+        t = rng.choice([-1.0, 1.0], 3) * np.exp(rng.uniform(0.0, np.log(2000.0 if far else 16.0), 3))
+        factor = float(rng.uniform(0.3, 3.0))
+        in_pose = rng.random() < 0.5
+        e = int(rng.integers(-42, 43)) if in_pose else int(rng.integers(-16, 22))
+        scene = SC.pose_scaled(SC.translated(scene, t), factor)
+        scene = (SC.pose_scaled if in_pose else SC.geom_scaled)(scene, 2.0 ** e)
+        scene["name"] = f"random{seed}"
+        out = (scene,) + out[1:]
     return out

@@ -211,6 +211,19 @@ def load_fullsize():
         return json.load(f)
 
 
+def golden_rays(g, scene, seed, n=2048):
+    """The scene.hit rays a pt_*.npz fixture was made with: random_rays, or - where the fixture says so - the same rays carried
+    into the scene's world (tests/_scale_cases.py:scaled_rays)."""
+    from _cases import random_rays
+
+    if "rays" not in g:
+        return random_rays(seed, n)
+    assert str(g["rays"]) == "scaled_rays", str(g["rays"])
+    from _scale_cases import scaled_rays
+
+    return scaled_rays("random_rays", seed, n, scene)
+
+
 def load_golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 

@@ -25,6 +25,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import _harness as H  # noqa: E402
 from _cases import pt_sample_list, pt_scene, random_rays, scene_digest  # noqa: E402
+from _scale_cases import golden_tag, scaled_rays  # noqa: E402
 
 # name, w, h, max_depth, use_bvh, n_samples, epoch (w, h, spp) or None
 CASES = [
@@ -47,6 +48,16 @@ CASES = [
     ("cbox_blob131072_glass", 1024, 1024, 8, True, 4096, (24, 24, 4)),
     # the reference's own largest mesh asset (media/beast.dae, 64 618 triangles) as the glass object, posed by a rotation + scale
     ("cbox_beast_glass", 512, 512, 8, True, 4096, (24, 24, 4)),
+    # worlds off unit scale (tests/_scale_cases.py): a scale in the geometry that puts part of Triangle::hit's divides outside the
+    # exact fast path's window, small and large; a scale in the pose that does the same to Ray::transform's divide; one that
+    # leaves none inside, with delta lights; a jittered scene scaled by 0.37 and moved to (1000, -2000, 512); projective object
+    # matrices on a wall and a sphere.  Their scene.hit rays are carried into the world ("rays" says by which generator).
+    ("cbox@geom:-13", 32, 24, 6, True, 1024, (16, 12, 4)),
+    ("cbox_blob512_glass@geom:17", 32, 24, 6, True, 1024, (16, 12, 4)),
+    ("cbox@pose:38", 32, 24, 6, True, 1024, (16, 12, 4)),
+    ("cbox_deltalights@geom:21", 32, 24, 6, True, 1024, (16, 12, 4)),
+    ("random303@posef:0.37@move:b", 32, 24, 6, True, 1024, (16, 12, 4)),
+    ("cbox@proj:mixed", 32, 24, 6, True, 1024, (16, 12, 4)),
 ]
 BIG_BLAS = 4096   # node arrays longer than this are stored as digests
 SEED = 20260331
@@ -62,10 +73,13 @@ def main():
         ref = H.RefPT(scene, w, h, depth, use_bvh)
         xs, ys, ss = pt_sample_list(SEED, w, h, n)
         rgb, draws = ref.trace_samples(SEED, xs, ys, ss)
-        org, d, b = random_rays(SEED + 1, 2048)
+        rays = "scaled_rays" if "@" in name else "random_rays"
+        org, d, b = scaled_rays("random_rays", SEED + 1, 2048, scene) if "@" in name else random_rays(SEED + 1, 2048)
         hits = ref.hit(org, d, b)
         out = dict(meta=np.array([w, h, depth, int(use_bvh), n], np.int64), seed=np.array(SEED, np.uint64),
                    scene=np.array(name), scene_sha256=np.array(scene_digest(scene)), rgb=rgb, draws=draws, hits=hits)
+        if rays != "random_rays":
+            out["rays"] = np.array(rays)
         if use_bvh:
             boxes, links, order = ref.dump_bvh(-1)
             out.update(tlas_boxes=boxes, tlas_links=links, tlas_order=order[: len(scene["objects"])].copy())
@@ -82,7 +96,7 @@ def main():
             ew, eh, spp = ep
             r2 = H.RefPT(scene, ew, eh, depth, use_bvh)
             out.update(epoch=r2.epoch(SEED, 3, spp), epoch_meta=np.array([ew, eh, spp, 3], np.int64))
-        tag = f"pt_{name}_{w}x{h}_d{depth}_{'bvh' if use_bvh else 'list'}"
+        tag = f"pt_{golden_tag(name)}_{w}x{h}_d{depth}_{'bvh' if use_bvh else 'list'}"
         np.savez_compressed(os.path.join(HERE, tag + ".npz"), **out)
         finite = np.isfinite(rgb).all(axis=1)
         print(f"{tag}: {n} samples, {int(finite.sum())} finite, mean radiance {rgb[finite].mean():.4f}, "

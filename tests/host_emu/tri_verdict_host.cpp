@@ -35,3 +35,13 @@ extern "C" int tri_verdict_host(const float* tri, const float* org, const float*
   }
   return 0;
 }
+
+// Ray::transform's divide (object_testN, pt_wave.h: the rotated direction over its norm, divNx3<NR, false>): out[i] = the window
+// verdict div_in_range of lane i alone.  num: 3 floats per lane, den: 1.
+extern "C" int div_window_host(const float* num, const float* den, size_t lanes, uint32_t* out) {
+  for (size_t i = 0; i < lanes; i++) {
+    const float n[1][3] = {{num[3 * i], num[3 * i + 1], num[3 * i + 2]}};
+    out[i] = div_in_range<1, false>(n, den + i);
+  }
+  return 0;
+}

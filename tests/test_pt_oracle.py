@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import _harness as H
-from _cases import pt_sample_list, pt_scene, random_rays, scene_digest
+from _cases import pt_sample_list, pt_scene, scene_digest
 
 GOLDENS = sorted(glob.glob(os.path.join(H.GOLDEN, "pt_*.npz")))
 
@@ -43,7 +43,7 @@ def test_oracle_matches_reference_golden(path, math_mode):
     rgb, draws, rays = o.trace_samples(seed, xs, ys, ss)
     assert bits_equal(rgb, g["rgb"]), "per-sample radiance differs from the reference"
     assert np.array_equal(draws, g["draws"]), "RNG draw ledger differs from the reference"
-    org, d, b = random_rays(seed + 1, 2048)
+    org, d, b = H.golden_rays(g, scene, seed + 1)
     assert bits_equal(o.hit(org, d, b), g["hits"]), "scene.hit differs from the reference"
     if use_bvh:
         boxes, links, order = o.dump_bvh(-1)

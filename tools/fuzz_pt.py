@@ -2,7 +2,8 @@
 """Differential fuzzing of the path-tracer kernels: seeded random scenes (tests/_cases.py:random_pt_scene), epoch image of
 every kernel (auto, wave kernel, wave kernel with dead-ray elision, lane per sample, lane per pixel, flattened walk, the
 streamed forms with a small slot population on every third seed) against the CPU oracle, bit for bit, plus equal ray counts;
-odd seeds build every BVH on the device.  usage: fuzz_pt.py [first_seed] [count]"""
+odd seeds build every BVH on the device.  Seeds from 100000 draw lights, from 200000 environment maps, from 300000 a world off unit
+scale (translated, scaled in the geometry or the pose, now and then projective).  usage: fuzz_pt.py [first_seed] [count]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
