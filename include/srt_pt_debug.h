@@ -128,6 +128,11 @@ int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c
  * the three rays); out: 19 planes ({hit as 0 / 1, t, dist} of rays 0, 1, 2 from the batch form, the same nine from tri_hit, and
  * 1 where the lane's wave held an ambiguous lane and computed u and v after all; a wave is 64 consecutive lanes). */
 int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out);
+/* BBox::hit as the sweeps evaluate it (pt_wave.h: box_hit_inv - both products per axis, the select on the results) next to the
+ * form of the per-lane traversals (pt_trace.h: box_hit_rec - the bound selected first), lane i on its own operands.  in: 14 planes
+ * of `lanes` floats (box min xyz, box max xyz, origin xyz, reciprocal direction xyz, incoming times x and y); out: 6 planes ({hit
+ * as 0 / 1, times.x, times.y} of box_hit_inv, the same three of box_hit_rec). */
+int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out);
 
 #ifdef __cplusplus
 }

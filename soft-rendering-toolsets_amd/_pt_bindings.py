@@ -143,6 +143,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_tonemap_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p]
     lib.srt_pt_math_div_sqrt.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_int, c_void_p]
     lib.srt_pt_math_tri_verdict.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_math_box_sweep.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_sync.argtypes = [c_void_p]
     lib.srt_pt_cancel.argtypes = [c_void_p]
     lib.srt_pt_cancel_requested.argtypes = [c_void_p]
@@ -1133,6 +1134,18 @@ class Pathtracer:
         self._check(self._lib, self._lib.srt_pt_math_tri_verdict(self._ctx, _p(planes), n, _p(out)))
         form = lambda b: {"hit": out[b:b + 9:3].T != 0, "t": out[b + 1:b + 9:3].T.copy(), "dist": out[b + 2:b + 9:3].T.copy()}
         return form(0), form(9), int(np.count_nonzero(out[18, ::64]))
+
+    def math_box_sweep(self, box, org, inv, times):
+        """BBox::hit of the sweeps (box_hit_inv) and of the per-lane traversals (box_hit_rec) on n sets.  box (n, 6) = min, max;
+        org (n, 3); inv (n, 3) = reciprocal direction; times (n, 2).  Returns two dicts of (n,) arrays {"hit": bool, "tx", "ty"}."""
+        box, org, inv, times = _f32(box).reshape(-1, 6), _f32(org).reshape(-1, 3), _f32(inv).reshape(-1, 3), _f32(times).reshape(-1, 2)
+        n = len(box)
+        assert len(org) == n and len(inv) == n and len(times) == n and n > 0
+        planes = np.ascontiguousarray(np.concatenate([box, org, inv, times], axis=1).T)
+        out = np.zeros((6, n), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_box_sweep(self._ctx, _p(planes), n, _p(out)))
+        form = lambda b: {"hit": out[b] != 0, "tx": out[b + 1].copy(), "ty": out[b + 2].copy()}
+        return form(0), form(3)
 
     def math_cos_sin(self, x):
         x = _f32(x)

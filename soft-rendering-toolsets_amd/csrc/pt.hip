@@ -357,6 +357,25 @@ __global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes
   }
 }
 
+// BBox::hit of the sweeps (box_hit_inv, pt_wave.h: both products per axis, the select on the results) next to the form of the
+// per-lane traversals (box_hit_rec, pt_trace.h: the bound selected first), lane i on its own box, origin, reciprocal direction
+// and incoming `times`.  in: 14 planes of `lanes` floats (box min xyz, box max xyz, origin xyz, 1 / direction xyz, times x, y);
+// out: 6 planes - {hit as 0 / 1, times.x, times.y} of box_hit_inv, then the same of box_hit_rec.
+__global__ void pt_box_sweep_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= lanes) return;
+  float v[14];
+#pragma unroll
+  for (int j = 0; j < 14; j++) v[j] = in[(size_t)j * lanes + i];
+  const float bx[6] = {v[0], v[1], v[2], v[3], v[4], v[5]};
+  const V3 org = v3(v[6], v[7], v[8]), inv = v3(v[9], v[10], v[11]);
+  float ax = v[12], ay = v[13], bxx = v[12], bxy = v[13];
+  const bool ha = box_hit_inv(bx, org, inv, ax, ay);
+  const bool hb = box_hit_rec(bx, org, inv, bxx, bxy);
+  out[i] = ha ? 1.0f : 0.0f; out[lanes + i] = ax; out[2 * lanes + i] = ay;
+  out[3 * lanes + i] = hb ? 1.0f : 0.0f; out[4 * lanes + i] = bxx; out[5 * lanes + i] = bxy;
+}
+
 }  // namespace srt
 
 // ---------------------------------------------------------------------------------------------------
@@ -1786,6 +1805,11 @@ int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c
 int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out) {
   return math_round_trip(pt, "srt_pt_math_tri_verdict", {in}, 27 * lanes, {out}, 19 * lanes, [&](float* const* d, float* const* o) {
     pt_tri_verdict_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  return math_round_trip(pt, "srt_pt_math_box_sweep", {in}, 14 * lanes, {out}, 6 * lanes, [&](float* const* d, float* const* o) {
+    pt_box_sweep_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
 }
 
 

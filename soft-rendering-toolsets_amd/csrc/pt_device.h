@@ -697,7 +697,7 @@ SRT_DEV SphHit sphere_hit(float radius, const Ray& ray) {
   const float delta = sphere_two_roots(radius, ray, hit_two, t_two);
   const float t_one = sphere_tangent_root(ray);
   const bool two = delta > 0, one = delta == 0;
-  h.hit = two ? hit_two : one;
+  h.hit = (two & hit_two) | one;                     // == two ? hit_two : one (delta == 0 excludes delta > 0), without a bool select
   h.t = two ? t_two : (one ? t_one : 0.0f);
   return h;
 }
@@ -715,8 +715,8 @@ SRT_DEV void sphere_hitN(float radius, V3 org, const V3* d, const float* b0, con
     const float delta = sphere_two_roots(radius, ray[r], hit_two, t_two);
     const bool two = delta > 0;
     one[r] = delta == 0;
-    any_one = any_one || one[r];
-    h[r].hit = two ? hit_two : one[r];
+    any_one = any_one | one[r];
+    h[r].hit = (two & hit_two) | one[r];               // == two ? hit_two : one[r] (delta == 0 excludes delta > 0), without a bool select
     h[r].t = two ? t_two : 0.0f;
   }
   if (__ballot(any_one) != 0ull) {

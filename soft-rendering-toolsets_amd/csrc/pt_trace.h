@@ -155,6 +155,47 @@ SRT_DEV void fold(Hit& best, bool hit, float dist, uint32_t obj, uint32_t tri) {
   else { best.hit = false; best.dist = 0.0f; best.obj = 0; best.tri = 0; }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The closest hit in the two-word form the sweeps of pt_wave.h carry from a leaf to the root and keep in their LDS slots:
+// id = object slot << shift | triangle, kRetMiss for "no hit"; a miss has dist == +0 (the default Trace).  `hit` is
+// id != kRetMiss wherever a rule reads it.  Every function below keeps "miss => dist == +0" provided its inputs do, and
+// computes what its four-field counterpart computes (tests/test_pt_sweep_forms_host.py enumerates both); a select of the
+// pair is two v_cndmask instead of four, and the verdicts are mask algebra (`&`, `|`, `!` on comparisons stay in scalar
+// mask registers; `a && b`, `c ? a : b` on bools may go through a 0 / 1 register and a compare).
+constexpr uint32_t kRetMiss = 0xFFFFFFFFu;
+constexpr uint32_t kRetMissEnv = 0xFFFFFFFEu;   // miss, and the environment light is visible along the (camera) ray
+struct PHit { float dist; uint32_t id; };
+SRT_DEV PHit packed_miss() { PHit p; p.dist = 0.0f; p.id = kRetMiss; return p; }
+// Trace::min's choice as a mask: left_wins(lhit, ldist, rhit, rdist)
+SRT_DEV bool left_wins_mask(bool lhit, float ldist, bool rhit, float rdist) { return lhit & (!rhit | (ldist < rdist)); }
+// fold(best, hit, dist, obj, tri) with id = obj << shift | tri.  left_wins(b, ., false, .) == b: a candidate that is a miss either
+// loses or meets a `best` that is a miss already, so only a hit that is not beaten changes anything (the ordered triangle fold of
+// object_testN is written the same way).
+SRT_DEV void packed_fold(PHit& best, bool hit, float dist, uint32_t id) {
+  const bool take = hit & !((best.id != kRetMiss) & (best.dist < dist));
+  best.dist = take ? dist : best.dist;
+  best.id = take ? id : best.id;
+}
+// One node of find_closest_hit from its children's results (student/bvh.inl:182-221): `hit_any` either child box was hit (else
+// the node returns the default Trace), `left_nearer` the left child is visited first, `hitboth`, `farx` = cur_far_t.x.
+// ret = nearer child's result; the farther child is visited iff farx < ret.distance || (!ret.hit && hitboth), and then
+// ret = Trace::min(ret, farther) - which is the farther child's result itself whenever the nearer one does not win (a miss is
+// the default Trace in both forms).  What the traversal would not have visited is computed by the sweeps all the same and
+// simply not selected here.
+SRT_DEV PHit packed_combine(PHit l, PHit r, bool hit_any, bool left_nearer, bool hitboth, float farx) {
+  PHit rc, rs;
+  rc.dist = left_nearer ? l.dist : r.dist; rc.id = left_nearer ? l.id : r.id;
+  rs.dist = left_nearer ? r.dist : l.dist; rs.id = left_nearer ? r.id : l.id;
+  const bool rc_hit = rc.id != kRetMiss, rs_hit = rs.id != kRetMiss;
+  const bool visit = (farx < rc.dist) | (!rc_hit & hitboth);
+  const bool far_taken = hit_any & visit & !left_wins_mask(rc_hit, rc.dist, rs_hit, rs.dist);
+  const bool near_kept = hit_any & !far_taken;
+  PHit ret;
+  ret.dist = far_taken ? rs.dist : (near_kept ? rc.dist : 0.0f);
+  ret.id = far_taken ? rs.id : (near_kept ? rc.id : kRetMiss);
+  return ret;
+}
+
 // BBox::hit on a record's child box with the reciprocal direction hoisted, straight-line form.
 SRT_DEV bool box_hit_rec(const float* __restrict__ bx, V3 o, V3 inv, float& tx, float& ty) {
   const bool sx = inv.x < 0, sy = inv.y < 0, sz = inv.z < 0;

@@ -164,28 +164,34 @@ SRT_DEV bool box_hit_inv(const float* __restrict__ bx, V3 o, V3 inv, float& tx, 
   // the six bounds are read into values first: `c ? bx[3] : bx[0]` on the memory operands is an lvalue select,
   // i.e. one per-lane vector load from a selected address instead of two wave-uniform scalar loads
   const float b0 = bx[0], b1 = bx[1], b2 = bx[2], b3 = bx[3], b4 = bx[4], b5 = bx[5];
-  float tmin = ((sx ? b3 : b0) - o.x) * inv.x;
-  float tmax = ((sx ? b0 : b3) - o.x) * inv.x;
-  const float tymin = ((sy ? b4 : b1) - o.y) * inv.y;
-  const float tymax = ((sy ? b1 : b4) - o.y) * inv.y;
-  const bool miss_y = (tmin > tymax) || (tymin > tmax);
+  // Both products per axis, then the select: the bounds are wave-uniform (SGPRs) and a vector instruction reads one scalar
+  // operand, so `(sx ? b3 : b0) - o.x` costs a move of one bound into a VGPR and a select before the subtraction.  Selecting
+  // between the two finished products is the same value bit for bit (a select commutes with a pure function of the selected
+  // operand, NaN included) and every instruction has one scalar operand.
+  const float lx = (b0 - o.x) * inv.x, hx = (b3 - o.x) * inv.x;
+  const float ly = (b1 - o.y) * inv.y, hy = (b4 - o.y) * inv.y;
+  const float lz = (b2 - o.z) * inv.z, hz = (b5 - o.z) * inv.z;
+  float tmin = sx ? hx : lx;
+  float tmax = sx ? lx : hx;
+  const float tymin = sy ? hy : ly;
+  const float tymax = sy ? ly : hy;
+  const bool miss_y = (tmin > tymax) | (tymin > tmax);
   tmin = (tymin > tmin) ? tymin : tmin;
   tmax = (tymax < tmax) ? tymax : tmax;
-  const float tzmin = ((sz ? b5 : b2) - o.z) * inv.z;
-  const float tzmax = ((sz ? b2 : b5) - o.z) * inv.z;
-  const bool miss_z = (tmin > tzmax) || (tzmin > tmax);
+  const float tzmin = sz ? hz : lz;
+  const float tzmax = sz ? lz : hz;
+  const bool miss_z = (tmin > tzmax) | (tzmin > tmax);
   tmin = (tzmin > tmin) ? tzmin : tmin;
   tmax = (tzmax < tmax) ? tzmax : tmax;
-  const bool hit = !miss_y && !miss_z;
-  const float nx = (tmin >= tx && tmin <= ty) ? tmin : tx;
-  const float ny = (tmax >= nx && tmax <= ty) ? tmax : ty;
+  const bool hit = !(miss_y | miss_z);
+  const float nx = ((tmin >= tx) & (tmin <= ty)) ? tmin : tx;
+  const float ny = ((tmax >= nx) & (tmax <= ty)) ? tmax : ty;
   tx = hit ? nx : tx;
   ty = hit ? ny : ty;
   return hit;
 }
 
-constexpr uint32_t kRetMiss = 0xFFFFFFFFu;
-constexpr uint32_t kRetMissEnv = 0xFFFFFFFEu;   // miss, and the environment light is visible along the (camera) ray
+// (kRetMiss / kRetMissEnv and the two-word PHit the sweeps carry: pt_trace.h)
 // (the sweep builds take <= 16 objects: 5 + 27 bits; the streamed build passes the scene's own split)
 SRT_DEV uint32_t pack_ret(const Hit& h, uint32_t shift = 27u) { return h.hit ? ((h.obj << shift) | h.tri) : kRetMiss; }
 SRT_DEV Hit unpack_ret(float dist, uint32_t id, uint32_t shift = 27u) {
@@ -353,7 +359,7 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
   }
   bool any = false;
 #pragma unroll
-  for (int r = 0; r < NR; r++) any = any || hit[r];
+  for (int r = 0; r < NR; r++) any = any | hit[r];
   if (xf && __ballot(any) != 0ull) {
     const V3 ow = mat_point_uniform(o.trans, oorg);   // Trace::transform: distance = |T*position - T*origin|
     float n2[NR], nr[NR];
@@ -963,14 +969,17 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
       SECTION_END(ST_LEAVES)
     } else if (Q == 0) {
       // List<Object>::hit, or a BVH<Object> whose root is a leaf: ordered fold over every object
+      PHit acc[NR];
 #pragma unroll
-      for (int r = 0; r < NR; r++) res[r] = no_hit();
+      for (int r = 0; r < NR; r++) acc[r] = packed_miss();
       for (uint32_t k = 0; k < nobj; k++) {
         bool h[NR]; float dd[NR]; uint32_t tt[NR];
         object_testN<LAZY, NR, TRAV == 4>(S, k, org, d, rb0, rb1, cnt, h, dd, tt, act, cidx, &P, lane_global, pass == 1, &emit_mask);
 #pragma unroll
-        for (int r = 0; r < NR; r++) fold(res[r], h[r], dd[r], k, tt[r]);
+        for (int r = 0; r < NR; r++) packed_fold(acc[r], h[r], dd[r], (k << 27) | tt[r]);
       }
+#pragma unroll
+      for (int r = 0; r < NR; r++) res[r] = unpack_ret(acc[r].dist, acc[r].id);
     } else {
       V3 inv[NR];
       float tx0[NR], ty0[NR];
@@ -995,8 +1004,9 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
           const bool hr = box_hit_inv(W.boxr, org, inv[r], t2x, t2y);
           // closer/second as in student/bvh.inl:186-209: both hit -> smaller entry time first (ties: right);
           // one hit -> that one, the other child gets ray.dist_bounds as its `times`
-          const bool hb = hl && hr;
-          const bool cl = hb ? (t1x < t2x) : hl;
+          // (mask algebra, not `hb ? (t1x < t2x) : hl`: a bool chosen by a bool goes through a 0 / 1 register and back)
+          const bool hb = hl & hr;
+          const bool cl = (hb & (t1x < t2x)) | (!hb & hl);
           const float cx = cl ? t1x : t2x, cy = cl ? t1y : t2y;
           const float fx = hb ? (cl ? t2x : t1x) : rb0[r];
           const float fy = hb ? (cl ? t2y : t1y) : rb1[r];
@@ -1010,7 +1020,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
       // bottom-up: leaves are evaluated in place, interior children read back, then the visit rule + Trace::min
       for (int q = (int)Q - 1; q >= 0; q--) {
         const WaveInterior& W = S.wave_tlas[q];
-        Hit L[NR], R[NR];
+        PHit L[NR], R[NR];                               // child results in the slot form (pt_trace.h), unpacked once after the root
         // A leaf child that holds a mesh with a real BVH<Triangle> is evaluated after its sibling and only for the rays
         // whose traversal can reach it: find_closest_hit visits the nearer child, and the other one iff
         // `cur_far_t.x < ret.distance || (!ret.hit && hitboth)` (student/bvh.inl:216) - whether node q itself is reached is
@@ -1021,31 +1031,31 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
           const Object& ob = S.objects[(uint32_t)~ref];
           return ob.kind == OBJ_MESH && ob.use_bvh != 0u && ob.nrec > 0u;
         };
-        auto eval_child = [&](int32_t ref, uint32_t n, Hit* out, const bool* need) {
+        auto eval_child = [&](int32_t ref, uint32_t n, PHit* out, const bool* need) {
           if (ref >= 0) {
 #pragma unroll
-            for (int r = 0; r < NR; r++) out[r] = unpack_ret(SLOT(ref, r, 0), __float_as_uint(SLOT(ref, r, 1)));
+            for (int r = 0; r < NR; r++) { out[r].dist = SLOT(ref, r, 0); out[r].id = __float_as_uint(SLOT(ref, r, 1)); }
           } else {
 #pragma unroll
-            for (int r = 0; r < NR; r++) out[r] = no_hit();
+            for (int r = 0; r < NR; r++) out[r] = packed_miss();
             const uint32_t first = (uint32_t)~ref;
             for (uint32_t k = first; k < first + n; k++) {
               bool h[NR]; float dd[NR]; uint32_t tt[NR];
               // (TRAV 4: a mesh with a real BVH<Triangle> is a leaf of its own - checked on the host - and goes through `queued`)
               object_testN<TRAV == 1, NR>(S, k, org, d, rb0, rb1, cnt, h, dd, tt, need, cidx);
 #pragma unroll
-              for (int r = 0; r < NR; r++) fold(out[r], h[r], dd[r], k, tt[r]);
+              for (int r = 0; r < NR; r++) packed_fold(out[r], h[r], dd[r], (k << 27) | tt[r]);
             }
           }
         };
-        auto need_of = [&](bool is_left, const Hit* other, bool other_known, bool* need) {
+        auto need_of = [&](bool is_left, const PHit* other, bool other_known, bool* need) {
 #pragma unroll
           for (int r = 0; r < NR; r++) {
             const uint32_t f = (uint32_t)(fl[r] >> (4 * q)) & 15u;
             const bool nearer = ((f & 4u) != 0) == is_left;
             const float farx = (q != 0) ? SLOT(q, r, 0) : farx0[r];
-            const bool second = !other_known || farx < other[r].dist || (!other[r].hit && (f & 8u));
-            need[r] = act[r] && (f & 3u) != 0 && (nearer || second);
+            const bool second = !other_known | (farx < other[r].dist) | ((other[r].id == kRetMiss) & ((f & 8u) != 0));
+            need[r] = act[r] & ((f & 3u) != 0) & (nearer | second);
           }
         };
         if constexpr (!LAZY) {                           // no per-lane walks: both children straight, in order
@@ -1059,16 +1069,16 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
           // counts as unknown (a superset again; what is not needed is never selected).
           const uint32_t lz = S.wave_lazy[q];
           const bool lazy_l = lazy_leaf(W.l_ref, W.l_cnt), lazy_r = lazy_leaf(W.r_ref, W.r_cnt);
-          auto queued = [&](int32_t ref, bool is_left, const Hit* other, bool other_known, Hit* out) {
+          auto queued = [&](int32_t ref, bool is_left, const PHit* other, bool other_known, PHit* out) {
             bool need[NR], h[NR]; float dd[NR]; uint32_t tt[NR];
             need_of(is_left, other, other_known, need);
             const uint32_t k = (uint32_t)~ref;
             object_queueN<NR>(S, k, org, d, rb0, rb1, h, dd, tt, need, P, lane_global, pass == 1, emit_mask);
 #pragma unroll
-            for (int r = 0; r < NR; r++) { out[r] = no_hit(); fold(out[r], h[r], dd[r], k, tt[r]); }
+            for (int r = 0; r < NR; r++) { out[r] = packed_miss(); packed_fold(out[r], h[r], dd[r], (k << 27) | tt[r]); }
           };
 #pragma unroll
-          for (int r = 0; r < NR; r++) { L[r] = no_hit(); R[r] = no_hit(); }
+          for (int r = 0; r < NR; r++) { L[r] = packed_miss(); R[r] = packed_miss(); }
           if (pass == 1) {
             // The probe pass needs no result, only the requests: the sibling counts as unknown for every ray (3 % more
             // requests than with the visit rule applied to a known sibling), and nothing else of the bottom-up sweep runs
@@ -1088,9 +1098,9 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         // mesh counts as unknown (a superset again; what is not needed is never selected)
         const uint32_t lz = (TRAV == 4) ? S.wave_lazy[q] : 0u;
         const bool right_first = lazy_l && !lazy_r;      // the sibling of a lazy leaf goes first
-        Hit first_out[NR];
+        PHit first_out[NR];
 #pragma unroll
-        for (int r = 0; r < NR; r++) { first_out[r] = no_hit(); L[r] = no_hit(); R[r] = no_hit(); }
+        for (int r = 0; r < NR; r++) { first_out[r] = packed_miss(); L[r] = packed_miss(); R[r] = packed_miss(); }
         // one call site for both children (a loop that is not unrolled): the leaf tests are most of the kernel's code
 #pragma nounroll
         for (int t = 0; t < 2; t++) {
@@ -1103,7 +1113,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
 #pragma unroll
             for (int r = 0; r < NR; r++) need[r] = act[r];
           }
-          Hit out[NR];
+          PHit out[NR];
           eval_child(ref, n, out, need);
 #pragma unroll
           for (int r = 0; r < NR; r++) {
@@ -1116,19 +1126,11 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
 #pragma unroll
         for (int r = 0; r < NR; r++) {
           const uint32_t f = (uint32_t)(fl[r] >> (4 * q)) & 15u;
-          const bool cl = (f & 4u) != 0;
-          const Hit rc = cl ? L[r] : R[r];
-          const Hit rs = cl ? R[r] : L[r];
-          Hit ret = no_hit();
-          if (f & 3u) {
-            ret = rc;
-            const float farx = (q != 0) ? SLOT(q, r, 0) : farx0[r];
-            if (farx < rc.dist || (!rc.hit && (f & 8u))) {       // student/bvh.inl:216
-              if (!left_wins(rc.hit, rc.dist, rs.hit, rs.dist)) ret = rs.hit ? rs : no_hit();
-            }
-          }
-          if (q > 0) { SLOT(q, r, 0) = ret.dist; SLOT(q, r, 1) = __uint_as_float(pack_ret(ret)); }
-          else res[r] = ret;
+          const float farx = (q != 0) ? SLOT(q, r, 0) : farx0[r];
+          // the visit rule (student/bvh.inl:216) and Trace::min on the two-word form: packed_combine, pt_trace.h
+          const PHit ret = packed_combine(L[r], R[r], (f & 3u) != 0, (f & 4u) != 0, (f & 8u) != 0, farx);
+          if (q > 0) { SLOT(q, r, 0) = ret.dist; SLOT(q, r, 1) = __uint_as_float(ret.id); }
+          else res[r] = unpack_ret(ret.dist, ret.id);
         }
         SECTION_END(ST_COMBINE)
       }
