@@ -128,6 +128,13 @@ int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c
  * the three rays); out: 19 planes ({hit as 0 / 1, t, dist} of rays 0, 1, 2 from the batch form, the same nine from tri_hit, and
  * 1 where the lane's wave held an ambiguous lane and computed u and v after all; a wave is 64 consecutive lanes). */
 int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out);
+/* The wave kernel's batch Sphere::hit (pt_device.h: sphere_hitN<3>, whose tangent root is computed wave-uniformly, then the distance
+ * step of Object::hit through sqrtN, as the sphere branch of object_testN in pt_wave.h performs it) next to the plain per-ray form
+ * (sphere_hit and |Ray::at(t) - origin|), lane i on its own radius, origin and three rays.  in: 19 planes of `lanes` floats (radius,
+ * origin xyz, direction xyz of rays 0, 1, 2, dist_bounds.x of the three rays, dist_bounds.y of the three rays); out: 22 planes ({hit
+ * as 0 / 1, t, dist} of rays 0, 1, 2 from the batch form, the same nine from the plain form, delta of rays 0, 1, 2, and 1 where the
+ * lane's wave held a lane with delta == 0 and computed the tangent root; a wave is 64 consecutive lanes). */
+int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* out);
 /* BBox::hit as the sweeps evaluate it (pt_wave.h: box_hit_inv - both products per axis, the select on the results) next to the
  * form of the per-lane traversals (pt_trace.h: box_hit_rec - the bound selected first), lane i on its own operands.  in: 14 planes
  * of `lanes` floats (box min xyz, box max xyz, origin xyz, reciprocal direction xyz, incoming times x and y); out: 6 planes ({hit

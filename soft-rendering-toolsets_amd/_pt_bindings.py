@@ -144,6 +144,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_math_div_sqrt.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_int, c_void_p]
     lib.srt_pt_math_tri_verdict.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_box_sweep.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_math_sphere_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_sync.argtypes = [c_void_p]
     lib.srt_pt_cancel.argtypes = [c_void_p]
     lib.srt_pt_cancel_requested.argtypes = [c_void_p]
@@ -1134,6 +1135,20 @@ class Pathtracer:
         self._check(self._lib, self._lib.srt_pt_math_tri_verdict(self._ctx, _p(planes), n, _p(out)))
         form = lambda b: {"hit": out[b:b + 9:3].T != 0, "t": out[b + 1:b + 9:3].T.copy(), "dist": out[b + 2:b + 9:3].T.copy()}
         return form(0), form(9), int(np.count_nonzero(out[18, ::64]))
+
+    def math_sphere_batch(self, radius, org, dirs, bounds):
+        """The wave kernel's batch Sphere::hit (sphere_hitN<3> and the distance step of object_testN's sphere branch)
+        and the plain sphere_hit on n (radius, origin, three rays) sets.  radius (n,); org (n, 3); dirs (n, 3, 3); bounds (n, 3, 2) =
+        dist_bounds of each ray.  Returns (batch, plain, delta, tangent): two dicts of (n, 3) arrays {"hit": bool, "t", "dist"}, the
+        plain form's delta (n, 3), and per set whether its wave (64 consecutive sets) computed the tangent root."""
+        radius, org, dirs, bounds = _f32(radius).reshape(-1, 1), _f32(org).reshape(-1, 3), _f32(dirs).reshape(-1, 9), _f32(bounds).reshape(-1, 3, 2)
+        n = len(radius)
+        assert len(org) == n and len(dirs) == n and len(bounds) == n and n > 0
+        planes = np.ascontiguousarray(np.concatenate([radius, org, dirs, bounds[:, :, 0], bounds[:, :, 1]], axis=1).T)
+        out = np.zeros((22, n), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_sphere_batch(self._ctx, _p(planes), n, _p(out)))
+        form = lambda b: {"hit": out[b:b + 9:3].T != 0, "t": out[b + 1:b + 9:3].T.copy(), "dist": out[b + 2:b + 9:3].T.copy()}
+        return form(0), form(9), out[18:21].T.copy(), out[21] != 0
 
     def math_box_sweep(self, box, org, inv, times):
         """BBox::hit of the sweeps (box_hit_inv) and of the per-lane traversals (box_hit_rec) on n sets.  box (n, 6) = min, max;

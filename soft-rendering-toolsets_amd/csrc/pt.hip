@@ -357,6 +357,63 @@ __global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes
   }
 }
 
+// Sphere::hit of the wave kernel's batch (sphere_hitN<3> and the distance step through sqrtN, as object_testN's sphere branch in
+// pt_wave.h performs them - restated below, since moving the branch into a function of its own changed a wave kernel's scratch)
+// next to the plain per-ray form (sphere_hit, then the distance as object_hit has it, pt_trace.h), lane i on its own radius,
+// origin and three rays.  in: 19 planes of `lanes` floats (radius, origin, three directions, then b0 and b1 of the three
+// rays); out: 22 planes - {hit, t, dist} x 3 rays of the batch form, the same of the plain form, delta of the three rays
+// (sphere_two_roots), and "this lane's wave computed the tangent root" (a lane with delta == 0 in it).
+__global__ void pt_sphere_batch_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t k = i < lanes ? i : lanes - 1;           // every lane of the last wave computes; the spares repeat the last lane
+  float v[19];
+#pragma unroll
+  for (int j = 0; j < 19; j++) v[j] = in[(size_t)j * lanes + k];
+  const float radius = v[0];
+  const V3 org = v3(v[1], v[2], v[3]);
+  V3 d[3], pos[3];
+  float b0[3], b1[3], tb[3], db[3];
+  bool hb[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) { d[r] = v3(v[4 + 3 * r], v[5 + 3 * r], v[6 + 3 * r]); b0[r] = v[13 + r]; b1[r] = v[16 + r]; }
+  bool tangent = false;
+  {                                                     // the sphere branch of object_testN (pt_wave.h), line for line: change both
+    constexpr int NR = 3;
+    SphHit sh[NR];
+    sphere_hitN<NR>(radius, org, d, b0, b1, sh, &tangent);
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      hb[r] = sh[r].hit; tb[r] = sh[r].t;
+      pos[r] = org + d[r] * sh[r].t;                    // Ray::at
+    }
+    float n2[NR], nr[NR];
+    bool miss[NR];                                      // no hit: t = 0, pos == origin
+#pragma unroll
+    for (int r = 0; r < NR; r++) { n2[r] = norm2(pos[r] - org); miss[r] = !hb[r]; }
+    sqrtN<NR>(n2, miss, nr);
+#pragma unroll
+    for (int r = 0; r < NR; r++) db[r] = fabsf(nr[r]);
+  }
+  if (i < lanes) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
+      const SphHit hp = sphere_hit(radius, ray);
+      bool hit_two;
+      float t_two;
+      const float delta = sphere_two_roots(radius, ray, hit_two, t_two);
+      out[(size_t)(3 * r) * lanes + i] = hb[r] ? 1.0f : 0.0f;
+      out[(size_t)(3 * r + 1) * lanes + i] = tb[r];
+      out[(size_t)(3 * r + 2) * lanes + i] = db[r];
+      out[(size_t)(9 + 3 * r) * lanes + i] = hp.hit ? 1.0f : 0.0f;
+      out[(size_t)(10 + 3 * r) * lanes + i] = hp.t;
+      out[(size_t)(11 + 3 * r) * lanes + i] = fabsf(norm(ray_at(ray, hp.t) - ray.o));
+      out[(size_t)(18 + r) * lanes + i] = delta;
+    }
+    out[(size_t)21 * lanes + i] = tangent ? 1.0f : 0.0f;
+  }
+}
+
 // BBox::hit of the sweeps (box_hit_inv, pt_wave.h: both products per axis, the select on the results) next to the form of the
 // per-lane traversals (box_hit_rec, pt_trace.h: the bound selected first), lane i on its own box, origin, reciprocal direction
 // and incoming `times`.  in: 14 planes of `lanes` floats (box min xyz, box max xyz, origin xyz, 1 / direction xyz, times x, y);
@@ -1805,6 +1862,11 @@ int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c
 int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out) {
   return math_round_trip(pt, "srt_pt_math_tri_verdict", {in}, 27 * lanes, {out}, 19 * lanes, [&](float* const* d, float* const* o) {
     pt_tri_verdict_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  return math_round_trip(pt, "srt_pt_math_sphere_batch", {in}, 19 * lanes, {out}, 22 * lanes, [&](float* const* d, float* const* o) {
+    pt_sphere_batch_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
 }
 
 int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out) {

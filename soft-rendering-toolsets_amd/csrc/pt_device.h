@@ -702,9 +702,10 @@ SRT_DEV SphHit sphere_hit(float radius, const Ray& ray) {
   return h;
 }
 // Sphere::hit for the N rays of a batch (shared origin), wave-uniformly: the tangent root (a full divide that only a lane with
-// delta == 0 reads) is computed when some lane of the wave has such a ray, which is next to never.
+// delta == 0 reads) is computed when some lane of the wave has such a ray, which is next to never (*tangent, when given, is set
+// then: wave-uniform).
 template <int N>
-SRT_DEV void sphere_hitN(float radius, V3 org, const V3* d, const float* b0, const float* b1, SphHit* h) {
+SRT_DEV void sphere_hitN(float radius, V3 org, const V3* d, const float* b0, const float* b1, SphHit* h, bool* tangent = nullptr) {
   Ray ray[N];
   bool one[N], any_one = false;
 #pragma unroll
@@ -722,6 +723,7 @@ SRT_DEV void sphere_hitN(float radius, V3 org, const V3* d, const float* b0, con
   if (__ballot(any_one) != 0ull) {
 #pragma unroll
     for (int r = 0; r < N; r++) h[r].t = one[r] ? sphere_tangent_root(ray[r]) : h[r].t;
+    if (tangent) *tangent = true;
   }
 }
 

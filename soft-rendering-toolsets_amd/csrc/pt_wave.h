@@ -242,7 +242,7 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
     }
   }
   V3 pos[NR];
-  if (o.kind == OBJ_SPHERE) {
+  if (o.kind == OBJ_SPHERE) {                         // (restated line for line in pt_sphere_batch_kernel, pt.hip: change both)
     SphHit sh[NR];
     sphere_hitN<NR>(o.radius, oorg, od, ob0, ob1, sh);
 #pragma unroll

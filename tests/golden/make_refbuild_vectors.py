@@ -4,12 +4,16 @@ tests in tests/test_raster_oracle.py and tests/test_pt_oracle.py and what oracle
 
 Run where the reference checkout is present and `make -C oracle ref` has built oracle/_ref:
 
-    python tests/golden/make_refbuild_vectors.py
+    python tests/golden/make_refbuild_vectors.py            (every fixture)
+    python tests/golden/make_refbuild_vectors.py sphere     (refbuild_sphere_edges.npz alone)
 
 refbuild_raster_random.npz  per supersample rate and seed: the primitive stream, the reference's RGBA8 and the SHA-256 of
                             its float supersample buffer
 refbuild_pt_samples.npz     per scene: its digest, the sample list, the reference's per-sample radiance and RNG draw counts
 refbuild_tonemap.npz        per seed: the radiance image (NaN and negative values included), the exposure, the reference's bytes
+refbuild_sphere_edges.npz   the Sphere::hit edge sets of tests/_sphere_cases.py (fixture_sets: tangents, the validity chain, special
+                            operands), the reference's scene.hit records {hit, distance, position, normal} of their rays on one-sphere
+                            scenes - the sphere at the origin, and at (0.3, -0.2, 0.1) scaled (1.5, 0.5, 2) - and the scenes' digests
 """
 import os
 import sys
@@ -20,6 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import _harness as H  # noqa: E402
+import _sphere_cases as SPH  # noqa: E402
 from _cases import adversarial_stream, pt_sample_list, pt_scene, random_triangles, scene_digest, tonemap_image  # noqa: E402
 
 RASTER_W, RASTER_H = 83, 59
@@ -43,8 +48,38 @@ def tonemap_input(seed):
     return rgb
 
 
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def sphere_edges():
+    index, radius, org, dirs, bounds, family, step = SPH.fixture_sets()
+    rr, oo, dd, bb = SPH.rays_of(radius, org, dirs, bounds)
+    assert len(rr) <= 20000 and set(family.tolist()) == set(range(len(SPH.FAMILIES)))
+    out = {"seed": np.int64(SPH.FIXTURE_SEED), "index": index, "radius": radius, "org": org, "dirs": dirs, "bounds": bounds,
+           "family": family, "step": step, "families": np.array(SPH.FAMILIES)}
+    for kind in SPH.SCENE_KINDS:
+        rec = SPH.scene_hits(lambda scene: H.RefPT(scene, 8, 8, 4, True), rr, oo, dd, bb, kind)
+        assert (rec[:, 8] == np.where(rec[:, 0] != 0, 0.0, rec[:, 8])).all()      # (the material of a hit is the scene's one)
+        out[f"ref_{kind}"] = rec[:, :8].copy()
+        out[f"scene_sha256_{kind}"] = np.array(SPH.scenes_digest(rr, kind, scene_digest))
+    path = os.path.join(HERE, "refbuild_sphere_edges.npz")
+    np.savez_compressed(path, **out)
+    # the stored inputs are what the generator of the cases makes today
+    g = np.load(path)
+    again = SPH.fixture_sets()
+    for key, a in zip(("index", "radius", "org", "dirs", "bounds", "family", "step"), again):
+        assert same_bits(g[key], a), key
+    print("wrote refbuild_sphere_edges.npz", os.path.getsize(path), "bytes,", len(rr), "rays, hits",
+          {kind: int((out[f"ref_{kind}"][:, 0] != 0).sum()) for kind in SPH.SCENE_KINDS})
+
+
 def main():
     assert H.ref_raster() is not None and H.ref_pt_lib() is not None, "build oracle/_ref first: make -C oracle ref"
+    if sys.argv[1:] == ["sphere"]:
+        return sphere_edges()
+    sphere_edges()
     out = {}
     for sr in RASTER_RATES:
         for seed in RASTER_SEEDS:
