@@ -141,6 +141,12 @@ int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* o
  * as 0 / 1, times.x, times.y} of box_hit_inv, the same three of box_hit_rec). */
 int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out);
 
+/* The HIP resources the library holds at this moment, process-wide (every path-tracer and rasterizer context, skin and timeline):
+ * out = {device buffers, pinned host buffers, events}.  Each counts the live allocations, not their bytes.  A test reads it before
+ * and after a sequence of calls that ends with the destroys: equal readings mean nothing leaked and nothing was freed twice.
+ * Needs no context and no device. */
+int srt_pt_live_resources(uint64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif

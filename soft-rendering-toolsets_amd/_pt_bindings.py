@@ -86,6 +86,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_skin_pose_refit_at.argtypes = [c_void_p, c_void_p, c_float, c_int]
     lib.srt_pt_rig_posed_host.argtypes = [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]
     lib.srt_pt_math_hypot.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_live_resources.argtypes = [c_void_p]
     lib.srt_pt_timeline_create.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.srt_pt_timeline_destroy.argtypes = [c_void_p]
     lib.srt_pt_timeline_transforms.argtypes = [c_void_p, c_float, c_void_p]
@@ -173,6 +174,15 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.hipSetDevice.argtypes = [c_int]
     lib.hipMemcpyAsync.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
     lib.hipStreamSynchronize.argtypes = [c_void_p]
+
+
+def live_resources() -> tuple:
+    """srt_pt_live_resources: the (device buffers, pinned buffers, events) the library holds right now, process-wide."""
+    from . import _check, load_library
+    lib = load_library()
+    out = np.zeros(3, np.uint64)
+    _check(lib, lib.srt_pt_live_resources(out.ctypes.data_as(c_void_p)))
+    return tuple(int(v) for v in out)
 
 
 def _p(a):

@@ -444,8 +444,8 @@ namespace {
 
 // After a synchronisation: did a streamed launch end with unfinished units (pt_stream_finish_kernel)?  Reported once.
 int check_stream_fault(srt_pt* pt, const char* what) {
-  if (pt->h_fault && *(volatile uint32_t*)pt->h_fault != 0u) {
-    *(volatile uint32_t*)pt->h_fault = 0u;
+  if (pt->h_fault && *(volatile uint32_t*)pt->h_fault.get() != 0u) {
+    *(volatile uint32_t*)pt->h_fault.get() = 0u;
     return srt::fail(SRT_ERR_STATE, "%s: a streamed launch ended before every work unit was finished (generation bound too small); the epoch's image is invalid", what);
   }
   return SRT_OK;
@@ -480,7 +480,7 @@ bool elision_provable(const srt_pt* pt) {
 DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B = nullptr) {
   const FlatScene& F = pt->built.flat;
   DScene S;
-  S.ray_log = B ? B->d_ray_log : nullptr; S.ray_log_cap = B ? B->ray_log_cap : 0u;
+  S.ray_log = B ? B->d_ray_log.get() : nullptr; S.ray_log_cap = B ? B->ray_log_cap : 0u;
   S.nodes = pt->d_nodes; S.tris = pt->d_tris; S.tri_nrm = pt->d_nrm; S.objects = pt->d_objects;
   S.lights = pt->d_lights; S.light_tris = pt->d_ltris; S.materials = pt->d_mats;
   S.wave_tlas = pt->d_wave; S.wave_q = (uint32_t)F.wave_tlas.size(); S.blas_recs = pt->d_blas; S.wave_lazy = pt->d_wave_lazy;
@@ -510,16 +510,17 @@ int stream_buffers(srt_pt* pt, hipStream_t s, srt_pt::EpochBuffers** out) {
   srt_pt::EpochBuffers& B = pt->epoch_buffers[s];
   // (hipMemsetAsync ON `s`: a plain hipMemset is ordered on the null stream only, which the callers' non-blocking streams do not wait
   //  for - a kernel on `s` could still see what the allocation held before)
+  int st;
   if (!B.d_cancel) {
-    SRT_HIP(hipMalloc(&B.d_cancel, sizeof(uint32_t)));
+    if ((st = B.d_cancel.ensure(1))) return st;
     SRT_HIP(hipMemsetAsync(B.d_cancel, 0, sizeof(uint32_t), s));
   }
   if (B.ray_log_cap != pt->ray_log_cap) {
-    if (B.d_ray_log) { SRT_HIP(hipStreamSynchronize(s)); SRT_HIP(hipFree(B.d_ray_log)); B.d_ray_log = nullptr; }
+    if (B.d_ray_log) { SRT_HIP(hipStreamSynchronize(s)); B.d_ray_log.reset(); }
     B.ray_log_cap = 0;
     if (pt->ray_log_cap) {
       const size_t words = kRayLogHeader + (size_t)kRayLogWords * pt->ray_log_cap;
-      SRT_HIP(hipMalloc(&B.d_ray_log, words * sizeof(uint32_t)));
+      if ((st = B.d_ray_log.ensure(words))) return st;
       SRT_HIP(hipMemsetAsync(B.d_ray_log, 0, kRayLogHeader * sizeof(uint32_t), s));
       B.ray_log_cap = pt->ray_log_cap;
     }
@@ -663,16 +664,17 @@ uint32_t env_u32(const char* name, uint32_t otherwise) {
 
 // Event brackets on the launch stream: around the dominant kernel's launches (pt->timed: srt_pt_kernel_time) and around one kernel of
 // the streamed form (pt->stream_timed[k]: srt_pt_stream_times; diagnostic, off by default).
-int time_begin(srt_pt* pt, hipStream_t s, std::vector<std::pair<hipEvent_t, hipEvent_t>>& pending, bool enabled) {
+int time_begin(srt_pt* pt, hipStream_t s, std::vector<EventPair>& pending, bool enabled) {
   if (!enabled) return SRT_OK;
-  std::pair<hipEvent_t, hipEvent_t> ev;
-  if (!pt->spare.empty()) { ev = pt->spare.back(); pt->spare.pop_back(); }
-  else { SRT_HIP(hipEventCreate(&ev.first)); SRT_HIP(hipEventCreate(&ev.second)); }
-  pending.push_back(ev);
-  SRT_HIP(hipEventRecord(ev.first, s));
+  EventPair ev;
+  int st;
+  if (!pt->spare.empty()) { ev = std::move(pt->spare.back()); pt->spare.pop_back(); }
+  else if ((st = ev.first.create()) || (st = ev.second.create())) return st;
+  pending.push_back(std::move(ev));
+  SRT_HIP(hipEventRecord(pending.back().first, s));
   return SRT_OK;
 }
-int time_end(hipStream_t s, std::vector<std::pair<hipEvent_t, hipEvent_t>>& pending, bool enabled) {
+int time_end(hipStream_t s, std::vector<EventPair>& pending, bool enabled) {
   if (!enabled) return SRT_OK;
   SRT_HIP(hipEventRecord(pending.back().second, s));
   return SRT_OK;
@@ -683,8 +685,8 @@ int sample_buffers(srt_pt* pt, hipStream_t s, uint32_t px, srt_pt::EpochBuffers*
   int st;
   if ((st = stream_buffers(pt, s, out)) != SRT_OK) return st;
   srt_pt::EpochBuffers& B = **out;
-  if ((st = ensure(&B.d_samples, &B.samples_floats, (size_t)px * samples_per_launch(px) * 4)) != SRT_OK) return st;
-  return ensure(&B.d_running, &B.running_floats, (size_t)px * 4);
+  if ((st = B.d_samples.ensure((size_t)px * samples_per_launch(px) * 4)) != SRT_OK) return st;
+  return B.d_running.ensure((size_t)px * 4);
 }
 
 // One epoch of any form that writes per-sample radiance: launches of <= 64 samples per pixel, each followed by the ordered per-pixel
@@ -743,9 +745,9 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
   srt_pt::EpochBuffers* Bp = nullptr;
   if ((st = sample_buffers(pt, s, px, &Bp)) != SRT_OK) return st;
   srt_pt::EpochBuffers& B = *Bp;
-  if ((st = ensure(&B.d_records, &B.records_floats, (size_t)nlanes * kRecFields * kMaxPathDepth)) != SRT_OK) return st;
+  if ((st = B.d_records.ensure((size_t)nlanes * kRecFields * kMaxPathDepth)) != SRT_OK) return st;
   if (!B.d_queue) {
-    SRT_HIP(hipMalloc(&B.d_queue, (1 + ST_COUNT_) * sizeof(unsigned long long)));
+    if ((st = B.d_queue.ensure(1 + ST_COUNT_))) return st;
     SRT_HIP(hipMemsetAsync(B.d_queue, 0, (1 + ST_COUNT_) * sizeof(unsigned long long), s));   // (on `s`: see stream_buffers)
   }
   const DScene DS = device_scene(pt, &B);
@@ -770,7 +772,7 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
     P.flat_ready = env_u32("SRT_FLAT_READY", kFlatReady);
     P.flat_interior = env_u32("SRT_FLAT_INTERIOR", kFlatInteriorMin);
     P.queue_head = B.d_queue; P.ray_counter = pt->d_totals + C_COUNT; P.elided_counter = pt->d_totals + C_COUNT + 1; P.stamps = B.d_queue + 1;
-    P.host_cancel = pt->d_host_cancel; P.dev_cancel = B.d_cancel;
+    P.host_cancel = pt->h_cancel.device(); P.dev_cancel = B.d_cancel;
     P.watch = (pt->wave_blocks >= 2 && !getenv("SRT_NO_CANCEL_WATCH")) ? 1u : 0u;   // the last workgroup watches for srt_pt_cancel (pt_wave.h; the variable: A/B runs)
     SRT_HIP(hipMemsetAsync(B.d_queue, 0, sizeof(unsigned long long), s));
     return SRT_OK;
@@ -820,7 +822,7 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
     pt->cast_depth = depth; pt->cast_lds_frames = lds_frames;
     SRT_HIP(hipFuncSetAttribute((const void*)ckern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt->cast_lds));
     if (getenv("SRT_CAST_STATS") && !pt->d_cast_stats) {
-      SRT_HIP(hipMalloc(&pt->d_cast_stats, CS_COUNT * sizeof(unsigned long long)));
+      if ((st = pt->d_cast_stats.ensure(CS_COUNT))) return st;
       SRT_HIP(hipMemsetAsync(pt->d_cast_stats, 0, CS_COUNT * sizeof(unsigned long long), s));
     }
     if (pt->d_cast_stats) SRT_HIP(hipFuncSetAttribute((const void*)ckern_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt->cast_lds));
@@ -844,9 +846,9 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
   srt_pt::EpochBuffers* Bp = nullptr;
   if ((st = sample_buffers(pt, s, px, &Bp)) != SRT_OK) return st;
   srt_pt::EpochBuffers& B = *Bp;
-  if (!B.d_sc) SRT_HIP(hipMalloc(&B.d_sc, sizeof(StreamCounters)));
+  if (!B.d_sc && (st = B.d_sc.ensure(1))) return st;
   const size_t spill_words = (size_t)(depth - pt->cast_lds_frames) * 3u * (size_t)pt->cast_blocks * (size_t)pt->cast_threads;
-  if (spill_words && (st = ensure(&B.d_cast_spill, &B.cast_spill_words, spill_words)) != SRT_OK) return st;
+  if (spill_words && (st = B.d_cast_spill.ensure(spill_words)) != SRT_OK) return st;
   const uint32_t shadow_batches = (uint32_t)((F.delta_lights.size() + 2) / 3);
   const DScene DS = device_scene(pt, &B);
   WaveParams P{};
@@ -877,23 +879,23 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
     P.nlanes = nlanes;
     nblocks = nlanes / lthreads;
     int st;
-    if ((st = ensure(&B.d_records, &B.records_floats, (size_t)nlanes * kRecFields * kMaxPathDepth)) != SRT_OK) return st;
-    if ((st = ensure(&B.d_state, &B.state_words, (size_t)nlanes * SW_DL_WORDS)) != SRT_OK) return st;
-    if ((st = ensure(&B.d_ray_o, &B.ray_o_n, 2 * (size_t)nlanes * nslots)) != SRT_OK) return st;   // {origin, direction} per request
-    if ((st = ensure(&B.d_ray_id, &B.ray_id_n, (size_t)nlanes * nslots)) != SRT_OK) return st;
-    if ((st = ensure(&B.d_hits, &B.hits_n, (size_t)nlanes * nslots)) != SRT_OK) return st;
-    if ((st = ensure(&B.d_alive_list, &B.alive_list_n, (size_t)nlanes)) != SRT_OK) return st;
-    if (B.block_counters_n < 2 * (size_t)nblocks) {
-      if ((st = ensure(&B.d_block_counters, &B.block_counters_n, 2 * (size_t)nblocks)) != SRT_OK) return st;
+    if ((st = B.d_records.ensure((size_t)nlanes * kRecFields * kMaxPathDepth)) != SRT_OK) return st;
+    if ((st = B.d_state.ensure((size_t)nlanes * SW_DL_WORDS)) != SRT_OK) return st;
+    if ((st = B.d_ray_o.ensure(2 * (size_t)nlanes * nslots)) != SRT_OK) return st;   // {origin, direction} per request
+    if ((st = B.d_ray_id.ensure((size_t)nlanes * nslots)) != SRT_OK) return st;
+    if ((st = B.d_hits.ensure((size_t)nlanes * nslots)) != SRT_OK) return st;
+    if ((st = B.d_alive_list.ensure((size_t)nlanes)) != SRT_OK) return st;
+    if (B.d_block_counters.capacity() < 2 * (size_t)nblocks) {
+      if ((st = B.d_block_counters.ensure(2 * (size_t)nblocks)) != SRT_OK) return st;
       SRT_HIP(hipMemsetAsync(B.d_block_counters, 0, 2 * (size_t)nblocks * sizeof(unsigned long long), s));
     }
     P.sample_out = B.d_samples; P.records = B.d_records; P.npix = px; P.chunk = kChunk;
-    P.queue_head = &B.d_sc->queue_head; P.ray_counter = pt->d_totals + C_COUNT; P.elided_counter = pt->d_totals + C_COUNT + 1;
+    P.queue_head = &B.d_sc.get()->queue_head; P.ray_counter = pt->d_totals + C_COUNT; P.elided_counter = pt->d_totals + C_COUNT + 1;
     P.stamps = nullptr; P.flat_ready = 0; P.flat_interior = 0;
     P.state = B.d_state; P.ray_o = B.d_ray_o; P.ray_d = B.d_ray_o + 1; P.hits = B.d_hits; P.sc = B.d_sc;
     P.block_counters = B.d_block_counters;
     P.obj_shift = stream_obj_shift(F);
-    P.host_cancel = pt->d_host_cancel; P.dev_cancel = B.d_cancel;
+    P.host_cancel = pt->h_cancel.device(); P.dev_cancel = B.d_cancel;
     P.alive_list = B.d_alive_list;
     SRT_HIP(hipMemsetAsync(B.d_sc, 0, sizeof(StreamCounters), s));
     SRT_HIP(hipMemsetAsync(B.d_state, 0, 2 * (size_t)nlanes * sizeof(uint32_t), s));   // the flags and emit planes: every slot idle
@@ -938,14 +940,14 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
         if ((st = time_end(s, timed[3], on)) != SRT_OK || (st = time_begin(pt, s, timed[0], on)) != SRT_OK) return st;   // (an empty bracket closes slot 0 below)
       }
       if ((st = time_end(s, timed[0], on)) != SRT_OK || (st = time_begin(pt, s, timed[1], on)) != SRT_OK) return st;
-      pt_compact_kernel<<<cgrid, dim3(1024), 0, s>>>(B.d_state + (size_t)SW_EMIT * nlanes, nlanes, nslots, B.d_sc, (uint32_t)g, B.d_ray_id, pt->d_totals + C_COUNT + 2, pt->d_host_cancel, B.d_cancel, B.d_alive_list);
+      pt_compact_kernel<<<cgrid, dim3(1024), 0, s>>>(B.d_state + (size_t)SW_EMIT * nlanes, nlanes, nslots, B.d_sc, (uint32_t)g, B.d_ray_id, pt->d_totals + C_COUNT + 2, pt->h_cancel.device(), B.d_cancel, B.d_alive_list);
       if ((st = time_end(s, timed[1], on)) != SRT_OK || (st = time_begin(pt, s, timed[2], on)) != SRT_OK) return st;
-      C.nrays = &B.d_sc->nrays[g & 1]; C.head = &B.d_sc->cast_head[g & 1]; C.gen = (uint32_t)g;
+      C.nrays = &B.d_sc.get()->nrays[g & 1]; C.head = &B.d_sc.get()->cast_head[g & 1]; C.gen = (uint32_t)g;
       cast<<<dim3(pt->cast_blocks), dim3(pt->cast_threads), pt->cast_lds, s>>>(DS, C);
       if ((st = time_end(s, timed[2], on)) != SRT_OK) return st;
     }
     if (pt->stream_timing) pt->stream_generations += gens;
-    pt_stream_finish_kernel<<<dim3(1), dim3(256), 0, s>>>(B.d_block_counters, nblocks, pt->d_totals + C_COUNT, B.d_sc, pt->d_fault, B.d_cancel);
+    pt_stream_finish_kernel<<<dim3(1), dim3(256), 0, s>>>(B.d_block_counters, nblocks, pt->d_totals + C_COUNT, B.d_sc, pt->h_fault.device(), B.d_cancel);
     return SRT_OK;
   };
   return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
@@ -960,10 +962,10 @@ int math_round_trip(srt_pt* pt, const char* what, const float* const (&in)[K], s
   for (const float* p : in) if (!p) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
   for (const float* p : out) if (!p) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
   if (!in_floats) return SRT_OK;
+  DeviceBuffer<float> din_own[K], dout_own[M];            // (this call's own: freed on every return)
   float *din[K], *dout[M];
-  srt::DeviceScratch tmp;
-  for (size_t k = 0; k < K; k++) SRT_HIP(tmp.alloc(&din[k], in_floats * 4));
-  for (size_t m = 0; m < M; m++) SRT_HIP(tmp.alloc(&dout[m], out_floats * 4));
+  for (size_t k = 0; k < K; k++) { if ((st = din_own[k].ensure(in_floats))) return st; din[k] = din_own[k]; }
+  for (size_t m = 0; m < M; m++) { if ((st = dout_own[m].ensure(out_floats))) return st; dout[m] = dout_own[m]; }
   for (size_t k = 0; k < K; k++) SRT_HIP(hipMemcpyAsync(din[k], in[k], in_floats * 4, hipMemcpyHostToDevice, pt->stream));
   launch(din, dout);
   SRT_HIP(hipGetLastError());
@@ -986,7 +988,7 @@ int render_epoch_units(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t sample
   auto launch = [&](uint32_t first_sample, uint32_t n) -> int {
     const uint64_t units = (uint64_t)px * n;
     pt_unit_kernel<<<dim3((unsigned)((units + 63) / 64)), dim3(64), 0, s>>>(DS, T, seed, first_sample, n, (uint32_t)units, B.d_samples, pt->d_totals + C_COUNT,
-                                                                            pt->d_host_cancel, B.d_cancel);
+                                                                            pt->h_cancel.device(), B.d_cancel);
     return SRT_OK;
   };
   return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
@@ -1006,7 +1008,7 @@ int render_epoch_normals(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t samp
   auto launch = [&](uint32_t first_sample, uint32_t n) -> int {
     const uint64_t units = (uint64_t)px * n;               // (px is a multiple of 64: whole waves)
     pt_normals_kernel<<<dim3((unsigned)((units + 63) / 64)), dim3(64), 0, s>>>(DS, T, seed, first_sample, px, (uint32_t)units, B.d_samples, pt->d_totals + C_COUNT,
-                                                                               pt->d_host_cancel, B.d_cancel);
+                                                                               pt->h_cancel.device(), B.d_cancel);
     return SRT_OK;
   };
   return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
@@ -1042,11 +1044,8 @@ int srt_pt_create(int device, srt_pt** out) {
     }
     if (device >= count) { delete pt; return srt::fail(SRT_ERR_INVALID, "device %d out of range [0,%d)", device, count); }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&pt->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&pt->d_totals, (C_COUNT + 4) * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void**)&pt->h_fault, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&pt->d_fault, pt->h_fault, 0) != hipSuccess ||
-        hipHostMalloc((void**)&pt->h_cancel, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&pt->d_host_cancel, pt->h_cancel, 0) != hipSuccess ||
+        pt->d_totals.ensure(C_COUNT + 4) != SRT_OK || pt->h_fault.ensure(1, hipHostMallocMapped) != SRT_OK ||
+        pt->h_cancel.ensure(1, hipHostMallocMapped) != SRT_OK ||
         hipMemset(pt->d_totals, 0, (C_COUNT + 4) * sizeof(unsigned long long)) != hipSuccess) {
       delete pt;
       return srt::fail(SRT_ERR_HIP, "HIP context setup failed on device %d", device);
@@ -1072,28 +1071,7 @@ int srt_pt_destroy(srt_pt* pt) {
                                             "object_trips", "object_lanes", "cycles_fetch", "cycles_interior", "walking_lanes", "cycles_leaf", "cycles_object"};
       if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, pt->d_cast_stats, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
         for (int i = 0; i < CS_COUNT; i++) fprintf(stderr, "[srt] cast %s %llu\n", names[i], h[i]);
-      (void)hipFree(pt->d_cast_stats);
     }
-    (void)hipFree(pt->d_nodes); (void)hipFree(pt->d_tris); (void)hipFree(pt->d_tri_packed); (void)hipFree(pt->d_nrm); (void)hipFree(pt->d_objects);
-    (void)hipFree(pt->d_lights); (void)hipFree(pt->d_ltris); (void)hipFree(pt->d_mats); (void)hipFree(pt->d_wave); (void)hipFree(pt->d_blas); (void)hipFree(pt->d_wave_lazy); (void)hipFree(pt->d_dlights); (void)hipFree(pt->d_env_map);
-    (void)hipFree(pt->d_tile_buf); (void)hipFree(pt->d_image); (void)hipFree(pt->d_totals);
-    (void)hipFree(pt->d_idx); (void)hipFree(pt->d_vpos); (void)hipFree(pt->d_vnrm);
-    bvh_workspace_free(&pt->bvh_ws);
-    drop_update_tables(pt, UINT32_MAX);
-    for (auto& pl : pt->pinned) { (void)hipHostFree(pl.h); (void)hipEventDestroy(pl.done); }
-    if (pt->top_event) (void)hipEventDestroy(pt->top_event);
-    if (pt->shade_event) (void)hipEventDestroy(pt->shade_event);
-    (void)hipFree(pt->d_pose_list); (void)hipFree(pt->d_pose_out); (void)hipFree(pt->d_slot_ordinal); (void)hipFree(pt->d_light_list);
-    if (pt->h_fault) (void)hipHostFree(pt->h_fault);
-    if (pt->h_cancel) (void)hipHostFree(pt->h_cancel);
-    for (auto& kv : pt->epoch_buffers) {
-      (void)hipFree(kv.second.d_cancel); (void)hipFree(kv.second.d_ray_log); (void)hipFree(kv.second.d_alive_list);
-      (void)hipFree(kv.second.d_samples); (void)hipFree(kv.second.d_records); (void)hipFree(kv.second.d_running); (void)hipFree(kv.second.d_queue);
-      (void)hipFree(kv.second.d_state); (void)hipFree(kv.second.d_ray_o); (void)hipFree(kv.second.d_ray_d); (void)hipFree(kv.second.d_ray_id); (void)hipFree(kv.second.d_cast_spill);
-      (void)hipFree(kv.second.d_hits); (void)hipFree(kv.second.d_sc); (void)hipFree(kv.second.d_block_counters);
-    }
-    for (auto& v : {&pt->timed, &pt->spare, &pt->stream_timed[0], &pt->stream_timed[1], &pt->stream_timed[2]})
-      for (auto& ev : *v) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     (void)hipStreamDestroy(pt->stream);
   }
   delete pt;
@@ -1338,7 +1316,7 @@ namespace {
 int render_device(srt_pt* pt, const char* what, void* stream, uint64_t seed, uint32_t sample_base, uint32_t samples, float* d_tiles_out) {
   int st = need_ready(pt, what);
   if (st != SRT_OK) return st;
-  if (__atomic_load_n(pt->h_cancel, __ATOMIC_ACQUIRE) != 0u) return SRT_CANCELLED;   // nothing more is enqueued until srt_pt_clear_cancel
+  if (__atomic_load_n(pt->h_cancel.get(), __ATOMIC_ACQUIRE) != 0u) return SRT_CANCELLED;   // nothing more is enqueued until srt_pt_clear_cancel
   hipStream_t s = (hipStream_t)stream;  // exactly the caller's stream; NULL is the HIP default stream
   const TileMap& T = pt->tiles;
   const uint64_t lanes = (uint64_t)T.local_tiles * T.tile_w * T.tile_h;
@@ -1360,7 +1338,7 @@ int render_device(srt_pt* pt, const char* what, void* stream, uint64_t seed, uin
       if ((st = stream_buffers(pt, s, &Bp)) != SRT_OK) return st;
       if ((st = time_begin(pt, s, pt->timed, pt->timing)) != SRT_OK) return st;
       pt_epoch_kernel<<<dim3(blocks), dim3(64), 0, s>>>(device_scene(pt, Bp), T, seed, sample_base, samples, d_tiles_out,
-                                                        pt->d_totals + C_COUNT, pt->d_host_cancel, Bp->d_cancel);
+                                                        pt->d_totals + C_COUNT, pt->h_cancel.device(), Bp->d_cancel);
       SRT_HIP(hipGetLastError());
       if ((st = time_end(s, pt->timed, pt->timing)) != SRT_OK) return st;
     }
@@ -1474,16 +1452,11 @@ int srt_pt_render_epoch(srt_pt* pt, uint64_t seed, uint32_t sample_base, uint32_
   const TileMap& T = pt->tiles;
   const size_t per_tile = (size_t)T.tile_w * T.tile_h * 3;
   const size_t need = per_tile * (T.local_tiles ? T.local_tiles : 1);
-  if (pt->tile_buf_floats < need) {
-    if (pt->d_tile_buf) SRT_HIP(hipFree(pt->d_tile_buf));
-    pt->d_tile_buf = nullptr;
-    SRT_HIP(hipMalloc(&pt->d_tile_buf, need * sizeof(float)));
-    pt->tile_buf_floats = need;
-  }
+  if ((st = pt->d_tile_buf.ensure(need)) != SRT_OK) return st;
   st = srt_pt_render_epoch_device(pt, (void*)pt->stream, seed, sample_base, samples, pt->d_tile_buf);
   if (st != SRT_OK) return st;
   SRT_HIP(hipStreamSynchronize(pt->stream));
-  if (__atomic_load_n(pt->h_cancel, __ATOMIC_ACQUIRE) != 0u) return SRT_CANCELLED;   // the epoch was cut short: rgb_out is not written
+  if (__atomic_load_n(pt->h_cancel.get(), __ATOMIC_ACQUIRE) != 0u) return SRT_CANCELLED;   // the epoch was cut short: rgb_out is not written
   if ((st = check_stream_fault(pt, "srt_pt_render_epoch")) != SRT_OK) return st;
   std::vector<float> host(per_tile * T.local_tiles);
   if (!host.empty()) SRT_HIP(hipMemcpy(host.data(), pt->d_tile_buf, host.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1527,7 +1500,7 @@ int srt_pt_kernel_time(srt_pt* pt, int enable, double* total_ms, uint64_t* launc
     SRT_HIP(hipEventElapsedTime(&ms, ev.first, ev.second));
     sum += ms;
     n++;
-    pt->spare.push_back(ev);
+    pt->spare.push_back(std::move(ev));
   }
   pt->timed.clear();
   pt->timing = enable != 0;
@@ -1546,7 +1519,7 @@ int srt_pt_stream_times(srt_pt* pt, int enable, double ms_out[4], uint64_t* gene
       float ms = 0.f;
       SRT_HIP(hipEventElapsedTime(&ms, ev.first, ev.second));
       sum += ms;
-      pt->spare.push_back(ev);
+      pt->spare.push_back(std::move(ev));
     }
     pt->stream_timed[k].clear();
     if (ms_out) ms_out[k] = sum;
@@ -1640,11 +1613,9 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
   if (n > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "too many samples in one call");
   for (size_t i = 0; i < n; i++)
     if (xs[i] >= pt->w || ys[i] >= pt->h) return srt::fail(SRT_ERR_INVALID, "sample %zu: pixel (%u,%u) outside %ux%u", i, xs[i], ys[i], pt->w, pt->h);
-  uint32_t *dx = nullptr, *dy = nullptr, *ds = nullptr, *dd = nullptr, *dr = nullptr;
-  float* drgb = nullptr;
-  srt::DeviceScratch tmp;
-  SRT_HIP(tmp.alloc(&dx, n * 4)); SRT_HIP(tmp.alloc(&dy, n * 4)); SRT_HIP(tmp.alloc(&ds, n * 4));
-  SRT_HIP(tmp.alloc(&dd, n * 4)); SRT_HIP(tmp.alloc(&dr, n * 4)); SRT_HIP(tmp.alloc(&drgb, n * 12));
+  DeviceBuffer<uint32_t> dx, dy, ds, dd, dr;
+  DeviceBuffer<float> drgb;
+  if ((st = dx.ensure(n)) || (st = dy.ensure(n)) || (st = ds.ensure(n)) || (st = dd.ensure(n)) || (st = dr.ensure(n)) || (st = drgb.ensure(3 * n))) return st;
   SRT_HIP(hipMemcpyAsync(dx, xs, n * 4, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(dy, ys, n * 4, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(ds, ss, n * 4, hipMemcpyHostToDevice, pt->stream));
@@ -1666,9 +1637,8 @@ int srt_pt_hit(srt_pt* pt, const float* origins, const float* dirs, const float*
   if ((st = need_committed(pt, "srt_pt_hit")) != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!origins || !dirs || !bounds || !out9) return srt::fail(SRT_ERR_INVALID, "srt_pt_hit: NULL argument");
-  float *dorg = nullptr, *ddir = nullptr, *db = nullptr, *dout = nullptr;
-  srt::DeviceScratch tmp;
-  SRT_HIP(tmp.alloc(&dorg, n * 12)); SRT_HIP(tmp.alloc(&ddir, n * 12)); SRT_HIP(tmp.alloc(&db, n * 8)); SRT_HIP(tmp.alloc(&dout, n * 36));
+  DeviceBuffer<float> dorg, ddir, db, dout;
+  if ((st = dorg.ensure(3 * n)) || (st = ddir.ensure(3 * n)) || (st = db.ensure(2 * n)) || (st = dout.ensure(9 * n))) return st;
   SRT_HIP(hipMemcpyAsync(dorg, origins, n * 12, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(ddir, dirs, n * 12, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(db, bounds, n * 8, hipMemcpyHostToDevice, pt->stream));
@@ -1705,10 +1675,9 @@ int srt_pt_particles_step(srt_pt* pt, float* pos, float* vel, float* age, size_t
   if ((st = settle(pt)) != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!pos || !vel || !age || !alive) return srt::fail(SRT_ERR_INVALID, "srt_pt_particles_step: NULL argument");
-  float *dp = nullptr, *dv = nullptr, *da = nullptr;
-  uint8_t* dl = nullptr;
-  srt::DeviceScratch tmp;
-  SRT_HIP(tmp.alloc(&dp, n * 12)); SRT_HIP(tmp.alloc(&dv, n * 12)); SRT_HIP(tmp.alloc(&da, n * 4)); SRT_HIP(tmp.alloc(&dl, n));
+  DeviceBuffer<float> dp, dv, da;
+  DeviceBuffer<uint8_t> dl;
+  if ((st = dp.ensure(3 * n)) || (st = dv.ensure(3 * n)) || (st = da.ensure(n)) || (st = dl.ensure(n))) return st;
   SRT_HIP(hipMemcpyAsync(dp, pos, n * 12, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(dv, vel, n * 12, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(da, age, n * 4, hipMemcpyHostToDevice, pt->stream));
@@ -1831,11 +1800,8 @@ int srt_pt_tonemap(srt_pt* pt, const float* rgb, uint32_t width, uint32_t height
   if (!(exposure > 0.0f)) return srt::fail(SRT_ERR_INVALID, "srt_pt_tonemap: exposure must be positive (got %g)", (double)exposure);
   const size_t px = (size_t)width * height;
   if (!px) return SRT_OK;
-  float* d_in = nullptr; uint8_t* d_out = nullptr;
-  srt::DeviceScratch tmp;
-  SRT_HIP(tmp.alloc(&d_in, px * 12));
-  SRT_HIP(tmp.alloc(&d_out, px * 4));
-  st = SRT_OK;
+  DeviceBuffer<float> d_in; DeviceBuffer<uint8_t> d_out;
+  if ((st = d_in.ensure(3 * px)) || (st = d_out.ensure(4 * px))) return st;
   if (hipMemcpyAsync(d_in, rgb, px * 12, hipMemcpyHostToDevice, pt->stream) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_tonemap: upload failed");
   if (st == SRT_OK) st = srt_pt_tonemap_device(pt, (void*)pt->stream, d_in, width, height, exposure, d_out);
   if (st == SRT_OK && (hipMemcpyAsync(rgba_out, d_out, px * 4, hipMemcpyDeviceToHost, pt->stream) != hipSuccess ||
@@ -1878,23 +1844,23 @@ int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out)
 // ---- Pathtracer::cancel ---------------------------------------------------------------------------------------------
 int srt_pt_cancel(srt_pt* pt) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_cancel: NULL context");
-  if (pt->h_cancel) __atomic_store_n(pt->h_cancel, 1u, __ATOMIC_RELEASE);   // (no HIP call: any thread, any time)
+  if (pt->h_cancel) __atomic_store_n(pt->h_cancel.get(), 1u, __ATOMIC_RELEASE);   // (no HIP call: any thread, any time)
   return SRT_OK;
 }
 
 int srt_pt_cancel_requested(srt_pt* pt) {
-  return pt && pt->h_cancel && __atomic_load_n(pt->h_cancel, __ATOMIC_ACQUIRE) != 0u ? 1 : 0;
+  return pt && pt->h_cancel && __atomic_load_n(pt->h_cancel.get(), __ATOMIC_ACQUIRE) != 0u ? 1 : 0;
 }
 
 int srt_pt_clear_cancel(srt_pt* pt) {
   int st = need_device(pt, "srt_pt_clear_cancel");
   if (st != SRT_OK) return st;
   SRT_HIP(hipDeviceSynchronize());                       // what was in flight has drained (it ends early once the flag is seen)
-  __atomic_store_n(pt->h_cancel, 0u, __ATOMIC_RELEASE);
+  __atomic_store_n(pt->h_cancel.get(), 0u, __ATOMIC_RELEASE);
   for (auto& kv : pt->epoch_buffers)
     if (kv.second.d_cancel) SRT_HIP(hipMemset(kv.second.d_cancel, 0, sizeof(uint32_t)));
   SRT_HIP(hipDeviceSynchronize());                       // (the memsets are on the null stream: done before any stream's next kernel)
-  *(volatile uint32_t*)pt->h_fault = 0u;                 // (a cancelled streamed launch leaves no fault, but nothing stale either)
+  *(volatile uint32_t*)pt->h_fault.get() = 0u;           // (a cancelled streamed launch leaves no fault, but nothing stale either)
   return SRT_OK;
 }
 

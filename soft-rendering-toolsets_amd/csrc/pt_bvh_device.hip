@@ -238,48 +238,36 @@ __global__ void bvh_root(DNode* __restrict__ nodes, uint32_t* __restrict__ prim,
 }  // namespace
 
 bool bvh_workspace_reserve(BvhWorkspace* ws, uint32_t n, bool prim_only) {
-  bool ok = true;
-  if (n > ws->prims) {
-    (void)hipFree(ws->d_prim); ws->d_prim = nullptr; ws->prims = 0;
-    BVH_HIP(hipMalloc(&ws->d_prim, (size_t)n * 4));
-    ws->prims = n;
-  }
-  if (!prim_only && n > ws->build_prims) {
+  bool ok = n <= ws->d_prim.capacity() || ws->d_prim.ensure(n) == SRT_OK;
+  if (ok && !prim_only && n > ws->build_prims) {
     const size_t node_cap = 8ull * n + 64 + 2 * (size_t)n + 8;
-    (void)hipFree(ws->d_boxes); (void)hipFree(ws->d_nodes); (void)hipFree(ws->d_l); (void)hipFree(ws->d_r); (void)hipFree(ws->d_child); (void)hipFree(ws->d_ns);
-    ws->d_boxes = nullptr; ws->d_nodes = nullptr; ws->d_l = ws->d_r = ws->d_child = ws->d_ns = nullptr; ws->build_prims = 0;
-    BVH_HIP(hipMalloc(&ws->d_boxes, (size_t)n * sizeof(DBox)));
-    BVH_HIP(hipMalloc(&ws->d_nodes, node_cap * sizeof(DNode)));
-    BVH_HIP(hipMalloc(&ws->d_l, (size_t)n * 4)); BVH_HIP(hipMalloc(&ws->d_r, (size_t)n * 4));
-    BVH_HIP(hipMalloc(&ws->d_child, node_cap * 4)); BVH_HIP(hipMalloc(&ws->d_ns, 4));
-    ws->build_prims = n;
+    // (all six go before the first comes back: the peak is the new set's alone)
+    ws->d_boxes.reset(); ws->d_nodes.reset(); ws->d_l.reset(); ws->d_r.reset(); ws->d_child.reset(); ws->d_ns.reset();
+    ws->build_prims = 0;
+    ok = ws->d_boxes.ensure((size_t)n * 6) == SRT_OK && ws->d_nodes.ensure(node_cap * sizeof(DNode)) == SRT_OK && ws->d_l.ensure(n) == SRT_OK &&
+         ws->d_r.ensure(n) == SRT_OK && ws->d_child.ensure(node_cap) == SRT_OK && ws->d_ns.ensure(1) == SRT_OK;
+    if (ok) ws->build_prims = n;
   }
-done:
   if (!ok) {
-    bvh_workspace_free(ws);
+    *ws = BvhWorkspace();
     (void)hipGetLastError();
   }
   return ok;
 }
 
-void bvh_workspace_free(BvhWorkspace* ws) {
-  (void)hipFree(ws->d_boxes); (void)hipFree(ws->d_nodes); (void)hipFree(ws->d_prim); (void)hipFree(ws->d_l); (void)hipFree(ws->d_r); (void)hipFree(ws->d_child); (void)hipFree(ws->d_ns);
-  *ws = BvhWorkspace();
-}
-
 // The build itself, over boxes that are on the device already (uploaded by build_bvh_device, or computed there by
 // srt_pt_update_mesh): the root, then one plan + one split launch and one blocking read-back per level.
-bool build_bvh_device_core(BvhWorkspace* ws, void* stream, uint32_t n, uint32_t max_leaf, HostBVH* out) {
+bool build_bvh_device_core(BvhWorkspace* ws, void* stream, const float* d_boxes6, uint32_t n, uint32_t max_leaf, HostBVH* out) {
   bool ok = true;
   hipStream_t s = (hipStream_t)stream;
   const size_t node_limit = 8ull * n + 64;
   const size_t node_cap = node_limit + 2 * (size_t)n + 8;
-  const DBox* d_boxes = (const DBox*)ws->d_boxes; DNode* d_nodes = (DNode*)ws->d_nodes;
+  const DBox* d_boxes = (const DBox*)d_boxes6; DNode* d_nodes = (DNode*)ws->d_nodes.get();
   uint32_t *d_prim = ws->d_prim, *d_l = ws->d_l, *d_r = ws->d_r, *d_child = ws->d_child, *d_ns = ws->d_ns;
   size_t total = 1;
   uint32_t first = 0, count = 1, levels = 0;
   out->nodes.clear(); out->prim.clear();
-  if (n == 0 || n > ws->build_prims || n > ws->prims) return false;
+  if (n == 0 || n > ws->build_prims || n > ws->d_prim.capacity()) return false;
   bvh_root<<<dim3(1), dim3(1024), 0, s>>>(d_nodes, d_prim, d_boxes, n);
   while (count) {
     // One launch + one blocking read-back per level.  A usable tree is at most 48 levels deep (kMaxBlasDepth; deeper ones are
@@ -318,13 +306,12 @@ done:
 
 // The device builder behind build_bvh (pt_scene.cpp) for large primitive sets.  `boxes6`: n x {mn[3], mx[3]} on the host.
 // Returns false when the build does not terminate (as the host build does) or a HIP call fails (out->nodes is then empty and
-// the caller falls back to reporting the host builder's verdict).  A workspace of its own per build, on the null stream.
+// the caller falls back to reporting the host builder's verdict).  A workspace of its own per build (freed on return), on the null stream.
 bool build_bvh_device(const float* boxes6, uint32_t n, uint32_t max_leaf, HostBVH* out) {
   BvhWorkspace ws;
   out->nodes.clear(); out->prim.clear();
   bool ok = bvh_workspace_reserve(&ws, n, false) && hipMemcpy(ws.d_boxes, boxes6, (size_t)n * sizeof(DBox), hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && build_bvh_device_core(&ws, nullptr, n, max_leaf, out);
-  bvh_workspace_free(&ws);
+  ok = ok && build_bvh_device_core(&ws, nullptr, ws.d_boxes, n, max_leaf, out);
   if (!ok) (void)hipGetLastError();
   return ok;
 }

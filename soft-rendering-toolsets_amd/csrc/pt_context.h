@@ -34,37 +34,35 @@ struct srt_pt {
   srt::TileMap tiles{32, 32, 0, 0, 0, 1, 0};
   uint32_t tiles_per_rank = 0;
   // device copies
-  srt::Node* d_nodes = nullptr; srt::Tri* d_tris = nullptr; srt::TriNrm* d_nrm = nullptr; srt::Object* d_objects = nullptr;
-  float* d_tri_packed = nullptr;                                 // the triangle records without padding (pt_scene.h): what the cast kernel reads
-  srt::Light* d_lights = nullptr; srt::LightTri* d_ltris = nullptr; srt::Material* d_mats = nullptr;
-  srt::WaveInterior* d_wave = nullptr; srt::WaveInterior* d_blas = nullptr; uint32_t* d_wave_lazy = nullptr;
-  srt::DeltaLight* d_dlights = nullptr;
+  srt::DeviceBuffer<srt::Node> d_nodes; srt::DeviceBuffer<srt::Tri> d_tris; srt::DeviceBuffer<srt::TriNrm> d_nrm; srt::DeviceBuffer<srt::Object> d_objects;
+  srt::DeviceBuffer<float> d_tri_packed;                         // the triangle records without padding (pt_scene.h): what the cast kernel reads
+  srt::DeviceBuffer<srt::Light> d_lights; srt::DeviceBuffer<srt::LightTri> d_ltris; srt::DeviceBuffer<srt::Material> d_mats;
+  srt::DeviceBuffer<srt::WaveInterior> d_wave, d_blas; srt::DeviceBuffer<uint32_t> d_wave_lazy;
+  srt::DeviceBuffer<srt::DeltaLight> d_dlights;
   std::vector<srt::DeltaLight> delta_lights;   // srt_pt_add_light, in call order
   uint32_t env_type = 0; float env_radiance[3] = {0, 0, 0};   // srt_pt_set_env_light
-  std::vector<float> env_map; uint32_t env_w = 0, env_h = 0; float* d_env_map = nullptr;   // srt_pt_set_env_map
-  float* d_tile_buf = nullptr; size_t tile_buf_floats = 0;
-  float* d_image = nullptr; size_t image_floats = 0;
+  std::vector<float> env_map; uint32_t env_w = 0, env_h = 0; srt::DeviceBuffer<float> d_env_map;   // srt_pt_set_env_map
+  srt::DeviceBuffer<float> d_tile_buf;
   int kernel_mode = 0;        // srt_pt_set_kernel: 0 auto, 1 per-lane (lane per pixel), 2 wave-uniform, 3 wave-uniform with section stamps, 4 per-lane (lane per
                               // sample), 5 flattened per-lane walk, 6 streamed (logic + ray-cast kernels), 7 streamed sweeps; wave_trav() picks the form
   // Scratch of one epoch in flight.  One set per stream the caller renders on: epochs launched on different streams
   // may overlap on the device (the next epoch's blocks fill the CUs the previous launch's tail leaves idle).
   struct EpochBuffers {
-    float* d_samples = nullptr; size_t samples_floats = 0;   // per-sample radiance
-    float* d_records = nullptr; size_t records_floats = 0;   // wave kernel: per-bounce records
-    float* d_running = nullptr; size_t running_floats = 0;   // (sum, count) across the launches of one epoch
-    unsigned long long* d_queue = nullptr;                   // wave kernel: queue head (+ section stamps)
-    // streamed form (pt_stream.h): saved path state, ray queue, hits, counters
-    uint32_t* d_state = nullptr; size_t state_words = 0;
-    float4* d_ray_o = nullptr; size_t ray_o_n = 0;
-    float4* d_ray_d = nullptr; size_t ray_d_n = 0;
-    uint32_t* d_ray_id = nullptr; size_t ray_id_n = 0;
-    uint2* d_hits = nullptr; size_t hits_n = 0;
-    srt::StreamCounters* d_sc = nullptr;
-    unsigned long long* d_block_counters = nullptr; size_t block_counters_n = 0;
-    uint32_t* d_cast_spill = nullptr; size_t cast_spill_words = 0;   // the ray-cast kernel's traversal frames beyond those in LDS
-    uint32_t* d_cancel = nullptr;                                     // srt_pt_cancel as the kernels of this stream have seen it (sticky until srt_pt_clear_cancel)
-    uint32_t* d_ray_log = nullptr; uint32_t ray_log_cap = 0;          // srt_pt_set_ray_log: this stream's ring (pt_trace.h: log_ray_event)
-    uint32_t* d_alive_list = nullptr; size_t alive_list_n = 0;          // streamed forms: the alive slots the next generation works from
+    srt::DeviceBuffer<float> d_samples;                      // per-sample radiance
+    srt::DeviceBuffer<float> d_records;                      // wave kernel: per-bounce records
+    srt::DeviceBuffer<float> d_running;                      // (sum, count) across the launches of one epoch
+    srt::DeviceBuffer<unsigned long long> d_queue;           // wave kernel: queue head (+ section stamps)
+    // streamed form (pt_stream.h): saved path state, ray queue (origins, then directions: one array), hits, counters
+    srt::DeviceBuffer<uint32_t> d_state;
+    srt::DeviceBuffer<float4> d_ray_o;
+    srt::DeviceBuffer<uint32_t> d_ray_id;
+    srt::DeviceBuffer<uint2> d_hits;
+    srt::DeviceBuffer<srt::StreamCounters> d_sc;
+    srt::DeviceBuffer<unsigned long long> d_block_counters;
+    srt::DeviceBuffer<uint32_t> d_cast_spill;                // the ray-cast kernel's traversal frames beyond those in LDS
+    srt::DeviceBuffer<uint32_t> d_cancel;                    // srt_pt_cancel as the kernels of this stream have seen it (sticky until srt_pt_clear_cancel)
+    srt::DeviceBuffer<uint32_t> d_ray_log; uint32_t ray_log_cap = 0;   // srt_pt_set_ray_log: this stream's ring (pt_trace.h: log_ray_event) and the rays it holds
+    srt::DeviceBuffer<uint32_t> d_alive_list;                // streamed forms: the alive slots the next generation works from
     uint32_t last_samples = 0, last_npix = 0;                         // what d_samples holds: samples per pixel and pixel slots of the last launch
   };
   std::map<hipStream_t, EpochBuffers> epoch_buffers;
@@ -73,12 +71,10 @@ struct srt_pt {
   int cast_blocks = 0, cast_threads = 0; size_t cast_lds = 0; uint32_t cast_depth = 0;   // pt_cast_kernel's launch shape (0: not derived yet)
   int bvh_builder = 1; uint32_t bvh_device_min = 16384;         // srt_pt_set_bvh_builder: device build for sets of >= this many primitives
   uint32_t stream_slots = 0;                                    // srt_pt_set_stream_slots (0: default)
-  unsigned long long* d_cast_stats = nullptr;                   // SRT_CAST_STATS=1: the STATS build of pt_cast_kernel adds into these
-  unsigned long long* d_totals = nullptr;   // C_COUNT instrumented totals + 4 slots: rays of the epoch kernels, rays elided, streamed forms: entries queued, alive slot-generations
-  uint32_t* h_fault = nullptr;              // pinned, device-visible: bit 0 = a streamed launch ended with unfinished units (sticky until reported)
-  uint32_t* d_fault = nullptr;              // its device address
-  uint32_t* h_cancel = nullptr;             // pinned, device-visible: srt_pt_cancel's flag (any host thread may set it)
-  uint32_t* d_host_cancel = nullptr;        // its device address
+  srt::DeviceBuffer<unsigned long long> d_cast_stats;           // SRT_CAST_STATS=1: the STATS build of pt_cast_kernel adds into these
+  srt::DeviceBuffer<unsigned long long> d_totals;   // C_COUNT instrumented totals + 4 slots: rays of the epoch kernels, rays elided, streamed forms: entries queued, alive slot-generations
+  srt::PinnedBuffer<uint32_t> h_fault;      // mapped: bit 0 = a streamed launch ended with unfinished units (sticky until reported); the kernels' address: device()
+  srt::PinnedBuffer<uint32_t> h_cancel;     // mapped: srt_pt_cancel's flag (any host thread may set it)
   uint32_t ray_log_cap = 0;                 // srt_pt_set_ray_log: rays per stream and read; 0: Pathtracer::log_ray is not delivered
   int elide = 0;                            // srt_pt_set_elision
   int normal_colors = 0;                    // srt_pt_set_normal_colors: read whenever a launch is enqueued
@@ -86,21 +82,20 @@ struct srt_pt {
   uint64_t camera_samples = 0;
   // srt_pt_kernel_time: event pairs recorded around the dominant kernel's launches, on the launch stream
   bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;   // pending (recorded, not yet read)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> spare;
+  std::vector<srt::EventPair> timed;   // pending (recorded, not yet read)
+  std::vector<srt::EventPair> spare;
   // srt_pt_stream_times: per-kernel event pairs of the streamed form {logic, compaction, ray cast}
   bool stream_timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> stream_timed[4];   // {logic (resolve), compaction, ray cast, probe}
+  std::vector<srt::EventPair> stream_timed[4];   // {logic (resolve), compaction, ray cast, probe}
   uint64_t stream_generations = 0;
   // srt_pt_scene_counts: since creation
   uint64_t blas_builds = 0, bytes_uploaded = 0, tri_bytes_uploaded = 0;
   // srt_pt_update_mesh: the index buffers of the meshes that can be updated (no instance, no area light), resident from commit on, one
   // after the other; the device builder's workspace; and the staging of the host form's vertex arrays.  Grown on demand, kept.
-  uint32_t* d_idx = nullptr; size_t idx_words = 0;
+  srt::DeviceBuffer<uint32_t> d_idx; size_t idx_words = 0;   // idx_words: the words in use
   std::vector<size_t> idx_off;              // per object in insertion order: first word of its index buffer in d_idx (SIZE_MAX: none)
   srt::BvhWorkspace bvh_ws;
-  float* d_vpos = nullptr; size_t vpos_floats = 0;
-  float* d_vnrm = nullptr; size_t vnrm_floats = 0;
+  srt::DeviceBuffer<float> d_vpos, d_vnrm;
   // srt_pt_refit_mesh: per refitted mesh (insertion index) what its kernels keep on the device, from the first refit until the mesh
   // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
   std::map<uint32_t, srt::RefitTables> refit_tables;
@@ -109,28 +104,28 @@ struct srt_pt {
   // object-space box and its posed box - made at the first device repose after a commit (drop_pose_tables: a commit, a mesh update
   // or refit and a host repose change what they mirror; so does a device repose that is refused).  The per-call arrays (the list,
   // the read-back staging, the mesh ordinals per slot) are grown on demand and kept.
-  srt::Object* d_pose_records = nullptr; float* d_local_boxes = nullptr; float* d_posed_boxes = nullptr;
+  srt::DeviceBuffer<srt::Object> d_pose_records; srt::DeviceBuffer<float> d_local_boxes, d_posed_boxes;
   bool pose_tables = false;
-  uint32_t* d_pose_list = nullptr; size_t pose_list_n = 0;
-  srt::PoseOut* d_pose_out = nullptr; size_t pose_out_n = 0;
-  uint32_t* d_slot_ordinal = nullptr; size_t slot_ordinal_n = 0;
+  srt::DeviceBuffer<uint32_t> d_pose_list;
+  srt::DeviceBuffer<srt::PoseOut> d_pose_out;
+  srt::DeviceBuffer<uint32_t> d_slot_ordinal;
   // srt_pt_set_dynamic_lights (the switch itself is built.dynamic_lights): srt_pt_repose_device's table of the listed lights
   // ({position in the list, light} pairs), grown on demand and kept; and the bytes of index buffers that went up for a light's
   // first update or refit (ensure_mesh_idx) and are counted with the verdict
-  uint32_t* d_light_list = nullptr; size_t light_list_n = 0;
+  srt::DeviceBuffer<uint32_t> d_light_list;
   uint64_t idx_uncounted = 0;
   // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
   uint64_t scene_generation = 0;
-  // srt_pt_repose_refit[_device]: the BVH<Object>'s refit tables (RefitTables of pt_bvh_device.h; d_tri_boxes stays NULL - the posed
-  // boxes of the pose tables stand in its place) and the slot of every object, made at the first device-form refit of a tree and
+  // srt_pt_repose_refit[_device]: the BVH<Object>'s refit tables (RefitTables of pt_bvh_device.h; d_tri_boxes stays empty - the posed
+  // boxes of the pose tables are passed in its place) and the slot of every object, made at the first device-form refit of a tree and
   // dropped wherever the tree is replaced (drop_top_tables).  top_list: what d_pose_list (and d_light_list) hold when the last call
   // that wrote them was a device-form refit - a call with the same list uploads nothing.  pinned: host staging of the lists, one
   // buffer per list still on its way (its event tells), so that a call never waits for the one before.
   srt::RefitTables top_tables; bool have_top_tables = false;
-  uint32_t* d_slot_of = nullptr;
+  srt::DeviceBuffer<uint32_t> d_slot_of;
   std::vector<uint32_t> top_list; bool top_list_valid = false;
   uint32_t top_lights = 0, top_light_max_ntri = 0;        // of top_list: listed lights, and the largest triangle count among them
-  struct PinnedList { uint32_t* h = nullptr; size_t words = 0; hipEvent_t done = nullptr; };
+  struct PinnedList { srt::PinnedBuffer<uint32_t> h; srt::Event done; };
   std::vector<PinnedList> pinned;
   // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of objects
   // they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls are
@@ -138,37 +133,25 @@ struct srt_pt {
   uint64_t top_pending = 0;
   std::vector<uint8_t> top_pending_flag;
   std::vector<uint32_t> top_pending_objects;
-  hipEvent_t top_event = nullptr;
+  srt::Event top_event;
   uint64_t top_refits = 0;                  // srt_pt_top_refit_count
   // srt_pt_shading_timeline_apply: the host's record of the materials / delta lights lags the device from a call that wrote them until
   // settle() reads d_mats / d_dlights back, behind the event recorded after the last such call.  While the materials lag,
   // elision_provable (pt.hip) proves nothing.
   bool shade_pending_mats = false, shade_pending_lights = false;
-  hipEvent_t shade_event = nullptr;
+  srt::Event shade_event;
 };
 
 namespace srt {
 
-// The one exit of scene data to the device.  tri_class: triangle, normal, packed-triangle or BLAS-record bytes - what an
+// The one exit of scene data to the device, counted.  tri_class: triangle, normal, packed-triangle or BLAS-record bytes - what an
 // instance shares and srt_pt_repose leaves alone (srt_pt_scene_counts tells them apart).
 template <typename T>
-inline int upload(srt_pt* pt, T** dst, const std::vector<T>& src, bool tri_class = false) {
-  if (*dst) { SRT_HIP(hipFree(*dst)); *dst = nullptr; }
-  const size_t n = src.empty() ? 1 : src.size();
-  SRT_HIP(hipMalloc(dst, n * sizeof(T)));
-  if (!src.empty()) SRT_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+inline int upload(srt_pt* pt, DeviceBuffer<T>* dst, const std::vector<T>& src, bool tri_class = false) {
+  const int st = dst->upload(src);
+  if (st != SRT_OK) return st;
   pt->bytes_uploaded += src.size() * sizeof(T);
   if (tri_class) pt->tri_bytes_uploaded += src.size() * sizeof(T);
-  return SRT_OK;
-}
-
-// A device array of at least `need` elements: grown (never shrunk) by freeing and allocating anew; what it held is gone then.
-template <typename T>
-inline int ensure(T** buf, size_t* have, size_t need) {
-  if (*have >= need && *buf) return SRT_OK;
-  if (*buf) { SRT_HIP(hipFree(*buf)); *buf = nullptr; *have = 0; }
-  SRT_HIP(hipMalloc(buf, need * sizeof(T)));
-  *have = need;
   return SRT_OK;
 }
 

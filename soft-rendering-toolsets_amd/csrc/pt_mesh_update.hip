@@ -146,22 +146,22 @@ void launch_mesh_records(void* stream, const float* d_pos, const float* d_nrm_in
   mesh_records_kernel<<<dim3((ntri + 255u) / 256u), dim3(256), 0, (hipStream_t)stream>>>(d_pos, d_nrm_in, d_idx, d_prim, ntri, d_tris, d_nrm, d_packed);
 }
 
-void launch_refit_boxes(void* stream, const RefitTables& T, float* d_node_boxes6) {
+void launch_refit_boxes(void* stream, const RefitTables& T, const float* d_leaf_boxes6, float* d_node_boxes6) {
   hipStream_t s = (hipStream_t)stream;
   if (T.nleaves)
-    refit_leaves_kernel<<<dim3((T.nleaves + 255u) / 256u), dim3(256), 0, s>>>((const uint2*)T.d_leaves, T.nleaves, T.d_prim, T.d_tri_boxes, d_node_boxes6);
+    refit_leaves_kernel<<<dim3((T.nleaves + 255u) / 256u), dim3(256), 0, s>>>(T.d_leaves, T.nleaves, T.d_prim, d_leaf_boxes6, d_node_boxes6);
   // deepest level first; runs of levels that fit one workgroup share a launch
   const std::vector<uint32_t>& off = T.level_off;
   uint32_t l = (uint32_t)off.size() - 1u;          // number of levels
   while (l > 0u) {
     const uint32_t hi = l - 1u, count = off[hi + 1u] - off[hi];
     if (count > 256u || T.level_launches) {
-      if (count) refit_level_kernel<<<dim3((count + 255u) / 256u), dim3(256), 0, s>>>((const uint2*)T.d_list + off[hi], count, d_node_boxes6);
+      if (count) refit_level_kernel<<<dim3((count + 255u) / 256u), dim3(256), 0, s>>>(T.d_list + off[hi], count, d_node_boxes6);
       l = hi;
     } else {
       uint32_t lo = hi;
       while (lo > 0u && off[lo] - off[lo - 1u] <= 256u) lo--;
-      refit_levels_block_kernel<<<dim3(1), dim3(256), 0, s>>>((const uint2*)T.d_list, T.d_level_off, lo, hi, d_node_boxes6);
+      refit_levels_block_kernel<<<dim3(1), dim3(256), 0, s>>>(T.d_list, T.d_level_off, lo, hi, d_node_boxes6);
       l = lo;
     }
   }
@@ -170,7 +170,7 @@ void launch_refit_boxes(void* stream, const RefitTables& T, float* d_node_boxes6
 void launch_refit_write(void* stream, const RefitTables& T, const float* d_node_boxes6, Node* d_mesh_nodes, WaveInterior* d_mesh_recs) {
   const uint32_t n = T.nnodes + T.nrec;
   if (!n) return;
-  refit_write_kernel<<<dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream>>>(d_node_boxes6, T.nnodes, d_mesh_nodes, (const uint2*)T.d_children, T.nrec, d_mesh_recs);
+  refit_write_kernel<<<dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream>>>(d_node_boxes6, T.nnodes, d_mesh_nodes, T.d_children, T.nrec, d_mesh_recs);
 }
 
 }  // namespace srt

@@ -25,20 +25,20 @@ struct srt_pt_skin {
   uint32_t object = 0, nverts = 0, ntri = 0, njoints = 0, ninf = 0;
   std::vector<float> inv;                   // Mat4::inverse(joint_to_bind(j)), 16 floats per joint
   std::vector<float> mats;                  // the frame's posed_j * inverse_j on their way up
-  float *d_pos = nullptr, *d_nrm = nullptr;             // the bind-pose mesh
-  float *d_inv = nullptr, *d_cap = nullptr, *d_mats = nullptr;
-  uint32_t *d_off = nullptr, *d_jidx = nullptr, *d_last = nullptr;
-  float* d_w = nullptr;
-  float *d_pos_out = nullptr, *d_nrm_out = nullptr;     // srt_pt_skin_pose's staging
+  DeviceBuffer<float> d_pos, d_nrm;                     // the bind-pose mesh
+  DeviceBuffer<float> d_inv, d_cap, d_mats;
+  DeviceBuffer<uint32_t> d_off, d_jidx, d_last;
+  DeviceBuffer<float> d_w;
+  DeviceBuffer<float> d_pos_out, d_nrm_out;             // srt_pt_skin_pose's staging
   // srt_pt_skin_set_rig: the hierarchy and the joints' keys, on both sides; d_local: Mat4::euler(pose) per joint, the frame's
   bool rigged = false;
   std::vector<int32_t> parent;
   std::vector<float> cap, rest_pose, knot_times, knot_quats;   // cap: {extent, radius} per joint, from srt_pt_skin_create
   std::vector<uint32_t> knot_offsets;
   float base[3] = {0.0f, 0.0f, 0.0f};
-  int32_t* d_parent = nullptr;
-  uint32_t* d_knot_offsets = nullptr;
-  float *d_base = nullptr, *d_rest_pose = nullptr, *d_knot_times = nullptr, *d_knot_quats = nullptr, *d_local = nullptr;
+  DeviceBuffer<int32_t> d_parent;
+  DeviceBuffer<uint32_t> d_knot_offsets;
+  DeviceBuffer<float> d_base, d_rest_pose, d_knot_times, d_knot_quats, d_local;
 };
 
 // ---- srt_pt_timeline: Anim_Pose::at(t) and Pose::transform() of listed objects (pt_anim.h, pt_anim.hip) ----
@@ -47,8 +47,8 @@ struct srt_pt_timeline {
   uint64_t generation = 0;                  // pt->scene_generation at creation
   std::vector<uint32_t> objects, track_offsets;           // insertion indices; 3 tracks per object, CSR
   std::vector<float> knot_times, knot_values;
-  uint32_t* d_track_offsets = nullptr;
-  float *d_knot_times = nullptr, *d_knot_values = nullptr, *d_trans = nullptr;   // d_trans: the frame's transforms, 16 floats per object
+  DeviceBuffer<uint32_t> d_track_offsets;
+  DeviceBuffer<float> d_knot_times, d_knot_values, d_trans;   // d_trans: the frame's transforms, 16 floats per object
 };
 
 // ---- srt_pt_shading_timeline: Anim_Material::at(t) / Scene_Light::set_time(t) of listed materials and delta lights (pt_anim.h, pt_anim.hip) ----
@@ -58,22 +58,16 @@ struct srt_pt_shading_timeline {
   std::vector<uint32_t> materials, lights, track_offsets;   // 6 tracks per material, then 6 per light, then 2 of the environment (env), CSR
   bool env = false;
   std::vector<float> knot_times, knot_values;
-  uint32_t *d_track_offsets = nullptr, *d_materials = nullptr, *d_lights = nullptr;
-  float *d_knot_times = nullptr, *d_knot_values = nullptr;
+  DeviceBuffer<uint32_t> d_track_offsets, d_materials, d_lights;
+  DeviceBuffer<float> d_knot_times, d_knot_values;
 };
 
 namespace {
 
-void free_refit_tables(RefitTables* T) {
-  for (void* p : {(void*)T->d_prim, T->d_leaves, T->d_list, T->d_children, (void*)T->d_level_off, (void*)T->d_tri_boxes, (void*)T->d_node_boxes})
-    if (p) (void)hipFree(p);
-  *T = RefitTables();
-}
-
 // The refit tables of `object` (UINT32_MAX: of every mesh): its tree is about to be replaced.
 void drop_refit_tables(srt_pt* pt, uint32_t object) {
   for (auto it = pt->refit_tables.begin(); it != pt->refit_tables.end();) {
-    if (object == UINT32_MAX || it->first == object) { free_refit_tables(&it->second); it = pt->refit_tables.erase(it); }
+    if (object == UINT32_MAX || it->first == object) it = pt->refit_tables.erase(it);
     else ++it;
   }
 }
@@ -81,18 +75,14 @@ void drop_refit_tables(srt_pt* pt, uint32_t object) {
 // The BVH<Object> is about to be replaced (or d_pose_list to be overwritten by another call: then only the list is forgotten).
 void forget_top_list(srt_pt* pt) { pt->top_list_valid = false; pt->top_list.clear(); }
 void drop_top_tables(srt_pt* pt) {
-  pt->top_tables.d_tri_boxes = nullptr;                   // (the pose tables' posed boxes: drop_pose_tables frees them)
-  if (pt->have_top_tables) free_refit_tables(&pt->top_tables);
+  pt->top_tables = RefitTables();
   pt->have_top_tables = false;
-  if (pt->d_slot_of) (void)hipFree(pt->d_slot_of);
-  pt->d_slot_of = nullptr;
+  pt->d_slot_of.reset();
   forget_top_list(pt);
 }
 
 void drop_pose_tables(srt_pt* pt) {
-  for (void* p : {(void*)pt->d_pose_records, (void*)pt->d_local_boxes, (void*)pt->d_posed_boxes})
-    if (p) (void)hipFree(p);
-  pt->d_pose_records = nullptr; pt->d_local_boxes = pt->d_posed_boxes = nullptr;
+  pt->d_pose_records.reset(); pt->d_local_boxes.reset(); pt->d_posed_boxes.reset();
   pt->pose_tables = false;
 }
 
@@ -116,15 +106,13 @@ hipError_t quiesce(srt_pt* pt) {
 int ensure_mesh_idx(srt_pt* pt, uint32_t object) {
   if (pt->idx_off[object] != SIZE_MAX) return SRT_OK;
   const std::vector<uint32_t>& idx = pt->built.inputs[object].mesh.idx;
-  uint32_t* fresh = nullptr;
-  SRT_HIP(hipMalloc(&fresh, (pt->idx_words + idx.size()) * sizeof(uint32_t)));
+  DeviceBuffer<uint32_t> fresh;
+  int st;
+  if ((st = fresh.ensure(pt->idx_words + idx.size()))) return st;
   if ((pt->idx_words && hipMemcpy(fresh, pt->d_idx, pt->idx_words * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess) ||
-      hipMemcpy(fresh + pt->idx_words, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(fresh);
+      hipMemcpy(fresh + pt->idx_words, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
     return srt::fail(SRT_ERR_HIP, "index buffer of object %u: device copy failed", object);
-  }
-  if (pt->d_idx) (void)hipFree(pt->d_idx);
-  pt->d_idx = fresh;
+  pt->d_idx = std::move(fresh);                           // (frees the old array)
   pt->idx_off[object] = pt->idx_words;
   pt->idx_words += idx.size();
   pt->idx_uncounted += idx.size() * sizeof(uint32_t);
@@ -194,19 +182,17 @@ int upload_object_tables(srt_pt* pt, bool records = true) {
 // re-packed them.  [0, keep) of the old array has not moved and [from, size) of the new one is new or has moved; with another
 // total length the array is allocated anew, the part that stays is copied on the device and only the rest comes from the host.
 template <typename T>
-int upload_tail(srt_pt* pt, hipStream_t s, T** dst, size_t old_size, const std::vector<T>& src, size_t keep_from, size_t keep_to, size_t keep_n,
+int upload_tail(srt_pt* pt, hipStream_t s, DeviceBuffer<T>* dst, size_t old_size, const std::vector<T>& src, size_t keep_from, size_t keep_to, size_t keep_n,
                 size_t up_from, size_t up_to, bool tri_class) {
   // old[keep_from, keep_from + keep_n) -> new[keep_to, ..);  src[up_from, up_to) -> new[up_from, up_to)
   if (src.size() != old_size || keep_from != keep_to) {
-    T* fresh = nullptr;
-    SRT_HIP(hipMalloc(&fresh, (src.empty() ? 1 : src.size()) * sizeof(T)));
+    DeviceBuffer<T> fresh;
+    int st;
+    if ((st = fresh.ensure(src.empty() ? 1 : src.size()))) return st;
     if ((keep_n && hipMemcpyAsync(fresh + keep_to, *dst + keep_from, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      (void)hipFree(fresh);
+        hipStreamSynchronize(s) != hipSuccess)
       return srt::fail(SRT_ERR_HIP, "srt_pt_update_mesh: device copy failed");
-    }
-    (void)hipFree(*dst);
-    *dst = fresh;
+    *dst = std::move(fresh);                              // (frees the old array)
   }
   if (up_to > up_from) {
     SRT_HIP(hipMemcpyAsync(*dst + up_from, src.data() + up_from, (up_to - up_from) * sizeof(T), hipMemcpyHostToDevice, s));
@@ -244,7 +230,7 @@ int stage_vertices(srt_pt* pt, const char* what, hipStream_t s, uint32_t object,
     if (refuse_non_finite)
       for (size_t k = 0; k < vfloats; k++)
         if (!std::isfinite(V->h_pos[k])) return srt::fail(SRT_ERR_INVALID, "%s: vertex %zu of the new positions has a non-finite coordinate", what, k / 3);
-    if ((st = ensure(&pt->d_vpos, &pt->vpos_floats, vfloats)) || (st = ensure(&pt->d_vnrm, &pt->vnrm_floats, vfloats))) return st;
+    if ((st = pt->d_vpos.ensure(vfloats)) || (st = pt->d_vnrm.ensure(vfloats))) return st;
     SRT_HIP(hipMemcpy(pt->d_vpos, V->h_pos, vfloats * sizeof(float), hipMemcpyHostToDevice));
     SRT_HIP(hipMemcpy(pt->d_vnrm, V->h_nrm, vfloats * sizeof(float), hipMemcpyHostToDevice));
     *staged_bytes = 2 * vfloats * sizeof(float);
@@ -282,7 +268,7 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Me
   bool device_built = false;
   if (device_wanted && bvh_workspace_reserve(&pt->bvh_ws, ntri, false)) {
     launch_mesh_boxes(s, V.d_pos, d_mesh_idx, ntri, pt->bvh_ws.d_boxes);
-    device_built = build_bvh_device_core(&pt->bvh_ws, s, ntri, 4, &device_tree);
+    device_built = build_bvh_device_core(&pt->bvh_ws, s, pt->bvh_ws.d_boxes, ntri, 4, &device_tree);
   }
   // The BVH<Object> build goes where srt_pt_repose's does.  A device build of the mesh that failed - no termination, or no
   // memory - is not tried a second time through the wrapper: the host builds give the verdict.
@@ -374,19 +360,12 @@ int make_refit_tables(const HostBVH& tree, const char* what, uint32_t object, Re
   T->level_off = off;
   const char* ll = getenv("SRT_REFIT_LEVEL_LAUNCHES");
   T->level_launches = ll && atoi(ll) != 0;
-  auto up = [&](auto** dst, const auto& src) -> bool {
-    using E = typename std::remove_reference<decltype(src)>::type::value_type;
-    if (hipMalloc((void**)dst, (src.empty() ? 1 : src.size()) * sizeof(E)) != hipSuccess) return false;
-    if (!src.empty() && hipMemcpy(*dst, src.data(), src.size() * sizeof(E), hipMemcpyHostToDevice) != hipSuccess) return false;
-    T->uncounted_bytes += src.size() * sizeof(E);
-    return true;
-  };
-  if (!up(&T->d_prim, tree.prim) || !up(&T->d_leaves, leaves) || !up(&T->d_list, list) || !up(&T->d_children, children) || !up(&T->d_level_off, off) ||
-      (!top && hipMalloc(&T->d_tri_boxes, (size_t)ntri * 6 * sizeof(float)) != hipSuccess) ||
-      hipMalloc(&T->d_node_boxes, (size_t)(nn ? nn : 1) * 6 * sizeof(float)) != hipSuccess) {
-    free_refit_tables(T);
+  if (T->d_prim.upload(tree.prim) || T->d_leaves.upload(leaves) || T->d_list.upload(list) || T->d_children.upload(children) || T->d_level_off.upload(off) ||
+      (!top && T->d_tri_boxes.ensure((size_t)ntri * 6)) || T->d_node_boxes.ensure((size_t)(nn ? nn : 1) * 6)) {
+    *T = RefitTables();
     return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
   }
+  T->uncounted_bytes += (tree.prim.size() + off.size()) * sizeof(uint32_t) + (leaves.size() + list.size() + children.size()) * sizeof(uint2);
   return SRT_OK;
 }
 
@@ -407,13 +386,13 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Mes
     if (it == pt->refit_tables.end()) {
       RefitTables fresh;
       if ((st = make_refit_tables(pt->built.blas[object], "srt_pt_refit_mesh", object, &fresh)) != SRT_OK) { (void)hipStreamSynchronize(s); return st; }   // (the read-back is on s)
-      it = pt->refit_tables.emplace(object, fresh).first;
+      it = pt->refit_tables.emplace(object, std::move(fresh)).first;
     }
     T = &it->second;
     // the new boxes, aside: triangle boxes, leaves, levels.  They come back (24 B per node) with the arrays of the device form
     // (24 B per vertex): the host checks those, takes the root box and keeps its own tree true.
     launch_mesh_boxes(s, V.d_pos, pt->d_idx + pt->idx_off[object], m.ntri, T->d_tri_boxes);
-    launch_refit_boxes(s, *T, T->d_node_boxes);
+    launch_refit_boxes(s, *T, T->d_tri_boxes, T->d_node_boxes);
     node_boxes.resize(6 * (size_t)T->nnodes);
     SRT_HIP(hipMemcpyAsync(node_boxes.data(), T->d_node_boxes, node_boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s));
     SRT_HIP(hipStreamSynchronize(s));
@@ -450,25 +429,13 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Mes
   return written(pt, write());
 }
 
-void skin_free_rig(srt_pt_skin* k) {
-  for (void* p : {(void*)k->d_parent, (void*)k->d_knot_offsets, (void*)k->d_base, (void*)k->d_rest_pose, (void*)k->d_knot_times, (void*)k->d_knot_quats,
-                  (void*)k->d_local})
-    if (p) (void)hipFree(p);
-  k->d_parent = nullptr; k->d_knot_offsets = nullptr;
-  k->d_base = k->d_rest_pose = k->d_knot_times = k->d_knot_quats = k->d_local = nullptr;
+// What srt_pt_skin_set_rig put on the device goes (the caller has waited for what reads it).
+void skin_drop_rig(srt_pt_skin* k) {
+  k->d_parent.reset(); k->d_knot_offsets.reset(); k->d_base.reset(); k->d_rest_pose.reset(); k->d_knot_times.reset(); k->d_knot_quats.reset(); k->d_local.reset();
   k->rigged = false;
 }
 
-void skin_free(srt_pt_skin* k) {
-  if (k->pt && k->pt->device >= 0) (void)hipSetDevice(k->pt->device);
-  for (void* p : {(void*)k->d_pos, (void*)k->d_nrm, (void*)k->d_inv, (void*)k->d_cap, (void*)k->d_mats, (void*)k->d_off, (void*)k->d_jidx, (void*)k->d_last,
-                  (void*)k->d_w, (void*)k->d_pos_out, (void*)k->d_nrm_out})
-    if (p) (void)hipFree(p);
-  skin_free_rig(k);
-  delete k;
-}
-
-// The device side of srt_pt_skin_create; on failure the caller frees what is there.
+// The device side of srt_pt_skin_create.
 int skin_build(srt_pt_skin* k, const float* bind_positions, const float* bind_normals, const srt_pt_skin_joint* joints) {
   srt_pt* pt = k->pt;
   const size_t vfloats = 3 * (size_t)k->nverts;
@@ -482,38 +449,30 @@ int skin_build(srt_pt_skin* k, const float* bind_positions, const float* bind_no
   SRT_HIP(hipSetDevice(pt->device));
   hipStream_t s = pt->stream;
   const uint32_t nblocks = (k->nverts + 255u) / 256u;
-  SRT_HIP(hipMalloc(&k->d_pos, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_nrm, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_pos_out, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_nrm_out, vfloats * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_inv, k->inv.size() * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_mats, k->inv.size() * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_cap, cap.size() * sizeof(float)));
-  SRT_HIP(hipMalloc(&k->d_off, ((size_t)k->nverts + 1) * sizeof(uint32_t)));
-  SRT_HIP(hipMalloc(&k->d_last, (size_t)k->nverts * sizeof(uint32_t)));
+  int st;
+  if ((st = k->d_pos.ensure(vfloats)) || (st = k->d_nrm.ensure(vfloats)) || (st = k->d_pos_out.ensure(vfloats)) || (st = k->d_nrm_out.ensure(vfloats)) ||
+      (st = k->d_inv.ensure(k->inv.size())) || (st = k->d_mats.ensure(k->inv.size())) || (st = k->d_cap.ensure(cap.size())) ||
+      (st = k->d_off.ensure((size_t)k->nverts + 1)) || (st = k->d_last.ensure(k->nverts)))
+    return st;
   SRT_HIP(hipMemcpy(k->d_pos, bind_positions, vfloats * sizeof(float), hipMemcpyHostToDevice));
   SRT_HIP(hipMemcpy(k->d_nrm, bind_normals, vfloats * sizeof(float), hipMemcpyHostToDevice));
   SRT_HIP(hipMemcpy(k->d_inv, k->inv.data(), k->inv.size() * sizeof(float), hipMemcpyHostToDevice));
   SRT_HIP(hipMemcpy(k->d_cap, cap.data(), cap.size() * sizeof(float), hipMemcpyHostToDevice));
   pt->bytes_uploaded += (2 * vfloats + k->inv.size() + cap.size()) * sizeof(float);
   // count, scan, fill; the counts and the block sums live only here
-  uint32_t *d_counts = nullptr, *d_sums = nullptr;
-  SRT_HIP(hipMalloc(&d_counts, (size_t)k->nverts * sizeof(uint32_t)));
-  int st = SRT_OK;
-  if (hipMalloc(&d_sums, (size_t)nblocks * sizeof(uint32_t)) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: out of device memory");
   uint32_t total = 0;
-  if (st == SRT_OK) {
+  {
+    DeviceBuffer<uint32_t> d_sums, d_counts;              // (freed in the reverse order: the counts first)
+    if ((st = d_counts.ensure(k->nverts))) return st;
+    if (d_sums.ensure(nblocks)) return srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: out of device memory");
     launch_skin_count(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, d_counts);
     launch_skin_scan(s, d_counts, k->nverts, k->d_off, d_sums);
     if (hipMemcpyAsync(&total, k->d_off + k->nverts, sizeof total, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
         hipGetLastError() != hipSuccess)
-      st = srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: the find_joints kernels failed");
+      return srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: the find_joints kernels failed");
   }
-  (void)hipFree(d_counts); (void)hipFree(d_sums);
-  if (st != SRT_OK) return st;
   k->ninf = total;
-  SRT_HIP(hipMalloc(&k->d_jidx, (total ? (size_t)total : 1) * sizeof(uint32_t)));
-  SRT_HIP(hipMalloc(&k->d_w, (total ? (size_t)total : 1) * sizeof(float)));
+  if ((st = k->d_jidx.ensure(total ? (size_t)total : 1)) || (st = k->d_w.ensure(total ? (size_t)total : 1))) return st;
   launch_skin_fill(s, k->d_pos, k->nverts, k->d_inv, k->d_cap, k->njoints, k->d_off, k->d_jidx, k->d_w);
   SRT_HIP(hipMemsetAsync(k->d_last, 0, (size_t)k->nverts * sizeof(uint32_t), s));
   launch_skin_last_triangle(s, pt->d_idx + pt->idx_off[k->object], k->ntri, k->nverts, k->d_last);
@@ -588,22 +547,6 @@ int skin_pose_at(srt_pt_skin* skin, const char* what, void* stream, float t, int
   return mesh_call(skin->pt, what, (hipStream_t)stream, skin->object, {nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, {}, {}}, skin->nverts);
 }
 
-// A device copy of n elements made once (blocking), counted as uploaded.
-template <typename T>
-int upload_table(srt_pt* pt, T** dst, const T* src, size_t n) {
-  SRT_HIP(hipMalloc((void**)dst, (n ? n : 1) * sizeof(T)));
-  if (n) SRT_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-  pt->bytes_uploaded += n * sizeof(T);
-  return SRT_OK;
-}
-
-void timeline_free(srt_pt_timeline* tl) {
-  if (tl->pt && tl->pt->device >= 0) (void)hipSetDevice(tl->pt->device);
-  for (void* p : {(void*)tl->d_track_offsets, (void*)tl->d_knot_times, (void*)tl->d_knot_values, (void*)tl->d_trans})
-    if (p) (void)hipFree(p);
-  delete tl;
-}
-
 int timeline_usable(const srt_pt_timeline* tl, const char* what) {
   if (!tl) return srt::fail(SRT_ERR_INVALID, "%s: NULL timeline", what);
   if (!tl->pt->committed || tl->generation != tl->pt->scene_generation)
@@ -676,10 +619,8 @@ int ensure_pose_tables(srt_pt* pt, hipStream_t s, const char* what, uint64_t* by
   const uint32_t nobj = (uint32_t)pt->built.inputs.size();
   const size_t room = nobj ? nobj : 1;
   drop_pose_tables(pt);
-  if (hipMalloc(&pt->d_pose_records, room * sizeof(Object)) != hipSuccess || hipMalloc(&pt->d_local_boxes, room * 6 * sizeof(float)) != hipSuccess ||
-      hipMalloc(&pt->d_posed_boxes, room * 6 * sizeof(float)) != hipSuccess) {
+  if (pt->d_pose_records.ensure(room) || pt->d_local_boxes.ensure(room * 6) || pt->d_posed_boxes.ensure(room * 6)) {
     (void)hipGetLastError();
-    drop_pose_tables(pt);
     return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
   }
   // (blocking copy, then kernels on `s` that read what the last commit or repose left in d_objects: all of it done by now)
@@ -693,16 +634,15 @@ int ensure_pose_tables(srt_pt* pt, hipStream_t s, const char* what, uint64_t* by
 // A pinned staging buffer of at least `words` words whose last copy has left it (or a new one).
 int pinned_list(srt_pt* pt, size_t words, srt_pt::PinnedList** out) {
   for (auto& pl : pt->pinned) {
-    if (pl.words < words) continue;
+    if (pl.h.capacity() < words) continue;
     const hipError_t left = hipEventQuery(pl.done);
     (void)hipGetLastError();                              // (hipErrorNotReady of a query is no error: not left behind for the launch check)
     if (left == hipSuccess) { *out = &pl; return SRT_OK; }
   }
   srt_pt::PinnedList pl;
-  pl.words = std::max<size_t>(words, 1024);
-  if (hipHostMalloc((void**)&pl.h, pl.words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return srt::fail(SRT_ERR_HIP, "out of pinned host memory");
-  if (hipEventCreateWithFlags(&pl.done, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(pl.h); return srt::fail(SRT_ERR_HIP, "event creation failed"); }
-  pt->pinned.push_back(pl);
+  if (pl.h.ensure(std::max<size_t>(words, 1024))) return srt::fail(SRT_ERR_HIP, "out of pinned host memory");
+  if (pl.done.create(hipEventDisableTiming)) return srt::fail(SRT_ERR_HIP, "event creation failed");
+  pt->pinned.push_back(std::move(pl));
   *out = &pt->pinned.back();
   return SRT_OK;
 }
@@ -783,7 +723,7 @@ int update_materials(srt_pt* pt, const char* what, const uint32_t* materials, co
     fresh[k] = material_record(m[k]);
   }
   if (pt->device >= 0) SRT_HIP(quiesce(pt));
-  return written(pt, write_records(pt, &F.materials, pt->d_mats, materials, fresh));
+  return written(pt, write_records(pt, &F.materials, pt->d_mats.get(), materials, fresh));
 }
 
 int update_lights(srt_pt* pt, const char* what, const uint32_t* lights, const float* radiance, const float* angle_bounds, const float* trans, uint32_t n) {
@@ -802,7 +742,7 @@ int update_lights(srt_pt* pt, const char* what, const uint32_t* lights, const fl
     fresh[k] = make_delta_light(type, radiance + 3 * (size_t)k, angle_bounds ? angle_bounds + 2 * (size_t)k : nullptr, T);
   }
   if (pt->device >= 0) SRT_HIP(quiesce(pt));
-  return written(pt, write_records(pt, &F.delta_lights, pt->d_dlights, lights, fresh));
+  return written(pt, write_records(pt, &F.delta_lights, pt->d_dlights.get(), lights, fresh));
 }
 
 int update_env_light(srt_pt* pt, const char* what, const float radiance[3]) {
@@ -814,13 +754,6 @@ int update_env_light(srt_pt* pt, const char* what, const float radiance[3]) {
                      pt->env_type == SRT_ENV_MAP ? "with an environment map" : "without an environment light");
   for (int i = 0; i < 3; i++) pt->env_radiance[i] = radiance[i];
   return SRT_OK;
-}
-
-void shading_free(srt_pt_shading_timeline* tl) {
-  if (tl->pt && tl->pt->device >= 0) (void)hipSetDevice(tl->pt->device);
-  for (void* p : {(void*)tl->d_track_offsets, (void*)tl->d_materials, (void*)tl->d_lights, (void*)tl->d_knot_times, (void*)tl->d_knot_values})
-    if (p) (void)hipFree(p);
-  delete tl;
 }
 
 int shading_usable(const srt_pt_shading_timeline* tl, const char* what) {
@@ -1021,7 +954,7 @@ int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions,
     if (st == SRT_OK) { pt->bytes_uploaded += pt->idx_uncounted; pt->idx_uncounted = 0; }
   }
   if (st == SRT_OK) st = skin_build(k, bind_positions, bind_normals, joints);
-  if (st != SRT_OK) { skin_free(k); return st; }
+  if (st != SRT_OK) { delete k; return st; }
   *skin = k;
   return SRT_OK;
 }
@@ -1029,7 +962,7 @@ int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions,
 int srt_pt_skin_destroy(srt_pt_skin* skin) {
   if (!skin) return SRT_OK;
   if (skin->pt->device >= 0) (void)quiesce(skin->pt);
-  skin_free(skin);
+  delete skin;
   return SRT_OK;
 }
 
@@ -1132,7 +1065,7 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
   std::vector<PoseOut> posed(n);
   std::vector<float> boxes;
   if (n) {
-    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n))) return refuse(st);
+    if ((st = pt->d_pose_list.ensure(n)) || (st = pt->d_pose_out.ensure(n))) return refuse(st);
     if (hipMemcpyAsync(pt->d_pose_list, objects, (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
     staged_bytes += (uint64_t)n * 4;
     launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
@@ -1145,9 +1078,7 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
   HostBVH device_tree;
   bool device_built = false;
   if (use_bvh && device_builds(pt) && nobj >= pt->bvh_device_min && nobj > 1u && bvh_workspace_reserve(&pt->bvh_ws, nobj, false)) {
-    BvhWorkspace view = pt->bvh_ws;                       // the context's workspace with the posed boxes in the place of its own
-    view.d_boxes = pt->d_posed_boxes;
-    device_built = build_bvh_device_core(&view, s, nobj, 1, &device_tree);
+    device_built = build_bvh_device_core(&pt->bvh_ws, s, pt->d_posed_boxes, nobj, 1, &device_tree);   // over the posed boxes where they are
   }
   if (use_bvh && !device_built) {
     boxes.resize((size_t)nobj * 6);
@@ -1186,7 +1117,7 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
     if (!top.lazy_objects.empty()) {
       ordinal.assign(nobj, 0u);
       for (size_t q = 0; q < top.lazy_objects.size(); q++) ordinal[top.lazy_objects[q]] = (uint32_t)q << 8;
-      if ((st = ensure(&pt->d_slot_ordinal, &pt->slot_ordinal_n, (size_t)nobj))) return refuse(st);
+      if ((st = pt->d_slot_ordinal.ensure(nobj))) return refuse(st);
       if (hipMemcpyAsync(pt->d_slot_ordinal, ordinal.data(), (size_t)nobj * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
       staged_bytes += (uint64_t)nobj * 4;
       d_ordinal = pt->d_slot_ordinal;
@@ -1195,7 +1126,7 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
   // the listed area lights (srt_pt_set_dynamic_lights), still aside
   const ListedLights lights = listed_lights(pt->built, objects, n);
   if (!lights.pairs.empty()) {
-    if ((st = ensure(&pt->d_light_list, &pt->light_list_n, lights.pairs.size()))) return refuse(st);
+    if ((st = pt->d_light_list.ensure(lights.pairs.size()))) return refuse(st);
     if (hipMemcpyAsync(pt->d_light_list, lights.pairs.data(), lights.pairs.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) return copy_failed();
     staged_bytes += (uint64_t)lights.pairs.size() * 4;
   }
@@ -1259,11 +1190,11 @@ int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects
     drop_top_tables(pt);
     RefitTables fresh;
     if ((st = make_refit_tables(pt->built.tlas, what, UINT32_MAX, &fresh)) != SRT_OK) return st;
-    pt->top_tables = fresh;
+    pt->top_tables = std::move(fresh);
     pt->have_top_tables = true;
-    pt->bytes_uploaded += fresh.uncounted_bytes;
+    pt->bytes_uploaded += pt->top_tables.uncounted_bytes;
     pt->top_tables.uncounted_bytes = 0;
-    if (hipMalloc(&pt->d_slot_of, (size_t)(nobj ? nobj : 1) * sizeof(uint32_t)) != hipSuccess) {
+    if (pt->d_slot_of.ensure(nobj ? nobj : 1)) {
       (void)hipGetLastError();
       drop_top_tables(pt);
       return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
@@ -1289,15 +1220,15 @@ int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects
     const ListedLights lights = listed_lights(pt->built, objects, n);
     forget_top_list(pt);
     // (growing one of these arrays frees the old one, which waits for what reads it: first calls and longer lists only)
-    if ((st = ensure(&pt->d_pose_list, &pt->pose_list_n, (size_t)n)) || (st = ensure(&pt->d_pose_out, &pt->pose_out_n, (size_t)n)) ||
-        (!lights.pairs.empty() && (st = ensure(&pt->d_light_list, &pt->light_list_n, lights.pairs.size()))))
+    if ((st = pt->d_pose_list.ensure(n)) || (st = pt->d_pose_out.ensure(n)) || (!lights.pairs.empty() && (st = pt->d_light_list.ensure(lights.pairs.size()))))
       return broken(st);
     srt_pt::PinnedList* pl = nullptr;
     if ((st = pinned_list(pt, (size_t)n + lights.pairs.size(), &pl)) != SRT_OK) return broken(st);
-    std::memcpy(pl->h, objects, (size_t)n * 4);
-    if (!lights.pairs.empty()) std::memcpy(pl->h + n, lights.pairs.data(), lights.pairs.size() * 4);
-    if ((he = hipMemcpyAsync(pt->d_pose_list, pl->h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_broken(he, "the copy of the list");
-    if (!lights.pairs.empty() && (he = hipMemcpyAsync(pt->d_light_list, pl->h + n, lights.pairs.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
+    uint32_t* const h = pl->h;
+    std::memcpy(h, objects, (size_t)n * 4);
+    if (!lights.pairs.empty()) std::memcpy(h + n, lights.pairs.data(), lights.pairs.size() * 4);
+    if ((he = hipMemcpyAsync(pt->d_pose_list, h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_broken(he, "the copy of the list");
+    if (!lights.pairs.empty() && (he = hipMemcpyAsync(pt->d_light_list, h + n, lights.pairs.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
       return hip_broken(he, "the copy of the light list");
     if ((he = hipEventRecord(pl->done, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
     pt->bytes_uploaded += (uint64_t)n * 4 + lights.pairs.size() * 4;
@@ -1306,14 +1237,13 @@ int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects
     pt->top_light_max_ntri = lights.max_ntri;
     pt->top_list_valid = true;
   }
-  if (!pt->top_event && (he = hipEventCreateWithFlags(&pt->top_event, hipEventDisableTiming)) != hipSuccess) return hip_broken(he, "hipEventCreate");
+  if (pt->top_event.create(hipEventDisableTiming)) return hip_broken(hipGetLastError(), "hipEventCreate");
   // Everything below only enqueues on `s`: the poses, the leaves through the tree's primitive order, the levels deepest first, the
   // boxes into the live nodes and sweep records, the listed records' matrices, the listed lights.  No verdict is needed: depth,
   // counts, order, kernel form and stack sizes are those of the committed tree.
   if (n) launch_pose_objects(s, pt->d_pose_list, d_trans, n, nobj, pt->d_local_boxes, pt->d_pose_out, pt->d_pose_records, pt->d_posed_boxes);
   if (use_bvh) {
-    pt->top_tables.d_tri_boxes = pt->d_posed_boxes;       // the tree's primitives are the objects: their boxes are the pose tables' (not owned)
-    launch_refit_boxes(s, pt->top_tables, pt->top_tables.d_node_boxes);
+    launch_refit_boxes(s, pt->top_tables, pt->d_posed_boxes, pt->top_tables.d_node_boxes);   // the tree's primitives are the objects: their boxes are the pose tables'
     launch_refit_write(s, pt->top_tables, pt->top_tables.d_node_boxes, pt->d_nodes, pt->d_wave);
   }
   if (n) {
@@ -1341,7 +1271,7 @@ int srt_pt_skin_set_rig(srt_pt_skin* skin, const int32_t* parent, const float ba
   if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
   srt_pt* pt = skin->pt;
   SRT_HIP(quiesce(pt));                                   // (a rig set before may still be read)
-  skin_free_rig(skin);
+  skin_drop_rig(skin);
   const size_t nk = knot_offsets[nj];
   skin->parent.assign(parent, parent + nj);
   skin->rest_pose.assign(rest_pose, rest_pose + 3 * (size_t)nj);
@@ -1349,16 +1279,13 @@ int srt_pt_skin_set_rig(srt_pt_skin* skin, const int32_t* parent, const float ba
   skin->knot_times.assign(knot_times, knot_times + nk);
   skin->knot_quats.assign(knot_quats, knot_quats + 4 * nk);
   std::memcpy(skin->base, base, sizeof skin->base);
-  if ((st = upload_table(pt, &skin->d_parent, skin->parent.data(), nj)) || (st = upload_table(pt, &skin->d_base, skin->base, 3)) ||
-      (st = upload_table(pt, &skin->d_rest_pose, skin->rest_pose.data(), skin->rest_pose.size())) ||
-      (st = upload_table(pt, &skin->d_knot_offsets, skin->knot_offsets.data(), skin->knot_offsets.size())) ||
-      (st = upload_table(pt, &skin->d_knot_times, skin->knot_times.data(), nk)) || (st = upload_table(pt, &skin->d_knot_quats, skin->knot_quats.data(), 4 * nk))) {
-    skin_free_rig(skin);
+  if ((st = skin->d_parent.upload(skin->parent)) || (st = skin->d_base.upload(skin->base, 3)) || (st = skin->d_rest_pose.upload(skin->rest_pose)) ||
+      (st = skin->d_knot_offsets.upload(skin->knot_offsets)) || (st = skin->d_knot_times.upload(skin->knot_times)) ||
+      (st = skin->d_knot_quats.upload(skin->knot_quats)))
     return st;
-  }
-  if (hipMalloc(&skin->d_local, 16 * (size_t)nj * sizeof(float)) != hipSuccess) {
+  pt->bytes_uploaded += (nj + skin->knot_offsets.size()) * sizeof(uint32_t) + (3 + skin->rest_pose.size() + 5 * nk) * sizeof(float);
+  if (skin->d_local.ensure(16 * (size_t)nj)) {
     (void)hipGetLastError();
-    skin_free_rig(skin);
     return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
   }
   skin->rigged = true;
@@ -1416,8 +1343,8 @@ int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, floa
   if (st != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!x || !y || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_hypot: NULL argument");
-  float* d = nullptr;
-  SRT_HIP(hipMalloc(&d, 3 * n * sizeof(float)));
+  DeviceBuffer<float> d;
+  if ((st = d.ensure(3 * n))) return st;
   hipError_t e = hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d + n, y, n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
@@ -1425,7 +1352,6 @@ int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, floa
     e = hipMemcpyAsync(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost, pt->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(pt->stream);
-  (void)hipFree(d);
   SRT_HIP(e);
   return SRT_OK;
 }
@@ -1452,13 +1378,12 @@ int srt_pt_timeline_create(srt_pt* pt, const uint32_t* objects, uint32_t nobject
     auto up = [&]() -> int {
       SRT_HIP(hipSetDevice(pt->device));
       int w;
-      if ((w = upload_table(pt, &tl->d_track_offsets, tl->track_offsets.data(), tl->track_offsets.size())) ||
-          (w = upload_table(pt, &tl->d_knot_times, tl->knot_times.data(), nk)) || (w = upload_table(pt, &tl->d_knot_values, tl->knot_values.data(), 4 * nk)))
+      if ((w = tl->d_track_offsets.upload(tl->track_offsets)) || (w = tl->d_knot_times.upload(tl->knot_times)) || (w = tl->d_knot_values.upload(tl->knot_values)))
         return w;
-      SRT_HIP(hipMalloc(&tl->d_trans, (nobjects ? (size_t)nobjects : 1) * 16 * sizeof(float)));
-      return SRT_OK;
+      pt->bytes_uploaded += tl->track_offsets.size() * sizeof(uint32_t) + 5 * nk * sizeof(float);
+      return tl->d_trans.ensure((nobjects ? (size_t)nobjects : 1) * 16);
     };
-    if ((st = up()) != SRT_OK) { timeline_free(tl); return st; }
+    if ((st = up()) != SRT_OK) { delete tl; return st; }
   }
   *timeline = tl;
   return SRT_OK;
@@ -1467,7 +1392,7 @@ int srt_pt_timeline_create(srt_pt* pt, const uint32_t* objects, uint32_t nobject
 int srt_pt_timeline_destroy(srt_pt_timeline* timeline) {
   if (!timeline) return SRT_OK;
   if (timeline->pt->device >= 0) (void)quiesce(timeline->pt);
-  timeline_free(timeline);
+  delete timeline;
   return SRT_OK;
 }
 
@@ -1547,13 +1472,13 @@ int srt_pt_shading_timeline_create(srt_pt* pt, const uint32_t* materials, uint32
     auto up = [&]() -> int {
       SRT_HIP(hipSetDevice(pt->device));
       int w;
-      if ((w = upload_table(pt, &tl->d_track_offsets, tl->track_offsets.data(), tl->track_offsets.size())) ||
-          (w = upload_table(pt, &tl->d_materials, tl->materials.data(), tl->materials.size())) || (w = upload_table(pt, &tl->d_lights, tl->lights.data(), tl->lights.size())) ||
-          (w = upload_table(pt, &tl->d_knot_times, tl->knot_times.data(), nk)) || (w = upload_table(pt, &tl->d_knot_values, tl->knot_values.data(), 4 * nk)))
+      if ((w = tl->d_track_offsets.upload(tl->track_offsets)) || (w = tl->d_materials.upload(tl->materials)) || (w = tl->d_lights.upload(tl->lights)) ||
+          (w = tl->d_knot_times.upload(tl->knot_times)) || (w = tl->d_knot_values.upload(tl->knot_values)))
         return w;
+      pt->bytes_uploaded += (tl->track_offsets.size() + tl->materials.size() + tl->lights.size()) * sizeof(uint32_t) + 5 * nk * sizeof(float);
       return SRT_OK;
     };
-    if ((st = up()) != SRT_OK) { shading_free(tl); return st; }
+    if ((st = up()) != SRT_OK) { delete tl; return st; }
   }
   *out = tl;
   return SRT_OK;
@@ -1562,7 +1487,7 @@ int srt_pt_shading_timeline_create(srt_pt* pt, const uint32_t* materials, uint32
 int srt_pt_shading_timeline_destroy(srt_pt_shading_timeline* timeline) {
   if (!timeline) return SRT_OK;
   if (timeline->pt->device >= 0) (void)quiesce(timeline->pt);
-  shading_free(timeline);
+  delete timeline;
   return SRT_OK;
 }
 
@@ -1609,7 +1534,7 @@ int srt_pt_shading_timeline_apply(srt_pt_shading_timeline* timeline, void* strea
   SRT_HIP(hipSetDevice(pt->device));
   const uint32_t nm = (uint32_t)timeline->materials.size(), nl = (uint32_t)timeline->lights.size();
   if (nm + nl) {
-    if (!pt->shade_event) SRT_HIP(hipEventCreateWithFlags(&pt->shade_event, hipEventDisableTiming));
+    { const int made = pt->shade_event.create(hipEventDisableTiming); if (made != SRT_OK) return made; }
     launch_anim_shading(stream, timeline->d_track_offsets, timeline->d_knot_times, timeline->d_knot_values, timeline->d_materials, nm, timeline->d_lights, nl, t,
                         pt->d_mats, pt->d_dlights);
     // the host's record is behind from here until settle(); a HIP failure leaves a record nobody can vouch for: commit again
@@ -1695,6 +1620,12 @@ int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_p
   if (!d_pos || !d_trans_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_particle_transforms_device: NULL argument");
   launch_particle_transforms(stream, d_pos, n, scale, d_trans_out);
   SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_live_resources(uint64_t out[3]) {
+  if (!out) return srt::fail(SRT_ERR_INVALID, "srt_pt_live_resources: NULL argument");
+  for (int k = 0; k < 3; k++) out[k] = owned_live((OwnedKind)k).load(std::memory_order_relaxed);
   return SRT_OK;
 }
 

@@ -879,32 +879,31 @@ struct srt_raster {
   bool have_target = false;
   // The frame's ordered stream, in PINNED host memory (grown geometrically): srt_raster_submit appends here and the upload is
   // one DMA transfer, no staging copy.
-  srt_prim* pending = nullptr; size_t pending_n = 0, pending_cap = 0;
+  srt::PinnedBuffer<srt_prim> pending; size_t pending_n = 0;
   std::vector<srt_prim> uploaded;   // what d_prims holds (host copy): an identical resubmission uploads and bins nothing
   bool dirty = true;                // pending differs from d_prims
-  hipEvent_t upload_done = nullptr; bool upload_pending = false;   // the DMA out of `pending` may still be reading it
+  srt::Event upload_done; bool upload_pending = false;   // the DMA out of `pending` may still be reading it
   // `reserved` words of `pending` that hold device-side indices (a line's ordinal, an image's ImageAux) while that DMA runs, with
   // the caller's values: put back by settle_upload() once the copy has read them, before anything looks at `pending` again
   std::vector<std::pair<size_t, uint32_t>> patched;
-  srt_prim* d_prims = nullptr; size_t prims_cap = 0;
-  int4* d_bbox = nullptr; size_t bbox_cap = 0;
-  uint2* d_lists = nullptr; size_t lists_cap = 0;      // coarse-bin lists, packed back to back (raster_bin_pass<2>), entries of {primitive, box}; kept across frames and streams
-  uint32_t* d_counts = nullptr; size_t counts_cap = 0; // per coarse bin: entries, then (second half) list offsets
-  uint32_t* d_super = nullptr; size_t super_cap = 0;   // super-bin lists (<= 64 x nprims) followed by their 64 counts
+  srt::DeviceBuffer<srt_prim> d_prims;
+  srt::DeviceBuffer<int4> d_bbox;
+  srt::DeviceBuffer<uint2> d_lists;                    // coarse-bin lists, packed back to back (raster_bin_pass<2>), entries of {primitive, box}; kept across frames and streams
+  srt::DeviceBuffer<uint32_t> d_counts;                // per coarse bin: entries, then (second half) list offsets
+  srt::DeviceBuffer<uint32_t> d_super;                 // super-bin lists (<= 64 x nprims) followed by their 64 counts
   bool bins_valid = false;                             // the bin lists on the device belong to the current stream / target / tiling
   bool verified = false;                               // ... and a frame with them has reported that every buffer was large enough
   uint32_t coarse_min = 4;                             // tiles per coarse-bin side to start from (raised when the lists get too long)
   // lines (SRT_PRIM_LINE): one LineAux per record, the intery table (raster_setup)
   uint32_t nlines = 0;
   bool has_images = false;                             // the stream on the device holds SRT_PRIM_IMAGE records (the tile kernel's IMG build)
-  LineAux* d_laux = nullptr; size_t laux_cap = 0;
-  float* d_ltable = nullptr; size_t ltable_cap = 0;
-  uint32_t* d_status = nullptr;                        // FS_* words of the frame in flight
-  uint32_t* h_status = nullptr;                        // ... written here (pinned, device-visible) by the tile kernel's first block
-  uint32_t* d_host_status = nullptr;                   // its device address
-  uint32_t* d_rgba = nullptr;
-  float4* d_samples = nullptr;
-  unsigned long long* d_stats = nullptr;
+  srt::DeviceBuffer<LineAux> d_laux;
+  srt::DeviceBuffer<float> d_ltable;
+  srt::DeviceBuffer<uint32_t> d_status;                // FS_* words of the frame in flight
+  srt::PinnedBuffer<uint32_t> h_status;                // ... written here (mapped: the kernel's address is device()) by the tile kernel's first block
+  srt::DeviceBuffer<uint32_t> d_rgba;
+  srt::DeviceBuffer<float4> d_samples;
+  srt::DeviceBuffer<unsigned long long> d_stats;
   bool resolved = false;
   uint8_t* bound_out = nullptr;                        // srt_raster_bind_output: the caller's framebuffer, pinned
   // textures (srt_raster_add_texture): host copies, then one device blob with 4-byte aligned levels
@@ -913,7 +912,7 @@ struct srt_raster {
   // The texel blob lives in PINNED host memory and is kept across srt_raster_clear_textures: DrawSVG's redraw clears and re-adds
   // the same mip chains every frame (drawsvg.cpp:462-474 builds them once per SVG), so a re-added level is COMPARED with what the
   // blob already holds at that offset instead of copied, and as long as every level matches the device copy stays as it is.
-  uint8_t* texel_blob = nullptr; size_t blob_n = 0, blob_cap = 0;   // blob_n: bytes of the current texture set
+  srt::PinnedBuffer<uint8_t> texel_blob; size_t blob_n = 0;   // blob_n: bytes of the current texture set
   size_t blob_kept = 0;                                // bytes of the previous set still in the blob behind blob_n (re-add comparison)
   size_t device_blob_n = 0;                            // d_texels holds texel_blob[0 .. device_blob_n) byte for byte
   bool tex_dirty = true;                               // the texture set changed since the image tables (ImageAux) were built
@@ -921,9 +920,9 @@ struct srt_raster {
   bool aux_valid = false;                              // d_aux / d_tabs belong to the stream on the device, this target and these textures
   bool rebuilding = false;                             // between srt_raster_clear_textures and the next frame: add_texture compares with prev_textures / the blob
   bool blob_upload_pending = false;                    // a DMA transfer may still be reading the pinned blob
-  uint8_t* d_texels = nullptr; size_t texels_cap = 0;
-  ImageAux* d_aux = nullptr; size_t aux_cap = 0;
-  float* d_tabs = nullptr; size_t tabs_cap = 0;
+  srt::DeviceBuffer<uint8_t> d_texels;
+  srt::DeviceBuffer<ImageAux> d_aux;
+  srt::DeviceBuffer<float> d_tabs;
   // What the host prepares for a stream's SRT_PRIM_IMAGE and SRT_PRIM_LINE records (prepare_images); kept between uploads for its
   // storage only - a redraw allocates nothing
   struct ImagePrep {
@@ -954,28 +953,17 @@ void set_tile_height(RasterParams& P, uint32_t tsy) {
   P.tiles_y = (P.h + P.tile_py - 1) / P.tile_py;
 }
 
-template <typename T>
-int grow(T** buf, size_t* cap, size_t need) {
-  if (*cap >= need && *buf) return SRT_OK;
-  if (*buf) SRT_HIP(hipFree(*buf));
-  *buf = nullptr; *cap = 0;      // a failed allocation below must not leave a capacity behind
-  SRT_HIP(hipMalloc(buf, need * sizeof(T)));
-  *cap = need;
-  return SRT_OK;
-}
-
 // A pinned host buffer of `cap` elements (`what`, for the error text) that keeps the first `keep` of the old one.  The caller has set
 // the device and has waited for every transfer that may still be reading the old buffer: it is freed here.
 template <typename T>
-int grow_pinned(T** buf, size_t* buf_cap, size_t keep, size_t cap, const char* what) {
-  T* grown = nullptr;
-  if (hipHostMalloc((void**)&grown, cap * sizeof(T), hipHostMallocDefault) != hipSuccess) {
+int grow_pinned(srt::PinnedBuffer<T>* buf, size_t keep, size_t cap, const char* what) {
+  srt::PinnedBuffer<T> grown;
+  if (grown.ensure(cap) != SRT_OK) {
     (void)hipGetLastError();
     return srt::fail(SRT_ERR_INVALID, "out of pinned host memory for %zu %s", cap, what);
   }
-  if (keep) std::memcpy(grown, *buf, keep * sizeof(T));
-  if (*buf) (void)hipHostFree(*buf);
-  *buf = grown; *buf_cap = cap;
+  if (keep) std::memcpy(grown.get(), buf->get(), keep * sizeof(T));
+  *buf = std::move(grown);
   return SRT_OK;
 }
 
@@ -995,7 +983,7 @@ bool same_stream_as_device(const srt_raster* r) {
   // A stream without images does not care about the textures (tex_dirty stays set for the next stream that does); one with
   // images is the same frame only if its tables - target, textures - are the ones on the device.
   return (!has_image || (r->aux_valid && !r->tex_dirty)) && n == r->uploaded.size() && r->P.nprims == (uint32_t)n &&
-         (n == 0 || std::memcmp(r->pending, r->uploaded.data(), n * sizeof(srt_prim)) == 0);
+         (n == 0 || std::memcmp(r->pending.get(), r->uploaded.data(), n * sizeof(srt_prim)) == 0);
 }
 
 // SRT_PRIM_IMAGE records: per-image constants and loop-value tables (ImageAux); SRT_PRIM_LINE records: their ordinal.
@@ -1086,7 +1074,7 @@ int upload_prims(srt_raster* r) {
   // the device's words into the records, the caller's into the list, which thereby becomes `patched` (empty until here: settle_upload)
   for (auto& dr : r->prep.device_reserved) std::swap(r->pending[dr.first].reserved, dr.second);
   r->patched.swap(r->prep.device_reserved);
-  hipError_t up = hipMemcpyAsync(r->d_prims, r->pending, n * sizeof(srt_prim), hipMemcpyHostToDevice, r->stream);
+  hipError_t up = hipMemcpyAsync(r->d_prims, r->pending.get(), n * sizeof(srt_prim), hipMemcpyHostToDevice, r->stream);
   if (up == hipSuccess) { up = hipEventRecord(r->upload_done, r->stream); r->upload_pending = up == hipSuccess; }
   if (up != hipSuccess) (void)hipStreamSynchronize(r->stream);       // (an event that could not be recorded: wait the plain way)
   SRT_HIP(up);
@@ -1099,11 +1087,11 @@ int upload_prims(srt_raster* r) {
 int upload_images(srt_raster* r) {
   const srt_raster::ImagePrep& prep = r->prep;
   int st;
-  if ((st = grow(&r->d_aux, &r->aux_cap, prep.aux.size())) != SRT_OK || (st = grow(&r->d_tabs, &r->tabs_cap, prep.tabs.size())) != SRT_OK) return st;
+  if ((st = r->d_aux.ensure(prep.aux.size())) != SRT_OK || (st = r->d_tabs.ensure(prep.tabs.size())) != SRT_OK) return st;
   SRT_HIP(hipMemcpy(r->d_aux, prep.aux.data(), prep.aux.size() * sizeof(ImageAux), hipMemcpyHostToDevice));
   SRT_HIP(hipMemcpy(r->d_tabs, prep.tabs.data(), prep.tabs.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (r->texels_cap < r->blob_n || !r->d_texels) {
-    if ((st = grow(&r->d_texels, &r->texels_cap, r->blob_n ? r->blob_n + r->blob_n / 4 : 4)) != SRT_OK) return st;
+  if (r->d_texels.capacity() < r->blob_n || !r->d_texels) {
+    if ((st = r->d_texels.ensure(r->blob_n ? r->blob_n + r->blob_n / 4 : 4)) != SRT_OK) return st;
     r->device_blob_n = 0;
   }
   if (r->device_blob_n < r->blob_n) {
@@ -1129,13 +1117,13 @@ int upload_stream(srt_raster* r) {
   if (r->rebuilding) { if (r->textures.size() != r->prev_textures.size()) r->tex_dirty = true; r->rebuilding = false; }
   r->blob_kept = 0;
   if (same_stream_as_device(r)) { r->dirty = false; return SRT_OK; }
-  if (n > r->prims_cap || n > r->bbox_cap) {
+  if (n > r->d_prims.capacity() || n > r->d_bbox.capacity()) {
     const size_t cap = n + n / 2 + 64;
-    if ((st = grow(&r->d_prims, &r->prims_cap, cap)) != SRT_OK || (st = grow(&r->d_bbox, &r->bbox_cap, cap)) != SRT_OK) return st;
+    if ((st = r->d_prims.ensure(cap)) != SRT_OK || (st = r->d_bbox.ensure(cap)) != SRT_OK) return st;
   }
   // what d_prims is about to hold, as the caller wrote it (the next frame's stream is compared with this); dropped again on every
   // failure below, with the records' own `reserved` words put back - without it the next frame just uploads
-  try { r->uploaded.assign(r->pending, r->pending + n); } catch (...) { r->uploaded.clear(); }
+  try { r->uploaded.assign(r->pending.get(), r->pending + n); } catch (...) { r->uploaded.clear(); }
   struct DropOnFailure {
     srt_raster* r; bool done = false;
     ~DropOnFailure() { if (!done) { r->uploaded.clear(); (void)settle_upload(r); } }
@@ -1143,7 +1131,7 @@ int upload_stream(srt_raster* r) {
   srt_raster::ImagePrep& prep = r->prep;
   if ((st = prepare_images(r->pending, n, r->textures, r->P, &prep)) != SRT_OK) return st;
   if ((st = upload_prims(r)) != SRT_OK) return st;
-  if (prep.nlines && (st = grow(&r->d_laux, &r->laux_cap, (size_t)prep.nlines + prep.nlines / 2)) != SRT_OK) return st;
+  if (prep.nlines && (st = r->d_laux.ensure((size_t)prep.nlines + prep.nlines / 2)) != SRT_OK) return st;
   if (!prep.aux.empty() && (st = upload_images(r)) != SRT_OK) return st;
   guard.done = true;
   r->nlines = prep.nlines;
@@ -1201,25 +1189,25 @@ int launch_frame(srt_raster* r, hipStream_t s, bool dump_samples, bool stats) {
     }
     const size_t nb = (size_t)P.coarse_x * P.coarse_y, ns = (size_t)P.super_x * P.super_y;
     int st;
-    if ((st = grow(&r->d_counts, &r->counts_cap, 2 * nb)) != SRT_OK) return st;
-    if ((st = grow(&r->d_super, &r->super_cap, ns * P.super_stride + 64)) != SRT_OK) return st;
+    if ((st = r->d_counts.ensure(2 * nb)) != SRT_OK) return st;
+    if ((st = r->d_super.ensure(ns * P.super_stride + 64)) != SRT_OK) return st;
     if (!r->d_lists) {       // first guess: a primitive in most bins of ONE super-bin (what small primitives come to); check_frame() corrects it
       const size_t guess = (size_t)P.nprims * P.super_bx * P.super_by * 3 / 4 + 65536;
-      if ((st = grow(&r->d_lists, &r->lists_cap, std::min<size_t>(guess, 1ull << 28))) != SRT_OK) return st;
+      if ((st = r->d_lists.ensure(std::min<size_t>(guess, 1ull << 28))) != SRT_OK) return st;
     }
     if (r->nlines && !r->d_ltable) {
-      if ((st = grow(&r->d_ltable, &r->ltable_cap, (size_t)r->nlines * 64 + 4096)) != SRT_OK) return st;
+      if ((st = r->d_ltable.ensure((size_t)r->nlines * 64 + 4096)) != SRT_OK) return st;
     }
     if (P.nprims) {
       const int bs = 256;
       raster_setup<<<dim3((P.nprims + bs - 1) / bs), dim3(bs), 0, s>>>(P, r->d_prims, r->d_aux, r->d_bbox, stats ? r->d_stats : nullptr,
-                                                                      r->d_laux, r->d_ltable, (uint32_t)std::min<size_t>(r->ltable_cap, 0xFFFFFFFFull), r->d_status);
+                                                                      r->d_laux, r->d_ltable, (uint32_t)std::min<size_t>(r->d_ltable.capacity(), 0xFFFFFFFFull), r->d_status);
     }
     // Ordered binning (raster_bin_pass): coarse bins of c x c tiles under <= 8 x 8 super-bins
     uint32_t* d_super_counts = r->d_super + ns * P.super_stride;
     raster_bin_pass<1><<<dim3((unsigned)ns), dim3(1024), 0, s>>>(P, r->d_bbox, nullptr, nullptr, r->d_super, d_super_counts, nullptr, 0u, r->d_status, r->d_prims);
-    raster_bin_pass<2><<<dim3((unsigned)nb), dim3(256), 0, s>>>(P, r->d_bbox, r->d_super, d_super_counts, reinterpret_cast<uint32_t*>(r->d_lists), r->d_counts, r->d_counts + nb,
-                                                                (uint32_t)std::min<size_t>(r->lists_cap, 0xFFFFFFFFull), r->d_status, r->d_prims);
+    raster_bin_pass<2><<<dim3((unsigned)nb), dim3(256), 0, s>>>(P, r->d_bbox, r->d_super, d_super_counts, reinterpret_cast<uint32_t*>(r->d_lists.get()), r->d_counts, r->d_counts + nb,
+                                                                (uint32_t)std::min<size_t>(r->d_lists.capacity(), 0xFFFFFFFFull), r->d_status, r->d_prims);
     r->bins_valid = true;
   }
   const uint32_t ntiles = P.tiles_x * P.tiles_y;
@@ -1227,9 +1215,9 @@ int launch_frame(srt_raster* r, hipStream_t s, bool dump_samples, bool stats) {
   const TilesKernel kern = tiles_kernel(stats, tsy, r->has_images);
   if (!kern) return srt::fail(SRT_ERR_STATE, "no tile kernel for %d-row tiles", tsy);
   const uint32_t wpb = tsy == 32 ? 1 : kTileWavesPerBlock;
-  kern<<<dim3((ntiles + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s>>>(P, r->d_prims, r->d_bbox, reinterpret_cast<const uint32_t*>(r->d_lists), r->d_counts,
+  kern<<<dim3((ntiles + wpb - 1) / wpb), dim3(WAVE * wpb), 0, s>>>(P, r->d_prims, r->d_bbox, reinterpret_cast<const uint32_t*>(r->d_lists.get()), r->d_counts,
                                                                   r->d_counts + (size_t)P.coarse_x * P.coarse_y, r->d_aux, r->d_tabs, r->d_texels, r->d_laux, r->d_ltable,
-                                                                  r->d_rgba, dump_samples ? r->d_samples : nullptr, stats ? r->d_stats : nullptr, r->d_status, r->d_host_status);
+                                                                  r->d_rgba, dump_samples ? r->d_samples : nullptr, stats ? r->d_stats : nullptr, r->d_status, r->h_status.device());
   SRT_HIP(hipGetLastError());
   r->resolved = true;
   return SRT_OK;
@@ -1239,13 +1227,13 @@ int launch_frame(srt_raster* r, hipStream_t s, bool dump_samples, bool stats) {
 // be repeated (storage grown, bins invalidated), 0 when the frame is good, < 0 on refusal / failure.
 int check_frame(srt_raster* r) {
   if (r->verified) return 0;
-  const volatile uint32_t* hs = r->h_status;
+  const volatile uint32_t* hs = r->h_status.get();
   const uint32_t table_need = hs[FS_TABLE_NEED], list_need = hs[FS_LIST_NEED], flags = hs[FS_FLAGS];
   if (flags & kFlagLineUnwalkable)
     return srt::fail(SRT_ERR_UNSUPPORTED, "a line's main loop runs over coordinates beyond 2^24, where the reference's `++x` on a float no longer advances");
   bool again = false;
-  if (table_need > r->ltable_cap) {
-    const int st = grow(&r->d_ltable, &r->ltable_cap, (size_t)table_need + table_need / 4 + 1024);
+  if (table_need > r->d_ltable.capacity()) {
+    const int st = r->d_ltable.ensure((size_t)table_need + table_need / 4 + 1024);
     if (st != SRT_OK) return st;
     again = true;
   }
@@ -1254,7 +1242,7 @@ int check_frame(srt_raster* r) {
       if (r->coarse_min >= 65536) return srt::fail(SRT_ERR_UNSUPPORTED, "the frame's bin lists need more than 2^32 entries");
       r->coarse_min *= 2;
     } else {
-      const int st = grow(&r->d_lists, &r->lists_cap, (size_t)list_need + list_need / 8 + 1024);
+      const int st = r->d_lists.ensure((size_t)list_need + list_need / 8 + 1024);
       if (st != SRT_OK) return st;
     }
     again = true;
@@ -1310,21 +1298,18 @@ int srt_raster_create(int device, srt_raster** out) {
   srt_raster* r = new (std::nothrow) srt_raster();
   if (!r) return srt::fail(SRT_ERR_INVALID, "out of host memory");
   r->device = device;
-  // (every failure below: srt_raster_destroy frees what the partly built context holds)
+  // (every failure below: srt_raster_destroy takes the partly built context away)
   const auto give_up = [r](const char* what) { (void)srt_raster_destroy(r); return srt::fail(SRT_ERR_HIP, "%s", what); };
   if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) return give_up("hipStreamCreate failed");
-  if (hipMalloc(&r->d_stats, ST_COUNT * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(&r->d_status, FS_COUNT * sizeof(uint32_t)) != hipSuccess ||
-      hipMemset(r->d_status, 0, FS_COUNT * sizeof(uint32_t)) != hipSuccess ||
-      hipHostMalloc((void**)&r->h_status, FS_COUNT * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&r->d_host_status, r->h_status, 0) != hipSuccess)
+  if (r->d_stats.ensure(ST_COUNT) != SRT_OK || r->d_status.ensure(FS_COUNT) != SRT_OK ||
+      hipMemset(r->d_status, 0, FS_COUNT * sizeof(uint32_t)) != hipSuccess || r->h_status.ensure(FS_COUNT, hipHostMallocMapped) != SRT_OK)
     return give_up("hipMalloc(stats) failed");
-  std::memset(r->h_status, 0, FS_COUNT * sizeof(uint32_t));
+  std::memset(r->h_status.get(), 0, FS_COUNT * sizeof(uint32_t));
   // hipMemset is ordered on the NULL stream; the context's kernels run on a non-blocking stream that does not wait for it.  Without
   // this wait the first frame could read what the allocation held before (seen on a box whose memory had been used: a stale
   // "line cannot be walked" flag refused a stream without lines).
   (void)hipDeviceSynchronize();
-  if (hipEventCreateWithFlags(&r->upload_done, hipEventDisableTiming) != hipSuccess) return give_up("hipEventCreate failed");
+  if (r->upload_done.create(hipEventDisableTiming) != SRT_OK) return give_up("hipEventCreate failed");
   *out = r;
   return SRT_OK;
 }
@@ -1334,24 +1319,6 @@ int srt_raster_destroy(srt_raster* r) {
   (void)hipSetDevice(r->device);
   if (r->stream) (void)hipStreamSynchronize(r->stream);   // (NULL stream / event: a context srt_raster_create gave up on)
   if (r->bound_out) (void)hipHostUnregister(r->bound_out);
-  (void)hipFree(r->d_prims);
-  (void)hipFree(r->d_bbox);
-  (void)hipFree(r->d_lists);
-  (void)hipFree(r->d_super);
-  (void)hipFree(r->d_counts);
-  (void)hipFree(r->d_rgba);
-  (void)hipFree(r->d_samples);
-  (void)hipFree(r->d_stats);
-  (void)hipFree(r->d_status);
-  (void)hipFree(r->d_texels);
-  (void)hipFree(r->d_aux);
-  (void)hipFree(r->d_tabs);
-  (void)hipFree(r->d_laux);
-  (void)hipFree(r->d_ltable);
-  if (r->h_status) (void)hipHostFree(r->h_status);
-  if (r->pending) (void)hipHostFree(r->pending);
-  if (r->texel_blob) (void)hipHostFree(r->texel_blob);
-  if (r->upload_done) (void)hipEventDestroy(r->upload_done);
   if (r->stream) (void)hipStreamDestroy(r->stream);
   (void)hipGetLastError();
   delete r;
@@ -1390,9 +1357,9 @@ int srt_raster_add_texture(srt_raster* r, uint32_t nlevels, const uint32_t* widt
       SRT_HIP(hipStreamSynchronize(r->stream));
       r->blob_upload_pending = false;
     }
-    if (r->blob_n + bytes > r->blob_cap) {
+    if (r->blob_n + bytes > r->texel_blob.capacity()) {
       SRT_HIP(hipSetDevice(r->device));
-      const int st = grow_pinned(&r->texel_blob, &r->blob_cap, r->blob_n, std::max(total, (r->blob_n + bytes) * 2), "bytes of texels");
+      const int st = grow_pinned(&r->texel_blob, r->blob_n, std::max(total, (r->blob_n + bytes) * 2), "bytes of texels");
       if (st != SRT_OK) return st;
     }
     std::memcpy(r->texel_blob + r->blob_n, level_texels[k], bytes);
@@ -1446,11 +1413,12 @@ int srt_raster_set_target(srt_raster* r, uint32_t width, uint32_t height, uint32
   P.tiles_x = (width + P.tile_px - 1) / P.tile_px;
   set_tile_height(P, choose_tile_height(sample_rate));   // (re-decided per frame: upload_stream)
   if (realloc_px) {
-    if (r->d_rgba) SRT_HIP(hipFree(r->d_rgba));
-    r->d_rgba = nullptr; r->have_target = false;   // until the allocation below has succeeded
-    SRT_HIP(hipMalloc(&r->d_rgba, (size_t)width * height * 4));
+    r->d_rgba.reset();
+    r->have_target = false;                        // until the allocation below has succeeded
+    const int st = r->d_rgba.ensure((size_t)width * height);
+    if (st != SRT_OK) return st;
   }
-  if (r->d_samples) { SRT_HIP(hipFree(r->d_samples)); r->d_samples = nullptr; }
+  r->d_samples.reset();
   r->have_target = true;
   r->resolved = false;
   r->bins_valid = false;                         // another tiling: setup (the lines' tables follow the target) and binning run again
@@ -1478,10 +1446,10 @@ int srt_raster_submit(srt_raster* r, const srt_prim* prims, size_t n) {
     if (prims[i].kind != SRT_PRIM_TRIANGLE && prims[i].kind != SRT_PRIM_POINT && prims[i].kind != SRT_PRIM_IMAGE && prims[i].kind != SRT_PRIM_LINE)
       return srt::fail(SRT_ERR_INVALID, "primitive %zu has unknown kind %u", i, prims[i].kind);
   { const int st = settle_upload(r); if (st != SRT_OK) return st; }
-  if (r->pending_n + n > r->pending_cap) {
+  if (r->pending_n + n > r->pending.capacity()) {
     SRT_HIP(hipSetDevice(r->device));
     SRT_HIP(hipStreamSynchronize(r->stream));      // (an upload may still be reading the old buffer)
-    const int st = grow_pinned(&r->pending, &r->pending_cap, r->pending_n, (r->pending_n + n) * 2 + 1024, "primitives");
+    const int st = grow_pinned(&r->pending, r->pending_n, (r->pending_n + n) * 2 + 1024, "primitives");
     if (st != SRT_OK) return st;
   }
   if (n) std::memcpy(r->pending + r->pending_n, prims, n * sizeof(srt_prim));
@@ -1515,7 +1483,7 @@ int srt_raster_resolve_device(srt_raster* r, void* stream, const uint8_t** d_rgb
   if (st != SRT_OK) return st;
   if (upload && s != r->stream) SRT_HIP(hipStreamSynchronize(r->stream));  // upload went on the context stream
   if ((st = run_frame(r, s, false, false)) != SRT_OK) return st;
-  if (d_rgba8_out) *d_rgba8_out = (const uint8_t*)r->d_rgba;
+  if (d_rgba8_out) *d_rgba8_out = (const uint8_t*)r->d_rgba.get();
   return SRT_OK;
 }
 
@@ -1531,7 +1499,7 @@ int srt_raster_read_samples(srt_raster* r, float* samples_out) {
   int st = begin_frame(r, "read_samples");
   if (st != SRT_OK) return st;
   const size_t bytes = (size_t)r->P.ssw * r->P.ssh * sizeof(float4);
-  if (!r->d_samples) SRT_HIP(hipMalloc(&r->d_samples, bytes));
+  if (!r->d_samples && (st = r->d_samples.ensure((size_t)r->P.ssw * r->P.ssh)) != SRT_OK) return st;
   if ((st = run_frame(r, r->stream, true, false)) != SRT_OK) return st;
   SRT_HIP(hipMemcpyAsync(samples_out, r->d_samples, bytes, hipMemcpyDeviceToHost, r->stream));
   SRT_HIP(hipStreamSynchronize(r->stream));
@@ -1552,7 +1520,7 @@ int srt_raster_stats(srt_raster* r, srt_raster_stats_t* out) {
   out->fragments = h[ST_FRAGMENTS];
   out->point_samples = h[ST_POINT_SAMPLES];
   out->bin_entries = h[ST_BIN_ENTRIES];
-  out->list_bytes = (uint64_t)(r->super_cap + r->counts_cap) * sizeof(uint32_t) + (uint64_t)r->lists_cap * sizeof(uint2);
+  out->list_bytes = (uint64_t)(r->d_super.capacity() + r->d_counts.capacity()) * sizeof(uint32_t) + (uint64_t)r->d_lists.capacity() * sizeof(uint2);
   return SRT_OK;
 }
 
