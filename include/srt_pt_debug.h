@@ -135,8 +135,8 @@ int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* ou
  * as 0 / 1, t, dist} of rays 0, 1, 2 from the batch form, the same nine from the plain form, delta of rays 0, 1, 2, and 1 where the
  * lane's wave held a lane with delta == 0 and computed the tangent root; a wave is 64 consecutive lanes). */
 int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* out);
-/* BBox::hit as the sweeps evaluate it (pt_wave.h: box_hit_inv - both products per axis, the select on the results) next to the
- * form of the per-lane traversals (pt_trace.h: box_hit_rec - the bound selected first), lane i on its own operands.  in: 14 planes
+/* BBox::hit as the sweeps of pt_wave.h evaluate it (box_hit_inv - both products per axis, the select on the results) next to the
+ * form of the per-lane traversals (box_hit_rec - the bound selected first; both in pt_trace.h), lane i on its own operands.  in: 14 planes
  * of `lanes` floats (box min xyz, box max xyz, origin xyz, reciprocal direction xyz, incoming times x and y); out: 6 planes ({hit
  * as 0 / 1, times.x, times.y} of box_hit_inv, the same three of box_hit_rec). */
 int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out);

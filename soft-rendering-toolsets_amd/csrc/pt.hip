@@ -1,5 +1,6 @@
-// MI355X (gfx950) path tracer: Pathtracer::trace_pixel and everything below it as HIP kernels, plus the
-// C ABI of include/srt_pt.h.  Reference paths are relative to /root/reference/Assignments/Scotty3D/src/.
+// MI355X (gfx950) path tracer: Pathtracer::trace_pixel and everything below it as HIP kernels, plus the render
+// part of the C ABI of include/srt_pt.h - the only unit that includes pt_wave.h / pt_stream.h (pt_context.h names the
+// others).  Reference paths are relative to /root/reference/Assignments/Scotty3D/src/.
 //
 //   trace_pixel               student/pathtracer.cpp:14-40      -> path_sample()
 //   trace                     student/pathtracer.cpp:174-218    -> the bounce loop of path_sample()
@@ -19,8 +20,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "pt_context.h"
@@ -135,304 +134,6 @@ __global__ __launch_bounds__(64, 8) void pt_normals_kernel(DScene S, TileMap T, 
   if ((threadIdx.x & 63) == 0 && r) atomicAdd(ray_counter, r);
 }
 
-// Explicit (x, y, sample) triples; instrumented when COUNT.  NORMALS: the normal-colors view (normal_sample) instead of a path.
-template <bool COUNT, bool NORMALS = false>
-__global__ __launch_bounds__(64) void pt_samples_kernel(DScene S, uint64_t seed, const uint32_t* __restrict__ xs,
-                                                        const uint32_t* __restrict__ ys, const uint32_t* __restrict__ ss,
-                                                        uint32_t n, float* __restrict__ rgb, uint32_t* __restrict__ draws,
-                                                        uint32_t* __restrict__ rays, unsigned long long* __restrict__ totals) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Counters cnt;
-  for (int k = 0; k < C_COUNT; k++) cnt.v[k] = 0;
-  Rng rng;
-  rng.key(seed, ys[i] * S.w + xs[i], ss[i]);
-  const Spec p = NORMALS ? normal_sample<COUNT>(S, xs[i], ys[i], rng, cnt) : path_sample<COUNT>(S, xs[i], ys[i], rng, cnt);
-  rgb[3 * i] = p.r; rgb[3 * i + 1] = p.g; rgb[3 * i + 2] = p.b;
-  if (draws) draws[i] = rng.draws;
-  if (COUNT) {
-    if (rays) rays[i] = cnt.v[C_RAYS];
-    for (int k = 0; k < C_COUNT; k++) atomicAdd(&totals[k], (unsigned long long)cnt.v[k]);
-  }
-}
-
-// FLAT: the query goes through flat_trace3 (pt_flat.h) in batch slot i % 3 instead of the nested scene_hit.
-template <bool FLAT>
-__global__ void pt_hit_kernel(DScene S, const float* __restrict__ org, const float* __restrict__ dir,
-                              const float* __restrict__ bounds, uint32_t n, float* __restrict__ out9) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i < n;                     // every lane stays in the kernel: flat_trace3 is a wave-wide loop
-  const uint32_t j = live ? i : 0;
-  Ray r;
-  r.o = v3(org[3 * j], org[3 * j + 1], org[3 * j + 2]);
-  r.d = v3(dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
-  r.b0 = bounds[2 * j]; r.b1 = bounds[2 * j + 1];
-  Counters cnt;
-  Hit h;
-  if (FLAT) {
-    const uint32_t slot = i % 3u;
-    Hit res[3];
-    flat_trace3(S, r.o, r.d, r.d, r.d, r.b0, r.b1, live && slot == 0, live && slot == 1, live && slot == 2, res[0], res[1], res[2]);
-    h = slot == 0 ? res[0] : (slot == 1 ? res[1] : res[2]);
-  } else {
-    h = scene_hit<false>(S, r, cnt);
-  }
-  if (!live) return;
-  float* o = out9 + 9 * i;
-  for (int k = 0; k < 9; k++) o[k] = 0.0f;
-  if (h.hit) {
-    const Surface sf = surface_of(S, h, r);
-    o[0] = 1.0f; o[1] = h.dist;
-    o[2] = sf.position.x; o[3] = sf.position.y; o[4] = sf.position.z;
-    o[5] = sf.normal.x; o[6] = sf.normal.y; o[7] = sf.normal.z;
-    o[8] = (float)S.objects[h.obj].material;
-  }
-}
-
-// Scene_Particles::Particle::update (student/particles.cpp:5-59), one lane per particle: the second caller of Object::hit
-// (SURVEY.md 8(f)-4).  The particle flies at constant velocity for what is left of dt, bounces off what
-// scene.hit(Ray(pos, velocity)) reports - default bounds [0, inf], the direction is the velocity, NOT normalised - and
-// gravity acts on the velocity after every leg.  The reference's loop does not return when hit_time stays <= 0; a lane
-// gives up after kParticleMaxLegs legs.
-constexpr uint32_t kParticleMaxLegs = 4096;
-__global__ __launch_bounds__(64) void pt_particles_kernel(DScene S, float* __restrict__ pos, float* __restrict__ vel, float* __restrict__ age,
-                                                          uint32_t n, float dt, float radius, uint8_t* __restrict__ alive) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  V3 p = v3(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
-  V3 velocity = v3(vel[3 * k], vel[3 * k + 1], vel[3 * k + 2]);
-  const V3 acceleration = v3(0.0f, -9.8f, 0.0f);
-  float remain = dt;
-  Counters cnt;
-  for (uint32_t leg = 0; remain > 0 && leg < kParticleMaxLegs; leg++) {
-    Ray r;
-    r.o = p; r.d = velocity; r.b0 = 0.0f; r.b1 = __uint_as_float(0x7f800000u);
-    const Hit h = scene_hit<false>(S, r, cnt);
-    V3 t_normal = v3(0, 0, 0), t_position = v3(0, 0, 0);       // a Trace without a hit is all zeros (rays/trace.h)
-    if (h.hit) { const Surface sf = surface_of(S, h, r); t_normal = sf.normal; t_position = sf.position; }
-    float cos_t = dot(t_normal, velocity * -1.0f) / (norm(velocity) * norm(t_normal));
-    V3 surface_normal = t_normal / norm(t_normal);
-    if (cos_t < 0) {
-      cos_t = (float)sqrt((double)(1 - cos_t * cos_t));          // unqualified sqrt: the double overload
-      surface_normal = surface_normal * -1.0f;
-    }
-    const float interval = fabsf(radius / cos_t);
-    const float hit_time = (h.dist - interval) / norm(r.d);
-    if (!h.hit || hit_time > remain || cos_t == 0) {
-      p = p + velocity * remain;
-      velocity = velocity + acceleration * remain;
-      break;
-    }
-    p = t_position - (velocity * interval) / norm(velocity);
-    velocity = velocity - surface_normal * (2.0f * dot(velocity, surface_normal));
-    velocity = velocity + acceleration * hit_time;
-    remain -= hit_time;
-  }
-  const float a = age[k] - dt;
-  age[k] = a;
-  alive[k] = a > 0 ? 1 : 0;
-  pos[3 * k] = p.x; pos[3 * k + 1] = p.y; pos[3 * k + 2] = p.z;
-  vel[3 * k] = velocity.x; vel[3 * k + 1] = velocity.y; vel[3 * k + 2] = velocity.z;
-}
-
-__global__ void pt_untile_kernel(TileMap T, uint32_t w, uint32_t h, uint32_t tiles_per_rank,
-                                 const float* __restrict__ gathered, float* __restrict__ image) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= w * h) return;
-  const uint32_t x = i % w, y = i / w;
-  const uint32_t tile = (y / T.tile_h) * T.tiles_x + (x / T.tile_w);
-  const uint32_t rank = tile % T.world, local = tile / T.world;
-  const size_t src = (((size_t)rank * tiles_per_rank + local) * (T.tile_w * T.tile_h) + (size_t)(y % T.tile_h) * T.tile_w +
-                      (x % T.tile_w)) * 3;
-  image[3 * (size_t)i] = gathered[src];
-  image[3 * (size_t)i + 1] = gathered[src + 1];
-  image[3 * (size_t)i + 2] = gathered[src + 2];
-}
-
-// Pathtracer::accumulate: s += (n - s) * (1.0f / accumulator_samples)
-__global__ void pt_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ epoch, size_t n, float inv) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) acc[i] += (epoch[i] - acc[i]) * inv;
-}
-
-__global__ void pt_math_kernel(const float* __restrict__ x, size_t n, float* __restrict__ c, float* __restrict__ s) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { c[i] = srt_cosf(x[i]); s[i] = srt_sinf(x[i]); }
-}
-
-__global__ void pt_acos_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = srt_acosf(x[i]);
-}
-
-__global__ void pt_atan2_kernel(const float* __restrict__ y, const float* __restrict__ x, size_t n, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = srt_atan2f(y[i], x[i]);
-}
-
-// HDR_Image::tonemap_to (util/hdr_image.cpp:161-187): output row j is image row h-1-j; per channel
-// 1 - exp(-c * exposure), Spectrum::to_srgb, (unsigned char)round(c * 255); alpha 255.  One lane per pixel, one packed
-// 32-bit store (consecutive lanes: consecutive pixels of an output row, 12-byte loads / 4-byte stores, fully coalesced).
-__global__ void pt_tonemap_kernel(const float* __restrict__ rgb, uint32_t w, uint32_t h, float exposure, uint32_t* __restrict__ rgba) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= (size_t)w * h) return;
-  const uint32_t j = (uint32_t)(p / w), i = (uint32_t)(p % w);
-  const float* s = rgb + 3 * ((size_t)(h - j - 1) * w + i);
-  uint32_t px = 0xff000000u;
-#pragma unroll
-  for (int c = 0; c < 3; c++) px |= srgb_byte(to_srgb(1.0f - srt_expf(-s[c] * exposure))) << (8 * c);
-  rgba[p] = px;
-}
-__global__ void pt_exp_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = srt_expf(x[i]);
-}
-__global__ void pt_pow_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = srt_powf(x[i], y[i]);
-}
-
-// Diagnostic for divNx3 / sqrtN (pt_device.h): lane i takes the operands of "rays" 3i, 3i+1, 3i+2 — exactly how the
-// wave kernel's batch tests call them.  io layout: planes of n3 = 3 * lanes floats: num0, num1, num2, den, x in; q0, q1, q2,
-// root out.  shared_c2: column 2's numerator of a lane is num2[3i] for its three rays (the triangle test's shared t numerator).
-__global__ void pt_div_sqrt_kernel(const float* __restrict__ in, size_t lanes, int shared_c2, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t n3 = lanes * 3;
-  const size_t k = (i < lanes ? i : lanes - 1) * 3;     // every lane of the last wave computes; the spares repeat the last lane
-  float num[3][3], den[3], q[3][3], x[3], root[3];
-  bool zero[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    num[r][0] = in[k + r]; num[r][1] = in[n3 + k + r];
-    num[r][2] = in[2 * n3 + (shared_c2 ? k : k + r)];
-    den[r] = in[3 * n3 + k + r];
-    x[r] = in[4 * n3 + k + r];
-    zero[r] = __float_as_uint(x[r]) == 0u;
-  }
-  if (shared_c2) divNx3<3, true>(num, den, q); else divNx3<3, false>(num, den, q);
-  sqrtN<3>(x, zero, root);
-  if (i < lanes) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      out[k + r] = q[r][0]; out[n3 + k + r] = q[r][1]; out[2 * n3 + k + r] = q[r][2];
-      out[3 * n3 + k + r] = root[r];
-    }
-  }
-}
-
-// Triangle::hit of the wave kernel's fold (tri_hitN<3>: verdict from the numerators, only t divided) next to the plain per-ray
-// form (tri_hit), lane i on its own triangle, origin and three rays.  in: 27 planes of `lanes` floats (p0, e1, e2, origin, three
-// directions, then b0 and b1 of the three rays); out: 19 planes - {hit, t, dist} x 3 rays of the batch form, the same of
-// tri_hit, and "this lane's wave computed u and v after all" (an ambiguous lane in it).
-__global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t k = i < lanes ? i : lanes - 1;           // every lane of the last wave computes; the spares repeat the last lane
-  float v[27];
-#pragma unroll
-  for (int j = 0; j < 27; j++) v[j] = in[(size_t)j * lanes + k];
-  Tri g;
-#pragma unroll
-  for (int j = 0; j < 3; j++) { g.p0[j] = v[j]; g.e1[j] = v[3 + j]; g.e2[j] = v[6 + j]; }
-  const V3 org = v3(v[9], v[10], v[11]);
-  V3 d[3];
-  float b0[3], b1[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) { d[r] = v3(v[12 + 3 * r], v[13 + 3 * r], v[14 + 3 * r]); b0[r] = v[21 + r]; b1[r] = v[24 + r]; }
-  TriHitT hb[3];
-  bool fallback = false;
-  tri_hitN<3>(g, org, d, b0, b1, hb, &fallback);
-  if (i < lanes) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
-      const TriHit hp = tri_hit(g, ray);
-      out[(size_t)(3 * r) * lanes + i] = hb[r].hit ? 1.0f : 0.0f;
-      out[(size_t)(3 * r + 1) * lanes + i] = hb[r].t;
-      out[(size_t)(3 * r + 2) * lanes + i] = hb[r].dist;
-      out[(size_t)(9 + 3 * r) * lanes + i] = hp.hit ? 1.0f : 0.0f;
-      out[(size_t)(10 + 3 * r) * lanes + i] = hp.t;
-      out[(size_t)(11 + 3 * r) * lanes + i] = hp.dist;
-    }
-    out[(size_t)18 * lanes + i] = fallback ? 1.0f : 0.0f;
-  }
-}
-
-// Sphere::hit of the wave kernel's batch (sphere_hitN<3> and the distance step through sqrtN, as object_testN's sphere branch in
-// pt_wave.h performs them - restated below, since moving the branch into a function of its own changed a wave kernel's scratch)
-// next to the plain per-ray form (sphere_hit, then the distance as object_hit has it, pt_trace.h), lane i on its own radius,
-// origin and three rays.  in: 19 planes of `lanes` floats (radius, origin, three directions, then b0 and b1 of the three
-// rays); out: 22 planes - {hit, t, dist} x 3 rays of the batch form, the same of the plain form, delta of the three rays
-// (sphere_two_roots), and "this lane's wave computed the tangent root" (a lane with delta == 0 in it).
-__global__ void pt_sphere_batch_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t k = i < lanes ? i : lanes - 1;           // every lane of the last wave computes; the spares repeat the last lane
-  float v[19];
-#pragma unroll
-  for (int j = 0; j < 19; j++) v[j] = in[(size_t)j * lanes + k];
-  const float radius = v[0];
-  const V3 org = v3(v[1], v[2], v[3]);
-  V3 d[3], pos[3];
-  float b0[3], b1[3], tb[3], db[3];
-  bool hb[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) { d[r] = v3(v[4 + 3 * r], v[5 + 3 * r], v[6 + 3 * r]); b0[r] = v[13 + r]; b1[r] = v[16 + r]; }
-  bool tangent = false;
-  {                                                     // the sphere branch of object_testN (pt_wave.h), line for line: change both
-    constexpr int NR = 3;
-    SphHit sh[NR];
-    sphere_hitN<NR>(radius, org, d, b0, b1, sh, &tangent);
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-      hb[r] = sh[r].hit; tb[r] = sh[r].t;
-      pos[r] = org + d[r] * sh[r].t;                    // Ray::at
-    }
-    float n2[NR], nr[NR];
-    bool miss[NR];                                      // no hit: t = 0, pos == origin
-#pragma unroll
-    for (int r = 0; r < NR; r++) { n2[r] = norm2(pos[r] - org); miss[r] = !hb[r]; }
-    sqrtN<NR>(n2, miss, nr);
-#pragma unroll
-    for (int r = 0; r < NR; r++) db[r] = fabsf(nr[r]);
-  }
-  if (i < lanes) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
-      const SphHit hp = sphere_hit(radius, ray);
-      bool hit_two;
-      float t_two;
-      const float delta = sphere_two_roots(radius, ray, hit_two, t_two);
-      out[(size_t)(3 * r) * lanes + i] = hb[r] ? 1.0f : 0.0f;
-      out[(size_t)(3 * r + 1) * lanes + i] = tb[r];
-      out[(size_t)(3 * r + 2) * lanes + i] = db[r];
-      out[(size_t)(9 + 3 * r) * lanes + i] = hp.hit ? 1.0f : 0.0f;
-      out[(size_t)(10 + 3 * r) * lanes + i] = hp.t;
-      out[(size_t)(11 + 3 * r) * lanes + i] = fabsf(norm(ray_at(ray, hp.t) - ray.o));
-      out[(size_t)(18 + r) * lanes + i] = delta;
-    }
-    out[(size_t)21 * lanes + i] = tangent ? 1.0f : 0.0f;
-  }
-}
-
-// BBox::hit of the sweeps (box_hit_inv, pt_wave.h: both products per axis, the select on the results) next to the form of the
-// per-lane traversals (box_hit_rec, pt_trace.h: the bound selected first), lane i on its own box, origin, reciprocal direction
-// and incoming `times`.  in: 14 planes of `lanes` floats (box min xyz, box max xyz, origin xyz, 1 / direction xyz, times x, y);
-// out: 6 planes - {hit as 0 / 1, times.x, times.y} of box_hit_inv, then the same of box_hit_rec.
-__global__ void pt_box_sweep_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= lanes) return;
-  float v[14];
-#pragma unroll
-  for (int j = 0; j < 14; j++) v[j] = in[(size_t)j * lanes + i];
-  const float bx[6] = {v[0], v[1], v[2], v[3], v[4], v[5]};
-  const V3 org = v3(v[6], v[7], v[8]), inv = v3(v[9], v[10], v[11]);
-  float ax = v[12], ay = v[13], bxx = v[12], bxy = v[13];
-  const bool ha = box_hit_inv(bx, org, inv, ax, ay);
-  const bool hb = box_hit_rec(bx, org, inv, bxx, bxy);
-  out[i] = ha ? 1.0f : 0.0f; out[lanes + i] = ax; out[2 * lanes + i] = ay;
-  out[3 * lanes + i] = hb ? 1.0f : 0.0f; out[4 * lanes + i] = bxx; out[5 * lanes + i] = bxy;
-}
-
 }  // namespace srt
 
 // ---------------------------------------------------------------------------------------------------
@@ -451,15 +152,6 @@ int check_stream_fault(srt_pt* pt, const char* what) {
   return SRT_OK;
 }
 
-int need_ready(srt_pt* pt, const char* what) {
-  int st = need_device(pt, what);
-  if (st != SRT_OK) return st;
-  if (!pt->committed) return not_committed(what);
-  if (!pt->have_cam) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_camera", what);
-  if (!pt->w || !pt->h) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_params", what);
-  return SRT_OK;
-}
-
 // srt_pt_set_elision asked for it and the BSDF-sampled direct ray of every continuous bounce is provably dead in this scene:
 // no delta light, no environment light, and no light material without emission (it would be shaded as a continuous,
 // non-Lambertian BSDF).  include/srt_pt.h, pt_wave.h.
@@ -475,33 +167,6 @@ bool elision_provable(const srt_pt* pt) {
         if (!(fabsf(m.a[i]) <= 1e15f)) return false;
   }
   return true;
-}
-
-DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B = nullptr) {
-  const FlatScene& F = pt->built.flat;
-  DScene S;
-  S.ray_log = B ? B->d_ray_log.get() : nullptr; S.ray_log_cap = B ? B->ray_log_cap : 0u;
-  S.nodes = pt->d_nodes; S.tris = pt->d_tris; S.tri_nrm = pt->d_nrm; S.objects = pt->d_objects;
-  S.lights = pt->d_lights; S.light_tris = pt->d_ltris; S.materials = pt->d_mats;
-  S.wave_tlas = pt->d_wave; S.wave_q = (uint32_t)F.wave_tlas.size(); S.blas_recs = pt->d_blas; S.wave_lazy = pt->d_wave_lazy;
-  S.delta_lights = pt->d_dlights; S.ndelta = (uint32_t)F.delta_lights.size();
-  S.env_map = pt->d_env_map; S.env_w = pt->env_w; S.env_h = pt->env_h;
-  S.env_type = pt->env_type; S.env_radiance[0] = pt->env_radiance[0]; S.env_radiance[1] = pt->env_radiance[1]; S.env_radiance[2] = pt->env_radiance[2];
-  S.nobjects = (uint32_t)F.objects.size(); S.nlights = (uint32_t)F.lights.size();
-  S.tlas_nodes = F.tlas_nodes; S.use_bvh = F.use_bvh ? 1u : 0u; S.light_tri_first = F.light_tri_first;
-  S.cam = pt->cam; S.w = pt->w; S.h = pt->h; S.max_depth = pt->max_depth;
-  S.elide = elision_provable(pt) ? 1u : 0u;
-  return S;
-}
-
-void update_tiling(srt_pt* pt) {
-  TileMap& T = pt->tiles;
-  if (!pt->w || !pt->h) { T.tiles_x = T.tiles_y = T.local_tiles = 0; pt->tiles_per_rank = 0; return; }
-  T.tiles_x = (pt->w + T.tile_w - 1) / T.tile_w;
-  T.tiles_y = (pt->h + T.tile_h - 1) / T.tile_h;
-  const uint32_t ntiles = T.tiles_x * T.tiles_y;
-  pt->tiles_per_rank = (ntiles + T.world - 1) / T.world;
-  T.local_tiles = (ntiles > T.rank) ? (ntiles - T.rank + T.world - 1) / T.world : 0;
 }
 
 // The scratch set of stream `s` (created on first use), with what every kernel form needs: the stream's sticky cancel word and,
@@ -529,16 +194,6 @@ int stream_buffers(srt_pt* pt, hipStream_t s, srt_pt::EpochBuffers** out) {
   return SRT_OK;
 }
 
-// Which traversal the persistent wave kernel would use for this scene and kernel mode: 0 wave-uniform sweeps,
-// 1 sweeps + per-lane walk of each BVH<Triangle>, 2 flattened per-lane walk (pt_flat.h); -1: not the wave kernel.
-// The flattened walk (pt_flat.h) packs a hit as 5 + 27 bits and a TLAS leaf's object count in 3 bits.
-bool flat_walk_fits(const FlatScene& F) {
-  bool fits = F.objects.size() >= 1 && F.objects.size() <= 31 && F.tris.size() < (1u << 27);
-  for (const WaveInterior& w : F.wave_tlas)
-    if ((w.l_ref < 0 && w.l_cnt > kFlatMaxLeafObjects) || (w.r_ref < 0 && w.r_cnt > kFlatMaxLeafObjects)) fits = false;
-  return fits;
-}
-
 // The streamed form (pt_stream.h): any number of objects, as long as a hit still packs into one word
 // (object slot << shift | triangle) and the references fit the 30-bit field of an LDS frame.
 uint32_t stream_obj_shift(const FlatScene& F) {
@@ -554,6 +209,8 @@ bool stream_fits(const FlatScene& F) {
   return true;
 }
 
+// Which traversal the persistent wave kernel would use for this scene and kernel mode: 0 wave-uniform sweeps,
+// 1 sweeps + per-lane walk of each BVH<Triangle>, 2 flattened per-lane walk (pt_flat.h); -1: not the wave kernel.
 int wave_trav(const srt_pt* pt) {
   const FlatScene& F = pt->built.flat;
   const int m = pt->kernel_mode;
@@ -953,28 +610,6 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
   return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
 }
 
-// The test-only math round trips (srt_pt_debug.h): `what`'s argument checks, upload the input planes of in_floats floats each,
-// launch(device inputs, device outputs), download the output planes of out_floats floats each, synchronise.
-template <size_t K, size_t M, class Launch>
-int math_round_trip(srt_pt* pt, const char* what, const float* const (&in)[K], size_t in_floats, float* const (&out)[M], size_t out_floats, Launch&& launch) {
-  int st = need_device(pt, what);
-  if (st != SRT_OK) return st;
-  for (const float* p : in) if (!p) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
-  for (const float* p : out) if (!p) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
-  if (!in_floats) return SRT_OK;
-  DeviceBuffer<float> din_own[K], dout_own[M];            // (this call's own: freed on every return)
-  float *din[K], *dout[M];
-  for (size_t k = 0; k < K; k++) { if ((st = din_own[k].ensure(in_floats))) return st; din[k] = din_own[k]; }
-  for (size_t m = 0; m < M; m++) { if ((st = dout_own[m].ensure(out_floats))) return st; dout[m] = dout_own[m]; }
-  for (size_t k = 0; k < K; k++) SRT_HIP(hipMemcpyAsync(din[k], in[k], in_floats * 4, hipMemcpyHostToDevice, pt->stream));
-  launch(din, dout);
-  SRT_HIP(hipGetLastError());
-  for (size_t m = 0; m < M; m++) SRT_HIP(hipMemcpyAsync(out[m], dout[m], out_floats * 4, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipStreamSynchronize(pt->stream));
-  return SRT_OK;
-}
-dim3 math_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // One epoch with one lane per sample (general scenes).
 int render_epoch_units(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t sample_base, uint32_t samples, float* d_tiles_out) {
   const TileMap& T = pt->tiles;
@@ -1016,299 +651,45 @@ int render_epoch_normals(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t samp
 
 }  // namespace
 
+// What the other units of the library call here (declared in pt_context.h / pt_internal.h).
 namespace srt {
-int need_device(srt_pt* pt, const char* what) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "%s: NULL context", what);
-  if (pt->device < 0) return srt::fail(SRT_ERR_NO_DEVICE, "%s needs a HIP device; this context is host-only and there is no CPU fallback", what);
-  SRT_HIP(hipSetDevice(pt->device));
-  return SRT_OK;
+DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B) {
+  const FlatScene& F = pt->built.flat;
+  DScene S;
+  S.ray_log = B ? B->d_ray_log.get() : nullptr; S.ray_log_cap = B ? B->ray_log_cap : 0u;
+  S.nodes = pt->d_nodes; S.tris = pt->d_tris; S.tri_nrm = pt->d_nrm; S.objects = pt->d_objects;
+  S.lights = pt->d_lights; S.light_tris = pt->d_ltris; S.materials = pt->d_mats;
+  S.wave_tlas = pt->d_wave; S.wave_q = (uint32_t)F.wave_tlas.size(); S.blas_recs = pt->d_blas; S.wave_lazy = pt->d_wave_lazy;
+  S.delta_lights = pt->d_dlights; S.ndelta = (uint32_t)F.delta_lights.size();
+  S.env_map = pt->d_env_map; S.env_w = pt->env_w; S.env_h = pt->env_h;
+  S.env_type = pt->env_type; S.env_radiance[0] = pt->env_radiance[0]; S.env_radiance[1] = pt->env_radiance[1]; S.env_radiance[2] = pt->env_radiance[2];
+  S.nobjects = (uint32_t)F.objects.size(); S.nlights = (uint32_t)F.lights.size();
+  S.tlas_nodes = F.tlas_nodes; S.use_bvh = F.use_bvh ? 1u : 0u; S.light_tri_first = F.light_tri_first;
+  S.cam = pt->cam; S.w = pt->w; S.h = pt->h; S.max_depth = pt->max_depth;
+  S.elide = elision_provable(pt) ? 1u : 0u;
+  return S;
+}
+
+// The flattened walk (pt_flat.h) packs a hit as 5 + 27 bits and a TLAS leaf's object count in 3 bits.
+bool flat_walk_fits(const FlatScene& F) {
+  bool fits = F.objects.size() >= 1 && F.objects.size() <= 31 && F.tris.size() < (1u << 27);
+  for (const WaveInterior& w : F.wave_tlas)
+    if ((w.l_ref < 0 && w.l_cnt > kFlatMaxLeafObjects) || (w.r_ref < 0 && w.r_cnt > kFlatMaxLeafObjects)) fits = false;
+  return fits;
+}
+
+void report_cast_stats(srt_pt* pt) {
+  if (pt->d_cast_stats) {                               // SRT_CAST_STATS=1 (diagnostic): the sums, on stderr
+    unsigned long long h[CS_COUNT];
+    static const char* names[CS_COUNT] = {"outer", "fetch", "interior_trips", "interior_lanes", "leaf_trips", "leaf_lanes", "leaf_tris",
+                                          "object_trips", "object_lanes", "cycles_fetch", "cycles_interior", "walking_lanes", "cycles_leaf", "cycles_object"};
+    if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, pt->d_cast_stats, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
+      for (int i = 0; i < CS_COUNT; i++) fprintf(stderr, "[srt] cast %s %llu\n", names[i], h[i]);
+  }
 }
 
 int pt_check_fault(srt_pt* pt, const char* what) { return pt ? check_stream_fault(pt, what) : SRT_OK; }
 }  // namespace srt
-
-extern "C" {
-
-int srt_pt_create(int device, srt_pt** out) {
-  if (!out) return srt::fail(SRT_ERR_INVALID, "srt_pt_create: out is NULL");
-  *out = nullptr;
-  srt_pt* pt = new (std::nothrow) srt_pt();
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "out of host memory");
-  if (device >= 0) {
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0) {
-      delete pt;
-      return srt::fail(SRT_ERR_NO_DEVICE, "no HIP device available (%s); this path has no CPU fallback",
-                       e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
-    }
-    if (device >= count) { delete pt; return srt::fail(SRT_ERR_INVALID, "device %d out of range [0,%d)", device, count); }
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&pt->stream, hipStreamNonBlocking) != hipSuccess ||
-        pt->d_totals.ensure(C_COUNT + 4) != SRT_OK || pt->h_fault.ensure(1, hipHostMallocMapped) != SRT_OK ||
-        pt->h_cancel.ensure(1, hipHostMallocMapped) != SRT_OK ||
-        hipMemset(pt->d_totals, 0, (C_COUNT + 4) * sizeof(unsigned long long)) != hipSuccess) {
-      delete pt;
-      return srt::fail(SRT_ERR_HIP, "HIP context setup failed on device %d", device);
-    }
-    *pt->h_fault = 0u;
-    *pt->h_cancel = 0u;
-    (void)hipDeviceSynchronize();                         // (the null-stream memset above: done before any non-blocking stream's first kernel)
-    pt->device = device;
-  }
-  *out = pt;
-  return SRT_OK;
-}
-
-int srt_pt_destroy(srt_pt* pt) {
-  if (!pt) return SRT_OK;
-  if (pt->device >= 0) {
-    (void)hipSetDevice(pt->device);
-    discard_pending(pt);
-    (void)hipStreamSynchronize(pt->stream);
-    if (pt->d_cast_stats) {                               // SRT_CAST_STATS=1 (diagnostic): the sums, on stderr
-      unsigned long long h[CS_COUNT];
-      static const char* names[CS_COUNT] = {"outer", "fetch", "interior_trips", "interior_lanes", "leaf_trips", "leaf_lanes", "leaf_tris",
-                                            "object_trips", "object_lanes", "cycles_fetch", "cycles_interior", "walking_lanes", "cycles_leaf", "cycles_object"};
-      if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, pt->d_cast_stats, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
-        for (int i = 0; i < CS_COUNT; i++) fprintf(stderr, "[srt] cast %s %llu\n", names[i], h[i]);
-    }
-    (void)hipStreamDestroy(pt->stream);
-  }
-  delete pt;
-  return SRT_OK;
-}
-
-int srt_pt_scene_begin(srt_pt* pt) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_begin: NULL context");
-  discard_pending(pt);
-  pt->inputs.clear();
-  pt->materials.clear();
-  pt->delta_lights.clear();
-  pt->env_type = 0;
-  pt->env_map.clear(); pt->env_w = pt->env_h = 0;
-  pt->committed = false;
-  pt->scene_generation++;
-  return SRT_OK;
-}
-
-int srt_pt_add_material(srt_pt* pt, const srt_pt_material* m, uint32_t* index_out) {
-  if (!pt || !m) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_material: NULL argument");
-  if (m->type > SRT_MAT_REFRACT) return srt::fail(SRT_ERR_INVALID, "unknown material type %u", m->type);
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  Material mm;
-  mm.type = m->type;
-  for (int i = 0; i < 3; i++) { mm.a[i] = m->a[i]; mm.b[i] = m->b[i]; }
-  mm.ior = m->ior;
-  pt->materials.push_back(mm);
-  if (index_out) *index_out = (uint32_t)pt->materials.size() - 1;
-  return SRT_OK;
-}
-
-int srt_pt_add_mesh(srt_pt* pt, const float* positions, const float* normals, uint32_t nverts, const uint32_t* indices,
-                    uint32_t nindices, const float trans[16], uint32_t material, int is_area_light) {
-  if (!pt || !positions || !normals || !indices || !trans) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_mesh: NULL argument");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (nverts == 0 || nindices == 0 || nindices % 3) return srt::fail(SRT_ERR_INVALID, "mesh needs >= 1 triangle (nindices %u)", nindices);
-  if (material >= pt->materials.size()) return srt::fail(SRT_ERR_INVALID, "material %u not defined", material);
-  for (uint32_t i = 0; i < nindices; i++)
-    if (indices[i] >= nverts) return srt::fail(SRT_ERR_INVALID, "index %u (= %u) out of range (nverts %u)", i, indices[i], nverts);
-  ObjectInput o;
-  o.kind = OBJ_MESH;
-  std::memcpy(&o.trans, trans, sizeof(Mat4));
-  o.material = material;
-  o.is_light = is_area_light != 0;
-  o.mesh.pos.assign(positions, positions + 3 * (size_t)nverts);
-  o.mesh.nrm.assign(normals, normals + 3 * (size_t)nverts);
-  o.mesh.idx.assign(indices, indices + nindices);
-  pt->inputs.push_back(std::move(o));
-  return SRT_OK;
-}
-
-int srt_pt_add_instance(srt_pt* pt, uint32_t source_object, const float trans[16], uint32_t material) {
-  if (!pt || !trans) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: NULL argument");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (source_object >= pt->inputs.size()) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: object %u is not added yet (%zu objects so far)", source_object, pt->inputs.size());
-  const ObjectInput& src = pt->inputs[source_object];
-  if (src.kind != OBJ_MESH || src.source >= 0)
-    return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: object %u is %s, not a mesh added by srt_pt_add_mesh", source_object,
-                     src.kind != OBJ_MESH ? "a sphere" : "an instance");
-  if (material >= pt->materials.size()) return srt::fail(SRT_ERR_INVALID, "material %u not defined", material);
-  if (pt->materials[material].type == SRT_MAT_DIFFUSE_LIGHT)
-    return srt::fail(SRT_ERR_INVALID, "srt_pt_add_instance: an emissive object needs triangles of its own in the area-light list; add it with srt_pt_add_mesh");
-  ObjectInput o;
-  o.kind = OBJ_MESH;
-  std::memcpy(&o.trans, trans, sizeof(Mat4));
-  o.material = material;
-  o.source = (int32_t)source_object;
-  pt->inputs.push_back(std::move(o));
-  return SRT_OK;
-}
-
-int srt_pt_add_sphere(srt_pt* pt, float radius, const float trans[16], uint32_t material) {
-  if (!pt || !trans) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_sphere: NULL argument");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (material >= pt->materials.size()) return srt::fail(SRT_ERR_INVALID, "material %u not defined", material);
-  ObjectInput o;
-  o.kind = OBJ_SPHERE;
-  std::memcpy(&o.trans, trans, sizeof(Mat4));
-  o.material = material;
-  o.radius = radius;
-  pt->inputs.push_back(std::move(o));
-  return SRT_OK;
-}
-
-int srt_pt_add_sphere_light(srt_pt* pt, float radius, const float trans[16], uint32_t material, const float* positions,
-                            const float* normals, uint32_t nverts, const uint32_t* indices, uint32_t nindices) {
-  if (!pt || !trans || !positions || !normals || !indices) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_sphere_light: NULL argument");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (material >= pt->materials.size()) return srt::fail(SRT_ERR_INVALID, "material %u not defined", material);
-  if (!nverts || !nindices || nindices % 3) return srt::fail(SRT_ERR_INVALID, "the light mesh needs triangles (%u vertices, %u indices)", nverts, nindices);
-  ObjectInput o;
-  o.kind = OBJ_SPHERE;
-  std::memcpy(&o.trans, trans, sizeof(Mat4));
-  o.material = material;
-  o.radius = radius;
-  o.is_light = true;
-  o.mesh.pos.assign(positions, positions + 3 * (size_t)nverts);
-  o.mesh.nrm.assign(normals, normals + 3 * (size_t)nverts);
-  o.mesh.idx.assign(indices, indices + nindices);
-  pt->inputs.push_back(std::move(o));
-  return SRT_OK;
-}
-
-int srt_pt_add_light(srt_pt* pt, uint32_t type, const float radiance[3], const float angle_bounds[2], const float trans[16]) {
-  if (!pt || !radiance || !trans) return srt::fail(SRT_ERR_INVALID, "srt_pt_add_light: NULL argument");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (type > SRT_LIGHT_SPOT) return srt::fail(SRT_ERR_INVALID, "unknown light type %u", type);
-  if (type == SRT_LIGHT_SPOT && !angle_bounds) return srt::fail(SRT_ERR_INVALID, "a spot light needs angle_bounds");
-  Mat4 T;
-  std::memcpy(&T, trans, sizeof(Mat4));
-  pt->delta_lights.push_back(make_delta_light(type, radiance, angle_bounds, T));
-  return SRT_OK;
-}
-
-int srt_pt_set_env_light(srt_pt* pt, uint32_t type, const float radiance[3]) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_env_light: NULL context");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (type > SRT_ENV_HEMISPHERE) return srt::fail(SRT_ERR_INVALID, "unknown environment light type %u (image maps: srt_pt_set_env_map)", type);
-  if (type != SRT_ENV_NONE && !radiance) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_env_light: radiance is NULL");
-  pt->env_type = type;
-  for (int i = 0; i < 3; i++) pt->env_radiance[i] = (type != SRT_ENV_NONE) ? radiance[i] : 0.0f;
-  return SRT_OK;
-}
-
-int srt_pt_set_env_map(srt_pt* pt, uint32_t width, uint32_t height, const float* rgb) {
-  if (!pt || !rgb) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_env_map: NULL argument");
-  if (pt->committed) return srt::fail(SRT_ERR_STATE, "scene already committed; call srt_pt_scene_begin first");
-  if (!width || !height || (uint64_t)width * height > (1ull << 28)) return srt::fail(SRT_ERR_INVALID, "environment map size %ux%u", width, height);
-  pt->env_type = SRT_ENV_MAP;
-  pt->env_w = width; pt->env_h = height;
-  pt->env_map.assign(rgb, rgb + 3 * (size_t)width * height);
-  return SRT_OK;
-}
-
-int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_scene_commit: NULL context");
-  discard_pending(pt);
-  if (pt->device >= 0) { SRT_HIP(hipSetDevice(pt->device)); drop_update_tables(pt, UINT32_MAX); }   // they describe trees and records that are about to go
-  pt->committed = false;    // build_scene replaces the host's record, the uploads below the device's: no scene until the last has gone through
-  // BVH<Triangle> builds of big meshes run on the device (pt_bvh_device.hip: identical arrays); srt_pt_set_bvh_builder
-  const DeviceBuilderScope builder(pt, device_builds(pt));
-  const std::string err = build_scene(pt->inputs, pt->materials, use_bvh != 0, &pt->built);
-  pt->blas_builds += pt->built.blas_builds;
-  if (!err.empty()) return srt::fail(SRT_ERR_UNSUPPORTED, "%s", err.c_str());
-  pt->built.flat.delta_lights = pt->delta_lights;
-  const FlatScene& F = pt->built.flat;
-  int st;
-  if ((st = check_depth(F.max_tlas_depth, F.max_blas_depth))) return st;
-  if (pt->device >= 0) {
-    SRT_HIP(hipSetDevice(pt->device));
-    SRT_HIP(hipStreamSynchronize(pt->stream));
-    if ((st = upload(pt, &pt->d_nodes, F.nodes)) || (st = upload(pt, &pt->d_tris, F.tris, true)) || (st = upload(pt, &pt->d_nrm, F.tri_nrm, true)) ||
-        (st = upload(pt, &pt->d_tri_packed, F.tri_packed, true)) ||
-        (st = upload(pt, &pt->d_objects, F.objects)) || (st = upload(pt, &pt->d_lights, F.lights)) ||
-        (st = upload(pt, &pt->d_ltris, F.light_tris)) || (st = upload(pt, &pt->d_mats, F.materials)) ||
-        (st = upload(pt, &pt->d_wave, F.wave_tlas)) || (st = upload(pt, &pt->d_blas, F.blas_recs, true)) || (st = upload(pt, &pt->d_wave_lazy, F.wave_lazy)) ||
-        (st = upload(pt, &pt->d_dlights, F.delta_lights)) || (st = upload(pt, &pt->d_env_map, pt->env_map)))
-      return st;
-    // the index buffers the kernels of pt_mesh_update.hip read (12 B per triangle)
-    std::vector<uint32_t> idx;
-    pt->idx_off.assign(pt->built.inputs.size(), SIZE_MAX);
-    for (size_t i = 0; i < pt->built.inputs.size(); i++) {
-      const ObjectInput& in = pt->built.inputs[i];
-      if (in.kind != OBJ_MESH || in.source >= 0 || (in.is_light && !pt->built.dynamic_lights)) continue;   // (a light's goes up later when the switch is set later: ensure_mesh_idx)
-      pt->idx_off[i] = idx.size();
-      idx.insert(idx.end(), in.mesh.idx.begin(), in.mesh.idx.end());
-    }
-    pt->idx_words = idx.size();
-    pt->idx_uncounted = 0;
-    if ((st = upload(pt, &pt->d_idx, idx))) return st;
-  }
-  pt->committed = true;
-  pt->scene_generation++;
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
-  return SRT_OK;
-}
-
-int srt_pt_set_stream_slots(srt_pt* pt, uint32_t slots) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_stream_slots: NULL context");
-  if (slots > kMaxStreamSlots) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_stream_slots: at most %u path slots (got %u)", kMaxStreamSlots, slots);
-  pt->stream_slots = slots;
-  return SRT_OK;
-}
-
-int srt_pt_set_bvh_builder(srt_pt* pt, int device, uint32_t min_primitives) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_bvh_builder: NULL context");
-  pt->bvh_builder = device ? 1 : 0;
-  pt->bvh_device_min = min_primitives;
-  return SRT_OK;
-}
-
-int srt_pt_set_camera(srt_pt* pt, const float iview[16], float vert_fov_deg, float aspect_ratio) {
-  if (!pt || !iview) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_camera: NULL argument");
-  pt->cam = make_camera(iview, vert_fov_deg, aspect_ratio);
-  pt->have_cam = true;
-  return SRT_OK;
-}
-
-int srt_pt_set_params(srt_pt* pt, uint32_t width, uint32_t height, uint32_t max_depth) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_params: NULL context");
-  if (!width || !height) return srt::fail(SRT_ERR_INVALID, "image must be at least 1x1 (got %ux%u)", width, height);
-  if ((uint64_t)width * height > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
-  if (width > 65535u || height > 65535u) return srt::fail(SRT_ERR_UNSUPPORTED, "image sides above 65535 are not supported (got %ux%u)", width, height);
-  if (max_depth > (uint32_t)kMaxPathDepth) return srt::fail(SRT_ERR_UNSUPPORTED, "max_depth %u > %d is not supported", max_depth, kMaxPathDepth);
-  pt->w = width; pt->h = height; pt->max_depth = max_depth;
-  update_tiling(pt);
-  return SRT_OK;
-}
-
-int srt_pt_set_tiling(srt_pt* pt, uint32_t tile_w, uint32_t tile_h, uint32_t rank, uint32_t world) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_tiling: NULL context");
-  if (!tile_w || !tile_h || tile_w % 8 || tile_h % 8) return srt::fail(SRT_ERR_INVALID, "tile size must be a positive multiple of 8 (got %ux%u)", tile_w, tile_h);
-  if (!world || rank >= world) return srt::fail(SRT_ERR_INVALID, "rank %u / world %u is not a valid shard", rank, world);
-  pt->tiles.tile_w = tile_w; pt->tiles.tile_h = tile_h; pt->tiles.rank = rank; pt->tiles.world = world;
-  update_tiling(pt);
-  return SRT_OK;
-}
-
-int srt_pt_tile_info(srt_pt* pt, uint32_t* local_tiles, uint32_t* tiles_per_rank, uint32_t* floats_per_tile) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_tile_info: NULL context");
-  if (!pt->w) return srt::fail(SRT_ERR_STATE, "srt_pt_tile_info before srt_pt_set_params");
-  if (local_tiles) *local_tiles = pt->tiles.local_tiles;
-  if (tiles_per_rank) *tiles_per_rank = pt->tiles_per_rank;
-  if (floats_per_tile) *floats_per_tile = pt->tiles.tile_w * pt->tiles.tile_h * 3;
-  return SRT_OK;
-}
-
-int srt_pt_set_kernel(srt_pt* pt, int mode) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_kernel: NULL context");
-  if (mode < 0 || mode > 7)
-    return srt::fail(SRT_ERR_INVALID, "kernel mode must be 0 (auto), 1 (per-lane, lane per pixel), 2 (wave-uniform), 3 (wave-uniform, stamped), 4 (per-lane, lane per sample), 5 (persistent waves, flattened per-lane walk), 6 (streamed: logic + ray-cast kernels) or 7 (streamed sweeps: BVH<Triangle> walks queued)");
-  pt->kernel_mode = mode;
-  return SRT_OK;
-}
-
-}  // extern "C"
 
 namespace {
 // srt_pt_render_epoch_device (d_tiles_out: the epoch's tile radiance) and srt_pt_render_samples_device (d_tiles_out == NULL: the
@@ -1417,29 +798,6 @@ int srt_pt_accumulator_tiles_device(srt_pt* pt, void* stream, const float* d_acc
   const uint32_t px = pt->tiles.local_tiles * pt->tiles.tile_w * pt->tiles.tile_h;
   if (!px) return SRT_OK;
   pt_acc_image_kernel<<<dim3((px + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(pt->tiles, d_accumulator, d_tiles_out);
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int srt_pt_untile_device(srt_pt* pt, void* stream, const float* d_gathered, float* d_image) {
-  int st = need_ready(pt, "srt_pt_untile_device");
-  if (st != SRT_OK) return st;
-  if (!d_gathered || !d_image) return srt::fail(SRT_ERR_INVALID, "srt_pt_untile_device: NULL buffer");
-  hipStream_t s = (hipStream_t)stream;  // exactly the caller's stream; NULL is the HIP default stream
-  const uint32_t n = pt->w * pt->h;
-  pt_untile_kernel<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(pt->tiles, pt->w, pt->h, pt->tiles_per_rank, d_gathered, d_image);
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int srt_pt_accumulate_device(srt_pt* pt, void* stream, float* d_accumulator, const float* d_epoch, size_t nfloats,
-                             uint32_t accumulator_samples) {
-  int st = need_device(pt, "srt_pt_accumulate_device");
-  if (st != SRT_OK) return st;
-  if (!d_accumulator || !d_epoch || !accumulator_samples) return srt::fail(SRT_ERR_INVALID, "srt_pt_accumulate_device: bad argument");
-  hipStream_t s = (hipStream_t)stream;  // exactly the caller's stream; NULL is the HIP default stream
-  pt_accumulate_kernel<<<dim3((unsigned)((nfloats + 255) / 256)), dim3(256), 0, s>>>(d_accumulator, d_epoch, nfloats,
-                                                                                 1.0f / accumulator_samples);
   SRT_HIP(hipGetLastError());
   return SRT_OK;
 }
@@ -1573,25 +931,6 @@ int srt_pt_ray_count(srt_pt* pt, uint64_t* rays, uint64_t* camera_samples, int r
   return SRT_OK;
 }
 
-int srt_pt_set_elision(srt_pt* pt, int on) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_elision: NULL context");
-  pt->elide = on ? 1 : 0;
-  pt->wave_blocks = 0;                                    // the launch configuration is re-derived for the other build
-  return SRT_OK;
-}
-
-int srt_pt_set_dynamic_lights(srt_pt* pt, int on) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_dynamic_lights: NULL context");
-  pt->built.dynamic_lights = on != 0;
-  return SRT_OK;
-}
-
-int srt_pt_set_normal_colors(srt_pt* pt, int on) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_normal_colors: NULL context");
-  pt->normal_colors = on ? 1 : 0;
-  return SRT_OK;
-}
-
 int srt_pt_rays_elided(srt_pt* pt, uint64_t* elided, int reset) {
   int st = need_device(pt, "srt_pt_rays_elided");
   if (st != SRT_OK) return st;
@@ -1602,244 +941,6 @@ int srt_pt_rays_elided(srt_pt* pt, uint64_t* elided, int reset) {
   if (reset) { SRT_HIP(hipMemset(pt->d_totals + C_COUNT + 1, 0, sizeof r)); SRT_HIP(hipDeviceSynchronize()); }
   return SRT_OK;
 }
-
-int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const uint32_t* ys, const uint32_t* ss, size_t n,
-                         float* rgb_out, uint32_t* draws_out, uint32_t* rays_out) {
-  int st = need_ready(pt, "srt_pt_trace_samples");
-  if (st != SRT_OK) return st;
-  if ((st = settle(pt)) != SRT_OK) return st;
-  if (n == 0) return SRT_OK;
-  if (!xs || !ys || !ss || !rgb_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_trace_samples: NULL argument");
-  if (n > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "too many samples in one call");
-  for (size_t i = 0; i < n; i++)
-    if (xs[i] >= pt->w || ys[i] >= pt->h) return srt::fail(SRT_ERR_INVALID, "sample %zu: pixel (%u,%u) outside %ux%u", i, xs[i], ys[i], pt->w, pt->h);
-  DeviceBuffer<uint32_t> dx, dy, ds, dd, dr;
-  DeviceBuffer<float> drgb;
-  if ((st = dx.ensure(n)) || (st = dy.ensure(n)) || (st = ds.ensure(n)) || (st = dd.ensure(n)) || (st = dr.ensure(n)) || (st = drgb.ensure(3 * n))) return st;
-  SRT_HIP(hipMemcpyAsync(dx, xs, n * 4, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemcpyAsync(dy, ys, n * 4, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemcpyAsync(ds, ss, n * 4, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemsetAsync(pt->d_totals, 0, C_COUNT * sizeof(unsigned long long), pt->stream));
-  const auto kern = pt->normal_colors ? pt_samples_kernel<true, true> : pt_samples_kernel<true, false>;
-  kern<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pt->stream>>>(device_scene(pt), seed, dx, dy, ds, (uint32_t)n, drgb, dd, dr, pt->d_totals);
-  SRT_HIP(hipGetLastError());
-  SRT_HIP(hipMemcpyAsync(rgb_out, drgb, n * 12, hipMemcpyDeviceToHost, pt->stream));
-  if (draws_out) SRT_HIP(hipMemcpyAsync(draws_out, dd, n * 4, hipMemcpyDeviceToHost, pt->stream));
-  if (rays_out) SRT_HIP(hipMemcpyAsync(rays_out, dr, n * 4, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipMemcpyAsync(pt->last_counters, pt->d_totals, sizeof pt->last_counters, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipStreamSynchronize(pt->stream));
-  return SRT_OK;
-}
-
-int srt_pt_hit(srt_pt* pt, const float* origins, const float* dirs, const float* bounds, size_t n, float* out9) {
-  int st = need_device(pt, "srt_pt_hit");
-  if (st != SRT_OK) return st;
-  if ((st = need_committed(pt, "srt_pt_hit")) != SRT_OK) return st;
-  if (n == 0) return SRT_OK;
-  if (!origins || !dirs || !bounds || !out9) return srt::fail(SRT_ERR_INVALID, "srt_pt_hit: NULL argument");
-  DeviceBuffer<float> dorg, ddir, db, dout;
-  if ((st = dorg.ensure(3 * n)) || (st = ddir.ensure(3 * n)) || (st = db.ensure(2 * n)) || (st = dout.ensure(9 * n))) return st;
-  SRT_HIP(hipMemcpyAsync(dorg, origins, n * 12, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemcpyAsync(ddir, dirs, n * 12, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemcpyAsync(db, bounds, n * 8, hipMemcpyHostToDevice, pt->stream));
-  DScene S = device_scene(pt);
-  if (pt->kernel_mode == 5) {
-    if (!flat_walk_fits(pt->built.flat)) return srt::fail(SRT_ERR_UNSUPPORTED, "the flattened walk needs 1..31 objects");
-    pt_hit_kernel<true><<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pt->stream>>>(S, dorg, ddir, db, (uint32_t)n, dout);
-  } else {
-    pt_hit_kernel<false><<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pt->stream>>>(S, dorg, ddir, db, (uint32_t)n, dout);
-  }
-  SRT_HIP(hipGetLastError());
-  SRT_HIP(hipMemcpyAsync(out9, dout, n * 36, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipStreamSynchronize(pt->stream));
-  return SRT_OK;
-}
-
-int srt_pt_particles_step_device(srt_pt* pt, void* stream, float* d_pos, float* d_vel, float* d_age, size_t n, float dt, float radius,
-                                 uint8_t* d_alive) {
-  int st = need_device(pt, "srt_pt_particles_step_device");
-  if (st != SRT_OK) return st;
-  if (!pt->committed) return not_committed("srt_pt_particles_step");
-  if (n == 0) return SRT_OK;
-  if (!d_pos || !d_vel || !d_age || !d_alive) return srt::fail(SRT_ERR_INVALID, "srt_pt_particles_step: NULL argument");
-  if (n > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "too many particles in one call");
-  pt_particles_kernel<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream>>>(device_scene(pt), d_pos, d_vel, d_age, (uint32_t)n, dt,
-                                                                                           radius, d_alive);
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int srt_pt_particles_step(srt_pt* pt, float* pos, float* vel, float* age, size_t n, float dt, float radius, uint8_t* alive) {
-  int st = need_device(pt, "srt_pt_particles_step");
-  if (st != SRT_OK) return st;
-  if ((st = settle(pt)) != SRT_OK) return st;
-  if (n == 0) return SRT_OK;
-  if (!pos || !vel || !age || !alive) return srt::fail(SRT_ERR_INVALID, "srt_pt_particles_step: NULL argument");
-  DeviceBuffer<float> dp, dv, da;
-  DeviceBuffer<uint8_t> dl;
-  if ((st = dp.ensure(3 * n)) || (st = dv.ensure(3 * n)) || (st = da.ensure(n)) || (st = dl.ensure(n))) return st;
-  SRT_HIP(hipMemcpyAsync(dp, pos, n * 12, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemcpyAsync(dv, vel, n * 12, hipMemcpyHostToDevice, pt->stream));
-  SRT_HIP(hipMemcpyAsync(da, age, n * 4, hipMemcpyHostToDevice, pt->stream));
-  st = srt_pt_particles_step_device(pt, (void*)pt->stream, dp, dv, da, n, dt, radius, dl);
-  if (st != SRT_OK) return st;
-  SRT_HIP(hipMemcpyAsync(pos, dp, n * 12, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipMemcpyAsync(vel, dv, n * 12, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipMemcpyAsync(age, da, n * 4, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipMemcpyAsync(alive, dl, n, hipMemcpyDeviceToHost, pt->stream));
-  SRT_HIP(hipStreamSynchronize(pt->stream));
-  return SRT_OK;
-}
-
-long srt_pt_dump_bvh(srt_pt* pt, int which, float* boxes, uint32_t* links, size_t cap, uint32_t* order) {
-  if (!pt || !boxes || !links) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_bvh: NULL argument");
-  { const int ready = need_committed(pt, "srt_pt_dump_bvh"); if (ready != SRT_OK) return ready; }
-  if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_STATE, "scene was committed without BVHs");
-  const HostBVH* b = &pt->built.tlas;
-  const ObjectInput* in = nullptr;
-  if (which >= 0) {
-    if ((size_t)which >= pt->built.tlas.prim.size()) return srt::fail(SRT_ERR_INVALID, "object slot %d out of range", which);
-    uint32_t obj = pt->built.tlas.prim[which];
-    in = &pt->built.inputs[obj];
-    if (in->kind != OBJ_MESH) return srt::fail(SRT_ERR_INVALID, "object slot %d is not a mesh", which);
-    if (in->source >= 0) { obj = (uint32_t)in->source; in = &pt->built.inputs[obj]; }   // an instance: the shared arrays
-    b = &pt->built.blas[obj];
-  }
-  for (size_t i = 0; i < b->nodes.size() && i < cap; i++) {
-    const HostNode& nd = b->nodes[i];
-    for (int a = 0; a < 3; a++) { boxes[6 * i + a] = nd.mn[a]; boxes[6 * i + 3 + a] = nd.mx[a]; }
-    links[4 * i] = nd.start; links[4 * i + 1] = nd.size; links[4 * i + 2] = nd.l; links[4 * i + 3] = nd.r;
-  }
-  if (order)
-    for (size_t i = 0; i < b->prim.size(); i++) order[i] = in ? in->mesh.idx[3 * b->prim[i]] : b->prim[i] + 1;
-  return (long)b->nodes.size();
-}
-
-long srt_pt_dump_lights(srt_pt* pt, int from_device, uint32_t* heads, float* mats, size_t cap_lights, float* tris, size_t cap_tris) {
-  if (!pt || (cap_lights && (!heads || !mats)) || (cap_tris && !tris)) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_lights: NULL argument");
-  { const int ready = need_committed(pt, "srt_pt_dump_lights"); if (ready != SRT_OK) return ready; }
-  if (from_device && pt->device < 0)
-    return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_dump_lights: this context is host-only, there are no device arrays to read (from_device = 0 reads the host's)");
-  const FlatScene& F = pt->built.flat;
-  const size_t nl = F.lights.size(), nt = F.light_tris.size();
-  std::vector<Light> lights(F.lights);
-  std::vector<LightTri> ltris(F.light_tris);
-  std::vector<Tri> tr(F.tris.begin() + F.light_tri_first, F.tris.end());
-  std::vector<TriNrm> tn(F.tri_nrm.begin() + F.light_tri_first, F.tri_nrm.end());
-  if (tr.size() != nt || tn.size() != nt) return srt::fail(SRT_ERR_STATE, "srt_pt_dump_lights: the light tables disagree about their triangle count");
-  if (from_device) {
-    SRT_HIP(hipSetDevice(pt->device));
-    SRT_HIP(hipDeviceSynchronize());
-    if (nl) SRT_HIP(hipMemcpy(lights.data(), pt->d_lights, nl * sizeof(Light), hipMemcpyDeviceToHost));
-    if (nt) {
-      SRT_HIP(hipMemcpy(ltris.data(), pt->d_ltris, nt * sizeof(LightTri), hipMemcpyDeviceToHost));
-      SRT_HIP(hipMemcpy(tr.data(), pt->d_tris + F.light_tri_first, nt * sizeof(Tri), hipMemcpyDeviceToHost));
-      SRT_HIP(hipMemcpy(tn.data(), pt->d_nrm + F.light_tri_first, nt * sizeof(TriNrm), hipMemcpyDeviceToHost));
-    }
-  }
-  size_t li = 0;
-  for (size_t i = 0; i < pt->built.inputs.size() && li < nl; i++) {
-    if (light_of(pt->built, (uint32_t)i) < 0) continue;
-    if (li < cap_lights) {
-      const Light& L = lights[li];
-      heads[4 * li] = L.has_trans; heads[4 * li + 1] = L.tri_base - F.light_tri_first; heads[4 * li + 2] = L.ntri; heads[4 * li + 3] = (uint32_t)i;
-      std::memcpy(mats + 64 * li, &L.trans, 64 * sizeof(float));   // trans, itrans, pdfT, pdfiT
-    }
-    li++;
-  }
-  for (size_t t = 0; t < nt && t < cap_tris; t++) {
-    float* o = tris + 31 * t;
-    std::memcpy(o, &ltris[t], 13 * sizeof(float));                 // v0 v1 v2 (four floats each, padding included), area_term
-    for (int a = 0; a < 3; a++) {
-      o[13 + a] = tr[t].p0[a]; o[16 + a] = tr[t].e1[a]; o[19 + a] = tr[t].e2[a];
-      o[22 + a] = tn[t].n0[a]; o[25 + a] = tn[t].n1[a]; o[28 + a] = tn[t].n2[a];
-    }
-  }
-  return (long)nl;
-}
-
-int srt_pt_counters(srt_pt* pt, uint64_t out[8]) {
-  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_counters: NULL argument");
-  for (int k = 0; k < C_COUNT; k++) out[k] = pt->last_counters[k];
-  return SRT_OK;
-}
-
-int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out) {
-  return math_round_trip(pt, "srt_pt_math_cos_sin", {x}, n, {cos_out, sin_out}, n, [&](float* const* d, float* const* o) {
-    pt_math_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0], o[1]); });
-}
-
-int srt_pt_math_acos(srt_pt* pt, const float* x, size_t n, float* out) {
-  return math_round_trip(pt, "srt_pt_math_acos", {x}, n, {out}, n, [&](float* const* d, float* const* o) {
-    pt_acos_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0]); });
-}
-
-int srt_pt_math_atan2(srt_pt* pt, const float* y, const float* x, size_t n, float* out) {
-  return math_round_trip(pt, "srt_pt_math_atan2", {y, x}, n, {out}, n, [&](float* const* d, float* const* o) {
-    pt_atan2_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], d[1], n, o[0]); });
-}
-
-int srt_pt_tonemap_device(srt_pt* pt, void* stream, const float* d_rgb, uint32_t width, uint32_t height, float exposure, uint8_t* d_rgba) {
-  int st = need_device(pt, "srt_pt_tonemap_device");
-  if (st != SRT_OK) return st;
-  if (!d_rgb || !d_rgba) return srt::fail(SRT_ERR_INVALID, "srt_pt_tonemap_device: NULL argument");
-  if (!(exposure > 0.0f)) return srt::fail(SRT_ERR_INVALID, "srt_pt_tonemap_device: exposure must be positive (got %g)", (double)exposure);
-  if ((reinterpret_cast<uintptr_t>(d_rgba) & 3u) != 0) return srt::fail(SRT_ERR_INVALID, "srt_pt_tonemap_device: rgba must be 4-byte aligned");
-  const size_t px = (size_t)width * height;
-  if (!px) return SRT_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);      // exactly the caller's stream; NULL is the HIP default stream, as for every *_device call
-  pt_tonemap_kernel<<<dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s>>>(d_rgb, width, height, exposure, reinterpret_cast<uint32_t*>(d_rgba));
-  SRT_HIP(hipGetLastError());
-  return SRT_OK;
-}
-
-int srt_pt_tonemap(srt_pt* pt, const float* rgb, uint32_t width, uint32_t height, float exposure, uint8_t* rgba_out) {
-  int st = need_device(pt, "srt_pt_tonemap");
-  if (st != SRT_OK) return st;
-  if (!rgb || !rgba_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_tonemap: NULL argument");
-  if (!(exposure > 0.0f)) return srt::fail(SRT_ERR_INVALID, "srt_pt_tonemap: exposure must be positive (got %g)", (double)exposure);
-  const size_t px = (size_t)width * height;
-  if (!px) return SRT_OK;
-  DeviceBuffer<float> d_in; DeviceBuffer<uint8_t> d_out;
-  if ((st = d_in.ensure(3 * px)) || (st = d_out.ensure(4 * px))) return st;
-  if (hipMemcpyAsync(d_in, rgb, px * 12, hipMemcpyHostToDevice, pt->stream) != hipSuccess) st = srt::fail(SRT_ERR_HIP, "srt_pt_tonemap: upload failed");
-  if (st == SRT_OK) st = srt_pt_tonemap_device(pt, (void*)pt->stream, d_in, width, height, exposure, d_out);
-  if (st == SRT_OK && (hipMemcpyAsync(rgba_out, d_out, px * 4, hipMemcpyDeviceToHost, pt->stream) != hipSuccess ||
-                       hipStreamSynchronize(pt->stream) != hipSuccess))
-    st = srt::fail(SRT_ERR_HIP, "srt_pt_tonemap: download failed");
-  return st;
-}
-
-int srt_pt_math_exp(srt_pt* pt, const float* x, size_t n, float* out) {
-  return math_round_trip(pt, "srt_pt_math_exp", {x}, n, {out}, n, [&](float* const* d, float* const* o) {
-    pt_exp_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0]); });
-}
-
-int srt_pt_math_pow(srt_pt* pt, const float* x, const float* y, size_t n, float* out) {
-  return math_round_trip(pt, "srt_pt_math_pow", {x, y}, n, {out}, n, [&](float* const* d, float* const* o) {
-    pt_pow_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], d[1], n, o[0]); });
-}
-
-int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c2, float* out) {
-  return math_round_trip(pt, "srt_pt_math_div_sqrt", {in}, 5 * 3 * lanes, {out}, 4 * 3 * lanes, [&](float* const* d, float* const* o) {
-    pt_div_sqrt_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, shared_c2, o[0]); });
-}
-
-int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out) {
-  return math_round_trip(pt, "srt_pt_math_tri_verdict", {in}, 27 * lanes, {out}, 19 * lanes, [&](float* const* d, float* const* o) {
-    pt_tri_verdict_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
-}
-
-int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* out) {
-  return math_round_trip(pt, "srt_pt_math_sphere_batch", {in}, 19 * lanes, {out}, 22 * lanes, [&](float* const* d, float* const* o) {
-    pt_sphere_batch_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
-}
-
-int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out) {
-  return math_round_trip(pt, "srt_pt_math_box_sweep", {in}, 14 * lanes, {out}, 6 * lanes, [&](float* const* d, float* const* o) {
-    pt_box_sweep_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
-}
-
 
 // ---- Pathtracer::cancel ---------------------------------------------------------------------------------------------
 int srt_pt_cancel(srt_pt* pt) {
@@ -1865,13 +966,6 @@ int srt_pt_clear_cancel(srt_pt* pt) {
 }
 
 // ---- Pathtracer::log_ray --------------------------------------------------------------------------------------------
-int srt_pt_set_ray_log(srt_pt* pt, uint32_t capacity) {
-  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_ray_log: NULL context");
-  if (capacity > (1u << 26)) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_ray_log: at most 2^26 rays per read (got %u)", capacity);
-  pt->ray_log_cap = capacity;                            // the rings follow at the next epoch on each stream (stream_buffers)
-  return SRT_OK;
-}
-
 namespace {
 // `rays` == nullptr: only count what is waiting in the ring (nothing is consumed).
 int read_ring(srt_pt::EpochBuffers& B, hipStream_t s, std::vector<srt_pt_logged_ray>* rays, size_t* waiting, uint64_t* dropped) {

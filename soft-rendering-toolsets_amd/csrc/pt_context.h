@@ -1,6 +1,12 @@
-// The path tracer's context (struct srt_pt) and the helpers its two translation units share: pt.hip (kernels, render paths, create /
-// begin / add / commit / destroy) and pt_update.cpp (host code only: what changes or queries a committed scene).  No header that
-// defines a non-template __global__ may be included here (pt_stream.h and pt_wave.h do): both units would define its kernels.
+// The path tracer's context (struct srt_pt) and the helpers the translation units behind include/srt_pt.h share:
+//   pt.hip          the render kernels, the choice of kernel form, the render paths and what reads back what a render leaves
+//   pt_context.cpp  host code only: create / destroy, scene begin / add / commit, camera, image size, tiling and the switches
+//   pt_update.cpp   host code only: what changes or queries a committed scene
+//   pt_query.hip    per-lane kernels on the committed scene outside a render (samples, hits, particles) and the dumps
+//   pt_image.hip    untile, accumulate, tonemap
+//   pt_probe.hip    the test-only math probes of srt_pt_debug.h
+// Only pt.hip may include pt_wave.h / pt_stream.h: they define non-template __global__ functions, which a second includer would
+// define again.  So neither may be included here, nor any other header that defines a kernel.
 #ifndef SRT_PT_CONTEXT_H
 #define SRT_PT_CONTEXT_H
 
@@ -19,6 +25,8 @@
 
 namespace srt {
 struct StreamCounters;   // pt_stream.h
+struct DScene;           // pt_trace.h
+constexpr uint32_t kMaxStreamSlots = 1u << 26;   // srt_pt_set_stream_slots: upper bound of the path-slot population (state planes: ~13 GB there)
 }
 
 struct srt_pt {
@@ -155,7 +163,16 @@ inline int upload(srt_pt* pt, DeviceBuffer<T>* dst, const std::vector<T>& src, b
   return SRT_OK;
 }
 
-int need_device(srt_pt* pt, const char* what);            // (pt.hip; everything below: pt_update.cpp)
+int need_device(srt_pt* pt, const char* what);            // (pt_context.cpp)
+// need_device, and the scene is committed, has a camera and an image size (pt_context.cpp)
+int need_ready(srt_pt* pt, const char* what);
+// The kernels' view of the committed scene; B: the scratch set whose ray-log ring they write, if any (pt.hip)
+DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B = nullptr);
+// The scene fits the flattened per-lane walk of pt_flat.h (pt.hip)
+bool flat_walk_fits(const FlatScene& F);
+// SRT_CAST_STATS=1: the ray-cast kernel's sums on stderr, for srt_pt_destroy (pt.hip)
+void report_cast_stats(srt_pt* pt);
+// (everything below: pt_update.cpp)
 // settle(): the host's record catches up with the device after srt_pt_repose_refit_device calls - every entry point that is not itself
 // enqueue-only calls it first (need_committed: and refuses, with not_committed's text, a scene that is not committed); discard_pending():
 // what is pending describes a scene that goes.

@@ -1,0 +1,275 @@
+// The test-only math probes of include/srt_pt_debug.h: each runs one piece of the device arithmetic (pt_device.h, pt_trace.h) on
+// caller-supplied operands, so that a test can compare it with the host's libm or with the plain per-ray form.  No scene, no render.
+#include <hip/hip_runtime.h>
+
+#include "pt_anim.h"
+#include "pt_context.h"
+#include "pt_device.h"
+#include "srt_pt_debug.h"
+
+#include "pt_trace.h"
+
+namespace srt {
+
+__global__ void pt_math_kernel(const float* __restrict__ x, size_t n, float* __restrict__ c, float* __restrict__ s) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { c[i] = srt_cosf(x[i]); s[i] = srt_sinf(x[i]); }
+}
+
+__global__ void pt_acos_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = srt_acosf(x[i]);
+}
+
+__global__ void pt_atan2_kernel(const float* __restrict__ y, const float* __restrict__ x, size_t n, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = srt_atan2f(y[i], x[i]);
+}
+
+__global__ void pt_exp_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = srt_expf(x[i]);
+}
+__global__ void pt_pow_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = srt_powf(x[i], y[i]);
+}
+
+// Diagnostic for divNx3 / sqrtN (pt_device.h): lane i takes the operands of "rays" 3i, 3i+1, 3i+2 — exactly how the
+// wave kernel's batch tests call them.  io layout: planes of n3 = 3 * lanes floats: num0, num1, num2, den, x in; q0, q1, q2,
+// root out.  shared_c2: column 2's numerator of a lane is num2[3i] for its three rays (the triangle test's shared t numerator).
+__global__ void pt_div_sqrt_kernel(const float* __restrict__ in, size_t lanes, int shared_c2, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n3 = lanes * 3;
+  const size_t k = (i < lanes ? i : lanes - 1) * 3;     // every lane of the last wave computes; the spares repeat the last lane
+  float num[3][3], den[3], q[3][3], x[3], root[3];
+  bool zero[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    num[r][0] = in[k + r]; num[r][1] = in[n3 + k + r];
+    num[r][2] = in[2 * n3 + (shared_c2 ? k : k + r)];
+    den[r] = in[3 * n3 + k + r];
+    x[r] = in[4 * n3 + k + r];
+    zero[r] = __float_as_uint(x[r]) == 0u;
+  }
+  if (shared_c2) divNx3<3, true>(num, den, q); else divNx3<3, false>(num, den, q);
+  sqrtN<3>(x, zero, root);
+  if (i < lanes) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      out[k + r] = q[r][0]; out[n3 + k + r] = q[r][1]; out[2 * n3 + k + r] = q[r][2];
+      out[3 * n3 + k + r] = root[r];
+    }
+  }
+}
+
+// Triangle::hit of the wave kernel's fold (tri_hitN<3>: verdict from the numerators, only t divided) next to the plain per-ray
+// form (tri_hit), lane i on its own triangle, origin and three rays.  in: 27 planes of `lanes` floats (p0, e1, e2, origin, three
+// directions, then b0 and b1 of the three rays); out: 19 planes - {hit, t, dist} x 3 rays of the batch form, the same of
+// tri_hit, and "this lane's wave computed u and v after all" (an ambiguous lane in it).
+__global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t k = i < lanes ? i : lanes - 1;           // every lane of the last wave computes; the spares repeat the last lane
+  float v[27];
+#pragma unroll
+  for (int j = 0; j < 27; j++) v[j] = in[(size_t)j * lanes + k];
+  Tri g;
+#pragma unroll
+  for (int j = 0; j < 3; j++) { g.p0[j] = v[j]; g.e1[j] = v[3 + j]; g.e2[j] = v[6 + j]; }
+  const V3 org = v3(v[9], v[10], v[11]);
+  V3 d[3];
+  float b0[3], b1[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) { d[r] = v3(v[12 + 3 * r], v[13 + 3 * r], v[14 + 3 * r]); b0[r] = v[21 + r]; b1[r] = v[24 + r]; }
+  TriHitT hb[3];
+  bool fallback = false;
+  tri_hitN<3>(g, org, d, b0, b1, hb, &fallback);
+  if (i < lanes) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
+      const TriHit hp = tri_hit(g, ray);
+      out[(size_t)(3 * r) * lanes + i] = hb[r].hit ? 1.0f : 0.0f;
+      out[(size_t)(3 * r + 1) * lanes + i] = hb[r].t;
+      out[(size_t)(3 * r + 2) * lanes + i] = hb[r].dist;
+      out[(size_t)(9 + 3 * r) * lanes + i] = hp.hit ? 1.0f : 0.0f;
+      out[(size_t)(10 + 3 * r) * lanes + i] = hp.t;
+      out[(size_t)(11 + 3 * r) * lanes + i] = hp.dist;
+    }
+    out[(size_t)18 * lanes + i] = fallback ? 1.0f : 0.0f;
+  }
+}
+
+// Sphere::hit of the wave kernel's batch (sphere_hitN<3> and the distance step through sqrtN, as object_testN's sphere branch in
+// pt_wave.h performs them - restated below, since moving the branch into a function of its own changed a wave kernel's scratch)
+// next to the plain per-ray form (sphere_hit, then the distance as object_hit has it, pt_trace.h), lane i on its own radius,
+// origin and three rays.  in: 19 planes of `lanes` floats (radius, origin, three directions, then b0 and b1 of the three
+// rays); out: 22 planes - {hit, t, dist} x 3 rays of the batch form, the same of the plain form, delta of the three rays
+// (sphere_two_roots), and "this lane's wave computed the tangent root" (a lane with delta == 0 in it).
+__global__ void pt_sphere_batch_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t k = i < lanes ? i : lanes - 1;           // every lane of the last wave computes; the spares repeat the last lane
+  float v[19];
+#pragma unroll
+  for (int j = 0; j < 19; j++) v[j] = in[(size_t)j * lanes + k];
+  const float radius = v[0];
+  const V3 org = v3(v[1], v[2], v[3]);
+  V3 d[3], pos[3];
+  float b0[3], b1[3], tb[3], db[3];
+  bool hb[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) { d[r] = v3(v[4 + 3 * r], v[5 + 3 * r], v[6 + 3 * r]); b0[r] = v[13 + r]; b1[r] = v[16 + r]; }
+  bool tangent = false;
+  {                                                     // the sphere branch of object_testN (pt_wave.h), line for line: change both
+    constexpr int NR = 3;
+    SphHit sh[NR];
+    sphere_hitN<NR>(radius, org, d, b0, b1, sh, &tangent);
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      hb[r] = sh[r].hit; tb[r] = sh[r].t;
+      pos[r] = org + d[r] * sh[r].t;                    // Ray::at
+    }
+    float n2[NR], nr[NR];
+    bool miss[NR];                                      // no hit: t = 0, pos == origin
+#pragma unroll
+    for (int r = 0; r < NR; r++) { n2[r] = norm2(pos[r] - org); miss[r] = !hb[r]; }
+    sqrtN<NR>(n2, miss, nr);
+#pragma unroll
+    for (int r = 0; r < NR; r++) db[r] = fabsf(nr[r]);
+  }
+  if (i < lanes) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
+      const SphHit hp = sphere_hit(radius, ray);
+      bool hit_two;
+      float t_two;
+      const float delta = sphere_two_roots(radius, ray, hit_two, t_two);
+      out[(size_t)(3 * r) * lanes + i] = hb[r] ? 1.0f : 0.0f;
+      out[(size_t)(3 * r + 1) * lanes + i] = tb[r];
+      out[(size_t)(3 * r + 2) * lanes + i] = db[r];
+      out[(size_t)(9 + 3 * r) * lanes + i] = hp.hit ? 1.0f : 0.0f;
+      out[(size_t)(10 + 3 * r) * lanes + i] = hp.t;
+      out[(size_t)(11 + 3 * r) * lanes + i] = fabsf(norm(ray_at(ray, hp.t) - ray.o));
+      out[(size_t)(18 + r) * lanes + i] = delta;
+    }
+    out[(size_t)21 * lanes + i] = tangent ? 1.0f : 0.0f;
+  }
+}
+
+// BBox::hit of the sweeps (box_hit_inv: both products per axis, the select on the results) next to the form of the per-lane
+// traversals (box_hit_rec: the bound selected first; both in pt_trace.h), lane i on its own box, origin, reciprocal direction
+// and incoming `times`.  in: 14 planes of `lanes` floats (box min xyz, box max xyz, origin xyz, 1 / direction xyz, times x, y);
+// out: 6 planes - {hit as 0 / 1, times.x, times.y} of box_hit_inv, then the same of box_hit_rec.
+__global__ void pt_box_sweep_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= lanes) return;
+  float v[14];
+#pragma unroll
+  for (int j = 0; j < 14; j++) v[j] = in[(size_t)j * lanes + i];
+  const float bx[6] = {v[0], v[1], v[2], v[3], v[4], v[5]};
+  const V3 org = v3(v[6], v[7], v[8]), inv = v3(v[9], v[10], v[11]);
+  float ax = v[12], ay = v[13], bxx = v[12], bxy = v[13];
+  const bool ha = box_hit_inv(bx, org, inv, ax, ay);
+  const bool hb = box_hit_rec(bx, org, inv, bxx, bxy);
+  out[i] = ha ? 1.0f : 0.0f; out[lanes + i] = ax; out[2 * lanes + i] = ay;
+  out[3 * lanes + i] = hb ? 1.0f : 0.0f; out[4 * lanes + i] = bxx; out[5 * lanes + i] = bxy;
+}
+
+}  // namespace srt
+
+using namespace srt;
+
+namespace {
+
+// The round trip every probe but srt_pt_math_hypot makes: `what`'s argument checks, upload the input planes of in_floats floats
+// each, launch(device inputs, device outputs), download the output planes of out_floats floats each, synchronise.
+template <size_t K, size_t M, class Launch>
+int math_round_trip(srt_pt* pt, const char* what, const float* const (&in)[K], size_t in_floats, float* const (&out)[M], size_t out_floats, Launch&& launch) {
+  int st = need_device(pt, what);
+  if (st != SRT_OK) return st;
+  for (const float* p : in) if (!p) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  for (const float* p : out) if (!p) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (!in_floats) return SRT_OK;
+  DeviceBuffer<float> din_own[K], dout_own[M];            // (this call's own: freed on every return)
+  float *din[K], *dout[M];
+  for (size_t k = 0; k < K; k++) { if ((st = din_own[k].ensure(in_floats))) return st; din[k] = din_own[k]; }
+  for (size_t m = 0; m < M; m++) { if ((st = dout_own[m].ensure(out_floats))) return st; dout[m] = dout_own[m]; }
+  for (size_t k = 0; k < K; k++) SRT_HIP(hipMemcpyAsync(din[k], in[k], in_floats * 4, hipMemcpyHostToDevice, pt->stream));
+  launch(din, dout);
+  SRT_HIP(hipGetLastError());
+  for (size_t m = 0; m < M; m++) SRT_HIP(hipMemcpyAsync(out[m], dout[m], out_floats * 4, hipMemcpyDeviceToHost, pt->stream));
+  SRT_HIP(hipStreamSynchronize(pt->stream));
+  return SRT_OK;
+}
+dim3 math_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+}  // namespace
+
+extern "C" {
+
+int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out) {
+  return math_round_trip(pt, "srt_pt_math_cos_sin", {x}, n, {cos_out, sin_out}, n, [&](float* const* d, float* const* o) {
+    pt_math_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0], o[1]); });
+}
+
+int srt_pt_math_acos(srt_pt* pt, const float* x, size_t n, float* out) {
+  return math_round_trip(pt, "srt_pt_math_acos", {x}, n, {out}, n, [&](float* const* d, float* const* o) {
+    pt_acos_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0]); });
+}
+
+int srt_pt_math_atan2(srt_pt* pt, const float* y, const float* x, size_t n, float* out) {
+  return math_round_trip(pt, "srt_pt_math_atan2", {y, x}, n, {out}, n, [&](float* const* d, float* const* o) {
+    pt_atan2_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], d[1], n, o[0]); });
+}
+
+// (srt_hypotf lives with the animation kernels: pt_anim.hip.  n == 0 returns before the NULL check, unlike the round trips above.)
+int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, float* out) {
+  int st = need_device(pt, "srt_pt_math_hypot");
+  if (st != SRT_OK) return st;
+  if (n == 0) return SRT_OK;
+  if (!x || !y || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_hypot: NULL argument");
+  DeviceBuffer<float> d;
+  if ((st = d.ensure(3 * n))) return st;
+  hipError_t e = hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + n, y, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_anim_hypot(pt->stream, d, d + n, n, d + 2 * n);
+    e = hipMemcpyAsync(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost, pt->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(pt->stream);
+  SRT_HIP(e);
+  return SRT_OK;
+}
+
+int srt_pt_math_exp(srt_pt* pt, const float* x, size_t n, float* out) {
+  return math_round_trip(pt, "srt_pt_math_exp", {x}, n, {out}, n, [&](float* const* d, float* const* o) {
+    pt_exp_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0]); });
+}
+
+int srt_pt_math_pow(srt_pt* pt, const float* x, const float* y, size_t n, float* out) {
+  return math_round_trip(pt, "srt_pt_math_pow", {x, y}, n, {out}, n, [&](float* const* d, float* const* o) {
+    pt_pow_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], d[1], n, o[0]); });
+}
+
+int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c2, float* out) {
+  return math_round_trip(pt, "srt_pt_math_div_sqrt", {in}, 5 * 3 * lanes, {out}, 4 * 3 * lanes, [&](float* const* d, float* const* o) {
+    pt_div_sqrt_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, shared_c2, o[0]); });
+}
+
+int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  return math_round_trip(pt, "srt_pt_math_tri_verdict", {in}, 27 * lanes, {out}, 19 * lanes, [&](float* const* d, float* const* o) {
+    pt_tri_verdict_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  return math_round_trip(pt, "srt_pt_math_sphere_batch", {in}, 19 * lanes, {out}, 22 * lanes, [&](float* const* d, float* const* o) {
+    pt_sphere_batch_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  return math_round_trip(pt, "srt_pt_math_box_sweep", {in}, 14 * lanes, {out}, 6 * lanes, [&](float* const* d, float* const* o) {
+    pt_box_sweep_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+}  // extern "C"

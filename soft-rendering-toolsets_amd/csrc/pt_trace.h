@@ -222,6 +222,40 @@ SRT_DEV bool box_hit_rec(const float* __restrict__ bx, V3 o, V3 inv, float& tx, 
   return hit;
 }
 
+// BBox::hit with the reciprocal direction hoisted (the reference recomputes the same 1/dir per box), in
+// straight-line form: the two early-outs become one verdict, `times` is narrowed only on a hit.
+SRT_DEV bool box_hit_inv(const float* __restrict__ bx, V3 o, V3 inv, float& tx, float& ty) {
+  const bool sx = inv.x < 0, sy = inv.y < 0, sz = inv.z < 0;
+  // the six bounds are read into values first: `c ? bx[3] : bx[0]` on the memory operands is an lvalue select,
+  // i.e. one per-lane vector load from a selected address instead of two wave-uniform scalar loads
+  const float b0 = bx[0], b1 = bx[1], b2 = bx[2], b3 = bx[3], b4 = bx[4], b5 = bx[5];
+  // Both products per axis, then the select: the bounds are wave-uniform (SGPRs) and a vector instruction reads one scalar
+  // operand, so `(sx ? b3 : b0) - o.x` costs a move of one bound into a VGPR and a select before the subtraction.  Selecting
+  // between the two finished products is the same value bit for bit (a select commutes with a pure function of the selected
+  // operand, NaN included) and every instruction has one scalar operand.
+  const float lx = (b0 - o.x) * inv.x, hx = (b3 - o.x) * inv.x;
+  const float ly = (b1 - o.y) * inv.y, hy = (b4 - o.y) * inv.y;
+  const float lz = (b2 - o.z) * inv.z, hz = (b5 - o.z) * inv.z;
+  float tmin = sx ? hx : lx;
+  float tmax = sx ? lx : hx;
+  const float tymin = sy ? hy : ly;
+  const float tymax = sy ? ly : hy;
+  const bool miss_y = (tmin > tymax) | (tymin > tmax);
+  tmin = (tymin > tmin) ? tymin : tmin;
+  tmax = (tymax < tmax) ? tymax : tmax;
+  const float tzmin = sz ? hz : lz;
+  const float tzmax = sz ? lz : hz;
+  const bool miss_z = (tmin > tzmax) | (tzmin > tmax);
+  tmin = (tzmin > tmin) ? tzmin : tmin;
+  tmax = (tzmax < tmax) ? tzmax : tmax;
+  const bool hit = !(miss_y | miss_z);
+  const float nx = ((tmin >= tx) & (tmin <= ty)) ? tmin : tx;
+  const float ny = ((tmax >= nx) & (tmax <= ty)) ? tmax : ty;
+  tx = hit ? nx : tx;
+  ty = hit ? ny : ty;
+  return hit;
+}
+
 // find_closest_hit of one BVH<Triangle> over its interior records: one 64-byte fetch brings both child boxes,
 // leaves are folded in place, a stack frame is 16 bytes (after the nearer child returns, its result reuses
 // the slots of cur_far_t).  Same visit rule and Trace::min as traverse<>().

@@ -1,6 +1,6 @@
 // The path tracer's host side after srt_pt_scene_commit: what changes or queries a committed scene - new vertices (srt_pt_update_mesh,
 // srt_pt_refit_mesh), skinning (srt_pt_skin*), new poses (srt_pt_repose*) and the figures about them.  Host code only: the kernels are in
-// pt_mesh_update.hip, pt_pose.hip, pt_light_update.hip, pt_skin.hip and pt_bvh_device.hip, the context and what pt.hip shares in pt_context.h.
+// pt_mesh_update.hip, pt_pose.hip, pt_light_update.hip, pt_skin.hip and pt_bvh_device.hip, the context and what the units share in pt_context.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -1335,24 +1335,6 @@ int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* 
   for (uint32_t j = 0; j < njoints; j++)
     for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = extents[3 * (size_t)j + a];
   anim_rig_posed_host(parent, cap.data(), base, rest_pose, knot_offsets, knot_times, knot_quats, njoints, t, euler_out, local.data(), posed_out);
-  return SRT_OK;
-}
-
-int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, float* out) {
-  int st = need_device(pt, "srt_pt_math_hypot");
-  if (st != SRT_OK) return st;
-  if (n == 0) return SRT_OK;
-  if (!x || !y || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_hypot: NULL argument");
-  DeviceBuffer<float> d;
-  if ((st = d.ensure(3 * n))) return st;
-  hipError_t e = hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + n, y, n * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_anim_hypot(pt->stream, d, d + n, n, d + 2 * n);
-    e = hipMemcpyAsync(out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost, pt->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(pt->stream);
-  SRT_HIP(e);
   return SRT_OK;
 }
 

@@ -103,7 +103,7 @@ SRT_DEV bool cancel_requested(const uint32_t* host_cancel) { return __hip_atomic
 
 constexpr uint32_t kStreamBlock = 256;    // threads per block of the streamed logic kernels (one queue atomic per block; four waves, so
                                           // that a CU takes the next block as soon as four waves are done)
-constexpr uint32_t kMaxStreamSlots = 1u << 26;   // srt_pt_set_stream_slots: upper bound of the path-slot population (state planes: ~13 GB there)
+                                          // (kMaxStreamSlots, the bound srt_pt_set_stream_slots checks: pt_context.h)
 constexpr uint32_t kMaxLazy = 4;          // TRAV 4: meshes with a real BVH<Triangle> whose walks are queued
 
 // Wave-uniform launch constants passed through an empty asm: the value stays in SGPRs, but arithmetic on it
@@ -157,40 +157,7 @@ SRT_DEV V3 mat_point_uniform(const Mat4& m, V3 v) {
   return v3(o[0] / o[3], o[1] / o[3], o[2] / o[3]);
 }
 
-// BBox::hit with the reciprocal direction hoisted (the reference recomputes the same 1/dir per box), in
-// straight-line form: the two early-outs become one verdict, `times` is narrowed only on a hit.
-SRT_DEV bool box_hit_inv(const float* __restrict__ bx, V3 o, V3 inv, float& tx, float& ty) {
-  const bool sx = inv.x < 0, sy = inv.y < 0, sz = inv.z < 0;
-  // the six bounds are read into values first: `c ? bx[3] : bx[0]` on the memory operands is an lvalue select,
-  // i.e. one per-lane vector load from a selected address instead of two wave-uniform scalar loads
-  const float b0 = bx[0], b1 = bx[1], b2 = bx[2], b3 = bx[3], b4 = bx[4], b5 = bx[5];
-  // Both products per axis, then the select: the bounds are wave-uniform (SGPRs) and a vector instruction reads one scalar
-  // operand, so `(sx ? b3 : b0) - o.x` costs a move of one bound into a VGPR and a select before the subtraction.  Selecting
-  // between the two finished products is the same value bit for bit (a select commutes with a pure function of the selected
-  // operand, NaN included) and every instruction has one scalar operand.
-  const float lx = (b0 - o.x) * inv.x, hx = (b3 - o.x) * inv.x;
-  const float ly = (b1 - o.y) * inv.y, hy = (b4 - o.y) * inv.y;
-  const float lz = (b2 - o.z) * inv.z, hz = (b5 - o.z) * inv.z;
-  float tmin = sx ? hx : lx;
-  float tmax = sx ? lx : hx;
-  const float tymin = sy ? hy : ly;
-  const float tymax = sy ? ly : hy;
-  const bool miss_y = (tmin > tymax) | (tymin > tmax);
-  tmin = (tymin > tmin) ? tymin : tmin;
-  tmax = (tymax < tmax) ? tymax : tmax;
-  const float tzmin = sz ? hz : lz;
-  const float tzmax = sz ? lz : hz;
-  const bool miss_z = (tmin > tzmax) | (tzmin > tmax);
-  tmin = (tzmin > tmin) ? tzmin : tmin;
-  tmax = (tzmax < tmax) ? tzmax : tmax;
-  const bool hit = !(miss_y | miss_z);
-  const float nx = ((tmin >= tx) & (tmin <= ty)) ? tmin : tx;
-  const float ny = ((tmax >= nx) & (tmax <= ty)) ? tmax : ty;
-  tx = hit ? nx : tx;
-  ty = hit ? ny : ty;
-  return hit;
-}
-
+// (box_hit_inv, the sweeps' BBox::hit: pt_trace.h, after box_hit_rec)
 // (kRetMiss / kRetMissEnv and the two-word PHit the sweeps carry: pt_trace.h)
 // (the sweep builds take <= 16 objects: 5 + 27 bits; the streamed build passes the scene's own split)
 SRT_DEV uint32_t pack_ret(const Hit& h, uint32_t shift = 27u) { return h.hit ? ((h.obj << shift) | h.tri) : kRetMiss; }
@@ -242,7 +209,7 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
     }
   }
   V3 pos[NR];
-  if (o.kind == OBJ_SPHERE) {                         // (restated line for line in pt_sphere_batch_kernel, pt.hip: change both)
+  if (o.kind == OBJ_SPHERE) {                         // (restated line for line in pt_sphere_batch_kernel, pt_probe.hip: change both)
     SphHit sh[NR];
     sphere_hitN<NR>(o.radius, oorg, od, ob0, ob1, sh);
 #pragma unroll

@@ -57,7 +57,7 @@ void emu_set_camera(void* h, const float* iview, float vfov, float ar, uint32_t 
   e->S.w = w; e->S.h = ht; e->S.max_depth = max_depth;
 }
 
-// pt_trace_samples_kernel (pt.hip) for n (x, y, sample) triples: radiance, RNG draws and rays of each; normals != 0: the
+// pt_samples_kernel (pt_query.hip) for n (x, y, sample) triples: radiance, RNG draws and rays of each; normals != 0: the
 // normal-colors view's first-hit sample instead.
 void emu_trace_samples(void* h, uint64_t seed, const uint32_t* xs, const uint32_t* ys, const uint32_t* ss, size_t n, int normals, float* rgb,
                        uint32_t* draws, uint32_t* rays) {
@@ -75,7 +75,7 @@ void emu_trace_samples(void* h, uint64_t seed, const uint32_t* xs, const uint32_
   }
 }
 
-// pt_hit_kernel (pt.hip) for n rays: the nine floats of srt_pt_hit {hit, dist, position, normal, material}, from the nested walk
+// pt_hit_kernel (pt_query.hip) for n rays: the nine floats of srt_pt_hit {hit, dist, position, normal, material}, from the nested walk
 // and from the flattened walk (ray i in batch slot i % 3, as the kernel places it).
 void emu_hit9(void* h, const float* org, const float* dir, const float* bounds, size_t n, float* nested9, float* flat9) {
   Emu* e = (Emu*)h;
