@@ -158,7 +158,7 @@ int check_stream_fault(srt_pt* pt, const char* what) {
 bool elision_provable(const srt_pt* pt) {
   const FlatScene& F = pt->built.flat;
   if (!pt->elide || !F.delta_lights.empty() || pt->env_type != 0) return false;
-  if (pt->shade_pending_mats) return false;               // srt_pt_shading_timeline_apply: F.materials lags the device until settle()
+  if (pt->shade.pending_mats) return false;               // srt_pt_shading_timeline_apply: F.materials lags the device until settle()
   for (const Material& m : F.materials) {
     if (m.type == 3u && !(0.2126f * m.a[0] + 0.7152f * m.a[1] + 0.0722f * m.a[2] > 0.0f)) return false;
     // the dead term is emission x albedo x cos x 1/pdf with 1/pdf <= pi / cos(1): finite as long as the factors are moderate

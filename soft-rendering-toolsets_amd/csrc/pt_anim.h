@@ -2,7 +2,7 @@
 // (student/spline.inl:5-72), Spline<Quat>::at (geometry/spline.inl:4-15) with slerp (lib/quat.h:177-189), Quat::to_euler
 // (lib/quat.h:124-135, lib/mat4.h:163-199), Mat4::euler / rotate / translate / scale (lib/mat4.h:382-418), Pose::transform
 // (scene/pose.cpp:4-10), Anim_Pose::at (:54-57) and Joint::joint_to_posed (student/skeleton.cpp:26-52) under
-// Skeleton::joint_to_posed (:106-115).  pt_anim.hip runs them one lane per object or joint; pt_update.cpp runs the same functions on
+// Skeleton::joint_to_posed (:106-115).  pt_anim.hip runs them one lane per object or joint; the pt_update_*.cpp units run the same functions on
 // the host (srt_pt_timeline_transforms, srt_pt_skin_posed: the definition the kernels are held to) and the host emulation
 // (tests/host_emu/anim_host.cpp) compiles this header with g++ -ffp-contract=off.  Every function restates the reference
 // operation for operation - one rounding per operator, sums in the order the reference's expressions associate, true divisions -

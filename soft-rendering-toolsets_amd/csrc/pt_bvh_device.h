@@ -1,5 +1,5 @@
 // The device BVH builder's core (pt_bvh_device.hip) and the per-triangle kernels of srt_pt_update_mesh (pt_mesh_update.hip) as
-// the path tracer's host code (srt_pt_scene_commit in pt_context.cpp, pt_update.cpp) calls them.  `stream` is a hipStream_t.
+// the path tracer's host code (srt_pt_scene_commit in pt_context.cpp, pt_update*.cpp) calls them.  `stream` is a hipStream_t.
 #ifndef SRT_PT_BVH_DEVICE_H
 #define SRT_PT_BVH_DEVICE_H
 

@@ -246,16 +246,16 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
       return st;
     // the index buffers the kernels of pt_mesh_update.hip read (12 B per triangle)
     std::vector<uint32_t> idx;
-    pt->idx_off.assign(pt->built.inputs.size(), SIZE_MAX);
+    pt->mesh.idx_off.assign(pt->built.inputs.size(), SIZE_MAX);
     for (size_t i = 0; i < pt->built.inputs.size(); i++) {
       const ObjectInput& in = pt->built.inputs[i];
       if (in.kind != OBJ_MESH || in.source >= 0 || (in.is_light && !pt->built.dynamic_lights)) continue;   // (a light's goes up later when the switch is set later: ensure_mesh_idx)
-      pt->idx_off[i] = idx.size();
+      pt->mesh.idx_off[i] = idx.size();
       idx.insert(idx.end(), in.mesh.idx.begin(), in.mesh.idx.end());
     }
-    pt->idx_words = idx.size();
-    pt->idx_uncounted = 0;
-    if ((st = upload(pt, &pt->d_idx, idx))) return st;
+    pt->mesh.idx_words = idx.size();
+    pt->mesh.idx_uncounted = 0;
+    if ((st = upload(pt, &pt->mesh.d_idx, idx))) return st;
   }
   pt->committed = true;
   pt->scene_generation++;
@@ -344,7 +344,13 @@ int srt_pt_set_normal_colors(srt_pt* pt, int on) {
 int srt_pt_set_ray_log(srt_pt* pt, uint32_t capacity) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_ray_log: NULL context");
   if (capacity > (1u << 26)) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_ray_log: at most 2^26 rays per read (got %u)", capacity);
-  pt->ray_log_cap = capacity;                            // the rings follow at the next epoch on each stream (stream_buffers)
+  pt->ray_log_cap = capacity;                             // the rings follow at the next epoch on each stream (stream_buffers)
+  return SRT_OK;
+}
+
+int srt_pt_live_resources(uint64_t out[3]) {
+  if (!out) return srt::fail(SRT_ERR_INVALID, "srt_pt_live_resources: NULL argument");
+  for (int k = 0; k < 3; k++) out[k] = owned_live((OwnedKind)k).load(std::memory_order_relaxed);
   return SRT_OK;
 }
 

@@ -1,7 +1,9 @@
 // The path tracer's context (struct srt_pt) and the helpers the translation units behind include/srt_pt.h share:
 //   pt.hip          the render kernels, the choice of kernel form, the render paths and what reads back what a render leaves
 //   pt_context.cpp  host code only: create / destroy, scene begin / add / commit, camera, image size, tiling and the switches
-//   pt_update.cpp   host code only: what changes or queries a committed scene
+//   pt_update*.cpp  host code only: what changes or queries a committed scene - pt_update_mesh.cpp (new vertices), pt_update_skin.cpp
+//                   (skins and rigs), pt_update_pose.cpp (poses, object timelines), pt_update_shading.cpp (materials, delta lights,
+//                   shading timelines) and pt_update.cpp (what they share - pt_update.h - and settle())
 //   pt_query.hip    per-lane kernels on the committed scene outside a render (samples, hits, particles) and the dumps
 //   pt_image.hip    untile, accumulate, tonemap
 //   pt_probe.hip    the test-only math probes of srt_pt_debug.h
@@ -99,55 +101,88 @@ struct srt_pt {
   // srt_pt_scene_counts: since creation
   uint64_t blas_builds = 0, bytes_uploaded = 0, tri_bytes_uploaded = 0;
   // srt_pt_update_mesh: the index buffers of the meshes that can be updated (no instance, no area light), resident from commit on, one
-  // after the other; the device builder's workspace; and the staging of the host form's vertex arrays.  Grown on demand, kept.
-  srt::DeviceBuffer<uint32_t> d_idx; size_t idx_words = 0;   // idx_words: the words in use
-  std::vector<size_t> idx_off;              // per object in insertion order: first word of its index buffer in d_idx (SIZE_MAX: none)
-  srt::BvhWorkspace bvh_ws;
-  srt::DeviceBuffer<float> d_vpos, d_vnrm;
-  // srt_pt_refit_mesh: per refitted mesh (insertion index) what its kernels keep on the device, from the first refit until the mesh
-  // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
-  std::map<uint32_t, srt::RefitTables> refit_tables;
-  uint64_t refits = 0;
+  // after the other; the device builder's workspace (srt_pt_repose_device builds the BVH<Object> in it too); and the staging of the
+  // host form's vertex arrays.  Grown on demand, kept.
+  struct MeshState {
+    srt::DeviceBuffer<uint32_t> d_idx; size_t idx_words = 0;   // idx_words: the words in use
+    std::vector<size_t> idx_off;            // per object in insertion order: first word of its index buffer in d_idx (SIZE_MAX: none)
+    // srt_pt_set_dynamic_lights (the switch itself is built.dynamic_lights): the bytes of index buffers that went up for a light's
+    // first update or refit (ensure_mesh_idx) and are counted with the verdict
+    uint64_t idx_uncounted = 0;
+    srt::BvhWorkspace bvh_ws;
+    srt::DeviceBuffer<float> d_vpos, d_vnrm;
+    // srt_pt_refit_mesh: per refitted mesh (insertion index) what its kernels keep on the device, from the first refit until the mesh
+    // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
+    std::map<uint32_t, srt::RefitTables> refit_tables;
+    uint64_t refits = 0;
+    // The refit tables of `object` (UINT32_MAX: of every mesh): its tree is about to be replaced.
+    void drop_refit_tables(uint32_t object) {
+      if (object == UINT32_MAX) refit_tables.clear();
+      else refit_tables.erase(object);
+    }
+  } mesh;
   // srt_pt_repose_device: what its kernels keep on the device between calls - every object's record by insertion index, its
-  // object-space box and its posed box - made at the first device repose after a commit (drop_pose_tables: a commit, a mesh update
-  // or refit and a host repose change what they mirror; so does a device repose that is refused).  The per-call arrays (the list,
-  // the read-back staging, the mesh ordinals per slot) are grown on demand and kept.
-  srt::DeviceBuffer<srt::Object> d_pose_records; srt::DeviceBuffer<float> d_local_boxes, d_posed_boxes;
-  bool pose_tables = false;
-  srt::DeviceBuffer<uint32_t> d_pose_list;
-  srt::DeviceBuffer<srt::PoseOut> d_pose_out;
-  srt::DeviceBuffer<uint32_t> d_slot_ordinal;
-  // srt_pt_set_dynamic_lights (the switch itself is built.dynamic_lights): srt_pt_repose_device's table of the listed lights
-  // ({position in the list, light} pairs), grown on demand and kept; and the bytes of index buffers that went up for a light's
-  // first update or refit (ensure_mesh_idx) and are counted with the verdict
-  srt::DeviceBuffer<uint32_t> d_light_list;
-  uint64_t idx_uncounted = 0;
-  // srt_pt_skin: counts srt_pt_scene_begin and srt_pt_scene_commit; a skin made under another count is stale
+  // object-space box and its posed box - made at the first device repose after a commit and good only while `valid` (drop(): a
+  // commit, a mesh update or refit and a host repose change what they mirror; so does a device repose that is refused).  The
+  // per-call arrays (the list, the read-back staging, the mesh ordinals per slot, and under srt_pt_set_dynamic_lights the listed
+  // lights as {position in the list, light} pairs) are grown on demand and kept.
+  struct PoseTables {
+    srt::DeviceBuffer<srt::Object> d_records; srt::DeviceBuffer<float> d_local_boxes, d_posed_boxes;
+    bool valid = false;
+    srt::DeviceBuffer<uint32_t> d_list;
+    srt::DeviceBuffer<srt::PoseOut> d_out;
+    srt::DeviceBuffer<uint32_t> d_slot_ordinal;
+    srt::DeviceBuffer<uint32_t> d_light_list;
+    void drop() {
+      d_records.reset(); d_local_boxes.reset(); d_posed_boxes.reset();
+      valid = false;
+    }
+  } pose;
+  // srt_pt_skin, srt_pt_timeline, srt_pt_shading_timeline: counts srt_pt_scene_begin and srt_pt_scene_commit; a handle made under
+  // another count is stale
   uint64_t scene_generation = 0;
   // srt_pt_repose_refit[_device]: the BVH<Object>'s refit tables (RefitTables of pt_bvh_device.h; d_tri_boxes stays empty - the posed
   // boxes of the pose tables are passed in its place) and the slot of every object, made at the first device-form refit of a tree and
-  // dropped wherever the tree is replaced (drop_top_tables).  top_list: what d_pose_list (and d_light_list) hold when the last call
-  // that wrote them was a device-form refit - a call with the same list uploads nothing.  pinned: host staging of the lists, one
-  // buffer per list still on its way (its event tells), so that a call never waits for the one before.
-  srt::RefitTables top_tables; bool have_top_tables = false;
-  srt::DeviceBuffer<uint32_t> d_slot_of;
-  std::vector<uint32_t> top_list; bool top_list_valid = false;
-  uint32_t top_lights = 0, top_light_max_ntri = 0;        // of top_list: listed lights, and the largest triangle count among them
-  struct PinnedList { srt::PinnedBuffer<uint32_t> h; srt::Event done; };
-  std::vector<PinnedList> pinned;
-  // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of objects
-  // they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls are
-  // pending), and the event recorded behind the last of them.
-  uint64_t top_pending = 0;
-  std::vector<uint8_t> top_pending_flag;
-  std::vector<uint32_t> top_pending_objects;
-  srt::Event top_event;
-  uint64_t top_refits = 0;                  // srt_pt_top_refit_count
+  // dropped wherever the tree is replaced (drop_tables()).  list: what pose.d_list (and pose.d_light_list) hold, while list_valid: the
+  // last call that wrote them was a device-form refit - a call with the same list uploads nothing.  pinned: host staging of the
+  // lists, one buffer per list still on its way (its event tells), so that a call never waits for the one before.
+  struct TopLevel {
+    srt::RefitTables tables; bool have_tables = false;
+    srt::DeviceBuffer<uint32_t> d_slot_of;
+    std::vector<uint32_t> list; bool list_valid = false;
+    uint32_t lights = 0, light_max_ntri = 0;              // of list: listed lights, and the largest triangle count among them
+    struct PinnedList { srt::PinnedBuffer<uint32_t> h; srt::Event done; };
+    std::vector<PinnedList> pinned;
+    // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of
+    // objects they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls
+    // are pending), and the event recorded behind the last of them.  (ShadingLag below is the same arrangement for the shading tables.)
+    uint64_t pending = 0;
+    std::vector<uint8_t> pending_flag;
+    std::vector<uint32_t> pending_objects;
+    srt::Event event;
+    uint64_t refits = 0;                    // srt_pt_top_refit_count
+    // The BVH<Object> is about to be replaced (or pose.d_list to be overwritten by another call: then only the list is forgotten).
+    void forget_list() { list_valid = false; list.clear(); }
+    void drop_tables() {
+      tables = srt::RefitTables();
+      have_tables = false;
+      d_slot_of.reset();
+      forget_list();
+    }
+    // No srt_pt_repose_refit_device call is waiting for settle() any more.
+    void forget_pending() {
+      pending = 0;
+      for (uint32_t i : pending_objects) pending_flag[i] = 0;
+      pending_objects.clear();
+    }
+  } top;
   // srt_pt_shading_timeline_apply: the host's record of the materials / delta lights lags the device from a call that wrote them until
   // settle() reads d_mats / d_dlights back, behind the event recorded after the last such call.  While the materials lag,
   // elision_provable (pt.hip) proves nothing.
-  bool shade_pending_mats = false, shade_pending_lights = false;
-  srt::Event shade_event;
+  struct ShadingLag {
+    bool pending_mats = false, pending_lights = false;
+    srt::Event event;
+  } shade;
 };
 
 namespace srt {
@@ -191,12 +226,6 @@ struct DeviceBuilderScope {
 };
 // SRT_OK, or the refusal of trees deeper than the traversal stacks.
 int check_depth(uint32_t tlas_depth, uint32_t blas_depth);
-// Every device write that follows a replaced host mirror (apply_* of pt_scene.h, build_scene) returns through here: after a failed
-// one the device arrays are behind the host's, so the scene is no longer committed and has to be committed again.
-inline int written(srt_pt* pt, int status) {
-  if (status != SRT_OK) pt->committed = false;
-  return status;
-}
 
 }  // namespace srt
 

@@ -63,7 +63,7 @@ __device__ __forceinline__ void store_box(float* boxes6, uint32_t i, const float
 }
 
 // One lane per leaf: leaf = {node, (first slot << 3) | count}; the fold of its triangles' boxes in primitive order.  Every index
-// in the tables was checked against the mesh's counts where they were made (make_refit_tables, pt_update.cpp), where a bad one is an error.
+// in the tables was checked against the mesh's counts where they were made (make_refit_tables, pt_update_mesh.cpp), where a bad one is an error.
 __global__ __launch_bounds__(256) void refit_leaves_kernel(const uint2* __restrict__ leaves, uint32_t nleaves, const uint32_t* __restrict__ prim,
                                                            const float* __restrict__ tri_boxes6, float* __restrict__ node_boxes6) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
