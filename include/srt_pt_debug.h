@@ -128,6 +128,15 @@ int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c
  * the three rays); out: 19 planes ({hit as 0 / 1, t, dist} of rays 0, 1, 2 from the batch form, the same nine from tri_hit, and
  * 1 where the lane's wave held an ambiguous lane and computed u and v after all; a wave is 64 consecutive lanes). */
 int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out);
+/* The leaf fold of the wave kernel's mesh branch (pt_device.h: leaf_foldN - a candidate pass over the leaf's triangles, then one
+ * quotient and one root per ray; a wave with a bad lane folds the leaf the long way) next to the plain ordered fold over tri_hit
+ * (ret = Trace::min(ret, Triangle::hit)), one leaf per wave of 64 consecutive lanes, lane i on its own origin and three rays.
+ * lanes must be a multiple of 64.  in: first, per wave, 148 words - the number of triangles as a uint32 (1..12), three unused
+ * words, then twelve triangles of 12 floats (p0 xyz and a pad, e1 xyz and a pad, e2 xyz and a pad) -, then 18 planes of `lanes`
+ * floats (origin xyz, direction xyz of rays 0, 1, 2, dist_bounds.x of the three rays, dist_bounds.y of the three rays); out: 25
+ * planes (per ray {hit as 0 / 1, winning triangle as a uint32 or 0 without a hit, t, dist} from the leaf code and the same four
+ * from the plain fold, then 1 where the lane's wave fell back).  SRT_ERR_INVALID for a count outside 1..12 or lanes % 64 != 0. */
+int srt_pt_math_leaf_fold(srt_pt* pt, const float* in, size_t lanes, float* out);
 /* The wave kernel's batch Sphere::hit (pt_device.h: sphere_hitN<3>, whose tangent root is computed wave-uniformly, then the distance
  * step of Object::hit through sqrtN, as the sphere branch of object_testN in pt_wave.h performs it) next to the plain per-ray form
  * (sphere_hit and |Ray::at(t) - origin|), lane i on its own radius, origin and three rays.  in: 19 planes of `lanes` floats (radius,

@@ -144,6 +144,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_tonemap_device.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p]
     lib.srt_pt_math_div_sqrt.argtypes = [c_void_p, c_void_p, c_size_t, ctypes.c_int, c_void_p]
     lib.srt_pt_math_tri_verdict.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_math_leaf_fold.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_box_sweep.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_sphere_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_sync.argtypes = [c_void_p]
@@ -1145,6 +1146,29 @@ class Pathtracer:
         self._check(self._lib, self._lib.srt_pt_math_tri_verdict(self._ctx, _p(planes), n, _p(out)))
         form = lambda b: {"hit": out[b:b + 9:3].T != 0, "t": out[b + 1:b + 9:3].T.copy(), "dist": out[b + 2:b + 9:3].T.copy()}
         return form(0), form(9), int(np.count_nonzero(out[18, ::64]))
+
+    def math_leaf_fold(self, tris, ntri, org, dirs, bounds):
+        """The leaf fold of the wave kernel's mesh branch (leaf_foldN<3>) and the plain ordered fold over tri_hit on W waves of 64
+        lanes, one leaf per wave.  tris (W, 12, 9) = p0, e1, e2 of up to twelve triangles; ntri (W,) in 1..12; org (W, 64, 3);
+        dirs (W, 64, 3, 3); bounds (W, 64, 3, 2) = dist_bounds of each ray.  Returns (leaf, plain, fell_back): two dicts of
+        (W, 64, 3) arrays {"hit": bool, "tri": uint32, "t", "dist"} and per wave whether it folded the leaf the long way."""
+        tris, ntri = _f32(tris).reshape(-1, 12, 3, 3), np.ascontiguousarray(ntri, np.uint32).reshape(-1)
+        W = len(ntri)
+        org, dirs, bounds = _f32(org).reshape(-1, 3), _f32(dirs).reshape(-1, 9), _f32(bounds).reshape(-1, 3, 2)
+        n = 64 * W
+        assert len(tris) == W and len(org) == n and len(dirs) == n and len(bounds) == n and W > 0
+        head = np.zeros((W, 148), np.float32)
+        head[:, 0] = ntri.view(np.float32)
+        padded = np.zeros((W, 12, 3, 4), np.float32)
+        padded[..., :3] = tris
+        head[:, 4:] = padded.reshape(W, 144)
+        planes = np.concatenate([org, dirs, bounds[:, :, 0], bounds[:, :, 1]], axis=1).T
+        buf = np.ascontiguousarray(np.concatenate([head.ravel(), planes.ravel()]), np.float32)
+        out = np.zeros((25, n), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_leaf_fold(self._ctx, _p(buf), n, _p(out)))
+        res = out[:24].reshape(3, 8, W, 64).transpose(1, 2, 3, 0)                 # (field, wave, lane, ray)
+        form = lambda b: {"hit": res[b] != 0, "tri": res[b + 1].view(np.uint32).copy(), "t": res[b + 2].copy(), "dist": res[b + 3].copy()}
+        return form(0), form(4), out[24].reshape(W, 64)[:, 0] != 0
 
     def math_sphere_batch(self, radius, org, dirs, bounds):
         """The wave kernel's batch Sphere::hit (sphere_hitN<3> and the distance step of object_testN's sphere branch)

@@ -564,6 +564,32 @@ SRT_DEV TriVerdict tri_verdict(float nu, float nv, float det) {
   return v;
 }
 
+// ---- One quotient and one root per ray and leaf: the candidate of the ordered fold ----
+// The fold over a leaf's triangles (ret = Trace::min(ret, Triangle::hit), object_testN in pt_wave.h) reads {hit, dist, t} of every
+// triangle and keeps those of one.  hit implies "not outside", and by the proof above the first three tests of "outside" follow
+// from the numerators for every lane that is in the window and not ambiguous.  So while every (ray, triangle) pair of a leaf is
+// decided that way, a ray with at most ONE triangle that is not outside - its candidate - can be hit by no other triangle of the
+// leaf, whatever their t and distance would have been: every other Trace::min step has a miss on the right and keeps the left
+// side, and the fold returns the candidate's own {hit, dist, t}, or the default Trace (no hit: dist = t = 0) when the candidate
+// fails t < 0 or the dist_bounds, or when there is none.  t and the distance are then computed once, for the candidate, by the
+// operations tri_hitN performs on the same operands - the same bits.  A lane is BAD, and its wave folds the leaf the long way,
+// when any of this does not hold: a pair out of the window (det == 0 is), an ambiguous pair (a NaN among nu, nv, det is, unless
+// a sign decided first, as in tri_hitN), or a second candidate (two coplanar triangles of a wall: only a ray through the shared
+// edge to within rounding; a closed mesh in one leaf: every ray through it).
+// Plain C++ (no device builtins): tests/host_emu runs the same functions on the CPU.
+struct LeafCand { float det, nt; uint32_t n; };       // n: the candidate's triangle index + 1, 0 = none (then det = 1, nt = 0: t = 0)
+SRT_DEV LeafCand leaf_cand_none() { LeafCand c; c.det = 1.0f; c.nt = 0.0f; c.n = 0u; return c; }
+// One (ray, triangle) pair; returns "bad" of this pair apart from the window, which the caller tests per lane (div_in_range).
+SRT_DEV bool leaf_cand_add(LeafCand& c, float nu, float nv, float det, float nt, uint32_t n) {
+  const TriVerdict v = tri_verdict(nu, nv, det);
+  const bool cand = !v.outside;
+  const bool bad = v.ambiguous | (cand & (c.n != 0u));
+  c.det = cand ? det : c.det;
+  c.nt = cand ? nt : c.nt;
+  c.n = cand ? n : c.n;
+  return bad;
+}
+
 // Triangle::hit of one triangle for the N rays of a batch (shared origin), for a caller that folds hits (Trace::min): hit,
 // distance and t, no barycentrics.  s, s x e2 and the numerator of t do not depend on the direction.  Inside div_window and
 // with no ambiguous lane in the wave (tri_verdict) only t is divided, through the shared-reciprocal refinement; with one, the
@@ -630,6 +656,113 @@ SRT_DEV void tri_hitN(const Tri& g, V3 org, const V3* d, const float* b0, const 
     const bool out_of_bounds = (h[r].dist < b0[r]) || (h[r].dist > b1[r]);
     h[r].hit = (det[r] != 0) & !outside[r] & !out_of_bounds;       // (no short-circuit: masks, not branches)
   }
+}
+
+// The ordered fold over the triangles of one leaf (<= 4 triangles, or a List<Triangle>) for the NR rays of a batch:
+// ret = Trace::min(ret, hit) per triangle, triangles tris[first .. first + ntri).  Out: bd = distance, bt = t, bn = index of the
+// winning triangle + 1 (0 = no hit, then bd = bt = 0: the default Trace).
+// The long way, one tri_hitN per triangle.  A miss changes nothing: left_wins(l, ., false, .) == l, so either the left side
+// is kept or both sides are misses and the fields already hold the default Trace (no hit => bd = bt = 0, true before the
+// loop and kept by every step).  Only a hit that is not beaten (ldist < rdist is false on NaN: the right side wins) is
+// taken: one mask and one select per field.  "hit so far" is carried as bn != 0, bn = winning triangle's index + 1: a flag
+// of its own lives in a register across the loop and costs three more instructions per ray and triangle.
+template <int NR>
+SRT_DEV void leaf_fold_longN(const Tri* __restrict__ tris, uint32_t first, uint32_t ntri, V3 oorg, const V3* od, const float* ob0,
+                             const float* ob1, float* bd, float* bt, uint32_t* bn) {
+#pragma unroll
+  for (int r = 0; r < NR; r++) { bd[r] = 0.0f; bt[r] = 0.0f; bn[r] = 0u; }
+  for (uint32_t t = 0; t < ntri; t++) {
+    TriHitT th[NR];
+    tri_hitN<NR>(tris[first + t], oorg, od, ob0, ob1, th);
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      const bool take = th[r].hit & !((bn[r] != 0u) & (bd[r] < th[r].dist));   // == th.hit && !left_wins(bh, bd, th.hit, th.dist)
+      bd[r] = take ? th[r].dist : bd[r];
+      bt[r] = take ? th[r].t : bt[r];
+      bn[r] = take ? first + t + 1u : bn[r];
+    }
+  }
+}
+// The fold as object_testN (pt_wave.h) runs it (ONCE): a candidate pass over the leaf (leaf_cand_add above, where the proof stands) -
+// per triangle the numerators and det exactly as tri_hitN forms them, no division, no root, no ballot -, then ONE ballot on "a
+// lane is bad".  Without a bad lane every (ray, triangle) pair is decided from its numerators and every ray has at most one
+// triangle that is not outside, so no other triangle of the leaf can be hit and the ordered fold returns that candidate's own
+// test: one quotient t (the operations of tri_hitN's decided path on the same operands), one norm2(d * t), one sqrtN call, the
+// bounds.  Lanes without a candidate compute on det = 1, nt = 0 (t = 0, distance +0) and report the default Trace, as does a
+// candidate that fails t < 0 or the bounds.
+// A wave with a bad lane (*fellback is set, when given: wave-uniform) folds the leaf with the plain per-ray tri_hit - the
+// compiler's own `/` and sqrtf, whose {hit, dist, t} tri_hitN equals bit for bit on every input (tests/test_pt_tri_verdict_gpu.py) -
+// one RAY after the other, the triangles in the inner loop: the cold path then needs the registers of one plain test and
+// nothing of it is alive across the candidate pass.  How the cold path is attached decides the kernel's scratch (DESIGN.md
+// section 6 has the table of forms); ONCE = false keeps the long way for the two kernel forms this form costs scratch.
+template <int NR, bool ONCE>
+SRT_DEV void leaf_foldN(const Tri* __restrict__ tris, uint32_t first, uint32_t ntri, V3 oorg, const V3* od, const float* ob0,
+                        const float* ob1, float* bd, float* bt, uint32_t* bn, bool* fellback = nullptr) {
+#if SRT_EXACT_FAST_PATHS
+  if (ONCE) {
+    LeafCand c[NR];
+#pragma unroll
+    for (int r = 0; r < NR; r++) c[r] = leaf_cand_none();
+    bool bad = false;
+    for (uint32_t t = 0; t < ntri; t++) {
+      const Tri& g = tris[first + t];
+      const V3 e1 = v3p(g.e1), e2 = v3p(g.e2);
+      const V3 s = oorg - v3p(g.p0);
+      const V3 sxe2 = cross(s, e2);
+      const float nt = -1.0f * dot(sxe2, e1);
+      float num[NR][3], det[NR];
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        const V3 e1xd = cross(e1, od[r]);
+        det[r] = dot(e1xd, e2);
+        num[r][0] = -1.0f * dot(sxe2, od[r]);
+        num[r][1] = dot(e1xd, s);
+        num[r][2] = nt;
+      }
+      bad = bad | !div_in_range<NR, true>(num, det);
+#pragma unroll
+      for (int r = 0; r < NR; r++) bad = bad | leaf_cand_add(c[r], num[r][0], num[r][1], det[r], nt, first + t + 1u);
+    }
+    if (__ballot(bad) == 0ull) {
+      float tq[NR], n2[NR], nr[NR];
+      bool zero[NR];
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        tq[r] = __builtin_amdgcn_div_fixupf(div_refine(c[r].nt, c[r].det, rcp_refined(c[r].det)), c[r].det, c[r].nt);
+        n2[r] = norm2(od[r] * tq[r]);
+        zero[r] = c[r].nt == 0.0f;                // the origin on the candidate's plane, or no candidate: exactly +0
+      }
+      sqrtN<NR>(n2, zero, nr);
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        const float dist = fabsf(nr[r]);
+        const bool hit = (c[r].n != 0u) & !(tq[r] < 0) & !((dist < ob0[r]) | (dist > ob1[r]));
+        bd[r] = hit ? dist : 0.0f;
+        bt[r] = hit ? tq[r] : 0.0f;
+        bn[r] = hit ? c[r].n : 0u;
+      }
+      return;
+    }
+    if (fellback) *fellback = true;
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      Ray ray; ray.o = oorg; ray.d = od[r]; ray.b0 = ob0[r]; ray.b1 = ob1[r];
+      float fd = 0.0f, ft = 0.0f;
+      uint32_t fn = 0u;
+#pragma nounroll
+      for (uint32_t t = 0; t < ntri; t++) {
+        const TriHit th = tri_hit(tris[first + t], ray);
+        const bool take = th.hit & !((fn != 0u) & (fd < th.dist));
+        fd = take ? th.dist : fd;
+        ft = take ? th.t : ft;
+        fn = take ? first + t + 1u : fn;
+      }
+      bd[r] = fd; bt[r] = ft; bn[r] = fn;
+    }
+    return;
+  }
+#endif
+  leaf_fold_longN<NR>(tris, first, ntri, oorg, od, ob0, ob1, bd, bt, bn);
 }
 
 // Triangle::hit of the (up to) four triangles of a BVH<Triangle> leaf for ONE ray: the twelve quotients and four

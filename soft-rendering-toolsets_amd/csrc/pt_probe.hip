@@ -100,6 +100,55 @@ __global__ void pt_tri_verdict_kernel(const float* __restrict__ in, size_t lanes
   }
 }
 
+// The leaf fold of the wave kernel's mesh branch (leaf_foldN<3, true>, pt_device.h: one candidate, one quotient and one root per ray)
+// next to the plain ordered fold over tri_hit, one leaf per wave (64 consecutive lanes), lane i on its own origin and three rays.
+// in: per wave 148 floats - the triangle count as a 32-bit integer, three unused words, twelve Tri records (p0, e1, e2 as xyz + pad) -
+// then 18 planes of `lanes` floats (origin, three directions, then b0 and b1 of the three rays); out: 25 planes - per ray
+// {hit as 0 / 1, winning triangle as a 32-bit integer, t, dist} of the leaf code, the same four of the plain fold, and "this lane's
+// wave met a bad lane and folded the leaf the long way".  lanes is a multiple of 64 and every count in 1..12 (checked by the caller).
+constexpr size_t kLeafFoldWave = 4 + 12 * sizeof(Tri) / sizeof(float);
+__global__ void pt_leaf_fold_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= lanes) return;                               // whole waves
+  const float* leaf = in + (i / 64) * kLeafFoldWave;
+  const uint32_t ntri = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(leaf[0]));
+  const Tri* tris = reinterpret_cast<const Tri*>(leaf + 4);
+  const float* planes = in + (lanes / 64) * kLeafFoldWave;
+  float v[18];
+#pragma unroll
+  for (int j = 0; j < 18; j++) v[j] = planes[(size_t)j * lanes + i];
+  const V3 org = v3(v[0], v[1], v[2]);
+  V3 d[3];
+  float b0[3], b1[3], bd[3], bt[3];
+  uint32_t bn[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++) { d[r] = v3(v[3 + 3 * r], v[4 + 3 * r], v[5 + 3 * r]); b0[r] = v[12 + r]; b1[r] = v[15 + r]; }
+  bool fellback = false;
+  leaf_foldN<3, true>(tris, 0u, ntri, org, d, b0, b1, bd, bt, bn, &fellback);
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    Ray ray; ray.o = org; ray.d = d[r]; ray.b0 = b0[r]; ray.b1 = b1[r];
+    bool ph = false;                                    // ret = Trace::min(ret, Triangle::hit), as Trace::min is written
+    float pd = 0.0f, ptt = 0.0f;
+    uint32_t pn = 0u;
+    for (uint32_t t = 0; t < ntri; t++) {
+      const TriHit h = tri_hit(tris[t], ray);
+      const bool left = ph && (!h.hit || pd < h.dist);
+      if (!left && h.hit) { ph = true; pd = h.dist; ptt = h.t; pn = t; }
+    }
+    const bool hit = bn[r] != 0u;
+    out[(size_t)(8 * r) * lanes + i] = hit ? 1.0f : 0.0f;
+    out[(size_t)(8 * r + 1) * lanes + i] = __uint_as_float(hit ? bn[r] - 1u : 0u);
+    out[(size_t)(8 * r + 2) * lanes + i] = bt[r];
+    out[(size_t)(8 * r + 3) * lanes + i] = bd[r];
+    out[(size_t)(8 * r + 4) * lanes + i] = ph ? 1.0f : 0.0f;
+    out[(size_t)(8 * r + 5) * lanes + i] = __uint_as_float(pn);
+    out[(size_t)(8 * r + 6) * lanes + i] = ptt;
+    out[(size_t)(8 * r + 7) * lanes + i] = pd;
+  }
+  out[(size_t)24 * lanes + i] = fellback ? 1.0f : 0.0f;
+}
+
 // Sphere::hit of the wave kernel's batch (sphere_hitN<3> and the distance step through sqrtN, as object_testN's sphere branch in
 // pt_wave.h performs them - restated below, since moving the branch into a function of its own changed a wave kernel's scratch)
 // next to the plain per-ray form (sphere_hit, then the distance as object_hit has it, pt_trace.h), lane i on its own radius,
@@ -260,6 +309,19 @@ int srt_pt_math_div_sqrt(srt_pt* pt, const float* in, size_t lanes, int shared_c
 int srt_pt_math_tri_verdict(srt_pt* pt, const float* in, size_t lanes, float* out) {
   return math_round_trip(pt, "srt_pt_math_tri_verdict", {in}, 27 * lanes, {out}, 19 * lanes, [&](float* const* d, float* const* o) {
     pt_tri_verdict_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_leaf_fold(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  if (lanes % 64) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_leaf_fold: %zu lanes are not whole waves of 64", lanes);
+  if (in)
+    for (size_t w = 0; w < lanes / 64; w++) {
+      uint32_t ntri;
+      __builtin_memcpy(&ntri, in + w * kLeafFoldWave, 4);
+      if (ntri < 1 || ntri > 12) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_leaf_fold: wave %zu has %u triangles (1..12)", w, ntri);
+    }
+  const size_t in_floats = (lanes / 64) * kLeafFoldWave + 18 * lanes;
+  return math_round_trip(pt, "srt_pt_math_leaf_fold", {in}, in_floats, {out}, 25 * lanes, [&](float* const* d, float* const* o) {
+    pt_leaf_fold_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
 }
 
 int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* out) {

@@ -178,7 +178,8 @@ SRT_DEV Hit no_hit() { Hit h; h.hit = false; h.dist = 0.0f; h.obj = 0; h.tri = 0
 // QUEUE (TRAV 4, the streamed sweeps): the walk of a real BVH<Triangle> is not done here.  In the probe pass (emit) the rays
 // that need it are written - in the mesh's object space - to their fixed queue positions and flagged in emit_mask; the
 // ray-cast kernel walks them between two generations; the complete pass reads {world distance, triangle} back.
-template <bool HAS_BLAS, int NR, bool QUEUE = false>
+// LEAF_ONCE: the mesh branch folds a leaf through leaf_foldN's candidate pass (pt_device.h).
+template <bool HAS_BLAS, int NR, bool QUEUE = false, bool LEAF_ONCE = true>
 SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, const float* rb0, const float* rb1,
                           Counters& cnt, bool* hit, float* dist, uint32_t* tri, const bool* need, uint32_t* cidx,
                           const WaveParams* QP = nullptr, uint32_t lane_global = 0, bool emit = false, uint32_t* emit_mask = nullptr) {
@@ -298,26 +299,10 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
     }
     return;                                              // world distances are final
   } else {                                            // one leaf of <= 4 triangles, or List<Triangle>: ordered fold
-    // ret = Trace::min(ret, hit) per triangle.  A miss changes nothing: left_wins(l, ., false, .) == l, so either the left side
-    // is kept or both sides are misses and the fields already hold the default Trace (no hit => bd = bt = 0, true before the
-    // loop and kept by every step).  Only a hit that is not beaten (ldist < rdist is false on NaN: the right side wins) is
-    // taken: one mask and one select per field.  "hit so far" is carried as bn != 0, bn = winning triangle's index + 1: a flag
-    // of its own lives in a register across the loop and costs three more instructions per ray and triangle.
+    // ret = Trace::min(ret, hit) per triangle (leaf_foldN, pt_device.h: one quotient and one root per ray, not per triangle)
     float bd[NR], bt[NR];
     uint32_t bn[NR];
-#pragma unroll
-    for (int r = 0; r < NR; r++) { bd[r] = 0.0f; bt[r] = 0.0f; bn[r] = 0u; }
-    for (uint32_t t = 0; t < o.ntri; t++) {
-      TriHitT th[NR];
-      tri_hitN<NR>(S.tris[o.tri_base + t], oorg, od, ob0, ob1, th);
-#pragma unroll
-      for (int r = 0; r < NR; r++) {
-        const bool take = th[r].hit & !((bn[r] != 0u) & (bd[r] < th[r].dist));   // == th.hit && !left_wins(bh, bd, th.hit, th.dist)
-        bd[r] = take ? th[r].dist : bd[r];
-        bt[r] = take ? th[r].t : bt[r];
-        bn[r] = take ? o.tri_base + t + 1u : bn[r];
-      }
-    }
+    leaf_foldN<NR, LEAF_ONCE>(S.tris, o.tri_base, o.ntri, oorg, od, ob0, ob1, bd, bt, bn);
 #pragma unroll
     for (int r = 0; r < NR; r++) {
       hit[r] = bn[r] != 0u; dist[r] = bd[r]; tri[r] = hit[r] ? bn[r] - 1u : 0u;
@@ -496,6 +481,9 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   constexpr int C = NR - 1;                              // slot of the indirect ray
   constexpr bool STREAM = TRAV >= 3;                     // pt_stream.h: 3 = every ray through the ray-cast kernel, 4 = sweeps here, BVH<Triangle> walks queued
   constexpr bool LAZY = TRAV == 1 || TRAV == 4;          // meshes with a real BVH<Triangle> are evaluated lazily inside the sweeps
+  // (the leaf fold's candidate pass raises the scratch of two forms - the stamped TRAV 1 build and the delta-light probe build
+  // of the streamed sweeps - by 16 and 4 B per lane: they keep the fold over tri_hitN.  Same bits either way.)
+  constexpr bool LEAF_ONCE = !(STAMP && TRAV == 1) && !(TRAV == 4 && DL && PHASE == 0);
   if constexpr (STREAM) {
     if (P_in.sc->done != 0u) return;                     // every unit is finished: the remaining generations are no-ops
   }
@@ -941,7 +929,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
       for (int r = 0; r < NR; r++) acc[r] = packed_miss();
       for (uint32_t k = 0; k < nobj; k++) {
         bool h[NR]; float dd[NR]; uint32_t tt[NR];
-        object_testN<LAZY, NR, TRAV == 4>(S, k, org, d, rb0, rb1, cnt, h, dd, tt, act, cidx, &P, lane_global, pass == 1, &emit_mask);
+        object_testN<LAZY, NR, TRAV == 4, LEAF_ONCE>(S, k, org, d, rb0, rb1, cnt, h, dd, tt, act, cidx, &P, lane_global, pass == 1, &emit_mask);
 #pragma unroll
         for (int r = 0; r < NR; r++) packed_fold(acc[r], h[r], dd[r], (k << 27) | tt[r]);
       }
@@ -1009,7 +997,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
             for (uint32_t k = first; k < first + n; k++) {
               bool h[NR]; float dd[NR]; uint32_t tt[NR];
               // (TRAV 4: a mesh with a real BVH<Triangle> is a leaf of its own - checked on the host - and goes through `queued`)
-              object_testN<TRAV == 1, NR>(S, k, org, d, rb0, rb1, cnt, h, dd, tt, need, cidx);
+              object_testN<TRAV == 1, NR, false, LEAF_ONCE>(S, k, org, d, rb0, rb1, cnt, h, dd, tt, need, cidx);
 #pragma unroll
               for (int r = 0; r < NR; r++) packed_fold(out[r], h[r], dd[r], (k << 27) | tt[r]);
             }
