@@ -146,6 +146,13 @@ int srt_pt_group_read_ray_log(srt_pt_group* g, int lane, srt_pt_logged_ray* out,
 int srt_pt_group_set_normal_colors(srt_pt_group* g, int on);
 /* srt_pt_set_dynamic_lights (below) on every member. */
 int srt_pt_group_set_dynamic_lights(srt_pt_group* g, int on);
+/* srt_pt_set_active (below) on every member, and srt_pt_set_active_device with one device array per rank (d_active[r]: n bytes on
+ * rank r's device; ranks that share a device may share the array), each on `stream` of its rank's device.  The group's lanes render
+ * on streams of their own, which nothing orders behind `stream`: the device form settles every member (srt_pt_sync) before it
+ * returns, so it waits.  A caller that wants the enqueue-only loop drives the members and their streams itself.  The first member's
+ * refusal is returned; the list is the same for every member, so a refused list is refused by the first and nothing was written. */
+int srt_pt_group_set_active(srt_pt_group* g, const uint32_t* objects, const uint8_t* active, uint32_t n);
+int srt_pt_group_set_active_device(srt_pt_group* g, void* stream, const uint32_t* objects, const uint8_t* const* d_active, uint32_t n);
 /* Device time of the exchange step of srt_pt_group_render_epoch[_device] - from the moment rank 0's own tiles are rendered to the end of
  * the un-tiling kernel on rank 0's stream: the gather (RCCL, or copies between ranks that share a device) and what it waits for, i.e. the
  * slowest other rank - summed over the epochs since the previous call (HIP events; waits for them); then recording on / off.  A diagnostic
@@ -309,9 +316,61 @@ int srt_pt_scene_tree_cost(srt_pt* pt, double* cost);
  * rays/pathtracer.cpp:149, bit-equal to Mat4::operator* (zero signs included).  d_pos holds 3 floats per particle - the layout
  * srt_pt_particles_step_device updates in place - so that step -> transforms -> srt_pt_repose_device -> render has no host data
  * in it (and with srt_pt_repose_refit_device in the place of srt_pt_repose_device, no host wait either).  Only enqueues on
- * `stream`; does not synchronise.  The population is fixed: n is the number of particle objects the scene was committed with.
- * Spawning and removing particles stays with the caller and needs a commit, as before. */
+ * `stream`; does not synchronise.  The CAPACITY is fixed: n is the number of particle objects the scene was committed with.  Within it
+ * the population changes without a commit: srt_pt_set_active[_device] switches a dead particle's object off and a spawned one's on
+ * (the pool loop under srt_pt_set_active_device). */
 int srt_pt_particle_transforms_device(srt_pt* pt, void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out);
+/* Switches objects of the committed scene off and on without committing again: what Scene_Particles::step2 does to its vector of
+ * particles each step (dead ones dropped, new ones appended), for a pool of fixed capacity.  `objects` are n insertion indices,
+ * active[k] belongs to objects[k], non-zero means active - the layout of srt_pt_particles_step's `alive` with the particles'
+ * indices as `objects`.  Every object is active after srt_pt_scene_commit; srt_pt_scene_begin and srt_pt_scene_commit drop the table.
+ *   Definition.  With posed_k = Object::bbox of object k, the effective box is E_k = active_k ? posed_k : BBox(), the reference's
+ * empty box (min = +FLT_MAX, max = -FLT_MAX on every axis, lib/bbox.h).  The BVH<Object> keeps its links and its primitive order;
+ * while any object is inactive its node boxes are srt_pt_repose_refit's fold over E (BBox::enclose of an empty box changes
+ * nothing), written into the top-level nodes and the sweep records; with every object active again they are that fold over the
+ * posed boxes - the committed boxes as values.  Topology never depends on the flags: every call that builds the BVH<Object>
+ * (srt_pt_scene_commit, srt_pt_repose[_device], srt_pt_update_mesh*, srt_pt_refit_mesh*, the skin poses, the timelines' repose)
+ * builds over the posed boxes of ALL objects and then, only while an object is inactive, ends with the masked fold;
+ * srt_pt_repose_refit[_device] and the timelines' repose_refit feed E to their leaf stage.  Nothing else of an inactive object
+ * changes: its record, its material and its posed box stay and keep following repose, refit, update and skin calls, so it returns
+ * where it would be.  A mesh that instances are made of may be inactive while its instances stay active.
+ *   Results are those of the reference's BVH<Object>::hit and BBox::hit on that tree with those boxes, a leaf whose objects are
+ * all inactive holding no primitive.  BBox::hit of the empty box is false for every ray without a NaN component - but that alone
+ * hides nothing: find_closest_hit visits the child whose box was MISSED whenever the other child returns a hit farther than
+ * ray.dist_bounds.x (cur_far_t starts as ray.dist_bounds, student/bvh.inl:191-192, 216).  So the tables the kernels walk also give
+ * such a leaf the count 0 - the count word of its top-level node and the l_cnt / r_cnt of the sweep record above it - as a build
+ * gives an empty leaf (a leaf of the BVH<Object> holds 0 or 1); srt_pt_dump_bvh keeps showing the committed links and sizes.
+ * Nothing that walks the BVH<Object> - path rays, shadow rays, srt_pt_hit, srt_pt_particles_step[_device] - reaches an inactive
+ * object, and closest hits are those of a fresh commit without it, exact ties apart.  CAVEAT: a ray with a NaN component passes
+ * every box, today as before; an inactive object shares its leaf with no other (the leaf is empty), so such a ray finds nothing
+ * there either, but no promise is made about rays with NaN components.  srt_pt_scene_tree_cost counts a node whose box is empty
+ * (mn > mx on an axis) as 0, and an empty root gives cost 0.
+ *   Refusals, the scene staying exactly as it was on the host and on the device (nothing live is written before the verdict):
+ * SRT_ERR_STATE without a committed scene; SRT_ERR_UNSUPPORTED for a scene committed with use_bvh == 0 (a list scene has no boxes)
+ * and for a scene whose BVH<Object> root is a leaf (a single object: find_closest_hit tests children only, the root's box never);
+ * SRT_ERR_INVALID for a NULL argument with n > 0, an index out of range, a duplicate, and an emissive object - an emissive mesh or a
+ * sphere light, also under srt_pt_set_dynamic_lights: the light list would go on sampling it.
+ *   This form BLOCKS: it settles and waits as srt_pt_repose_refit waits, runs the definition on the host's record and uploads the
+ * top-level nodes (32 B each: boxes and leaf counts) and the sweep records (64 B each), nothing else.  A call that changes no flag writes and uploads
+ * nothing.  A host-only context runs the definition and nothing else. */
+int srt_pt_set_active(srt_pt* pt, const uint32_t* objects, const uint8_t* active, uint32_t n);
+/* The same with the flags in device memory (d_active: n bytes, read on `stream` - srt_pt_particles_step_device's d_alive as it
+ * is), ENQUEUE-ONLY under the contract of srt_pt_repose_refit_device: the list is validated on the host first (refusals and status
+ * codes as above; a host-only context validates and then returns SRT_ERR_UNSUPPORTED), then the call only enqueues on `stream`, in
+ * order: a kernel copies the listed flags into the context's table (1 B per object, by insertion index); the leaf stage of the
+ * refit reads E - the posed boxes masked by the table; the interior levels, deepest first; the boxes into the live top-level nodes
+ * and sweep records; the leaf counts into the same (two small launches).  No synchronisation, no read-back.  Steady state uploads the list (4 B per listed object) and nothing when
+ * the list equals the previous device-form call's - srt_pt_repose_refit_device's included: the two share the list.  Blocking work
+ * only where srt_pt_repose_refit_device has it: the first call after a commit or a rebuild (the same tables; 1 B per object more
+ * for the table while an object is inactive), and growth.  Ordering is srt_pt_repose_refit_device's.  The host's record lags and
+ * settles on the same path, which behind such a call additionally reads the table back (1 B per object).
+ *   The pool loop, all on one stream and without a host wait: srt_pt_particles_step_device -> srt_pt_particle_transforms_device
+ * -> srt_pt_set_active_device(d_alive) -> srt_pt_repose_refit_device -> srt_pt_render_epoch_device.  A caller spawns by writing
+ * pos, vel and age of a dead slot and setting its alive byte, with a kernel or torch op of its own, before the next frame. */
+int srt_pt_set_active_device(srt_pt* pt, void* stream, const uint32_t* objects, const uint8_t* d_active, uint32_t n);
+/* The table after settling: one byte per object in insertion order (1 active, 0 inactive) into active_out[0 .. objects).
+ * SRT_ERR_INVALID when cap is less than the object count, SRT_ERR_STATE without a commit. */
+int srt_pt_get_active(srt_pt* pt, uint8_t* active_out, uint32_t cap);
 /* New vertex arrays for ONE mesh of the committed scene without committing again: what a renderer of deforming meshes (a skinned
  * skeleton, cloth, a caller's own kernel) gets from the reference only by running build_scene again on Scene_Object::posed_mesh()
  * (rays/pathtracer.cpp:66-176, per frame).  `object` is the insertion index of an object added by srt_pt_add_mesh; positions /

@@ -67,6 +67,11 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_repose_refit.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_repose_refit_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_scene_tree_cost.argtypes = [c_void_p, POINTER(ctypes.c_double)]
+    lib.srt_pt_set_active.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_set_active_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_get_active.argtypes = [c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_group_set_active.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_group_set_active_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_top_refit_count.argtypes = [c_void_p, POINTER(c_uint64)]
     lib.srt_pt_top_refit_pending.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_mesh_tree_cost.argtypes = [c_void_p, c_uint32, POINTER(ctypes.c_double)]
@@ -671,6 +676,28 @@ class Pathtracer:
         idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
         self._check(self._lib, self._lib.srt_pt_repose_refit_device(self._ctx, c_void_p(stream), _p(idx), c_void_p(d_trans_ptr), len(idx)))
 
+    def set_active(self, indices, flags) -> None:
+        """srt_pt_set_active: switches the objects with these insertion indices off (flag 0) or on (non-zero) without committing
+        again - an inactive object keeps its record and pose, and nothing that walks the BVH<Object> reaches it.  Blocks."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        if len(f) != len(idx):
+            raise ValueError(f"{len(idx)} objects but {len(f)} flags")
+        self._check(self._lib, self._lib.srt_pt_set_active(self._ctx, _p(idx), _p(f), len(idx)))
+
+    def set_active_device(self, indices, d_active_ptr: int, stream: int = 0) -> None:
+        """srt_pt_set_active_device: the same from a device array of len(indices) bytes (particles_step_device's d_alive), only
+        enqueued on `stream`: no wait, no read-back.  The host's record settles as after repose_refit_device."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._check(self._lib, self._lib.srt_pt_set_active_device(self._ctx, c_void_p(stream), _p(idx), c_void_p(d_active_ptr), len(idx)))
+
+    def active(self) -> np.ndarray:
+        """srt_pt_get_active: one uint8 per object in insertion order, 1 = active (after settling)."""
+        n = int(self.scene_counts()["objects"])
+        out = np.zeros(max(n, 1), np.uint8)
+        self._check(self._lib, self._lib.srt_pt_get_active(self._ctx, _p(out), n))
+        return out[:n]
+
     def scene_tree_cost(self) -> float:
         """srt_pt_scene_tree_cost: SAH cost of the current BVH<Object> (after settling)."""
         c = ctypes.c_double()
@@ -1263,6 +1290,24 @@ class PathtracerGroup:
             m.repose_refit_device(indices, ptr, stream)
         for m in self.members:
             m._check(m._lib, m._lib.srt_pt_sync(m._ctx))
+
+    def set_active(self, indices, flags) -> None:
+        """srt_pt_group_set_active: srt_pt_set_active on every rank."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        if len(f) != len(idx):
+            raise ValueError(f"{len(idx)} objects but {len(f)} flags")
+        self._check(self._lib, self._lib.srt_pt_group_set_active(self._g, _p(idx), _p(f), len(idx)))
+
+    def set_active_device(self, indices, d_active_ptrs, stream: int = 0) -> None:
+        """srt_pt_group_set_active_device: one device pointer per rank, as repose_refit_device takes d_trans_ptrs; every member is
+        settled before this returns (the group's lanes render on streams of their own)."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        ptrs = list(d_active_ptrs)
+        if len(ptrs) != len(self.members):
+            raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
+        arr = (c_void_p * len(ptrs))(*[c_void_p(int(p)) for p in ptrs])
+        self._check(self._lib, self._lib.srt_pt_group_set_active_device(self._g, c_void_p(stream), _p(idx), arr, len(idx)))
 
     def update_mesh(self, index: int, pos, nrm) -> None:
         for m in self.members:

@@ -52,8 +52,9 @@ struct RefitTables {
   int level_launches = 0;                // != 0: one launch per level even where a run of levels fits one workgroup (measurements)
 };
 // Leaf boxes from d_leaf_boxes6 (by original primitive: a mesh's T.d_tri_boxes, launch_mesh_boxes' output; the BVH<Object>'s posed
-// boxes), then the interior levels, deepest first, into d_node_boxes6 (six floats per node).  Only enqueues.
-void launch_refit_boxes(void* stream, const RefitTables& T, const float* d_leaf_boxes6, float* d_node_boxes6);
+// boxes), then the interior levels, deepest first, into d_node_boxes6 (six floats per node).  Only enqueues.  d_mask (NULL: none): one
+// byte per original primitive, 0 = the leaf stage folds BBox() in the place of that primitive's box (srt_pt_set_active's table).
+void launch_refit_boxes(void* stream, const RefitTables& T, const float* d_leaf_boxes6, float* d_node_boxes6, const uint8_t* d_mask = nullptr);
 // The boxes into the mesh's live nodes (d_mesh_nodes: its first Node) and interior records (d_mesh_recs: its first record).
 void launch_refit_write(void* stream, const RefitTables& T, const float* d_node_boxes6, Node* d_mesh_nodes, WaveInterior* d_mesh_recs);
 

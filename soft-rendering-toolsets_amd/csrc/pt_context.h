@@ -125,16 +125,18 @@ struct srt_pt {
   // object-space box and its posed box - made at the first device repose after a commit and good only while `valid` (drop(): a
   // commit, a mesh update or refit and a host repose change what they mirror; so does a device repose that is refused).  The
   // per-call arrays (the list, the read-back staging, the mesh ordinals per slot, and under srt_pt_set_dynamic_lights the listed
-  // lights as {position in the list, light} pairs) are grown on demand and kept.
+  // lights as {position in the list, light} pairs) are grown on demand and kept.  d_active: srt_pt_set_active's table, one byte per
+  // object by insertion index, made with the others from built.active (all 1: a fill on the device, nothing goes up).
   struct PoseTables {
     srt::DeviceBuffer<srt::Object> d_records; srt::DeviceBuffer<float> d_local_boxes, d_posed_boxes;
+    srt::DeviceBuffer<uint8_t> d_active;
     bool valid = false;
     srt::DeviceBuffer<uint32_t> d_list;
     srt::DeviceBuffer<srt::PoseOut> d_out;
     srt::DeviceBuffer<uint32_t> d_slot_ordinal;
     srt::DeviceBuffer<uint32_t> d_light_list;
     void drop() {
-      d_records.reset(); d_local_boxes.reset(); d_posed_boxes.reset();
+      d_records.reset(); d_local_boxes.reset(); d_posed_boxes.reset(); d_active.reset();
       valid = false;
     }
   } pose;
@@ -156,7 +158,9 @@ struct srt_pt {
     // The host's record lags the device after srt_pt_repose_refit_device until settle(): the calls not applied yet, the SET of
     // objects they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls
     // are pending), and the event recorded behind the last of them.  (ShadingLag below is the same arrangement for the shading tables.)
-    uint64_t pending = 0;
+    // pending_active: those of the pending calls that were srt_pt_set_active_device (they are no refits, and settle() reads the
+    // active table back only behind one of them).
+    uint64_t pending = 0, pending_active = 0;
     std::vector<uint8_t> pending_flag;
     std::vector<uint32_t> pending_objects;
     srt::Event event;
@@ -171,7 +175,7 @@ struct srt_pt {
     }
     // No srt_pt_repose_refit_device call is waiting for settle() any more.
     void forget_pending() {
-      pending = 0;
+      pending = pending_active = 0;
       for (uint32_t i : pending_objects) pending_flag[i] = 0;
       pending_objects.clear();
     }

@@ -502,6 +502,23 @@ int srt_pt_group_set_dynamic_lights(srt_pt_group* g, int on) {
   return SRT_OK;
 }
 
+int srt_pt_group_set_active(srt_pt_group* g, const uint32_t* objects, const uint8_t* active, uint32_t n) {
+  if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_set_active: NULL group");
+  for (srt_pt* c : g->ctx) { const int st = srt_pt_set_active(c, objects, active, n); if (st != SRT_OK) return st; }
+  return SRT_OK;
+}
+
+int srt_pt_group_set_active_device(srt_pt_group* g, void* stream, const uint32_t* objects, const uint8_t* const* d_active, uint32_t n) {
+  if (!g || (n && !d_active)) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_set_active_device: NULL argument");
+  for (size_t r = 0; r < g->ctx.size(); r++) {
+    const int st = srt_pt_set_active_device(g->ctx[r], stream, objects, n ? d_active[r] : nullptr, n);
+    if (st != SRT_OK) return st;
+  }
+  // (the lanes' streams are not ordered behind `stream`: every member settles before the group renders again)
+  for (srt_pt* c : g->ctx) { const int st = srt_pt_sync(c); if (st != SRT_OK) return st; }
+  return SRT_OK;
+}
+
 int srt_pt_group_set_ray_log(srt_pt_group* g, uint32_t capacity) {
   if (!g) return srt::fail(SRT_ERR_INVALID, "srt_pt_group_set_ray_log: NULL group");
   for (srt_pt* c : g->ctx) { const int st = srt_pt_set_ray_log(c, capacity); if (st != SRT_OK) return st; }

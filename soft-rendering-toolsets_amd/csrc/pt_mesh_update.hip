@@ -64,8 +64,11 @@ __device__ __forceinline__ void store_box(float* boxes6, uint32_t i, const float
 
 // One lane per leaf: leaf = {node, (first slot << 3) | count}; the fold of its triangles' boxes in primitive order.  Every index
 // in the tables was checked against the mesh's counts where they were made (make_refit_tables, pt_update_mesh.cpp), where a bad one is an error.
+// mask (the BVH<Object> under srt_pt_set_active; NULL: every primitive counts): one byte per primitive, 0 = BBox() is folded in the
+// place of its box (an enclose of the empty box leaves the fold unchanged).
 __global__ __launch_bounds__(256) void refit_leaves_kernel(const uint2* __restrict__ leaves, uint32_t nleaves, const uint32_t* __restrict__ prim,
-                                                           const float* __restrict__ tri_boxes6, float* __restrict__ node_boxes6) {
+                                                           const float* __restrict__ tri_boxes6, const uint8_t* __restrict__ mask,
+                                                           float* __restrict__ node_boxes6) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nleaves) return;
   const uint2 leaf = leaves[i];
@@ -75,7 +78,8 @@ __global__ __launch_bounds__(256) void refit_leaves_kernel(const uint2* __restri
   for (uint32_t k = first; k < first + count; k++) {
     const uint32_t t = prim[k];
     float tb[6];
-    load_box(tri_boxes6, t, tb);
+    if (mask && !mask[t]) box_empty(tb);
+    else load_box(tri_boxes6, t, tb);
     box_enclose(b, tb);
   }
   store_box(node_boxes6, leaf.x, b);
@@ -146,10 +150,10 @@ void launch_mesh_records(void* stream, const float* d_pos, const float* d_nrm_in
   mesh_records_kernel<<<dim3((ntri + 255u) / 256u), dim3(256), 0, (hipStream_t)stream>>>(d_pos, d_nrm_in, d_idx, d_prim, ntri, d_tris, d_nrm, d_packed);
 }
 
-void launch_refit_boxes(void* stream, const RefitTables& T, const float* d_leaf_boxes6, float* d_node_boxes6) {
+void launch_refit_boxes(void* stream, const RefitTables& T, const float* d_leaf_boxes6, float* d_node_boxes6, const uint8_t* d_mask) {
   hipStream_t s = (hipStream_t)stream;
   if (T.nleaves)
-    refit_leaves_kernel<<<dim3((T.nleaves + 255u) / 256u), dim3(256), 0, s>>>(T.d_leaves, T.nleaves, T.d_prim, d_leaf_boxes6, d_node_boxes6);
+    refit_leaves_kernel<<<dim3((T.nleaves + 255u) / 256u), dim3(256), 0, s>>>(T.d_leaves, T.nleaves, T.d_prim, d_leaf_boxes6, d_mask, d_node_boxes6);
   // deepest level first; runs of levels that fit one workgroup share a launch
   const std::vector<uint32_t>& off = T.level_off;
   uint32_t l = (uint32_t)off.size() - 1u;          // number of levels

@@ -123,6 +123,14 @@ void launch_top_slots(void* stream, const uint32_t* d_prim, uint32_t nobj, uint3
 // d_objects[d_slot_of[i]] (slot i when d_slot_of is NULL: a list scene).  Copies only; no other field of a live record is written.
 void launch_top_objects(void* stream, const uint32_t* d_listed, uint32_t n, uint32_t nobj, const uint32_t* d_slot_of, const Object* d_by_index,
                         Object* d_objects);
+// srt_pt_set_active_device: d_table[d_listed[k]] = d_flags[k] != 0 for k < n - the table holds one byte per object by insertion index
+// (nobj of them), which the leaf stage of the BVH<Object>'s refit takes as its mask (launch_refit_boxes, pt_bvh_device.h).
+void launch_active_scatter(void* stream, const uint32_t* d_listed, const uint8_t* d_flags, uint32_t n, uint32_t nobj, uint8_t* d_table);
+// Behind it, and behind the refit's box stages: the count a leaf of the BVH<Object> holds for the walks - the count word of the live
+// top-level nodes and the l_cnt / r_cnt of the live sweep records - 0 while every object of the leaf is inactive (two launches: leaves,
+// then records).  T: the BVH<Object>'s refit tables.
+struct RefitTables;
+void launch_top_counts(void* stream, const RefitTables& T, const uint8_t* d_table, uint32_t nobj, Node* d_nodes, WaveInterior* d_wave);
 // One lane per particle: d_trans_out[16 k ..] = translate(d_pos[3 k ..]) * scale(scale).
 void launch_particle_transforms(void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out);
 

@@ -7,6 +7,7 @@
 // object: its launches are a few thousand lanes of a few hundred bytes, and its matrices are where the arithmetic is.
 #include <hip/hip_runtime.h>
 
+#include "pt_bvh_device.h"
 #include "pt_pose.h"
 
 namespace srt {
@@ -121,6 +122,48 @@ __global__ __launch_bounds__(256) void top_objects_kernel(const uint32_t* __rest
   else live[slot].has_trans = by_index[i].has_trans;
 }
 
+// srt_pt_set_active_device.  One lane per listed object: its flag (any non-zero byte: active) into the table by insertion index, as 0 / 1.
+// An element scatter of single bytes - a few thousand lanes at the most, the table a few cache lines: loads of consecutive list words
+// and flag bytes, one byte store per lane, no two lanes on one byte (the list holds no duplicate: checked on the host).
+__global__ __launch_bounds__(256) void active_scatter_kernel(const uint32_t* __restrict__ listed, const uint8_t* __restrict__ flags, uint32_t n, uint32_t nobj,
+                                                             uint8_t* __restrict__ table) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t i = listed[k];
+  if (i >= nobj) return;                                         // (the list was checked on the host before anything was enqueued)
+  table[i] = flags[k] ? (uint8_t)1 : (uint8_t)0;
+}
+
+// What the leaves of the BVH<Object> hold for the walks, after the table changed (write_top_counts, pt_scene.h).  One lane per leaf
+// {node, (first slot << 3) | count}: the count word of its live node - its count, or 0 while every object in it is inactive.
+__global__ __launch_bounds__(256) void top_leaf_counts_kernel(const uint2* __restrict__ leaves, uint32_t nleaves, const uint32_t* __restrict__ prim,
+                                                              const uint8_t* __restrict__ table, uint32_t nobj, uint32_t nnodes, Node* __restrict__ nodes) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nleaves) return;
+  const uint2 leaf = leaves[i];
+  if (leaf.x >= nnodes) return;                                  // (the tables were checked where they were made: make_refit_tables)
+  const uint32_t first = leaf.y >> 3, count = leaf.y & 7u;
+  uint32_t any = 0u;
+  for (uint32_t k = first; k < first + count; k++) {
+    const uint32_t o = prim[k];
+    if (o < nobj && table[o]) any = 1u;
+  }
+  nodes[leaf.x].count = LEAF_BIT | (any ? count : 0u);
+}
+
+// One lane per sweep record, in a launch behind the one above: children = {left node, right node}; a child that is a leaf gives the
+// record its count.  An interior child's entry is not touched.
+__global__ __launch_bounds__(256) void top_record_counts_kernel(const uint2* __restrict__ children, uint32_t nrec, uint32_t nnodes, const Node* __restrict__ nodes,
+                                                                WaveInterior* __restrict__ recs) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nrec) return;
+  const uint2 c = children[q];
+  if (c.x >= nnodes || c.y >= nnodes) return;
+  const uint32_t l = nodes[c.x].count, r = nodes[c.y].count;
+  if (l & LEAF_BIT) recs[q].l_cnt = l & ~LEAF_BIT;
+  if (r & LEAF_BIT) recs[q].r_cnt = r & ~LEAF_BIT;
+}
+
 __global__ __launch_bounds__(256) void particle_transforms_kernel(const float* __restrict__ pos, uint32_t n, float scale, float* __restrict__ out) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
@@ -163,6 +206,17 @@ void launch_top_objects(void* stream, const uint32_t* d_listed, uint32_t n, uint
                         Object* d_objects) {
   if (!n) return;
   top_objects_kernel<<<dim3(blocks_for((size_t)n * 9u)), dim3(256), 0, (hipStream_t)stream>>>(d_listed, n, nobj, d_slot_of, d_by_index, d_objects);
+}
+
+void launch_active_scatter(void* stream, const uint32_t* d_listed, const uint8_t* d_flags, uint32_t n, uint32_t nobj, uint8_t* d_table) {
+  if (!n) return;
+  active_scatter_kernel<<<dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream>>>(d_listed, d_flags, n, nobj, d_table);
+}
+
+void launch_top_counts(void* stream, const RefitTables& T, const uint8_t* d_table, uint32_t nobj, Node* d_nodes, WaveInterior* d_wave) {
+  hipStream_t s = (hipStream_t)stream;
+  if (T.nleaves) top_leaf_counts_kernel<<<dim3(blocks_for(T.nleaves)), dim3(256), 0, s>>>(T.d_leaves, T.nleaves, T.d_prim, d_table, nobj, T.nnodes, d_nodes);
+  if (T.nrec) top_record_counts_kernel<<<dim3(blocks_for(T.nrec)), dim3(256), 0, s>>>(T.d_children, T.nrec, T.nnodes, d_nodes, d_wave);
 }
 
 void launch_particle_transforms(void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {

@@ -473,6 +473,7 @@ std::string build_scene(const std::vector<ObjectInput>& objects, const std::vect
   B = BuiltScene();
   B.dynamic_lights = dynamic_lights;
   B.inputs = objects;
+  B.active.assign(objects.size(), 1);
   FlatScene& F = B.flat;
   F.use_bvh = use_bvh;
   F.materials = materials;
@@ -718,6 +719,7 @@ void apply_repose(BuiltScene* built, ReposedTop* top) {
       break;
     }
   }
+  if (any_inactive(B)) mask_top(built);              // (srt_pt_set_active: the build was over every posed box; the boxes are the masked fold)
 }
 
 std::string check_mesh_update(const BuiltScene& B, uint32_t object, uint32_t nverts) {
@@ -856,6 +858,7 @@ void apply_mesh_update(BuiltScene* built, MeshUpdate* update) {
   B.tlas.prim.swap(U.top.tlas.prim);
   const int32_t li = light_of(B, U.object);          // an emissive mesh (BuiltScene::dynamic_lights): its light-list copy and LightTri records
   if (li >= 0) write_light_mesh(built, (uint32_t)li, U.object);
+  if (any_inactive(B)) mask_top(built);
 }
 
 void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32_t>& idx, std::vector<float>* boxes6) {
@@ -1001,6 +1004,7 @@ std::string prepare_top_refit(const BuiltScene& B, const uint32_t* objects, cons
     uint32_t has_trans;
     posed_values(B.inputs[i].trans, &B.local_boxes[6 * (size_t)i], &itrans, &has_trans, &posed[6 * (size_t)i]);
   }
+  effective_boxes(B, &posed);
   top_refit_boxes(B.tlas, posed.data(), &R.boxes);
   return "";
 }
@@ -1028,28 +1032,114 @@ void apply_top_refit(BuiltScene* built, TopRefit* refit) {
       lt.area_term = light_area_term(L.pdfT, lt.v0, lt.v1, lt.v2);
     }
   }
-  if (!F.use_bvh) return;
-  HostBVH& tree = B.tlas;
+  if (F.use_bvh) write_top_boxes(built, R.boxes);
+}
+
+void write_top_boxes(BuiltScene* built, const std::vector<float>& boxes6) {
+  FlatScene& F = built->flat;
+  HostBVH& tree = built->tlas;
   for (size_t n = 0; n < tree.nodes.size(); n++) {
     HostNode& h = tree.nodes[n];
     Node& f = F.nodes[n];
-    for (int a = 0; a < 3; a++) { h.mn[a] = f.mn[a] = R.boxes[6 * n + a]; h.mx[a] = f.mx[a] = R.boxes[6 * n + 3 + a]; }
+    for (int a = 0; a < 3; a++) { h.mn[a] = f.mn[a] = boxes6[6 * n + a]; h.mx[a] = f.mx[a] = boxes6[6 * n + 3 + a]; }
   }
   // sweep records in node order, as append_records numbers them: both child boxes, nothing else
   size_t q = 0;
   for (const HostNode& h : tree.nodes) {
     if (h.l == h.r) continue;
     WaveInterior& wi = F.wave_tlas[q++];
-    for (int a = 0; a < 6; a++) { wi.boxl[a] = R.boxes[6 * (size_t)h.l + a]; wi.boxr[a] = R.boxes[6 * (size_t)h.r + a]; }
+    for (int a = 0; a < 6; a++) { wi.boxl[a] = boxes6[6 * (size_t)h.l + a]; wi.boxr[a] = boxes6[6 * (size_t)h.r + a]; }
   }
+}
+
+bool any_inactive(const BuiltScene& B) {
+  return std::find(B.active.begin(), B.active.end(), (uint8_t)0) != B.active.end();
+}
+
+void effective_boxes(const BuiltScene& B, std::vector<float>* posed6) {
+  const Box empty;
+  for (size_t i = 0; i < B.active.size(); i++)
+    if (!B.active[i])
+      for (int a = 0; a < 3; a++) { (*posed6)[6 * i + a] = empty.mn[a]; (*posed6)[6 * i + 3 + a] = empty.mx[a]; }
+}
+
+void posed_boxes(const BuiltScene& B, std::vector<float>* posed6) {
+  const size_t nobj = B.inputs.size();
+  posed6->resize(6 * nobj);
+  for (size_t i = 0; i < nobj; i++) {
+    Mat4 itrans;
+    uint32_t has_trans;
+    posed_values(B.inputs[i].trans, &B.local_boxes[6 * i], &itrans, &has_trans, &(*posed6)[6 * i]);
+  }
+}
+
+void write_top_counts(BuiltScene* built) {
+  FlatScene& F = built->flat;
+  if (!F.use_bvh) return;
+  const HostBVH& tree = built->tlas;
+  // what a leaf holds for the walks: its primitives, or nothing while every one of them is inactive (the BVH<Object>'s leaves hold 0 or 1)
+  auto held = [&](const HostNode& h) {
+    for (uint32_t k = h.start; k < h.start + h.size; k++)
+      if (built->active[tree.prim[k]]) return h.size;
+    return 0u;
+  };
+  size_t q = 0;
+  for (size_t n = 0; n < tree.nodes.size(); n++) {
+    const HostNode& h = tree.nodes[n];
+    if (h.l == h.r) { F.nodes[n].count = LEAF_BIT | held(h); continue; }
+    WaveInterior& wi = F.wave_tlas[q++];               // (numbered in node order, as append_records numbers them)
+    const HostNode &a = tree.nodes[h.l], &c = tree.nodes[h.r];
+    if (a.l == a.r) wi.l_cnt = held(a);
+    if (c.l == c.r) wi.r_cnt = held(c);
+  }
+}
+
+void mask_top(BuiltScene* built) {
+  if (!built->flat.use_bvh) return;
+  std::vector<float> posed, boxes;
+  posed_boxes(*built, &posed);
+  effective_boxes(*built, &posed);
+  top_refit_boxes(built->tlas, posed.data(), &boxes);
+  write_top_boxes(built, boxes);
+  write_top_counts(built);
+}
+
+std::string check_active_list(const BuiltScene& B, const uint32_t* objects, uint32_t n, bool* unsupported) {
+  *unsupported = true;
+  if (!B.flat.use_bvh) return "the scene was committed without BVHs: there are no boxes to hide an object behind";
+  if (B.tlas.nodes.size() < 2) return "the root of the BVH<Object> is a leaf, and the root's box is never tested: an object alone in its scene cannot be hidden";
+  *unsupported = false;
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  std::vector<bool> seen(nobj, false);
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t i = objects[k];
+    if (i >= nobj) return "object " + std::to_string(i) + " is out of range (the scene has " + std::to_string(nobj) + " objects)";
+    if (seen[i]) return "object " + std::to_string(i) + " is listed twice";
+    if (B.inputs[i].is_light) return "object " + std::to_string(i) + " is an area light: the light list would go on sampling it";
+    seen[i] = true;
+  }
+  return "";
+}
+
+bool apply_set_active(BuiltScene* built, const uint32_t* objects, const uint8_t* active, uint32_t n) {
+  bool changed = false;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint8_t a = active[k] ? 1 : 0;
+    if (built->active[objects[k]] != a) { built->active[objects[k]] = a; changed = true; }
+  }
+  if (changed) mask_top(built);
+  return changed;
 }
 
 double tree_cost(const HostBVH& tree) {
   if (tree.nodes.empty()) return 0.0;
-  auto area = [](const HostNode& h) {
+  auto empty = [](const HostNode& h) { return h.mn[0] > h.mx[0] || h.mn[1] > h.mx[1] || h.mn[2] > h.mx[2]; };   // (nothing active below)
+  auto area = [&](const HostNode& h) {
+    if (empty(h)) return 0.0;
     const double x = (double)h.mx[0] - (double)h.mn[0], y = (double)h.mx[1] - (double)h.mn[1], z = (double)h.mx[2] - (double)h.mn[2];
     return 2.0 * (x * y + y * z + z * x);
   };
+  if (empty(tree.nodes[0])) return 0.0;
   const double root = area(tree.nodes[0]);
   double cost = 0.0;
   for (const HostNode& h : tree.nodes) cost += (h.l == h.r ? (double)h.size : 1.0) * (area(h) / root);

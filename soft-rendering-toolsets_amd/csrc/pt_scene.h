@@ -167,6 +167,10 @@ struct BuiltScene {
   // srt_pt_set_dynamic_lights: check_repose_list / check_mesh_update admit area lights, and the apply_* functions keep the light
   // tables true (light_record, light_area_term, write_light_mesh below).  build_scene keeps the switch of the scene it replaces.
   bool dynamic_lights = false;
+  // srt_pt_set_active: one byte per object in insertion order, 1 = active.  build_scene sets every one.  An inactive object keeps
+  // its record and its posed box; only the box the BVH<Object> folds for it is BBox() (effective_boxes), which no ray without a
+  // NaN component passes.  The topology never depends on the table: every build is over the posed boxes of all objects.
+  std::vector<uint8_t> active;
 };
 
 // What srt_pt_repose derives for new poses of a committed scene, built next to it: the BVH<Object> and everything that follows
@@ -316,8 +320,34 @@ struct TopRefit {
 void top_refit_boxes(const HostBVH& tree, const float* posed_boxes6, std::vector<float>* boxes6);
 std::string prepare_top_refit(const BuiltScene& built, const uint32_t* objects, const Mat4* trans, uint32_t n, TopRefit* out);
 void apply_top_refit(BuiltScene* built, TopRefit* refit);
+// srt_pt_set_active, the definition.  effective_boxes: the boxes the BVH<Object>'s leaves fold - posed6 (six floats per object by
+// insertion index: Object::bbox) with BBox(), min = +FLT_MAX and max = -FLT_MAX, in the place of every inactive object's.
+// posed_boxes: Object::bbox of every object from the scene's own transforms and object-space boxes.  write_top_boxes: the one place
+// that writes boxes (six floats per node) into the BVH<Object> - the host tree, flat.nodes[0 .. tlas_nodes) and flat.wave_tlas; links,
+// references and counts stay.  write_top_counts: the number of objects a leaf of the BVH<Object> holds FOR THE WALKS - the count
+// word of its flattened node and the l_cnt / r_cnt of the sweep record above it: the leaf's size, or 0 while every object in it is
+// inactive.  The host tree (what srt_pt_dump_bvh shows) keeps its sizes.  An empty box alone does not hide a leaf: find_closest_hit
+// visits the child whose box was MISSED whenever the other child returns a hit farther than ray.dist_bounds.x, because cur_far_t
+// starts as ray.dist_bounds (student/bvh.inl:191-192, 216) - so a hidden leaf is also left without primitives, which the walks take
+// as they take the empty leaves a build can produce (a leaf holds 0 or 1).  mask_top: top_refit_boxes over
+// effective_boxes(posed_boxes), written by write_top_boxes, then write_top_counts - what apply_set_active runs, and what every call
+// that replaces the BVH<Object> (apply_repose, apply_mesh_update, apply_mesh_refit) ends with while any_inactive(); with every
+// object active those calls run no extra fold.
+// check_active_list: "" or why the n listed objects cannot be switched - *unsupported: the scene has no BVH<Object> to hide an
+// object from (committed without BVHs) or its root is a leaf (find_closest_hit tests children only, never the root's own box);
+// otherwise a bad argument: out of range, a duplicate, an emissive object (the light list would go on sampling it).
+// apply_set_active: the listed flags into the table (non-zero: active); false, and nothing written, when no flag changes.
+bool any_inactive(const BuiltScene& built);
+void effective_boxes(const BuiltScene& built, std::vector<float>* posed6);
+void posed_boxes(const BuiltScene& built, std::vector<float>* posed6);
+void write_top_boxes(BuiltScene* built, const std::vector<float>& boxes6);
+void write_top_counts(BuiltScene* built);
+void mask_top(BuiltScene* built);
+std::string check_active_list(const BuiltScene& built, const uint32_t* objects, uint32_t n, bool* unsupported);
+bool apply_set_active(BuiltScene* built, const uint32_t* objects, const uint8_t* active, uint32_t n);
 // SAH cost of a BVH (what a caller compares before and after refits to decide when to rebuild), in double from the node boxes:
 // sum over interior nodes of SA(n) / SA(root) + sum over leaves of size(n) * SA(n) / SA(root), SA = 2 (xy + yz + zx) of the extents.
+// A node whose box is empty (mn > mx on an axis: nothing active below it) contributes 0, and an empty root gives cost 0.
 double tree_cost(const HostBVH& tree);
 
 Camera make_camera(const float iview[16], float vert_fov_deg, float aspect_ratio);

@@ -130,7 +130,7 @@ void discard_pending(srt_pt* pt) {
   }
   if (!pt->top.pending) return;
   if (hipSetDevice(pt->device) == hipSuccess) (void)hipEventSynchronize(pt->top.event);
-  pt->top.refits += pt->top.pending;                      // (they ran; only their read-back is not worth making any more)
+  pt->top.refits += pt->top.pending - pt->top.pending_active;   // (they ran; only their read-back is not worth making any more)
   pt->top.forget_pending();
 }
 

@@ -59,13 +59,20 @@ int ensure_pose_tables(srt_pt* pt, hipStream_t s, const char* what, uint64_t* by
   const uint32_t nobj = (uint32_t)pt->built.inputs.size();
   const size_t room = nobj ? nobj : 1;
   pt->pose.drop();
-  if (pt->pose.d_records.ensure(room) || pt->pose.d_local_boxes.ensure(room * 6) || pt->pose.d_posed_boxes.ensure(room * 6)) {
+  if (pt->pose.d_records.ensure(room) || pt->pose.d_local_boxes.ensure(room * 6) || pt->pose.d_posed_boxes.ensure(room * 6) || pt->pose.d_active.ensure(room)) {
     (void)hipGetLastError();
     return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
   }
   // (blocking copy, then kernels on `s` that read what the last commit or repose left in d_objects: all of it done by now)
   if (nobj) SRT_HIP(hipMemcpy(pt->pose.d_local_boxes, pt->built.local_boxes.data(), (size_t)nobj * 6 * sizeof(float), hipMemcpyHostToDevice));
   *bytes += (uint64_t)nobj * 6 * sizeof(float);
+  // srt_pt_set_active's table: the host's (1 B per object up) while an object is inactive, otherwise a fill on the device
+  if (nobj && any_inactive(pt->built)) {
+    SRT_HIP(hipMemcpy(pt->pose.d_active, pt->built.active.data(), nobj, hipMemcpyHostToDevice));
+    *bytes += nobj;
+  } else if (nobj) {
+    SRT_HIP(hipMemsetAsync(pt->pose.d_active, 1, nobj, s));
+  }
   launch_pose_tables(s, pt->d_objects, nobj, pt->built.flat.tlas_nodes, pt->pose.d_records, pt->pose.d_local_boxes, pt->pose.d_posed_boxes);
   pt->pose.valid = true;
   return SRT_OK;
@@ -110,6 +117,98 @@ int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n) {
   return upload_listed_lights(pt, objects, n);
 }
 
+// What the device forms of srt_pt_repose_refit and srt_pt_set_active share.
+// A HIP failure after the first enqueue may leave tables, lists or live arrays half written: the scene is no longer committed, what was
+// pending is forgotten (settle() has no record to bring up to date) and the tables go; the scene has to be committed again.
+int top_broken(srt_pt* pt, int status) {
+  pt->committed = false;
+  if (hipSetDevice(pt->device) == hipSuccess) (void)hipDeviceSynchronize();
+  (void)hipGetLastError();
+  pt->top.forget_pending();
+  pt->pose.drop();
+  pt->top.drop_tables();
+  return status;
+}
+int top_hip_broken(srt_pt* pt, const char* what, hipError_t e, const char* step) {
+  return top_broken(pt, srt::fail(SRT_ERR_HIP, "%s: %s failed (%s); the scene has to be committed again", what, step, hipGetErrorString(e)));
+}
+
+// First call after a commit or after a call that replaced the BVH<Object> (blocking, counted once): the pose tables as
+// srt_pt_repose_device makes them (24 B per object up), the tree's refit tables (about 28 B per object up) and the slot of
+// every object (a kernel).  Nothing is pending then - every call that drops these tables settles first.
+int ensure_top_tables(srt_pt* pt, hipStream_t s, const char* what) {
+  int st;
+  if ((st = ensure_pose_tables(pt, s, what, &pt->bytes_uploaded))) return st;
+  if (!pt->built.flat.use_bvh || pt->top.have_tables) return SRT_OK;
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  pt->top.drop_tables();
+  RefitTables fresh;
+  if ((st = make_refit_tables(pt->built.tlas, what, UINT32_MAX, &fresh)) != SRT_OK) return st;
+  pt->top.tables = std::move(fresh);
+  pt->top.have_tables = true;
+  pt->bytes_uploaded += pt->top.tables.uncounted_bytes;
+  pt->top.tables.uncounted_bytes = 0;
+  if (pt->top.d_slot_of.ensure(nobj ? nobj : 1)) {
+    (void)hipGetLastError();
+    pt->top.drop_tables();
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+  }
+  launch_top_slots(s, pt->top.tables.d_prim, nobj, pt->top.d_slot_of);
+  return SRT_OK;
+}
+
+// The list (4 B per listed object, 8 B more per listed light) into pose.d_list, through pinned memory so that the copy is only
+// enqueued - unless the device holds this very list already.
+int stage_top_list(srt_pt* pt, hipStream_t s, const char* what, const uint32_t* objects, uint32_t n) {
+  if (!n || (pt->top.list_valid && pt->top.list.size() == n && std::memcmp(pt->top.list.data(), objects, (size_t)n * 4) == 0)) return SRT_OK;
+  int st;
+  hipError_t he;
+  const ListedLights lights = listed_lights(pt->built, objects, n);
+  pt->top.forget_list();
+  // (growing one of these arrays frees the old one, which waits for what reads it: first calls and longer lists only)
+  if ((st = pt->pose.d_list.ensure(n)) || (st = pt->pose.d_out.ensure(n)) || (!lights.pairs.empty() && (st = pt->pose.d_light_list.ensure(lights.pairs.size()))))
+    return top_broken(pt, st);
+  srt_pt::TopLevel::PinnedList* pl = nullptr;
+  if ((st = pinned_list(pt, (size_t)n + lights.pairs.size(), &pl)) != SRT_OK) return top_broken(pt, st);
+  uint32_t* const h = pl->h;
+  std::memcpy(h, objects, (size_t)n * 4);
+  if (!lights.pairs.empty()) std::memcpy(h + n, lights.pairs.data(), lights.pairs.size() * 4);
+  if ((he = hipMemcpyAsync(pt->pose.d_list, h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return top_hip_broken(pt, what, he, "the copy of the list");
+  if (!lights.pairs.empty() && (he = hipMemcpyAsync(pt->pose.d_light_list, h + n, lights.pairs.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return top_hip_broken(pt, what, he, "the copy of the light list");
+  if ((he = hipEventRecord(pl->done, s)) != hipSuccess) return top_hip_broken(pt, what, he, "hipEventRecord");
+  pt->bytes_uploaded += (uint64_t)n * 4 + lights.pairs.size() * 4;
+  pt->top.list.assign(objects, objects + n);
+  pt->top.lights = (uint32_t)(lights.pairs.size() / 2);
+  pt->top.light_max_ntri = lights.max_ntri;
+  pt->top.list_valid = true;
+  return SRT_OK;
+}
+
+// The leaves from the effective boxes (the posed boxes, BBox() for what the active table switches off), the levels, the live boxes.
+void enqueue_top_boxes(srt_pt* pt, hipStream_t s) {
+  launch_refit_boxes(s, pt->top.tables, pt->pose.d_posed_boxes, pt->top.tables.d_node_boxes, pt->pose.d_active);   // the tree's primitives are the objects: their boxes are the pose tables'
+  launch_refit_write(s, pt->top.tables, pt->top.tables.d_node_boxes, pt->d_nodes, pt->d_wave);
+}
+
+// The launches went in, the event behind them is recorded, and the host's record is behind by one more call until settle().
+int record_pending(srt_pt* pt, hipStream_t s, const char* what) {
+  hipError_t he;
+  if ((he = hipGetLastError()) != hipSuccess) return top_hip_broken(pt, what, he, "a launch");
+  if (pt->top.event.create(hipEventDisableTiming)) return top_hip_broken(pt, what, hipGetLastError(), "hipEventCreate");
+  if ((he = hipEventRecord(pt->top.event, s)) != hipSuccess) return top_hip_broken(pt, what, he, "hipEventRecord");
+  pt->top.pending++;
+  if (pt->top.pending_flag.size() != pt->built.inputs.size()) pt->top.pending_flag.assign(pt->built.inputs.size(), 0);   // (nothing is pending across a commit)
+  return SRT_OK;
+}
+
+// srt_pt_set_active[_device]: the scene layer's verdict on the list, as a status.
+int active_list_usable(srt_pt* pt, const char* what, const uint32_t* objects, uint32_t n) {
+  bool unsupported = false;
+  const std::string refused = check_active_list(pt->built, objects, n, &unsupported);
+  return refused.empty() ? SRT_OK : srt::fail(unsupported ? SRT_ERR_UNSUPPORTED : SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+}
+
 }  // namespace
 
 namespace srt {
@@ -121,20 +220,23 @@ namespace srt {
 int settle_top(srt_pt* pt) {
   if (!pt->top.pending) return SRT_OK;
   if (!pt->committed) { discard_pending(pt); return SRT_OK; }   // (a failure took the scene away: there is no record to bring up to date)
-  const uint64_t calls = pt->top.pending;
+  const uint64_t calls = pt->top.pending, flag_calls = pt->top.pending_active;
   std::vector<uint32_t> objects = pt->top.pending_objects;
   pt->top.forget_pending();
   const uint32_t nobj = (uint32_t)pt->built.inputs.size();
   const bool use_bvh = pt->built.flat.use_bvh;
   std::vector<Object> records(nobj);
+  std::vector<uint8_t> active(flag_calls ? nobj : 0);     // (srt_pt_set_active_device: 1 B per object, only behind such a call)
   TopRefit R;
   if (use_bvh) R.boxes.resize(6 * (size_t)pt->top.tables.nnodes);
   if (hipSetDevice(pt->device) != hipSuccess || hipEventSynchronize(pt->top.event) != hipSuccess ||
       (nobj && hipMemcpy(records.data(), pt->pose.d_records, (size_t)nobj * sizeof(Object), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (!active.empty() && hipMemcpy(active.data(), pt->pose.d_active, active.size(), hipMemcpyDeviceToHost) != hipSuccess) ||
       (!R.boxes.empty() && hipMemcpy(R.boxes.data(), pt->top.tables.d_node_boxes, R.boxes.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
     pt->committed = false;
     return srt::fail(SRT_ERR_HIP, "settling srt_pt_repose_refit_device: %s; the scene has to be committed again", hipGetErrorString(hipGetLastError()));
   }
+  if (!active.empty()) pt->built.active.swap(active);     // (the boxes read back are the masked fold's already)
   for (uint32_t i : objects) {                            // (every object once: top.pending_flag)
     R.listed.push_back(i);
     R.trans.push_back(records[i].trans);
@@ -142,7 +244,8 @@ int settle_top(srt_pt* pt) {
     R.has_trans.push_back(records[i].has_trans);
   }
   apply_top_refit(&pt->built, &R);
-  pt->top.refits += calls;
+  if (flag_calls) write_top_counts(&pt->built);           // (what launch_top_counts left in the live nodes and sweep records)
+  pt->top.refits += calls - flag_calls;
   return SRT_OK;
 }
 
@@ -316,85 +419,71 @@ int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects
     return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the poses are computed on the device only; this context is host-only (srt_pt_repose_refit takes host matrices)", what);
   SRT_HIP(hipSetDevice(pt->device));
   hipStream_t s = (hipStream_t)stream;
-  const FlatScene& F = pt->built.flat;
-  const bool use_bvh = F.use_bvh;
+  const bool use_bvh = pt->built.flat.use_bvh;
   const uint32_t nobj = (uint32_t)pt->built.inputs.size();
   int st;
-  // First call after a commit or after a call that replaced the BVH<Object> (blocking, counted once): the pose tables as
-  // srt_pt_repose_device makes them (24 B per object up), the tree's refit tables (about 28 B per object up) and the slot of
-  // every object (a kernel).  Nothing is pending then - every call that drops these tables settles first.
-  if ((st = ensure_pose_tables(pt, s, what, &pt->bytes_uploaded))) return st;
-  if (use_bvh && !pt->top.have_tables) {
-    pt->top.drop_tables();
-    RefitTables fresh;
-    if ((st = make_refit_tables(pt->built.tlas, what, UINT32_MAX, &fresh)) != SRT_OK) return st;
-    pt->top.tables = std::move(fresh);
-    pt->top.have_tables = true;
-    pt->bytes_uploaded += pt->top.tables.uncounted_bytes;
-    pt->top.tables.uncounted_bytes = 0;
-    if (pt->top.d_slot_of.ensure(nobj ? nobj : 1)) {
-      (void)hipGetLastError();
-      pt->top.drop_tables();
-      return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
-    }
-    launch_top_slots(s, pt->top.tables.d_prim, nobj, pt->top.d_slot_of);
-  }
-  // A HIP failure from here on may leave tables, lists or live arrays half written: the scene is no longer committed, what was
-  // pending is forgotten (settle() has no record to bring up to date) and the tables go; the scene has to be committed again.
-  auto broken = [&](int status) {
-    pt->committed = false;
-    if (hipSetDevice(pt->device) == hipSuccess) (void)hipDeviceSynchronize();
-    (void)hipGetLastError();
-    pt->top.forget_pending();
-    pt->pose.drop();
-    pt->top.drop_tables();
-    return status;
-  };
-  auto hip_broken = [&](hipError_t e, const char* step) { return broken(srt::fail(SRT_ERR_HIP, "%s: %s failed (%s); the scene has to be committed again", what, step, hipGetErrorString(e))); };
-  hipError_t he;
-  // The list (4 B per listed object, 8 B more per listed light), through pinned memory so that the copy is only enqueued - unless
-  // the device holds this very list already.
-  if (n && !(pt->top.list_valid && pt->top.list.size() == n && std::memcmp(pt->top.list.data(), objects, (size_t)n * 4) == 0)) {
-    const ListedLights lights = listed_lights(pt->built, objects, n);
-    pt->top.forget_list();
-    // (growing one of these arrays frees the old one, which waits for what reads it: first calls and longer lists only)
-    if ((st = pt->pose.d_list.ensure(n)) || (st = pt->pose.d_out.ensure(n)) || (!lights.pairs.empty() && (st = pt->pose.d_light_list.ensure(lights.pairs.size()))))
-      return broken(st);
-    srt_pt::TopLevel::PinnedList* pl = nullptr;
-    if ((st = pinned_list(pt, (size_t)n + lights.pairs.size(), &pl)) != SRT_OK) return broken(st);
-    uint32_t* const h = pl->h;
-    std::memcpy(h, objects, (size_t)n * 4);
-    if (!lights.pairs.empty()) std::memcpy(h + n, lights.pairs.data(), lights.pairs.size() * 4);
-    if ((he = hipMemcpyAsync(pt->pose.d_list, h, (size_t)n * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_broken(he, "the copy of the list");
-    if (!lights.pairs.empty() && (he = hipMemcpyAsync(pt->pose.d_light_list, h + n, lights.pairs.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-      return hip_broken(he, "the copy of the light list");
-    if ((he = hipEventRecord(pl->done, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
-    pt->bytes_uploaded += (uint64_t)n * 4 + lights.pairs.size() * 4;
-    pt->top.list.assign(objects, objects + n);
-    pt->top.lights = (uint32_t)(lights.pairs.size() / 2);
-    pt->top.light_max_ntri = lights.max_ntri;
-    pt->top.list_valid = true;
-  }
-  if (pt->top.event.create(hipEventDisableTiming)) return hip_broken(hipGetLastError(), "hipEventCreate");
-  // Everything below only enqueues on `s`: the poses, the leaves through the tree's primitive order, the levels deepest first, the
-  // boxes into the live nodes and sweep records, the listed records' matrices, the listed lights.  No verdict is needed: depth,
-  // counts, order, kernel form and stack sizes are those of the committed tree.
+  if ((st = ensure_top_tables(pt, s, what)) || (st = stage_top_list(pt, s, what, objects, n))) return st;
+  // Everything below only enqueues on `s`: the poses, the leaves through the tree's primitive order (an inactive object's as
+  // BBox(): srt_pt_set_active), the levels deepest first, the boxes into the live nodes and sweep records, the listed records'
+  // matrices, the listed lights.  No verdict is needed: depth, counts, order, kernel form and stack sizes are those of the committed tree.
   if (n) launch_pose_objects(s, pt->pose.d_list, d_trans, n, nobj, pt->pose.d_local_boxes, pt->pose.d_out, pt->pose.d_records, pt->pose.d_posed_boxes);
-  if (use_bvh) {
-    launch_refit_boxes(s, pt->top.tables, pt->pose.d_posed_boxes, pt->top.tables.d_node_boxes);   // the tree's primitives are the objects: their boxes are the pose tables'
-    launch_refit_write(s, pt->top.tables, pt->top.tables.d_node_boxes, pt->d_nodes, pt->d_wave);
-  }
+  if (use_bvh) enqueue_top_boxes(pt, s);
   if (n) {
     launch_top_objects(s, pt->pose.d_list, n, nobj, use_bvh ? pt->top.d_slot_of : nullptr, pt->pose.d_records, pt->d_objects);
     if (pt->top.lights) launch_listed_lights(pt, s, pt->top.lights, pt->top.light_max_ntri, n);
   }
-  if ((he = hipGetLastError()) != hipSuccess) return hip_broken(he, "a launch");
-  if ((he = hipEventRecord(pt->top.event, s)) != hipSuccess) return hip_broken(he, "hipEventRecord");
-  // the host's record is behind from here until settle(): one more call, and the objects it listed that no pending call had listed
-  pt->top.pending++;
-  if (pt->top.pending_flag.size() != nobj) pt->top.pending_flag.assign(nobj, 0);   // (nothing is pending across a commit)
+  if ((st = record_pending(pt, s, what))) return st;
+  // the objects this call listed that no pending call had listed
   for (uint32_t k = 0; k < n; k++)
     if (!pt->top.pending_flag[objects[k]]) { pt->top.pending_flag[objects[k]] = 1; pt->top.pending_objects.push_back(objects[k]); }
+  return SRT_OK;
+}
+
+int srt_pt_set_active(srt_pt* pt, const uint32_t* objects, const uint8_t* active, uint32_t n) {
+  const char* what = "srt_pt_set_active";
+  if (!pt || (n && (!objects || !active))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st;
+  if ((st = need_committed(pt, what))) return st;
+  if ((st = active_list_usable(pt, what, objects, n))) return st;
+  bool changes = false;
+  for (uint32_t k = 0; k < n && !changes; k++) changes = pt->built.active[objects[k]] != (active[k] ? 1 : 0);
+  if (!changes) return SRT_OK;                            // nothing is written and nothing goes up
+  // nothing fails on the host side from here on: the table and the boxes change in place
+  if (pt->device >= 0) SRT_HIP(quiesce(pt));
+  apply_set_active(&pt->built, objects, active, n);
+  if (pt->device < 0) return SRT_OK;
+  pt->pose.drop();                                        // (its copy of the table is behind; the tree's tables stay: the tree did)
+  return written(pt, write_top_refit(pt, objects, 0));    // the top-level nodes and the sweep records, no object record
+}
+
+int srt_pt_set_active_device(srt_pt* pt, void* stream, const uint32_t* objects, const uint8_t* d_active, uint32_t n) {
+  const char* what = "srt_pt_set_active_device";
+  if (!pt || (n && (!objects || !d_active))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (!pt->committed) return not_committed(what);         // (no settle(): this call only adds to what is pending)
+  int st;
+  if ((st = active_list_usable(pt, what, objects, n))) return st;
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the flags are read on the device only; this context is host-only (srt_pt_set_active takes host flags)", what);
+  SRT_HIP(hipSetDevice(pt->device));
+  hipStream_t s = (hipStream_t)stream;
+  if ((st = ensure_top_tables(pt, s, what)) || (st = stage_top_list(pt, s, what, objects, n))) return st;
+  // only enqueues on `s`: the listed flags into the table, then the refit's own stages with the table as the leaf stage's mask
+  const uint32_t nobj = (uint32_t)pt->built.inputs.size();
+  launch_active_scatter(s, pt->pose.d_list, d_active, n, nobj, pt->pose.d_active);
+  enqueue_top_boxes(pt, s);
+  launch_top_counts(s, pt->top.tables, pt->pose.d_active, nobj, pt->d_nodes, pt->d_wave);   // a hidden leaf holds nothing for the walks
+  if ((st = record_pending(pt, s, what))) return st;
+  pt->top.pending_active++;
+  return SRT_OK;
+}
+
+int srt_pt_get_active(srt_pt* pt, uint8_t* active_out, uint32_t cap) {
+  if (!pt || (cap && !active_out)) return srt::fail(SRT_ERR_INVALID, "srt_pt_get_active: NULL argument");
+  const int st = need_committed(pt, "srt_pt_get_active");
+  if (st != SRT_OK) return st;
+  const size_t nobj = pt->built.active.size();
+  if (cap < nobj) return srt::fail(SRT_ERR_INVALID, "srt_pt_get_active: room for %u flags, the scene has %zu objects", cap, nobj);
+  if (nobj) std::memcpy(active_out, pt->built.active.data(), nobj);
   return SRT_OK;
 }
 
