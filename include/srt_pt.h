@@ -431,10 +431,52 @@ int srt_pt_refit_mesh(srt_pt* pt, uint32_t object, const float* positions, const
  * stream), which the call synchronises where the host needs a verdict (the arrays come back once, 24 B per vertex, and are
  * checked there; the root box comes back with the node boxes) and before it returns. */
 int srt_pt_refit_mesh_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts);
+/* New vertex arrays for one mesh with BOTH trees kept: srt_pt_refit_mesh without the rebuild of the BVH<Object>.  Arguments,
+ * preconditions, refusals and their messages are srt_pt_refit_mesh's, a non-finite position coordinate (SRT_ERR_INVALID) included.
+ * The mesh's BVH<Triangle>, its triangle, normal and packed records and its light-list copy change exactly as srt_pt_refit_mesh
+ * changes them, and the object-space box of the mesh and of each of its instances becomes the new root box.  The BVH<Object> keeps
+ * its links {start, size, l, r} and its primitive order and takes new boxes as in srt_pt_repose_refit: a leaf's is the
+ * BBox::enclose fold, from BBox(), of Object::bbox (rays/object.h:51-55) of its objects - every object's from its unchanged transform
+ * and its object-space box, BBox() for what srt_pt_set_active switched off - an interior node's the enclose of its left and then its
+ * right child's (student/bvh.inl:73-75, 119-123).  No link, order, count, slot, ordinal, lazy table or depth changes anywhere, so the
+ * call cannot fail for a tree's sake: the scene is what srt_pt_refit_mesh would leave if its last step were srt_pt_repose_refit of
+ * the mesh and its instances with their current transforms in place of the rebuild.  Results are those of the reference's
+ * BVH<Primitive>::hit (student/bvh.inl:166-276) on those trees; srt_pt_mesh_tree_cost and srt_pt_scene_tree_cost tell when a
+ * rebuild (srt_pt_update_mesh, srt_pt_repose) pays.  Blocks, and settles first.  A host-only context (device = -1) runs the
+ * definition (prepare_mesh_refit_inplace / apply_mesh_refit_inplace, pt_scene.cpp) and nothing else.  A device context uploads only
+ * what changed: the vertices into the staging (24 B each), the top-level nodes and sweep records (32 B and 64 B each); the mesh's
+ * boxes and records are written by the kernels of srt_pt_refit_mesh, whose tables it shares.  No table of object order goes up and
+ * the refit tables of both trees stay.  With a scene committed with use_bvh == 0 there is no tree and the call does what
+ * srt_pt_update_mesh does.  srt_pt_refit_count counts it. */
+int srt_pt_refit_mesh_inplace(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts);
+/* The same from two device arrays, ENQUEUE-ONLY under the contract written at srt_pt_repose_refit_device: the host validates first
+ * (srt_pt_update_mesh's refusals, status codes and texts; a host-only context validates and then returns SRT_ERR_UNSUPPORTED) and
+ * then only enqueues on `stream` (a hipStream_t; NULL: the null stream) - no wait, no synchronisation, nothing copied to the host.
+ * In order: the two arrays are copied device-to-device into buffers the context owns for that mesh (24 B per vertex), so the
+ * caller's arrays - and a skin's staging - may be overwritten as soon as work enqueued behind the call may run; the triangle boxes,
+ * the leaves and the levels of the mesh's tree (pt_mesh_update.hip); its live nodes and interior records; its triangle records in
+ * the kept order; for an emissive mesh under srt_pt_set_dynamic_lights its light tables (pt_light_update.hip); the link (pt_pose.hip,
+ * one lane per member of the mesh's family - the mesh and its instances): the new root box as the member's object-space box and
+ * Object::bbox of it under the member's current transform, in the tables srt_pt_repose_refit_device keeps; and that call's own
+ * stages over them - the leaf stage masked by the active table, the levels, the live top-level nodes and sweep records.  Blocking
+ * work only where srt_pt_repose_refit_device has it: the first call after a commit or after a call that replaced a tree (its
+ * tables, the mesh's refit tables, the family - 4 B per member - and the vertex buffers; counted once), so a steady-state call
+ * uploads nothing.  Ordering is that call's: work enqueued behind it on `stream` sees the new scene, other streams are the
+ * caller's to order with events.  The two calls share their tables: a srt_pt_repose_refit_device behind this call poses the new boxes.
+ * NON-FINITE VERTICES ARE NOT REFUSED by this form - there is no verdict to wait for: the scene holds what the kernels computed,
+ * and the host's record takes the vertices and the node boxes as read back.  A caller who wants the check uses the blocking forms
+ * (srt_pt_refit_mesh_inplace, srt_pt_refit_mesh[_device]).  The host's record lags until the next call that is not enqueue-only
+ * settles it: one wait, and per mesh touched - however many calls are pending - one read-back of 24 B per vertex and 24 B per node
+ * (srt_pt_mesh_refit_pending, srt_pt_debug.h); every pending call is pending for srt_pt_top_refit_pending too, and counted by
+ * srt_pt_refit_count, not srt_pt_top_refit_count.  A HIP error after the first enqueue or while settling is SRT_ERR_HIP and leaves
+ * the context without a committed scene and with nothing pending.  With a scene committed with use_bvh == 0 the call does what
+ * srt_pt_refit_mesh_device does, and BLOCKS as it does. */
+int srt_pt_refit_mesh_inplace_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts);
 /* SAH cost of the mesh's current BVH<Triangle>, on the host in double from the host node boxes: the sum over interior nodes of
  * SA(n) / SA(root) plus the sum over leaves of size(n) * SA(n) / SA(root), SA = 2 (xy + yz + zx) of a box's extents.  What a
  * caller compares before and after refits to decide when to rebuild with srt_pt_update_mesh.  Refusals as for srt_pt_refit_mesh;
- * SRT_ERR_UNSUPPORTED for a scene committed with use_bvh == 0. */
+ * SRT_ERR_UNSUPPORTED for a scene committed with use_bvh == 0.  Settles first, so the cost behind enqueue-only in-place refits is
+ * the refitted tree's. */
 int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost);
 
 /* ---- Skinning: Skeleton::find_joints and Skeleton::skin on the device ----
@@ -523,6 +565,12 @@ int srt_pt_skin_posed_device(srt_pt_skin* skin, void* stream, float t, float* d_
 int srt_pt_skin_vertices_at_device(srt_pt_skin* skin, void* stream, float t, int flat_normals, float* d_positions_out, float* d_normals_out);
 int srt_pt_skin_pose_at(srt_pt_skin* skin, void* stream, float t, int flat_normals);
 int srt_pt_skin_pose_refit_at(srt_pt_skin* skin, void* stream, float t, int flat_normals);
+/* srt_pt_skin_pose_refit and srt_pt_skin_pose_refit_at with srt_pt_refit_mesh_inplace_device in place of the refit: skin -> staging ->
+ * both trees refitted, ENQUEUE-ONLY as that call is (it copies the staging, so the next pose may overwrite it at once).  With a rig
+ * a frame is one float and uploads nothing; from `posed` it uploads 64 B per joint, through pinned staging of the skin's own (one
+ * buffer per copy still on its way), so that copy too is only enqueued and `posed` is not read after the call returns. */
+int srt_pt_skin_pose_inplace(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
+int srt_pt_skin_pose_inplace_at(srt_pt_skin* skin, void* stream, float t, int flat_normals);
 /* Every call on a skin but destroy and counts returns SRT_ERR_STATE once its context's scene was begun or committed again (the
  * skin is stale: destroy it, create another), and SRT_ERR_INVALID for a NULL argument. */
 /* ---- Timelines: the Animate mode's keyframes evaluated on the device ----

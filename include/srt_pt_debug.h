@@ -69,7 +69,8 @@ int srt_pt_counters(srt_pt* pt, uint64_t out[8]);
  * object order - the records its kernel writes on the device are not uploads.  A refused update adds nothing to the builds. */
 int srt_pt_scene_counts(srt_pt* pt, uint64_t out[8]);
 /* The trailing counter of the same family, in a call of its own so that out[8] above keeps its size for existing callers: the
- * successful srt_pt_refit_mesh[_device] / srt_pt_skin_pose_refit calls since creation.  A refit adds nothing to the builds and
+ * successful srt_pt_refit_mesh[_device] / srt_pt_skin_pose_refit calls since creation, and the srt_pt_refit_mesh_inplace[_device] /
+ * srt_pt_skin_pose_inplace calls (settles first, so the enqueue-only ones are counted).  A refit adds nothing to the builds and
  * nothing to the triangle-class upload figure (its kernels write the records); to the uploads it adds the vertex arrays (host
  * form), the BVH<Object> nodes and the tables of object order, and at a mesh's first refit its refit tables (4 B per triangle,
  * 8 B per node and per interior record, the level offsets).  A refused refit adds nothing to any figure: the vertices it had
@@ -80,8 +81,12 @@ int srt_pt_refit_count(srt_pt* pt, uint64_t* refits);
  * triangle-class figure; to the uploads it adds what srt_pt_repose_refit[_device] document. */
 int srt_pt_top_refit_count(srt_pt* pt, uint64_t* refits);
 /* What the host's record lags by, WITHOUT settling: out[0] = the srt_pt_repose_refit_device calls not applied yet, out[1] = the
- * entries of the set of objects they listed - at most the scene's object count, however many calls are pending. */
+ * entries of the set of objects they listed - at most the scene's object count, however many calls are pending.  (A pending
+ * srt_pt_refit_mesh_inplace_device call refits the BVH<Object> too: it is counted in out[0] and lists no object.) */
 int srt_pt_top_refit_pending(srt_pt* pt, uint64_t out[2]);
+/* The same for srt_pt_refit_mesh_inplace_device, WITHOUT settling: out[0] = the calls not applied yet, out[1] = the meshes they
+ * touched - at most one entry per mesh, however many calls are pending. */
+int srt_pt_mesh_refit_pending(srt_pt* pt, uint64_t out[2]);
 /* The area-light tables of the committed scene (what srt_pt_set_dynamic_lights keeps true).  Returns the number of lights, or a
  * negative status.  Per light li < cap_lights: heads[4 li ..] = {has_trans, first light triangle (tri_base - first light triangle
  * of the scene), triangle count, insertion index of the object}, mats[64 li ..] = trans, itrans, pdfT, pdfiT.  Per light triangle

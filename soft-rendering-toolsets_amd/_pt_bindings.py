@@ -64,6 +64,11 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_refit_mesh.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_refit_mesh_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_skin_pose_refit.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
+    lib.srt_pt_refit_mesh_inplace.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_refit_mesh_inplace_device.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_mesh_refit_pending.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_skin_pose_inplace.argtypes = [c_void_p, c_void_p, c_void_p, c_int]
+    lib.srt_pt_skin_pose_inplace_at.argtypes = [c_void_p, c_void_p, c_float, c_int]
     lib.srt_pt_repose_refit.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_repose_refit_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
     lib.srt_pt_scene_tree_cost.argtypes = [c_void_p, POINTER(ctypes.c_double)]
@@ -264,6 +269,17 @@ class Skin:
         posed = self._posed(posed)
         self._check(self._lib, self._lib.srt_pt_skin_pose_refit(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals))))
 
+    def pose_inplace(self, posed, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose_inplace: skin, then srt_pt_refit_mesh_inplace_device with the result - both trees kept, only enqueued on
+        `stream`: no wait, no read-back (64 B per joint go up).  The host's record settles as after repose_refit_device."""
+        posed = self._posed(posed)
+        self._check(self._lib, self._lib.srt_pt_skin_pose_inplace(self._h, c_void_p(stream), _p(posed), int(bool(flat_normals))))
+
+    def pose_inplace_at(self, t: float, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose_inplace_at: pose_inplace() with the matrices of time t computed on the device from the rig - a frame is
+        one float, nothing goes up and nothing is waited for."""
+        self._check(self._lib, self._lib.srt_pt_skin_pose_inplace_at(self._h, c_void_p(stream), float(t), int(bool(flat_normals))))
+
     def set_rig(self, parent, base, rest_pose, knot_offsets, knot_times, knot_quats) -> None:
         """srt_pt_skin_set_rig: the hierarchy (parent[j] < j or -1, the joints in the skin's order), Skeleton::base_pos, the rest pose
         (3 Euler angles in degrees per joint) and the joints' keys as CSR (knot_offsets[njoints + 1], times, xyzw quaternions).
@@ -334,6 +350,24 @@ class SkinGroup:
     def pose_refit(self, posed, flat_normals: bool = False) -> None:
         for k in self.skins:
             k.pose_refit(posed, flat_normals)
+
+    def _settle(self) -> None:
+        for k in self.skins:
+            k._check(k._lib, k._lib.srt_pt_sync(k._pt._ctx))
+
+    def pose_inplace(self, posed, flat_normals: bool = False) -> None:
+        """Skin.pose_inplace on every rank.  The group's lanes render on streams of their own, which nothing orders behind the
+        pose's stream: every member is settled (srt_pt_sync) before this returns, as PathtracerGroup.set_active_device does and for
+        the same reason.  A caller that wants the enqueue-only loop drives the members' skins and streams itself."""
+        for k in self.skins:
+            k.pose_inplace(posed, flat_normals)
+        self._settle()
+
+    def pose_inplace_at(self, t: float, flat_normals: bool = False) -> None:
+        """Skin.pose_inplace_at on every rank with the same t; every member is settled before this returns (see pose_inplace)."""
+        for k in self.skins:
+            k.pose_inplace_at(t, flat_normals)
+        self._settle()
 
     def set_rig(self, parent, base, rest_pose, knot_offsets, knot_times, knot_quats) -> None:
         for k in self.skins:
@@ -746,6 +780,27 @@ class Pathtracer:
     def refit_mesh_device(self, index: int, d_pos_ptr: int, d_nrm_ptr: int, nverts: int, stream: int = 0) -> None:
         """srt_pt_refit_mesh_device: the same from two device arrays of nverts * 3 floats (e.g. tensor.data_ptr())."""
         self._check(self._lib, self._lib.srt_pt_refit_mesh_device(self._ctx, c_void_p(stream), int(index), c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr), int(nverts)))
+
+    def refit_mesh_inplace(self, index: int, pos, nrm) -> None:
+        """srt_pt_refit_mesh_inplace: refit_mesh with the BVH<Object> kept as well - it takes new boxes as in repose_refit, nothing is
+        built and no table of object order goes up.  Blocks.  mesh_tree_cost() / scene_tree_cost() tell when a rebuild pays."""
+        pos, nrm = _f32(pos).reshape(-1, 3), _f32(nrm).reshape(-1, 3)
+        if len(pos) != len(nrm):
+            raise ValueError(f"{len(pos)} positions but {len(nrm)} normals")
+        self._check(self._lib, self._lib.srt_pt_refit_mesh_inplace(self._ctx, int(index), _p(pos), _p(nrm), len(pos)))
+
+    def refit_mesh_inplace_device(self, index: int, d_pos_ptr: int, d_nrm_ptr: int, nverts: int, stream: int = 0) -> None:
+        """srt_pt_refit_mesh_inplace_device: the same from two device arrays of nverts * 3 floats, only enqueued on `stream`: no wait,
+        no read-back, and the arrays may be overwritten behind the call.  Non-finite vertices are NOT refused (the blocking forms
+        check).  The host's record settles at the next call that is not enqueue-only (dump_bvh, hit, sync, ...)."""
+        self._check(self._lib, self._lib.srt_pt_refit_mesh_inplace_device(self._ctx, c_void_p(stream), int(index), c_void_p(d_pos_ptr), c_void_p(d_nrm_ptr),
+                                                                          int(nverts)))
+
+    def mesh_refit_pending(self):
+        """srt_pt_mesh_refit_pending: (refit_mesh_inplace_device calls the host has not applied yet, meshes they touched); does not settle."""
+        out = np.zeros(2, np.uint64)
+        self._check(self._lib, self._lib.srt_pt_mesh_refit_pending(self._ctx, _p(out)))
+        return int(out[0]), int(out[1])
 
     def mesh_tree_cost(self, index: int) -> float:
         """srt_pt_mesh_tree_cost: SAH cost of the mesh's current BVH<Triangle> - compare before and after refits to decide when to rebuild."""
@@ -1316,6 +1371,22 @@ class PathtracerGroup:
     def refit_mesh(self, index: int, pos, nrm) -> None:
         for m in self.members:
             m.refit_mesh(index, pos, nrm)
+
+    def refit_mesh_inplace(self, index: int, pos, nrm) -> None:
+        for m in self.members:
+            m.refit_mesh_inplace(index, pos, nrm)
+
+    def refit_mesh_inplace_device(self, index: int, d_pos_ptrs, d_nrm_ptrs, nverts: int, stream: int = 0) -> None:
+        """srt_pt_refit_mesh_inplace_device on every rank: one pair of device pointers per rank, as repose_refit_device takes
+        d_trans_ptrs.  The group's lanes render on streams of their own, which nothing orders behind `stream`: every member is settled
+        (srt_pt_sync) before this returns, as set_active_device does and for the same reason."""
+        pp, nn = list(d_pos_ptrs), list(d_nrm_ptrs)
+        if len(pp) != len(self.members) or len(nn) != len(self.members):
+            raise ValueError(f"{len(self.members)} ranks but {len(pp)} position and {len(nn)} normal arrays")
+        for m, p, n in zip(self.members, pp, nn):
+            m.refit_mesh_inplace_device(index, p, n, nverts, stream)
+        for m in self.members:
+            m._check(m._lib, m._lib.srt_pt_sync(m._ctx))
 
     def create_skin(self, index: int, bind_pos, bind_nrm, joints) -> SkinGroup:
         """One skin per rank; SkinGroup.pose poses each rank, as update_mesh updates each."""

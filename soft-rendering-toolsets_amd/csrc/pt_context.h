@@ -115,10 +115,24 @@ struct srt_pt {
     // is rebuilt (srt_pt_update_mesh) or the scene committed again; and the refits so far
     std::map<uint32_t, srt::RefitTables> refit_tables;
     uint64_t refits = 0;
+    // srt_pt_refit_mesh_inplace_device: per mesh refitted that way, as long as its refit tables live, the context's own copy of the
+    // vertex arrays (24 B per vertex: the caller's arrays, and a skin's staging, may be overwritten before the host settles) and its
+    // family - the mesh and its instances by insertion index, one lane each of the link kernel (pt_pose.h).
+    struct Inplace {
+      srt::DeviceBuffer<float> d_pos, d_nrm;
+      srt::DeviceBuffer<uint32_t> d_family; uint32_t nfamily = 0;
+    };
+    std::map<uint32_t, Inplace> inplace;
+    // The host's record lags the device after srt_pt_refit_mesh_inplace_device until settle(), as TopLevel's below does: the calls not
+    // applied yet and the meshes they touched in first-seen order (at most one entry per mesh however many calls are pending).
+    // Every such call refits the BVH<Object> too and is one of top.pending: top.event is the event behind the last of them.
+    uint64_t pending = 0;
+    std::vector<uint32_t> pending_meshes;
+    void forget_pending() { pending = 0; pending_meshes.clear(); }
     // The refit tables of `object` (UINT32_MAX: of every mesh): its tree is about to be replaced.
     void drop_refit_tables(uint32_t object) {
-      if (object == UINT32_MAX) refit_tables.clear();
-      else refit_tables.erase(object);
+      if (object == UINT32_MAX) { refit_tables.clear(); inplace.clear(); }
+      else { refit_tables.erase(object); inplace.erase(object); }
     }
   } mesh;
   // srt_pt_repose_device: what its kernels keep on the device between calls - every object's record by insertion index, its
@@ -159,7 +173,8 @@ struct srt_pt {
     // objects they listed (a flag per object and the objects in first-seen order: at most one entry per object however many calls
     // are pending), and the event recorded behind the last of them.  (ShadingLag below is the same arrangement for the shading tables.)
     // pending_active: those of the pending calls that were srt_pt_set_active_device (they are no refits, and settle() reads the
-    // active table back only behind one of them).
+    // active table back only behind one of them).  mesh.pending of them were srt_pt_refit_mesh_inplace_device calls (counted by
+    // srt_pt_refit_count, not as refits of this tree's poses).
     uint64_t pending = 0, pending_active = 0;
     std::vector<uint8_t> pending_flag;
     std::vector<uint32_t> pending_objects;

@@ -131,6 +131,11 @@ void launch_active_scatter(void* stream, const uint32_t* d_listed, const uint8_t
 // then records).  T: the BVH<Object>'s refit tables.
 struct RefitTables;
 void launch_top_counts(void* stream, const RefitTables& T, const uint8_t* d_table, uint32_t nobj, Node* d_nodes, WaveInterior* d_wave);
+// srt_pt_refit_mesh_inplace_device: one lane per member k < n of a refitted mesh's family (d_family: the mesh and its instances, by
+// insertion index).  Node 0 of d_node_boxes6 (the mesh's refitted boxes) -> d_local_boxes6[6 i ..], and its Object::bbox under the
+// unchanged transform of d_by_index[i] -> d_posed_boxes6[6 i ..].  Nothing a render kernel reads; the top-level refit's stages follow.
+void launch_mesh_link(void* stream, const uint32_t* d_family, uint32_t n, uint32_t nobj, const float* d_node_boxes6, const Object* d_by_index,
+                      float* d_local_boxes6, float* d_posed_boxes6);
 // One lane per particle: d_trans_out[16 k ..] = translate(d_pos[3 k ..]) * scale(scale).
 void launch_particle_transforms(void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out);
 

@@ -164,6 +164,27 @@ __global__ __launch_bounds__(256) void top_record_counts_kernel(const uint2* __r
   if (r & LEAF_BIT) recs[q].r_cnt = r & ~LEAF_BIT;
 }
 
+// srt_pt_refit_mesh_inplace_device, the link between the two trees.  One lane per member of a refitted mesh's family (the mesh and its
+// instances, by insertion index): the mesh's new root box - node 0 of its refitted node boxes - becomes the member's object-space box,
+// and Object::bbox of it under the member's unchanged transform (its record by insertion index) the member's posed box: pose_box
+// when has_trans, the box itself otherwise, as posed_boxes_kernel and pose_object have it.  A family is a handful of lanes; each
+// reads the same 24 B box and its own record's 64 B matrix, and writes 48 B.  No two lanes write one object (the family holds no duplicate).
+__global__ __launch_bounds__(256) void mesh_link_kernel(const uint32_t* __restrict__ family, uint32_t n, uint32_t nobj, const float* __restrict__ node_boxes6,
+                                                        const Object* __restrict__ by_index, float* __restrict__ local6, float* __restrict__ posed6) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t i = family[k];
+  if (i >= nobj) return;                                         // (the family was made on the host from the committed scene)
+  float b[6], t[16];
+  load_box(node_boxes6, 0u, b);
+  store_box(local6, i, b);
+  if (by_index[i].has_trans) {
+    for (int e = 0; e < 16; e++) t[e] = by_index[i].trans.c[e / 4][e % 4];
+    pose_box(t, b);
+  }
+  store_box(posed6, i, b);
+}
+
 __global__ __launch_bounds__(256) void particle_transforms_kernel(const float* __restrict__ pos, uint32_t n, float scale, float* __restrict__ out) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
@@ -217,6 +238,12 @@ void launch_top_counts(void* stream, const RefitTables& T, const uint8_t* d_tabl
   hipStream_t s = (hipStream_t)stream;
   if (T.nleaves) top_leaf_counts_kernel<<<dim3(blocks_for(T.nleaves)), dim3(256), 0, s>>>(T.d_leaves, T.nleaves, T.d_prim, d_table, nobj, T.nnodes, d_nodes);
   if (T.nrec) top_record_counts_kernel<<<dim3(blocks_for(T.nrec)), dim3(256), 0, s>>>(T.d_children, T.nrec, T.nnodes, d_nodes, d_wave);
+}
+
+void launch_mesh_link(void* stream, const uint32_t* d_family, uint32_t n, uint32_t nobj, const float* d_node_boxes6, const Object* d_by_index,
+                      float* d_local_boxes6, float* d_posed_boxes6) {
+  if (!n) return;
+  mesh_link_kernel<<<dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream>>>(d_family, n, nobj, d_node_boxes6, d_by_index, d_local_boxes6, d_posed_boxes6);
 }
 
 void launch_particle_transforms(void* stream, const float* d_pos, uint32_t n, float scale, float* d_trans_out) {

@@ -883,16 +883,16 @@ void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32
     for (int a = 0; a < 3; a++) { (*boxes6)[6 * n + a] = nb[n].mn[a]; (*boxes6)[6 * n + 3 + a] = nb[n].mx[a]; }
 }
 
-std::string prepare_mesh_refit(const BuiltScene& B, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
-                               const float* node_boxes, MeshRefit* out, bool* bad_argument) {
-  *bad_argument = true;
+// What both refits of a mesh start with: the refusals, then the new arrays, the node boxes and every object's object-space box.
+static std::string mesh_refit_head(const BuiltScene& B, uint32_t object, const float* pos, const float* nrm, uint32_t nverts, const float* node_boxes,
+                                   bool refuse_non_finite, MeshRefit* out) {
   const std::string refused = check_mesh_update(B, object, nverts);
   if (!refused.empty()) return refused;
   if (!B.flat.use_bvh) return "the scene was committed without BVHs: there is no tree to refit";
-  for (size_t k = 0; k < 3 * (size_t)nverts; k++)
-    if (!std::isfinite(pos[k]))
-      return "vertex " + std::to_string(k / 3) + " of the new positions has a non-finite coordinate";
-  *bad_argument = false;
+  if (refuse_non_finite)
+    for (size_t k = 0; k < 3 * (size_t)nverts; k++)
+      if (!std::isfinite(pos[k]))
+        return "vertex " + std::to_string(k / 3) + " of the new positions has a non-finite coordinate";
   const uint32_t nobj = (uint32_t)B.inputs.size();
   MeshRefit& R = *out;
   R = MeshRefit();
@@ -907,6 +907,17 @@ std::string prepare_mesh_refit(const BuiltScene& B, uint32_t object, const float
   for (uint32_t i = 0; i < nobj; i++)
     if (i == object || (B.inputs[i].kind == OBJ_MESH && B.inputs[i].source == (int32_t)object))
       for (int a = 0; a < 6; a++) R.local_boxes[6 * (size_t)i + a] = R.boxes[a];
+  return "";
+}
+
+std::string prepare_mesh_refit(const BuiltScene& B, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                               const float* node_boxes, MeshRefit* out, bool* bad_argument) {
+  *bad_argument = true;
+  const std::string refused = mesh_refit_head(B, object, pos, nrm, nverts, node_boxes, true, out);
+  if (!refused.empty()) return refused;
+  *bad_argument = false;
+  const uint32_t nobj = (uint32_t)B.inputs.size();
+  MeshRefit& R = *out;
   std::vector<Mat4> trans(nobj);
   for (uint32_t i = 0; i < nobj; i++) trans[i] = B.inputs[i].trans;
   Top T;
@@ -922,16 +933,15 @@ std::string prepare_mesh_refit(const BuiltScene& B, uint32_t object, const float
   return "";
 }
 
-void apply_mesh_refit(BuiltScene* built, MeshRefit* refit) {
+// The mesh's own half of a refit, in place: the vertex arrays, the object-space boxes, the BVH<Triangle>'s boxes on both sides, the
+// interior records, the triangle records in the kept order and the light-list copy.  (A rebuilt BVH<Object> is in by now: the
+// BVH<Triangle> nodes are written behind it.)
+static void write_mesh_refit(BuiltScene* built, MeshRefit* refit) {
   BuiltScene& B = *built;
   FlatScene& F = B.flat;
   MeshRefit& R = *refit;
   const MeshStore m = B.store[R.object];
   MeshInput& mesh = B.inputs[R.object].mesh;
-  mesh.pos.swap(R.pos);
-  mesh.nrm.swap(R.nrm);
-  B.local_boxes.swap(R.local_boxes);
-  apply_repose(built, &R.top);                     // the BVH<Object> and the tables of object order; the BVH<Triangle> nodes stay behind it
   HostBVH& tree = B.blas[R.object];
   for (size_t n = 0; n < tree.nodes.size(); n++) {
     HostNode& h = tree.nodes[n];
@@ -955,6 +965,45 @@ void apply_mesh_refit(BuiltScene* built, MeshRefit* refit) {
   std::copy(packed.begin(), packed.end(), F.tri_packed.begin() + 9 * (size_t)m.tri_base);
   const int32_t li = light_of(B, R.object);          // an emissive mesh (BuiltScene::dynamic_lights): its light-list copy and LightTri records
   if (li >= 0) write_light_mesh(built, (uint32_t)li, R.object);
+}
+
+void apply_mesh_refit(BuiltScene* built, MeshRefit* refit) {
+  MeshRefit& R = *refit;
+  MeshInput& mesh = built->inputs[R.object].mesh;
+  mesh.pos.swap(R.pos);
+  mesh.nrm.swap(R.nrm);
+  built->local_boxes.swap(R.local_boxes);
+  apply_repose(built, &R.top);                     // the BVH<Object> and the tables of object order; the BVH<Triangle> nodes stay behind it
+  write_mesh_refit(built, refit);
+}
+
+std::string prepare_mesh_refit_inplace(const BuiltScene& B, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                                       const float* node_boxes, bool refuse_non_finite, MeshRefit* out) {
+  const std::string refused = mesh_refit_head(B, object, pos, nrm, nverts, node_boxes, refuse_non_finite, out);
+  if (!refused.empty()) return refused;
+  // Object::bbox of every object from its unchanged transform and its object-space box, masked by the active table, folded
+  // through the kept tree
+  const size_t nobj = B.inputs.size();
+  std::vector<float> posed(6 * nobj);
+  for (size_t i = 0; i < nobj; i++) {
+    Mat4 itrans;
+    uint32_t has_trans;
+    posed_values(B.inputs[i].trans, &out->local_boxes[6 * i], &itrans, &has_trans, &posed[6 * i]);
+  }
+  effective_boxes(B, &posed);
+  top_refit_boxes(B.tlas, posed.data(), &out->top_boxes);
+  return "";
+}
+
+void apply_mesh_refit_inplace(BuiltScene* built, MeshRefit* refit) {
+  MeshRefit& R = *refit;
+  MeshInput& mesh = built->inputs[R.object].mesh;
+  mesh.pos.swap(R.pos);
+  mesh.nrm.swap(R.nrm);
+  built->local_boxes.swap(R.local_boxes);
+  write_mesh_refit(built, refit);
+  write_top_boxes(built, R.top_boxes);
+  if (any_inactive(*built)) write_top_counts(built);
 }
 
 void top_refit_boxes(const HostBVH& tree, const float* posed, std::vector<float>* boxes6) {

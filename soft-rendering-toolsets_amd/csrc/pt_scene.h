@@ -290,6 +290,7 @@ struct MeshRefit {
   std::vector<float> boxes;           // six floats {mn, mx} per node of the mesh's BVH<Triangle>
   std::vector<float> local_boxes;     // of every object
   ReposedTop top;                     // (listed / trans stay empty: no pose changes)
+  std::vector<float> top_boxes;       // prepare_mesh_refit_inplace only: six floats per node of the kept BVH<Object>
 };
 // The refitted boxes alone: six floats per node of `tree` over the triangles of (pos, idx).
 void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32_t>& idx, std::vector<float>* boxes6);
@@ -300,6 +301,18 @@ void refit_boxes(const HostBVH& tree, const float* pos, const std::vector<uint32
 std::string prepare_mesh_refit(const BuiltScene& built, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
                                const float* node_boxes, MeshRefit* out, bool* bad_argument);
 void apply_mesh_refit(BuiltScene* built, MeshRefit* refit);
+// srt_pt_refit_mesh_inplace, the definition: the refit above with BOTH trees kept.  The mesh's BVH<Triangle>, its triangle, normal and
+// packed records, its light-list copy and the object-space boxes of the mesh and of its instances change exactly as
+// prepare_mesh_refit / apply_mesh_refit change them; the BVH<Object> is not rebuilt but takes the boxes of top_refit_boxes over
+// effective_boxes of the posed boxes - Object::bbox of every object from its unchanged transform and its (new) object-space box -
+// through write_top_boxes, and write_top_counts runs while any object is inactive.  No link, order, count, slot, ordinal, lazy table
+// or depth changes anywhere: the result is what srt_pt_refit_mesh would give if its last step were srt_pt_repose_refit of the mesh
+// and its instances with their current transforms in place of the rebuild.  So nothing here can fail but the arguments:
+// check_mesh_update's refusals, a scene without BVHs and - unless !refuse_non_finite: the device form's lagging record takes what the
+// kernels computed - a non-finite coordinate.  `node_boxes` as in prepare_mesh_refit.  R->top stays empty.
+std::string prepare_mesh_refit_inplace(const BuiltScene& built, uint32_t object, const float* pos, const float* nrm, uint32_t nverts,
+                                       const float* node_boxes, bool refuse_non_finite, MeshRefit* out);
+void apply_mesh_refit_inplace(BuiltScene* built, MeshRefit* refit);
 // What srt_pt_repose_refit derives for new poses of a committed scene: the BVH<Object> keeps its links {start, size, l, r} and its
 // primitive order and takes new boxes, as a mesh's tree does in prepare_mesh_refit - a leaf's is the BBox::enclose fold, from
 // BBox(), of Object::bbox of its objects in primitive order (a leaf holds 0 or 1), an interior node's the enclose of its left and

@@ -115,7 +115,8 @@ void launch_listed_lights(srt_pt* pt, hipStream_t s, uint32_t nl, uint32_t max_n
 
 void drop_update_tables(srt_pt* pt, uint32_t object) { pt->mesh.drop_refit_tables(object); pt->pose.drop(); pt->top.drop_tables(); }
 
-// Both laggards catch up (settle_top of pt_update_pose.cpp, settle_shading of pt_update_shading.cpp); with nothing pending it does nothing.
+// The laggards catch up (settle_top of pt_update_pose.cpp, which begins with settle_mesh of pt_update_mesh.cpp - the top half reads
+// the boxes its calls left behind the mesh's -, and settle_shading of pt_update_shading.cpp); with nothing pending it does nothing.
 int settle(srt_pt* pt) {
   if (!pt) return SRT_OK;
   const int st = settle_top(pt);
@@ -130,7 +131,9 @@ void discard_pending(srt_pt* pt) {
   }
   if (!pt->top.pending) return;
   if (hipSetDevice(pt->device) == hipSuccess) (void)hipEventSynchronize(pt->top.event);
-  pt->top.refits += pt->top.pending - pt->top.pending_active;   // (they ran; only their read-back is not worth making any more)
+  pt->top.refits += pt->top.pending - pt->top.pending_active - pt->mesh.pending;   // (they ran; only their read-back is not worth making any more)
+  pt->mesh.refits += pt->mesh.pending;
+  pt->mesh.forget_pending();
   pt->top.forget_pending();
 }
 

@@ -34,11 +34,28 @@ void launch_listed_lights(srt_pt* pt, hipStream_t s, uint32_t nl, uint32_t max_n
 struct MeshVertices { const float *h_pos, *h_nrm, *d_pos, *d_nrm; std::vector<float> back_pos, back_nrm; };
 int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, MeshVertices V, uint32_t nverts);
 int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, MeshVertices V, uint32_t nverts);
+int refit_mesh_inplace(srt_pt* pt, const char* what, uint32_t object, const float* pos, const float* nrm, uint32_t nverts);
+int refit_mesh_inplace_device(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* d_pos, const float* d_nrm, uint32_t nverts);
 int make_refit_tables(const HostBVH& tree, const char* what, uint32_t object, RefitTables* T);
 
-// The two halves of settle() (pt_update_pose.cpp, pt_update_shading.cpp)
+// The parts of settle() (pt_update_mesh.cpp, pt_update_pose.cpp, pt_update_shading.cpp): settle_top begins with settle_mesh
+int settle_mesh(srt_pt* pt);
 int settle_top(srt_pt* pt);
 int settle_shading(srt_pt* pt);
+
+// (pt_update_pose.cpp) What the enqueue-only refits of the BVH<Object> share - srt_pt_repose_refit_device, srt_pt_set_active_device and
+// srt_pt_refit_mesh_inplace_device.  ensure_top_tables: the pose tables and the tree's refit tables, made (blocking, counted once) at
+// the first such call after a commit or after a call that replaced the tree.  enqueue_top_boxes: the leaf stage masked by the active
+// table, the levels, the write into the live top-level nodes and sweep records.  record_top_pending: the launch check, the event
+// behind the call, one more call for settle_top.  top_broken / top_hip_broken: a HIP failure after the first enqueue - the scene is no
+// longer committed and nothing is pending.  write_top_refit: the host forms' upload of the top-level nodes, the sweep records and
+// the n listed object records.
+int ensure_top_tables(srt_pt* pt, hipStream_t s, const char* what);
+void enqueue_top_boxes(srt_pt* pt, hipStream_t s);
+int record_top_pending(srt_pt* pt, hipStream_t s, const char* what);
+int top_broken(srt_pt* pt, int status);
+int top_hip_broken(srt_pt* pt, const char* what, hipError_t e, const char* step);
+int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n);
 
 // The head of srt_pt_skin, srt_pt_timeline and srt_pt_shading_timeline: a handle belongs to the scene its context held when it was
 // made.  (Each handle's *_usable refuses NULL and a stale handle in words of its own.)

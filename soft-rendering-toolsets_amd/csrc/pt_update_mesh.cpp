@@ -1,5 +1,6 @@
 // New vertices for a committed mesh: srt_pt_update_mesh[_device] rebuilds its BVH<Triangle>, srt_pt_refit_mesh[_device] refits it in
-// place (the skin poses of pt_update_skin.cpp end in one of the two), and the figures about both.  Host code only: the kernels are in
+// place, srt_pt_refit_mesh_inplace[_device] refits it and the BVH<Object> above it - the device form only enqueues, and settle_mesh
+// brings the host's record up to date later - (the skin poses of pt_update_skin.cpp end in one of the three), and the figures about them.  Host code only: the kernels are in
 // pt_mesh_update.hip, pt_light_update.hip and pt_bvh_device.hip, what the update units share in pt_update.h.
 #include <algorithm>
 #include <cmath>
@@ -223,6 +224,19 @@ int make_refit_tables(const HostBVH& tree, const char* what, uint32_t object, Re
   return SRT_OK;
 }
 
+// The refit tables of mesh `object`, made from its host tree at its first refit after a commit or a rebuild (blocking).
+static int mesh_refit_tables(srt_pt* pt, uint32_t object, RefitTables** T) {
+  auto it = pt->mesh.refit_tables.find(object);
+  if (it == pt->mesh.refit_tables.end()) {
+    RefitTables fresh;
+    const int st = make_refit_tables(pt->built.blas[object], "srt_pt_refit_mesh", object, &fresh);
+    if (st != SRT_OK) return st;
+    it = pt->mesh.refit_tables.emplace(object, std::move(fresh)).first;
+  }
+  *T = &it->second;
+  return SRT_OK;
+}
+
 // srt_pt_refit_mesh / srt_pt_refit_mesh_device / srt_pt_skin_pose_refit.
 int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, MeshVertices V, uint32_t nverts) {
   int st;
@@ -236,13 +250,7 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Mes
   uint64_t staged_bytes = 0;                              // (counted with the verdict: a refused refit adds nothing to the figures)
   if (on_device) {
     if ((st = stage_vertices(pt, what, s, object, nverts, true, &V, &staged_bytes))) return st;
-    auto it = pt->mesh.refit_tables.find(object);
-    if (it == pt->mesh.refit_tables.end()) {
-      RefitTables fresh;
-      if ((st = make_refit_tables(pt->built.blas[object], "srt_pt_refit_mesh", object, &fresh)) != SRT_OK) { (void)hipStreamSynchronize(s); return st; }   // (the read-back is on s)
-      it = pt->mesh.refit_tables.emplace(object, std::move(fresh)).first;
-    }
-    T = &it->second;
+    if ((st = mesh_refit_tables(pt, object, &T)) != SRT_OK) { (void)hipStreamSynchronize(s); return st; }   // (the read-back is on s)
     // the new boxes, aside: triangle boxes, leaves, levels.  They come back (24 B per node) with the arrays of the device form
     // (24 B per vertex): the host checks those, takes the root box and keeps its own tree true.
     launch_mesh_boxes(s, V.d_pos, pt->mesh.d_idx + pt->mesh.idx_off[object], m.ntri, T->d_tri_boxes);
@@ -283,6 +291,160 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Mes
   return written(pt, write());
 }
 
+
+// srt_pt_refit_mesh_inplace: the host form.  Blocks; the definition is prepare_mesh_refit_inplace / apply_mesh_refit_inplace.
+int refit_mesh_inplace(srt_pt* pt, const char* what, uint32_t object, const float* pos, const float* nrm, uint32_t nverts) {
+  int st;
+  if ((st = check_mesh_call(pt, what, object, nverts, pos))) return st;
+  MeshVertices V{pos, nrm, nullptr, nullptr, {}, {}};
+  if (!pt->built.flat.use_bvh) return update_mesh(pt, what, pt->stream, object, V, nverts);   // a list has no trees: the update
+  const bool on_device = pt->device >= 0;
+  hipStream_t s = pt->stream;
+  const MeshStore m = pt->built.store[object];
+  std::vector<float> node_boxes;
+  RefitTables* T = nullptr;
+  uint64_t staged_bytes = 0;                              // (counted with the verdict: a refused refit adds nothing to the figures)
+  if (on_device) {
+    if ((st = stage_vertices(pt, what, s, object, nverts, true, &V, &staged_bytes))) return st;
+    if ((st = mesh_refit_tables(pt, object, &T)) != SRT_OK) return st;
+    // the new boxes, aside, and back (24 B per node): the host takes the root box and keeps its own tree true
+    launch_mesh_boxes(s, V.d_pos, pt->mesh.d_idx + pt->mesh.idx_off[object], m.ntri, T->d_tri_boxes);
+    launch_refit_boxes(s, *T, T->d_tri_boxes, T->d_node_boxes);
+    node_boxes.resize(6 * (size_t)T->nnodes);
+    SRT_HIP(hipMemcpyAsync(node_boxes.data(), T->d_node_boxes, node_boxes.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+  }
+  MeshRefit R;
+  const std::string err = prepare_mesh_refit_inplace(pt->built, object, V.h_pos, V.h_nrm, nverts, on_device ? node_boxes.data() : nullptr, true, &R);
+  if (!err.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, err.c_str());
+  // nothing fails on the host side from here on: boxes and records change in place, and both trees keep their shape
+  apply_mesh_refit_inplace(&pt->built, &R);
+  pt->mesh.refits++;
+  if (!on_device) return SRT_OK;
+  pt->pose.drop();                                        // the object-space boxes changed (the trees' tables stay: the trees did)
+  pt->bytes_uploaded += staged_bytes + T->uncounted_bytes + pt->mesh.idx_uncounted;
+  T->uncounted_bytes = 0;
+  pt->mesh.idx_uncounted = 0;
+  auto write = [&]() -> int {
+    int w;
+    if ((w = write_top_refit(pt, nullptr, 0))) return w;  // the top-level nodes and the sweep records, no object record
+    launch_refit_write(s, *T, T->d_node_boxes, pt->d_nodes + pt->built.flat.tlas_nodes + m.node_off, pt->d_blas + m.rec_base);
+    launch_mesh_records(s, V.d_pos, V.d_nrm, pt->mesh.d_idx + pt->mesh.idx_off[object], T->d_prim, m.ntri, pt->d_tris + m.tri_base, pt->d_nrm + m.tri_base,
+                        pt->d_tri_packed + 9 * (size_t)m.tri_base);
+    SRT_HIP(hipStreamSynchronize(s));
+    SRT_HIP(hipGetLastError());
+    return write_light_mesh_device(pt, s, object, false, V.d_pos, V.d_nrm);
+  };
+  return written(pt, write());
+}
+
+// What srt_pt_refit_mesh_inplace_device keeps per mesh beside its refit tables, made at the mesh's first such call after a commit or a
+// rebuild (blocking; 4 B per member of the family go up): the vertex buffers, the family, and an emissive mesh's index buffer.
+static int ensure_inplace(srt_pt* pt, const char* what, uint32_t object, uint32_t nverts, srt_pt::MeshState::Inplace** out) {
+  auto it = pt->mesh.inplace.find(object);
+  if (it != pt->mesh.inplace.end()) { *out = &it->second; return SRT_OK; }
+  int st;
+  if (pt->mesh.idx_off[object] == SIZE_MAX) {             // an emissive mesh under srt_pt_set_dynamic_lights: its index buffer goes up now
+    SRT_HIP(quiesce(pt));
+    if ((st = ensure_mesh_idx(pt, object))) return st;
+  }
+  std::vector<uint32_t> family(1, object);
+  for (uint32_t i = 0; i < (uint32_t)pt->built.inputs.size(); i++)
+    if (pt->built.inputs[i].kind == OBJ_MESH && pt->built.inputs[i].source == (int32_t)object) family.push_back(i);
+  srt_pt::MeshState::Inplace fresh;
+  const size_t vfloats = 3 * (size_t)(nverts ? nverts : 1);
+  if (fresh.d_pos.ensure(vfloats) || fresh.d_nrm.ensure(vfloats) || fresh.d_family.upload(family)) {
+    (void)hipGetLastError();
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+  }
+  fresh.nfamily = (uint32_t)family.size();
+  pt->bytes_uploaded += family.size() * sizeof(uint32_t);
+  *out = &pt->mesh.inplace.emplace(object, std::move(fresh)).first->second;
+  return SRT_OK;
+}
+
+// srt_pt_refit_mesh_inplace_device / srt_pt_skin_pose_inplace[_at].
+int refit_mesh_inplace_device(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, const float* d_pos, const float* d_nrm, uint32_t nverts) {
+  if (!pt->committed) return not_committed(what);         // (no settle(): this call only adds to what is pending)
+  const std::string refused = check_mesh_update(pt->built, object, nverts);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  if (pt->device < 0)
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: the refit is enqueued on the device only; this context is host-only (srt_pt_refit_mesh_inplace takes host arrays)", what);
+  if (!pt->built.flat.use_bvh) return refit_mesh(pt, what, s, object, {nullptr, nullptr, d_pos, d_nrm, {}, {}}, nverts);   // a list has no trees: the update, which blocks
+  SRT_HIP(hipSetDevice(pt->device));
+  // First call after a commit or after a call that replaced one of the trees (blocking, counted once): the pose tables and the
+  // BVH<Object>'s refit tables, the mesh's refit tables, its family and its vertex buffers.  Nothing is pending then.
+  int st;
+  RefitTables* T = nullptr;
+  srt_pt::MeshState::Inplace* I = nullptr;
+  if ((st = ensure_top_tables(pt, s, what)) || (st = mesh_refit_tables(pt, object, &T)) || (st = ensure_inplace(pt, what, object, nverts, &I))) return st;
+  pt->bytes_uploaded += T->uncounted_bytes + pt->mesh.idx_uncounted;
+  T->uncounted_bytes = 0;
+  pt->mesh.idx_uncounted = 0;
+  // Everything below only enqueues on `s`: the vertices into the context's own buffers, the triangle boxes, the leaves and levels
+  // of the mesh's tree, its live nodes and records, its triangle records in the kept order, an emissive mesh's light tables, the
+  // link - the family's object-space and posed boxes - and the BVH<Object>'s own refit.  No verdict is needed: depth, counts,
+  // orders, kernel form and stack sizes are those of the committed trees.
+  const FlatScene& F = pt->built.flat;
+  const MeshStore m = pt->built.store[object];
+  const uint32_t* d_idx = pt->mesh.d_idx + pt->mesh.idx_off[object];
+  const size_t vbytes = 3 * (size_t)nverts * sizeof(float);
+  hipError_t he;
+  if (vbytes && ((he = hipMemcpyAsync(I->d_pos, d_pos, vbytes, hipMemcpyDeviceToDevice, s)) != hipSuccess ||
+                 (he = hipMemcpyAsync(I->d_nrm, d_nrm, vbytes, hipMemcpyDeviceToDevice, s)) != hipSuccess))
+    return top_hip_broken(pt, what, he, "the copy of the vertices");
+  launch_mesh_boxes(s, I->d_pos, d_idx, m.ntri, T->d_tri_boxes);
+  launch_refit_boxes(s, *T, T->d_tri_boxes, T->d_node_boxes);
+  launch_refit_write(s, *T, T->d_node_boxes, pt->d_nodes + F.tlas_nodes + m.node_off, pt->d_blas + m.rec_base);
+  launch_mesh_records(s, I->d_pos, I->d_nrm, d_idx, T->d_prim, m.ntri, pt->d_tris + m.tri_base, pt->d_nrm + m.tri_base, pt->d_tri_packed + 9 * (size_t)m.tri_base);
+  const int32_t li = light_of(pt->built, object);
+  if (li >= 0) {
+    const Light& L = F.lights[(size_t)li];
+    launch_light_triangles(s, I->d_pos, I->d_nrm, d_idx, L.ntri, pt->d_lights + li, pt->d_tris + L.tri_base, pt->d_nrm + L.tri_base,
+                           pt->d_tri_packed + 9 * (size_t)L.tri_base, pt->d_ltris + (L.tri_base - F.light_tri_first));
+  }
+  launch_mesh_link(s, I->d_family, I->nfamily, (uint32_t)pt->built.inputs.size(), T->d_node_boxes, pt->pose.d_records, pt->pose.d_local_boxes,
+                   pt->pose.d_posed_boxes);
+  enqueue_top_boxes(pt, s);
+  if ((st = record_top_pending(pt, s, what))) return st;
+  pt->mesh.pending++;
+  if (std::find(pt->mesh.pending_meshes.begin(), pt->mesh.pending_meshes.end(), object) == pt->mesh.pending_meshes.end()) pt->mesh.pending_meshes.push_back(object);
+  return SRT_OK;
+}
+
+// The host's record catches up with the device after srt_pt_refit_mesh_inplace_device calls (the head of settle_top): one wait for the
+// event behind the last pending call and, per mesh they touched - however many calls - one read-back of its vertices (24 B each, from the context's buffers) and
+// node boxes (24 B per node), applied through the definition without the finiteness check and with the boxes as read.  The BVH<Object>'s
+// boxes the definition writes here are the host's own fold; settle_top then reads the device's back over them.
+int settle_mesh(srt_pt* pt) {
+  if (!pt->mesh.pending) return SRT_OK;
+  const uint64_t calls = pt->mesh.pending;
+  const std::vector<uint32_t> meshes = pt->mesh.pending_meshes;
+  pt->mesh.forget_pending();
+  auto broken = [&](const char* why) {
+    return top_broken(pt, srt::fail(SRT_ERR_HIP, "settling srt_pt_refit_mesh_inplace_device: %s; the scene has to be committed again", why));
+  };
+  if (hipSetDevice(pt->device) != hipSuccess || hipEventSynchronize(pt->top.event) != hipSuccess) return broken(hipGetErrorString(hipGetLastError()));
+  for (uint32_t object : meshes) {
+    auto I = pt->mesh.inplace.find(object);
+    auto T = pt->mesh.refit_tables.find(object);
+    if (I == pt->mesh.inplace.end() || T == pt->mesh.refit_tables.end()) return broken("the mesh's device tables are gone");
+    const size_t vfloats = pt->built.inputs[object].mesh.pos.size();
+    std::vector<float> pos(vfloats), nrm(vfloats), boxes(6 * (size_t)T->second.nnodes);
+    if ((vfloats && (hipMemcpy(pos.data(), I->second.d_pos, vfloats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+                     hipMemcpy(nrm.data(), I->second.d_nrm, vfloats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) ||
+        (!boxes.empty() && hipMemcpy(boxes.data(), T->second.d_node_boxes, boxes.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
+      return broken(hipGetErrorString(hipGetLastError()));
+    MeshRefit R;
+    const std::string err = prepare_mesh_refit_inplace(pt->built, object, pos.data(), nrm.data(), (uint32_t)(vfloats / 3), boxes.data(), false, &R);
+    if (!err.empty()) return broken(err.c_str());
+    apply_mesh_refit_inplace(&pt->built, &R);
+  }
+  pt->mesh.refits += calls;
+  return SRT_OK;
+}
+
 }  // namespace srt
 
 extern "C" {
@@ -307,9 +469,26 @@ int srt_pt_refit_mesh_device(srt_pt* pt, void* stream, uint32_t object, const fl
   return refit_mesh(pt, "srt_pt_refit_mesh_device", (hipStream_t)stream, object, {nullptr, nullptr, d_positions, d_normals, {}, {}}, nverts);
 }
 
+int srt_pt_refit_mesh_inplace(srt_pt* pt, uint32_t object, const float* positions, const float* normals, uint32_t nverts) {
+  if (!pt || !positions || !normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh_inplace: NULL argument");
+  return refit_mesh_inplace(pt, "srt_pt_refit_mesh_inplace", object, positions, normals, nverts);
+}
+
+int srt_pt_refit_mesh_inplace_device(srt_pt* pt, void* stream, uint32_t object, const float* d_positions, const float* d_normals, uint32_t nverts) {
+  if (!pt || !d_positions || !d_normals) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_mesh_inplace_device: NULL argument");
+  return refit_mesh_inplace_device(pt, "srt_pt_refit_mesh_inplace_device", (hipStream_t)stream, object, d_positions, d_normals, nverts);
+}
+
+int srt_pt_mesh_refit_pending(srt_pt* pt, uint64_t out[2]) {
+  if (!pt || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_refit_pending: NULL argument");
+  out[0] = pt->mesh.pending;
+  out[1] = pt->mesh.pending_meshes.size();
+  return SRT_OK;
+}
+
 int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost) {
   if (!pt || !cost) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: NULL argument");
-  if (!pt->committed) return not_committed("srt_pt_mesh_tree_cost");
+  { const int ready = need_committed(pt, "srt_pt_mesh_tree_cost"); if (ready != SRT_OK) return ready; }   // (settles: the cost is the tree's as refitted)
   const std::string refused = check_mesh_update(pt->built, object, (uint32_t)(object < pt->built.inputs.size() ? pt->built.inputs[object].mesh.pos.size() / 3 : 0));
   if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "srt_pt_mesh_tree_cost: %s", refused.c_str());
   if (!pt->built.flat.use_bvh) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_mesh_tree_cost: the scene was committed without BVHs, the mesh has no tree");
@@ -319,6 +498,7 @@ int srt_pt_mesh_tree_cost(srt_pt* pt, uint32_t object, double* cost) {
 
 int srt_pt_refit_count(srt_pt* pt, uint64_t* refits) {
   if (!pt || !refits) return srt::fail(SRT_ERR_INVALID, "srt_pt_refit_count: NULL argument");
+  { const int settled = settle(pt); if (settled != SRT_OK) return settled; }
   *refits = pt->mesh.refits;
   return SRT_OK;
 }

@@ -94,6 +94,10 @@ int pinned_list(srt_pt* pt, size_t words, srt_pt::TopLevel::PinnedList** out) {
   return SRT_OK;
 }
 
+}  // namespace
+
+namespace srt {
+
 // srt_pt_repose_refit's device side after apply_top_refit: the arrays that changed, from the host's record.
 int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n) {
   const FlatScene& F = pt->built.flat;
@@ -125,6 +129,7 @@ int top_broken(srt_pt* pt, int status) {
   if (hipSetDevice(pt->device) == hipSuccess) (void)hipDeviceSynchronize();
   (void)hipGetLastError();
   pt->top.forget_pending();
+  pt->mesh.forget_pending();
   pt->pose.drop();
   pt->top.drop_tables();
   return status;
@@ -159,7 +164,7 @@ int ensure_top_tables(srt_pt* pt, hipStream_t s, const char* what) {
 
 // The list (4 B per listed object, 8 B more per listed light) into pose.d_list, through pinned memory so that the copy is only
 // enqueued - unless the device holds this very list already.
-int stage_top_list(srt_pt* pt, hipStream_t s, const char* what, const uint32_t* objects, uint32_t n) {
+static int stage_top_list(srt_pt* pt, hipStream_t s, const char* what, const uint32_t* objects, uint32_t n) {
   if (!n || (pt->top.list_valid && pt->top.list.size() == n && std::memcmp(pt->top.list.data(), objects, (size_t)n * 4) == 0)) return SRT_OK;
   int st;
   hipError_t he;
@@ -192,7 +197,7 @@ void enqueue_top_boxes(srt_pt* pt, hipStream_t s) {
 }
 
 // The launches went in, the event behind them is recorded, and the host's record is behind by one more call until settle().
-int record_pending(srt_pt* pt, hipStream_t s, const char* what) {
+int record_top_pending(srt_pt* pt, hipStream_t s, const char* what) {
   hipError_t he;
   if ((he = hipGetLastError()) != hipSuccess) return top_hip_broken(pt, what, he, "a launch");
   if (pt->top.event.create(hipEventDisableTiming)) return top_hip_broken(pt, what, hipGetLastError(), "hipEventCreate");
@@ -203,15 +208,11 @@ int record_pending(srt_pt* pt, hipStream_t s, const char* what) {
 }
 
 // srt_pt_set_active[_device]: the scene layer's verdict on the list, as a status.
-int active_list_usable(srt_pt* pt, const char* what, const uint32_t* objects, uint32_t n) {
+static int active_list_usable(srt_pt* pt, const char* what, const uint32_t* objects, uint32_t n) {
   bool unsupported = false;
   const std::string refused = check_active_list(pt->built, objects, n, &unsupported);
   return refused.empty() ? SRT_OK : srt::fail(unsupported ? SRT_ERR_UNSUPPORTED : SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
 }
-
-}  // namespace
-
-namespace srt {
 
 // The host's record catches up with the device after srt_pt_repose_refit_device calls: one wait for the event behind the last of
 // them, one read-back (176 B per object: the records by insertion index; 24 B per node: the top-level boxes), and the scene
@@ -220,7 +221,8 @@ namespace srt {
 int settle_top(srt_pt* pt) {
   if (!pt->top.pending) return SRT_OK;
   if (!pt->committed) { discard_pending(pt); return SRT_OK; }   // (a failure took the scene away: there is no record to bring up to date)
-  const uint64_t calls = pt->top.pending, flag_calls = pt->top.pending_active;
+  const uint64_t calls = pt->top.pending, flag_calls = pt->top.pending_active, mesh_calls = pt->mesh.pending;
+  { const int st = settle_mesh(pt); if (st != SRT_OK) return st; }   // the mesh half first: the boxes read back below lie over what it folds
   std::vector<uint32_t> objects = pt->top.pending_objects;
   pt->top.forget_pending();
   const uint32_t nobj = (uint32_t)pt->built.inputs.size();
@@ -245,7 +247,7 @@ int settle_top(srt_pt* pt) {
   }
   apply_top_refit(&pt->built, &R);
   if (flag_calls) write_top_counts(&pt->built);           // (what launch_top_counts left in the live nodes and sweep records)
-  pt->top.refits += calls - flag_calls;
+  pt->top.refits += calls - flag_calls - mesh_calls;
   return SRT_OK;
 }
 
@@ -432,7 +434,7 @@ int srt_pt_repose_refit_device(srt_pt* pt, void* stream, const uint32_t* objects
     launch_top_objects(s, pt->pose.d_list, n, nobj, use_bvh ? pt->top.d_slot_of : nullptr, pt->pose.d_records, pt->d_objects);
     if (pt->top.lights) launch_listed_lights(pt, s, pt->top.lights, pt->top.light_max_ntri, n);
   }
-  if ((st = record_pending(pt, s, what))) return st;
+  if ((st = record_top_pending(pt, s, what))) return st;
   // the objects this call listed that no pending call had listed
   for (uint32_t k = 0; k < n; k++)
     if (!pt->top.pending_flag[objects[k]]) { pt->top.pending_flag[objects[k]] = 1; pt->top.pending_objects.push_back(objects[k]); }
@@ -472,7 +474,7 @@ int srt_pt_set_active_device(srt_pt* pt, void* stream, const uint32_t* objects, 
   launch_active_scatter(s, pt->pose.d_list, d_active, n, nobj, pt->pose.d_active);
   enqueue_top_boxes(pt, s);
   launch_top_counts(s, pt->top.tables, pt->pose.d_active, nobj, pt->d_nodes, pt->d_wave);   // a hidden leaf holds nothing for the walks
-  if ((st = record_pending(pt, s, what))) return st;
+  if ((st = record_top_pending(pt, s, what))) return st;
   pt->top.pending_active++;
   return SRT_OK;
 }

@@ -17,7 +17,10 @@ using namespace srt;
 struct srt_pt_skin : SceneHandle {
   uint32_t object = 0, nverts = 0, ntri = 0, njoints = 0, ninf = 0;
   std::vector<float> inv;                   // Mat4::inverse(joint_to_bind(j)), 16 floats per joint
-  std::vector<float> mats;                  // the frame's posed_j * inverse_j on their way up
+  // The frame's posed_j * inverse_j on their way up: pinned, one buffer per frame still on its way (its event tells), so that the copy is
+  // only enqueued and an enqueue-only pose never rewrites what an earlier one's copy has yet to read.
+  struct Mats { PinnedBuffer<float> h; Event done; };
+  std::vector<Mats> mats;
   DeviceBuffer<float> d_pos, d_nrm;                     // the bind-pose mesh
   DeviceBuffer<float> d_inv, d_cap, d_mats;
   DeviceBuffer<uint32_t> d_off, d_jidx, d_last;
@@ -106,9 +109,24 @@ int skin_enqueue(srt_pt_skin* k, const char* what, hipStream_t s, const float* p
   const int usable = skin_usable(k, what);
   if (usable != SRT_OK) return usable;
   SRT_HIP(hipSetDevice(k->pt->device));
-  for (uint32_t j = 0; j < k->njoints; j++) skin_mat4_mul(posed + 16 * (size_t)j, &k->inv[16 * (size_t)j], &k->mats[16 * (size_t)j]);
-  SRT_HIP(hipMemcpyAsync(k->d_mats, k->mats.data(), k->mats.size() * sizeof(float), hipMemcpyHostToDevice, s));   // 64 B per joint
-  k->pt->bytes_uploaded += k->mats.size() * sizeof(float);
+  srt_pt_skin::Mats* m = nullptr;
+  for (auto& c : k->mats) {
+    const hipError_t left = hipEventQuery(c.done);
+    (void)hipGetLastError();                              // (hipErrorNotReady of a query is no error: not left behind for the launch check)
+    if (left == hipSuccess) { m = &c; break; }
+  }
+  if (!m) {
+    srt_pt_skin::Mats fresh;
+    if (fresh.h.ensure(k->inv.size())) return srt::fail(SRT_ERR_HIP, "%s: out of pinned host memory", what);
+    if (fresh.done.create(hipEventDisableTiming)) return srt::fail(SRT_ERR_HIP, "%s: event creation failed", what);
+    k->mats.push_back(std::move(fresh));
+    m = &k->mats.back();
+  }
+  float* const h = m->h;
+  for (uint32_t j = 0; j < k->njoints; j++) skin_mat4_mul(posed + 16 * (size_t)j, &k->inv[16 * (size_t)j], h + 16 * (size_t)j);
+  SRT_HIP(hipMemcpyAsync(k->d_mats, h, k->inv.size() * sizeof(float), hipMemcpyHostToDevice, s));   // 64 B per joint
+  SRT_HIP(hipEventRecord(m->done, s));
+  k->pt->bytes_uploaded += k->inv.size() * sizeof(float);
   skin_launch(k, s, flat_normals, d_pos_out, d_nrm_out);
   return SRT_OK;
 }
@@ -183,7 +201,6 @@ int srt_pt_skin_create(srt_pt* pt, uint32_t object, const float* bind_positions,
   k->pt = pt; k->generation = pt->scene_generation; k->object = object; k->nverts = nverts; k->njoints = njoints;
   k->ntri = pt->built.store[object].ntri;
   k->inv.resize(16 * (size_t)njoints);
-  k->mats.resize(16 * (size_t)njoints);
   return handle_publish(k, skin, [&]() -> int {
     if (pt->mesh.idx_off[object] == SIZE_MAX) {           // an emissive mesh under srt_pt_set_dynamic_lights: its index buffer goes up now
       if (quiesce(pt) != hipSuccess) return srt::fail(SRT_ERR_HIP, "srt_pt_skin_create: synchronisation failed");
@@ -307,6 +324,22 @@ int srt_pt_skin_pose_at(srt_pt_skin* skin, void* stream, float t, int flat_norma
 
 int srt_pt_skin_pose_refit_at(srt_pt_skin* skin, void* stream, float t, int flat_normals) {
   return skin_pose_at(skin, "srt_pt_skin_pose_refit_at", stream, t, flat_normals, refit_mesh);
+}
+
+int srt_pt_skin_pose_inplace(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals) {
+  const char* what = "srt_pt_skin_pose_inplace";
+  if (!skin || !posed) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_enqueue(skin, what, (hipStream_t)stream, posed, flat_normals, skin->d_pos_out, skin->d_nrm_out);
+  if (st != SRT_OK) return st;
+  return refit_mesh_inplace_device(skin->pt, what, (hipStream_t)stream, skin->object, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
+}
+
+int srt_pt_skin_pose_inplace_at(srt_pt_skin* skin, void* stream, float t, int flat_normals) {
+  const char* what = "srt_pt_skin_pose_inplace_at";
+  if (!skin) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_enqueue_at(skin, what, (hipStream_t)stream, t, flat_normals, skin->d_pos_out, skin->d_nrm_out);
+  if (st != SRT_OK) return st;
+  return refit_mesh_inplace_device(skin->pt, what, (hipStream_t)stream, skin->object, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
 }
 
 int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* extents, const float base[3], const float* rest_pose,
