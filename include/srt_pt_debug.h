@@ -106,6 +106,9 @@ int srt_pt_dump_shading(srt_pt* pt, int from_device, uint32_t counts[2], srt_pt_
                         float* light_values, size_t cap_lights, uint32_t* env_type, float env_radiance[3]);
 /* cosf/sinf of the kernel (SRT-MATH v2) for n host floats; parity tests compare them with glibc. */
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);
+/* The same through srt_sincosf2 (both values from one reduction: what the samplers call); srt_pt_math_cos_sin goes through the
+ * single-function forms.  Argument i is evaluated by lane i % 64 of wave i / 64, every wave with all of its lanes. */
+int srt_pt_math_sincos2(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out);
 /* The kernels' atan2f (glibc 2.35's algorithm restated; Spot_Light::sample) evaluated on the device. */
 int srt_pt_math_atan2(srt_pt* pt, const float* y, const float* x, size_t n, float* out);
 /* The kernels' acosf (glibc 2.35's algorithm restated; Samplers::Hemisphere::Uniform) evaluated on the device. */

@@ -138,6 +138,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_dump_bvh.restype = c_long
     lib.srt_pt_counters.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_math_cos_sin.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.srt_pt_math_sincos2.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.srt_pt_math_acos.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_atan2.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_set_elision.argtypes = [c_void_p, c_int]
@@ -1282,6 +1283,13 @@ class Pathtracer:
         x = _f32(x)
         c, s = np.zeros_like(x), np.zeros_like(x)
         self._check(self._lib, self._lib.srt_pt_math_cos_sin(self._ctx, _p(x), len(x), _p(c), _p(s)))
+        return c, s
+
+    def math_sincos2(self, x):
+        """(cos, sin) through srt_sincosf2; math_cos_sin goes through the single-function forms."""
+        x = _f32(x)
+        c, s = np.zeros_like(x), np.zeros_like(x)
+        self._check(self._lib, self._lib.srt_pt_math_sincos2(self._ctx, _p(x), len(x), _p(c), _p(s)))
         return c, s
 
     def sync(self) -> None:

@@ -166,6 +166,19 @@ SRT_DEV V3 mat_point(const Mat4& m, V3 v) {
   for (int j = 0; j < 4; j++) o[j] = ((m.c[0][j] * v.x + m.c[1][j] * v.y) + m.c[2][j] * v.z) + m.c[3][j] * 1.0f;
   return v3(o[0] / o[3], o[1] / o[3], o[2] / o[3]);
 }
+// The same for the wave kernel: x / 1.0f == x bit for bit, so the perspective divide is skipped when w == 1 in every active
+// lane (always the case for affine matrices and finite points); one lane with another w sends the wave through the divides.
+// The matrix may differ from lane to lane.
+SRT_DEV V3 mat_point_uniform(const Mat4& m, V3 v) {
+  float o[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) o[j] = ((m.c[0][j] * v.x + m.c[1][j] * v.y) + m.c[2][j] * v.z) + m.c[3][j] * 1.0f;
+  if (__ballot(o[3] != 1.0f) == 0ull) return v3(o[0], o[1], o[2]);
+  return v3(o[0] / o[3], o[1] / o[3], o[2] / o[3]);
+}
+// W1: the caller is the wave kernel and takes the form above
+template <bool W1>
+SRT_DEV V3 mat_point_as(const Mat4& m, V3 v) { return W1 ? mat_point_uniform(m, v) : mat_point(m, v); }
 SRT_DEV V3 mat_rotate(const Mat4& m, V3 v) {
   float o[3];
 #pragma unroll
@@ -181,8 +194,9 @@ SRT_DEV V3 mat_rotate_transposed(const Mat4& m, V3 v) {
 }
 
 // Ray::transform (lib/ray.h:31-37)
+template <bool W1 = false>
 SRT_DEV void ray_transform(Ray& r, const Mat4& m) {
-  r.o = mat_point(m, r.o);
+  r.o = mat_point_as<W1>(m, r.o);
   r.d = mat_rotate(m, r.d);
   const float d = norm(r.d);
   r.b0 *= d;
@@ -249,7 +263,9 @@ SRT_HD float sincos_poly(double x, double x2, bool negated_cos_table, int n) {
     return (float)(c + x6 * c2);
   }
 }
-SRT_HD float srt_sincosf(float y, int want_cos) {
+// glibc's control flow, kept as the form the branch-free functions below are held to (tests/test_pt_sincos_host.py compares them
+// for every float in range, bit for bit), as tri_hit stays beside tri_hitN.  Nothing on a hot path calls the _plain functions.
+SRT_HD float srt_sincosf_plain(float y, int want_cos) {
   double x = (double)y;
   const uint32_t top = (f2u(y) >> 20) & 0x7ffu;
   if (top < 0x3f4u) {                      // abstop12(y) < abstop12(pi/4 = 0x1.921FB6p-1f)
@@ -267,7 +283,7 @@ SRT_HD float srt_sincosf(float y, int want_cos) {
   return u2f(0x7fc00000u);
 }
 // cosf(y) and sinf(y) together: both glibc routines reduce y the same way, so the reduction is shared.
-SRT_HD void srt_sincosf2(float y, float& c, float& s) {
+SRT_HD void srt_sincosf2_plain(float y, float& c, float& s) {
   double x = (double)y;
   const uint32_t top = (f2u(y) >> 20) & 0x7ffu;
   if (top < 0x3f4u) {
@@ -289,6 +305,57 @@ SRT_HD void srt_sincosf2(float y, float& c, float& s) {
     return;
   }
   c = s = u2f(0x7fc00000u);
+}
+// The same arithmetic in one straight line: lanes of a wave hold different quadrants and both sides of pi/4, so the
+// branches above are walked one after the other.  Every argument is reduced (below pi/4 the quadrant n is 0, x - 0 * hpi == x, and
+// the table and sign selects fall on the short path's values), the sine form and the cosine form of the reduced argument are
+// evaluated once each and the caller selects by the parity of n.  The signs are applied to the two results, not to their operands:
+// the sine form is odd in x (every product and sum rounds symmetrically), and the negated cosine table negates every term.
+// fs = sincos_poly(x * s, x * x, (n & 2) != 0, 0), fc = the same with an odd last argument, for y below 120 in magnitude;
+// larger arguments, infinities and NaN reduce 0 in their place (the double -> int32 conversion stays defined on the host)
+// and the callers override the result.
+SRT_HD void sincos_both(float y, uint32_t top, float& fs, float& fc, int& n_out) {
+  double x = (double)((top < 0x42fu) ? y : 0.0f);
+  const double r = x * 0x1.45F306DC9C883p+23;
+  const int n = ((int32_t)r + 0x800000) >> 24;
+  x = x - n * 0x1.921FB54442D18p0;
+  const double x2 = x * x;
+  const double x3 = x * x2;
+  const double s1 = 0x1.1107605230bc4p-7 + x2 * -0x1.994eb3774cf24p-13;
+  const double x7 = x3 * x2;
+  const double s = x + x3 * -0x1.555545995a603p-3;
+  const float ps = (float)(s + x7 * s1);
+  const double x4 = x2 * x2;
+  const double c2 = -0x1.6c087e89a359dp-10 + x2 * 0x1.99343027bf8c3p-16;
+  const double c1 = 0x1p0 + x2 * -0x1.ffffffd0c621cp-2;
+  const double x6 = x4 * x2;
+  const double c = c1 + x4 * 0x1.55553e1068f19p-5;
+  const float pc = (float)(c + x6 * c2);
+  fs = u2f(f2u(ps) ^ ((uint32_t)((n + 1) & 2) << 30));    // quadrants 1 and 2: the sine form of -x
+  fc = u2f(f2u(pc) ^ ((uint32_t)(n & 2) << 30));          // quadrants 2 and 3: the negated cosine table
+  n_out = n;
+}
+SRT_HD float srt_sincosf(float y, int want_cos) {
+  const uint32_t top = (f2u(y) >> 20) & 0x7ffu;
+  float fs, fc;
+  int n;
+  sincos_both(y, top, fs, fc, n);
+  float v = (((n ^ want_cos) & 1) == 0) ? fs : fc;
+  if (top < 0x398u) v = want_cos ? 1.0f : y;       // |y| < 2^-12
+  if (top >= 0x42fu) v = u2f(0x7fc00000u);         // abstop12(120.0f)
+  return v;
+}
+// cosf(y) and sinf(y) together: one sine form and one cosine form of the same operands, whichever way round.
+SRT_HD void srt_sincosf2(float y, float& c, float& s) {
+  const uint32_t top = (f2u(y) >> 20) & 0x7ffu;
+  float fs, fc;
+  int n;
+  sincos_both(y, top, fs, fc, n);
+  const bool odd = (n & 1) != 0;
+  c = odd ? fs : fc;
+  s = odd ? fc : fs;
+  if (top < 0x398u) { c = 1.0f; s = y; }
+  if (top >= 0x42fu) c = s = u2f(0x7fc00000u);
 }
 // ---------------------------------------------------------------------------------------------------
 // SRT-MATH v2, atan2f: glibc 2.35 __ieee754_atan2f / __atanf (sysdeps/ieee754/flt-32/e_atan2f.c, s_atanf.c — the

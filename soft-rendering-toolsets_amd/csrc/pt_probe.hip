@@ -16,6 +16,14 @@ __global__ void pt_math_kernel(const float* __restrict__ x, size_t n, float* __r
   if (i < n) { c[i] = srt_cosf(x[i]); s[i] = srt_sinf(x[i]); }
 }
 
+// srt_sincosf2: no bounds guard around the call, so that every wave runs it with all 64 lanes (the spares repeat the last argument)
+__global__ void pt_sincos2_kernel(const float* __restrict__ x, size_t n, float* __restrict__ c, float* __restrict__ s) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float cv, sv;
+  srt_sincosf2(x[i < n ? i : n - 1], cv, sv);
+  if (i < n) { c[i] = cv; s[i] = sv; }
+}
+
 __global__ void pt_acos_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = srt_acosf(x[i]);
@@ -260,6 +268,11 @@ extern "C" {
 int srt_pt_math_cos_sin(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out) {
   return math_round_trip(pt, "srt_pt_math_cos_sin", {x}, n, {cos_out, sin_out}, n, [&](float* const* d, float* const* o) {
     pt_math_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0], o[1]); });
+}
+
+int srt_pt_math_sincos2(srt_pt* pt, const float* x, size_t n, float* cos_out, float* sin_out) {
+  return math_round_trip(pt, "srt_pt_math_sincos2", {x}, n, {cos_out, sin_out}, n, [&](float* const* d, float* const* o) {
+    pt_sincos2_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0], o[1]); });
 }
 
 int srt_pt_math_acos(srt_pt* pt, const float* x, size_t n, float* out) {

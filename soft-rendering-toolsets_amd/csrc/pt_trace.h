@@ -482,11 +482,14 @@ SRT_DEV Hit scene_hit(const DScene& S, const Ray& ray, Counters& cnt) {
 }
 
 // Trace payload of the winner (position, normal) as Object::hit + Trace::transform produce it.
+// W1 (here, in light_sample and in light_pdf): the caller is the wave kernel's shade section - the point transforms skip the
+// divide by a w that is 1 in every active lane (mat_point_uniform); the lane-per-sample kernels and the queries keep the plain form.
 struct Surface { V3 position, normal; };
+template <bool W1 = false>
 SRT_DEV Surface surface_of(const DScene& S, const Hit& h, const Ray& wray) {
   const Object& o = S.objects[h.obj];
   Ray ray = wray;
-  if (o.has_trans) ray_transform(ray, o.itrans);
+  if (o.has_trans) ray_transform<W1>(ray, o.itrans);
   Surface sf;
   if (o.kind == OBJ_SPHERE) {
     const SphHit sh = sphere_hit(o.radius, ray);
@@ -500,7 +503,7 @@ SRT_DEV Surface surface_of(const DScene& S, const Hit& h, const Ray& wray) {
     sf.normal = (v3p(nn.n0) * th.u + v3p(nn.n1) * th.v) + v3p(nn.n2) * (1.0f - th.u - th.v);
   }
   if (o.has_trans) {
-    sf.position = mat_point(o.trans, sf.position);
+    sf.position = mat_point_as<W1>(o.trans, sf.position);
     sf.normal = unit(mat_rotate_transposed(o.itrans, sf.normal));  // itrans.T().rotate(n).unit()
   }
   return sf;
@@ -640,6 +643,7 @@ SRT_DEV V3 env_sample(Rng& rng) {
 
 // Pathtracer::sample_area_lights (rays/pathtracer.cpp:301-311): List<Object>::sample -> Object::sample ->
 // List<Triangle>::sample -> Samplers::Triangle::sample; with an environment light a coin picks between the two.
+template <bool W1 = false>
 SRT_DEV V3 light_sample(const DScene& S, V3 from, Rng& rng) {
   if (S.env_type != 0u) {
     if (S.nlights == 0) return env_sample(rng);
@@ -647,7 +651,7 @@ SRT_DEV V3 light_sample(const DScene& S, V3 from, Rng& rng) {
   }
   if (S.nlights == 0) return v3(0, 0, 0);
   const Light& L = S.lights[rng.integer(0, (int)S.nlights)];
-  if (L.has_trans) from = mat_point(L.itrans, from);
+  if (L.has_trans) from = mat_point_as<W1>(L.itrans, from);
   const uint32_t t = (uint32_t)rng.integer(0, (int)L.ntri);
   const LightTri& lt = S.light_tris[L.tri_base - S.light_tri_first + t];
   const float u = sqrtf(rng.unit());
@@ -660,7 +664,7 @@ SRT_DEV V3 light_sample(const DScene& S, V3 from, Rng& rng) {
   return dir;
 }
 // Pathtracer::area_lights_pdf -> List<Object>::pdf -> Object::pdf -> List<Triangle>::pdf -> Triangle::pdf.
-template <bool COUNT>
+template <bool COUNT, bool W1 = false>
 SRT_DEV float light_pdf(const DScene& S, V3 from, V3 dir, Counters& cnt) {
   int n = 0;
   float pdf = 0.0f;
@@ -671,7 +675,7 @@ SRT_DEV float light_pdf(const DScene& S, V3 from, V3 dir, Counters& cnt) {
       const Light& L = S.lights[li];
       float sum = 0.0f;
       Ray tray = wray;
-      ray_transform(tray, L.pdfiT);             // Triangle::pdf transforms per triangle; same matrix, same result
+      ray_transform<W1>(tray, L.pdfiT);         // Triangle::pdf transforms per triangle; same matrix, same result
       for (uint32_t t = 0; t < L.ntri; t++) {
         if (COUNT) cnt.v[C_LTRI]++;
         const uint32_t gi = L.tri_base + t;
@@ -681,7 +685,7 @@ SRT_DEV float light_pdf(const DScene& S, V3 from, V3 dir, Counters& cnt) {
           const TriNrm& nn = S.tri_nrm[gi];
           V3 position = ray_at(tray, th.t);
           V3 normal = (v3p(nn.n0) * th.u + v3p(nn.n1) * th.v) + v3p(nn.n2) * (1.0f - th.u - th.v);
-          position = mat_point(L.pdfT, position);                       // trace.transform(T, iT.T())
+          position = mat_point_as<W1>(L.pdfT, position);                // trace.transform(T, iT.T())
           normal = unit(mat_rotate_transposed(L.pdfiT, normal));
           const float a = S.light_tris[gi - S.light_tri_first].area_term;
           const float g = norm2(position - wray.o) / fabsf(dot(normal, wray.d));

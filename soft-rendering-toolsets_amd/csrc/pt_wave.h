@@ -147,15 +147,7 @@ SRT_DEV uint32_t tile_slot(const TileMap& T, uint32_t p) {
   return local_tile * px_per_tile + ly * T.tile_w + lx;
 }
 
-// Mat4 * Vec3 for wave-uniform matrices: x / 1.0f == x bit for bit, so the perspective divide is skipped
-// when w == 1 in every lane (always the case for affine matrices and finite points).
-SRT_DEV V3 mat_point_uniform(const Mat4& m, V3 v) {
-  float o[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) o[j] = ((m.c[0][j] * v.x + m.c[1][j] * v.y) + m.c[2][j] * v.z) + m.c[3][j] * 1.0f;
-  if (__ballot(o[3] != 1.0f) == 0ull) return v3(o[0], o[1], o[2]);
-  return v3(o[0] / o[3], o[1] / o[3], o[2] / o[3]);
-}
+// (mat_point_uniform, Mat4 * Vec3 without the divide by a w of 1: pt_device.h, after mat_point)
 
 // (box_hit_inv, the sweeps' BBox::hit: pt_trace.h, after box_hit_rec)
 // (kRetMiss / kRetMissEnv and the two-word PHit the sweeps carry: pt_trace.h)
@@ -1274,7 +1266,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
           ray = camera_ray(opq(S.cam), ((float)PX_ + jx) / (float)img_w, ((float)PY_ + jy) / (float)img_h);
         }
         burst = false;
-        Surface sf = surface_of(S, ch, ray);
+        Surface sf = surface_of<true>(S, ch, ray);
         if (!is_sided(m.type) && dot(sf.normal, ray.d) > 0.0f) sf.normal = neg(sf.normal);
         const Frame fr = rotate_to(sf.normal);
         const V3 out_dir = unit(frame_to_local(fr, ray.o - sf.position));
@@ -1296,10 +1288,10 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         V3 chosen = world_in;
         bool log_fire = false;
         if (!discrete) {
-          const V3 to_light = light_sample(S, sf.position, rng);
+          const V3 to_light = light_sample<true>(S, sf.position, rng);
           chosen = rng.coin(0.5f) ? world_in : to_light;
           log_fire = rng.coin(0.0005f);                 // log_ray(world_ray_task6, 5.0f) with probability 0.0005 (student/pathtracer.cpp:148)
-          pdf_area = light_pdf<false>(S, sf.position, to_light, cnt);
+          pdf_area = light_pdf<false, true>(S, sf.position, to_light, cnt);
         }
         if (m.type == 0) { s2.atten = s1.atten; s2.dir = lambert_direction(rng); }
         else s2 = scatter(m, out_dir, rng);
