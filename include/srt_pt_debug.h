@@ -157,6 +157,12 @@ int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* o
  * of `lanes` floats (box min xyz, box max xyz, origin xyz, reciprocal direction xyz, incoming times x and y); out: 6 planes ({hit
  * as 0 / 1, times.x, times.y} of box_hit_inv, the same three of box_hit_rec). */
 int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out);
+/* Mat4 * Vec3 as the leaf section of pt_wave.h transforms points with an object's matrix (pt_device.h: mat_point_affine - for a
+ * bottom row of (+-0, +-0, +-0, 1) and a finite first output row in every lane of the wave, w is not computed) next to the plain
+ * projective product (mat_point), one matrix per wave of 64 consecutive lanes, lane i on its own point.  lanes must be a multiple
+ * of 64.  in: first, per wave, the matrix as Mat4::data has it (16 floats, column-major), then 3 planes of `lanes` floats (the point);
+ * out: 7 planes (x, y, z from mat_point_affine, x, y, z from mat_point, and 1 where the lane's wave did not compute w). */
+int srt_pt_math_point_affine(srt_pt* pt, const float* in, size_t lanes, float* out);
 
 /* The HIP resources the library holds at this moment, process-wide (every path-tracer and rasterizer context, skin and timeline):
  * out = {device buffers, pinned host buffers, events}.  Each counts the live allocations, not their bytes.  A test reads it before

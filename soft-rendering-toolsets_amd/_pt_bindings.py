@@ -157,6 +157,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_math_tri_verdict.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_leaf_fold.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_box_sweep.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_math_point_affine.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_sphere_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_sync.argtypes = [c_void_p]
     lib.srt_pt_cancel.argtypes = [c_void_p]
@@ -1278,6 +1279,18 @@ class Pathtracer:
         self._check(self._lib, self._lib.srt_pt_math_box_sweep(self._ctx, _p(planes), n, _p(out)))
         form = lambda b: {"hit": out[b] != 0, "tx": out[b + 1].copy(), "ty": out[b + 2].copy()}
         return form(0), form(3)
+
+    def math_point_affine(self, mats, points):
+        """Mat4 * Vec3 of the wave kernel's leaf section (mat_point_affine) and the plain mat_point on W waves of 64 lanes, one matrix
+        per wave.  mats (W, 16) as Mat4::data; points (W * 64, 3).  Returns (affine (n, 3), plain (n, 3), per wave whether w was not
+        computed)."""
+        mats, points = _f32(mats).reshape(-1, 16), _f32(points).reshape(-1, 3)
+        W, n = len(mats), len(points)
+        assert n == 64 * W and W > 0
+        buf = np.ascontiguousarray(np.concatenate([mats.ravel(), points.T.ravel()]), np.float32)
+        out = np.zeros((7, n), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_point_affine(self._ctx, _p(buf), n, _p(out)))
+        return out[0:3].T.copy(), out[3:6].T.copy(), out[6].reshape(W, 64)[:, 0] != 0
 
     def math_cos_sin(self, x):
         x = _f32(x)

@@ -158,6 +158,14 @@ SRT_DEV Spec operator*(Spec a, float s) { return spec(a.r * s, a.g * s, a.b * s)
 SRT_DEV float luma(Spec a) { return 0.2126f * a.r + 0.7152f * a.g + 0.0722f * a.b; }   // lib/spectrum.h:111
 SRT_DEV bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 SRT_DEV bool valid(Spec a) { return finite_f(a.r) && finite_f(a.g) && finite_f(a.b); }  // lib/spectrum.h:115
+// finite_f as one v_cmp_class_f32 on the device
+SRT_DEV bool class_finite(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_classf(v, 0x1f8);             // -normal, -denormal, -0, +0, +denormal, +normal
+#else
+  return finite_f(v);
+#endif
+}
 
 // Mat4 * Vec3 (projective, lib/mat4.h:125-131) and Mat4::rotate (w = 0; the 0*col3 term is kept).
 SRT_DEV V3 mat_point(const Mat4& m, V3 v) {
@@ -173,6 +181,33 @@ SRT_DEV V3 mat_point_uniform(const Mat4& m, V3 v) {
   float o[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) o[j] = ((m.c[0][j] * v.x + m.c[1][j] * v.y) + m.c[2][j] * v.z) + m.c[3][j] * 1.0f;
+  if (__ballot(o[3] != 1.0f) == 0ull) return v3(o[0], o[1], o[2]);
+  return v3(o[0] / o[3], o[1] / o[3], o[2] / o[3]);
+}
+// The same for a matrix that is the same in every lane (an object's trans / itrans in the leaf section of pt_wave.h): w is known to
+// be 1 without computing it.
+//   * `affine` = the bottom row is (+-0, +-0, +-0, 1) - mat_affine_row, tested once per object on the bit patterns, which for a
+//     wave-uniform matrix is integer work on the scalar unit.
+//   * For such a row and finite x, y, z: w = ((+-0 * x + +-0 * y) + +-0 * z) + 1 * 1 = +-0 + 1 = 1 exactly.
+//   * x, y and z are finite whenever o[0] is: row 0 adds a product of each of them, a non-finite factor makes its product +-inf or
+//     NaN (0 * inf included), and a sum that contains +-inf or NaN is not finite, whatever the matrix holds.
+// So with an affine row and a finite o[0] in every active lane the three rows are mat_point's result bit for bit (x / 1.0f == x);
+// one class compare stands in for the fourth row and its comparison.  Anything else computes w and goes on as mat_point_uniform.
+#ifndef SRT_POINT_AFFINE
+#define SRT_POINT_AFFINE 1
+#endif
+SRT_DEV bool mat_affine_row(const Mat4& m) {
+  return SRT_POINT_AFFINE != 0 && ((__float_as_uint(m.c[0][3]) | __float_as_uint(m.c[1][3]) | __float_as_uint(m.c[2][3])) << 1) == 0u &&
+         __float_as_uint(m.c[3][3]) == 0x3f800000u;
+}
+SRT_DEV V3 mat_point_affine(const Mat4& m, bool affine, V3 v, bool* w_skipped = nullptr) {   // (w_skipped: the probe's report)
+  float o[4];
+#pragma unroll
+  for (int j = 0; j < 3; j++) o[j] = ((m.c[0][j] * v.x + m.c[1][j] * v.y) + m.c[2][j] * v.z) + m.c[3][j] * 1.0f;
+  const bool skip = affine && __ballot(!class_finite(o[0])) == 0ull;
+  if (w_skipped) *w_skipped = skip;
+  if (skip) return v3(o[0], o[1], o[2]);
+  o[3] = ((m.c[0][3] * v.x + m.c[1][3] * v.y) + m.c[2][3] * v.z) + m.c[3][3] * 1.0f;
   if (__ballot(o[3] != 1.0f) == 0ull) return v3(o[0], o[1], o[2]);
   return v3(o[0] / o[3], o[1] / o[3], o[2] / o[3]);
 }

@@ -233,6 +233,24 @@ __global__ void pt_box_sweep_kernel(const float* __restrict__ in, size_t lanes, 
   out[3 * lanes + i] = hb ? 1.0f : 0.0f; out[4 * lanes + i] = bxx; out[5 * lanes + i] = bxy;
 }
 
+// Mat4 * Vec3 of the leaf section's point transforms (mat_point_affine, pt_device.h: w not computed for an affine wave-uniform matrix
+// and finite points) next to mat_point, one matrix per wave of 64 lanes, lane i on its own point.  Layout: srt_pt_math_point_affine.
+__global__ void pt_point_affine_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= lanes) return;                               // (whole waves: lanes % 64 == 0)
+  Mat4 m;
+#pragma unroll
+  for (int j = 0; j < 16; j++) m.c[j / 4][j % 4] = in[(i / 64) * 16 + j];
+  const float* pl = in + (lanes / 64) * 16;
+  const V3 v = v3(pl[i], pl[lanes + i], pl[2 * lanes + i]);
+  bool skipped = false;
+  const V3 a = mat_point_affine(m, mat_affine_row(m), v, &skipped);
+  const V3 b = mat_point(m, v);
+  out[i] = a.x; out[lanes + i] = a.y; out[2 * lanes + i] = a.z;
+  out[3 * lanes + i] = b.x; out[4 * lanes + i] = b.y; out[5 * lanes + i] = b.z;
+  out[6 * lanes + i] = skipped ? 1.0f : 0.0f;
+}
+
 }  // namespace srt
 
 using namespace srt;
@@ -345,6 +363,12 @@ int srt_pt_math_sphere_batch(srt_pt* pt, const float* in, size_t lanes, float* o
 int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out) {
   return math_round_trip(pt, "srt_pt_math_box_sweep", {in}, 14 * lanes, {out}, 6 * lanes, [&](float* const* d, float* const* o) {
     pt_box_sweep_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_point_affine(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  if (lanes % 64) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_point_affine: %zu lanes are not whole waves of 64", lanes);
+  return math_round_trip(pt, "srt_pt_math_point_affine", {in}, (lanes / 64) * 16 + 3 * lanes, {out}, 7 * lanes, [&](float* const* d, float* const* o) {
+    pt_point_affine_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
 }
 
 }  // extern "C"

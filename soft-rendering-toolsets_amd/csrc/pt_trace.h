@@ -256,6 +256,30 @@ SRT_DEV bool box_hit_inv(const float* __restrict__ bx, V3 o, V3 inv, float& tx, 
   return hit;
 }
 
+// One (node, ray) step of the top-down sweep of pt_wave.h: both child boxes, the nearer / farther decision as in
+// student/bvh.inl:186-209 (both hit -> smaller entry time first, ties: right; one hit -> that one, the other child gets
+// ray.dist_bounds as its `times`), and the `times` for the children.  Returns the node's four flag bits {1 left hit, 2 right hit,
+// 4 left nearer, 8 both}; farx = cur_far_t.x; (lx, ly) / (rx, ry) = `times` of the children.
+// (mask algebra, not `hb ? (t1x < t2x) : hl`: a bool chosen by a bool goes through a 0 / 1 register and back)
+SRT_DEV uint32_t topdown_step(const WaveInterior& W, V3 org, V3 inv, float tx, float ty, float rb0, float rb1,
+                              float& farx, float& lx, float& ly, float& rx, float& ry) {
+  float t1x = tx, t1y = ty, t2x = tx, t2y = ty;
+  const bool hl = box_hit_inv(W.boxl, org, inv, t1x, t1y);
+  const bool hr = box_hit_inv(W.boxr, org, inv, t2x, t2y);
+  const bool hb = hl & hr;
+  const bool cl = (hb & (t1x < t2x)) | (!hb & hl);
+  // closer = (cl ? t1 : t2), second = hb ? (cl ? t2 : t1) : dist_bounds, and the left child is the closer one iff cl.  Written out
+  // per child: the left one gets its own box's times iff that box was hit (cl | hb == hl), the right one iff its box was hit or
+  // neither was (!cl | hb == hr | !hl; a missed box leaves `times` as they came), and dist_bounds otherwise - one select per
+  // field, where choosing closer / second first and handing them out afterwards is three.  The same bits: selects only
+  // (tests/test_pt_topdown_step_host.py holds it to the long form over every flag combination).
+  const bool own_l = hl, own_r = hr | !hl;
+  farx = hb ? (cl ? t2x : t1x) : rb0;
+  lx = own_l ? t1x : rb0; ly = own_l ? t1y : rb1;
+  rx = own_r ? t2x : rb0; ry = own_r ? t2y : rb1;
+  return (hl ? 1u : 0u) | (hr ? 2u : 0u) | (cl ? 4u : 0u) | (hb ? 8u : 0u);
+}
+
 // find_closest_hit of one BVH<Triangle> over its interior records: one 64-byte fetch brings both child boxes,
 // leaves are folded in place, a stack frame is 16 bytes (after the nearer child returns, its result reuses
 // the slots of cur_far_t).  Same visit rule and Trace::min as traverse<>().

@@ -147,7 +147,8 @@ SRT_DEV uint32_t tile_slot(const TileMap& T, uint32_t p) {
   return local_tile * px_per_tile + ly * T.tile_w + lx;
 }
 
-// (mat_point_uniform, Mat4 * Vec3 without the divide by a w of 1: pt_device.h, after mat_point)
+// (mat_point_uniform, Mat4 * Vec3 without the divide by a w of 1, and mat_point_affine, the same without computing that w for a
+//  wave-uniform affine matrix: pt_device.h, after mat_point)
 
 // (box_hit_inv, the sweeps' BBox::hit: pt_trace.h, after box_hit_rec)
 // (kRetMiss / kRetMissEnv and the two-word PHit the sweeps carry: pt_trace.h)
@@ -183,7 +184,7 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
 #pragma unroll
   for (int r = 0; r < NR; r++) { od[r] = d[r]; ob0[r] = rb0[r]; ob1[r] = rb1[r]; }
   if (xf) {                                           // Ray::transform with the shared origin
-    oorg = mat_point_uniform(o.itrans, org);
+    oorg = mat_point_affine(o.itrans, mat_affine_row(o.itrans), org);   // (the object's matrices are wave-uniform: pt_device.h)
     float n2[NR], dn[NR], num[NR][3], q[NR][3];
     bool nz[NR];
 #pragma unroll
@@ -305,13 +306,14 @@ SRT_DEV void object_testN(const DScene& S, uint32_t k, V3 org, const V3* d, cons
 #pragma unroll
   for (int r = 0; r < NR; r++) any = any | hit[r];
   if (xf && __ballot(any) != 0ull) {
-    const V3 ow = mat_point_uniform(o.trans, oorg);   // Trace::transform: distance = |T*position - T*origin|
+    const bool affine = mat_affine_row(o.trans);
+    const V3 ow = mat_point_affine(o.trans, affine, oorg);   // Trace::transform: distance = |T*position - T*origin|
     float n2[NR], nr[NR];
     bool miss[NR];                                    // the same point twice: exactly +0
 #pragma unroll
     for (int r = 0; r < NR; r++) {
       const V3 p = hit[r] ? pos[r] : oorg;            // lanes without a hit transform a harmless point
-      n2[r] = norm2(mat_point_uniform(o.trans, p) - ow);
+      n2[r] = norm2(mat_point_affine(o.trans, affine, p) - ow);
       miss[r] = !hit[r];
     }
     sqrtN<NR>(n2, miss, nr);
@@ -939,30 +941,27 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         const float dn = norm(d[r]);
         tx0[r] = rb0[r] / dn; ty0[r] = rb1[r] / dn;   // Vec2 time_initial = dist_bounds / dir.norm()
       }
-      // top-down: box tests, nearer/farther decision, hand `times` down
-      for (uint32_t q = 0; q < Q; q++) {
-        const WaveInterior& W = S.wave_tlas[q];
+      // top-down: box tests, nearer/farther decision, hand `times` down (topdown_step, pt_trace.h)
+      // (The loop sits in a lambda that is called at once.  Same arithmetic either way, but with the loop written inline this
+      //  compiler keeps more scalars alive across it and spills them: 420 v_readlane / v_writelane in the Cornell kernel against
+      //  350 - the parent has 336 - and half of what the leaf section's point transforms gain is lost again)
+      auto topdown = [&]() {
+        for (uint32_t q = 0; q < Q; q++) {
+          const WaveInterior& W = S.wave_tlas[q];
 #pragma unroll
-        for (int r = 0; r < NR; r++) {
-          float tx = tx0[r], ty = ty0[r];
-          if (q != 0) { tx = SLOT(q, r, 0); ty = SLOT(q, r, 1); }
-          float t1x = tx, t1y = ty, t2x = tx, t2y = ty;
-          const bool hl = box_hit_inv(W.boxl, org, inv[r], t1x, t1y);
-          const bool hr = box_hit_inv(W.boxr, org, inv[r], t2x, t2y);
-          // closer/second as in student/bvh.inl:186-209: both hit -> smaller entry time first (ties: right);
-          // one hit -> that one, the other child gets ray.dist_bounds as its `times`
-          // (mask algebra, not `hb ? (t1x < t2x) : hl`: a bool chosen by a bool goes through a 0 / 1 register and back)
-          const bool hb = hl & hr;
-          const bool cl = (hb & (t1x < t2x)) | (!hb & hl);
-          const float cx = cl ? t1x : t2x, cy = cl ? t1y : t2y;
-          const float fx = hb ? (cl ? t2x : t1x) : rb0[r];
-          const float fy = hb ? (cl ? t2y : t1y) : rb1[r];
-          fl[r] |= (unsigned long long)((hl ? 1u : 0u) | (hr ? 2u : 0u) | (cl ? 4u : 0u) | (hb ? 8u : 0u)) << (4 * q);
-          if (q != 0) SLOT(q, r, 0) = fx; else farx0[r] = fx;
-          if (W.l_ref >= 0) { SLOT(W.l_ref, r, 0) = cl ? cx : fx; SLOT(W.l_ref, r, 1) = cl ? cy : fy; }
-          if (W.r_ref >= 0) { SLOT(W.r_ref, r, 0) = cl ? fx : cx; SLOT(W.r_ref, r, 1) = cl ? fy : cy; }
+          for (int r = 0; r < NR; r++) {
+            float tx = tx0[r], ty = ty0[r];
+            if (q != 0) { tx = SLOT(q, r, 0); ty = SLOT(q, r, 1); }
+            float fx, lx, ly, rx, ry;
+            const uint32_t f = topdown_step(W, org, inv[r], tx, ty, rb0[r], rb1[r], fx, lx, ly, rx, ry);
+            fl[r] |= (unsigned long long)f << (4 * q);
+            if (q != 0) SLOT(q, r, 0) = fx; else farx0[r] = fx;
+            if (W.l_ref >= 0) { SLOT(W.l_ref, r, 0) = lx; SLOT(W.l_ref, r, 1) = ly; }
+            if (W.r_ref >= 0) { SLOT(W.r_ref, r, 0) = rx; SLOT(W.r_ref, r, 1) = ry; }
+          }
         }
-      }
+      };
+      topdown();
       SECTION_END(ST_TOPDOWN)
       // bottom-up: leaves are evaluated in place, interior children read back, then the visit rule + Trace::min
       for (int q = (int)Q - 1; q >= 0; q--) {
