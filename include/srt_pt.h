@@ -571,6 +571,51 @@ int srt_pt_skin_pose_refit_at(srt_pt_skin* skin, void* stream, float t, int flat
  * buffer per copy still on its way), so that copy too is only enqueued and `posed` is not read after the call returns. */
 int srt_pt_skin_pose_inplace(srt_pt_skin* skin, void* stream, const float* posed, int flat_normals);
 int srt_pt_skin_pose_inplace_at(srt_pt_skin* skin, void* stream, float t, int flat_normals);
+/* ---- IK handles: Skeleton::do_ik / step_ik on the device ----
+ * A skin with a rig keeps the CURRENT Joint::pose of every joint on the device (3 Euler angles in degrees per joint, the joints'
+ * order), with a mirror on the host that an enqueue-only call leaves behind and the next host read settles.  srt_pt_skin_set_rig
+ * sets it to the rest pose (and drops the handles: the hierarchy they were made for is gone).  The `_at(t)` calls above neither
+ * read nor write it.  The calls below change it as the reference's Animate mode does - Skeleton::set_time, then Skeleton::do_ik -
+ * and skin from it, so that targets -> IK -> skin -> refit -> render is one stream's work.
+ *   The arithmetic is Skeleton::step_ik with Joint::compute_gradient (student/skeleton.cpp:117-191) operation for operation: exactly
+ * 50 iterations with tau = 1 / 50.0f, and per joint the gradient summed from 0.0f over the enabled handles whose chain holds the
+ * joint IN THE ORDER OF THE HANDLE LIST - that order is part of the result.  Results equal the reference's bit for bit while every
+ * angle stays below the 6875 degrees of the sin / cos restatement (NaN beyond).  Targets and poses are not checked for NaN / Inf: the
+ * rig computes what the reference computes.  Limits (SRT_ERR_UNSUPPORTED beyond): the skin's 4096 joints, and 1024 handles per skin.
+ *
+ * srt_pt_skin_set_ik_handles: the joints of the handles (indices into the skin's joints), in the order Skeleton::do_ik visits
+ * them; n == 0 clears.  Builds, once per handle set, the per-joint lists of the handles whose chain holds the joint, and uploads
+ * them with the list (waits).  SRT_ERR_STATE without a rig; SRT_ERR_INVALID for NULL or a joint out of range, SRT_ERR_UNSUPPORTED for
+ * more than 1024 handles: the skin keeps the handles it had. */
+int srt_pt_skin_set_ik_handles(srt_pt_skin* skin, const uint32_t* joints, uint32_t n);
+/* Write and read the current pose: njoints * 3 host floats.  Both wait for the device; the read settles the mirror. */
+int srt_pt_skin_set_joint_pose(srt_pt_skin* skin, const float* euler3);
+int srt_pt_skin_joint_pose(srt_pt_skin* skin, float* euler3_out);
+/* Skeleton::set_time(t) on the current pose (scene/skeleton.cpp:47-54), ENQUEUE-ONLY on `stream`: a joint with keys takes
+ * anim.at(t).to_euler(); a joint without keys keeps its current pose - IK's changes included, as in the reference; it does not go
+ * back to the rest pose.  (Handle keys, h->anim, stay with the caller: the reference's set_time only copies them into target /
+ * enabled, which are arguments here.) */
+int srt_pt_skin_set_time(srt_pt_skin* skin, void* stream, float t);
+/* Skeleton::do_ik once: targets3 holds 3 floats per handle (IK_Handle::target, skeleton space - no base_pos), enabled one byte per
+ * handle (nonzero: enabled; NULL: every handle).  With no handle enabled the poses keep their bits (do_ik returns before step_ik).
+ * The host form uploads both, runs the kernel on the context's stream and waits.  SRT_ERR_STATE without a rig or without handles. */
+int srt_pt_skin_step_ik(srt_pt_skin* skin, const float* targets3, const uint8_t* enabled);
+/* The same with both arrays in device memory (d_enabled: srt_pt_set_active_device's byte convention; NULL: every handle),
+ * ENQUEUE-ONLY under srt_pt_skin_pose_inplace's contract: one launch on `stream` does all 50 iterations; nothing is read from host
+ * memory, nothing is uploaded, and there is no synchronisation. */
+int srt_pt_skin_step_ik_device(srt_pt_skin* skin, void* stream, const float* d_targets3, const uint8_t* d_enabled);
+/* Skeleton::joint_to_posed(j) (with base_pos) of every joint from the current pose: srt_pt_skin_posed / srt_pt_skin_posed_device
+ * without a time.  The host form settles the mirror (waits) and computes on the host. */
+int srt_pt_skin_posed_current(srt_pt_skin* skin, float* posed_out);
+int srt_pt_skin_posed_current_device(srt_pt_skin* skin, void* stream, float* d_posed_out);
+/* srt_pt_skin_vertices_at_device, and srt_pt_skin_pose_at / srt_pt_skin_pose_refit_at / srt_pt_skin_pose_inplace_at selected by `how`,
+ * fed from the current pose instead of from time t: the same kernels, only the source of the Euler angles differs.  Waits,
+ * refusals and counters are those of the `_at` call that `how` selects; SRT_ERR_INVALID for another `how`. */
+#define SRT_PT_SKIN_UPDATE 0  /* srt_pt_update_mesh_device: the BVH<Triangle> rebuilt */
+#define SRT_PT_SKIN_REFIT 1   /* srt_pt_refit_mesh_device */
+#define SRT_PT_SKIN_INPLACE 2 /* srt_pt_refit_mesh_inplace_device: enqueue-only */
+int srt_pt_skin_vertices_current_device(srt_pt_skin* skin, void* stream, int flat_normals, float* d_positions_out, float* d_normals_out);
+int srt_pt_skin_pose_current(srt_pt_skin* skin, void* stream, int flat_normals, int how);
 /* Every call on a skin but destroy and counts returns SRT_ERR_STATE once its context's scene was begun or committed again (the
  * skin is stale: destroy it, create another), and SRT_ERR_INVALID for a NULL argument. */
 /* ---- Timelines: the Animate mode's keyframes evaluated on the device ----

@@ -121,6 +121,13 @@ int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, floa
  * Joint::pose after set_time, posed_out 16 floats per joint.  SRT_ERR_INVALID as for srt_pt_skin_set_rig. */
 int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* extents, const float base[3], const float* rest_pose,
                           const uint32_t* knot_offsets, const float* knot_times, const float* knot_quats, float t, float* euler_out, float* posed_out);
+/* What srt_pt_skin_step_ik computes, without a skin or a context: Skeleton::do_ik `calls` times on pose_inout (3 floats per joint,
+ * in place) for a hierarchy as srt_pt_skin_set_rig takes it (parents first), the joints' extents (3 floats each), the handles'
+ * joints in do_ik's order, their targets (3 floats each, skeleton space) and enabled bytes (NULL: every handle).  The same functions
+ * the kernel runs (pt_ik.h), on the host.  SRT_ERR_INVALID for a NULL argument, a parent out of order or a handle's joint out of
+ * range; SRT_ERR_UNSUPPORTED beyond 4096 joints or 1024 handles; pose_inout is untouched then. */
+int srt_pt_rig_step_ik_host(uint32_t njoints, const int32_t* parent, const float* extents, float* pose_inout, const uint32_t* handle_joints,
+                            const float* targets, const uint8_t* enabled, uint32_t nhandles, uint32_t calls);
 
 /* The epilogue's expf / powf (glibc 2.35's algorithms restated, FMA build) evaluated on the device. */
 int srt_pt_math_exp(srt_pt* pt, const float* x, size_t n, float* out);

@@ -95,6 +95,17 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_skin_pose_at.argtypes = [c_void_p, c_void_p, c_float, c_int]
     lib.srt_pt_skin_pose_refit_at.argtypes = [c_void_p, c_void_p, c_float, c_int]
     lib.srt_pt_rig_posed_host.argtypes = [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p]
+    lib.srt_pt_skin_set_ik_handles.argtypes = [c_void_p, c_void_p, c_uint32]
+    lib.srt_pt_skin_set_joint_pose.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_skin_joint_pose.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_skin_set_time.argtypes = [c_void_p, c_void_p, c_float]
+    lib.srt_pt_skin_step_ik.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_skin_step_ik_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_skin_posed_current.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_skin_posed_current_device.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_skin_vertices_current_device.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.srt_pt_skin_pose_current.argtypes = [c_void_p, c_void_p, c_int, c_int]
+    lib.srt_pt_rig_step_ik_host.argtypes = [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32]
     lib.srt_pt_math_hypot.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_live_resources.argtypes = [c_void_p]
     lib.srt_pt_timeline_create.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -320,6 +331,72 @@ class Skin:
         """srt_pt_skin_pose_refit_at: pose_refit() with the matrices of time t computed on the device from the rig."""
         self._check(self._lib, self._lib.srt_pt_skin_pose_refit_at(self._h, c_void_p(stream), float(t), int(bool(flat_normals))))
 
+    # ---- the current Joint::pose and the IK handles (Skeleton::set_time, Skeleton::do_ik) ----
+    HOW = {"update": 0, "refit": 1, "inplace": 2}          # SRT_PT_SKIN_UPDATE / _REFIT / _INPLACE
+
+    def set_ik_handles(self, joints) -> None:
+        """srt_pt_skin_set_ik_handles: the handles' joints in the order Skeleton::do_ik visits them (that order is part of the
+        result); an empty list clears."""
+        joints = np.ascontiguousarray(joints, np.uint32).reshape(-1)
+        self._check(self._lib, self._lib.srt_pt_skin_set_ik_handles(self._h, _p(joints) if len(joints) else None, len(joints)))
+        self.nhandles = len(joints)
+
+    def set_joint_pose(self, euler) -> None:
+        """srt_pt_skin_set_joint_pose: the current Joint::pose, (njoints, 3) Euler angles in degrees."""
+        euler = _f32(euler).reshape(-1, 3)
+        if len(euler) != self.njoints:
+            raise ValueError(f"{len(euler)} poses for {self.njoints} joints")
+        self._check(self._lib, self._lib.srt_pt_skin_set_joint_pose(self._h, _p(euler)))
+
+    def joint_pose(self) -> np.ndarray:
+        """srt_pt_skin_joint_pose: the current Joint::pose, (njoints, 3); waits for what was enqueued."""
+        out = np.zeros((self.njoints, 3), np.float32)
+        self._check(self._lib, self._lib.srt_pt_skin_joint_pose(self._h, _p(out)))
+        return out
+
+    def set_time(self, t: float, stream: int = 0) -> None:
+        """srt_pt_skin_set_time: Skeleton::set_time(t) on the current pose - keyed joints take their keys' value, the others keep
+        what they have; only enqueues."""
+        self._check(self._lib, self._lib.srt_pt_skin_set_time(self._h, c_void_p(stream), float(t)))
+
+    def _handle_arrays(self, targets, enabled):
+        n = getattr(self, "nhandles", 0)
+        targets = _f32(targets).reshape(-1, 3)
+        if enabled is not None:
+            enabled = np.ascontiguousarray(enabled, np.uint8).reshape(-1)
+        if n and (len(targets) != n or (enabled is not None and len(enabled) != n)):
+            raise ValueError(f"{len(targets)} targets and {None if enabled is None else len(enabled)} enabled bytes for {n} handles")
+        return targets, enabled
+
+    def step_ik(self, targets, enabled=None) -> None:
+        """srt_pt_skin_step_ik: Skeleton::do_ik once - 50 iterations towards `targets` ((nhandles, 3), skeleton space) for the handles
+        whose `enabled` byte is nonzero (None: all); uploads, runs the kernel, waits."""
+        targets, enabled = self._handle_arrays(targets, enabled)
+        self._check(self._lib, self._lib.srt_pt_skin_step_ik(self._h, _p(targets), None if enabled is None else _p(enabled)))
+
+    def step_ik_device(self, d_targets_ptr: int, d_enabled_ptr: int = 0, stream: int = 0) -> None:
+        """srt_pt_skin_step_ik_device: the same with targets (nhandles * 3 floats) and enabled bytes (0: all) in device memory; one
+        launch, only enqueued."""
+        self._check(self._lib, self._lib.srt_pt_skin_step_ik_device(self._h, c_void_p(stream), c_void_p(d_targets_ptr), c_void_p(d_enabled_ptr or None)))
+
+    def posed_current(self) -> np.ndarray:
+        """srt_pt_skin_posed_current: Skeleton::joint_to_posed of every joint from the current pose, (njoints, 16)."""
+        out = np.zeros((self.njoints, 16), np.float32)
+        self._check(self._lib, self._lib.srt_pt_skin_posed_current(self._h, _p(out)))
+        return out
+
+    def posed_current_device(self, d_posed_ptr: int, stream: int = 0) -> None:
+        self._check(self._lib, self._lib.srt_pt_skin_posed_current_device(self._h, c_void_p(stream), c_void_p(d_posed_ptr)))
+
+    def vertices_current_device(self, d_pos_ptr: int, d_nrm_ptr: int, flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_vertices_current_device: vertices_at_device from the current pose."""
+        self._check(self._lib, self._lib.srt_pt_skin_vertices_current_device(self._h, c_void_p(stream), int(bool(flat_normals)), c_void_p(d_pos_ptr),
+                                                                             c_void_p(d_nrm_ptr)))
+
+    def pose_current(self, how: str = "inplace", flat_normals: bool = False, stream: int = 0) -> None:
+        """srt_pt_skin_pose_current: pose_at ("update"), pose_refit_at ("refit") or pose_inplace_at ("inplace") from the current pose."""
+        self._check(self._lib, self._lib.srt_pt_skin_pose_current(self._h, c_void_p(stream), int(bool(flat_normals)), self.HOW[how]))
+
     def close(self) -> None:
         if self._h:
             self._lib.srt_pt_skin_destroy(self._h)
@@ -386,6 +463,41 @@ class SkinGroup:
     def pose_refit_at(self, t: float, flat_normals: bool = False) -> None:
         for k in self.skins:
             k.pose_refit_at(t, flat_normals)
+
+    def set_ik_handles(self, joints) -> None:
+        for k in self.skins:
+            k.set_ik_handles(joints)
+
+    def set_joint_pose(self, euler) -> None:
+        for k in self.skins:
+            k.set_joint_pose(euler)
+
+    def joint_pose(self) -> np.ndarray:
+        return self.skins[0].joint_pose()
+
+    def set_time(self, t: float) -> None:
+        for k in self.skins:
+            k.set_time(t)
+
+    def step_ik(self, targets, enabled=None) -> None:
+        """Every rank's skin takes the same step: the ranks' poses stay the same bits."""
+        for k in self.skins:
+            k.step_ik(targets, enabled)
+
+    def step_ik_device(self, d_targets_ptrs, d_enabled_ptrs=None) -> None:
+        """Skin.step_ik_device on every rank, with one device array per rank (ranks that share a device may share it)."""
+        for r, k in enumerate(self.skins):
+            k.step_ik_device(d_targets_ptrs[r], d_enabled_ptrs[r] if d_enabled_ptrs else 0)
+
+    def posed_current(self) -> np.ndarray:
+        return self.skins[0].posed_current()
+
+    def pose_current(self, how: str = "inplace", flat_normals: bool = False) -> None:
+        """Skin.pose_current on every rank; with "inplace" every member is settled before this returns (see pose_inplace)."""
+        for k in self.skins:
+            k.pose_current(how, flat_normals)
+        if how == "inplace":
+            self._settle()
 
     def close(self) -> None:
         for k in self.skins:

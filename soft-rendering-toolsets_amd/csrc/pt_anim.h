@@ -241,10 +241,10 @@ SRT_ANIM_FN AnimV3 anim_joint_pose(const float* rest_pose, const uint32_t* knot_
 // Skeleton::joint_to_posed(j) (student/skeleton.cpp:106-115) = translate(base_pos) * Joint::joint_to_posed (:26-52): from
 // iter = euler(pose_j), for every ancestor from the parent up to the root iter = translate(extent) * iter, then iter = euler(pose) *
 // iter.  local: Mat4::euler(pose) per joint, 16 floats each; cap: the skin's {extent, radius}, 4 floats per joint; parent[j] < j or -1.  The walk is as long
-// as the joint is deep and never longer than njoints.
-SRT_ANIM_FN void anim_joint_to_posed(const int32_t* parent, const float* cap, const float* base, const float* local, uint32_t njoints, uint32_t j,
-                                     float* posed) {
-  float iter[16], next[16], tr[16];
+// as the joint is deep and never longer than njoints.  anim_joint_chain is the walk alone - Joint::joint_to_posed, skeleton space,
+// what Skeleton::step_ik reads (pt_ik.h).
+SRT_ANIM_FN void anim_joint_chain(const int32_t* parent, const float* cap, const float* local, uint32_t njoints, uint32_t j, float* iter) {
+  float next[16], tr[16];
   for (int i = 0; i < 16; i++) iter[i] = local[16 * (size_t)j + i];
   int32_t cur = parent[j];
   for (uint32_t step = 0; cur >= 0 && (uint32_t)cur < njoints && step < njoints; step++) {
@@ -253,6 +253,12 @@ SRT_ANIM_FN void anim_joint_to_posed(const int32_t* parent, const float* cap, co
     skin_mat4_mul(local + 16 * (size_t)cur, next, iter);
     cur = parent[cur];
   }
+}
+
+SRT_ANIM_FN void anim_joint_to_posed(const int32_t* parent, const float* cap, const float* base, const float* local, uint32_t njoints, uint32_t j,
+                                     float* posed) {
+  float iter[16], tr[16];
+  anim_joint_chain(parent, cap, local, njoints, j, iter);
   anim_mat4_translate(anim_v3(base), tr);
   skin_mat4_mul(tr, iter, posed);
 }
@@ -393,6 +399,9 @@ void launch_anim_pose(void* stream, const uint32_t* d_track_offsets, const float
 void launch_anim_joints(void* stream, const int32_t* d_parent, const float* d_cap, const float* d_base, const float* d_rest_pose, const uint32_t* d_knot_offsets,
                         const float* d_times, const float* d_quats, uint32_t njoints, float t, float* d_local, const float* d_inv, float* d_mats,
                         float* d_posed_out);
+// The same two kernels with Mat4::euler of d_pose (3 floats per joint: the skin's current Joint::pose) in the place of set_time(t)'s angles
+void launch_anim_joints_pose(void* stream, const int32_t* d_parent, const float* d_cap, const float* d_base, const float* d_pose, uint32_t njoints,
+                             float* d_local, const float* d_inv, float* d_mats, float* d_posed_out);
 // srt_pt_shading_timeline_apply: one lane per item, materials first, then lights.  Lane k < nmaterials writes a, b and ior of
 // d_mats[d_materials[k]] (anim_material_item, anim_material_store; the type is read from the record and stays); lane nmaterials + j
 // writes radiance and angle_bounds (option keys) and trans, itrans, has_trans (pose keys) of d_dlights[d_lights[j]].  The track

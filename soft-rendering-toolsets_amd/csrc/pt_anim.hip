@@ -34,6 +34,15 @@ __global__ __launch_bounds__(kBlock) void anim_joint_local_kernel(const float* _
   for (int i = 0; i < 16; i++) local[16 * (size_t)j + i] = m[i];
 }
 
+// The same from the skin's current Joint::pose (srt_pt_skin_*_current): only the source of the Euler angles differs.
+__global__ __launch_bounds__(kBlock) void anim_joint_local_pose_kernel(const float* __restrict__ pose, uint32_t njoints, float* __restrict__ local) {
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= njoints) return;
+  float m[16];
+  anim_mat4_euler(anim_v3(pose + 3 * (size_t)j), m);
+  for (int i = 0; i < 16; i++) local[16 * (size_t)j + i] = m[i];
+}
+
 __global__ __launch_bounds__(kBlock) void anim_joint_chain_kernel(const int32_t* __restrict__ parent, const float* __restrict__ cap,
                                                                  const float* __restrict__ base, const float* __restrict__ local, uint32_t njoints,
                                                                  const float* __restrict__ inv, float* __restrict__ mats, float* __restrict__ posed_out) {
@@ -104,6 +113,13 @@ void launch_anim_joints(void* stream, const int32_t* d_parent, const float* d_ca
                         float* d_posed_out) {
   if (!njoints) return;
   anim_joint_local_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_rest_pose, d_knot_offsets, d_times, d_quats, njoints, t, d_local);
+  anim_joint_chain_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_parent, d_cap, d_base, d_local, njoints, d_inv, d_mats, d_posed_out);
+}
+
+void launch_anim_joints_pose(void* stream, const int32_t* d_parent, const float* d_cap, const float* d_base, const float* d_pose, uint32_t njoints,
+                             float* d_local, const float* d_inv, float* d_mats, float* d_posed_out) {
+  if (!njoints) return;
+  anim_joint_local_pose_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_pose, njoints, d_local);
   anim_joint_chain_kernel<<<grid_for(njoints), dim3(kBlock), 0, (hipStream_t)stream>>>(d_parent, d_cap, d_base, d_local, njoints, d_inv, d_mats, d_posed_out);
 }
 

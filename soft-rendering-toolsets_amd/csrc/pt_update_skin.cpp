@@ -1,12 +1,14 @@
 // Skins and rigs on a committed mesh: Skeleton::find_joints once (srt_pt_skin_create), Skeleton::skin per frame from the caller's
-// matrices or from the rig's keys (srt_pt_skin_set_rig), into the caller's arrays or - through update_mesh / refit_mesh - into the
-// scene.  Host code only: the kernels are in pt_skin.hip and pt_anim.hip, the joint arithmetic both sides share in pt_skin.h and pt_anim.h.
+// matrices, from the rig's keys (srt_pt_skin_set_rig) or from the current pose that IK handles drive (srt_pt_skin_step_ik), into the
+// caller's arrays or - through update_mesh / refit_mesh - into the scene.  Host code only: the kernels are in pt_skin.hip, pt_anim.hip
+// and pt_ik.hip, the joint arithmetic both sides share in pt_skin.h, pt_anim.h and pt_ik.h.
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "pt_anim.h"
+#include "pt_ik.h"
 #include "pt_skin.h"
 #include "pt_update.h"
 #include "srt_pt_debug.h"
@@ -35,14 +37,31 @@ struct srt_pt_skin : SceneHandle {
   DeviceBuffer<int32_t> d_parent;
   DeviceBuffer<uint32_t> d_knot_offsets;
   DeviceBuffer<float> d_base, d_rest_pose, d_knot_times, d_knot_quats, d_local;
+  // The current Joint::pose, 3 floats per joint (srt_pt_skin_set_rig: the rest pose), which srt_pt_skin_set_time and srt_pt_skin_step_ik*
+  // change and the *_current calls read; the `_at` calls neither read nor write it.  `pose` is the host's mirror: an enqueue-only call
+  // leaves it behind (pose_lags) and the next host read settles it.  The IK handles: their joints in do_ik's order and, per joint, the
+  // handles whose chain holds it (ik_build_csr), on both sides.
+  std::vector<float> pose;
+  bool pose_lags = false;
+  std::vector<uint32_t> ik_joints, ik_off, ik_list;
+  DeviceBuffer<float> d_pose, d_ik_scratch, d_ik_targets;
+  DeviceBuffer<uint8_t> d_ik_enabled;
+  DeviceBuffer<uint32_t> d_ik_joints, d_ik_off, d_ik_list;
 };
 
 namespace {
 
+void skin_drop_handles(srt_pt_skin* k) {
+  k->ik_joints.clear(); k->ik_off.clear(); k->ik_list.clear();
+  k->d_ik_joints.reset(); k->d_ik_off.reset(); k->d_ik_list.reset(); k->d_ik_targets.reset(); k->d_ik_enabled.reset();
+}
+
 // What srt_pt_skin_set_rig put on the device goes (the caller has waited for what reads it).
 void skin_drop_rig(srt_pt_skin* k) {
   k->d_parent.reset(); k->d_knot_offsets.reset(); k->d_base.reset(); k->d_rest_pose.reset(); k->d_knot_times.reset(); k->d_knot_quats.reset(); k->d_local.reset();
+  k->d_pose.reset(); k->d_ik_scratch.reset();
   k->rigged = false;
+  skin_drop_handles(k);
 }
 
 // The device side of srt_pt_skin_create.
@@ -172,11 +191,50 @@ int skin_pose_at(srt_pt_skin* skin, const char* what, void* stream, float t, int
 }
 
 // What srt_pt_skin_set_rig refuses about its arrays, as a message (empty: nothing).
-std::string check_rig(uint32_t njoints, const int32_t* parent, const uint32_t* knot_offsets, const float* knot_times) {
+std::string check_parents(uint32_t njoints, const int32_t* parent) {
   for (uint32_t j = 0; j < njoints; j++)
     if (parent[j] < -1 || parent[j] >= (int32_t)j)
       return "joint " + std::to_string(j) + " has parent " + std::to_string(parent[j]) + " (-1, or a joint in front of it: parents come first, as Skeleton::for_joints visits them)";
+  return std::string();
+}
+
+std::string check_rig(uint32_t njoints, const int32_t* parent, const uint32_t* knot_offsets, const float* knot_times) {
+  const std::string refused = check_parents(njoints, parent);
+  if (!refused.empty()) return refused;
   return anim_check_tracks(knot_offsets, njoints, 1, knot_times, false, "joint");
+}
+
+// The host's mirror of the current pose, read back when an enqueue-only call has left it behind (waits).
+int pose_settle(srt_pt_skin* k) {
+  if (!k->pose_lags) return SRT_OK;
+  SRT_HIP(quiesce(k->pt));
+  SRT_HIP(hipMemcpy(k->pose.data(), k->d_pose, k->pose.size() * sizeof(float), hipMemcpyDeviceToHost));
+  k->pose_lags = false;
+  return SRT_OK;
+}
+
+// The skin's matrices from the current pose on s, then the skinning kernels: skin_enqueue_at with another source of Euler angles.
+int skin_enqueue_current(srt_pt_skin* k, const char* what, hipStream_t s, int flat_normals, float* d_pos_out, float* d_nrm_out) {
+  const int rigged = skin_rigged(k, what);
+  if (rigged != SRT_OK) return rigged;
+  SRT_HIP(hipSetDevice(k->pt->device));
+  launch_anim_joints_pose(s, k->d_parent, k->d_cap, k->d_base, k->d_pose, k->njoints, k->d_local, k->d_inv, k->d_mats, nullptr);
+  skin_launch(k, s, flat_normals, d_pos_out, d_nrm_out);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+// A rigged skin with handles, for srt_pt_skin_step_ik*.
+int skin_has_handles(const srt_pt_skin* k, const char* what) {
+  const int rigged = skin_rigged(k, what);
+  if (rigged != SRT_OK) return rigged;
+  if (k->ik_joints.empty()) return srt::fail(SRT_ERR_STATE, "%s: the skin has no IK handles (srt_pt_skin_set_ik_handles)", what);
+  return SRT_OK;
+}
+
+void ik_launch(srt_pt_skin* k, hipStream_t s, const float* d_targets, const uint8_t* d_enabled) {
+  launch_ik_step(s, k->d_parent, k->d_cap, k->njoints, k->d_ik_joints, (uint32_t)k->ik_joints.size(), k->d_ik_off, k->d_ik_list, d_targets, d_enabled, k->d_ik_scratch, k->d_pose);
+  k->pose_lags = true;
 }
 
 }  // namespace
@@ -289,6 +347,14 @@ int srt_pt_skin_set_rig(srt_pt_skin* skin, const int32_t* parent, const float ba
     (void)hipGetLastError();
     return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
   }
+  // the current pose starts as the rest pose (device to device: nothing more goes up)
+  if (skin->d_pose.ensure(3 * (size_t)nj) || skin->d_ik_scratch.ensure((size_t)kIkJointFloats * nj)) {
+    (void)hipGetLastError();
+    return srt::fail(SRT_ERR_HIP, "%s: out of device memory", what);
+  }
+  SRT_HIP(hipMemcpy(skin->d_pose, skin->d_rest_pose, 3 * (size_t)nj * sizeof(float), hipMemcpyDeviceToDevice));
+  skin->pose = skin->rest_pose;
+  skin->pose_lags = false;
   skin->rigged = true;
   return SRT_OK;
 }
@@ -340,6 +406,151 @@ int srt_pt_skin_pose_inplace_at(srt_pt_skin* skin, void* stream, float t, int fl
   const int st = skin_enqueue_at(skin, what, (hipStream_t)stream, t, flat_normals, skin->d_pos_out, skin->d_nrm_out);
   if (st != SRT_OK) return st;
   return refit_mesh_inplace_device(skin->pt, what, (hipStream_t)stream, skin->object, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
+}
+
+int srt_pt_skin_set_ik_handles(srt_pt_skin* skin, const uint32_t* joints, uint32_t n) {
+  const char* what = "srt_pt_skin_set_ik_handles";
+  if (!skin || (n && !joints)) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st = skin_rigged(skin, what);
+  if (st != SRT_OK) return st;
+  if (!ik_supported(skin->njoints, n)) return srt::fail(SRT_ERR_UNSUPPORTED, "%s: %u handles (at most %u per skin)", what, n, kIkMaxHandles);
+  const std::string refused = ik_check_handles(joints, n, skin->njoints);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  srt_pt* pt = skin->pt;
+  SRT_HIP(quiesce(pt));                                   // (the handles set before may still be read)
+  skin_drop_handles(skin);
+  if (!n) return SRT_OK;
+  skin->ik_joints.assign(joints, joints + n);
+  ik_build_csr(skin->parent.data(), skin->njoints, joints, n, skin->ik_off, skin->ik_list);
+  if ((st = skin->d_ik_joints.upload(skin->ik_joints)) || (st = skin->d_ik_off.upload(skin->ik_off)) || (st = skin->d_ik_list.upload(skin->ik_list)) ||
+      (st = skin->d_ik_targets.ensure(3 * (size_t)n)) || (st = skin->d_ik_enabled.ensure(n))) {
+    skin_drop_handles(skin);
+    return st;
+  }
+  pt->bytes_uploaded += (skin->ik_joints.size() + skin->ik_off.size() + skin->ik_list.size()) * sizeof(uint32_t);
+  return SRT_OK;
+}
+
+int srt_pt_skin_set_joint_pose(srt_pt_skin* skin, const float* euler3) {
+  const char* what = "srt_pt_skin_set_joint_pose";
+  if (!skin || !euler3) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_rigged(skin, what);
+  if (st != SRT_OK) return st;
+  SRT_HIP(quiesce(skin->pt));                             // (an enqueued call may still read or write the pose)
+  SRT_HIP(hipMemcpy(skin->d_pose, euler3, skin->pose.size() * sizeof(float), hipMemcpyHostToDevice));
+  skin->pose.assign(euler3, euler3 + skin->pose.size());
+  skin->pose_lags = false;
+  skin->pt->bytes_uploaded += skin->pose.size() * sizeof(float);
+  return SRT_OK;
+}
+
+int srt_pt_skin_joint_pose(srt_pt_skin* skin, float* euler3_out) {
+  const char* what = "srt_pt_skin_joint_pose";
+  if (!skin || !euler3_out) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st = skin_rigged(skin, what);
+  if (st != SRT_OK || (st = pose_settle(skin)) != SRT_OK) return st;
+  std::memcpy(euler3_out, skin->pose.data(), skin->pose.size() * sizeof(float));
+  return SRT_OK;
+}
+
+int srt_pt_skin_set_time(srt_pt_skin* skin, void* stream, float t) {
+  const char* what = "srt_pt_skin_set_time";
+  if (!skin) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_rigged(skin, what);
+  if (st != SRT_OK) return st;
+  SRT_HIP(hipSetDevice(skin->pt->device));
+  launch_ik_set_time((hipStream_t)stream, skin->d_knot_offsets, skin->d_knot_times, skin->d_knot_quats, skin->njoints, t, skin->d_pose);
+  skin->pose_lags = true;
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_skin_step_ik(srt_pt_skin* skin, const float* targets3, const uint8_t* enabled) {
+  const char* what = "srt_pt_skin_step_ik";
+  if (!skin || !targets3) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_has_handles(skin, what);
+  if (st != SRT_OK) return st;
+  srt_pt* pt = skin->pt;
+  SRT_HIP(quiesce(pt));                                   // (an enqueue-only call on another stream may still use the pose or the staging)
+  hipStream_t s = pt->stream;
+  const size_t n = skin->ik_joints.size();
+  SRT_HIP(hipMemcpyAsync(skin->d_ik_targets, targets3, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+  if (enabled) SRT_HIP(hipMemcpyAsync(skin->d_ik_enabled, enabled, n, hipMemcpyHostToDevice, s));
+  pt->bytes_uploaded += 3 * n * sizeof(float) + (enabled ? n : 0);
+  ik_launch(skin, s, skin->d_ik_targets, enabled ? skin->d_ik_enabled.get() : nullptr);
+  SRT_HIP(hipGetLastError());
+  SRT_HIP(hipStreamSynchronize(s));
+  return pose_settle(skin);
+}
+
+int srt_pt_skin_step_ik_device(srt_pt_skin* skin, void* stream, const float* d_targets3, const uint8_t* d_enabled) {
+  const char* what = "srt_pt_skin_step_ik_device";
+  if (!skin || !d_targets3) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_has_handles(skin, what);
+  if (st != SRT_OK) return st;
+  SRT_HIP(hipSetDevice(skin->pt->device));
+  ik_launch(skin, (hipStream_t)stream, d_targets3, d_enabled);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_skin_posed_current(srt_pt_skin* skin, float* posed_out) {
+  const char* what = "srt_pt_skin_posed_current";
+  if (!skin || !posed_out) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  int st = skin_rigged(skin, what);
+  if (st != SRT_OK || (st = pose_settle(skin)) != SRT_OK) return st;
+  std::vector<float> local(16 * (size_t)skin->njoints);
+  for (uint32_t j = 0; j < skin->njoints; j++) anim_mat4_euler(anim_v3(&skin->pose[3 * (size_t)j]), &local[16 * (size_t)j]);
+  for (uint32_t j = 0; j < skin->njoints; j++)
+    anim_joint_to_posed(skin->parent.data(), skin->cap.data(), skin->base, local.data(), skin->njoints, j, posed_out + 16 * (size_t)j);
+  return SRT_OK;
+}
+
+int srt_pt_skin_posed_current_device(srt_pt_skin* skin, void* stream, float* d_posed_out) {
+  const char* what = "srt_pt_skin_posed_current_device";
+  if (!skin || !d_posed_out) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  const int st = skin_rigged(skin, what);
+  if (st != SRT_OK) return st;
+  SRT_HIP(hipSetDevice(skin->pt->device));
+  launch_anim_joints_pose((hipStream_t)stream, skin->d_parent, skin->d_cap, skin->d_base, skin->d_pose, skin->njoints, skin->d_local, skin->d_inv, nullptr, d_posed_out);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
+
+int srt_pt_skin_vertices_current_device(srt_pt_skin* skin, void* stream, int flat_normals, float* d_positions_out, float* d_normals_out) {
+  if (!skin || !d_positions_out || !d_normals_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_skin_vertices_current_device: NULL argument");
+  return skin_enqueue_current(skin, "srt_pt_skin_vertices_current_device", (hipStream_t)stream, flat_normals, d_positions_out, d_normals_out);
+}
+
+int srt_pt_skin_pose_current(srt_pt_skin* skin, void* stream, int flat_normals, int how) {
+  const char* what = "srt_pt_skin_pose_current";
+  if (!skin) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (how != SRT_PT_SKIN_UPDATE && how != SRT_PT_SKIN_REFIT && how != SRT_PT_SKIN_INPLACE)
+    return srt::fail(SRT_ERR_INVALID, "%s: how = %d (SRT_PT_SKIN_UPDATE, SRT_PT_SKIN_REFIT or SRT_PT_SKIN_INPLACE)", what, how);
+  const int st = skin_enqueue_current(skin, what, (hipStream_t)stream, flat_normals, skin->d_pos_out, skin->d_nrm_out);
+  if (st != SRT_OK) return st;
+  if (how == SRT_PT_SKIN_INPLACE)
+    return refit_mesh_inplace_device(skin->pt, what, (hipStream_t)stream, skin->object, skin->d_pos_out, skin->d_nrm_out, skin->nverts);
+  return (how == SRT_PT_SKIN_UPDATE ? update_mesh : refit_mesh)(skin->pt, what, (hipStream_t)stream, skin->object,
+                                                               {nullptr, nullptr, skin->d_pos_out, skin->d_nrm_out, {}, {}}, skin->nverts);
+}
+
+int srt_pt_rig_step_ik_host(uint32_t njoints, const int32_t* parent, const float* extents, float* pose_inout, const uint32_t* handle_joints,
+                            const float* targets, const uint8_t* enabled, uint32_t nhandles, uint32_t calls) {
+  const char* what = "srt_pt_rig_step_ik_host";
+  if (!parent || !extents || !pose_inout || (nhandles && (!handle_joints || !targets))) return srt::fail(SRT_ERR_INVALID, "%s: NULL argument", what);
+  if (!ik_supported(njoints, nhandles))
+    return srt::fail(SRT_ERR_UNSUPPORTED, "%s: %u joints and %u handles (at most %u and %u)", what, njoints, nhandles, kSkinMaxJoints, kIkMaxHandles);
+  std::string refused = check_parents(njoints, parent);
+  if (refused.empty()) refused = ik_check_handles(handle_joints, nhandles, njoints);
+  if (!refused.empty()) return srt::fail(SRT_ERR_INVALID, "%s: %s", what, refused.c_str());
+  std::vector<float> cap(4 * (size_t)njoints, 0.0f), scratch((size_t)kIkJointFloats * njoints);
+  for (uint32_t j = 0; j < njoints; j++)
+    for (int a = 0; a < 3; a++) cap[4 * (size_t)j + a] = extents[3 * (size_t)j + a];
+  std::vector<uint32_t> off, list;
+  ik_build_csr(parent, njoints, handle_joints, nhandles, off, list);
+  for (uint32_t c = 0; c < calls; c++) ik_step_host(parent, cap.data(), njoints, handle_joints, off.data(), list.data(), targets, enabled, scratch.data(), pose_inout);
+  return SRT_OK;
 }
 
 int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* extents, const float base[3], const float* rest_pose,
