@@ -365,8 +365,8 @@ int srt_pt_set_active(srt_pt* pt, const uint32_t* objects, const uint8_t* active
  * for the table while an object is inactive), and growth.  Ordering is srt_pt_repose_refit_device's.  The host's record lags and
  * settles on the same path, which behind such a call additionally reads the table back (1 B per object).
  *   The pool loop, all on one stream and without a host wait: srt_pt_particles_step_device -> srt_pt_particle_transforms_device
- * -> srt_pt_set_active_device(d_alive) -> srt_pt_repose_refit_device -> srt_pt_render_epoch_device.  A caller spawns by writing
- * pos, vel and age of a dead slot and setting its alive byte, with a kernel or torch op of its own, before the next frame. */
+ * -> srt_pt_set_active_device(d_alive) -> srt_pt_repose_refit_device -> srt_pt_render_epoch_device.  Spawning into the dead slots,
+ * the substep loop and the rest of Scene_Particles::step are srt_pt_emitter's (below), which runs this loop for a pool it owns. */
 int srt_pt_set_active_device(srt_pt* pt, void* stream, const uint32_t* objects, const uint8_t* d_active, uint32_t n);
 /* The table after settling: one byte per object in insertion order (1 active, 0 inactive) into active_out[0 .. objects).
  * SRT_ERR_INVALID when cap is less than the object count, SRT_ERR_STATE without a commit. */
@@ -880,12 +880,79 @@ int srt_pt_hit(srt_pt* pt, const float* origins, const float* dirs, const float*
  * Scene_Particles::step2 (scene/particles.cpp:134-138), the second caller of Object::hit besides the path tracer (the scene
  * it collides with is Simulate::build_scene's BVH<Object>, gui/simulate.cpp:69-99: commit the same objects).  pos / vel: 3
  * floats per particle, age: 1, updated in place; alive[k] = update()'s return value (age > 0).  dt is one simulation step
- * (Options::dt), radius the particle radius times Options::scale.  Spawning and removing particles stay with the caller.
+ * (Options::dt), radius the particle radius times Options::scale.  Spawning and removing particles are srt_pt_emitter's (below).
  * The reference's loop never returns when its hit_time stays <= 0; the kernel gives such a particle up after 4096 legs.
  * Host form: synchronous.  Device form: device pointers, enqueued on `stream` (NULL = the HIP default stream). */
 int srt_pt_particles_step(srt_pt* pt, float* pos, float* vel, float* age, size_t n, float dt, float radius, uint8_t* alive);
 int srt_pt_particles_step_device(srt_pt* pt, void* stream, float* d_pos, float* d_vel, float* d_age, size_t n, float dt, float radius,
                                  uint8_t* d_alive);
+
+/* ---- srt_pt_emitter: the whole Scene_Particles::step (scene/particles.cpp:101-162) for a pool of fixed capacity ----
+ * The `enabled` and `opt.dt < EPS_F` exits, the `last_update` substep loop, step2 - update, deaths, the cooldown loop, the spawn
+ * arithmetic - and gen_instances, bit-equal to the reference's own code, on one stream without a host wait.
+ *   The pool: `objects` are `capacity` objects of `render`'s committed scene (insertion indices), one per slot, validated exactly
+ * as srt_pt_set_active validates its list - the same refusals, the same codes.  The emitter owns pos / vel (3 floats per slot), age
+ * (1), alive (1 byte) and birth (a uint32: the birth ordinal of the particle in the slot) on the device; every slot starts dead.
+ * `radius` is Scene_Particles::radius; the step uses radius * scale as the reference does.
+ *   The collide context: `collide` is the context whose committed scene the particles bounce off, on the same device.  The
+ * reference collides with Simulate::build_scene's scene of Scene_Objects only (gui/simulate.cpp:69-99); a collide context that
+ * holds those objects and nothing else is what makes the step the reference's.  collide == render is allowed and gives the pool
+ * loop of srt_pt_set_active_device: the particles then also bounce off each other's active meshes, which the reference never does.
+ *   The schedule is the host's, exactly: last_update (float) and particle_cooldown (double) depend on the dts and the options
+ * only, so the host mirrors them with the reference's types and expressions (`particle_cooldown -= dt` is a double minus a float,
+ * `cooldown = 1.0 / opt.pps` is computed in double, the comparison is `<= 0.0f`) and knows every substep's spawn count without
+ * reading the device.  The reference's loops are unbounded; one call is bounded by 4096 substeps and by 1048576 spawns per
+ * substep, and a call beyond either is refused with SRT_ERR_UNSUPPORTED before anything is enqueued, the schedule unchanged.
+ *   Per substep, on the stream, two launches: Particle::update for the ALIVE slots only against collide's scene (a dead slot is
+ * neither traced nor written; 4096 legs at most, as srt_pt_particles_step); then the spawns: the k-th spawn of the substep goes to
+ * the k-th dead slot in ascending slot index, counted after that substep's deaths - a slot that died in this substep can be reused
+ * in it.  Spawns beyond the dead slots are dropped and counted; birth ordinals and uniforms advance as if they had spawned, so the
+ * stream of uniforms stays aligned with the reference's.
+ *   Uniforms: the spawn with birth ordinal b consumes two, the z one first, then the angle one.  With a buffer set
+ * (srt_pt_emitter_set_uniforms_device: n floats on the device, kept by the caller) they are d_uniforms[2 b] and d_uniforms[2 b + 1];
+ * a step whose last ordinal lies beyond the buffer is refused with SRT_ERR_INVALID before anything is enqueued.  Without one they are
+ * the first two draws of SRT-RNG v1 keyed (seed, emitter key, b) - the emitter key is objects[0] - with unit() as DESIGN.md
+ * section 4 defines it.
+ *   Order: the reference keeps survivors in order and appends births, so its vector is always sorted by birth; the pool's alive
+ * slots sorted by `birth` equal that vector bit for bit (pos, velocity, age).  The slot order itself is the pool's own.
+ *   Deviations from the reference: the fixed capacity with a drop counter, the slot order, and the 4096-leg cap of the step.
+ * Anim_Particles / Anim_Pose keys of the emitter stay with the caller (srt_pt_emitter_set_options / _set_pose per frame); the
+ * particle colour is the pool objects' material.
+ *   A handle is stale once `render`'s scene is begun or committed again (SRT_ERR_STATE); `collide` must hold a committed scene
+ * whenever a step runs.  Destroy the emitter before either context.  On a host-only `render` (device -1) the emitter validates
+ * and keeps the schedule; everything that touches the pool returns SRT_ERR_UNSUPPORTED. */
+typedef struct srt_pt_emitter srt_pt_emitter; /* opaque */
+int srt_pt_emitter_create(srt_pt* render, srt_pt* collide, const uint32_t* objects, uint32_t capacity, float radius, srt_pt_emitter** out);
+int srt_pt_emitter_destroy(srt_pt_emitter* em);
+/* Scene_Particles::Options without name and colour; the defaults are the reference's: velocity 25, angle 0, scale 0.1, lifetime 15,
+ * pps 5, dt 0.01, enabled 0.  Nothing is uploaded: the values are launch parameters. */
+int srt_pt_emitter_set_options(srt_pt_emitter* em, float velocity, float angle, float scale, float lifetime, float pps, float dt, int enabled);
+/* Scene_Particles::pose: pos3 and euler3 (degrees), stored like the camera, nothing uploaded.  Starts as Pose::id(). */
+int srt_pt_emitter_set_pose(srt_pt_emitter* em, const float* pos3, const float* euler3);
+int srt_pt_emitter_seed(srt_pt_emitter* em, uint64_t seed);
+/* d_uniforms NULL or n 0: back to the seeded generator. */
+int srt_pt_emitter_set_uniforms_device(srt_pt_emitter* em, const float* d_uniforms, size_t n);
+/* Scene_Particles::step(scene, dt) without gen_instances.  _device: only enqueues on `stream` - no synchronisation, no read-back,
+ * no upload; a disabled emitter enqueues srt_pt_emitter_clear_device.  The blocking form runs on render's own stream and waits. */
+int srt_pt_emitter_step_device(srt_pt_emitter* em, void* stream, float dt);
+int srt_pt_emitter_step(srt_pt_emitter* em, float dt);
+/* gen_instances: srt_pt_particle_transforms_device(pos, scale) into the emitter's own matrices, srt_pt_set_active_device(alive) and
+ * srt_pt_repose_refit_device on `render`, under their contracts - what they upload and where they block is all this call does. */
+int srt_pt_emitter_present_device(srt_pt_emitter* em, void* stream);
+/* step + present */
+int srt_pt_emitter_frame_device(srt_pt_emitter* em, void* stream, float dt);
+/* Scene_Particles::clear(): every slot becomes dead; last_update and particle_cooldown stay, as in the reference. */
+int srt_pt_emitter_clear_device(srt_pt_emitter* em, void* stream);
+int srt_pt_emitter_clear(srt_pt_emitter* em);
+/* The five arrays, blocking (the device is idle when they return); a NULL array is skipped.  pos / vel: capacity * 3 floats, age:
+ * capacity floats, alive: capacity bytes, birth: capacity uint32.  For seeding a pool, saving and restoring it, and tests. */
+int srt_pt_emitter_read(srt_pt_emitter* em, float* pos, float* vel, float* age, uint8_t* alive, uint32_t* birth);
+int srt_pt_emitter_write(srt_pt_emitter* em, const float* pos, const float* vel, const float* age, const uint8_t* alive, const uint32_t* birth);
+/* out[0] = alive slots, out[1] = birth ordinals consumed so far (dropped spawns included), out[2] = spawns dropped.  Blocking.  On a
+ * host-only context out[0] and out[2] are 0. */
+int srt_pt_emitter_counts(srt_pt_emitter* em, uint64_t out[3]);
+/* The device pointers {pos, vel, age, alive, birth}, for callers with kernels of their own. */
+int srt_pt_emitter_arrays_device(srt_pt_emitter* em, void* out[5]);
 
 /* Host-side BVH arrays after commit.  which = -1: the BVH<Object> (order = 1-based insertion index of the
  * objects in BVH primitive order); which >= 0: the BVH<Triangle> of the which-th BVH<Object> primitive

@@ -128,6 +128,11 @@ int srt_pt_rig_posed_host(uint32_t njoints, const int32_t* parent, const float* 
  * range; SRT_ERR_UNSUPPORTED beyond 4096 joints or 1024 handles; pose_inout is untouched then. */
 int srt_pt_rig_step_ik_host(uint32_t njoints, const int32_t* parent, const float* extents, float* pose_inout, const uint32_t* handle_joints,
                             const float* targets, const uint8_t* enabled, uint32_t nhandles, uint32_t calls);
+/* The schedule half of srt_pt_emitter_step(em, dt) alone - last_update, particle_cooldown and the birth ordinals advance as the step
+ * advances them, nothing is enqueued - on any context, a host-only one included.  *substeps = the substeps of the call,
+ * spawns_out[i] (i < min(*substeps, cap)) = the spawns behind substep i, *cleared = 1 when the emitter is disabled (the step would
+ * clear).  schedule_out (may be NULL): {last_update as a double, particle_cooldown} afterwards.  Refusals are the step's. */
+int srt_pt_emitter_advance_host(srt_pt_emitter* em, float dt, uint32_t* substeps, uint32_t* spawns_out, uint32_t cap, int* cleared, double schedule_out[2]);
 
 /* The epilogue's expf / powf (glibc 2.35's algorithms restated, FMA build) evaluated on the device. */
 int srt_pt_math_exp(srt_pt* pt, const float* x, size_t n, float* out);

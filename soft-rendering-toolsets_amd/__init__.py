@@ -271,4 +271,4 @@ class SoftwareRenderer:
         _check(self._lib, self._lib.srt_raster_sync(self._ctx))
 
 
-from ._pt_bindings import LOGGED_RAY_DTYPE, MATERIAL_DTYPE, SKIN_JOINT_DTYPE, ShadingTimeline, ShadingTimelineGroup, Pathtracer, PathtracerGroup, Scene, Skin, SkinGroup, SrtCancelled, Timeline, TimelineGroup, skin_joints, timeline_tracks  # noqa: E402,F401
+from ._pt_bindings import Emitter, EmitterGroup, LOGGED_RAY_DTYPE, MATERIAL_DTYPE, SKIN_JOINT_DTYPE, ShadingTimeline, ShadingTimelineGroup, Pathtracer, PathtracerGroup, Scene, Skin, SkinGroup, SrtCancelled, Timeline, TimelineGroup, skin_joints, timeline_tracks  # noqa: E402,F401

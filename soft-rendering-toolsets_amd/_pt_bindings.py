@@ -145,6 +145,23 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_hit.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_particles_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p]
     lib.srt_pt_particles_step_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p]
+    lib.srt_pt_emitter_create.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_void_p]
+    lib.srt_pt_emitter_destroy.argtypes = [c_void_p]
+    lib.srt_pt_emitter_set_options.argtypes = [c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_int]
+    lib.srt_pt_emitter_set_pose.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_emitter_seed.argtypes = [c_void_p, c_uint64]
+    lib.srt_pt_emitter_set_uniforms_device.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.srt_pt_emitter_step_device.argtypes = [c_void_p, c_void_p, c_float]
+    lib.srt_pt_emitter_step.argtypes = [c_void_p, c_float]
+    lib.srt_pt_emitter_present_device.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_emitter_frame_device.argtypes = [c_void_p, c_void_p, c_float]
+    lib.srt_pt_emitter_clear_device.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_emitter_clear.argtypes = [c_void_p]
+    lib.srt_pt_emitter_read.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_emitter_write.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_emitter_counts.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_emitter_arrays_device.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_emitter_advance_host.argtypes = [c_void_p, c_float, POINTER(c_uint32), c_void_p, c_uint32, POINTER(c_int), c_void_p]
     lib.srt_pt_dump_bvh.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_dump_bvh.restype = c_long
     lib.srt_pt_counters.argtypes = [c_void_p, c_void_p]
@@ -593,6 +610,168 @@ class TimelineGroup:
             tl.close()
 
 
+class Emitter:
+    """srt_pt_emitter (Pathtracer.create_emitter): the whole Scene_Particles::step for a pool of fixed capacity whose slots are objects of
+    the committed scene - the substep loop, Particle::update against the collide context's scene, deaths, the spawns into the lowest
+    dead slots, gen_instances - on one stream without a host wait.  Closing the Pathtracer closes the emitters it created."""
+
+    def __init__(self, pt, collide, handle, objects):
+        self._pt, self._collide, self._lib, self._check = pt, collide, pt._lib, pt._check
+        self._h = handle
+        self.objects = objects
+        self.capacity = len(objects)
+
+    def set_options(self, velocity: float = 25.0, angle: float = 0.0, scale: float = 0.1, lifetime: float = 15.0, pps: float = 5.0, dt: float = 0.01,
+                    enabled: bool = False) -> None:
+        """srt_pt_emitter_set_options: Scene_Particles::Options (the defaults are the reference's)."""
+        self._check(self._lib, self._lib.srt_pt_emitter_set_options(self._h, float(velocity), float(angle), float(scale), float(lifetime), float(pps), float(dt),
+                                                                   int(bool(enabled))))
+
+    def set_pose(self, pos, euler) -> None:
+        """srt_pt_emitter_set_pose: Scene_Particles::pose, position and Euler angles in degrees."""
+        p, e = _f32(pos).reshape(3), _f32(euler).reshape(3)
+        self._check(self._lib, self._lib.srt_pt_emitter_set_pose(self._h, _p(p), _p(e)))
+
+    def seed(self, seed: int) -> None:
+        self._check(self._lib, self._lib.srt_pt_emitter_seed(self._h, c_uint64(seed)))
+
+    def set_uniforms_device(self, d_uniforms_ptr: int, n: int) -> None:
+        """srt_pt_emitter_set_uniforms_device: n floats on the device, two per birth ordinal (0: back to the seeded generator)."""
+        self._check(self._lib, self._lib.srt_pt_emitter_set_uniforms_device(self._h, c_void_p(d_uniforms_ptr), c_size_t(n)))
+
+    def step_device(self, dt: float, stream: int = 0) -> None:
+        """srt_pt_emitter_step_device: Scene_Particles::step(scene, dt) without gen_instances; only enqueues."""
+        self._check(self._lib, self._lib.srt_pt_emitter_step_device(self._h, c_void_p(stream), float(dt)))
+
+    def step(self, dt: float) -> None:
+        self._check(self._lib, self._lib.srt_pt_emitter_step(self._h, float(dt)))
+
+    def present_device(self, stream: int = 0) -> None:
+        """srt_pt_emitter_present_device: gen_instances - the transforms, the active flags and the refit of the render scene; only enqueues."""
+        self._check(self._lib, self._lib.srt_pt_emitter_present_device(self._h, c_void_p(stream)))
+
+    def frame_device(self, dt: float, stream: int = 0) -> None:
+        self._check(self._lib, self._lib.srt_pt_emitter_frame_device(self._h, c_void_p(stream), float(dt)))
+
+    def clear_device(self, stream: int = 0) -> None:
+        self._check(self._lib, self._lib.srt_pt_emitter_clear_device(self._h, c_void_p(stream)))
+
+    def clear(self) -> None:
+        self._check(self._lib, self._lib.srt_pt_emitter_clear(self._h))
+
+    def read(self) -> dict:
+        """srt_pt_emitter_read: {"pos", "vel" (capacity, 3), "age", "alive" (uint8), "birth" (uint32)}; blocking."""
+        n = self.capacity
+        out = {"pos": np.zeros((n, 3), np.float32), "vel": np.zeros((n, 3), np.float32), "age": np.zeros(n, np.float32), "alive": np.zeros(n, np.uint8),
+               "birth": np.zeros(n, np.uint32)}
+        self._check(self._lib, self._lib.srt_pt_emitter_read(self._h, _p(out["pos"]), _p(out["vel"]), _p(out["age"]), _p(out["alive"]), _p(out["birth"])))
+        return out
+
+    def write(self, pos=None, vel=None, age=None, alive=None, birth=None) -> None:
+        """srt_pt_emitter_write: the arrays given (None: left as they are); blocking."""
+        n = self.capacity
+        arrays = []
+        for a, dtype, shape in ((pos, np.float32, (n, 3)), (vel, np.float32, (n, 3)), (age, np.float32, (n,)), (alive, np.uint8, (n,)), (birth, np.uint32, (n,))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype)
+                if a.shape != shape:
+                    raise ValueError(f"an array of shape {a.shape} for a pool of {n} slots")
+            arrays.append(a)
+        self._check(self._lib, self._lib.srt_pt_emitter_write(self._h, *(None if a is None else _p(a) for a in arrays)))
+
+    def counts(self) -> dict:
+        """srt_pt_emitter_counts: {"alive", "born", "dropped"}; blocking."""
+        out = np.zeros(3, np.uint64)
+        self._check(self._lib, self._lib.srt_pt_emitter_counts(self._h, _p(out)))
+        return {"alive": int(out[0]), "born": int(out[1]), "dropped": int(out[2])}
+
+    def arrays_device(self) -> dict:
+        """srt_pt_emitter_arrays_device: the device pointers of pos, vel, age, alive and birth."""
+        out = (c_void_p * 5)()
+        self._check(self._lib, self._lib.srt_pt_emitter_arrays_device(self._h, out))
+        return {k: int(out[i] or 0) for i, k in enumerate(("pos", "vel", "age", "alive", "birth"))}
+
+    def advance_host(self, dt: float):
+        """srt_pt_emitter_advance_host (srt_pt_debug.h): the schedule half of step(dt) alone - (spawns per substep, cleared, (last_update, particle_cooldown))."""
+        n, cleared = c_uint32(), c_int()
+        spawns, sched = np.zeros(4096, np.uint32), np.zeros(2, np.float64)
+        self._check(self._lib, self._lib.srt_pt_emitter_advance_host(self._h, float(dt), ctypes.byref(n), _p(spawns), len(spawns), ctypes.byref(cleared), _p(sched)))
+        return spawns[:n.value].copy(), bool(cleared.value), (float(sched[0]), float(sched[1]))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.srt_pt_emitter_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self._pt._ctx and self._collide._ctx:      # (Pathtracer.close() has closed the emitters it made)
+                self.close()
+        except Exception:
+            pass
+
+
+class EmitterGroup:
+    """PathtracerGroup.create_emitter: one Emitter per rank (the scene is replicated); every rank gets the same calls.  The device forms
+    take one uniform buffer per rank."""
+
+    def __init__(self, emitters):
+        self.emitters = emitters
+        self.capacity = emitters[0].capacity
+
+    def _all(self, name, *args, **kw):
+        return [getattr(e, name)(*args, **kw) for e in self.emitters]
+
+    def set_options(self, *args, **kw) -> None:
+        self._all("set_options", *args, **kw)
+
+    def set_pose(self, pos, euler) -> None:
+        self._all("set_pose", pos, euler)
+
+    def seed(self, seed: int) -> None:
+        self._all("seed", seed)
+
+    def set_uniforms_device(self, d_uniforms_ptrs, n: int) -> None:
+        if len(d_uniforms_ptrs) != len(self.emitters):
+            raise ValueError(f"{len(d_uniforms_ptrs)} uniform buffers for {len(self.emitters)} ranks")
+        for e, p in zip(self.emitters, d_uniforms_ptrs):
+            e.set_uniforms_device(p, n)
+
+    def step_device(self, dt: float, stream: int = 0) -> None:
+        self._all("step_device", dt, stream)
+
+    def step(self, dt: float) -> None:
+        self._all("step", dt)
+
+    def _settle(self) -> None:
+        for e in self.emitters:
+            e._check(e._lib, e._lib.srt_pt_sync(e._pt._ctx))
+
+    def present_device(self, stream: int = 0) -> None:
+        """Emitter.present_device on every rank; like TimelineGroup.repose_refit each member is settled before this returns."""
+        self._all("present_device", stream)
+        self._settle()
+
+    def frame_device(self, dt: float, stream: int = 0) -> None:
+        self._all("frame_device", dt, stream)
+        self._settle()
+
+    def clear(self) -> None:
+        self._all("clear")
+
+    def read(self) -> dict:
+        return self.emitters[0].read()
+
+    def write(self, **arrays) -> None:
+        self._all("write", **arrays)
+
+    def counts(self) -> dict:
+        return self.emitters[0].counts()
+
+    def close(self) -> None:
+        self._all("close")
+
+
 MATERIAL_DTYPE = np.dtype([("type", np.uint32), ("a", np.float32, 3), ("b", np.float32, 3), ("ior", np.float32)])   # srt_pt_material
 
 
@@ -948,6 +1127,19 @@ class Pathtracer:
         tl = Timeline(self, h, idx)
         self._timelines = [r for r in self._timelines if r() is not None] + [weakref.ref(tl)]
         return tl
+
+    def create_emitter(self, collide, objects, radius: float) -> Emitter:
+        """srt_pt_emitter_create: an emitter over the pool `objects` (insertion indices of this context's committed scene, one per slot)
+        whose particles bounce off the committed scene of the Pathtracer `collide` - the reference's Simulate scene when that holds the
+        Scene_Objects only; `collide` may be this Pathtracer.  Closing either Pathtracer closes the emitter."""
+        idx = np.ascontiguousarray(objects, np.uint32).reshape(-1)
+        h = c_void_p()
+        self._check(self._lib, self._lib.srt_pt_emitter_create(self._ctx, collide._ctx if collide is not None else None, _p(idx) if len(idx) else None, len(idx),
+                                                               float(radius), ctypes.byref(h)))
+        em = Emitter(self, collide, h, idx)
+        for pt in {id(self): self, id(collide): collide}.values():
+            pt._timelines = [r for r in pt._timelines if r() is not None] + [weakref.ref(em)]
+        return em
 
     def update_materials(self, indices, materials) -> None:
         """srt_pt_update_materials: new values (material_records(..): the form build_scene takes) for the materials with these indices
@@ -1544,6 +1736,21 @@ class PathtracerGroup:
                 tl.close()
             raise
         return TimelineGroup(made)
+
+    def create_emitter(self, collide_group, objects, radius: float) -> EmitterGroup:
+        """One emitter per rank over the rank's own context (srt_pt_group_context) and the same rank of `collide_group` (which may be
+        this group): a forwarder, with no group entry points in C."""
+        if len(collide_group.members) != len(self.members):
+            raise ValueError(f"a collide group of {len(collide_group.members)} ranks for a group of {len(self.members)}")
+        made = []
+        try:
+            for m, c in zip(self.members, collide_group.members):
+                made.append(m.create_emitter(c, objects, radius))
+        except Exception:
+            for em in made:
+                em.close()
+            raise
+        return EmitterGroup(made)
 
     def update_materials(self, indices, materials) -> None:
         for m in self.members:

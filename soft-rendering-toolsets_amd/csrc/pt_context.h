@@ -3,7 +3,8 @@
 //   pt_context.cpp  host code only: create / destroy, scene begin / add / commit, camera, image size, tiling and the switches
 //   pt_update*.cpp  host code only: what changes or queries a committed scene - pt_update_mesh.cpp (new vertices), pt_update_skin.cpp
 //                   (skins and rigs), pt_update_pose.cpp (poses, object timelines), pt_update_shading.cpp (materials, delta lights,
-//                   shading timelines) and pt_update.cpp (what they share - pt_update.h - and settle())
+//                   shading timelines), pt_update_emitter.cpp (particle emitters) and pt_update.cpp (what they share - pt_update.h -
+//                   and settle())
 //   pt_query.hip    per-lane kernels on the committed scene outside a render (samples, hits, particles) and the dumps
 //   pt_image.hip    untile, accumulate, tonemap
 //   pt_probe.hip    the test-only math probes of srt_pt_debug.h

@@ -13,6 +13,7 @@
 
 #include "pt_trace.h"
 #include "pt_flat.h"
+#include "pt_particle.h"
 
 namespace srt {
 
@@ -70,45 +71,14 @@ __global__ void pt_hit_kernel(DScene S, const float* __restrict__ org, const flo
   }
 }
 
-// Scene_Particles::Particle::update (student/particles.cpp:5-59), one lane per particle: the second caller of Object::hit
-// (SURVEY.md 8(f)-4).  The particle flies at constant velocity for what is left of dt, bounces off what
-// scene.hit(Ray(pos, velocity)) reports - default bounds [0, inf], the direction is the velocity, NOT normalised - and
-// gravity acts on the velocity after every leg.  The reference's loop does not return when hit_time stays <= 0; a lane
-// gives up after kParticleMaxLegs legs.
-constexpr uint32_t kParticleMaxLegs = 4096;
+// Scene_Particles::Particle::update (pt_particle.h: particle_update), one lane per particle.
 __global__ __launch_bounds__(64) void pt_particles_kernel(DScene S, float* __restrict__ pos, float* __restrict__ vel, float* __restrict__ age,
                                                           uint32_t n, float dt, float radius, uint8_t* __restrict__ alive) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   V3 p = v3(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
   V3 velocity = v3(vel[3 * k], vel[3 * k + 1], vel[3 * k + 2]);
-  const V3 acceleration = v3(0.0f, -9.8f, 0.0f);
-  float remain = dt;
-  Counters cnt;
-  for (uint32_t leg = 0; remain > 0 && leg < kParticleMaxLegs; leg++) {
-    Ray r;
-    r.o = p; r.d = velocity; r.b0 = 0.0f; r.b1 = __uint_as_float(0x7f800000u);
-    const Hit h = scene_hit<false>(S, r, cnt);
-    V3 t_normal = v3(0, 0, 0), t_position = v3(0, 0, 0);       // a Trace without a hit is all zeros (rays/trace.h)
-    if (h.hit) { const Surface sf = surface_of(S, h, r); t_normal = sf.normal; t_position = sf.position; }
-    float cos_t = dot(t_normal, velocity * -1.0f) / (norm(velocity) * norm(t_normal));
-    V3 surface_normal = t_normal / norm(t_normal);
-    if (cos_t < 0) {
-      cos_t = (float)sqrt((double)(1 - cos_t * cos_t));          // unqualified sqrt: the double overload
-      surface_normal = surface_normal * -1.0f;
-    }
-    const float interval = fabsf(radius / cos_t);
-    const float hit_time = (h.dist - interval) / norm(r.d);
-    if (!h.hit || hit_time > remain || cos_t == 0) {
-      p = p + velocity * remain;
-      velocity = velocity + acceleration * remain;
-      break;
-    }
-    p = t_position - (velocity * interval) / norm(velocity);
-    velocity = velocity - surface_normal * (2.0f * dot(velocity, surface_normal));
-    velocity = velocity + acceleration * hit_time;
-    remain -= hit_time;
-  }
+  particle_update(S, p, velocity, dt, radius);
   const float a = age[k] - dt;
   age[k] = a;
   alive[k] = a > 0 ? 1 : 0;

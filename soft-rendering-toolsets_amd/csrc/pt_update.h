@@ -1,5 +1,5 @@
-// What the units that change a committed scene share - pt_update.cpp, pt_update_mesh.cpp, pt_update_skin.cpp, pt_update_pose.cpp and
-// pt_update_shading.cpp - and nobody else: each name here is used by more than one of them; what the rest of csrc/ calls is in
+// What the units that change a committed scene share - pt_update.cpp, pt_update_mesh.cpp, pt_update_skin.cpp, pt_update_pose.cpp,
+// pt_update_shading.cpp and pt_update_emitter.cpp - and nobody else: each name here is used by more than one of them; what the rest of csrc/ calls is in
 // pt_context.h.  Host code only.
 #ifndef SRT_PT_UPDATE_H
 #define SRT_PT_UPDATE_H
@@ -57,7 +57,7 @@ int top_broken(srt_pt* pt, int status);
 int top_hip_broken(srt_pt* pt, const char* what, hipError_t e, const char* step);
 int write_top_refit(srt_pt* pt, const uint32_t* objects, uint32_t n);
 
-// The head of srt_pt_skin, srt_pt_timeline and srt_pt_shading_timeline: a handle belongs to the scene its context held when it was
+// The head of srt_pt_skin, srt_pt_timeline, srt_pt_shading_timeline and srt_pt_emitter: a handle belongs to the scene its context held when it was
 // made.  (Each handle's *_usable refuses NULL and a stale handle in words of its own.)
 struct SceneHandle {
   srt_pt* pt = nullptr;
