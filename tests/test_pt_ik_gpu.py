@@ -1,8 +1,11 @@
 """GPU: Skeleton::do_ik / step_ik by one kernel launch (pt_ik.hip) - Skin.step_ik and step_ik_device against the poses the reference
 recorded after every call (tests/golden/ik_*.npz), set_time on the current pose, posed_current and vertices_current_device against
 the recorded joint_to_posed and posed_mesh(), the frame step_ik_device -> pose_current -> render_epoch_device on one stream against a
-fresh commit of the recorded vertices, the `_at` calls left as they were, the group form and every refusal.  Every comparison is
-bit for bit on float32 viewed as uint32, NaN matching NaN.  Device arrays are torch tensors passed by data_ptr()."""
+fresh commit of the recorded vertices, the `_at` calls left as they were, the group form and every refusal.  Beyond the recorded
+sizes - the LDS form with every wave busy, 256 / 257 joints, lanes with many joints, up to 1024 handles with hundreds on one joint,
+keyed rigs of more than one block - the generated rigs of _ik_cases.py against the host definitions (srt_pt_rig_step_ik_host,
+srt_pt_rig_posed_host), which the recordings pin to the reference.  Every comparison is bit for bit on float32 viewed as uint32, NaN
+matching NaN.  Device arrays are torch tensors passed by data_ptr()."""
 import ctypes
 
 import numpy as np
@@ -57,10 +60,17 @@ def make_pt(srt, scene, device=0):
     return pt
 
 
-def rigged_skin(srt, name):
-    """(context, skin, fixture) of a recorded rig on a one-mesh scene: the committed skin fixture's mesh and joints where there is one,
-    the small blob and joints made from the rig otherwise."""
-    ik = IK.load(name)
+@pytest.fixture(scope="module")
+def lib(srt):
+    return srt.load_library()
+
+
+def rigged_skin(srt, case):
+    """(context, skin, case) of a rig on a one-mesh scene - a recorded rig by name, or a case dict with a fixture's inputs
+    (IK.generated, IK.generated_keyed): the committed skin fixture's mesh and joints where there is one, the small blob and joints made
+    from the rig otherwise."""
+    name = case if isinstance(case, str) else None
+    ik = IK.load(name) if name else case
     if name in IK.MESHED:
         g, joints = SC.load_fixture(name)
         pos, nrm, idx = g["pos"], g["nrm"], g["idx"]
@@ -72,7 +82,8 @@ def rigged_skin(srt, name):
     pt.build_scene(SC.single_mesh_scene(pos, nrm, idx))
     skin = pt.create_skin(0, pos, nrm, joints)
     skin.set_rig(*IK.rig_arrays(ik))
-    skin.set_ik_handles(ik["handle_joints"])
+    if name or "handle_joints" in ik:                         # (a keyed rig of IK.generated_keyed has no handles)
+        skin.set_ik_handles(ik["handle_joints"])
     return pt, skin, ik
 
 
@@ -148,6 +159,86 @@ def test_step_ik_device_equals_the_reference(srt, torch, name):
     same = AC.bits_equal(every, skin.joint_pose())
     skin.close(); pt.close()
     assert not any(bad) and back_to_back == 0 and kept_bits and same, (bad, back_to_back, kept_bits, same)
+
+
+@pytest.mark.parametrize("name", IK.GENERATED)
+def test_generated_rigs_equal_the_host_definition(srt, torch, lib, name):
+    """The generated rigs (IK.GENERATED_SIZES: around one wave, around the LDS form's last size, a lane with three joints and with
+    sixteen, 1024 handles, a root under every handle) against srt_pt_rig_step_ik_host: joint_pose() after each of the three calls
+    through Skin.step_ik, after each through step_ik_device, and after the three enqueued back to back on a stream of their own;
+    then posed_current from the host and from the joint kernels against srt_pt_rig_posed_host of the last pose.  Mismatching words
+    per comparison; every one is zero."""
+    g = IK.generated(name)
+    want = IK.generated_poses(lib, name)
+    want_posed = IK.posed_host(lib, g, 0.0, rest=want[-1])[1]
+    pt, skin, _ = rigged_skin(srt, g)
+    nj = skin.njoints
+    assert AC.bits_equal(skin.joint_pose(), g["rest_pose"])
+    host_form = [AC.mismatches(skin.joint_pose(), want[c]) for c in replay(skin, g)]
+    skin.set_joint_pose(g["rest_pose"])
+    inputs = device_inputs(torch, g)
+    uploaded = pt.scene_counts()["uploaded_bytes"]
+    device_form = [AC.mismatches(skin.joint_pose(), want[c]) for c in replay(skin, g, inputs)]
+    sent = pt.scene_counts()["uploaded_bytes"] - uploaded                              # the device form sends nothing up
+    skin.set_joint_pose(g["rest_pose"])
+    st = torch.cuda.Stream(device="cuda:0")
+    torch.cuda.synchronize()
+    for _ in replay(skin, g, inputs, stream=st.cuda_stream):
+        pass
+    back_to_back = AC.mismatches(skin.joint_pose(), want[-1])
+    d_posed = torch.zeros((nj + 1, 16), device="cuda:0")
+    skin.posed_current_device(d_posed.data_ptr())
+    torch.cuda.synchronize()
+    posed = (AC.mismatches(skin.posed_current(), want_posed), AC.mismatches(d_posed.cpu().numpy()[:nj], want_posed))
+    room = d_posed[nj].any().item()
+    skin.close(); pt.close()
+    print(name, "mismatching words:", host_form, device_form, back_to_back, posed)
+    assert host_form == [0, 0, 0] and device_form == [0, 0, 0] and sent == 0 and back_to_back == 0 and posed == (0, 0) and not room, \
+        (host_form, device_form, sent, back_to_back, posed, room)
+
+
+@pytest.mark.parametrize("name", ["gen256_1024", "gen1000_1024"])
+def test_every_handle_of_1024(srt, torch, lib, name):
+    """enabled = NULL with the handle tables full, in the LDS form and on scratch: the host form with a byte of one per handle."""
+    g = IK.generated(name)
+    nh = len(g["handle_joints"])
+    assert nh == IK.MAX_HANDLES
+    st, want = IK.step_host(lib, g["parent"], g["extent"], g["rest_pose"], g["handle_joints"], g["targets"][1], np.ones(nh, np.uint8))
+    assert st == 0 and not AC.bits_equal(want, IK.generated_poses(lib, name)[0])
+    pt, skin, _ = rigged_skin(srt, g)
+    skin.step_ik(g["targets"][1])
+    host_form = AC.mismatches(skin.joint_pose(), want)
+    skin.set_joint_pose(g["rest_pose"])
+    d_t = torch.from_numpy(np.ascontiguousarray(g["targets"][1], F)).to("cuda:0")
+    torch.cuda.synchronize()
+    skin.step_ik_device(d_t.data_ptr())
+    device_form = AC.mismatches(skin.joint_pose(), want)
+    skin.close(); pt.close()
+    assert (host_form, device_form) == (0, 0)
+
+
+@pytest.mark.parametrize("nj", IK.KEYED_SIZES)
+def test_keyed_rigs_at_size(srt, torch, lib, nj):
+    """Skeleton::set_time and the rig's matrices at a time, beyond one block of either kernel: half the joints keyed with every knot
+    count, at every time of the timeline tests.  set_time(t) gives the keyed joints srt_pt_rig_posed_host's Euler angles and leaves
+    the others the bits they had (a pose that is not the rest pose); posed_at(t) and posed_at_device(t) are its matrices."""
+    g = IK.generated_keyed(nj)
+    keyed = np.diff(g["knot_offsets"].astype(np.int64)) > 0
+    pt, skin, _ = rigged_skin(srt, g)
+    skin.set_joint_pose(g["had"])
+    d_posed = torch.zeros((nj + 1, 16), device="cuda:0")
+    bad = []
+    for t in AC.TIMES:
+        euler, posed = IK.posed_host(lib, g, t)
+        skin.set_time(float(t))
+        pose = skin.joint_pose()
+        skin.posed_at_device(float(t), d_posed.data_ptr())
+        torch.cuda.synchronize()
+        bad.append((AC.mismatches(pose[keyed], euler[keyed]), int(np.sum(pose[~keyed].view(np.uint32) != g["had"][~keyed].view(np.uint32))),
+                    AC.mismatches(skin.posed_at(float(t)), posed), AC.mismatches(d_posed.cpu().numpy()[:nj], posed)))
+    room = d_posed[nj].any().item()
+    skin.close(); pt.close()
+    assert bad == [(0, 0, 0, 0)] * len(AC.TIMES) and not room, bad
 
 
 @pytest.mark.parametrize("how", ["inplace", "update", "refit"])

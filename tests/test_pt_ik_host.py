@@ -2,7 +2,8 @@
 (tests/golden/ik_*.npz, made by tests/golden/make_ik_golden.py): srt_pt_rig_step_ik_host after every recorded call, joint_to_posed
 after the last one, the first iteration's intermediate values from the host emulation, the cases that leave the poses' bits alone,
 the summation order, every refusal a host can reach, and a sanitized stand-alone program over the handle check, the CSR and the
-solve.  Every comparison is on float32 viewed as uint32, NaN matching NaN; there are no tolerances."""
+solve; then the generated rigs the GPU tests run (IK.generated, IK.generated_keyed): the conditions that make them worth running,
+and the host definitions against the host emulations on them.  Every comparison is on float32 viewed as uint32, NaN matching NaN; there are no tolerances."""
 import ctypes
 import os
 import subprocess
@@ -80,7 +81,10 @@ def test_fixture_holds_the_cases(name):
             if g["enabled"][c][h]:
                 reached[chain] = True
     moved = np.abs(g["pose"] - g["pose_before"]).max(axis=2).sum(axis=0)
-    assert reached.any() and np.all(moved[reached] > 1.0) and np.all(moved[~reached] == 0)
+    assert reached.any() and np.all(moved[reached] > IK.LEAST_MOVED.get(name, 1.0)) and np.all(moved[~reached] == 0)
+    assert IK.LEAST_MOVED.get(name, 1.0) >= (0.05 if name == "wide200" else 1.0)
+    if name == "wide200":
+        IK.check_wide(g)
     if name in IK.MESHED:
         import _skin_cases as SC
 
@@ -184,14 +188,82 @@ def test_disabled_and_no_handles_keep_the_bits(lib, name):
 
 
 def test_reversed_handle_order_differs(lib):
-    """A joint's gradient is summed in handle order and floats do not associate: the tree rig with its handle list reversed - the
-    same handles, targets and flags - ends on other bits, so the fixture can tell a wrong summation order."""
-    g = IK.load("blob128_tree5")
-    c = 0
-    fwd = IK.step_host(lib, g["parent"], g["extent"], g["pose_before"][c], g["handle_joints"], g["targets"][c], g["enabled"][c])[1]
-    rev = IK.step_host(lib, g["parent"], g["extent"], g["pose_before"][c], g["handle_joints"][::-1], g["targets"][c][::-1], g["enabled"][c][::-1])[1]
-    assert AC.bits_equal(fwd, g["pose"][c]) and not AC.bits_equal(rev, g["pose"][c])
-    assert np.abs(rev - g["pose"][c]).max() < 1e-2                                    # (the same solve but for the rounding)
+    """A joint's gradient is summed in handle order and floats do not associate: the tree rig, and wide200 with 64 handles under
+    one root, with the handle list reversed - the same handles, targets and flags - end on other bits, so the fixtures can tell a
+    wrong summation order."""
+    for name in ("blob128_tree5", "wide200"):
+        g = IK.load(name)
+        c = 0
+        fwd = IK.step_host(lib, g["parent"], g["extent"], g["pose_before"][c], g["handle_joints"], g["targets"][c], g["enabled"][c])[1]
+        rev = IK.step_host(lib, g["parent"], g["extent"], g["pose_before"][c], g["handle_joints"][::-1], g["targets"][c][::-1], g["enabled"][c][::-1])[1]
+        assert AC.bits_equal(fwd, g["pose"][c]) and not AC.bits_equal(rev, g["pose"][c]), name
+        assert np.abs(rev - g["pose"][c]).max() < 1e-2, name                          # (the same solve but for the rounding)
+
+
+@pytest.mark.parametrize("name", IK.GENERATED)
+def test_generated_rigs_hold_their_conditions(lib, name):
+    """What test_pt_ik_gpu.py relies on in a generated rig, asserted on the data and on srt_pt_rig_step_ik_host's poses: the shape of
+    the hierarchy and of the handle list, finite poses below 1000 degrees, every reached joint moved, every other bit kept, another
+    result for the reversed handle list.  Conditions on the seed: one that misses takes another seed (IK._SEEDS), not another bound."""
+    g = IK.generated(name)
+    nj, nh = IK.GENERATED_SIZES[IK.GENERATED.index(name)]
+    par, hj, en = g["parent"], g["handle_joints"], g["enabled"]
+    chains = IK.chains(par, hj)
+    assert len(par) == nj <= IK.MAX_JOINTS and len(hj) == nh <= IK.MAX_HANDLES and g["targets"].shape == (3, nh, 3) and en.shape == (3, nh)
+    assert all(p < k for k, p in enumerate(par)) and (par < 0).sum() >= 2 and max(len(c) for c in chains) <= IK.MAX_DEPTH + 1 and g["depth"].max() <= IK.MAX_DEPTH
+    length = np.linalg.norm(g["extent"].astype(np.float64), axis=1)
+    assert length.min() > 0.199 and length.max() < 0.501 and np.abs(g["rest_pose"]).max() <= 30 and np.abs(g["targets"]).max() <= 2
+    # handles with repeats, one on a root, one root above all of them; the three masks
+    assert len(set(hj.tolist())) < nh and par[hj[0]] < 0 and len(chains[0]) == 1 and {c[-1] for c in chains} == {int(hj[0])}
+    assert en[0].all() and en[1].sum() == nh // 2 and not en[2, 64:128].any() and en[2, :64].all() and en[2, 128:].all()
+    # a CSR list as long as the handle list (the root's): 64 handles and more wherever the rig has that many
+    held = np.bincount(np.concatenate(chains), minlength=nj)
+    assert held.max() == nh and (nh < 64 or held.max() >= 64) and np.bincount(hj).max() >= max(2, nh // 8)
+    # a handle's chain with joints of two 64-lane groups of the workgroup: its matrices and `current` cross waves
+    if nj > 64:
+        assert max(len(IK.waves(c)) for c in chains) >= 2
+    if nj > IK.BLOCK:
+        assert any(len({j % IK.BLOCK for j in c}) < len(c) for c in chains)           # and a chain with two joints of one lane
+    poses = np.concatenate([g["rest_pose"][None], IK.generated_poses(lib, name)])
+    assert np.isfinite(poses).all() and np.abs(poses).max() < 1000
+    reached = np.zeros(nj, bool)
+    for c in range(3):
+        for h in np.nonzero(en[c])[0]:
+            reached[chains[h]] = True
+    moved = np.abs(np.diff(poses, axis=0)).max(axis=2).sum(axis=0)
+    assert reached.any() and not reached.all() and moved[reached].min() > 0.01, moved[reached].min()
+    assert np.array_equal(poses[-1][~reached].view(np.uint32), g["rest_pose"][~reached].view(np.uint32))
+    for c in range(3):                                       # call by call: a joint no enabled handle of this call reaches keeps its bits
+        off = np.ones(nj, bool)
+        for h in np.nonzero(en[c])[0]:
+            off[chains[h]] = False
+        assert np.array_equal(poses[c + 1][off].view(np.uint32), poses[c][off].view(np.uint32))
+    rev = IK.step_host(lib, par, g["extent"], g["rest_pose"], hj[::-1], g["targets"][0][::-1], en[0][::-1])[1]
+    assert not AC.bits_equal(rev, poses[1]) and np.abs(rev - poses[1]).max() < 1e-2
+
+
+@pytest.mark.parametrize("name", IK.GENERATED)
+def test_generated_rigs_equal_the_emulation(lib, name):
+    """srt_pt_rig_step_ik_host against the independent g++ build of the same header, one call on each generated rig."""
+    g = IK.generated(name)
+    e = IK.emu_one_call(g, 0, pose=g["rest_pose"])
+    assert AC.mismatches(e["pose"], IK.generated_poses(lib, name)[0]) == 0
+
+
+@pytest.mark.parametrize("nj", IK.KEYED_SIZES)
+def test_keyed_rigs_equal_the_emulation(lib, nj):
+    """srt_pt_rig_posed_host on the keyed rigs of test_pt_ik_gpu.py against the host emulation of pt_anim.h, at every time; half the
+    joints keyed, every knot count present, a keyed joint in the last block of 64."""
+    g = IK.generated_keyed(nj)
+    counts = np.diff(g["knot_offsets"].astype(np.int64))
+    assert (counts > 0).sum() == nj // 2 and set(counts.tolist()) == set(AC.KNOTS) and (counts[64 * ((nj - 1) // 64):] > 0).any()
+    assert not AC.bits_equal(g["had"], g["rest_pose"])
+    rig = (np.ascontiguousarray(g["parent"], np.int32), g["extent"], g["base"], g["rest_pose"], g["knot_offsets"], g["knot_times"], g["knot_quats"])
+    for t in AC.TIMES:
+        euler, posed = IK.posed_host(lib, g, t)
+        e_euler, e_posed = AC.emu_rig(*rig, t)
+        assert AC.mismatches(euler, e_euler) == 0 and AC.mismatches(posed, e_posed) == 0, float(t)
+        assert np.isfinite(posed).all()
 
 
 def test_refusals_leave_the_pose_alone(lib):
