@@ -175,6 +175,15 @@ int srt_pt_math_box_sweep(srt_pt* pt, const float* in, size_t lanes, float* out)
  * of 64.  in: first, per wave, the matrix as Mat4::data has it (16 floats, column-major), then 3 planes of `lanes` floats (the point);
  * out: 7 planes (x, y, z from mat_point_affine, x, y, z from mat_point, and 1 where the lane's wave did not compute w). */
 int srt_pt_math_point_affine(srt_pt* pt, const float* in, size_t lanes, float* out);
+/* The top-down sweep of pt_wave.h over a seven-node tree with the min / max step behind its no-NaN guard (pt_trace.h: box_hit_minmax;
+ * a wave takes it iff every box of its tree is finite with lo <= hi and every lane's origin is finite and its reciprocals finite and
+ * not zero) next to the same sweep through the old step, one tree per wave of 64 consecutive lanes, lane i on its own ray.  lanes must
+ * be a multiple of 64.  in: first, per wave, seven WaveInterior records (16 words each: left box min xyz max xyz, right box the same,
+ * l_ref, r_ref, two counts; a child reference is negative for a leaf or the index of a later node of the seven), then 10 planes of
+ * `lanes` floats (origin xyz, reciprocal direction xyz, the root's times x and y, dist_bounds x and y); out: 85 planes - per node
+ * {flag nibble as a 32-bit integer, cur_far_t.x, left child's times x, y, right child's times x, y} of the guarded sweep (42), the
+ * same of the old step (42), and 1 where the lane's wave took the min / max step. */
+int srt_pt_math_topdown_minmax(srt_pt* pt, const float* in, size_t lanes, float* out);
 
 /* The HIP resources the library holds at this moment, process-wide (every path-tracer and rasterizer context, skin and timeline):
  * out = {device buffers, pinned host buffers, events}.  Each counts the live allocations, not their bytes.  A test reads it before

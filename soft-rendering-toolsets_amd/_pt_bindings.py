@@ -186,6 +186,7 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_math_leaf_fold.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_box_sweep.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_point_affine.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_math_topdown_minmax.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_math_sphere_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_sync.argtypes = [c_void_p]
     lib.srt_pt_cancel.argtypes = [c_void_p]
@@ -1595,6 +1596,24 @@ class Pathtracer:
         out = np.zeros((7, n), np.float32)
         self._check(self._lib, self._lib.srt_pt_math_point_affine(self._ctx, _p(buf), n, _p(out)))
         return out[0:3].T.copy(), out[3:6].T.copy(), out[6].reshape(W, 64)[:, 0] != 0
+
+    def math_topdown_minmax(self, records, rays):
+        """The top-down sweep with the min / max step behind its guard and through the old step alone, on W waves of 64 lanes with one
+        seven-node tree each.  records (W, 7, 16) uint32 = WaveInterior words; rays (W * 64, 10) = origin, reciprocal direction, the
+        root's times, dist_bounds.  Returns (guarded (n, 7, 6) uint32, old (n, 7, 6) uint32 - per node {flags, cur_far_t.x, left times
+        x, y, right times x, y} as bits -, per wave whether it took the min / max step)."""
+        records = np.ascontiguousarray(records, np.uint32).reshape(-1, 7, 16)
+        rays = _f32(rays).reshape(-1, 10)
+        W, n = len(records), len(rays)
+        assert n == 64 * W and W > 0
+        buf = np.ascontiguousarray(np.concatenate([records.ravel().view(np.float32), rays.T.ravel()]), np.float32)
+        out = np.zeros((85, n), np.float32)
+        self._check(self._lib, self._lib.srt_pt_math_topdown_minmax(self._ctx, _p(buf), n, _p(out)))
+        bits = out[:84].view(np.uint32)
+        form = lambda b: np.ascontiguousarray(bits[b:b + 42].reshape(7, 6, n).transpose(2, 0, 1))
+        took = out[84].reshape(W, 64) != 0
+        assert (took == took[:, :1]).all()
+        return form(0), form(42), took[:, 0]
 
     def math_cos_sin(self, x):
         x = _f32(x)

@@ -2,6 +2,8 @@
 // caller-supplied operands, so that a test can compare it with the host's libm or with the plain per-ray form.  No scene, no render.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "pt_anim.h"
 #include "pt_context.h"
 #include "pt_device.h"
@@ -251,6 +253,54 @@ __global__ void pt_point_affine_kernel(const float* __restrict__ in, size_t lane
   out[6 * lanes + i] = skipped ? 1.0f : 0.0f;
 }
 
+// The top-down sweep of pt_wave.h with the min / max step behind its guard (box_hit_minmax, the minmax_*_ok predicates, pt_trace.h)
+// next to the same sweep through the old step alone, one seven-node tree per wave of 64 lanes, lane i on its own ray.  The loop and
+// the guard are those of pt_wave_kernel, restated (change both): the boxes once per wave, origin and reciprocals in one ballot, the
+// old loop behind one scalar branch, `times` and flags through LDS slots.  Layout: srt_pt_math_topdown_minmax.
+constexpr int kProbeQ = 7;
+__global__ void pt_topdown_minmax_kernel(const float* __restrict__ in, size_t lanes, float* __restrict__ out) {
+  __shared__ float s_slot[4][kProbeQ][2][64];
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= lanes) return;                               // (whole waves: lanes % 64 == 0)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t w = (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(i / 64));
+  const WaveInterior* __restrict__ recs = reinterpret_cast<const WaveInterior*>(in) + w * kProbeQ;
+  const float* pl = in + (lanes / 64) * kProbeQ * 16;
+  float v[10];
+#pragma unroll
+  for (int j = 0; j < 10; j++) v[j] = pl[(size_t)j * lanes + i];
+  const V3 org = v3(v[0], v[1], v[2]), inv = v3(v[3], v[4], v[5]);
+  const float tx0 = v[6], ty0 = v[7], rb0 = v[8], rb1 = v[9];
+#define PSLOT(q, f) s_slot[wave][q][f][lane]
+  bool bok = true;
+  if (lane < kProbeQ) {
+    const bool l = minmax_box_ok(recs[lane].boxl), r = minmax_box_ok(recs[lane].boxr);
+    bok = l & r;
+  }
+  const bool boxes_ok = __ballot(!bok) == 0ull;
+  const bool org_ok = minmax_origin_ok(org), inv_ok = minmax_inv_ok(inv);
+  const bool ok = org_ok & inv_ok;
+  const bool fast = boxes_ok && __ballot(!ok) == 0ull;
+  auto sweep = [&](auto minmax, float* __restrict__ o) {
+    for (int q = 0; q < kProbeQ; q++) {
+      const WaveInterior& W = recs[q];
+      float tx = tx0, ty = ty0;
+      if (q != 0) { tx = PSLOT(q, 0); ty = PSLOT(q, 1); }
+      float fx, lx, ly, rx, ry;
+      const uint32_t f = topdown_step<decltype(minmax)::value>(W, org, inv, tx, ty, rb0, rb1, fx, lx, ly, rx, ry);
+      if (q != 0) { PSLOT(q, 0) = fx; PSLOT(q, 1) = __uint_as_float(f); }
+      if (W.l_ref >= 0) { PSLOT(W.l_ref, 0) = lx; PSLOT(W.l_ref, 1) = ly; }
+      if (W.r_ref >= 0) { PSLOT(W.r_ref, 0) = rx; PSLOT(W.r_ref, 1) = ry; }
+      float* p = o + (size_t)(6 * q) * lanes + i;
+      p[0] = __uint_as_float(f); p[lanes] = fx; p[2 * lanes] = lx; p[3 * lanes] = ly; p[4 * lanes] = rx; p[5 * lanes] = ry;
+    }
+  };
+  if (fast) sweep(std::true_type{}, out); else sweep(std::false_type{}, out);
+  sweep(std::false_type{}, out + (size_t)(6 * kProbeQ) * lanes);
+  out[(size_t)(12 * kProbeQ) * lanes + i] = fast ? 1.0f : 0.0f;
+#undef PSLOT
+}
+
 }  // namespace srt
 
 using namespace srt;
@@ -369,6 +419,22 @@ int srt_pt_math_point_affine(srt_pt* pt, const float* in, size_t lanes, float* o
   if (lanes % 64) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_point_affine: %zu lanes are not whole waves of 64", lanes);
   return math_round_trip(pt, "srt_pt_math_point_affine", {in}, (lanes / 64) * 16 + 3 * lanes, {out}, 7 * lanes, [&](float* const* d, float* const* o) {
     pt_point_affine_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
+}
+
+int srt_pt_math_topdown_minmax(srt_pt* pt, const float* in, size_t lanes, float* out) {
+  if (lanes % 64) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_topdown_minmax: %zu lanes are not whole waves of 64", lanes);
+  if (in)                                               // a child is a leaf (< 0) or a later node of the wave's seven: the slots it indexes
+    for (size_t w = 0; w < lanes / 64; w++)
+      for (int q = 0; q < kProbeQ; q++) {
+        WaveInterior W;
+        __builtin_memcpy(&W, in + (w * kProbeQ + (size_t)q) * 16, sizeof(W));
+        for (int32_t ref : {W.l_ref, W.r_ref})
+          if (ref >= 0 && (ref <= q || ref >= kProbeQ))
+            return srt::fail(SRT_ERR_INVALID, "srt_pt_math_topdown_minmax: wave %zu, node %d has child %d (a leaf, or %d..%d)", w, q, ref, q + 1, kProbeQ - 1);
+      }
+  const size_t in_floats = (lanes / 64) * kProbeQ * 16 + 10 * lanes;
+  return math_round_trip(pt, "srt_pt_math_topdown_minmax", {in}, in_floats, {out}, (12 * kProbeQ + 1) * lanes, [&](float* const* d, float* const* o) {
+    pt_topdown_minmax_kernel<<<math_grid(lanes), dim3(256), 0, pt->stream>>>(d[0], lanes, o[0]); });
 }
 
 }  // extern "C"

@@ -256,16 +256,88 @@ SRT_DEV bool box_hit_inv(const float* __restrict__ bx, V3 o, V3 inv, float& tx, 
   return hit;
 }
 
+// The guard of box_hit_minmax below, in two parts.  A lane's batch passes when the origin is finite and each reciprocal is
+// finite and not zero (one class compare each; the sweep folds the twelve of a three-ray batch into one ballot); a box passes
+// when its six bounds are finite and lo <= hi on every axis (an empty box - lo = FLT_MAX, hi = -FLT_MAX - does not, nor does a
+// sphere of infinite radius).
+SRT_DEV bool class_finite_nonzero(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_classf(v, 0x198);             // -normal, -denormal, +denormal, +normal
+#else
+  return finite_f(v) && v != 0.0f;
+#endif
+}
+SRT_DEV bool minmax_origin_ok(V3 o) {
+  const bool x = class_finite(o.x), y = class_finite(o.y), z = class_finite(o.z);
+  return x & y & z;
+}
+SRT_DEV bool minmax_inv_ok(V3 inv) {
+  const bool x = class_finite_nonzero(inv.x), y = class_finite_nonzero(inv.y), z = class_finite_nonzero(inv.z);
+  return x & y & z;
+}
+SRT_DEV bool minmax_box_ok(const float* __restrict__ bx) {
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const bool lo = finite_f(bx[a]), hi = finite_f(bx[3 + a]);
+    ok = ok & lo & hi & (bx[a] <= bx[3 + a]);
+  }
+  return ok;
+}
+
+// box_hit_inv from per-axis min / max: the values of box_hit_inv for every input that passes the guard above, whatever `times`
+// hold.  Only the sign of a zero in `times` may differ.
+//   No product is NaN.  b - o is finite or, on overflow, +-inf, never NaN (both operands are finite); times a finite reciprocal
+//   that is not zero it is finite or +-inf (0 * inf would need an infinite factor next to a zero one; inf * 0 a zero reciprocal).
+//   Each axis interval is ordered.  lo <= hi and rounding is monotone, so lo - o <= hi - o, and multiplying by inv keeps the
+//   order (inv > 0) or turns it round (inv < 0), again through a monotone rounding: box_hit_inv's select on the sign of inv
+//   picks the smaller product as the axis' tmin and the larger as its tmax - min(l, h) and max(l, h) as values.  Where
+//   l == h (a flat box, or both products rounded alike) the two forms may pick zeros of different sign, nothing else.
+//   The running tmin / tmax are the same values.  `(tymin > tmin) ? tymin : tmin` is max(tmin, tymin) for operands that are
+//   not NaN, `(tymax < tmax) ? tymax : tmax` is min, up to the sign of a zero.
+//   The verdict is the same.  With three ordered intervals box_hit_inv's two partial verdicts (x against y, then their
+//   intersection against z) say "miss" iff the intersection of all three is empty, which is tmin > tmax of the final values:
+//   if x and y are disjoint the running tmin exceeds the running tmax and the z step can only push them further apart;
+//   if not, the running pair is ordered and miss_z is the emptiness of its intersection with z.  Every comparison treats
+//   -0 and +0 alike.
+//   `times` are narrowed alike.  box_hit_inv: nx = (tmin in [tx, ty]) ? tmin : tx, ny = (tmax >= nx & tmax <= ty) ? tmax : ty,
+//   both kept only on a hit.  On a hit tmin <= tmax, so where nx = tmin the test tmax >= nx holds, and where nx = tx it is
+//   tmax >= tx: in2 below.  A NaN in tx or ty fails the same comparisons in both forms (every one of them has it as an
+//   operand there and here).
+//   Readers of what may carry the other zero: the children's own tests (tmin >= tx, tmin <= ty, tmax >= tx, tmax <= ty),
+//   `t1x < t2x` in topdown_step, `farx < rc.dist` in packed_combine and `farx < other[r].dist` in need_of (pt_wave.h) - ordered
+//   comparisons all, blind to the sign of a zero; the leaf tests take dist_bounds, not `times`.  A child's nx can only be a zero
+//   that the comparisons above cannot tell from the other, so the flag bits, the child order and every result downstream are
+//   the same (tests/test_pt_box_minmax_host.py counts the zeros and holds everything else to box_hit_inv).
+// The axes are folded one after the other so that two products are alive at a time, not six.
+SRT_DEV bool box_hit_minmax(const float* __restrict__ bx, V3 o, V3 inv, float& tx, float& ty) {
+  const float b0 = bx[0], b1 = bx[1], b2 = bx[2], b3 = bx[3], b4 = bx[4], b5 = bx[5];
+  const float lx = (b0 - o.x) * inv.x, hx = (b3 - o.x) * inv.x;
+  float tmin = __builtin_fminf(lx, hx), tmax = __builtin_fmaxf(lx, hx);
+  const float ly = (b1 - o.y) * inv.y, hy = (b4 - o.y) * inv.y;
+  tmin = __builtin_fmaxf(tmin, __builtin_fminf(ly, hy)); tmax = __builtin_fminf(tmax, __builtin_fmaxf(ly, hy));
+  const float lz = (b2 - o.z) * inv.z, hz = (b5 - o.z) * inv.z;
+  tmin = __builtin_fmaxf(tmin, __builtin_fminf(lz, hz)); tmax = __builtin_fminf(tmax, __builtin_fmaxf(lz, hz));
+  const bool hit = !(tmin > tmax);
+  const bool in1 = hit & (tmin >= tx) & (tmin <= ty);
+  const bool in2 = hit & (in1 | (tmax >= tx)) & (tmax <= ty);
+  tx = in1 ? tmin : tx;
+  ty = in2 ? tmax : ty;
+  return hit;
+}
+
 // One (node, ray) step of the top-down sweep of pt_wave.h: both child boxes, the nearer / farther decision as in
 // student/bvh.inl:186-209 (both hit -> smaller entry time first, ties: right; one hit -> that one, the other child gets
 // ray.dist_bounds as its `times`), and the `times` for the children.  Returns the node's four flag bits {1 left hit, 2 right hit,
 // 4 left nearer, 8 both}; farx = cur_far_t.x; (lx, ly) / (rx, ry) = `times` of the children.
 // (mask algebra, not `hb ? (t1x < t2x) : hl`: a bool chosen by a bool goes through a 0 / 1 register and back)
+// MINMAX: the box tests as box_hit_minmax - for a wave whose boxes and batch passed its guard.
+template <bool MINMAX = false>
 SRT_DEV uint32_t topdown_step(const WaveInterior& W, V3 org, V3 inv, float tx, float ty, float rb0, float rb1,
                               float& farx, float& lx, float& ly, float& rx, float& ry) {
   float t1x = tx, t1y = ty, t2x = tx, t2y = ty;
-  const bool hl = box_hit_inv(W.boxl, org, inv, t1x, t1y);
-  const bool hr = box_hit_inv(W.boxr, org, inv, t2x, t2y);
+  const bool hl = MINMAX ? box_hit_minmax(W.boxl, org, inv, t1x, t1y) : box_hit_inv(W.boxl, org, inv, t1x, t1y);
+  const bool hr = MINMAX ? box_hit_minmax(W.boxr, org, inv, t2x, t2y) : box_hit_inv(W.boxr, org, inv, t2x, t2y);
   const bool hb = hl & hr;
   const bool cl = (hb & (t1x < t2x)) | (!hb & hl);
   // closer = (cl ? t1 : t2), second = hb ? (cl ? t2 : t1) : dist_bounds, and the left child is the closer one iff cl.  Written out

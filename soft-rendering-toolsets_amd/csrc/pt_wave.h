@@ -38,6 +38,8 @@
 #define SRT_PT_WAVE_H
 
 
+#include <type_traits>
+
 #include "pt_trace.h"
 #include "pt_flat.h"
 #include "pt_stream.h"
@@ -436,6 +438,26 @@ template <> struct ColdU32<true> {
 constexpr int kColdWords = 4;
 __host__ __device__ constexpr bool cold_in_lds(int trav) { return trav == 0; }
 
+// The wave-uniform flags of pt_wave_kernel.  The forms that carry the boxes' verdict for the min / max step keep it in one scalar
+// with "the unit queue is empty": the kernel stands at its 106 SGPRs, and a scalar of its own alive across the batch loop cost the
+// headline form 104 B of scratch per lane (and an LDS word the CU's fourth block: the slots and the cold words fill its 160 KiB
+// exactly).  Every other form keeps its bool, and compiles as before.
+template <bool WITH_BOXES> struct WaveFlags;
+template <> struct WaveFlags<false> {
+  bool empty_ = false;
+  SRT_DEV bool queue_empty() const { return empty_; }
+  SRT_DEV void set_queue_empty() { empty_ = true; }
+  SRT_DEV bool boxes_ok() const { return false; }
+  SRT_DEV void set_boxes_ok() {}
+};
+template <> struct WaveFlags<true> {
+  uint32_t bits_ = 0u;
+  SRT_DEV bool queue_empty() const { return (bits_ & 1u) != 0u; }
+  SRT_DEV void set_queue_empty() { bits_ |= 1u; }
+  SRT_DEV bool boxes_ok() const { return (bits_ & 2u) != 0u; }
+  SRT_DEV void set_boxes_ok() { bits_ |= 2u; }
+};
+
 // PHASE (streamed sweeps, TRAV 4, without delta / environment lights): the two passes of a generation as TWO kernels.
 //   1 "resolve": load the slot, complete sweep with the walks' results, finish the bounce, terminate or shade, save.
 //   2 "probe":   load what the next batch's rays need (origin, directions, bounds, flags), refill idle slots from the unit queue,
@@ -478,6 +500,10 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   // (the leaf fold's candidate pass raises the scratch of two forms - the stamped TRAV 1 build and the delta-light probe build
   // of the streamed sweeps - by 16 and 4 B per lane: they keep the fold over tri_hitN.  Same bits either way.)
   constexpr bool LEAF_ONCE = !(STAMP && TRAV == 1) && !(TRAV == 4 && DL && PHASE == 0);
+  // The top-down step's box tests from min / max (box_hit_minmax, pt_trace.h) behind its no-NaN guard: the persistent sweep forms
+  // without delta lights.  The other sweep forms gain scratch with a second copy of the loop and keep the one step; and
+  // SRT_PLAIN_DIV_SQRT switches it off with the other fast paths.
+  constexpr bool MINMAX = SRT_EXACT_FAST_PATHS && TRAV == 0 && !DL && PHASE == 0;
   if constexpr (STREAM) {
     if (P_in.sc->done != 0u) return;                     // every unit is finished: the remaining generations are no-ops
   }
@@ -525,9 +551,9 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   }
   // per-wave sweep slots: [q][ray][field] x 64 lanes.  A slot is reused as it goes through the sweeps:
   //   written by the parent   field 0 = tin.x, field 1 = tin.y      (top-down, before step q)
-  //   after step q            field 0 = cur_far_t.x of node q        (tin is dead once read)
-  //   after bottom-up step q  field 0 = ret.dist, field 1 = ret.id   (read by the parent)
-  // The root (q = 0) has no slot: it receives no `times` and nobody reads its result; its cur_far_t.x stays in registers.
+  //   after step q            field 0 = cur_far_t.x of node q, field 1 = the node's four flag bits (tin is dead once read)
+  //   after bottom-up step q  field 0 = ret.dist, field 1 = ret.id   (read by the parent; the flags are read before ret.id lands)
+  // The root (q = 0) has no slot: it receives no `times` and nobody reads its result; its cur_far_t.x and flags stay in registers.
   constexpr bool COLD = cold_in_lds(TRAV);
   uint32_t* const cold = reinterpret_cast<uint32_t*>(lds_f) + threadIdx.x;           // [variable][thread of the block]
   float* wl = lds_f + (COLD ? kColdWords * 256 : 0) + (size_t)wave * (Q > 0 ? Q - 1 : 0) * (2 * NR) * 64 + lane;   // (PHASE 2: no dynamic LDS, never touched)
@@ -597,7 +623,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
 
   // wave-uniform queue window
   uint32_t chunk_next = 0, chunk_end = 0;
-  bool queue_empty = false;
+  WaveFlags<MINMAX> wflags;                              // "the unit queue is empty" (and, MINMAX, the boxes' verdict)
   uint32_t units_finished = 0;                           // TRAV 3: units this lane completed (or found outside the image)
 
   // TRAV == 3 (pt_stream.h): this invocation is one generation.  The slot's state comes from HBM, pass 0 of the loop
@@ -706,6 +732,19 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
     }
   };
 
+  // The first part of the min / max step's guard, once per launch and wave: every box of the sweep's records is finite with
+  // lo <= hi.  Read from the records themselves - the device-side refit and repose paths rewrite them without the host -, a lane
+  // per record, one ballot.
+  if constexpr (MINMAX) {
+    bool ok = true;
+    for (uint32_t q = (uint32_t)lane; q < Q; q += 64u) {
+      const WaveInterior& W = S.wave_tlas[q];
+      const bool l = minmax_box_ok(W.boxl), r = minmax_box_ok(W.boxr);
+      ok = ok & l & r;
+    }
+    if (__ballot(!ok) == 0ull) wflags.set_boxes_ok();
+  }
+
   for (int pass = (PHASE == 2 ? 1 : 0);; pass++) {
     // ---------------- 1. refill idle lanes ----------------
     const unsigned long long need = (!STREAM || (PHASE != 1 && pass == 1)) ? __ballot(!alive && has_slot) : 0ull;
@@ -729,20 +768,20 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         __syncthreads();                                  // (s_blk is reused below)
       }
     }
-    if ((!STREAM && need != 0ull && !(queue_empty && chunk_next == chunk_end)) || (STREAM && PHASE != 1 && pass == 1)) {
+    if ((!STREAM && need != 0ull && !(wflags.queue_empty() && chunk_next == chunk_end)) || (STREAM && PHASE != 1 && pass == 1)) {
       const uint32_t want = (uint32_t)__popcll(need);
       const uint32_t my_rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
       uint32_t given = 0, my_unit = stream_unit;
       while (!STREAM && given < want) {
         if (chunk_next == chunk_end) {
-          if (queue_empty) break;
+          if (wflags.queue_empty()) break;
           unsigned long long start = 0;
           const uint32_t grab = P.chunk;
           if (lane == 0) {
             start = atomicAdd(P.queue_head, (unsigned long long)grab);
           }
           start = __shfl(start, 0);
-          if (start >= P.total_units) { queue_empty = true; break; }
+          if (start >= P.total_units) { wflags.set_queue_empty(); break; }
           chunk_next = (uint32_t)start;
           chunk_end = (uint32_t)(start + grab < P.total_units ? start + grab : P.total_units);
         }
@@ -822,7 +861,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
       }
     } else {
       if (__ballot(alive) == 0ull) {
-        if (queue_empty && chunk_next == chunk_end) break;
+        if (wflags.queue_empty() && chunk_next == chunk_end) break;
         continue;
       }
     }
@@ -932,11 +971,11 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
     } else {
       V3 inv[NR];
       float tx0[NR], ty0[NR];
-      unsigned long long fl[NR];
+      uint32_t fl0[NR];
       float farx0[NR];
 #pragma unroll
       for (int r = 0; r < NR; r++) {
-        fl[r] = 0ull; farx0[r] = 0.0f;
+        fl0[r] = 0u; farx0[r] = 0.0f;
         inv[r] = v3(1.0f / d[r].x, 1.0f / d[r].y, 1.0f / d[r].z);
         const float dn = norm(d[r]);
         tx0[r] = rb0[r] / dn; ty0[r] = rb1[r] / dn;   // Vec2 time_initial = dist_bounds / dir.norm()
@@ -945,7 +984,8 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
       // (The loop sits in a lambda that is called at once.  Same arithmetic either way, but with the loop written inline this
       //  compiler keeps more scalars alive across it and spills them: 420 v_readlane / v_writelane in the Cornell kernel against
       //  350 - the parent has 336 - and half of what the leaf section's point transforms gain is lost again)
-      auto topdown = [&]() {
+      // (A generic lambda, instantiated for both forms of the step: std::true_type = the box tests from min / max.)
+      auto topdown = [&](auto minmax) {
         for (uint32_t q = 0; q < Q; q++) {
           const WaveInterior& W = S.wave_tlas[q];
 #pragma unroll
@@ -953,15 +993,24 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
             float tx = tx0[r], ty = ty0[r];
             if (q != 0) { tx = SLOT(q, r, 0); ty = SLOT(q, r, 1); }
             float fx, lx, ly, rx, ry;
-            const uint32_t f = topdown_step(W, org, inv[r], tx, ty, rb0[r], rb1[r], fx, lx, ly, rx, ry);
-            fl[r] |= (unsigned long long)f << (4 * q);
-            if (q != 0) SLOT(q, r, 0) = fx; else farx0[r] = fx;
+            const uint32_t f = topdown_step<decltype(minmax)::value>(W, org, inv[r], tx, ty, rb0[r], rb1[r], fx, lx, ly, rx, ry);
+            if (q != 0) { SLOT(q, r, 0) = fx; SLOT(q, r, 1) = __uint_as_float(f); } else { farx0[r] = fx; fl0[r] = f; }
             if (W.l_ref >= 0) { SLOT(W.l_ref, r, 0) = lx; SLOT(W.l_ref, r, 1) = ly; }
             if (W.r_ref >= 0) { SLOT(W.r_ref, r, 0) = rx; SLOT(W.r_ref, r, 1) = ry; }
           }
         }
       };
-      topdown();
+      // The min / max step (box_hit_minmax, pt_trace.h) behind its guard: the launch's boxes passed (wflags, above the batch
+      // loop) and no lane of this batch has an origin that is not finite or a reciprocal that is zero, infinite or NaN - an
+      // axis-parallel direction, that is.  One scalar branch; any failing lane sends the wave's batch through the old step.
+      bool batch_ok = false;
+      if constexpr (MINMAX) {
+        bool ok = minmax_origin_ok(org);
+#pragma unroll
+        for (int r = 0; r < NR; r++) { const bool inv_ok = minmax_inv_ok(inv[r]); ok = ok & inv_ok; }
+        batch_ok = wflags.boxes_ok() && __ballot(!ok) == 0ull;
+      }
+      if (MINMAX && batch_ok) topdown(std::true_type{}); else topdown(std::false_type{});
       SECTION_END(ST_TOPDOWN)
       // bottom-up: leaves are evaluated in place, interior children read back, then the visit rule + Trace::min
       for (int q = (int)Q - 1; q >= 0; q--) {
@@ -997,7 +1046,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         auto need_of = [&](bool is_left, const PHit* other, bool other_known, bool* need) {
 #pragma unroll
           for (int r = 0; r < NR; r++) {
-            const uint32_t f = (uint32_t)(fl[r] >> (4 * q)) & 15u;
+            const uint32_t f = (q != 0) ? __float_as_uint(SLOT(q, r, 1)) : fl0[r];
             const bool nearer = ((f & 4u) != 0) == is_left;
             const float farx = (q != 0) ? SLOT(q, r, 0) : farx0[r];
             const bool second = !other_known | (farx < other[r].dist) | ((other[r].id == kRetMiss) & ((f & 8u) != 0));
@@ -1071,7 +1120,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         SECTION_END(ST_LEAVES)
 #pragma unroll
         for (int r = 0; r < NR; r++) {
-          const uint32_t f = (uint32_t)(fl[r] >> (4 * q)) & 15u;
+          const uint32_t f = (q != 0) ? __float_as_uint(SLOT(q, r, 1)) : fl0[r];
           const float farx = (q != 0) ? SLOT(q, r, 0) : farx0[r];
           // the visit rule (student/bvh.inl:216) and Trace::min on the two-word form: packed_combine, pt_trace.h
           const PHit ret = packed_combine(L[r], R[r], (f & 3u) != 0, (f & 4u) != 0, (f & 8u) != 0, farx);
