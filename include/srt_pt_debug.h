@@ -185,11 +185,11 @@ int srt_pt_math_point_affine(srt_pt* pt, const float* in, size_t lanes, float* o
  * same of the old step (42), and 1 where the lane's wave took the min / max step. */
 int srt_pt_math_topdown_minmax(srt_pt* pt, const float* in, size_t lanes, float* out);
 
-/* The HIP resources the library holds at this moment, process-wide (every path-tracer and rasterizer context, skin and timeline):
- * out = {device buffers, pinned host buffers, events}.  Each counts the live allocations, not their bytes.  A test reads it before
- * and after a sequence of calls that ends with the destroys: equal readings mean nothing leaked and nothing was freed twice.
- * Needs no context and no device. */
-int srt_pt_live_resources(uint64_t out[3]);
+/* The HIP resources the library holds at this moment, process-wide (every path-tracer and rasterizer context, multi-device group,
+ * skin and timeline): out = {device buffers, pinned host buffers, events, streams}.  Each counts the live allocations, not their
+ * bytes.  A test reads it before and after a sequence of calls that ends with the destroys: equal readings mean nothing leaked and
+ * nothing was freed twice.  Needs no context and no device. */
+int srt_pt_live_resources(uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -219,10 +219,10 @@ def bind(lib: ctypes.CDLL) -> None:
 
 
 def live_resources() -> tuple:
-    """srt_pt_live_resources: the (device buffers, pinned buffers, events) the library holds right now, process-wide."""
+    """srt_pt_live_resources: the (device buffers, pinned buffers, events, streams) the library holds right now, process-wide."""
     from . import _check, load_library
     lib = load_library()
-    out = np.zeros(3, np.uint64)
+    out = np.zeros(4, np.uint64)
     _check(lib, lib.srt_pt_live_resources(out.ctypes.data_as(c_void_p)))
     return tuple(int(v) for v in out)
 
@@ -428,79 +428,113 @@ class Skin:
             pass
 
 
-class SkinGroup:
+def _settle(members) -> None:
+    """srt_pt_sync on every member (a Pathtracer each).  The group's lanes render on streams of their own, which nothing orders behind
+    the stream an enqueue-only call was given: the group forms of such calls settle every member before they return."""
+    for m in members:
+        m.sync()
+
+
+def _one_per_rank(ptrs, ranks: int, message: str = "{ranks} ranks but {got} device arrays") -> list:
+    """The per-rank device pointers of a group call as a list, or ValueError when there is not one per rank."""
+    ptrs = list(ptrs)
+    if len(ptrs) != ranks:
+        raise ValueError(message.format(ranks=ranks, got=len(ptrs)))
+    return ptrs
+
+
+def _handle_per_rank(make, *per_rank) -> list:
+    """[make(*one of each per-rank list) for every rank]; when one fails the handles made so far are closed and the error goes on."""
+    made = []
+    try:
+        for args in zip(*per_rank):
+            made.append(make(*args))
+    except Exception:
+        for h in made:
+            h.close()
+        raise
+    return made
+
+
+class _HandleGroup:
+    """What the handle groups of a PathtracerGroup share: one handle per rank (the scene is replicated), every rank gets the same calls
+    (_all), rank 0 answers the read-backs (_first: the ranks hold the same bits)."""
+
+    def __init__(self, handles):
+        self._handles = handles
+
+    def _all(self, name, *args, **kw):
+        return [getattr(h, name)(*args, **kw) for h in self._handles]
+
+    def _first(self, name, *args, **kw):
+        return getattr(self._handles[0], name)(*args, **kw)
+
+    def _settle(self) -> None:
+        _settle(h._pt for h in self._handles)
+
+    def close(self) -> None:
+        self._all("close")
+
+
+class SkinGroup(_HandleGroup):
     """PathtracerGroup.create_skin: one Skin per rank (the scene is replicated), posed together."""
 
     def __init__(self, skins):
+        super().__init__(skins)
         self.skins = skins
 
     def map(self):
-        return self.skins[0].map()
+        return self._first("map")
 
     def vertices(self, posed, flat_normals: bool = False):
-        return self.skins[0].vertices(posed, flat_normals)
+        return self._first("vertices", posed, flat_normals)
 
     def pose(self, posed, flat_normals: bool = False) -> None:
-        for k in self.skins:
-            k.pose(posed, flat_normals)
+        self._all("pose", posed, flat_normals)
 
     def pose_refit(self, posed, flat_normals: bool = False) -> None:
-        for k in self.skins:
-            k.pose_refit(posed, flat_normals)
-
-    def _settle(self) -> None:
-        for k in self.skins:
-            k._check(k._lib, k._lib.srt_pt_sync(k._pt._ctx))
+        self._all("pose_refit", posed, flat_normals)
 
     def pose_inplace(self, posed, flat_normals: bool = False) -> None:
         """Skin.pose_inplace on every rank.  The group's lanes render on streams of their own, which nothing orders behind the
         pose's stream: every member is settled (srt_pt_sync) before this returns, as PathtracerGroup.set_active_device does and for
         the same reason.  A caller that wants the enqueue-only loop drives the members' skins and streams itself."""
-        for k in self.skins:
-            k.pose_inplace(posed, flat_normals)
+        self._all("pose_inplace", posed, flat_normals)
         self._settle()
 
     def pose_inplace_at(self, t: float, flat_normals: bool = False) -> None:
         """Skin.pose_inplace_at on every rank with the same t; every member is settled before this returns (see pose_inplace)."""
-        for k in self.skins:
-            k.pose_inplace_at(t, flat_normals)
+        self._all("pose_inplace_at", t, flat_normals)
         self._settle()
 
     def set_rig(self, parent, base, rest_pose, knot_offsets, knot_times, knot_quats) -> None:
-        for k in self.skins:
-            k.set_rig(parent, base, rest_pose, knot_offsets, knot_times, knot_quats)
+        self._all("set_rig", parent, base, rest_pose, knot_offsets, knot_times, knot_quats)
 
     def posed_at(self, t: float) -> np.ndarray:
-        return self.skins[0].posed_at(t)
+        return self._first("posed_at", t)
 
     def pose_at(self, t: float, flat_normals: bool = False) -> None:
         """Every rank's skin takes the pose of the same time t."""
-        for k in self.skins:
-            k.pose_at(t, flat_normals)
+        self._all("pose_at", t, flat_normals)
 
     def pose_refit_at(self, t: float, flat_normals: bool = False) -> None:
-        for k in self.skins:
-            k.pose_refit_at(t, flat_normals)
+        self._all("pose_refit_at", t, flat_normals)
 
     def set_ik_handles(self, joints) -> None:
-        for k in self.skins:
-            k.set_ik_handles(joints)
+        self._all("set_ik_handles", joints)
 
     def set_joint_pose(self, euler) -> None:
-        for k in self.skins:
-            k.set_joint_pose(euler)
+        self._all("set_joint_pose", euler)
 
     def joint_pose(self) -> np.ndarray:
-        return self.skins[0].joint_pose()
+        return self._first("joint_pose")
 
     def set_time(self, t: float) -> None:
-        for k in self.skins:
-            k.set_time(t)
+        self._all("set_time", t)
 
     def step_ik(self, targets, enabled=None) -> None:
         """Every rank's skin takes the same step: the ranks' poses stay the same bits."""
-        for k in self.skins:
-            k.step_ik(targets, enabled)
+        self._all("step_ik", targets, enabled)
 
     def step_ik_device(self, d_targets_ptrs, d_enabled_ptrs=None) -> None:
         """Skin.step_ik_device on every rank, with one device array per rank (ranks that share a device may share it)."""
@@ -508,18 +542,13 @@ class SkinGroup:
             k.step_ik_device(d_targets_ptrs[r], d_enabled_ptrs[r] if d_enabled_ptrs else 0)
 
     def posed_current(self) -> np.ndarray:
-        return self.skins[0].posed_current()
+        return self._first("posed_current")
 
     def pose_current(self, how: str = "inplace", flat_normals: bool = False) -> None:
         """Skin.pose_current on every rank; with "inplace" every member is settled before this returns (see pose_inplace)."""
-        for k in self.skins:
-            k.pose_current(how, flat_normals)
+        self._all("pose_current", how, flat_normals)
         if how == "inplace":
             self._settle()
-
-    def close(self) -> None:
-        for k in self.skins:
-            k.close()
 
 
 def timeline_tracks(tracks):
@@ -586,29 +615,23 @@ class Timeline:
             pass
 
 
-class TimelineGroup:
+class TimelineGroup(_HandleGroup):
     """PathtracerGroup.create_timeline: one Timeline per rank (the scene is replicated); all ranks get the same t."""
 
     def __init__(self, timelines):
+        super().__init__(timelines)
         self.timelines = timelines
 
     def transforms(self, t: float) -> np.ndarray:
-        return self.timelines[0].transforms(t)
+        return self._first("transforms", t)
 
     def repose_refit(self, t: float, stream: int = 0) -> None:
         """Timeline.repose_refit on every rank; like PathtracerGroup.repose_refit_device each member is settled before this returns."""
-        for tl in self.timelines:
-            tl.repose_refit(t, stream)
-        for tl in self.timelines:
-            tl._check(tl._lib, tl._lib.srt_pt_sync(tl._pt._ctx))
+        self._all("repose_refit", t, stream)
+        self._settle()
 
     def repose(self, t: float, stream: int = 0) -> None:
-        for tl in self.timelines:
-            tl.repose(t, stream)
-
-    def close(self) -> None:
-        for tl in self.timelines:
-            tl.close()
+        self._all("repose", t, stream)
 
 
 class Emitter:
@@ -712,16 +735,14 @@ class Emitter:
             pass
 
 
-class EmitterGroup:
+class EmitterGroup(_HandleGroup):
     """PathtracerGroup.create_emitter: one Emitter per rank (the scene is replicated); every rank gets the same calls.  The device forms
     take one uniform buffer per rank."""
 
     def __init__(self, emitters):
+        super().__init__(emitters)
         self.emitters = emitters
         self.capacity = emitters[0].capacity
-
-    def _all(self, name, *args, **kw):
-        return [getattr(e, name)(*args, **kw) for e in self.emitters]
 
     def set_options(self, *args, **kw) -> None:
         self._all("set_options", *args, **kw)
@@ -733,9 +754,7 @@ class EmitterGroup:
         self._all("seed", seed)
 
     def set_uniforms_device(self, d_uniforms_ptrs, n: int) -> None:
-        if len(d_uniforms_ptrs) != len(self.emitters):
-            raise ValueError(f"{len(d_uniforms_ptrs)} uniform buffers for {len(self.emitters)} ranks")
-        for e, p in zip(self.emitters, d_uniforms_ptrs):
+        for e, p in zip(self.emitters, _one_per_rank(d_uniforms_ptrs, len(self.emitters), "{got} uniform buffers for {ranks} ranks")):
             e.set_uniforms_device(p, n)
 
     def step_device(self, dt: float, stream: int = 0) -> None:
@@ -743,10 +762,6 @@ class EmitterGroup:
 
     def step(self, dt: float) -> None:
         self._all("step", dt)
-
-    def _settle(self) -> None:
-        for e in self.emitters:
-            e._check(e._lib, e._lib.srt_pt_sync(e._pt._ctx))
 
     def present_device(self, stream: int = 0) -> None:
         """Emitter.present_device on every rank; like TimelineGroup.repose_refit each member is settled before this returns."""
@@ -761,16 +776,13 @@ class EmitterGroup:
         self._all("clear")
 
     def read(self) -> dict:
-        return self.emitters[0].read()
+        return self._first("read")
 
     def write(self, **arrays) -> None:
         self._all("write", **arrays)
 
     def counts(self) -> dict:
-        return self.emitters[0].counts()
-
-    def close(self) -> None:
-        self._all("close")
+        return self._first("counts")
 
 
 MATERIAL_DTYPE = np.dtype([("type", np.uint32), ("a", np.float32, 3), ("b", np.float32, 3), ("ior", np.float32)])   # srt_pt_material
@@ -844,30 +856,24 @@ class ShadingTimeline:
             pass
 
 
-class ShadingTimelineGroup:
+class ShadingTimelineGroup(_HandleGroup):
     """PathtracerGroup.create_shading_timeline: one ShadingTimeline per rank (the scene is replicated); all ranks get the same t."""
 
     def __init__(self, timelines):
+        super().__init__(timelines)
         self.timelines = timelines
 
     def values(self, t: float) -> dict:
-        return self.timelines[0].values(t)
+        return self._first("values", t)
 
     def update(self, t: float) -> None:
-        for tl in self.timelines:
-            tl.update(t)
+        self._all("update", t)
 
     def apply(self, t: float, stream: int = 0) -> None:
         """ShadingTimeline.apply on every rank; like TimelineGroup.repose_refit each member is settled before this returns (the
         group's lanes render on streams of their own, which nothing orders behind `stream`)."""
-        for tl in self.timelines:
-            tl.apply(t, stream)
-        for tl in self.timelines:
-            tl._check(tl._lib, tl._lib.srt_pt_sync(tl._pt._ctx))
-
-    def close(self) -> None:
-        for tl in self.timelines:
-            tl.close()
+        self._all("apply", t, stream)
+        self._settle()
 
 
 class Scene:
@@ -1668,10 +1674,7 @@ class PathtracerGroup:
     def repose_device(self, indices, d_trans_ptrs, stream: int = 0) -> None:
         """srt_pt_repose_device on every rank: one device pointer per rank, each on its rank's device (ranks that share a device may
         share the array)."""
-        ptrs = list(d_trans_ptrs)
-        if len(ptrs) != len(self.members):
-            raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
-        for m, ptr in zip(self.members, ptrs):
+        for m, ptr in zip(self.members, _one_per_rank(d_trans_ptrs, len(self.members))):
             m.repose_device(indices, ptr, stream)
 
     def repose_refit(self, indices, Ts) -> None:
@@ -1682,13 +1685,9 @@ class PathtracerGroup:
         """srt_pt_repose_refit_device on every rank: one device pointer per rank, as repose_device.  The group's lanes render on
         streams of their own, which nothing orders behind `stream`: each member is settled (srt_pt_sync) before this returns, so the
         group form waits for the refit.  A caller that wants the enqueue-only loop drives the members and their streams itself."""
-        ptrs = list(d_trans_ptrs)
-        if len(ptrs) != len(self.members):
-            raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
-        for m, ptr in zip(self.members, ptrs):
+        for m, ptr in zip(self.members, _one_per_rank(d_trans_ptrs, len(self.members))):
             m.repose_refit_device(indices, ptr, stream)
-        for m in self.members:
-            m._check(m._lib, m._lib.srt_pt_sync(m._ctx))
+        _settle(self.members)
 
     def set_active(self, indices, flags) -> None:
         """srt_pt_group_set_active: srt_pt_set_active on every rank."""
@@ -1702,10 +1701,8 @@ class PathtracerGroup:
         """srt_pt_group_set_active_device: one device pointer per rank, as repose_refit_device takes d_trans_ptrs; every member is
         settled before this returns (the group's lanes render on streams of their own)."""
         idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
-        ptrs = list(d_active_ptrs)
-        if len(ptrs) != len(self.members):
-            raise ValueError(f"{len(self.members)} ranks but {len(ptrs)} device arrays")
-        arr = (c_void_p * len(ptrs))(*[c_void_p(int(p)) for p in ptrs])
+        ptrs = _one_per_rank(d_active_ptrs, len(self.members))
+        arr =(c_void_p * len(ptrs))(*[c_void_p(int(p)) for p in ptrs])
         self._check(self._lib, self._lib.srt_pt_group_set_active_device(self._g, c_void_p(stream), _p(idx), arr, len(idx)))
 
     def update_mesh(self, index: int, pos, nrm) -> None:
@@ -1729,47 +1726,22 @@ class PathtracerGroup:
             raise ValueError(f"{len(self.members)} ranks but {len(pp)} position and {len(nn)} normal arrays")
         for m, p, n in zip(self.members, pp, nn):
             m.refit_mesh_inplace_device(index, p, n, nverts, stream)
-        for m in self.members:
-            m._check(m._lib, m._lib.srt_pt_sync(m._ctx))
+        _settle(self.members)
 
     def create_skin(self, index: int, bind_pos, bind_nrm, joints) -> SkinGroup:
         """One skin per rank; SkinGroup.pose poses each rank, as update_mesh updates each."""
-        skins = []
-        try:
-            for m in self.members:
-                skins.append(m.create_skin(index, bind_pos, bind_nrm, joints))
-        except Exception:
-            for k in skins:
-                k.close()
-            raise
-        return SkinGroup(skins)
+        return SkinGroup(_handle_per_rank(lambda m: m.create_skin(index, bind_pos, bind_nrm, joints), self.members))
 
     def create_timeline(self, objects, tracks) -> TimelineGroup:
         """One timeline per rank; TimelineGroup.repose_refit / repose give every rank the same t."""
-        made = []
-        try:
-            for m in self.members:
-                made.append(m.create_timeline(objects, tracks))
-        except Exception:
-            for tl in made:
-                tl.close()
-            raise
-        return TimelineGroup(made)
+        return TimelineGroup(_handle_per_rank(lambda m: m.create_timeline(objects, tracks), self.members))
 
     def create_emitter(self, collide_group, objects, radius: float) -> EmitterGroup:
         """One emitter per rank over the rank's own context (srt_pt_group_context) and the same rank of `collide_group` (which may be
         this group): a forwarder, with no group entry points in C."""
         if len(collide_group.members) != len(self.members):
             raise ValueError(f"a collide group of {len(collide_group.members)} ranks for a group of {len(self.members)}")
-        made = []
-        try:
-            for m, c in zip(self.members, collide_group.members):
-                made.append(m.create_emitter(c, objects, radius))
-        except Exception:
-            for em in made:
-                em.close()
-            raise
-        return EmitterGroup(made)
+        return EmitterGroup(_handle_per_rank(lambda m, c: m.create_emitter(c, objects, radius), self.members, collide_group.members))
 
     def update_materials(self, indices, materials) -> None:
         for m in self.members:
@@ -1789,15 +1761,7 @@ class PathtracerGroup:
 
     def create_shading_timeline(self, materials, lights, env, tracks) -> ShadingTimelineGroup:
         """One shading timeline per rank; ShadingTimelineGroup.update / apply give every rank the same t."""
-        made = []
-        try:
-            for m in self.members:
-                made.append(m.create_shading_timeline(materials, lights, env, tracks))
-        except Exception:
-            for tl in made:
-                tl.close()
-            raise
-        return ShadingTimelineGroup(made)
+        return ShadingTimelineGroup(_handle_per_rank(lambda m: m.create_shading_timeline(materials, lights, env, tracks), self.members))
 
     def scene_counts(self) -> list:
         """Every member's Pathtracer.scene_counts(), by rank (the scene is replicated)."""

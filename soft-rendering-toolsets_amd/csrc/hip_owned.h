@@ -1,7 +1,8 @@
-// The owners of what the host code gets from HIP: device memory, pinned host memory and events.  Move-only; a member of one of
-// these types is all a struct needs to say about a resource - no free list mirrors it.  An empty owner makes no HIP call, in its
+// The owners of what the host code gets from HIP: device memory, pinned host memory, events and streams.  Move-only; a member of one
+// of these types is all a struct needs to say about a resource - no free list mirrors it.  An empty owner makes no HIP call, in its
 // destructor, reset() and moves alike (host-only contexts live on machines without a GPU), and no owner sets the device: the
-// entry points have done so before they touch anything.
+// entry points have done so before they touch anything.  A struct whose owners live on several devices (the group of pt_group.cpp)
+// therefore resets each of them under its own device before it is deleted, and leaves its destructor nothing to free.
 #ifndef SRT_HIP_OWNED_H
 #define SRT_HIP_OWNED_H
 
@@ -20,9 +21,9 @@ namespace srt {
 int fail(int status, const char* fmt, ...);   // srt_common.h
 
 // Live objects that hold a resource, per type (srt_pt_live_resources): what a test compares before and after.
-enum OwnedKind { OWNED_DEVICE = 0, OWNED_PINNED = 1, OWNED_EVENT = 2 };
+enum OwnedKind { OWNED_DEVICE = 0, OWNED_PINNED = 1, OWNED_EVENT = 2, OWNED_STREAM = 3, OWNED_KINDS = 4 };
 inline std::atomic<uint64_t>& owned_live(OwnedKind k) {
-  static std::atomic<uint64_t> live[3];
+  static std::atomic<uint64_t> live[OWNED_KINDS];
   return live[k];
 }
 inline void owned_count(OwnedKind k, bool born) {
@@ -163,6 +164,37 @@ class Event {
   hipEvent_t e_ = nullptr;
 };
 using EventPair = std::pair<Event, Event>;   // a timing bracket
+
+// One hipStream_t.  (Whoever holds it synchronises it before it goes: reset() only destroys.)
+class Stream {
+ public:
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+  Stream& operator=(Stream&& o) noexcept {
+    if (this != &o) { reset(); s_ = o.s_; o.s_ = nullptr; }
+    return *this;
+  }
+  ~Stream() { reset(); }
+
+  operator hipStream_t() const { return s_; }
+  void reset() {
+    if (s_) { (void)hipStreamDestroy(s_); owned_count(OWNED_STREAM, false); }
+    s_ = nullptr;
+  }
+  // A new stream (`flags` are hipStreamCreateWithFlags'); one that is there already stays.
+  int create(unsigned flags) {
+    if (s_) return SRT_OK;
+    const hipError_t e = hipStreamCreateWithFlags(&s_, flags);
+    if (e != hipSuccess) { s_ = nullptr; return srt::fail(SRT_ERR_HIP, "hipStreamCreateWithFlags: %s", hipGetErrorString(e)); }
+    owned_count(OWNED_STREAM, true);
+    return SRT_OK;
+  }
+
+ private:
+  hipStream_t s_ = nullptr;
+};
 
 }  // namespace srt
 

@@ -62,7 +62,7 @@ int srt_pt_create(int device, srt_pt** out) {
                        e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
     }
     if (device >= count) { delete pt; return srt::fail(SRT_ERR_INVALID, "device %d out of range [0,%d)", device, count); }
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&pt->stream, hipStreamNonBlocking) != hipSuccess ||
+    if (hipSetDevice(device) != hipSuccess || pt->stream.create(hipStreamNonBlocking) != SRT_OK ||
         pt->d_totals.ensure(C_COUNT + 4) != SRT_OK || pt->h_fault.ensure(1, hipHostMallocMapped) != SRT_OK ||
         pt->h_cancel.ensure(1, hipHostMallocMapped) != SRT_OK ||
         hipMemset(pt->d_totals, 0, (C_COUNT + 4) * sizeof(unsigned long long)) != hipSuccess) {
@@ -85,7 +85,7 @@ int srt_pt_destroy(srt_pt* pt) {
     discard_pending(pt);
     (void)hipStreamSynchronize(pt->stream);
     report_cast_stats(pt);
-    (void)hipStreamDestroy(pt->stream);
+    pt->stream.reset();                                   // (the stream goes first, what its kernels used after it)
   }
   delete pt;
   return SRT_OK;
@@ -348,9 +348,9 @@ int srt_pt_set_ray_log(srt_pt* pt, uint32_t capacity) {
   return SRT_OK;
 }
 
-int srt_pt_live_resources(uint64_t out[3]) {
+int srt_pt_live_resources(uint64_t out[4]) {
   if (!out) return srt::fail(SRT_ERR_INVALID, "srt_pt_live_resources: NULL argument");
-  for (int k = 0; k < 3; k++) out[k] = owned_live((OwnedKind)k).load(std::memory_order_relaxed);
+  for (int k = 0; k < OWNED_KINDS; k++) out[k] = owned_live((OwnedKind)k).load(std::memory_order_relaxed);
   return SRT_OK;
 }
 

@@ -34,7 +34,7 @@ constexpr uint32_t kMaxStreamSlots = 1u << 26;   // srt_pt_set_stream_slots: upp
 
 struct srt_pt {
   int device = -1;            // -1: host-only context (scene assembly / BVH inspection, no rendering)
-  hipStream_t stream = nullptr;
+  srt::Stream stream;
   std::vector<srt::ObjectInput> inputs;
   std::vector<srt::Material> materials;
   srt::BuiltScene built;

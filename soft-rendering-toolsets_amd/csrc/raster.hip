@@ -874,7 +874,7 @@ __global__ __launch_bounds__(WAVE * (TSY == 32 ? 1 : SRT_RASTER_WPB), TSY == 32 
 // ---------------------------------------------------------------------------------------------
 struct srt_raster {
   int device = 0;
-  hipStream_t stream = nullptr;
+  srt::Stream stream;
   RasterParams P{};
   bool have_target = false;
   // The frame's ordered stream, in PINNED host memory (grown geometrically): srt_raster_submit appends here and the upload is
@@ -1300,7 +1300,7 @@ int srt_raster_create(int device, srt_raster** out) {
   r->device = device;
   // (every failure below: srt_raster_destroy takes the partly built context away)
   const auto give_up = [r](const char* what) { (void)srt_raster_destroy(r); return srt::fail(SRT_ERR_HIP, "%s", what); };
-  if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) return give_up("hipStreamCreate failed");
+  if (r->stream.create(hipStreamNonBlocking) != SRT_OK) return give_up("hipStreamCreate failed");
   if (r->d_stats.ensure(ST_COUNT) != SRT_OK || r->d_status.ensure(FS_COUNT) != SRT_OK ||
       hipMemset(r->d_status, 0, FS_COUNT * sizeof(uint32_t)) != hipSuccess || r->h_status.ensure(FS_COUNT, hipHostMallocMapped) != SRT_OK)
     return give_up("hipMalloc(stats) failed");
@@ -1319,7 +1319,7 @@ int srt_raster_destroy(srt_raster* r) {
   (void)hipSetDevice(r->device);
   if (r->stream) (void)hipStreamSynchronize(r->stream);   // (NULL stream / event: a context srt_raster_create gave up on)
   if (r->bound_out) (void)hipHostUnregister(r->bound_out);
-  if (r->stream) (void)hipStreamDestroy(r->stream);
+  r->stream.reset();                                      // (the stream goes first, what its kernels used after it)
   (void)hipGetLastError();
   delete r;
   return SRT_OK;

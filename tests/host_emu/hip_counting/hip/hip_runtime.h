@@ -12,17 +12,19 @@
 enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1 };
 typedef struct hip_counting_event* hipEvent_t;
-enum : unsigned { hipHostMallocDefault = 0u, hipHostMallocMapped = 2u, hipEventDefault = 0u, hipEventDisableTiming = 2u };
+typedef struct hip_counting_stream* hipStream_t;
+enum : unsigned { hipHostMallocDefault = 0u, hipHostMallocMapped = 2u, hipEventDefault = 0u, hipEventDisableTiming = 2u, hipStreamNonBlocking = 1u };
 struct uint2 { unsigned x, y; };
 struct float4 { float x, y, z, w; };
 
 // What the calls did: one letter per call in `log` (m hipMalloc, f hipFree, M hipHostMalloc, F hipHostFree, p
-// hipHostGetDevicePointer, c hipMemcpy, e hipEventCreateWithFlags, d hipEventDestroy), the bytes of the last allocation and copy,
-// and the blocks / events alive.  fail_at = k: the k-th allocating call from now (m, M or e) fails; 0: none does.
+// hipHostGetDevicePointer, c hipMemcpy, e hipEventCreateWithFlags, d hipEventDestroy, s hipStreamCreateWithFlags, x
+// hipStreamDestroy), the bytes of the last allocation and copy, and the blocks / events / streams alive.  fail_at = k: the k-th
+// allocating call from now (m, M, e or s) fails; 0: none does.
 struct HipCounting {
   std::string log;
   size_t last_alloc_bytes = 0, last_copy_bytes = 0;
-  long device_blocks = 0, pinned_blocks = 0, events = 0;
+  long device_blocks = 0, pinned_blocks = 0, events = 0, streams = 0;
   int fail_at = 0;
   bool allocation_fails() { return fail_at > 0 && --fail_at == 0; }
 };
@@ -63,4 +65,13 @@ inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
   return hipSuccess;
 }
 inline hipError_t hipEventDestroy(hipEvent_t e) { HipCounting& c = hip_counting(); c.log += 'd'; if (e) c.events--; std::free(e); return hipSuccess; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+  HipCounting& c = hip_counting();
+  c.log += 's';
+  if (c.allocation_fails()) { *s = nullptr; return hipErrorOutOfMemory; }
+  *s = static_cast<hipStream_t>(std::malloc(1));
+  c.streams++;
+  return hipSuccess;
+}
+inline hipError_t hipStreamDestroy(hipStream_t s) { HipCounting& c = hip_counting(); c.log += 'x'; if (s) c.streams--; std::free(s); return hipSuccess; }
 #endif

@@ -1,4 +1,4 @@
-// TEST-ONLY: the owners of csrc/hip_owned.h (DeviceBuffer, PinnedBuffer, Event) against the counting stand-in for the HIP runtime
+// TEST-ONLY: the owners of csrc/hip_owned.h (DeviceBuffer, PinnedBuffer, Event, Stream) against the counting stand-in for the HIP runtime
 // (tests/host_emu/hip_counting/), as a stand-alone program that tests/test_hip_owned_host.py builds with AddressSanitizer and
 // UndefinedBehaviorSanitizer and runs once.  A double free, a use after free or a leak ends the run with the sanitizer's report.
 #include <cstdarg>
@@ -22,17 +22,24 @@ static HipCounting& C = hip_counting();
 static std::string take_log() { std::string l; l.swap(C.log); return l; }
 static uint64_t live(OwnedKind k) { return owned_live(k).load(); }
 static bool all_gone() {
-  return C.device_blocks == 0 && C.pinned_blocks == 0 && C.events == 0 && live(OWNED_DEVICE) == 0 && live(OWNED_PINNED) == 0 && live(OWNED_EVENT) == 0;
+  return C.device_blocks == 0 && C.pinned_blocks == 0 && C.events == 0 && C.streams == 0 && live(OWNED_DEVICE) == 0 && live(OWNED_PINNED) == 0 &&
+         live(OWNED_EVENT) == 0 && live(OWNED_STREAM) == 0;
 }
 
 // An empty owner makes no call at all: construction, reset(), moves, destruction.
+// Shaped like one rank's slot of a group lane (pt_group.cpp: LaneRank).
+struct LaneSlot { Stream stream; Event event; DeviceBuffer<float> tiles; };
+
 static void empty_owners() {
   {
     DeviceBuffer<float> a, b(std::move(a)); PinnedBuffer<uint32_t> p, q(std::move(p)); Event e, f(std::move(e));
+    Stream s, t(std::move(s));
     DeviceBuffer<void> v;
-    a = std::move(b); p = std::move(q); e = std::move(f);
-    a.reset(); p.reset(); e.reset(); v.reset();
-    CHECK(!a && a.capacity() == 0 && !p && p.capacity() == 0 && p.device() == nullptr && (hipEvent_t)e == nullptr);
+    a = std::move(b); p = std::move(q); e = std::move(f); s = std::move(t);
+    a.reset(); p.reset(); e.reset(); s.reset(); v.reset();
+    CHECK(!a && a.capacity() == 0 && !p && p.capacity() == 0 && p.device() == nullptr && (hipEvent_t)e == nullptr && (hipStream_t)s == nullptr);
+    LaneSlot L, M(std::move(L));
+    L = std::move(M);
     RefitTables T, U(std::move(T));
     T = std::move(U);
     BvhWorkspace W;
@@ -125,6 +132,40 @@ static void events() {
   CHECK(take_log() == "ddd" && all_gone());
 }
 
+static void streams() {
+  {
+    Stream s;
+    CHECK(s.create(hipStreamNonBlocking) == SRT_OK && (hipStream_t)s != nullptr && take_log() == "s" && live(OWNED_STREAM) == 1);
+    const hipStream_t raw = s;
+    CHECK(s.create(hipStreamNonBlocking) == SRT_OK && (hipStream_t)s == raw && take_log().empty());   // one that is there stays
+    Stream t(std::move(s));                                 // construction: no call
+    CHECK((hipStream_t)s == nullptr && (hipStream_t)t == raw && take_log().empty());
+    s = std::move(t);
+    Stream& self = s;
+    s = std::move(self);
+    CHECK((hipStream_t)s == raw && take_log().empty() && live(OWNED_STREAM) == 1);
+    Stream u;
+    CHECK(u.create(hipStreamNonBlocking) == SRT_OK && take_log() == "s" && live(OWNED_STREAM) == 2);
+    u = std::move(s);                                       // onto a full owner: its stream goes, once
+    CHECK((hipStream_t)s == nullptr && (hipStream_t)u == raw && take_log() == "x" && live(OWNED_STREAM) == 1 && C.streams == 1);
+    C.fail_at = 1;
+    Stream g;
+    CHECK(g.create(hipStreamNonBlocking) == SRT_ERR_HIP && (hipStream_t)g == nullptr && take_log() == "s" && live(OWNED_STREAM) == 1);
+    u.reset();
+    CHECK((hipStream_t)u == nullptr && take_log() == "x");
+    u.reset();
+    CHECK(take_log().empty());
+  }
+  CHECK(take_log().empty() && all_gone());
+}
+
+// What making one rank's slot of a group lane asks (pt_group.cpp), in its order.
+static int fill(LaneSlot* L) {
+  int st;
+  if ((st = L->stream.create(hipStreamNonBlocking)) || (st = L->event.create(hipEventDisableTiming)) || (st = L->tiles.ensure(64))) return st;
+  return SRT_OK;
+}
+
 // What making the refit tables of a tree asks of RefitTables, in its order: five tables uploaded, two box arrays allocated.
 static int fill(RefitTables* T, bool top) {
   const std::vector<uint32_t> prim(12, 1u), off = {0u, 1u, 3u};
@@ -180,6 +221,26 @@ static void structs_of_owners() {
       take_log();
     }
   }
+  {
+    LaneSlot L;
+    CHECK(fill(&L) == SRT_OK && take_log() == "sem" && live(OWNED_STREAM) == 1 && live(OWNED_EVENT) == 1 && live(OWNED_DEVICE) == 1);
+    const hipStream_t raw = L.stream;
+    LaneSlot M(std::move(L));                               // as a vector of slots moves them
+    CHECK((hipStream_t)L.stream == nullptr && !L.tiles && (hipStream_t)M.stream == raw && M.tiles.capacity() == 64 && take_log().empty());
+    M = LaneSlot();                                         // how the group gives a rank's slot back, under that rank's device
+    CHECK(take_log() == "xdf" && all_gone());
+  }
+  CHECK(take_log().empty() && all_gone());
+  for (int k = 1; k <= 3; k++) {
+    {
+      LaneSlot L;
+      C.fail_at = k;
+      CHECK(fill(&L) == SRT_ERR_HIP && C.fail_at == 0);
+      CHECK(live(OWNED_STREAM) + live(OWNED_EVENT) + live(OWNED_DEVICE) == (uint64_t)(k - 1) && C.streams + C.events + C.device_blocks == k - 1);
+    }
+    CHECK(all_gone());
+    take_log();
+  }
   for (int k = 1; k <= 7; k++) {
     {
       BvhWorkspace W;
@@ -199,6 +260,7 @@ int main() {
   device_buffer();
   pinned_buffer();
   events();
+  streams();
   structs_of_owners();
   CHECK(all_gone() && srt::g_fails > 0);
   std::printf("hip_owned: ok\n");

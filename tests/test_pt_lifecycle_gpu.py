@@ -1,8 +1,9 @@
-"""GPU: who owns what.  Every HIP allocation and event of the library lives in an owner (csrc/hip_owned.h) that counts itself, and
-srt_pt_live_resources reads the counts: a context that has been through every entry point that allocates, then destroyed with its
-skins and timelines, leaves the three counts where they were - nothing leaks, nothing is freed twice (a second free of a block
-would take a count below its start).  The same drive repeated on a live context holds the counts still, handles of an older commit
-stay destroyable, and the images along the way are the oracle's, bit for bit: moving ownership moved no data.  Smallest sizes
+"""GPU: who owns what.  Every HIP allocation, event and stream of the library lives in an owner (csrc/hip_owned.h) that counts
+itself, and srt_pt_live_resources reads the four counts: a context that has been through every entry point that allocates, then
+destroyed with its skins and timelines, leaves the four counts where they were - nothing leaks, nothing is freed twice (a second
+free of a block would take a count below its start).  The same drive repeated on a live context holds the counts still, handles of
+an older commit stay destroyable, and the images along the way are the oracle's, bit for bit: moving ownership moved no data.  The
+multi-device group (csrc/pt_group.cpp) gets the same three checks, and one of a create that fails half-way.  Smallest sizes
 throughout: 32x24 pixels, depth 3, 2 samples per epoch."""
 import os
 
@@ -173,7 +174,7 @@ def drive(srt, torch, pt, scene, name, use_bvh, read_timers):
 
 @pytest.mark.parametrize("name,use_bvh", SCENES, ids=IDS)
 def test_balance_and_pixels(srt, torch, live, goldens, name, use_bvh):
-    """1 and 4: create, drive every owner, destroy - the three counts are back where they started; and the images rendered on the
+    """1 and 4: create, drive every owner, destroy - the four counts are back where they started; and the images rendered on the
     way are the committed goldens.  The timing brackets of the last renders are left unread: destroy owns them too (all four slots
     of the streamed form's)."""
     scene = pt_scene(name)
@@ -182,7 +183,7 @@ def test_balance_and_pixels(srt, torch, live, goldens, name, use_bvh):
     commit(pt, scene, use_bvh)
     images, handles = drive(srt, torch, pt, scene, name, use_bvh, read_timers=False)
     during = live()
-    assert during[0] > before[0] and during[1] > before[1] and during[2] > before[2], (before, during)
+    assert during[0] > before[0] and during[1] > before[1] and during[2] > before[2] and during[3] > before[3], (before, during)
     for h in handles:
         h.close()
     pt.close()
@@ -230,4 +231,91 @@ def test_stale_handles(srt, torch, live):
     for h in handles:
         h.close()
     pt.close()
+    assert live() == before, (before, live())
+
+
+# ---- the multi-device group (srt_pt_create_multi): what the drop-in class and the benchmark render through -------------------------
+# cbox with BVHs.  32x24 is less than one 32x32 tile: ranks 1 and 2 of a three-rank group own nothing, the smallest case in which a
+# per-rank loop can go wrong.  72x40 has padding tiles, and going there replaces every lane buffer and accumulator.
+GROUP_SCENE, GROUP_KEY, W2, HT2 = "cbox", "cbox-bvh", 72, 40
+
+
+def commit_group(g, scene, w, h):
+    g.set_params(w, h, 1, DEPTH, True)
+    g.build_scene(scene)
+    g.set_camera(scene["camera"])
+
+
+@pytest.mark.parametrize("devices", [[0], [0, 0, 0]], ids=["1rank", "3ranks"])
+def test_group_balance(srt, live, goldens, devices):
+    """5: a group through every entry point of its own that allocates - lanes 0, 1 and the display lane, both kinds of timing pair
+    (read and left unread), the accumulators, the ray log, a change of image size, handle groups - then closed: the four counts
+    are back where they started, and the first epoch is the committed golden."""
+    scene = pt_scene(GROUP_SCENE)
+    before = live()
+    g = srt.PathtracerGroup(devices)
+    commit_group(g, scene, W, HT)
+    assert AC.bits_equal(g.render_epoch(SEED, 0, SPP), goldens[GROUP_KEY]), f"devices {devices}: the epoch differs from the golden"
+    g.render_epoch_lane(1, SEED, 0, SPP)
+    g.gather_time(True)
+    g.render_epoch(SEED, 0, SPP)
+    ms, epochs = g.gather_time(False)                       # (read: the pair goes to the spares)
+    assert epochs == 1 and ms >= 0.0
+    g.gather_time(True)
+    g.render_epoch(SEED, 0, SPP)                            # (left unread: destroy owns the pair)
+    # two launches in flight on lanes 0 and 1, folded in launch order; one epoch folded is that epoch
+    g.render_samples(0, SEED, 0, SPP)
+    g.render_samples(1, SEED, SPP, SPP)
+    g.wait_lane(0)
+    g.fold(0, SPP, 0, 2 * SPP, 0)
+    assert AC.bits_equal(g.accumulator_image(), goldens[GROUP_KEY]), f"devices {devices}: the folded epoch differs from the golden"
+    g.wait_lane(1)
+    g.fold(1, SPP, SPP, 2 * SPP, 0)
+    assert np.isfinite(g.accumulator_image()).all()
+    g.set_ray_log(16)
+    g.render_epoch(SEED, 0, SPP)
+    g.read_ray_log()
+    g.set_ray_log(0)
+    commit_group(g, scene, W2, HT2)
+    assert g.render_epoch(SEED, 0, SPP).shape == (HT2, W2, 3)
+    s = sphere_index(scene)
+    at = committed_T(scene, s)[12:15]
+    tl = g.create_timeline([s], [((np.array([0.0, 1.0], F), np.stack([at, at + F(0.01)])), None, None)])
+    tl.repose_refit(0.5)
+    sh = g.create_shading_timeline([0], [], False, [(np.array([0.0, 1.0], F), np.array([[0.2, 0.3, 0.4], [0.5, 0.5, 0.5]], F))] + [None] * 5)
+    sh.apply(0.5)
+    tl.close()
+    sh.close()
+    during = live()
+    assert all(d > b for d, b in zip(during, before)) and len(during) == 4, (before, during)
+    g.close()
+    assert live() == before, (before, during, live())
+
+
+def test_group_steady_state(srt, live):
+    """6: one two-rank group between two image sizes, three times: the lane buffers and accumulators a new size replaces are freed, so
+    the second and the third round end on the same counts."""
+    scene = pt_scene(GROUP_SCENE)
+    before = live()
+    g = srt.PathtracerGroup([0, 0])
+    commit_group(g, scene, W, HT)
+    after = []
+    for _ in range(3):
+        for w, h in ((W, HT), (W2, HT2)):
+            g.set_params(w, h, 1, DEPTH, True)
+            g.reset_accumulator()
+            g.render_epoch(SEED, 0, SPP)
+        after.append(live())
+    assert after[1] == after[2], after
+    g.close()
+    assert live() == before, (before, after, live())
+
+
+def test_group_create_fails_half_way(srt, live):
+    """7: rank 1's device does not exist (srt_pt_create refuses it before it touches a device): rank 0's context, events and stream go
+    away with the partly built group."""
+    before = live()
+    with pytest.raises(srt.SrtError) as e:
+        srt.PathtracerGroup([0, 10_000])
+    assert e.value.status == -1                             # SRT_ERR_INVALID
     assert live() == before, (before, live())
