@@ -876,6 +876,34 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
  * not be normalised (the particle step passes velocities): times, distances and dist_bounds follow lib/ray.h and
  * student/bvh.inl exactly as the reference scales them. */
 int srt_pt_hit(srt_pt* pt, const float* origins, const float* dirs, const float* bounds, size_t n, float* out9);
+/* The same for rays that lie in device memory, results into device memory, ENQUEUE-ONLY under the contract written at
+ * srt_pt_repose_refit_device: the host validates first, then the call only enqueues on `stream` (NULL = the HIP default stream) and
+ * returns - no synchronisation, nothing copied to the host.  d_origins / d_dirs: 3 floats per ray; d_bounds: 2 per ray as
+ * srt_pt_hit's bounds, NULL = {0, +inf} for every ray.  Each output may be NULL, not all three:
+ *   d_out9  srt_pt_hit's record bit for bit: {hit, distance, position[3], normal[3], material}, nine zeros on a miss;
+ *   d_ids   two words per ray: the 0-based insertion index of the object hit, then the triangle's place in that object's own
+ *           BVH<Triangle> primitive order (the index into srt_pt_dump_bvh's `order` of the object; the index order in a scene
+ *           committed without BVHs; an instance reports its OWN insertion index and the shared mesh's place).  A sphere gives
+ *           0xFFFFFFFF as the second word, a miss 0xFFFFFFFF for both;
+ *   d_hit   one byte per ray: 1 when a closest hit exists within the bounds, else 0 - the shadow-ray question (it is the closest-hit
+ *           walk all the same: there is no early exit).  Asked alone, no surface is computed and one byte per ray is written.
+ * It reads the LIVE device scene - every enqueue-only update enqueued on `stream` before it is seen (srt_pt_repose_refit_device,
+ * srt_pt_set_active_device, the skin poses, srt_pt_shading_timeline_apply; other streams: the caller's events) - and does not
+ * settle the host's record.  It ignores srt_pt_cancel and leaves srt_pt_ray_count and the timing brackets alone.
+ *   Routing: a scene srt_pt_set_kernel(6) would render (a BVH<Object> on top, hits that pack into one word, a traversal stack that
+ * fits) goes through the persistent ray-cast kernel of the streamed forms: pack (32-byte requests), cast, resolve - 44 B of scratch
+ * per ray, one set per stream, grown on demand (growth waits, once); a call of more than 4 Mi rays is cut into chunks enqueued back
+ * to back (SRT_HIT_CHUNK overrides the chunk: a diagnostic).  Every other scene and kernel modes 1 and 4 take srt_pt_hit's
+ * per-lane walk straight from the caller's arrays; mode 5 the flattened walk (1..31 objects, refused otherwise).  The automatic
+ * mode follows the measurement: it takes the ray-cast kernel for calls of at least 2^19 rays - the crossover for
+ * incoherent rays; a persistent launch has a fixed cost - on the scenes whose render it streams as well (a mesh with a real
+ * BVH<Triangle>, or more than 16 objects), and the per-lane walk otherwise: on a Cornell box of single-leaf meshes that walk is
+ * ahead at every size.  Modes 2, 3, 6 and 7 take the ray-cast kernel wherever it applies.  The results are identical on every route.
+ *   SRT_ERR_INVALID: NULL pt, NULL origins or directions with n > 0, no output at all.  SRT_ERR_STATE: no committed scene.
+ * SRT_ERR_UNSUPPORTED: n > 0x7fffffff; a host-only context.  n == 0 enqueues nothing.  A ray with a NaN component or an all-zero
+ * direction terminates with an unspecified result (the caveat of srt_pt_set_active). */
+int srt_pt_hit_device(srt_pt* pt, void* stream, const float* d_origins, const float* d_dirs, const float* d_bounds, size_t n,
+                      float* d_out9, uint32_t* d_ids, uint8_t* d_hit);
 /* Scene_Particles::Particle::update (student/particles.cpp:5-59) for n particles against the committed scene - the loop body of
  * Scene_Particles::step2 (scene/particles.cpp:134-138), the second caller of Object::hit besides the path tracer (the scene
  * it collides with is Simulate::build_scene's BVH<Object>, gui/simulate.cpp:69-99: commit the same objects).  pos / vel: 3

@@ -54,6 +54,10 @@ int srt_pt_stream_counters(srt_pt* pt, uint64_t out[4], int reset);
  * srt_pt_set_normal_colors is on: the first-hit kernel of the normal-colors view, whatever the scene and the kernel mode. */
 int srt_pt_kernel_form(srt_pt* pt, int* form);
 
+/* Which route srt_pt_hit_device took: the calls since creation that went through {the ray-cast kernel, the nested per-lane walk,
+ * the flattened per-lane walk}.  Lets a test state that the cast path really ran.  Works on a host-only context (all zero). */
+int srt_pt_hit_device_paths(srt_pt* pt, uint64_t out[3]);
+
 /* Traversal counters of the LAST srt_pt_trace_samples call (an instrumented launch):
  * {rays, box_tests, objects_entered, tri_tests, sphere_tests, tlas_nodes, blas_nodes, light_tri_tests}. */
 int srt_pt_counters(srt_pt* pt, uint64_t out[8]);

@@ -143,6 +143,8 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_kernel_form.argtypes = [c_void_p, POINTER(c_int)]
     lib.srt_pt_trace_samples.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
     lib.srt_pt_hit.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_hit_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]
+    lib.srt_pt_hit_device_paths.argtypes = [c_void_p, c_void_p]
     lib.srt_pt_particles_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p]
     lib.srt_pt_particles_step_device.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p]
     lib.srt_pt_emitter_create.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_void_p]
@@ -1423,6 +1425,42 @@ class Pathtracer:
         out = np.zeros((len(org), 9), np.float32)
         self._check(self._lib, self._lib.srt_pt_hit(self._ctx, _p(org), _p(dirs), _p(bounds), len(org), _p(out)))
         return out
+
+    def hit_device(self, d_org_ptr: int, d_dirs_ptr: int, d_bounds_ptr: int, n: int, d_out9_ptr: int = 0, d_ids_ptr: int = 0, d_hit_ptr: int = 0,
+                   stream: int = 0) -> None:
+        """srt_pt_hit_device: scene.hit for n rays in device memory ((n, 3), (n, 3) float32 and (n, 2) float32 or 0 for {0, inf}), only
+        enqueued on `stream`: no wait, nothing comes back to the host, the live device scene is read.  Outputs (each optional, not all
+        three 0): (n, 9) float32 records as hit() returns them, (n, 2) uint32 {object insertion index, triangle's place in the mesh's
+        primitive order}, (n,) uint8 hit flags."""
+        self._check(self._lib, self._lib.srt_pt_hit_device(self._ctx, c_void_p(stream), c_void_p(d_org_ptr), c_void_p(d_dirs_ptr), c_void_p(d_bounds_ptr),
+                                                           int(n), c_void_p(d_out9_ptr), c_void_p(d_ids_ptr), c_void_p(d_hit_ptr)))
+
+    def hit_tensors(self, org, dirs, bounds=None, ids: bool = False, flags: bool = False):
+        """hit_device for float32 CUDA tensors on the context's device ((n, 3), (n, 3), optionally (n, 2)), enqueued on torch's
+        current stream.  Returns the (n, 9) records, then the (n, 2) int32 ids and the (n,) uint8 flags where asked for (a tuple
+        then) - without synchronising: they are ordered behind the query on that stream."""
+        import torch
+
+        n = int(org.shape[0])
+        for name, t, cols in (("org", org, 3), ("dirs", dirs, 3), ("bounds", bounds, 2)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, cols) or not t.is_contiguous() or t.device != org.device:
+                raise ValueError(f"hit_tensors: {name} must be a contiguous float32 CUDA tensor of shape ({n}, {cols}) on {org.device}")
+        with torch.cuda.device(org.device):
+            out = torch.empty((n, 9), dtype=torch.float32, device=org.device)
+            d_ids = torch.empty((n, 2), dtype=torch.int32, device=org.device) if ids else None   # (the words of the uint32 pairs; -1: none)
+            d_flags = torch.empty((n,), dtype=torch.uint8, device=org.device) if flags else None
+            self.hit_device(org.data_ptr(), dirs.data_ptr(), bounds.data_ptr() if bounds is not None else 0, n, out.data_ptr(),
+                            d_ids.data_ptr() if ids else 0, d_flags.data_ptr() if flags else 0, stream=torch.cuda.current_stream().cuda_stream)
+        res = (out,) + ((d_ids,) if ids else ()) + ((d_flags,) if flags else ())
+        return res[0] if len(res) == 1 else res
+
+    def hit_device_paths(self):
+        """srt_pt_hit_device_paths: hit_device calls so far through (the ray-cast kernel, the nested per-lane walk, the flattened one)."""
+        out = np.zeros(3, np.uint64)
+        self._check(self._lib, self._lib.srt_pt_hit_device_paths(self._ctx, _p(out)))
+        return tuple(int(v) for v in out)
 
     def particles_step(self, pos, vel, age, dt: float, radius: float):
         """Scene_Particles::Particle::update for every particle (scene/particles.cpp:134-138): returns (pos, vel, age, alive)."""

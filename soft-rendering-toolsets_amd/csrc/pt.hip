@@ -441,6 +441,51 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
   return launch_epoch(pt, s, B, sample_base, samples, d_tiles_out, stage, launch);
 }
 
+// pt_cast_kernel's launch shape for trees that need `depth` frames per lane: as many of them in LDS as SRT_CAST_LDS_FRAMES allows, and
+// the block size that puts the most waves on a CU.  What the render (render_epoch_stream) and the queries (query_cast_applies) share.
+int derive_cast_shape(srt_pt* pt, CastKernel ckern, bool walk, uint32_t depth, srt_pt::CastShape* out) {
+  srt_pt::CastShape S;
+  S.kern = (const void*)ckern;
+  int cus = 0;
+  SRT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pt->device));
+  // 13 frames of 12 bytes x 64 lanes: 16 waves per CU fit into the 160 KB (what the general build's ~100 VGPRs allow); the
+  // walk-only build needs 85 VGPRs - five waves per SIMD - and takes 10 frames for 20 waves per CU (cast 138 -> 132 ms)
+  const uint32_t lds_max = env_u32("SRT_CAST_LDS_FRAMES", walk ? 10u : 13u);
+  const uint32_t lds_frames = depth < lds_max ? depth : (lds_max < 1u ? 1u : lds_max);
+  const size_t per_wave = (size_t)lds_frames * 3u * 64u * sizeof(uint32_t);
+  int best_waves = 0;
+  for (int w : {4, 2, 1}) {
+    const size_t lds = per_wave * (size_t)w;
+    if (lds > 160u * 1024u) continue;
+    if (hipFuncSetAttribute((const void*)ckern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) continue;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)ckern, 64 * w, lds) != hipSuccess || per_cu < 1) continue;
+    if (per_cu * w > best_waves) { best_waves = per_cu * w; S.threads = 64 * w; S.blocks = per_cu * cus; S.lds = lds; }
+  }
+  if (best_waves == 0) return srt::fail(SRT_ERR_UNSUPPORTED, "the ray-cast kernel's traversal stack (%u frames per lane) does not fit into LDS", depth);
+  S.depth = depth; S.lds_frames = lds_frames;
+  SRT_HIP(hipFuncSetAttribute((const void*)ckern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds));
+  if (getenv("SRT_DEBUG")) fprintf(stderr, "[srt] pt_cast_kernel: %d blocks x %d threads, %zu B LDS per block (%u of %u frames per lane), %d waves/CU\n",
+                                   S.blocks, S.threads, S.lds, lds_frames, depth, best_waves);
+  *out = S;
+  return SRT_OK;
+}
+// The phase scheduler's thresholds (pt_stream.h) with their SRT_CAST_* overrides.
+void cast_scheduler(CastParams& C, bool walk) {
+  C.fetch_min = env_u32("SRT_CAST_FETCH", 16u);
+  C.interior_min = env_u32("SRT_CAST_INTERIOR", 16u);
+  if (C.fetch_min < 1u) C.fetch_min = 1u;
+  C.leaf_min = env_u32("SRT_CAST_LEAF", 12u);
+  C.object_min = env_u32("SRT_CAST_OBJECT", walk ? 16u : 24u);
+  C.own_share = env_u32("SRT_CAST_OWN", 128u);
+  C.grab = env_u32("SRT_CAST_GRAB", 32u);
+  if (C.grab < 1u) C.grab = 1u;
+  if (C.own_share > 256u) C.own_share = 256u;
+  C.pops = env_u32("SRT_CAST_POPS", 2u);
+  if (C.leaf_min < 1u) C.leaf_min = 1u;
+  if (C.object_min < 1u) C.object_min = 1u;
+}
+
 // One epoch in the streamed form (pt_stream.h, K.trav 3 / 4): per launch of <= 64 samples per pixel a fixed number of generations, each
 // one logic kernel (pt_wave_kernel<.., TRAV = 3, ..>: consume hits, shade, refill, emit rays) and one ray-cast kernel;
 // then the ordered per-pixel reduction.
@@ -456,35 +501,14 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
   // the cast kernel's launch shape: frames per lane from the scene's tree depths, as many waves per CU as the LDS holds
   const uint32_t depth = (trav == 4 ? 0u : F.max_tlas_depth) + F.max_blas_depth + 1u;
   const CastKernel ckern = cast_kernel(false, trav == 4), ckern_stats = cast_kernel(true, trav == 4);
-  if (pt->cast_blocks == 0 || pt->cast_depth != depth || pt->cast_kern != (const void*)ckern) {
-    pt->cast_kern = (const void*)ckern;
-    int cus = 0;
-    SRT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pt->device));
-    // 13 frames of 12 bytes x 64 lanes: 16 waves per CU fit into the 160 KB (what the general build's ~100 VGPRs allow); the
-    // walk-only build needs 85 VGPRs - five waves per SIMD - and takes 10 frames for 20 waves per CU (cast 138 -> 132 ms)
-    const uint32_t lds_max = env_u32("SRT_CAST_LDS_FRAMES", trav == 4 ? 10u : 13u);
-    const uint32_t lds_frames = depth < lds_max ? depth : (lds_max < 1u ? 1u : lds_max);
-    const size_t per_wave = (size_t)lds_frames * 3u * 64u * sizeof(uint32_t);
-    int best_waves = 0;
-    pt->cast_blocks = 0;
-    for (int w : {4, 2, 1}) {
-      const size_t lds = per_wave * (size_t)w;
-      if (lds > 160u * 1024u) continue;
-      if (hipFuncSetAttribute((const void*)ckern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) continue;
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)ckern, 64 * w, lds) != hipSuccess || per_cu < 1) continue;
-      if (per_cu * w > best_waves) { best_waves = per_cu * w; pt->cast_threads = 64 * w; pt->cast_blocks = per_cu * cus; pt->cast_lds = lds; }
-    }
-    if (best_waves == 0) return srt::fail(SRT_ERR_UNSUPPORTED, "the ray-cast kernel's traversal stack (%u frames per lane) does not fit into LDS", depth);
-    pt->cast_depth = depth; pt->cast_lds_frames = lds_frames;
-    SRT_HIP(hipFuncSetAttribute((const void*)ckern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt->cast_lds));
+  srt_pt::CastShape& shape = pt->cast;
+  if (shape.blocks == 0 || shape.depth != depth || shape.kern != (const void*)ckern) {
+    if ((st = derive_cast_shape(pt, ckern, trav == 4, depth, &shape)) != SRT_OK) return st;
     if (getenv("SRT_CAST_STATS") && !pt->d_cast_stats) {
       if ((st = pt->d_cast_stats.ensure(CS_COUNT))) return st;
       SRT_HIP(hipMemsetAsync(pt->d_cast_stats, 0, CS_COUNT * sizeof(unsigned long long), s));
     }
-    if (pt->d_cast_stats) SRT_HIP(hipFuncSetAttribute((const void*)ckern_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt->cast_lds));
-    if (getenv("SRT_DEBUG")) fprintf(stderr, "[srt] pt_cast_kernel: %d blocks x %d threads, %zu B LDS per block (%u of %u frames per lane), %d waves/CU\n",
-                                     pt->cast_blocks, pt->cast_threads, pt->cast_lds, lds_frames, depth, best_waves);
+    if (pt->d_cast_stats) SRT_HIP(hipFuncSetAttribute((const void*)ckern_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
   }
   const CastKernel cast = pt->d_cast_stats ? ckern_stats : ckern;
   // the logic kernel: 1024-thread blocks; the streamed sweeps keep their per-wave slots in LDS (16 waves)
@@ -504,7 +528,7 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
   if ((st = sample_buffers(pt, s, px, &Bp)) != SRT_OK) return st;
   srt_pt::EpochBuffers& B = *Bp;
   if (!B.d_sc && (st = B.d_sc.ensure(1))) return st;
-  const size_t spill_words = (size_t)(depth - pt->cast_lds_frames) * 3u * (size_t)pt->cast_blocks * (size_t)pt->cast_threads;
+  const size_t spill_words = (size_t)(depth - shape.lds_frames) * 3u * (size_t)shape.blocks * (size_t)shape.threads;
   if (spill_words && (st = B.d_cast_spill.ensure(spill_words)) != SRT_OK) return st;
   const uint32_t shadow_batches = (uint32_t)((F.delta_lights.size() + 2) / 3);
   const DScene DS = device_scene(pt, &B);
@@ -561,21 +585,10 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
     gens = ((uint64_t)P.total_units * M + nlanes - 1) / nlanes + M + 2;
     C = CastParams{};
     C.ray_o = B.d_ray_o; C.ray_d = B.d_ray_o + 1; C.ray_id = B.d_ray_id; C.hits = B.d_hits; C.nlanes = nlanes;
-    C.depth = depth; C.lds_frames = pt->cast_lds_frames; C.spill = B.d_cast_spill; C.obj_shift = P.obj_shift; C.sc = B.d_sc; C.total_units = P.total_units;
+    C.depth = depth; C.lds_frames = shape.lds_frames; C.spill = B.d_cast_spill; C.obj_shift = P.obj_shift; C.sc = B.d_sc; C.total_units = P.total_units;
     C.walk_nr = trav == 4 ? burst : 0u;
     for (size_t i = 0; i < F.lazy_objects.size() && i < 4; i++) C.lazy_obj[i] = F.lazy_objects[i];
-    C.fetch_min = env_u32("SRT_CAST_FETCH", 16u);
-    C.interior_min = env_u32("SRT_CAST_INTERIOR", 16u);
-    if (C.fetch_min < 1u) C.fetch_min = 1u;
-    C.leaf_min = env_u32("SRT_CAST_LEAF", 12u);
-    C.object_min = env_u32("SRT_CAST_OBJECT", trav == 4 ? 16u : 24u);
-    C.own_share = env_u32("SRT_CAST_OWN", 128u);
-    C.grab = env_u32("SRT_CAST_GRAB", 32u);
-    if (C.grab < 1u) C.grab = 1u;
-    if (C.own_share > 256u) C.own_share = 256u;
-    C.pops = env_u32("SRT_CAST_POPS", 2u);
-    if (C.leaf_min < 1u) C.leaf_min = 1u;
-    if (C.object_min < 1u) C.object_min = 1u;
+    cast_scheduler(C, trav == 4);
     C.stats = pt->d_cast_stats;
     C.tri_packed = pt->d_tri_packed;
     C.dev_cancel = B.d_cancel;
@@ -600,7 +613,7 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
       pt_compact_kernel<<<cgrid, dim3(1024), 0, s>>>(B.d_state + (size_t)SW_EMIT * nlanes, nlanes, nslots, B.d_sc, (uint32_t)g, B.d_ray_id, pt->d_totals + C_COUNT + 2, pt->h_cancel.device(), B.d_cancel, B.d_alive_list);
       if ((st = time_end(s, timed[1], on)) != SRT_OK || (st = time_begin(pt, s, timed[2], on)) != SRT_OK) return st;
       C.nrays = &B.d_sc.get()->nrays[g & 1]; C.head = &B.d_sc.get()->cast_head[g & 1]; C.gen = (uint32_t)g;
-      cast<<<dim3(pt->cast_blocks), dim3(pt->cast_threads), pt->cast_lds, s>>>(DS, C);
+      cast<<<dim3(shape.blocks), dim3(shape.threads), shape.lds, s>>>(DS, C);
       if ((st = time_end(s, timed[2], on)) != SRT_OK) return st;
     }
     if (pt->stream_timing) pt->stream_generations += gens;
@@ -689,6 +702,55 @@ void report_cast_stats(srt_pt* pt) {
 }
 
 int pt_check_fault(srt_pt* pt, const char* what) { return pt ? check_stream_fault(pt, what) : SRT_OK; }
+
+// ---- srt_pt_hit_device's cast path (pt_hit_device.hip): this unit alone may name pt_cast_kernel ----
+// The scenes form 3 renders whose rays start in a BVH<Object>, with a traversal stack that fits (the shape is derived here, once per depth).
+// `automatic`: only the scenes whose render the automatic mode streams as well (wave_trav: a mesh with a real BVH<Triangle>, or more
+// objects than the sweeps take) - on the others the per-lane walk is ahead at every size.
+bool query_cast_applies(srt_pt* pt, bool automatic) {
+  const FlatScene& F = pt->built.flat;
+  if (!F.use_bvh || !stream_fits(F)) return false;
+  if (automatic && F.blas_recs.empty() && F.objects.size() <= kWaveMaxObjects) return false;
+  const uint32_t depth = F.max_tlas_depth + F.max_blas_depth + 1u;
+  const CastKernel ckern = cast_kernel(false, false);
+  srt_pt::CastShape& shape = pt->query_cast;
+  if (shape.blocks != 0 && shape.depth == depth && shape.kern == (const void*)ckern) return true;
+  return derive_cast_shape(pt, ckern, false, depth, &shape) == SRT_OK;
+}
+
+// Scratch of stream `s` for chunks of up to `cap` rays, its counters zeroed on `s`.  *nrays / *head: the words the pack kernel presets.
+int query_cast_prepare(srt_pt* pt, hipStream_t s, size_t cap, srt_pt::QueryBuffers** out, uint32_t** nrays, uint32_t** head, uint32_t* obj_shift) {
+  srt_pt::QueryBuffers& Q = pt->query_buffers[s];
+  const srt_pt::CastShape& shape = pt->query_cast;
+  int st;
+  if ((st = Q.d_req.ensure(2 * cap)) || (st = Q.d_ray_id.ensure(cap)) || (st = Q.d_hits.ensure(cap)) || (st = Q.d_sc.ensure(1))) return st;
+  if (!Q.d_zero) {
+    if ((st = Q.d_zero.ensure(1))) return st;
+    SRT_HIP(hipMemsetAsync(Q.d_zero, 0, sizeof(uint32_t), s));   // (on `s`: see stream_buffers)
+  }
+  const size_t spill_words = (size_t)(shape.depth - shape.lds_frames) * 3u * (size_t)shape.blocks * (size_t)shape.threads;
+  if (spill_words && (st = Q.d_spill.ensure(spill_words)) != SRT_OK) return st;
+  SRT_HIP(hipMemsetAsync(Q.d_sc, 0, sizeof(StreamCounters), s));
+  *out = &Q;
+  *nrays = &Q.d_sc.get()->nrays[0]; *head = &Q.d_sc.get()->cast_head[0];
+  *obj_shift = stream_obj_shift(pt->built.flat);
+  return SRT_OK;
+}
+
+// scene.hit for the chunk packed into Q: generation 0 of a launch of its own - world rays, no units, never cancelled.
+int query_cast_launch(srt_pt* pt, hipStream_t s, srt_pt::QueryBuffers& Q) {
+  const srt_pt::CastShape& shape = pt->query_cast;
+  CastParams C{};
+  C.ray_o = Q.d_req; C.ray_d = Q.d_req + 1; C.ray_id = Q.d_ray_id; C.hits = Q.d_hits; C.nlanes = 0; C.walk_nr = 0;
+  C.sc = Q.d_sc; C.total_units = 0; C.gen = 0;
+  C.nrays = &Q.d_sc.get()->nrays[0]; C.head = &Q.d_sc.get()->cast_head[0];
+  C.depth = shape.depth; C.lds_frames = shape.lds_frames; C.spill = Q.d_spill; C.obj_shift = stream_obj_shift(pt->built.flat);
+  cast_scheduler(C, false);
+  C.stats = nullptr; C.tri_packed = pt->d_tri_packed; C.dev_cancel = Q.d_zero;
+  cast_kernel(false, false)<<<dim3(shape.blocks), dim3(shape.threads), shape.lds, s>>>(device_scene(pt), C);
+  SRT_HIP(hipGetLastError());
+  return SRT_OK;
+}
 }  // namespace srt
 
 namespace {

@@ -259,7 +259,7 @@ int srt_pt_scene_commit(srt_pt* pt, int use_bvh) {
   }
   pt->committed = true;
   pt->scene_generation++;
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->drop_cast_shapes();
   return SRT_OK;
 }
 

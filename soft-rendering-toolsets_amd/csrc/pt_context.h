@@ -6,6 +6,7 @@
 //                   shading timelines), pt_update_emitter.cpp (particle emitters) and pt_update.cpp (what they share - pt_update.h -
 //                   and settle())
 //   pt_query.hip    per-lane kernels on the committed scene outside a render (samples, hits, particles) and the dumps
+//   pt_hit_device.hip  srt_pt_hit_device: rays from device memory through pt.hip's ray-cast kernel (pack, resolve) or the per-lane walk
 //   pt_image.hip    untile, accumulate, tonemap
 //   pt_probe.hip    the test-only math probes of srt_pt_debug.h
 // Only pt.hip may include pt_wave.h / pt_stream.h: they define non-template __global__ functions, which a second includer would
@@ -77,9 +78,27 @@ struct srt_pt {
     uint32_t last_samples = 0, last_npix = 0;                         // what d_samples holds: samples per pixel and pixel slots of the last launch
   };
   std::map<hipStream_t, EpochBuffers> epoch_buffers;
+  // Scratch of srt_pt_hit_device's cast path, one set per stream the caller queries on (44 B per ray of a chunk + the spill columns):
+  // the chunk's requests as the cast kernel reads them, the identity list, the hit words; and what the launch keeps to itself - a
+  // StreamCounters block, a cancel word that stays zero (a query ignores srt_pt_cancel) and the frames beyond those in LDS.
+  struct QueryBuffers {
+    srt::DeviceBuffer<float4> d_req;                         // {origin, b0} {dir, b1} per ray
+    srt::DeviceBuffer<uint32_t> d_ray_id;
+    srt::DeviceBuffer<uint2> d_hits;
+    srt::DeviceBuffer<srt::StreamCounters> d_sc;
+    srt::DeviceBuffer<uint32_t> d_zero;
+    srt::DeviceBuffer<uint32_t> d_spill;
+  };
+  std::map<hipStream_t, QueryBuffers> query_buffers;
+  uint64_t hit_device_paths[3] = {0, 0, 0};                  // srt_pt_hit_device_paths: calls through {the cast kernel, the nested walk, the flattened walk}
   int wave_blocks = 0; size_t wave_lds = 0; int wave_mode = -1; const void* wave_kern = nullptr;
-  const void* cast_kern = nullptr; uint32_t cast_lds_frames = 0;                                 // traversal frames per lane kept in LDS (the deeper ones: d_cast_spill)
-  int cast_blocks = 0, cast_threads = 0; size_t cast_lds = 0; uint32_t cast_depth = 0;   // pt_cast_kernel's launch shape (0: not derived yet)
+  // pt_cast_kernel's launch shape (blocks == 0: not derived yet).  The render's and the queries' are cached apart: on a scene of the
+  // streamed sweeps the render launches the walk-only build and a query the general one.
+  struct CastShape {
+    const void* kern = nullptr; uint32_t lds_frames = 0;     // traversal frames per lane kept in LDS (the deeper ones: the spill columns)
+    int blocks = 0, threads = 0; size_t lds = 0; uint32_t depth = 0;
+  } cast, query_cast;
+  void drop_cast_shapes() { cast.blocks = 0; query_cast.blocks = 0; }   // the ray-cast kernel's stack depth follows the scene
   int bvh_builder = 1; uint32_t bvh_device_min = 16384;         // srt_pt_set_bvh_builder: device build for sets of >= this many primitives
   uint32_t stream_slots = 0;                                    // srt_pt_set_stream_slots (0: default)
   srt::DeviceBuffer<unsigned long long> d_cast_stats;           // SRT_CAST_STATS=1: the STATS build of pt_cast_kernel adds into these
@@ -227,6 +246,14 @@ DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B = nullptr);
 bool flat_walk_fits(const FlatScene& F);
 // SRT_CAST_STATS=1: the ray-cast kernel's sums on stderr, for srt_pt_destroy (pt.hip)
 void report_cast_stats(srt_pt* pt);
+// srt_pt_hit_device's cast path (pt.hip; the caller is pt_hit_device.hip): does pt_cast_kernel take the committed scene's world rays -
+// what srt_pt_set_kernel(6) renders, a BVH<Object> on top, the traversal stack fits (the queries' launch shape is derived on the way;
+// automatic: and the automatic mode streams the scene's render too);
+// stream `s`'s scratch for chunks of up to `cap` rays with its counters zeroed on `s` (*nrays, *head: the words the pack kernel presets,
+// *obj_shift: how a hit word packs its object); and the launch over the chunk that was packed.  The last two only enqueue, but for growth.
+bool query_cast_applies(srt_pt* pt, bool automatic);
+int query_cast_prepare(srt_pt* pt, hipStream_t s, size_t cap, srt_pt::QueryBuffers** out, uint32_t** nrays, uint32_t** head, uint32_t* obj_shift);
+int query_cast_launch(srt_pt* pt, hipStream_t s, srt_pt::QueryBuffers& Q);
 // (everything below: pt_update.cpp)
 // settle(): the host's record catches up with the device after srt_pt_repose_refit_device calls - every entry point that is not itself
 // enqueue-only calls it first (need_committed: and refuses, with not_committed's text, a scene that is not committed); discard_pending():

@@ -24,6 +24,7 @@
 #define SRT_PT_STREAM_H
 
 #include "pt_flat.h"
+#include "pt_queue.h"
 
 namespace srt {
 
@@ -53,12 +54,7 @@ enum {
 // The first `k` frames of a lane live in LDS, deeper ones in a per-lane column of global memory (`g`, frame i word j at
 // g[((i - k) * 3 + j) * gstride]): with the childless-frame rule of flat_interior a walk rarely gets that deep, and LDS sized
 // for the tree's full depth is what limited the kernel's waves per CU.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-// The streamed forms' queue traffic - rays, list entries, hits, saved path state - passes through memory once per generation:
-// non-temporal accesses, so that it does not push the scene out of L2.
-SRT_DEV void nt_store_ray(float4* plane, size_t i, float x, float y, float z, float w) { __builtin_nontemporal_store(f32x4{x, y, z, w}, reinterpret_cast<f32x4*>(plane) + i); }
-SRT_DEV uint2 nt_load_hit(const uint2* hits, size_t i) { const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(hits) + i); return make_uint2(v.x, v.y); }
+// (f32x4, u32x2_t and the queue's non-temporal accesses nt_store_ray / nt_load_hit: pt_queue.h)
 typedef __attribute__((address_space(3))) uint32_t lds_u32;   // (an explicit LDS pointer: ds_read / ds_write, never FLAT)
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 struct LdsStack {

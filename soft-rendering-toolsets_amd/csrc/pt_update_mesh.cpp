@@ -143,7 +143,7 @@ int update_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Me
   apply_mesh_update(&pt->built, &U);
   if (on_device) drop_update_tables(pt, object);          // they describe the tree and the boxes that were just replaced
   if (use_bvh) pt->blas_builds++;
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->drop_cast_shapes();
   if (!on_device) return SRT_OK;
   pt->bytes_uploaded += pt->mesh.idx_uncounted;
   pt->mesh.idx_uncounted = 0;
@@ -270,7 +270,7 @@ int refit_mesh(srt_pt* pt, const char* what, hipStream_t s, uint32_t object, Mes
   const size_t old_tlas = pt->built.flat.tlas_nodes;
   apply_mesh_refit(&pt->built, &R);
   pt->mesh.refits++;
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->drop_cast_shapes();
   if (!on_device) return SRT_OK;
   pt->pose.drop();                                        // the object-space boxes changed
   pt->top.drop_tables();                                  // the BVH<Object> was rebuilt

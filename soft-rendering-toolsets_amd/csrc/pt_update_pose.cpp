@@ -271,7 +271,7 @@ int srt_pt_repose(srt_pt* pt, const uint32_t* objects, const float* trans, uint3
   const size_t old_tlas_nodes = pt->built.flat.tlas_nodes;
   if (on_device) SRT_HIP(quiesce(pt));
   apply_repose(&pt->built, &top);
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->drop_cast_shapes();
   if (!on_device) return SRT_OK;
   pt->pose.drop();                                        // srt_pt_repose_device's tables mirror the poses that were just replaced
   pt->top.drop_tables();                                  // srt_pt_repose_refit_device's describe the tree that was just replaced
@@ -378,7 +378,7 @@ int srt_pt_repose_device(srt_pt* pt, void* stream, const uint32_t* objects, cons
   if (hipStreamSynchronize(s) != hipSuccess || quiesce(pt) != hipSuccess) return refuse(srt::fail(SRT_ERR_HIP, "%s: synchronisation failed", what));
   apply_repose(&pt->built, &top);
   pt->top.drop_tables();                                  // srt_pt_repose_refit_device's describe the tree that was just replaced
-  pt->cast_blocks = 0;                                    // the ray-cast kernel's stack depth follows the scene
+  pt->drop_cast_shapes();
   pt->bytes_uploaded += staged_bytes;
   auto write = [&]() -> int {
     int w;
