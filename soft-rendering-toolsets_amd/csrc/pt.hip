@@ -394,6 +394,7 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
     SRT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pt->device));
     if (per_cu < 1) return srt::fail(SRT_ERR_UNSUPPORTED, "wave kernel does not fit on a CU (LDS %zu bytes)", lds);
     pt->wave_blocks = per_cu * cus;
+    pt->wave_cus = cus;
     pt->wave_lds = lds;
     if (getenv("SRT_DEBUG")) fprintf(stderr, "[srt] pt_wave_kernel: %d blocks/CU x %d CUs, %zu B LDS per block\n", per_cu, cus, lds);
   }
@@ -407,6 +408,14 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
     if ((st = B.d_queue.ensure(1 + ST_COUNT_))) return st;
     SRT_HIP(hipMemsetAsync(B.d_queue, 0, (1 + ST_COUNT_) * sizeof(unsigned long long), s));   // (on `s`: see stream_buffers)
   }
+  // the launch's camera table (pt_camera_kernel): sized like d_samples, for the most samples a launch takes
+  const bool cam_table = camera_table(K.stamp, trav, K.two ? 2 : 3);
+  const size_t cam_n = (size_t)px * samples_per_launch(px);
+  if (cam_table && (st = B.d_camera.ensure(cam_n * 5 + 4)) != SRT_OK) return st;
+  uint32_t* const cam_base = B.d_camera;                 // planes at fixed places of the stream's buffer, however many samples a launch has
+  uint2* const cam_rng = reinterpret_cast<uint2*>(cam_base);
+  float* const cam_dir = reinterpret_cast<float*>(cam_base + 2 * cam_n);
+  float* const cam_org = reinterpret_cast<float*>(cam_base + 5 * cam_n);
   const DScene DS = device_scene(pt, &B);
   WaveParams P{};
   auto stage = [&](uint32_t first_sample, uint32_t n) -> int {
@@ -431,10 +440,21 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
     P.queue_head = B.d_queue; P.ray_counter = pt->d_totals + C_COUNT; P.elided_counter = pt->d_totals + C_COUNT + 1; P.stamps = B.d_queue + 1;
     P.host_cancel = pt->h_cancel.device(); P.dev_cancel = B.d_cancel;
     P.watch = (pt->wave_blocks >= 2 && !getenv("SRT_NO_CANCEL_WATCH")) ? 1u : 0u;   // the last workgroup watches for srt_pt_cancel (pt_wave.h; the variable: A/B runs)
+    if (cam_table) { P.cam_rng = cam_rng; P.cam_dir = cam_dir; P.cam_org = cam_org; }
     SRT_HIP(hipMemsetAsync(B.d_queue, 0, sizeof(unsigned long long), s));
     return SRT_OK;
   };
-  auto launch = [&](uint32_t, uint32_t) -> int {
+  auto launch = [&](uint32_t, uint32_t n) -> int {
+    // the camera rays of the launch's samples first, at full width: part of the launch, and inside its timing bracket.  One block per
+    // CU in a grid-stride loop, not a block per 256 entries: with a launch of the other stream in flight the pre-pass starts in that
+    // launch's tail and this stream's wave kernel cannot start before it ends - a quarter of a million short blocks trickling through
+    // the slots the tail frees cost the overlapped step more than the table saved (DESIGN.md section 6 has the shapes measured).
+    if (cam_table) {
+      const size_t want = ((size_t)px * n + 255) / 256;
+      const uint32_t most = env_u32("SRT_CAMERA_BLOCKS", (uint32_t)pt->wave_cus);
+      const uint32_t blocks = (uint32_t)(want < most ? want : (most < 1u ? 1u : most));
+      pt_camera_kernel<<<dim3(blocks), dim3(256), 0, s>>>(DS.cam, T, pt->w, pt->h, seed, P.sample_base, n, cam_rng, cam_dir, cam_org, B.d_cancel);
+    }
     launch_wave(kern, dim3(pt->wave_blocks), dim3(256), lds, s, DS, P);
     return SRT_OK;
   };

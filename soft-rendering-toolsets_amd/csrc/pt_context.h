@@ -61,6 +61,10 @@ struct srt_pt {
   // may overlap on the device (the next epoch's blocks fill the CUs the previous launch's tail leaves idle).
   struct EpochBuffers {
     srt::DeviceBuffer<float> d_samples;                      // per-sample radiance
+    // persistent wave forms: the camera table of the launch in flight (pt_wave.h: pt_camera_kernel), rebuilt in front of every launch.
+    // Per sample of a launch 20 B - RNG state (2 dwords), then, in a second plane, the direction (3) -, then the shared origin:
+    // 1.34 GB per stream at 1024 x 1024 pixels and 64 samples per launch, next to d_samples' 1.07 GB.
+    srt::DeviceBuffer<uint32_t> d_camera;
     srt::DeviceBuffer<float> d_records;                      // wave kernel: per-bounce records
     srt::DeviceBuffer<float> d_running;                      // (sum, count) across the launches of one epoch
     srt::DeviceBuffer<unsigned long long> d_queue;           // wave kernel: queue head (+ section stamps)
@@ -92,6 +96,7 @@ struct srt_pt {
   std::map<hipStream_t, QueryBuffers> query_buffers;
   uint64_t hit_device_paths[3] = {0, 0, 0};                  // srt_pt_hit_device_paths: calls through {the cast kernel, the nested walk, the flattened walk}
   int wave_blocks = 0; size_t wave_lds = 0; int wave_mode = -1; const void* wave_kern = nullptr;
+  int wave_cus = 0;           // CUs of the device, read with wave_blocks (the camera pre-pass's launch shape)
   // pt_cast_kernel's launch shape (blocks == 0: not derived yet).  The render's and the queries' are cached apart: on a scene of the
   // streamed sweeps the render launches the walk-only build and a query the general one.
   struct CastShape {

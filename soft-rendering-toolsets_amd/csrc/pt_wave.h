@@ -34,6 +34,11 @@
 // regeneration, no tail of idle lanes.  Every sample's radiance is written to a
 // per-unit buffer; pt_reduce_kernel then adds the samples of a pixel in sample order, exactly as do_trace
 // does (rays/pathtracer.cpp:216-226), so the image does not depend on which lane traced what.
+// The camera rays themselves are not computed in the loop: a refill is work for the handful of lanes that are idle at the top of a
+// cycle, issued for the whole wave, and a camera ray is ~235 vector instructions of splitmix64, PCG steps, divides and a root.
+// pt_camera_kernel computes them for every sample of a launch, at full width, into a table in front of the launch; the refill loads
+// a unit's directions, and shade - which needs the ray of a parked camera hit again, and the RNG position behind its two jitter
+// draws - loads that sample's direction and RNG state (SRT_CAMERA_TABLE below; camera_table() names the forms that do).
 #ifndef SRT_PT_WAVE_H
 #define SRT_PT_WAVE_H
 
@@ -52,6 +57,23 @@ constexpr uint32_t kBurst = 3;            // camera rays per burst = samples per
 constexpr uint32_t kMissTri = 0xFFFFFFFFu;
 constexpr uint32_t kFlatReady = 16;        // TRAV 2: lanes with a finished batch that make the wave leave the walk
 constexpr int kRecFields = 8;             // two float4 per bounce: {direct rgb, discrete} and {atten rgb, inv_pdf}
+
+// The camera table of a launch (persistent forms).  Seed, pixel, sample index and camera are all known before a launch starts, so
+// pt_camera_kernel (below, after the loop's kernel) computes every sample's camera ray at full wave width in front of it - one lane
+// per (pixel slot, sample), 20 bytes per sample: the direction and Rng::state after the two jitter draws - and the loop loads where
+// it used to compute at the width of the few lanes that refill or shade a first hit.  Two planes, [pixel slot][sample] each: a unit's
+// samples are neighbours, the refill reads directions only, and the units a wave draws in one cycle are consecutive.
+// SRT_CAMERA_TABLE=0 keeps the inline arithmetic (A/B builds).
+#ifndef SRT_CAMERA_TABLE
+#define SRT_CAMERA_TABLE 1
+#endif
+// Which forms read the table: the persistent ones (TRAV 0..2; the streamed forms refill a generation's idle slots at once, at full
+// width, and keep the arithmetic), less the two that would pay for it with scratch.  The stamped build of the Cornell form gains 16 B
+// per lane with the table and the two-ray Cornell form 4 B (with the refill's loads; with shade's alone it gains none, and no time
+// either): both keep the inline code, and their launches have no pre-pass.
+__host__ __device__ constexpr bool camera_table(bool stamp, int trav, int nr) {
+  return SRT_CAMERA_TABLE != 0 && trav >= 0 && trav <= 2 && !(trav == 0 && (stamp || nr == 2));
+}
 
 struct WaveParams {
   TileMap T;
@@ -75,10 +97,15 @@ struct WaveParams {
   uint32_t flat_ready;       // TRAV 2: lanes with a finished batch that make the wave leave the walk
   uint32_t flat_interior;    // TRAV 2: lanes at interior nodes that keep the wave in the interior-step loop       // STAMP build only: per-section cycle sums
   // TRAV 3 (streamed form, pt_stream.h): one invocation = one generation; nlanes = path slots
-  uint32_t* state;           // [word][slot] saved path state
-  float4* ray_o;             // rays / walk requests of this generation at FIXED positions: [2 * ([queue slot][path slot])], and
-  float4* ray_d;             //   ray_d = ray_o + 1 (origin and direction of a request side by side: one 32-byte piece);
+  // (The persistent forms, TRAV 0..2, use none of the pointers below; there the first three words carry the launch's camera table,
+  //  which pt_camera_kernel fills in front of the launch - see SRT_CAMERA_TABLE.  The streamed forms' argument block is unchanged.)
+  union { uint32_t* state;   // [word][slot] saved path state
+          const uint2* cam_rng; };   // camera table: [pixel slot][sample of the launch] Rng::state after the two jitter draws
+  union { float4* ray_o;     // rays / walk requests of this generation at FIXED positions: [2 * ([queue slot][path slot])], and
+          const float* cam_dir; };   // camera table: [pixel slot][sample of the launch][3] direction of the sample's camera ray
+  union { float4* ray_d;     //   ray_d = ray_o + 1 (origin and direction of a request side by side: one 32-byte piece);
                              //   TRAV 3: queue slot = batch slot; TRAV 4: queue slot = mesh ordinal * NR + batch slot
+          const float* cam_org; };   // camera table: the origin every camera ray of the launch shares (iview * 0), three floats
   const uint2* hits;         // [queue slot][path slot] results of the previous generation's rays / walks
   StreamCounters* sc;
   unsigned long long* block_counters;   // [block][2]: rays counted / rays elided by that block of the logic kernel, all generations
@@ -504,6 +531,9 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   // without delta lights.  The other sweep forms gain scratch with a second copy of the loop and keep the one step; and
   // SRT_PLAIN_DIV_SQRT switches it off with the other fast paths.
   constexpr bool MINMAX = SRT_EXACT_FAST_PATHS && TRAV == 0 && !DL && PHASE == 0;
+  // Camera rays from the launch's camera table instead of the inline arithmetic - in the refill, in shade and in the environment
+  // map's lookup; see camera_table().
+  constexpr bool CAMTAB = camera_table(STAMP, TRAV, NR);
   if constexpr (STREAM) {
     if (P_in.sc->done != 0u) return;                     // every unit is finished: the remaining generations are no-ops
   }
@@ -809,18 +839,31 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
           level = 0;
           depth = S.max_depth;
           // camera rays of the unit's samples (trace_pixel, student/pathtracer.cpp:26-31); absent samples repeat the first
-          const Camera cam_c = opq(S.cam);
-          const uint64_t seed = opq(P.seed);
-          const uint32_t sample_base = opq(P.sample_base);
+          if constexpr (CAMTAB) {
+            // ... as pt_camera_kernel left them in the launch's table.  (The RNG position is not needed here: shade takes it from
+            // the table when it picks a camera hit up.)
+            const float* cd = P.cam_dir + ((size_t)u_pixel * P.samples + u_first) * 3u;
 #pragma unroll
-          for (int j = 0; j < NR; j++) {
-            const uint32_t sj = u_first + ((uint32_t)j < u_count ? (uint32_t)j : 0u);
-            rng.key(seed, y * img_w + x, sample_base + sj);
-            const float jx = rng.unit() * 1.0f;
-            const float jy = rng.unit() * 1.0f;
-            const Ray cam = camera_ray(cam_c, ((float)x + jx) / (float)img_w, ((float)y + jy) / (float)img_h);
-            org = cam.o;                                // the same for every camera ray (iview * origin)
-            d[j] = cam.d; cb0 = cam.b0; cb1 = cam.b1;
+            for (int j = 0; j < NR; j++) {
+              const uint32_t oj = ((uint32_t)j < u_count ? (uint32_t)j : 0u) * 3u;
+              d[j] = v3(cd[oj], cd[oj + 1u], cd[oj + 2u]);
+            }
+            org = v3(P.cam_org[0], P.cam_org[1], P.cam_org[2]);
+            cb0 = 0.0f; cb1 = __uint_as_float(0x7f800000u);
+          } else {
+            const Camera cam_c = opq(S.cam);
+            const uint64_t seed = opq(P.seed);
+            const uint32_t sample_base = opq(P.sample_base);
+#pragma unroll
+            for (int j = 0; j < NR; j++) {
+              const uint32_t sj = u_first + ((uint32_t)j < u_count ? (uint32_t)j : 0u);
+              rng.key(seed, y * img_w + x, sample_base + sj);
+              const float jx = rng.unit() * 1.0f;
+              const float jy = rng.unit() * 1.0f;
+              const Ray cam = camera_ray(cam_c, ((float)x + jx) / (float)img_w, ((float)y + jy) / (float)img_h);
+              org = cam.o;                              // the same for every camera ray (iview * origin)
+              d[j] = cam.d; cb0 = cam.b0; cb1 = cam.b1;
+            }
           }
           actA = u_count > 1;                           // slot usage of a burst: ray j exists iff j < count
           actB = u_count > 2;
@@ -1258,13 +1301,18 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         if (miss_env && level == 0) {
           e = spec(S.env_radiance[0], S.env_radiance[1], S.env_radiance[2]);
           if (S.env_type == 3u) {                         // Env_Map::evaluate(ray.dir) of the sample's camera ray
-            Rng cr;
-            const uint32_t img_w = opq(S.w), img_h = opq(S.h);
-            cr.key(opq(P.seed), PY_ * img_w + PX_, opq(P.sample_base) + S_CUR_);
-            const float jx = cr.unit() * 1.0f;
-            const float jy = cr.unit() * 1.0f;
-            const Ray cam = camera_ray(opq(S.cam), ((float)PX_ + jx) / (float)img_w, ((float)PY_ + jy) / (float)img_h);
-            e = env_map_evaluate(S, cam.d);
+            if constexpr (CAMTAB) {
+              const float* cd = P.cam_dir + ((size_t)pixel_slot * P.samples + S_CUR_) * 3u;
+              e = env_map_evaluate(S, v3(cd[0], cd[1], cd[2]));
+            } else {
+              Rng cr;
+              const uint32_t img_w = opq(S.w), img_h = opq(S.h);
+              cr.key(opq(P.seed), PY_ * img_w + PX_, opq(P.sample_base) + S_CUR_);
+              const float jx = cr.unit() * 1.0f;
+              const float jy = cr.unit() * 1.0f;
+              const Ray cam = camera_ray(opq(S.cam), ((float)PX_ + jx) / (float)img_w, ((float)PY_ + jy) / (float)img_h);
+              e = env_map_evaluate(S, cam.d);
+            }
           }
         }
         if (!terminal) {
@@ -1308,10 +1356,23 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         if (level == 0) {
           // a camera ray: regenerate it (and the RNG position after its two jitter draws) from the sample index
           const uint32_t img_w = opq(S.w), img_h = opq(S.h);
-          rng.key(opq(P.seed), PY_ * img_w + PX_, opq(P.sample_base) + S_CUR_);
-          const float jx = rng.unit() * 1.0f;
-          const float jy = rng.unit() * 1.0f;
-          ray = camera_ray(opq(S.cam), ((float)PX_ + jx) / (float)img_w, ((float)PY_ + jy) / (float)img_h);
+          if constexpr (CAMTAB) {
+            // ... which is to say: read both from the launch's camera table; Rng::key's increment stays a computation
+            const size_t ti = (size_t)pixel_slot * P.samples + S_CUR_;
+            const float* cd = P.cam_dir + ti * 3u;
+            const uint2 st = P.cam_rng[ti];
+            rng.state = (uint64_t)st.x | ((uint64_t)st.y << 32);
+            rng.inc = (((((uint64_t)(PY_ * img_w + PX_)) << 32) | (uint64_t)(opq(P.sample_base) + S_CUR_)) << 1) | 1ull;
+            rng.draws = 2;
+            ray.o = v3(P.cam_org[0], P.cam_org[1], P.cam_org[2]);
+            ray.d = v3(cd[0], cd[1], cd[2]);
+            ray.b0 = 0.0f; ray.b1 = __uint_as_float(0x7f800000u);
+          } else {
+            rng.key(opq(P.seed), PY_ * img_w + PX_, opq(P.sample_base) + S_CUR_);
+            const float jx = rng.unit() * 1.0f;
+            const float jy = rng.unit() * 1.0f;
+            ray = camera_ray(opq(S.cam), ((float)PX_ + jx) / (float)img_w, ((float)PY_ + jy) / (float)img_h);
+          }
         }
         burst = false;
         Surface sf = surface_of<true>(S, ch, ray);
@@ -1406,6 +1467,40 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   } else if (lane == 0) {
     atomicAdd(P.ray_counter, r);
     if (NR == 2) atomicAdd(P.elided_counter, r - rt);
+  }
+}
+
+// The camera table of one launch of the persistent forms (SRT_CAMERA_TABLE above; WaveParams::cam_*): one lane per (pixel slot, sample of
+// the launch), the sample index fastest, a grid-stride loop.  It computes what the loop's refill and shade computed for themselves -
+// the same device functions on the same operands, so the same bits: Rng::key(seed, y * w + x, sample_base + s), the two jitter
+// draws, camera_ray - and stores the direction and the RNG state after the draws.  The ray's origin (iview * 0, Ray::transform's
+// mat_point) is the same for every sample and is written once; its bounds are the camera's {0, +inf} and are not stored.  The
+// samples of a padding pixel of an edge tile get no entry.  (The launch is one block per CU, not one lane per entry: see
+// render_epoch_wave, pt.hip.)
+__global__ __launch_bounds__(256) void pt_camera_kernel(Camera cam, TileMap T, uint32_t w, uint32_t h, uint64_t seed, uint32_t sample_base,
+                                                        uint32_t samples, uint2* __restrict__ cam_rng, float* __restrict__ cam_dir,
+                                                        float* __restrict__ cam_org, const uint32_t* dev_cancel) {
+  if (cancel_raised(dev_cancel)) return;                 // srt_pt_cancel: what is left of the epoch is not rendered
+  const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t entries = (size_t)(T.local_tiles * T.tile_w * T.tile_h) * samples;
+  if (first == 0) {
+    const V3 o = mat_point(cam.iview, v3(0, 0, 0));
+    cam_org[0] = o.x; cam_org[1] = o.y; cam_org[2] = o.z;
+  }
+  for (size_t i = first; i < entries; i += (size_t)gridDim.x * blockDim.x) {
+    uint32_t p, s;
+    if ((i >> 32) == 0) { p = (uint32_t)i / samples; s = (uint32_t)i % samples; }   // (all but the largest shards: no 64-bit division)
+    else { p = (uint32_t)(i / samples); s = (uint32_t)(i % samples); }
+    uint32_t x, y;
+    unit_pixel(T, p, x, y);
+    if (x >= w || y >= h) continue;
+    Rng rng;
+    rng.key(seed, y * w + x, sample_base + s);
+    const float jx = rng.unit() * 1.0f;
+    const float jy = rng.unit() * 1.0f;
+    const Ray ray = camera_ray(cam, ((float)x + jx) / (float)w, ((float)y + jy) / (float)h);
+    cam_rng[i] = make_uint2((uint32_t)rng.state, (uint32_t)(rng.state >> 32));
+    cam_dir[3 * i] = ray.d.x; cam_dir[3 * i + 1] = ray.d.y; cam_dir[3 * i + 2] = ray.d.z;
   }
 }
 

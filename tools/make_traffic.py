@@ -36,7 +36,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KERNELS = ("pt_wave_kernel", "pt_cast_kernel", "pt_compact_kernel", "pt_unit_kernel")
+KERNELS = ("pt_wave_kernel", "pt_camera_kernel", "pt_cast_kernel", "pt_compact_kernel", "pt_unit_kernel")   # (pt_camera_kernel: the wave launch's pre-pass)
 
 
 def find(out, sub, suffix):
