@@ -13,6 +13,11 @@ struct Emu {
   std::vector<Material> materials;
   BuiltScene built;
   DScene S;
+  // what scene.hit does not read: kept for the modules that shade (path_host.cpp), which put it into their own copy of S
+  std::vector<DeltaLight> delta_lights;
+  uint32_t env_type = 0, env_w = 0, env_h = 0;
+  float env_radiance[3] = {0, 0, 0};
+  std::vector<float> env_map;
 };
 
 // A stack that records the deepest frame index a walk touches.  Its array is larger than any tree the product accepts needs, so
@@ -73,6 +78,37 @@ int emu_add_sphere(void* h, float radius, const float* T, uint32_t material) {
   ObjectInput o; o.kind = OBJ_SPHERE; o.material = material; o.radius = radius;
   for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) o.trans.c[c][r] = T[4 * c + r];
   e->inputs.push_back(o);
+  return 0;
+}
+// The rest of a scene as the C ABI collects it (pt_context.cpp): an emissive sphere with its light mesh (srt_pt_add_sphere_light),
+// a delta light (srt_pt_add_light), the environment light or map (srt_pt_set_env_light / srt_pt_set_env_map).
+int emu_feed_sphere_light(void* h, float radius, const float* T, uint32_t material, const float* pos, const float* nrm, uint32_t nv,
+                          const uint32_t* idx, uint32_t ni) {
+  Emu* e = (Emu*)h;
+  ObjectInput o; o.kind = OBJ_SPHERE; o.material = material; o.radius = radius; o.is_light = true;
+  for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) o.trans.c[c][r] = T[4 * c + r];
+  o.mesh.pos.assign(pos, pos + 3 * nv); o.mesh.nrm.assign(nrm, nrm + 3 * nv); o.mesh.idx.assign(idx, idx + ni);
+  e->inputs.push_back(o);
+  return 0;
+}
+int emu_feed_light(void* h, uint32_t type, const float* radiance, const float* angle_bounds, const float* T) {
+  Emu* e = (Emu*)h;
+  Mat4 m;
+  for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) m.c[c][r] = T[4 * c + r];
+  e->delta_lights.push_back(make_delta_light(type, radiance, angle_bounds, m));
+  return 0;
+}
+int emu_feed_env_light(void* h, uint32_t type, const float* radiance) {
+  Emu* e = (Emu*)h;
+  e->env_type = type; e->env_w = e->env_h = 0; e->env_map.clear();
+  for (int i = 0; i < 3; i++) e->env_radiance[i] = radiance[i];
+  return 0;
+}
+int emu_feed_env_map(void* h, uint32_t width, uint32_t height, const float* rgb) {
+  Emu* e = (Emu*)h;
+  if (!width || !height) return -1;
+  e->env_type = 3; e->env_w = width; e->env_h = height;
+  e->env_map.assign(rgb, rgb + 3 * (size_t)width * height);
   return 0;
 }
 int emu_commit(void* h, int use_bvh) {
