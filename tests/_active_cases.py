@@ -6,8 +6,6 @@ defined by the host definition (check_active_list / apply_set_active / mask_top,
 for the host (tests/host_emu/active_flat_host.cpp): EmuActive below.  The boxes themselves are top_boxes_numpy of
 _repose_refit_cases fed with masked posed boxes (masked)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -27,17 +25,7 @@ TIES_CAP = 0
 
 
 def emu_lib():
-    out = os.path.join(H.ORACLE_DIR, "_build", "libactive_flat_host.so")
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    srcs = [os.path.join(emu, "active_flat_host.cpp"), os.path.join(csrc, "pt_scene.cpp")]
-    deps = srcs + [os.path.join(emu, f) for f in ("repose_refit_flat_host.cpp", "refit_flat_host.cpp", "flat_host.cpp", "instances_flat_host.cpp")] + \
-        [os.path.join(csrc, f) for f in ("pt_flat.h", "pt_trace.h", "pt_device.h", "pt_scene.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc,
-                        "-I" + os.path.join(H.ROOT, "include"), *srcs, "-o", out], check=True)
-    lib = ctypes.CDLL(out)
+    lib = ctypes.CDLL(H.build_host_lib("active_flat_host", ["active_flat_host.cpp"], scene_layer=True))
     lib.emu_refit_create.restype = ctypes.c_void_p
     lib.emu_dump_top.restype = ctypes.c_long
     lib.emu_dump_top.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]

@@ -5,7 +5,6 @@ Joint::joint_to_posed) and records as tests/golden/anim_objects.npz and anim_rig
 fixtures, so that what is evaluated is what was recorded.  Everything here is data: knot times, knot values, time lists."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -158,24 +157,12 @@ def mismatches(a, b):
 
 # ---- the host emulation of pt_anim.h (tests/host_emu/anim_host.cpp, g++ -ffp-contract=off) ----
 _emu = None
-EMU_PATH = os.path.join(H.ORACLE_DIR, "_build", "libanim_host.so")
-
-
-def _compile(out, srcs, extra=(), shared=True):
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    deps = list(srcs) + [os.path.join(csrc, f) for f in ("pt_anim.h", "pt_skin.h", "pt_device.h", "pt_scene.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", *(["-fPIC", "-shared"] if shared else []), *extra, "-I" + emu, "-I" + csrc,
-                        "-I" + os.path.join(H.ROOT, "include"), *srcs, "-o", out, "-lm"], check=True)
-    return out
 
 
 def anim_emu():
     global _emu
     if _emu is None:
-        _emu = ctypes.CDLL(_compile(EMU_PATH, [os.path.join(H.ROOT, "tests", "host_emu", "anim_host.cpp")]))
+        _emu = ctypes.CDLL(H.build_host_lib("anim_host", ["anim_host.cpp"], extra=("-lm",)))
         _emu.anim_emu_hypot_sweep.restype = ctypes.c_uint64
         _emu.anim_emu_hypot_sweep.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
     return _emu
@@ -183,8 +170,8 @@ def anim_emu():
 
 def sanitized_program():
     """tests/host_emu/anim_sanitized_main.cpp built with -fsanitize=address,undefined: a program of its own, run as its own process."""
-    return _compile(os.path.join(H.ORACLE_DIR, "_build", "anim_sanitized"), [os.path.join(H.ROOT, "tests", "host_emu", "anim_sanitized_main.cpp")],
-                    extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"), shared=False)
+    return H.build_host_lib("anim_sanitized", ["anim_sanitized_main.cpp"], program=True,
+                            extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-lm"))
 
 
 def emu_objects(offsets, times, values, t):

@@ -11,7 +11,6 @@ survivors of a frame are then the tail of the previous vector and the births its
 the birth ordinals."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -99,15 +98,7 @@ _emu = None
 def emitter_emu():
     global _emu
     if _emu is None:
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        src = os.path.join(H.ROOT, "tests", "host_emu", "emitter_host.cpp")
-        out = os.path.join(H.ORACLE_DIR, "_build", "libemitter_host.so")
-        deps = [src] + [os.path.join(csrc, f) for f in ("pt_emitter.h", "pt_anim.h", "pt_skin.h", "pt_device.h", "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I" + os.path.dirname(src), "-I" + csrc,
-                            "-I" + os.path.join(H.ROOT, "include"), src, "-o", out, "-lm"], check=True)
-        _emu = ctypes.CDLL(out)
+        _emu = ctypes.CDLL(H.build_host_lib("emitter_host", ["emitter_host.cpp"], extra=("-lm",)))
     return _emu
 
 

@@ -508,22 +508,79 @@ def epochs_through(through, total, spe):
 # with g++ (same -ffp-contract=off) and run one lane at a time.  Checks the traversal LOGIC on the CPU; the HIP
 # build of the same source is what the GPU tests check.
 # ------------------------------------------------------------------------------------------------
+CSRC = os.path.join(ROOT, "soft-rendering-toolsets_amd", "csrc")
+HOST_EMU = os.path.join(ROOT, "tests", "host_emu")
+BUILD_DIR = os.path.join(ORACLE_DIR, "_build")
+# The scene layer (host-only C++ of the product): the one place in tests/ and tools/ that names its files.
+SCENE_LAYER_SRCS = [os.path.join(CSRC, f) for f in ("pt_scene.cpp",)]
+SANITIZE = ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+
+
+def _compile(out, srcs, flags, *, scene_layer, extra, device_headers, keep):
+    """The one compiler line of the tests.  srcs: paths, or names under tests/host_emu.  `extra` stands in front of the common include
+    directories (so a site's own -I wins) except its -l items, which go behind the sources.  keep: build only if `out` is missing or
+    older than a file the compiler read last time (its list, and the command, are kept in out + ".d")."""
+    srcs = [os.path.join(HOST_EMU, s) for s in srcs] + (SCENE_LAYER_SRCS if scene_layer else [])
+    incs = ["-I" + HOST_EMU, "-I" + CSRC] if device_headers else []
+    cmd = ["g++", *flags, "-std=c++17", "-ffp-contract=off", *(e for e in extra if not e.startswith("-l")), *incs,
+           "-I" + os.path.join(ROOT, "include"), *srcs, *(e for e in extra if e.startswith("-l"))]
+    if not keep:
+        subprocess.run(cmd + ["-o", out], check=True)
+        return out
+    import json
+
+    record = out + ".d"
+    rel = lambda p: os.path.relpath(p, ROOT)          # (the tree may be copied elsewhere together with what was built in it)
+    try:
+        with open(record) as f:
+            old = json.load(f)
+        fresh = old["cmd"] == [c.replace(ROOT, "@") for c in cmd] and \
+            all(os.path.getmtime(os.path.join(ROOT, d)) <= os.path.getmtime(out) for d in old["deps"])
+    except (OSError, ValueError, KeyError):
+        fresh = False
+    if not fresh:
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.run(cmd + ["-o", out], check=True)
+        rules = subprocess.run([c for c in cmd if c != "-shared"] + ["-MM"], check=True, capture_output=True, text=True).stdout
+        deps = sorted({rel(t) for t in rules.replace("\\\n", " ").split() if not t.endswith(":")})
+        with open(record, "w") as f:
+            json.dump({"cmd": [c.replace(ROOT, "@") for c in cmd], "deps": deps}, f)
+    return out
+
+
+def build_host_lib(name, srcs, *, scene_layer=False, extra=(), device_headers=True, program=False):
+    """oracle/_build/lib<name>.so (program: oracle/_build/<name>, a program with its own main) from srcs, built if missing or stale:
+    -O2 -ffp-contract=off as the product build, tests/host_emu (the stand-in for the HIP runtime) and csrc/ (the device headers) on
+    the include path unless device_headers is off, the scene layer linked in where scene_layer is set."""
+    out = os.path.join(BUILD_DIR, name if program else f"lib{name}.so")
+    return _compile(out, srcs, ("-O2",) if program else ("-O2", "-fPIC", "-shared"), scene_layer=scene_layer, extra=extra,
+                    device_headers=device_headers, keep=True)
+
+
+def run_sanitized_main(tmp_path, main_cpp, *, scene_layer=True, extra_srcs=(), args=(), expect=None, extra=(), flags=SANITIZE,
+                       device_headers=True):
+    """A stand-alone program (its own main, nothing loaded into Python) built into tmp_path with AddressSanitizer and
+    UndefinedBehaviorSanitizer and run once as its own process: exit status 0 and the line `expect` ("<name>: ok" by default, <name>
+    being main_cpp without "_main.cpp").  Returns what it printed."""
+    name = os.path.basename(main_cpp)[: -len(".cpp")]
+    name = name[: -len("_main")] if name.endswith("_main") else name
+    exe = os.path.join(str(tmp_path), name)
+    if not os.path.exists(exe):                       # (a test that runs its program on several inputs builds it once)
+        _compile(exe, [main_cpp, *extra_srcs], flags, scene_layer=scene_layer, extra=extra, device_headers=device_headers, keep=False)
+    r = subprocess.run([exe, *(str(a) for a in args)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert (expect or name + ": ok") in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    return r.stdout
+
+
 _emu = None
 
 
 def host_emu():
     global _emu
     if _emu is None:
-        out = os.path.join(ORACLE_DIR, "_build", "libflat_host.so")
-        csrc = os.path.join(ROOT, "soft-rendering-toolsets_amd", "csrc")
-        srcs = [os.path.join(ROOT, "tests", "host_emu", "flat_host.cpp"), os.path.join(csrc, "pt_scene.cpp")]
-        deps = srcs + [os.path.join(csrc, f) for f in ("pt_flat.h", "pt_trace.h", "pt_device.h", "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                            "-I" + os.path.join(ROOT, "tests", "host_emu"), "-I" + csrc, "-I" + os.path.join(ROOT, "include"),
-                            *srcs, "-o", out], check=True)
-        _emu = ctypes.CDLL(out)
+        _emu = ctypes.CDLL(build_host_lib("flat_host", ["flat_host.cpp"], scene_layer=True))
         _emu.emu_create.restype = ctypes.c_void_p
     return _emu
 
@@ -601,16 +658,11 @@ def pt_core_driver():
     library: tests/host_emu/pt_core_driver.cpp + soft-rendering-toolsets_amd/host/pathtracer_core.cpp, built with g++."""
     global _core_driver
     if _core_driver is None:
-        out = os.path.join(ORACLE_DIR, "_build", "libpt_core_driver.so")
         host = os.path.join(ROOT, "soft-rendering-toolsets_amd", "host")
         lib = os.path.join(ROOT, "soft-rendering-toolsets_amd", "lib")
-        srcs = [os.path.join(ROOT, "tests", "host_emu", "pt_core_driver.cpp"), os.path.join(host, "pathtracer_core.cpp")]
-        deps = srcs + [os.path.join(host, "pathtracer_core.h"), os.path.join(ROOT, "include", "srt_pt.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + host, "-I" + os.path.join(ROOT, "include"),
-                            "-I/opt/rocm/include", *srcs, "-L" + lib, "-lsrt_hip", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
-                            "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-o", out], check=True)
+        out = build_host_lib("pt_core_driver", ["pt_core_driver.cpp", os.path.join(host, "pathtracer_core.cpp")], device_headers=False,
+                             extra=("-D__HIP_PLATFORM_AMD__", "-I" + host, "-I/opt/rocm/include", "-L" + lib, "-lsrt_hip", "-L/opt/rocm/lib",
+                                    "-lamdhip64", "-lpthread", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib"))
         _core_driver = ctypes.CDLL(out)
         _core_driver.core_create.restype = ctypes.c_void_p
         _core_driver.core_context.restype = ctypes.c_void_p

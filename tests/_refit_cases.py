@@ -6,8 +6,6 @@ vertices builds: the oracle, which only builds, walks another tree.  What a refi
 refit (refit_boxes / apply_mesh_refit, pt_scene.cpp) walked by the device headers compiled for the host
 (tests/host_emu/refit_flat_host.cpp): EmuRefit below."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -33,17 +31,7 @@ def deep_moved(scene):
 
 
 def emu_lib():
-    out = os.path.join(H.ORACLE_DIR, "_build", "librefit_flat_host.so")
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    srcs = [os.path.join(emu, "refit_flat_host.cpp"), os.path.join(csrc, "pt_scene.cpp")]
-    deps = srcs + [os.path.join(emu, f) for f in ("flat_host.cpp", "instances_flat_host.cpp")] + \
-        [os.path.join(csrc, f) for f in ("pt_flat.h", "pt_trace.h", "pt_device.h", "pt_scene.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc,
-                        "-I" + os.path.join(H.ROOT, "include"), *srcs, "-o", out], check=True)
-    lib = ctypes.CDLL(out)
+    lib = ctypes.CDLL(H.build_host_lib("refit_flat_host", ["refit_flat_host.cpp"], scene_layer=True))
     lib.emu_refit_create.restype = ctypes.c_void_p
     return lib
 

@@ -6,8 +6,6 @@ the scene a fresh commit of the new vertices builds: the oracle, which only buil
 compute is defined by the host definition (prepare_mesh_refit_inplace / apply_mesh_refit_inplace, pt_scene.cpp) walked by the
 device headers compiled for the host (tests/host_emu/refit_inplace_flat_host.cpp): EmuInplace below."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -25,17 +23,7 @@ TIES_CAP = 0
 
 
 def emu_lib():
-    out = os.path.join(H.ORACLE_DIR, "_build", "librefit_inplace_flat_host.so")
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    srcs = [os.path.join(emu, "refit_inplace_flat_host.cpp"), os.path.join(csrc, "pt_scene.cpp")]
-    deps = srcs + [os.path.join(emu, f) for f in ("repose_refit_flat_host.cpp", "refit_flat_host.cpp", "flat_host.cpp", "instances_flat_host.cpp")] + \
-        [os.path.join(csrc, f) for f in ("pt_flat.h", "pt_trace.h", "pt_device.h", "pt_scene.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc,
-                        "-I" + os.path.join(H.ROOT, "include"), *srcs, "-o", out], check=True)
-    lib = ctypes.CDLL(out)
+    lib = ctypes.CDLL(H.build_host_lib("refit_inplace_flat_host", ["refit_inplace_flat_host.cpp"], scene_layer=True))
     lib.emu_refit_create.restype = ctypes.c_void_p
     lib.emu_dump_top.restype = ctypes.c_long
     lib.emu_dump_top.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]

@@ -2,9 +2,7 @@
 over pt_pose.h (tests/host_emu/pose_host.cpp), the matrices and boxes the device functions are compared on, the numpy
 restatement of translate * scale, and the scene file the sanitized stand-alone program reads."""
 import ctypes
-import os
 import struct
-import subprocess
 
 import numpy as np
 
@@ -16,15 +14,7 @@ PARTICLE_SCALE = np.float32(0.03)          # pt_scene("cbox_particles"): Mat4::t
 
 
 def pose_lib():
-    out = os.path.join(H.ORACLE_DIR, "_build", "libpose_host.so")
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    src = os.path.join(emu, "pose_host.cpp")
-    deps = [src] + [os.path.join(csrc, f) for f in ("pt_scene.cpp", "pt_scene.h", "pt_pose.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc, src, "-o", out], check=True)
-    lib = ctypes.CDLL(out)
+    lib = ctypes.CDLL(H.build_host_lib("pose_host", ["pose_host.cpp"]))
     lib.pose_emu_mismatches.restype = ctypes.c_long
     lib.pose_ts_mismatches.restype = ctypes.c_long
     lib.pose_ts_mismatches.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float]

@@ -264,14 +264,14 @@ SRC = os.path.join(H.ROOT, "tests", "host_emu", "shading_host.cpp")
 def shading_emu():
     global _emu
     if _emu is None:
-        _emu = ctypes.CDLL(AC._compile(os.path.join(H.ORACLE_DIR, "_build", "libshading_host.so"), [SRC]))
+        _emu = ctypes.CDLL(H.build_host_lib("shading_host", [SRC], extra=("-lm",)))
     return _emu
 
 
 def sanitized_program():
     """The same file with its main(), built with -fsanitize=address,undefined: a program of its own, run as its own process."""
-    return AC._compile(os.path.join(H.ORACLE_DIR, "_build", "shading_sanitized"), [SRC],
-                       extra=("-g", "-DSHADING_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"), shared=False)
+    return H.build_host_lib("shading_sanitized", [SRC], program=True,
+                            extra=("-g", "-DSHADING_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-lm"))
 
 
 def emu_values(g, group, t):

@@ -8,8 +8,6 @@ from the oracle's dumps (test_pt_update_host.py::test_deformations_exercise_both
     original 315, D1 323, D2 325, D3 315
 D1 and D2 change the node count (the ranges stored behind the mesh move); D3, a translation, keeps it."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -94,15 +92,7 @@ def one_point(scene, index):
 
 
 def update_lib():
-    out = os.path.join(H.ORACLE_DIR, "_build", "libupdate_host.so")
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    src = os.path.join(emu, "update_host.cpp")
-    deps = [src] + [os.path.join(csrc, f) for f in ("pt_scene.cpp", "pt_scene.h", "pt_mesh_update.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc, src, "-o", out], check=True)
-    lib = ctypes.CDLL(out)
+    lib = ctypes.CDLL(H.build_host_lib("update_host", ["update_host.cpp"]))
     lib.upd_create.restype = ctypes.c_void_p
     lib.upd_clone.restype = ctypes.c_void_p
     lib.upd_error.restype = ctypes.c_char_p

@@ -1,57 +1,12 @@
 // Stand-alone check of srt_pt_set_active's scene layer (pt_scene.cpp alone; tests/test_pt_active_host.py builds it with
 // -fsanitize=address,undefined and runs it once) on the scene and the list of the file given as argv[1] (the format of
-// repose_device_sanitized_main.cpp): the definition - check_active_list / apply_set_active / mask_top - the fold of the effective
+// scene_main_common.h:load_scene_file): the definition - check_active_list / apply_set_active / mask_top - the fold of the effective
 // boxes, the empty-node rule of tree_cost, the rebuild and refit paths while objects are hidden, and the settle bookkeeping (the
 // table and the boxes applied as srt_pt_set_active_device's read-back delivers them).
-//
-// File (little endian, 32-bit words): nmat, then per material {type, a[3], b[3], ior}; nobj, then per object {kind (0 mesh,
-// 1 sphere, 2 instance), is_light, material, source, radius, T[16], nverts, nidx, pos[3 nverts], nrm[3 nverts], idx[nidx]};
-// n, then n insertion indices and n transforms of 16 floats.
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-struct Reader {
-  std::vector<unsigned char> bytes;
-  size_t at = 0;
-  bool ok = true;
-  void read(void* dst, size_t n) {
-    if (at + n > bytes.size()) { ok = false; std::memset(dst, 0, n); return; }
-    std::memcpy(dst, bytes.data() + at, n);
-    at += n;
-  }
-  uint32_t u32() { uint32_t v; read(&v, 4); return v; }
-  float f32() { float v; read(&v, 4); return v; }
-  template <class T> void array(std::vector<T>* v, size_t n) {
-    if (at + n * sizeof(T) > bytes.size()) { ok = false; return; }
-    v->resize(n);
-    if (n) read(v->data(), n * sizeof(T));
-  }
-};
-
-template <class V>
-static bool same_bytes(const V& a, const V& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
-}
-
-static bool same_scene(const BuiltScene& a, const BuiltScene& b) {
-  if (a.inputs.size() != b.inputs.size()) return false;
-  for (size_t i = 0; i < a.inputs.size(); i++)
-    if (std::memcmp(&a.inputs[i].trans, &b.inputs[i].trans, sizeof(Mat4)) != 0) return false;
-  return same_bytes(a.flat.nodes, b.flat.nodes) && same_bytes(a.flat.objects, b.flat.objects) && same_bytes(a.flat.wave_tlas, b.flat.wave_tlas) &&
-         a.flat.wave_lazy == b.flat.wave_lazy && a.flat.lazy_objects == b.flat.lazy_objects && same_bytes(a.tlas.nodes, b.tlas.nodes) &&
-         a.tlas.prim == b.tlas.prim && a.flat.tlas_nodes == b.flat.tlas_nodes && a.active == b.active;
-}
+#include "scene_main_common.h"
 
 static bool same_links(const HostBVH& a, const HostBVH& b) {
   if (a.prim != b.prim || a.nodes.size() != b.nodes.size()) return false;
@@ -119,43 +74,13 @@ static void check_masked(const BuiltScene& S) {
 
 int main(int argc, char** argv) {
   if (argc < 2) { std::printf("usage: %s scene-file\n", argv[0]); return 2; }
-  Reader R;
-  if (FILE* f = std::fopen(argv[1], "rb")) {
-    unsigned char buf[65536];
-    size_t got;
-    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) R.bytes.insert(R.bytes.end(), buf, buf + got);
-    std::fclose(f);
-  }
-  std::vector<Material> mats(R.u32());
-  for (Material& m : mats) {
-    std::memset(&m, 0, sizeof m);
-    m.type = R.u32();
-    for (float& v : m.a) v = R.f32();
-    for (float& v : m.b) v = R.f32();
-    m.ior = R.f32();
-  }
-  std::vector<ObjectInput> inputs(R.ok ? R.u32() : 0);
-  for (ObjectInput& o : inputs) {
-    const uint32_t kind = R.u32();
-    o.kind = kind == 1u ? OBJ_SPHERE : OBJ_MESH;
-    o.is_light = R.u32() != 0u;
-    o.material = R.u32();
-    const uint32_t source = R.u32();
-    o.source = kind == 2u ? (int32_t)source : -1;
-    o.radius = R.f32();
-    R.read(&o.trans, sizeof(Mat4));
-    const uint32_t nverts = R.u32(), nidx = R.u32();
-    R.array(&o.mesh.pos, 3 * (size_t)nverts);
-    R.array(&o.mesh.nrm, 3 * (size_t)nverts);
-    R.array(&o.mesh.idx, nidx);
-    if (!R.ok) break;
-  }
-  const uint32_t n = R.ok ? R.u32() : 0;
+  std::vector<Material> mats;
+  std::vector<ObjectInput> inputs;
   std::vector<uint32_t> listed;
   std::vector<Mat4> moved;
-  R.array(&listed, n);
-  R.array(&moved, n);
-  if (!R.ok || R.at != R.bytes.size() || inputs.size() < 2 || n < 2) { std::printf("cannot read %s\n", argv[1]); return 2; }
+  const bool read = load_scene_file(argv[1], &mats, &inputs, &listed, &moved);
+  const uint32_t n = (uint32_t)listed.size();
+  if (!read || inputs.size() < 2 || n < 2) { std::printf("cannot read %s\n", argv[1]); return 2; }
   const uint32_t nobj = (uint32_t)inputs.size();
 
   BuiltScene S;
@@ -169,7 +94,7 @@ int main(int argc, char** argv) {
   // every other listed object off; a call that changes nothing writes nothing
   std::vector<uint8_t> flags(n), ones(n, 1);
   for (uint32_t k = 0; k < n; k++) flags[k] = (k & 1u) ? 7 : 0;
-  EXPECT(!apply_set_active(&S, listed.data(), ones.data(), n) && same_scene(S, first));
+  EXPECT(!apply_set_active(&S, listed.data(), ones.data(), n) && same_posed_scene(S, first));
   EXPECT(apply_set_active(&S, listed.data(), flags.data(), n));
   EXPECT(!apply_set_active(&S, listed.data(), flags.data(), n));
   for (uint32_t k = 0; k < n; k++) EXPECT(S.active[listed[k]] == ((k & 1u) ? 1 : 0));
@@ -182,7 +107,7 @@ int main(int argc, char** argv) {
   {
     TopRefit T;
     EXPECT(prepare_top_refit(S, listed.data(), moved.data(), n, &T).empty());
-    EXPECT(same_scene(S, masked));
+    EXPECT(same_posed_scene(S, masked));
     apply_top_refit(&S, &T);
     EXPECT(S.active == masked.active && same_links(S.tlas, first.tlas));
     check_masked(S);
@@ -212,7 +137,7 @@ int main(int argc, char** argv) {
     L.active.swap(table);
     apply_top_refit(&L, &Q);
     write_top_counts(&L);                                 // (what settle() does behind a srt_pt_set_active_device call)
-    EXPECT(same_scene(L, masked));
+    EXPECT(same_posed_scene(L, masked));
   }
 
   // every object that may be hidden hidden: the root is empty and the cost 0 only when nothing is left
@@ -244,7 +169,7 @@ int main(int argc, char** argv) {
         if (inputs[i].is_light) { EXPECT(check_active_list(S, &i, 1, &unsupported).find("area light") != std::string::npos && !unsupported); break; }
     }
     S.dynamic_lights = false;
-    EXPECT(same_scene(S, masked));
+    EXPECT(same_posed_scene(S, masked));
     BuiltScene list_scene, one;
     EXPECT(build_scene(inputs, mats, false, &list_scene).empty());
     EXPECT(!check_active_list(list_scene, listed.data(), n, &unsupported).empty() && unsupported);

@@ -1,24 +1,7 @@
 // Stand-alone check of instanced scenes and re-posing on the host side (pt_scene.cpp alone; tests/test_pt_instances_host.py builds
 // it with -fsanitize=address,undefined and runs it once): commit a scene with instances, compare it with the same scene made of
 // copies, repose it - good lists, refused lists, poses whose BVH<Object> build does not terminate -, commit again.
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-static Mat4 pose(float s, float x, float y, float z) {
-  Mat4 m = mat_identity();
-  m.c[0][0] = m.c[1][1] = m.c[2][2] = s;
-  m.c[3][0] = x; m.c[3][1] = y; m.c[3][2] = z;
-  return m;
-}
+#include "scene_main_common.h"
 
 // A grid of n x n quads over [0,1]^2 lifted into a shallow bowl: 2 n^2 triangles, enough for a BVH<Triangle> with interior nodes.
 static MeshInput bowl(int n) {
@@ -38,37 +21,6 @@ static MeshInput bowl(int n) {
       m.idx.insert(m.idx.end(), t, t + 6);
     }
   return m;
-}
-
-static bool same_tree(const HostBVH& a, const HostBVH& b) {
-  return a.nodes.size() == b.nodes.size() && a.prim == b.prim &&
-         (a.nodes.empty() || std::memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(HostNode)) == 0);
-}
-
-// Everything a kernel reads that does not depend on where a mesh is stored.
-static bool same_top(const FlatScene& a, const FlatScene& b) {
-  if (a.tlas_nodes != b.tlas_nodes || a.objects.size() != b.objects.size() || a.wave_tlas.size() != b.wave_tlas.size() ||
-      a.wave_lazy != b.wave_lazy || a.lazy_objects != b.lazy_objects || a.max_tlas_depth != b.max_tlas_depth)
-    return false;
-  if (a.tlas_nodes && std::memcmp(a.nodes.data(), b.nodes.data(), a.tlas_nodes * sizeof(Node)) != 0) return false;
-  if (!a.wave_tlas.empty() && std::memcmp(a.wave_tlas.data(), b.wave_tlas.data(), a.wave_tlas.size() * sizeof(WaveInterior)) != 0) return false;
-  for (size_t k = 0; k < a.objects.size(); k++) {
-    const Object &x = a.objects[k], &y = b.objects[k];
-    if (x.kind != y.kind || x.has_trans != y.has_trans || x.material != y.material || x.use_bvh != y.use_bvh || x.id != y.id ||
-        x.ntri != y.ntri || x.nnodes != y.nnodes || x.nrec != y.nrec || std::memcmp(&x.trans, &y.trans, 2 * sizeof(Mat4)) != 0)
-      return false;
-    // the ranges may lie elsewhere, their contents may not differ
-    for (uint32_t t = 0; t < x.ntri; t++)
-      if (std::memcmp(&a.tris[x.tri_base + t], &b.tris[y.tri_base + t], sizeof(Tri)) != 0 ||
-          std::memcmp(&a.tri_nrm[x.tri_base + t], &b.tri_nrm[y.tri_base + t], sizeof(TriNrm)) != 0 ||
-          std::memcmp(&a.tri_packed[9 * (size_t)(x.tri_base + t)], &b.tri_packed[9 * (size_t)(y.tri_base + t)], 9 * sizeof(float)) != 0)
-        return false;
-    for (uint32_t r = 0; r < x.nrec; r++)
-      if (std::memcmp(&a.blas_recs[x.rec_base + r], &b.blas_recs[y.rec_base + r], sizeof(WaveInterior)) != 0) return false;
-    for (uint32_t n = 0; n < x.nnodes; n++)
-      if (std::memcmp(&a.nodes[x.node_base + n], &b.nodes[y.node_base + n], sizeof(Node)) != 0) return false;
-  }
-  return true;
 }
 
 static std::vector<ObjectInput> scene(bool instanced, const std::vector<Mat4>& poses) {
@@ -91,10 +43,7 @@ static std::vector<ObjectInput> scene(bool instanced, const std::vector<Mat4>& p
 }
 
 int main() {
-  std::vector<Material> mats(2);
-  std::memset(mats.data(), 0, 2 * sizeof(Material));
-  mats[0].a[0] = mats[0].a[1] = mats[0].a[2] = 0.5f;
-  mats[1].type = 3; mats[1].a[0] = mats[1].a[1] = mats[1].a[2] = 5.0f;
+  const std::vector<Material> mats = two_materials();
   std::vector<Mat4> poses;
   for (int k = 0; k < 24; k++) poses.push_back(pose(0.1f + 0.01f * (k % 5), 0.37f * k - 3.0f, 0.11f * ((k * 7) % 9), 0.53f * ((k * 5) % 11) - 2.0f));
   poses[0] = mat_identity();                         // the source itself has no transform
@@ -103,7 +52,7 @@ int main() {
     BuiltScene S, C;
     EXPECT(build_scene(scene(true, poses), mats, use_bvh != 0, &S).empty());
     EXPECT(build_scene(scene(false, poses), mats, use_bvh != 0, &C).empty());
-    EXPECT(same_top(S.flat, C.flat) && same_tree(S.tlas, C.tlas));
+    EXPECT(same_contents(S.flat, C.flat) && same_tree(S.tlas, C.tlas));
     EXPECT(C.flat.tris.size() - S.flat.tris.size() == 23u * 72u);
     EXPECT(S.blas_builds + 23 * (uint64_t)use_bvh == C.blas_builds);
 
@@ -116,7 +65,7 @@ int main() {
     EXPECT(!prepare_repose(S, light_idx, &T1, 1, &top, &bad).empty() && bad);
     EXPECT(!prepare_repose(S, twice, two, 2, &top, &bad).empty() && bad);
     EXPECT(!prepare_repose(S, beyond, &T1, 1, &top, &bad).empty() && bad);
-    EXPECT(same_top(S.flat, C.flat));
+    EXPECT(same_contents(S.flat, C.flat));
 
     // a good list: the source, a few instances, the sphere - against a fresh commit of the new poses
     std::vector<uint32_t> idx = {1, 4, 9, 17, 24, 25};
@@ -126,13 +75,13 @@ int main() {
     nt[0].c[1][1] = 0.4f;                              // the source: non-uniform scale
     for (size_t k = 0; k + 1 < idx.size(); k++) moved[idx[k] - 1] = nt[k];
     EXPECT(prepare_repose(S, idx.data(), nt.data(), (uint32_t)idx.size(), &top, &bad).empty() && !bad);
-    EXPECT(same_top(S.flat, C.flat));                 // prepared aside: nothing has changed yet
+    EXPECT(same_contents(S.flat, C.flat));                 // prepared aside: nothing has changed yet
     apply_repose(&S, &top);
     std::vector<ObjectInput> fresh_in = scene(false, moved);
     fresh_in.back().trans = nt.back();
     BuiltScene fresh;
     EXPECT(build_scene(fresh_in, mats, use_bvh != 0, &fresh).empty());
-    EXPECT(same_top(S.flat, fresh.flat) && same_tree(S.tlas, fresh.tlas));
+    EXPECT(same_contents(S.flat, fresh.flat) && same_tree(S.tlas, fresh.tlas));
     EXPECT(S.flat.tris.size() + 23u * 72u == fresh.flat.tris.size() && S.flat.light_tri_first + 23u * 72u == fresh.flat.light_tri_first);
 
     // two instances on one pose: BVH<Object>::build would never return; refused, the scene stays
@@ -141,7 +90,7 @@ int main() {
       const BuiltScene before = S;
       ReposedTop stuck;
       EXPECT(!prepare_repose(S, pair, two, 2, &stuck, &bad).empty() && !bad);
-      EXPECT(same_top(S.flat, before.flat) && same_tree(S.tlas, before.tlas));
+      EXPECT(same_contents(S.flat, before.flat) && same_tree(S.tlas, before.tlas));
     }
 
     // back to the first poses, then a second commit of the same inputs
@@ -151,10 +100,10 @@ int main() {
     ReposedTop again;
     EXPECT(prepare_repose(S, idx.data(), back.data(), (uint32_t)idx.size(), &again, &bad).empty());
     apply_repose(&S, &again);
-    EXPECT(same_top(S.flat, C.flat) && same_tree(S.tlas, C.tlas));
+    EXPECT(same_contents(S.flat, C.flat) && same_tree(S.tlas, C.tlas));
     BuiltScene S2;
     EXPECT(build_scene(S.inputs, mats, use_bvh != 0, &S2).empty());
-    EXPECT(same_top(S2.flat, C.flat) && same_tree(S2.tlas, C.tlas));
+    EXPECT(same_contents(S2.flat, C.flat) && same_tree(S2.tlas, C.tlas));
     // an instance of an instance, of a sphere, of something later: refused by build_scene as well
     std::vector<ObjectInput> bad_in = scene(true, poses);
     bad_in[5].source = 4;

@@ -2,51 +2,9 @@
 // -fsanitize=address,undefined and runs it once): commit a scene with an emissive sheet, an emissive sphere and a plain mesh,
 // repose the lights, update and refit the emissive sheet, make refused calls; after every step the light tables are compared
 // with a fresh build_scene of the same inputs.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-static Mat4 pose(float s, float x, float y, float z) {
-  Mat4 m = mat_identity();
-  m.c[0][0] = m.c[1][1] = m.c[2][2] = s;
-  m.c[3][0] = x; m.c[3][1] = y; m.c[3][2] = z;
-  return m;
-}
-
-// n x n quads over [0,1]^2 lifted by amp * a ripple of `waves` periods: 2 n^2 triangles
-static MeshInput sheet(int n, float amp, float waves) {
-  MeshInput m;
-  for (int j = 0; j <= n; j++)
-    for (int i = 0; i <= n; i++) {
-      const float x = (float)i / n, z = (float)j / n;
-      const float p[3] = {x, amp * std::sin(6.2831853f * waves * x) * std::cos(6.2831853f * waves * z), z};
-      const float nn[3] = {0.0f, 1.0f, 0.0f};
-      m.pos.insert(m.pos.end(), p, p + 3);
-      m.nrm.insert(m.nrm.end(), nn, nn + 3);
-    }
-  for (int j = 0; j < n; j++)
-    for (int i = 0; i < n; i++) {
-      const uint32_t a = (uint32_t)(j * (n + 1) + i), b = a + 1, c = a + (uint32_t)n + 1, d = c + 1;
-      const uint32_t t[6] = {a, c, b, b, c, d};
-      m.idx.insert(m.idx.end(), t, t + 6);
-    }
-  return m;
-}
-
-template <class V>
-static bool same_bytes(const V& a, const V& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
-}
+#include "scene_main_common.h"
 
 // The light tables and what a pose decides, wherever the light range starts.
 static bool same_lights(const BuiltScene& A, const BuiltScene& B) {
@@ -86,10 +44,7 @@ static bool build(const std::vector<ObjectInput>& in, const std::vector<Material
 }
 
 int main() {
-  std::vector<Material> mats(2);
-  std::memset(mats.data(), 0, 2 * sizeof(Material));
-  mats[0].a[0] = mats[0].a[1] = mats[0].a[2] = 0.5f;
-  mats[1].type = 3; mats[1].a[0] = mats[1].a[1] = mats[1].a[2] = 5.0f;
+  const std::vector<Material> mats = two_materials();
   const MeshInput E0 = sheet(5, 0.05f, 1.0f), E1 = sheet(5, 0.5f, 2.0f), E2 = sheet(5, 0.0f, 1.0f);
   const Mat4 L0 = pose(0.5f, 0.0f, 2.0f, 0.0f), S0 = pose(1.0f, -1.0f, 1.5f, 0.3f);
   Mat4 L1 = pose(0.8f, 0.3f, 1.7f, -0.2f);

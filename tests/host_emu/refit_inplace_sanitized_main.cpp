@@ -3,83 +3,9 @@
 // meshes with both trees kept, the identity with srt_pt_refit_mesh + srt_pt_repose_refit, inactive objects, supplied node boxes,
 // non-finite vertices taken and refused, every refusal; after every refit the links, orders, counts and tables of object order of
 // both trees are the committed ones and every box of the BVH<Object> is the fold it is defined as.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-static Mat4 pose(float s, float x, float y, float z) {
-  Mat4 m = mat_identity();
-  m.c[0][0] = m.c[1][1] = m.c[2][2] = s;
-  m.c[3][0] = x; m.c[3][1] = y; m.c[3][2] = z;
-  return m;
-}
-
-// n x n quads over [0,1]^2 lifted by amp * a ripple of `waves` periods
-static MeshInput sheet(int n, float amp, float waves) {
-  MeshInput m;
-  for (int j = 0; j <= n; j++)
-    for (int i = 0; i <= n; i++) {
-      const float x = (float)i / n, z = (float)j / n;
-      const float p[3] = {x, amp * std::sin(6.2831853f * waves * x) * std::cos(6.2831853f * waves * z), z};
-      const float nn[3] = {0.0f, 1.0f, 0.0f};
-      m.pos.insert(m.pos.end(), p, p + 3);
-      m.nrm.insert(m.nrm.end(), nn, nn + 3);
-    }
-  for (int j = 0; j < n; j++)
-    for (int i = 0; i < n; i++) {
-      const uint32_t a = (uint32_t)(j * (n + 1) + i), b = a + 1, c = a + (uint32_t)n + 1, d = c + 1;
-      const uint32_t t[6] = {a, c, b, b, c, d};
-      m.idx.insert(m.idx.end(), t, t + 6);
-    }
-  return m;
-}
-
-// 0: an area light; 1: sheet A; 2: sheet B; 3, 4: instances of A; 5: an instance of B; 6: a sphere
-static std::vector<ObjectInput> scene(const MeshInput& A, const MeshInput& B) {
-  std::vector<ObjectInput> in;
-  ObjectInput light;
-  light.trans = pose(0.5f, 0.0f, 2.0f, 0.0f);
-  light.material = 1; light.is_light = true; light.mesh = sheet(1, 0.0f, 1.0f);
-  in.push_back(light);
-  ObjectInput a; a.trans = mat_identity(); a.mesh = A; in.push_back(a);
-  ObjectInput b; b.trans = pose(0.7f, 1.5f, 0.2f, -0.4f); b.mesh = B; in.push_back(b);
-  ObjectInput i1; i1.trans = pose(0.3f, -1.0f, 0.5f, 0.8f); i1.source = 1; in.push_back(i1);
-  ObjectInput i2; i2.trans = pose(0.6f, 0.2f, -1.1f, 1.9f); i2.source = 1; in.push_back(i2);
-  ObjectInput i3; i3.trans = pose(0.4f, -2.0f, 0.1f, -1.2f); i3.source = 2; in.push_back(i3);
-  ObjectInput s; s.kind = OBJ_SPHERE; s.radius = 0.2f; s.trans = pose(1.0f, -1.0f, 1.5f, 0.3f); in.push_back(s);
-  return in;
-}
-
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
-
-// Byte for byte: host trees, inputs and every flattened array.
-static bool identical(const BuiltScene& A, const BuiltScene& B) {
-  const FlatScene &a = A.flat, &b = B.flat;
-  if (!same_bytes(a.nodes, b.nodes) || !same_bytes(a.tris, b.tris) || !same_bytes(a.tri_nrm, b.tri_nrm) || a.tri_packed != b.tri_packed ||
-      !same_bytes(a.objects, b.objects) || !same_bytes(a.wave_tlas, b.wave_tlas) || !same_bytes(a.blas_recs, b.blas_recs) || a.wave_lazy != b.wave_lazy ||
-      a.lazy_objects != b.lazy_objects || a.tlas_nodes != b.tlas_nodes || a.max_tlas_depth != b.max_tlas_depth || a.max_blas_depth != b.max_blas_depth)
-    return false;
-  if (A.local_boxes != B.local_boxes || !same_bytes(A.tlas.nodes, B.tlas.nodes) || A.tlas.prim != B.tlas.prim || A.blas.size() != B.blas.size() || A.active != B.active)
-    return false;
-  for (size_t i = 0; i < A.blas.size(); i++)
-    if (!same_bytes(A.blas[i].nodes, B.blas[i].nodes) || A.blas[i].prim != B.blas[i].prim || A.inputs[i].mesh.pos != B.inputs[i].mesh.pos ||
-        A.inputs[i].mesh.nrm != B.inputs[i].mesh.nrm)
-      return false;
-  return true;
-}
+#include "scene_main_common.h"
 
 static bool inplace(BuiltScene* S, uint32_t object, const MeshInput& m, const float* boxes = nullptr, bool refuse = true) {
   MeshRefit R;
@@ -115,10 +41,7 @@ static void check_top(const BuiltScene& S, const BuiltScene& was) {
 }
 
 int main() {
-  std::vector<Material> mats(2);
-  std::memset(mats.data(), 0, 2 * sizeof(Material));
-  mats[0].a[0] = mats[0].a[1] = mats[0].a[2] = 0.5f;
-  mats[1].type = 3; mats[1].a[0] = mats[1].a[1] = mats[1].a[2] = 5.0f;
+  const std::vector<Material> mats = two_materials();
   const MeshInput A0 = sheet(7, 0.05f, 1.0f), A1 = sheet(7, 0.6f, 2.5f), B0 = sheet(5, 0.1f, 1.5f), B1 = sheet(5, 0.9f, 0.5f);
 
   BuiltScene S, first;

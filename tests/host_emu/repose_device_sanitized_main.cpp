@@ -2,44 +2,7 @@
 // with -fsanitize=address,undefined and runs it once): prepare_repose_supplied - the per-object values supplied by the caller
 // instead of computed - against prepare_repose on the scene and the list of the file given as argv[1], with the posed boxes and
 // with a tree built beforehand, in a scene with BVHs and in a list scene; and refused lists, which leave the scene alone.
-//
-// File (little endian, 32-bit words): nmat, then per material {type, a[3], b[3], ior}; nobj, then per object {kind (0 mesh,
-// 1 sphere, 2 instance), is_light, material, source, radius, T[16], nverts, nidx, pos[3 nverts], nrm[3 nverts], idx[nidx]};
-// n, then n insertion indices and n transforms of 16 floats.
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-struct Reader {
-  std::vector<unsigned char> bytes;
-  size_t at = 0;
-  bool ok = true;
-  void read(void* dst, size_t n) {
-    if (at + n > bytes.size()) { ok = false; std::memset(dst, 0, n); return; }
-    std::memcpy(dst, bytes.data() + at, n);
-    at += n;
-  }
-  uint32_t u32() { uint32_t v; read(&v, 4); return v; }
-  float f32() { float v; read(&v, 4); return v; }
-  template <class T> void array(std::vector<T>* v, size_t n) {
-    if (at + n * sizeof(T) > bytes.size()) { ok = false; return; }
-    v->resize(n);
-    if (n) read(v->data(), n * sizeof(T));
-  }
-};
-
-template <class V>
-static bool same_bytes(const V& a, const V& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
-}
+#include "scene_main_common.h"
 
 static bool same_top(const ReposedTop& a, const ReposedTop& b) {
   return a.listed == b.listed && same_bytes(a.trans, b.trans) && same_bytes(a.tlas.nodes, b.tlas.nodes) && a.tlas.prim == b.tlas.prim &&
@@ -47,54 +10,15 @@ static bool same_top(const ReposedTop& a, const ReposedTop& b) {
          a.wave_lazy == b.wave_lazy && a.lazy_objects == b.lazy_objects && same_bytes(a.objects, b.objects);
 }
 
-static bool same_scene(const BuiltScene& a, const BuiltScene& b) {
-  if (a.inputs.size() != b.inputs.size()) return false;
-  for (size_t i = 0; i < a.inputs.size(); i++)
-    if (std::memcmp(&a.inputs[i].trans, &b.inputs[i].trans, sizeof(Mat4)) != 0) return false;
-  return same_bytes(a.flat.nodes, b.flat.nodes) && same_bytes(a.flat.objects, b.flat.objects) && same_bytes(a.flat.wave_tlas, b.flat.wave_tlas) &&
-         a.flat.wave_lazy == b.flat.wave_lazy && a.flat.lazy_objects == b.flat.lazy_objects && same_bytes(a.tlas.nodes, b.tlas.nodes) &&
-         a.tlas.prim == b.tlas.prim && a.flat.tlas_nodes == b.flat.tlas_nodes && a.flat.max_tlas_depth == b.flat.max_tlas_depth;
-}
-
 int main(int argc, char** argv) {
   if (argc < 2) { std::printf("usage: %s scene-file\n", argv[0]); return 2; }
-  Reader R;
-  if (FILE* f = std::fopen(argv[1], "rb")) {
-    unsigned char buf[65536];
-    size_t got;
-    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) R.bytes.insert(R.bytes.end(), buf, buf + got);
-    std::fclose(f);
-  }
-  std::vector<Material> mats(R.u32());
-  for (Material& m : mats) {
-    std::memset(&m, 0, sizeof m);
-    m.type = R.u32();
-    for (float& v : m.a) v = R.f32();
-    for (float& v : m.b) v = R.f32();
-    m.ior = R.f32();
-  }
-  std::vector<ObjectInput> inputs(R.ok ? R.u32() : 0);
-  for (ObjectInput& o : inputs) {
-    const uint32_t kind = R.u32();
-    o.kind = kind == 1u ? OBJ_SPHERE : OBJ_MESH;
-    o.is_light = R.u32() != 0u;
-    o.material = R.u32();
-    const uint32_t source = R.u32();
-    o.source = kind == 2u ? (int32_t)source : -1;
-    o.radius = R.f32();
-    R.read(&o.trans, sizeof(Mat4));
-    const uint32_t nverts = R.u32(), nidx = R.u32();
-    R.array(&o.mesh.pos, 3 * (size_t)nverts);
-    R.array(&o.mesh.nrm, 3 * (size_t)nverts);
-    R.array(&o.mesh.idx, nidx);
-    if (!R.ok) break;
-  }
-  const uint32_t n = R.ok ? R.u32() : 0;
+  std::vector<Material> mats;
+  std::vector<ObjectInput> inputs;
   std::vector<uint32_t> listed;
   std::vector<Mat4> moved;
-  R.array(&listed, n);
-  R.array(&moved, n);
-  if (!R.ok || R.at != R.bytes.size() || inputs.empty() || !n) { std::printf("cannot read %s\n", argv[1]); return 2; }
+  const bool read = load_scene_file(argv[1], &mats, &inputs, &listed, &moved);
+  const uint32_t n = (uint32_t)listed.size();
+  if (!read || inputs.empty() || !n) { std::printf("cannot read %s\n", argv[1]); return 2; }
   const uint32_t nobj = (uint32_t)inputs.size();
 
   for (int use_bvh = 1; use_bvh >= 0; use_bvh--) {
@@ -133,7 +57,7 @@ int main(int argc, char** argv) {
       EXPECT(!prepare_repose_supplied(S, listed.data(), n, P, &none, &bad).empty() && bad);
       P.boxes6 = boxes.data();
     }
-    EXPECT(same_scene(S, first));                        // preparing leaves the scene alone
+    EXPECT(same_posed_scene(S, first));                        // preparing leaves the scene alone
     // refused lists: a duplicate, out of range, an area light
     ReposedTop refused;
     std::vector<uint32_t> dup(listed);
@@ -150,7 +74,7 @@ int main(int argc, char** argv) {
         EXPECT(check_repose_list(S, light.data(), n) == prepare_repose(S, light.data(), moved.data(), n, &refused, &bad));
         break;
       }
-    EXPECT(same_scene(S, first));
+    EXPECT(same_posed_scene(S, first));
     // applied: the scene of a fresh build on the new poses, and of srt_pt_repose's path
     BuiltScene H = S, fresh;
     apply_repose(&S, &from_boxes);
@@ -158,7 +82,7 @@ int main(int argc, char** argv) {
     std::vector<ObjectInput> posed_inputs = inputs;
     for (uint32_t i = 0; i < nobj; i++) posed_inputs[i].trans = all[i];
     EXPECT(build_scene(posed_inputs, mats, use_bvh != 0, &fresh).empty());
-    EXPECT(same_scene(S, H) && same_scene(S, fresh));
+    EXPECT(same_posed_scene(S, H) && same_posed_scene(S, fresh));
     // and back, supplied again: the unlisted objects take their values from the records the first repose left
     std::vector<Mat4> home(n), home_inv(n);
     std::vector<uint32_t> home_has(n);
@@ -175,7 +99,7 @@ int main(int argc, char** argv) {
     ReposedTop back;
     EXPECT(prepare_repose_supplied(S, listed.data(), n, Q, &back, &bad).empty() && !bad);
     apply_repose(&S, &back);
-    EXPECT(same_scene(S, first));
+    EXPECT(same_posed_scene(S, first));
   }
   if (failures) return 1;
   std::printf("repose_device_sanitized: ok (%u objects, %u listed)\n", nobj, n);

@@ -1,59 +1,13 @@
 // Stand-alone check of srt_pt_repose_refit's scene layer (pt_scene.cpp alone; tests/test_pt_repose_refit_host.py builds it with
 // -fsanitize=address,undefined and runs it once) on the scene and the list of the file given as argv[1] (the format of
-// repose_device_sanitized_main.cpp): the definition - prepare_top_refit / apply_top_refit - and the settle path, which applies
+// scene_main_common.h:load_scene_file): the definition - prepare_top_refit / apply_top_refit - and the settle path, which applies
 // records and boxes that were computed elsewhere (here: copied out of a refitted scene, as srt_pt_repose_refit_device's
 // read-back delivers them), in a scene with BVHs and in a list scene.  After every refit the tree's links and order are the
 // committed ones, every box is the fold it is defined as, and the flattened nodes and sweep records say what the host tree says.
-//
-// File (little endian, 32-bit words): nmat, then per material {type, a[3], b[3], ior}; nobj, then per object {kind (0 mesh,
-// 1 sphere, 2 instance), is_light, material, source, radius, T[16], nverts, nidx, pos[3 nverts], nrm[3 nverts], idx[nidx]};
-// n, then n insertion indices and n transforms of 16 floats.
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-struct Reader {
-  std::vector<unsigned char> bytes;
-  size_t at = 0;
-  bool ok = true;
-  void read(void* dst, size_t n) {
-    if (at + n > bytes.size()) { ok = false; std::memset(dst, 0, n); return; }
-    std::memcpy(dst, bytes.data() + at, n);
-    at += n;
-  }
-  uint32_t u32() { uint32_t v; read(&v, 4); return v; }
-  float f32() { float v; read(&v, 4); return v; }
-  template <class T> void array(std::vector<T>* v, size_t n) {
-    if (at + n * sizeof(T) > bytes.size()) { ok = false; return; }
-    v->resize(n);
-    if (n) read(v->data(), n * sizeof(T));
-  }
-};
-
-template <class V>
-static bool same_bytes(const V& a, const V& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
-}
-
-static bool same_scene(const BuiltScene& a, const BuiltScene& b) {
-  if (a.inputs.size() != b.inputs.size()) return false;
-  for (size_t i = 0; i < a.inputs.size(); i++)
-    if (std::memcmp(&a.inputs[i].trans, &b.inputs[i].trans, sizeof(Mat4)) != 0) return false;
-  return same_bytes(a.flat.nodes, b.flat.nodes) && same_bytes(a.flat.objects, b.flat.objects) && same_bytes(a.flat.wave_tlas, b.flat.wave_tlas) &&
-         a.flat.wave_lazy == b.flat.wave_lazy && a.flat.lazy_objects == b.flat.lazy_objects && same_bytes(a.tlas.nodes, b.tlas.nodes) &&
-         a.tlas.prim == b.tlas.prim && a.flat.tlas_nodes == b.flat.tlas_nodes && a.flat.max_tlas_depth == b.flat.max_tlas_depth &&
-         same_bytes(a.flat.lights, b.flat.lights) && same_bytes(a.flat.light_tris, b.flat.light_tris);
-}
+#include "scene_main_common.h"
 
 // The refitted top of S against its definition: the transforms `all` of every object, the committed scene `was`.
 static void check_refitted(const BuiltScene& S, const std::vector<Mat4>& all, const BuiltScene& was) {
@@ -109,43 +63,13 @@ static void check_refitted(const BuiltScene& S, const std::vector<Mat4>& all, co
 
 int main(int argc, char** argv) {
   if (argc < 2) { std::printf("usage: %s scene-file\n", argv[0]); return 2; }
-  Reader R;
-  if (FILE* f = std::fopen(argv[1], "rb")) {
-    unsigned char buf[65536];
-    size_t got;
-    while ((got = std::fread(buf, 1, sizeof buf, f)) > 0) R.bytes.insert(R.bytes.end(), buf, buf + got);
-    std::fclose(f);
-  }
-  std::vector<Material> mats(R.u32());
-  for (Material& m : mats) {
-    std::memset(&m, 0, sizeof m);
-    m.type = R.u32();
-    for (float& v : m.a) v = R.f32();
-    for (float& v : m.b) v = R.f32();
-    m.ior = R.f32();
-  }
-  std::vector<ObjectInput> inputs(R.ok ? R.u32() : 0);
-  for (ObjectInput& o : inputs) {
-    const uint32_t kind = R.u32();
-    o.kind = kind == 1u ? OBJ_SPHERE : OBJ_MESH;
-    o.is_light = R.u32() != 0u;
-    o.material = R.u32();
-    const uint32_t source = R.u32();
-    o.source = kind == 2u ? (int32_t)source : -1;
-    o.radius = R.f32();
-    R.read(&o.trans, sizeof(Mat4));
-    const uint32_t nverts = R.u32(), nidx = R.u32();
-    R.array(&o.mesh.pos, 3 * (size_t)nverts);
-    R.array(&o.mesh.nrm, 3 * (size_t)nverts);
-    R.array(&o.mesh.idx, nidx);
-    if (!R.ok) break;
-  }
-  const uint32_t n = R.ok ? R.u32() : 0;
+  std::vector<Material> mats;
+  std::vector<ObjectInput> inputs;
   std::vector<uint32_t> listed;
   std::vector<Mat4> moved;
-  R.array(&listed, n);
-  R.array(&moved, n);
-  if (!R.ok || R.at != R.bytes.size() || inputs.empty() || !n) { std::printf("cannot read %s\n", argv[1]); return 2; }
+  const bool read = load_scene_file(argv[1], &mats, &inputs, &listed, &moved);
+  const uint32_t n = (uint32_t)listed.size();
+  if (!read || inputs.empty() || !n) { std::printf("cannot read %s\n", argv[1]); return 2; }
   const uint32_t nobj = (uint32_t)inputs.size();
 
 
@@ -162,9 +86,9 @@ int main(int argc, char** argv) {
     for (uint32_t k = 0; k < n; k++) same[k] = inputs[listed[k]].trans;
     TopRefit R;
     EXPECT(prepare_top_refit(S, listed.data(), same.data(), n, &R).empty());
-    EXPECT(same_scene(S, first));                        // preparing leaves the scene alone
+    EXPECT(same_posed_scene(S, first));                        // preparing leaves the scene alone
     apply_top_refit(&S, &R);
-    EXPECT(same_scene(S, first));
+    EXPECT(same_posed_scene(S, first));
     // the new poses
     EXPECT(prepare_top_refit(S, listed.data(), moved.data(), n, &R).empty());
     EXPECT(R.boxes.size() == (use_bvh ? 6 * S.tlas.nodes.size() : 0));
@@ -190,7 +114,7 @@ int main(int argc, char** argv) {
       if (use_bvh)
         for (const HostNode& h : S.tlas.nodes) { Q.boxes.insert(Q.boxes.end(), h.mn, h.mn + 3); Q.boxes.insert(Q.boxes.end(), h.mx, h.mx + 3); }
       apply_top_refit(&L, &Q);
-      EXPECT(same_scene(L, S));
+      EXPECT(same_posed_scene(L, S));
     }
     // a rebuild of the same poses is a fresh build's; refitting the rebuilt tree with its own poses changes nothing
     {
@@ -203,16 +127,16 @@ int main(int argc, char** argv) {
       for (uint32_t i = 0; i < nobj; i++) posed_inputs[i].trans = all[i];
       fresh.dynamic_lights = true;
       EXPECT(build_scene(posed_inputs, mats, use_bvh != 0, &fresh).empty());
-      EXPECT(same_scene(B, fresh));
+      EXPECT(same_posed_scene(B, fresh));
       EXPECT(prepare_top_refit(B, listed.data(), moved.data(), n, &R).empty());
       apply_top_refit(&B, &R);
-      EXPECT(same_scene(B, fresh));
+      EXPECT(same_posed_scene(B, fresh));
       if (use_bvh) EXPECT(tree_cost(B.tlas) == tree_cost(fresh.tlas));
     }
     // and home again
     EXPECT(prepare_top_refit(S, listed.data(), same.data(), n, &R).empty());
     apply_top_refit(&S, &R);
-    EXPECT(same_scene(S, first));
+    EXPECT(same_posed_scene(S, first));
     // refused lists leave the scene alone: a duplicate, out of range, an area light without the switch
     const BuiltScene before = S;
     std::vector<uint32_t> dup(listed);
@@ -230,7 +154,7 @@ int main(int argc, char** argv) {
         break;
       }
     S.dynamic_lights = true;
-    EXPECT(same_scene(S, before));
+    EXPECT(same_posed_scene(S, before));
     // non-finite matrices are not refused: the scene takes what the definition computes
     {
       BuiltScene C = S;

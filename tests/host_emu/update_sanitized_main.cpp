@@ -2,94 +2,17 @@
 // -fsanitize=address,undefined and runs it once): commit a scene with two meshes and instances, update one mesh - more nodes,
 // fewer nodes, the same -, repose, update the other, refused updates, and back; after every step the scene is compared with a
 // fresh build_scene of the same inputs.
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "pt_scene.h"
-
-using namespace srt;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); failures++; } } while (0)
-
-static Mat4 pose(float s, float x, float y, float z) {
-  Mat4 m = mat_identity();
-  m.c[0][0] = m.c[1][1] = m.c[2][2] = s;
-  m.c[3][0] = x; m.c[3][1] = y; m.c[3][2] = z;
-  return m;
-}
-
-// n x n quads over [0,1]^2 lifted by amp * a ripple of `waves` periods: 2 n^2 triangles whose tree depends on amp and waves.
-static MeshInput sheet(int n, float amp, float waves) {
-  MeshInput m;
-  for (int j = 0; j <= n; j++)
-    for (int i = 0; i <= n; i++) {
-      const float x = (float)i / n, z = (float)j / n;
-      const float p[3] = {x, amp * std::sin(6.2831853f * waves * x) * std::cos(6.2831853f * waves * z), z};
-      const float nn[3] = {0.0f, 1.0f, 0.0f};
-      m.pos.insert(m.pos.end(), p, p + 3);
-      m.nrm.insert(m.nrm.end(), nn, nn + 3);
-    }
-  for (int j = 0; j < n; j++)
-    for (int i = 0; i < n; i++) {
-      const uint32_t a = (uint32_t)(j * (n + 1) + i), b = a + 1, c = a + (uint32_t)n + 1, d = c + 1;
-      const uint32_t t[6] = {a, c, b, b, c, d};
-      m.idx.insert(m.idx.end(), t, t + 6);
-    }
-  return m;
-}
-
-static bool same_tree(const HostBVH& a, const HostBVH& b) {
-  return a.nodes.size() == b.nodes.size() && a.prim == b.prim &&
-         (a.nodes.empty() || std::memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(HostNode)) == 0);
-}
+#include "scene_main_common.h"
 
 // Everything a kernel reads, wherever a mesh is stored.
 static bool same_scene(const BuiltScene& A, const BuiltScene& B) {
   const FlatScene &a = A.flat, &b = B.flat;
-  if (a.tlas_nodes != b.tlas_nodes || a.objects.size() != b.objects.size() || a.wave_tlas.size() != b.wave_tlas.size() || a.wave_lazy != b.wave_lazy ||
-      a.lazy_objects != b.lazy_objects || a.max_tlas_depth != b.max_tlas_depth || a.max_blas_depth != b.max_blas_depth || a.nodes.size() != b.nodes.size() ||
-      a.blas_recs.size() != b.blas_recs.size() || a.tris.size() != b.tris.size() || A.local_boxes != B.local_boxes || !same_tree(A.tlas, B.tlas))
+  if (a.max_blas_depth != b.max_blas_depth || a.nodes.size() != b.nodes.size() || a.blas_recs.size() != b.blas_recs.size() || a.tris.size() != b.tris.size() ||
+      A.local_boxes != B.local_boxes || !same_tree(A.tlas, B.tlas))
     return false;
   for (size_t i = 0; i < A.blas.size(); i++)
     if (!same_tree(A.blas[i], B.blas[i])) return false;
-  if (a.tlas_nodes && std::memcmp(a.nodes.data(), b.nodes.data(), a.tlas_nodes * sizeof(Node)) != 0) return false;
-  if (!a.wave_tlas.empty() && std::memcmp(a.wave_tlas.data(), b.wave_tlas.data(), a.wave_tlas.size() * sizeof(WaveInterior)) != 0) return false;
-  for (size_t k = 0; k < a.objects.size(); k++) {
-    const Object &x = a.objects[k], &y = b.objects[k];
-    if (x.kind != y.kind || x.has_trans != y.has_trans || x.material != y.material || x.use_bvh != y.use_bvh || x.id != y.id || x.ntri != y.ntri ||
-        x.nnodes != y.nnodes || x.nrec != y.nrec || std::memcmp(&x.trans, &y.trans, 2 * sizeof(Mat4)) != 0)
-      return false;
-    for (uint32_t t = 0; t < x.ntri; t++)
-      if (std::memcmp(&a.tris[x.tri_base + t], &b.tris[y.tri_base + t], sizeof(Tri)) != 0 ||
-          std::memcmp(&a.tri_nrm[x.tri_base + t], &b.tri_nrm[y.tri_base + t], sizeof(TriNrm)) != 0 ||
-          std::memcmp(&a.tri_packed[9 * (size_t)(x.tri_base + t)], &b.tri_packed[9 * (size_t)(y.tri_base + t)], 9 * sizeof(float)) != 0)
-        return false;
-    for (uint32_t r = 0; r < x.nrec; r++)
-      if (std::memcmp(&a.blas_recs[x.rec_base + r], &b.blas_recs[y.rec_base + r], sizeof(WaveInterior)) != 0) return false;
-    for (uint32_t n = 0; n < x.nnodes; n++)
-      if (std::memcmp(&a.nodes[x.node_base + n], &b.nodes[y.node_base + n], sizeof(Node)) != 0) return false;
-  }
-  return true;
-}
-
-// 0: an area light; 1: sheet A; 2: sheet B; 3, 4: instances of A; 5: an instance of B; 6: a sphere
-static std::vector<ObjectInput> scene(const MeshInput& A, const MeshInput& B) {
-  std::vector<ObjectInput> in;
-  ObjectInput light;
-  light.trans = pose(0.5f, 0.0f, 2.0f, 0.0f);
-  light.material = 1; light.is_light = true; light.mesh = sheet(1, 0.0f, 1.0f);
-  in.push_back(light);
-  ObjectInput a; a.trans = mat_identity(); a.mesh = A; in.push_back(a);
-  ObjectInput b; b.trans = pose(0.7f, 1.5f, 0.2f, -0.4f); b.mesh = B; in.push_back(b);
-  ObjectInput i1; i1.trans = pose(0.3f, -1.0f, 0.5f, 0.8f); i1.source = 1; in.push_back(i1);
-  ObjectInput i2; i2.trans = pose(0.6f, 0.2f, -1.1f, 1.9f); i2.source = 1; in.push_back(i2);
-  ObjectInput i3; i3.trans = pose(0.4f, -2.0f, 0.1f, -1.2f); i3.source = 2; in.push_back(i3);
-  ObjectInput s; s.kind = OBJ_SPHERE; s.radius = 0.2f; s.trans = pose(1.0f, -1.0f, 1.5f, 0.3f); in.push_back(s);
-  return in;
+  return same_contents(a, b);
 }
 
 static bool update(BuiltScene* S, uint32_t object, const MeshInput& m, bool* bad) {
@@ -101,10 +24,7 @@ static bool update(BuiltScene* S, uint32_t object, const MeshInput& m, bool* bad
 }
 
 int main() {
-  std::vector<Material> mats(2);
-  std::memset(mats.data(), 0, 2 * sizeof(Material));
-  mats[0].a[0] = mats[0].a[1] = mats[0].a[2] = 0.5f;
-  mats[1].type = 3; mats[1].a[0] = mats[1].a[1] = mats[1].a[2] = 5.0f;
+  const std::vector<Material> mats = two_materials();
   const MeshInput A0 = sheet(7, 0.05f, 1.0f), A1 = sheet(7, 0.6f, 2.5f), A2 = sheet(7, 0.0f, 1.0f), B0 = sheet(5, 0.1f, 1.5f), B1 = sheet(5, 0.9f, 0.5f);
 
   for (int use_bvh = 1; use_bvh >= 0; use_bvh--) {

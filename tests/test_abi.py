@@ -78,3 +78,12 @@ def test_product_does_not_reference_the_oracle():
             if f.endswith((".py", ".hip", ".cpp", ".h", ".c", "Makefile")):
                 text = open(os.path.join(root, f), errors="replace").read()
                 assert "liboracle" not in text and "oracle/" not in text and "_ref/" not in text, os.path.join(root, f)
+
+
+def test_scene_layer_sources_are_listed_in_both_builds():
+    """Every csrc/pt_scene*.cpp is in csrc/Makefile's SRCS (the product) and in _harness.SCENE_LAYER_SRCS (what the host tests link)."""
+    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
+    present = sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, "pt_scene*.cpp")))
+    srcs = re.search(r"^SRCS\s*:=(.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()
+    assert present and sorted(f for f in srcs if f.startswith("pt_scene")) == present
+    assert sorted(os.path.basename(p) for p in H.SCENE_LAYER_SRCS) == present and all(os.path.dirname(p) == csrc for p in H.SCENE_LAYER_SRCS)

@@ -4,7 +4,6 @@ the ABI on a host-only context, against a numpy restatement of the masked boxes;
 that rebuild or refit the BVH<Object>; refusals; and a sanitized stand-alone program over the definition and the settle bookkeeping.
 (What needs a device even in its host form - srt_pt_particles_step, srt_pt_hit, the skins - is in test_pt_active_gpu.py.)"""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -260,11 +259,4 @@ def test_sanitized_definition_and_settle(tmp_path, particles):
     idx, Ts = IC.repose_case(S)
     scene_file = str(tmp_path / "particles.scene")
     RDC.write_scene_file(scene_file, S, idx, Ts)
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    exe = str(tmp_path / "active_sanitized")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                    "-I" + csrc, os.path.join(H.ROOT, "tests", "host_emu", "active_sanitized_main.cpp"), os.path.join(csrc, "pt_scene.cpp"),
-                    "-o", exe], check=True)
-    r = subprocess.run([exe, scene_file], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "active_sanitized: ok (74 objects, 12 listed)" in r.stdout
+    H.run_sanitized_main(tmp_path, "active_sanitized_main.cpp", args=[scene_file], expect="active_sanitized: ok (74 objects, 12 listed)")

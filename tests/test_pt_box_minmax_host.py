@@ -9,24 +9,14 @@ must refuse a zero, infinite or NaN reciprocal, a non-finite origin, a non-finit
 
 sweep_flag_slot_main.cpp: the flag nibble through the slot word that is dead between the sweeps (csrc/pt_wave.h), all sixteen nibbles
 at every node of trees with 2 to 16 leaves against the 64-bit word, in the kernel's order of reads and writes."""
-import os
-import subprocess
-
 import _harness as H
 
 
 def _build_and_run(tmp_path, name, ok_line):
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    exe = str(tmp_path / name)
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I" + emu,
-                    "-I" + csrc,
-                    "-I" + os.path.join(H.ROOT, "include"), os.path.join(emu, name + "_main.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
-    assert ok_line in r.stdout
-    return r.stdout
+    out = H.run_sanitized_main(tmp_path, name + "_main.cpp", scene_layer=False, expect=ok_line, flags=("-O2",),      # (as the product build: no sanitizer)
+                               extra=("-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas"))
+    print(out)
+    return out
 
 
 def test_box_minmax_equals_box_hit_inv_inside_the_guard(tmp_path):

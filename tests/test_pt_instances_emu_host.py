@@ -3,8 +3,6 @@ whose objects share triangle and BVH<Triangle> ranges (srt_pt_add_instance).  S 
 hit flag, distance bits and object slot of every ray must agree; the triangle index is a storage address and may differ, so it
 is compared relative to the object's first triangle through the oracle's hit record instead (position, normal, material)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,16 +13,7 @@ from _cases import random_rays, unnormalised_rays
 
 
 def emu_lib():
-    out = os.path.join(H.ORACLE_DIR, "_build", "libinstances_flat_host.so")
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    srcs = [os.path.join(emu, "instances_flat_host.cpp"), os.path.join(csrc, "pt_scene.cpp")]
-    deps = srcs + [os.path.join(emu, "flat_host.cpp")] + [os.path.join(csrc, f) for f in ("pt_flat.h", "pt_trace.h", "pt_device.h", "pt_scene.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc,
-                        "-I" + os.path.join(H.ROOT, "include"), *srcs, "-o", out], check=True)
-    lib = ctypes.CDLL(out)
+    lib = ctypes.CDLL(H.build_host_lib("instances_flat_host", ["instances_flat_host.cpp"], scene_layer=True))
     lib.emu_create.restype = ctypes.c_void_p
     return lib
 

@@ -1,8 +1,6 @@
 """CPU: instanced meshes (srt_pt_add_instance), re-posing a committed scene (srt_pt_repose) and srt_pt_scene_counts on a
 host-only context.  S has instances, S' = expand(S) has srt_pt_add_mesh of the source's arrays in their place: both must dump
 the same trees as each other and as the oracle's build of S' (the oracle knows nothing of instances); only storage differs."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -244,12 +242,4 @@ def test_sanitized_commit_repose_commit(tmp_path):
     """tests/host_emu/instances_sanitized_main.cpp - a stand-alone program over pt_scene.cpp alone: commit a scene with instances,
     repose it (a good list, refused lists, a build that does not terminate), commit again - built with AddressSanitizer and
     UndefinedBehaviorSanitizer and run once on the CPU."""
-    root = H.ROOT
-    csrc = os.path.join(root, "soft-rendering-toolsets_amd", "csrc")
-    exe = str(tmp_path / "instances_sanitized")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                    "-I" + csrc, os.path.join(root, "tests", "host_emu", "instances_sanitized_main.cpp"), os.path.join(csrc, "pt_scene.cpp"),
-                    "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "instances_sanitized: ok" in r.stdout
+    H.run_sanitized_main(tmp_path, "instances_sanitized_main.cpp")

@@ -14,7 +14,6 @@ import ctypes
 import glob
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -68,16 +67,7 @@ class _EmuNormals(H.EmuPT):
     """normal_sample() of csrc/pt_trace.h compiled for the host (tests/host_emu/normals_host.cpp), one lane at a time."""
 
     def __init__(self, scene, use_bvh):
-        out = os.path.join(H.ORACLE_DIR, "_build", "libnormals_host.so")
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        emu = os.path.join(H.ROOT, "tests", "host_emu")
-        srcs = [os.path.join(emu, "normals_host.cpp"), os.path.join(csrc, "pt_scene.cpp")]
-        deps = srcs + [os.path.join(emu, "flat_host.cpp")] + [os.path.join(csrc, f) for f in ("pt_flat.h", "pt_trace.h", "pt_device.h", "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + emu, "-I" + csrc,
-                            "-I" + os.path.join(H.ROOT, "include"), *srcs, "-o", out], check=True)
-        self.lib = ctypes.CDLL(out)
+        self.lib = ctypes.CDLL(H.build_host_lib("normals_host", ["normals_host.cpp"], scene_layer=True))
         self.lib.emu_create.restype = ctypes.c_void_p
         self.h_ = ctypes.c_void_p(self.lib.emu_create())
         self.use_bvh = use_bvh
@@ -147,15 +137,10 @@ def test_abi_declares_exports_and_binds_the_switch(lib):
 
 def _normals_driver():
     """tests/host_emu/pt_core_normals_driver.cpp + host/pathtracer_core.cpp, built with g++ against the driver's own stand-in ABI."""
-    out = os.path.join(H.ORACLE_DIR, "_build", "libpt_core_normals_driver.so")
     host = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "host")
-    srcs = [os.path.join(H.ROOT, "tests", "host_emu", "pt_core_normals_driver.cpp"), os.path.join(host, "pathtracer_core.cpp")]
-    deps = srcs + [os.path.join(host, "pathtracer_core.h"), os.path.join(H.ROOT, "include", "srt_pt.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__", "-I" + host, "-I" + os.path.join(H.ROOT, "include"),
-                        "-I/opt/rocm/include", *srcs, "-L/opt/rocm/lib", "-lamdhip64", "-lpthread", "-Wl,-Bsymbolic", "-Wl,-rpath,/opt/rocm/lib",
-                        "-o", out], check=True)
+    out = H.build_host_lib("pt_core_normals_driver", ["pt_core_normals_driver.cpp", os.path.join(host, "pathtracer_core.cpp")], device_headers=False,
+                           extra=("-O1", "-D__HIP_PLATFORM_AMD__", "-I" + host, "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread",
+                                  "-Wl,-Bsymbolic", "-Wl,-rpath,/opt/rocm/lib"))
     d = ctypes.CDLL(out)
     d.normals_driver_run.restype = ctypes.c_size_t
     d.normals_driver_run.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_char_p, ctypes.c_size_t]

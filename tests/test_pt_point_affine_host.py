@@ -4,8 +4,6 @@ the plain projective product mat_point, bit for bit, one lane at a time: affine 
 perspective row, points with inf and NaN, points that overflow the first row only, 0 * inf in the first row.  The wave-wide form
 (one bad lane sends its whole wave through w) is the GPU test's: tests/test_pt_point_affine_gpu.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -18,15 +16,7 @@ _lib = None
 def _host():
     global _lib
     if _lib is None:
-        out = os.path.join(H.ORACLE_DIR, "_build", "libpoint_affine_host.so")
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        src = os.path.join(H.ROOT, "tests", "host_emu", "point_affine_host.cpp")
-        deps = [src, os.path.join(csrc, "pt_device.h"), os.path.join(csrc, "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(H.ROOT, "tests", "host_emu"),
-                            "-I" + csrc, "-I" + os.path.join(H.ROOT, "include"), src, "-o", out], check=True)
-        _lib = ctypes.CDLL(out)
+        _lib = ctypes.CDLL(H.build_host_lib("point_affine_host", ["point_affine_host.cpp"]))
     return _lib
 
 

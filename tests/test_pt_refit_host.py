@@ -4,7 +4,6 @@ keeps links and primitive order and gives every node the exact min / max fold of
 checks with ==; refusals leave every dump and count as they were; and a sanitized stand-alone program runs the same layer."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -284,12 +283,4 @@ def test_mesh_tree_cost(srt, scenes):
 def test_sanitized_refit(tmp_path):
     """tests/host_emu/refit_sanitized_main.cpp - a stand-alone program over pt_scene.cpp alone: refits, a repose, an update, the
     refusals - built with AddressSanitizer and UndefinedBehaviorSanitizer and run once on the CPU."""
-    root = H.ROOT
-    csrc = os.path.join(root, "soft-rendering-toolsets_amd", "csrc")
-    exe = str(tmp_path / "refit_sanitized")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                    "-I" + csrc, os.path.join(root, "tests", "host_emu", "refit_sanitized_main.cpp"), os.path.join(csrc, "pt_scene.cpp"),
-                    "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "refit_sanitized: ok" in r.stdout
+    H.run_sanitized_main(tmp_path, "refit_sanitized_main.cpp")

@@ -6,7 +6,6 @@ scene; refusals leave every dump and count as they were; the emulation's closest
 sanitized stand-alone program runs the same layer."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -311,12 +310,4 @@ def test_closest_hits_equal_the_oracle(scenes, which):
 def test_sanitized_refit_inplace(tmp_path):
     """tests/host_emu/refit_inplace_sanitized_main.cpp - a stand-alone program over pt_scene.cpp alone - built with AddressSanitizer
     and UndefinedBehaviorSanitizer and run once on the CPU."""
-    root = H.ROOT
-    csrc = os.path.join(root, "soft-rendering-toolsets_amd", "csrc")
-    exe = str(tmp_path / "refit_inplace_sanitized")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                    "-I" + csrc, os.path.join(root, "tests", "host_emu", "refit_inplace_sanitized_main.cpp"), os.path.join(csrc, "pt_scene.cpp"),
-                    "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "refit_inplace_sanitized: ok" in r.stdout
+    H.run_sanitized_main(tmp_path, "refit_inplace_sanitized_main.cpp")

@@ -4,7 +4,6 @@ the ABI on a host-only context; and a sanitized stand-alone program over prepare
 the per-object values supplied by the caller."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -127,12 +126,4 @@ def test_sanitized_supplied_repose(tmp_path):
     assert len(S["objects"]) == 74 and len(idx) == 12
     scene_file = str(tmp_path / "particles.scene")
     RC.write_scene_file(scene_file, S, idx, Ts)
-    root = H.ROOT
-    csrc = os.path.join(root, "soft-rendering-toolsets_amd", "csrc")
-    exe = str(tmp_path / "repose_device_sanitized")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                    "-I" + csrc, os.path.join(root, "tests", "host_emu", "repose_device_sanitized_main.cpp"), os.path.join(csrc, "pt_scene.cpp"),
-                    "-o", exe], check=True)
-    r = subprocess.run([exe, scene_file], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "repose_device_sanitized: ok (74 objects, 12 listed)" in r.stdout
+    H.run_sanitized_main(tmp_path, "repose_device_sanitized_main.cpp", args=[scene_file], expect="repose_device_sanitized: ok (74 objects, 12 listed)")

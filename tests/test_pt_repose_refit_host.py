@@ -4,7 +4,6 @@ build must agree; the emulation of a refitted scene (tests/host_emu/repose_refit
 hits on a fresh commit of the same poses; refusals; and a sanitized stand-alone program over the definition and the settle path."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -250,11 +249,4 @@ def test_sanitized_definition_and_settle(tmp_path, particles):
     S, idx, Ts = particles["S"], particles["idx"], particles["Ts"]
     scene_file = str(tmp_path / "particles.scene")
     RDC.write_scene_file(scene_file, S, idx, Ts)
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    exe = str(tmp_path / "repose_refit_sanitized")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
-                    "-I" + csrc, os.path.join(H.ROOT, "tests", "host_emu", "repose_refit_sanitized_main.cpp"), os.path.join(csrc, "pt_scene.cpp"),
-                    "-o", exe], check=True)
-    r = subprocess.run([exe, scene_file], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "repose_refit_sanitized: ok (74 objects, 12 listed)" in r.stdout
+    H.run_sanitized_main(tmp_path, "repose_refit_sanitized_main.cpp", args=[scene_file], expect="repose_refit_sanitized: ok (74 objects, 12 listed)")

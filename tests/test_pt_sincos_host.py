@@ -6,7 +6,6 @@ neighbourhoods, the quadrant edges and the renderer's two ranges.  The double ->
 The HIP build of the same functions is checked by tests/test_pt_sincos_gpu.py."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -14,23 +13,12 @@ import _harness as H
 import _sincos_cases as SC
 
 _lib = None
-_CSRC = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-_SRC = os.path.join(H.ROOT, "tests", "host_emu", "sincos_host.cpp")
-
-
-def _compile(out, extra, shared):
-    deps = [_SRC, os.path.join(_CSRC, "pt_device.h"), os.path.join(_CSRC, "pt_scene.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", *extra, *(["-fPIC", "-shared"] if shared else []), "-pthread",
-                        "-I" + os.path.join(H.ROOT, "tests", "host_emu"), "-I" + _CSRC, "-I" + os.path.join(H.ROOT, "include"), _SRC, "-o", out], check=True)
-    return out
 
 
 def _host():
     global _lib
     if _lib is None:
-        _lib = ctypes.CDLL(_compile(os.path.join(H.ORACLE_DIR, "_build", "libsincos_host.so"), ["-O2"], True))
+        _lib = ctypes.CDLL(H.build_host_lib("sincos_host", ["sincos_host.cpp"], extra=("-pthread",)))
         _lib.sincos_sweep.restype = ctypes.c_uint64
         _lib.sincos_sweep.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
         _lib.sincos_eval.restype = None
@@ -85,6 +73,5 @@ def test_renderer_ranges_equal_the_oracle():
 def test_sanitized_program(tmp_path):
     """-fsanitize=undefined,float-cast-overflow over NaN, +-inf, +-0, denormals and |y| >= 120 (up to FLT_MAX): the conversion of the
     reduction must see a value in range for every one of them.  A program of its own, run as its own process."""
-    exe = _compile(str(tmp_path / "sincos_sanitized"), ["-O1", "-g", "-DSINCOS_HOST_MAIN", "-fsanitize=undefined,float-cast-overflow", "-fno-sanitize-recover=all"], False)
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "sincos_sanitized: ok" in run.stdout and "runtime error" not in run.stderr, run.stdout[-2000:] + run.stderr[-2000:]
+    H.run_sanitized_main(tmp_path, "sincos_host.cpp", scene_layer=False, expect="sincos_sanitized: ok", extra=("-DSINCOS_HOST_MAIN", "-pthread"),
+                         flags=("-O1", "-g", "-fsanitize=undefined,float-cast-overflow", "-fno-sanitize-recover=all"))

@@ -4,7 +4,6 @@ AddressSanitizer / UndefinedBehaviorSanitizer, as a stand-alone program - agains
 the header, and every entry point's argument validation on a host-only context, which has no skinning (there is no CPU path)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -73,16 +72,10 @@ def fixture_blob(name, path):
 @pytest.mark.parametrize("sanitized", [False, True])
 def test_device_functions_on_the_host(tmp_path, sanitized):
     """tests/host_emu/skin_host.cpp over both fixtures: the map, the positions and the flat normals, bit for bit."""
-    csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-    emu = os.path.join(H.ROOT, "tests", "host_emu")
-    exe = str(tmp_path / "skin_host")
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitized else ["-O2"]
-    subprocess.run(["g++", *flags, "-std=c++17", "-ffp-contract=off", "-I" + emu, "-I" + csrc, os.path.join(emu, "skin_host.cpp"), "-o", exe], check=True)
     for name in RIGS:
         blob = str(tmp_path / f"{name}.bin")
         fixture_blob(name, blob)
-        r = subprocess.run([exe, blob], capture_output=True, text=True)
-        assert r.returncode == 0 and "skin_host: ok" in r.stdout, name + "\n" + r.stdout + r.stderr
+        H.run_sanitized_main(tmp_path, "skin_host.cpp", scene_layer=False, args=[blob], flags=H.SANITIZE if sanitized else ("-O2",))
 
 
 def test_abi_and_validation_on_a_host_only_context(srt):

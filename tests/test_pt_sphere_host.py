@@ -6,7 +6,6 @@ inputs that keep these tests - and tests/test_pt_sphere_gpu.py - from going holl
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -148,15 +147,7 @@ _lib = None
 def _host():
     global _lib
     if _lib is None:
-        out = os.path.join(H.ORACLE_DIR, "_build", "libsphere_host.so")
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        src = os.path.join(H.ROOT, "tests", "host_emu", "sphere_host.cpp")
-        deps = [src, os.path.join(csrc, "pt_device.h"), os.path.join(csrc, "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(H.ROOT, "tests", "host_emu"),
-                            "-I" + csrc, "-I" + os.path.join(H.ROOT, "include"), src, "-o", out], check=True)
-        _lib = ctypes.CDLL(out)
+        _lib = ctypes.CDLL(H.build_host_lib("sphere_host", ["sphere_host.cpp"]))
     return _lib
 
 

@@ -5,8 +5,6 @@ child results, flags and far times; bit for bit, NaN payloads included.  The HIP
 tests/test_pt_sweep_forms_gpu.py renders with."""
 import ctypes
 import itertools
-import os
-import subprocess
 
 import numpy as np
 
@@ -21,15 +19,7 @@ _lib = None
 def _host():
     global _lib
     if _lib is None:
-        out = os.path.join(H.ORACLE_DIR, "_build", "libsweep_forms_host.so")
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        src = os.path.join(H.ROOT, "tests", "host_emu", "sweep_forms_host.cpp")
-        deps = [src] + [os.path.join(csrc, f) for f in ("pt_trace.h", "pt_device.h", "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(H.ROOT, "tests", "host_emu"),
-                            "-I" + csrc, "-I" + os.path.join(H.ROOT, "include"), src, "-o", out], check=True)
-        _lib = ctypes.CDLL(out)
+        _lib = ctypes.CDLL(H.build_host_lib("sweep_forms_host", ["sweep_forms_host.cpp"]))
     return _lib
 
 

@@ -4,8 +4,6 @@ second chosen as student/bvh.inl:186-209 chooses them, then handed to the childr
 both children's times, on 2^16 random cases (both boxes hit, one, none; ties) and with incoming times that are NaN, inverted or
 infinite.  Renders through it: tests/test_pt_point_affine_gpu.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -18,15 +16,7 @@ F = np.float32
 def _host():
     global _lib
     if _lib is None:
-        out = os.path.join(H.ORACLE_DIR, "_build", "libtopdown_step_host.so")
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        src = os.path.join(H.ROOT, "tests", "host_emu", "topdown_step_host.cpp")
-        deps = [src] + [os.path.join(csrc, f) for f in ("pt_trace.h", "pt_device.h", "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(H.ROOT, "tests", "host_emu"),
-                            "-I" + csrc, "-I" + os.path.join(H.ROOT, "include"), src, "-o", out], check=True)
-        _lib = ctypes.CDLL(out)
+        _lib = ctypes.CDLL(H.build_host_lib("topdown_step_host", ["topdown_step_host.cpp"]))
     return _lib
 
 

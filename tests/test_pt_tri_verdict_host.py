@@ -3,8 +3,6 @@
 reference's u < 0 || v < 0 || (1 - u - v) < 0 on the correctly rounded quotients.  The HIP build of the same function, and the
 fallback of the ambiguous lanes, are checked by tests/test_pt_tri_verdict_gpu.py."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
@@ -17,15 +15,7 @@ _lib = None
 def _host():
     global _lib
     if _lib is None:
-        out = os.path.join(H.ORACLE_DIR, "_build", "libtri_verdict_host.so")
-        csrc = os.path.join(H.ROOT, "soft-rendering-toolsets_amd", "csrc")
-        src = os.path.join(H.ROOT, "tests", "host_emu", "tri_verdict_host.cpp")
-        deps = [src, os.path.join(csrc, "pt_device.h"), os.path.join(csrc, "pt_scene.h")]
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(H.ROOT, "tests", "host_emu"),
-                            "-I" + csrc, "-I" + os.path.join(H.ROOT, "include"), src, "-o", out], check=True)
-        _lib = ctypes.CDLL(out)
+        _lib = ctypes.CDLL(H.build_host_lib("tri_verdict_host", ["tri_verdict_host.cpp"]))
     return _lib
 
 
