@@ -144,6 +144,8 @@ int srt_pt_group_set_ray_log(srt_pt_group* g, uint32_t capacity);
 int srt_pt_group_read_ray_log(srt_pt_group* g, int lane, srt_pt_logged_ray* out, size_t cap, size_t* n_out, uint64_t* dropped);
 /* srt_pt_set_normal_colors (below) on every member. */
 int srt_pt_group_set_normal_colors(srt_pt_group* g, int on);
+/* srt_pt_set_env_sampling (below) on every member. */
+int srt_pt_group_set_env_sampling(srt_pt_group* g, uint32_t mode);
 /* srt_pt_set_dynamic_lights (below) on every member. */
 int srt_pt_group_set_dynamic_lights(srt_pt_group* g, int on);
 /* srt_pt_set_active (below) on every member, and srt_pt_set_active_device with one device array per rank (d_active[r]: n bytes on
@@ -207,6 +209,33 @@ int srt_pt_set_env_light(srt_pt* pt, uint32_t type, const float radiance[3]);
  * up from the regenerated camera direction when a sample that left the scene is resolved). */
 #define SRT_ENV_MAP 3u
 int srt_pt_set_env_map(srt_pt* pt, uint32_t width, uint32_t height, const float* rgb);
+/* Which of Env_Map's two samplers (rays/env_light.h:43-52) sample_area_lights / area_lights_pdf use for an environment map:
+ * SRT_ENV_SAMPLING_UNIFORM, the fork's "step one" (student/env_light.cpp:8-32) and the default - every output is what it was
+ * without the switch - or SRT_ENV_SAMPLING_IMAGE, its "step two": image_sampler, a Samplers::Sphere::Image
+ * (student/samplers.cpp:27-137) - luminance * |sin theta| per texel, a normalised CDF, std::upper_bound on ONE draw, a pdf with a
+ * Jacobian.  The reference's arithmetic bit for bit, quirks included: sample() returns the texel's corner direction without
+ * jitter and draws one number where the uniform sampler draws two (the draw ledger of a sample changes); pdf() takes the sine of
+ * the NORMALISED theta in [0, 1]; an index of w * h (row h) is a legal result of sample(); a black map has NaN tables and a map
+ * with negative texels a CDF that is not sorted, on which the result is what libstdc++'s bisection steps arrive at.  So this mode
+ * does not converge to the uniform mode's image and does not claim to.
+ * A launch parameter like srt_pt_set_normal_colors: stored, read when a launch is enqueued, callable before or after the commit
+ * and whenever nothing of the context is being enqueued.  An unknown mode is SRT_ERR_INVALID.  SRT_ENV_SAMPLING_IMAGE with an
+ * environment that is no map (none, sphere, hemisphere) is refused, SRT_ERR_INVALID, by the LAUNCH that would sample it -
+ * srt_pt_render_epoch[_device], srt_pt_render_samples_device, srt_pt_trace_samples and the group forms; the call itself only
+ * stores the mode, and the normal-colors view, which samples no light, renders whatever the mode.  The sampler's tables (8 B per
+ * texel and the doubles of sample()'s h + 1 rows and w columns) are built on the host in the reference's order - its float total
+ * is accumulated serially, row-major - and uploaded by the first launch that needs them for a map; srt_pt_scene_begin and
+ * srt_pt_set_env_map drop them.  That first launch is therefore NOT enqueue-only, whichever entry point makes it
+ * (srt_pt_render_epoch_device, srt_pt_render_samples_device and the group's lane forms included): it builds the tables on the host,
+ * allocates device memory and copies them with a blocking copy before it enqueues its kernels - do not capture it in a graph, and
+ * expect a host wait; a caller that needs the loop enqueue-only from its first step makes one launch (srt_pt_trace_samples of one
+ * sample will do) after the commit.  Every later launch for the same map only enqueues.  With the mode off nothing is built,
+ * allocated, uploaded or counted.  Every kernel form that
+ * takes an environment map takes the mode (srt_pt_set_kernel 0, 1, 2, 4, 6); the forms that refuse environment lights still do. */
+#define SRT_ENV_SAMPLING_UNIFORM 0u
+#define SRT_ENV_SAMPLING_IMAGE 1u
+int srt_pt_set_env_sampling(srt_pt* pt, uint32_t mode);
+int srt_pt_env_sampling(srt_pt* pt, uint32_t* mode);
 
 /* Builds every BVH<Triangle> (leaf size 4) and the BVH<Object> (leaf size 1) exactly as the reference
  * does — or the List<> forms when use_bvh == 0 — flattens them and uploads the scene. */

@@ -117,6 +117,22 @@ int srt_pt_math_sincos2(srt_pt* pt, const float* x, size_t n, float* cos_out, fl
 int srt_pt_math_atan2(srt_pt* pt, const float* y, const float* x, size_t n, float* out);
 /* The kernels' acosf (glibc 2.35's algorithm restated; Samplers::Hemisphere::Uniform) evaluated on the device. */
 int srt_pt_math_acos(srt_pt* pt, const float* x, size_t n, float* out);
+/* The kernels' DOUBLE sin of a float in [0, 1] (glibc 2.35's __sin restated with the fused multiply-adds of its FMA build;
+ * Samplers::Sphere::Image::pdf, student/samplers.cpp:135) evaluated on the device.  out: n doubles. */
+int srt_pt_math_sin_unit(srt_pt* pt, const float* x, size_t n, double* out);
+/* Samplers::Sphere::Image of the context's environment map (srt_pt_set_env_map; SRT_ERR_INVALID without one), whatever
+ * srt_pt_set_env_sampling says: dims = {w, h}, *total the constructor's float total, cdf / pdf the normalised _cdf / _pdf (w * h
+ * floats each, row-major), trig the doubles of sample() (student/samplers.cpp:103-112) - sin theta of rows 0 .. h, cos theta of rows
+ * 0 .. h, cos phi of columns 0 .. w - 1, sin phi of columns 0 .. w - 1: 2 (h + 1) + 2 w doubles.  from_device == 0: the host's
+ * tables (built if this map has none yet; a host-only context will do); != 0: the device copies read back (made and uploaded if
+ * missing; waits for the device; total is the host's - the device holds the normalised tables).  NULL arrays are skipped. */
+int srt_pt_dump_env_sampler(srt_pt* pt, int from_device, uint32_t dims[2], float* total, float* cdf, float* pdf, size_t cap_texels,
+                            double* trig, size_t cap_trig);
+/* sample() and pdf() of that sampler by a kernel, through the device functions the render uses (env_image_upper_bound,
+ * env_image_direction, env_image_pdf in csrc/pt_trace.h): for each of nu chosen draws u the index std::upper_bound arrives at and
+ * the direction (3 floats) sample() returns for it; for each of nd directions (3 floats, not normalised by the call) pdf(). */
+int srt_pt_env_sampler_probe(srt_pt* pt, const float* u, size_t nu, uint32_t* index_out, float* dir_out, const float* dirs, size_t nd,
+                             float* pdf_out);
 /* The timelines' hypotf (glibc 2.35's __hypotf restated: evaluated in fp64; Mat4::to_euler, lib/mat4.h:177) evaluated on the device. */
 int srt_pt_math_hypot(srt_pt* pt, const float* x, const float* y, size_t n, float* out);
 /* What srt_pt_skin_set_rig validates and srt_pt_skin_posed computes, without a skin or a context (a host-only context has no skins):

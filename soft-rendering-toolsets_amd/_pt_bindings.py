@@ -174,6 +174,12 @@ def bind(lib: ctypes.CDLL) -> None:
     lib.srt_pt_set_elision.argtypes = [c_void_p, c_int]
     lib.srt_pt_rays_elided.argtypes = [c_void_p, POINTER(c_uint64), c_int]
     lib.srt_pt_set_normal_colors.argtypes = [c_void_p, c_int]
+    lib.srt_pt_set_env_sampling.argtypes = [c_void_p, c_uint32]
+    lib.srt_pt_env_sampling.argtypes = [c_void_p, c_void_p]
+    lib.srt_pt_group_set_env_sampling.argtypes = [c_void_p, c_uint32]
+    lib.srt_pt_math_sin_unit.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.srt_pt_dump_env_sampler.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
+    lib.srt_pt_env_sampler_probe.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.srt_pt_group_set_normal_colors.argtypes = [c_void_p, c_int]
     lib.srt_pt_set_dynamic_lights.argtypes = [c_void_p, c_int]
     lib.srt_pt_group_set_dynamic_lights.argtypes = [c_void_p, c_int]
@@ -1505,6 +1511,48 @@ class Pathtracer:
         Spectrum::direction(normal) of the camera ray's hit (include/srt_pt.h).  Takes effect at the next launch."""
         self._check(self._lib, self._lib.srt_pt_set_normal_colors(self._ctx, int(bool(on))))
 
+    ENV_SAMPLING = ("uniform", "image")
+
+    def set_env_sampling(self, mode: str) -> None:
+        """srt_pt_set_env_sampling: "uniform" (the default) or "image" - Env_Map's importance sampler, Samplers::Sphere::Image of the
+        reference bit for bit, quirks included (include/srt_pt.h).  Takes effect at the next launch; a launch with "image" and an
+        environment that is no map is refused."""
+        if mode not in self.ENV_SAMPLING:
+            raise ValueError(f"env sampling mode {mode!r}: one of {self.ENV_SAMPLING}")
+        self._check(self._lib, self._lib.srt_pt_set_env_sampling(self._ctx, self.ENV_SAMPLING.index(mode)))
+
+    def env_sampling(self) -> str:
+        mode = c_uint32(0)
+        self._check(self._lib, self._lib.srt_pt_env_sampling(self._ctx, ctypes.byref(mode)))
+        return self.ENV_SAMPLING[mode.value]
+
+    def math_sin_unit(self, x):
+        """srt_pt_math_sin_unit: the kernels' double sin of floats in [0, 1], as float64."""
+        x = _f32(x)
+        out = np.zeros(len(x), np.float64)
+        self._check(self._lib, self._lib.srt_pt_math_sin_unit(self._ctx, _p(x), len(x), _p(out)))
+        return out
+
+    def dump_env_sampler(self, from_device: bool = False) -> dict:
+        """srt_pt_dump_env_sampler: {"w", "h", "total", "cdf", "pdf" (h * w each), "sin_theta", "cos_theta" (h + 1), "cos_phi",
+        "sin_phi" (w)} of the environment map's Samplers::Sphere::Image, from the host's or the device's tables."""
+        dims, total = np.zeros(2, np.uint32), ctypes.c_float(0)
+        self._check(self._lib, self._lib.srt_pt_dump_env_sampler(self._ctx, int(from_device), _p(dims), ctypes.byref(total), None, None, 0, None, 0))
+        w, h = int(dims[0]), int(dims[1])
+        cdf, pdf, trig = np.zeros(w * h, np.float32), np.zeros(w * h, np.float32), np.zeros(2 * (h + 1) + 2 * w, np.float64)
+        self._check(self._lib, self._lib.srt_pt_dump_env_sampler(self._ctx, int(from_device), _p(dims), ctypes.byref(total), _p(cdf), _p(pdf),
+                                                                  w * h, _p(trig), len(trig)))
+        return {"w": w, "h": h, "total": np.float32(total.value), "cdf": cdf, "pdf": pdf, "sin_theta": trig[:h + 1].copy(),
+                "cos_theta": trig[h + 1:2 * h + 2].copy(), "cos_phi": trig[2 * h + 2:2 * h + 2 + w].copy(), "sin_phi": trig[2 * h + 2 + w:].copy()}
+
+    def env_sampler_probe(self, u=(), dirs=()):
+        """srt_pt_env_sampler_probe: (index, direction (n, 3)) of sample() for each draw u, and pdf() of each direction, by a kernel."""
+        u = _f32(u).reshape(-1)
+        dirs = np.ascontiguousarray(_f32(dirs).reshape(-1, 3))
+        index, out, pdf = np.zeros(len(u), np.uint32), np.zeros((len(u), 3), np.float32), np.zeros(len(dirs), np.float32)
+        self._check(self._lib, self._lib.srt_pt_env_sampler_probe(self._ctx, _p(u), len(u), _p(index), _p(out), _p(dirs), len(dirs), _p(pdf)))
+        return index, out, pdf
+
     def set_dynamic_lights(self, on: bool) -> None:
         """srt_pt_set_dynamic_lights: repose / update_mesh / refit_mesh / create_skin (and their device forms) accept area lights and
         keep the light tables what a fresh commit would make them.  Off by default; before or after build_scene."""
@@ -1816,6 +1864,12 @@ class PathtracerGroup:
     def set_elision(self, on: bool) -> None:
         for m in self.members:
             m.set_elision(on)
+
+    def set_env_sampling(self, mode: str) -> None:
+        """srt_pt_group_set_env_sampling: Pathtracer.set_env_sampling on every member."""
+        if mode not in Pathtracer.ENV_SAMPLING:
+            raise ValueError(f"env sampling mode {mode!r}: one of {Pathtracer.ENV_SAMPLING}")
+        self._check(self._lib, self._lib.srt_pt_group_set_env_sampling(self._g, Pathtracer.ENV_SAMPLING.index(mode)))
 
     def set_normal_colors(self, on: bool) -> None:
         """srt_pt_group_set_normal_colors: the normal-colors debug view on every member."""

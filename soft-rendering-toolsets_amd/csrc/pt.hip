@@ -38,6 +38,8 @@ namespace srt {
 
 // One lane per pixel of this rank's tiles; the lane walks the epoch's samples in order so the per-pixel
 // sum is accumulated exactly like do_trace (rays/pathtracer.cpp:216-226).
+// (ENVIMG, here and in pt_unit_kernel: path_sample's build with Env_Map's image sampler - srt_pt_set_env_sampling; false: the kernel as it was)
+template <bool ENVIMG>
 __global__ __launch_bounds__(64) void pt_epoch_kernel(DScene S, TileMap T, uint64_t seed, uint32_t sample_base,
                                                       uint32_t samples, float* __restrict__ tiles_out,
                                                       unsigned long long* __restrict__ ray_counter, const uint32_t* host_cancel, uint32_t* dev_cancel) {
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(64) void pt_epoch_kernel(DScene S, TileMap T, uint6
   uint32_t sampled = 0;
   for (uint32_t s = 0; s < samples; s++) {
     rng.key(seed, y * S.w + x, sample_base + s);
-    const Spec p = path_sample<false>(S, x, y, rng, cnt);
+    const Spec p = path_sample<false, ENVIMG>(S, x, y, rng, cnt);
     if (valid(p)) { acc = acc + p; sampled++; }
   }
   if (sampled > 0) acc = acc * (1.0f / sampled);
@@ -82,6 +84,7 @@ __global__ __launch_bounds__(64) void pt_epoch_kernel(DScene S, TileMap T, uint6
 // pt_reduce_kernel adds a pixel's samples in order.  Lanes of a wave hold consecutive samples of one pixel.
 // 8 waves/SIMD (64 VGPRs, the rest spilled): the kernel waits on memory two thirds of the time, and occupancy hides
 // that better than registers do (131 k-triangle scene: 325 -> 417 Mrays/s).
+template <bool ENVIMG>
 __global__ __launch_bounds__(64, 8) void pt_unit_kernel(DScene S, TileMap T, uint64_t seed, uint32_t sample_base, uint32_t samples,
                                                      uint32_t total_units, float* __restrict__ sample_out,
                                                      unsigned long long* __restrict__ ray_counter, const uint32_t* host_cancel, uint32_t* dev_cancel) {
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(64, 8) void pt_unit_kernel(DScene S, TileMap T, uin
     if (x < S.w && y < S.h) {
       Rng rng;
       rng.key(seed, y * S.w + x, sample_base + u % samples);
-      const Spec p = path_sample<false>(S, x, y, rng, cnt);
+      const Spec p = path_sample<false, ENVIMG>(S, x, y, rng, cnt);
       reinterpret_cast<float4*>(sample_out)[(size_t)(u % samples) * (total_units / samples) + u / samples] = make_float4(p.r, p.g, p.b, 0.0f);
     }
   }
@@ -253,6 +256,7 @@ struct KernelForm {
   int trav = -1;            // wave_trav(): -1 one lane per sample (mode 1: per pixel), 0..2 the persistent wave kernel, 3 / 4 the streamed form
   bool stamp = false;       // mode 3: the build with section stamps
   bool dl = false;          // delta or environment lights
+  bool envimg = false;      // srt_pt_set_env_sampling(SRT_ENV_SAMPLING_IMAGE): the builds that hold Env_Map's image sampler
   bool two = false;         // two-ray batches
   uint32_t burst = kBurst;  // samples per unit
 };
@@ -270,6 +274,9 @@ int resolve_form(const srt_pt* pt, KernelForm* out) {
   }
   K.stamp = pt->kernel_mode == 3;
   K.dl = !F.delta_lights.empty() || pt->env_type != 0;
+  if (pt->env_sampling == SRT_ENV_SAMPLING_IMAGE && !pt->env_image.valid)   // (env_image_ready comes first on every launch path)
+    return srt::fail(SRT_ERR_STATE, "image sampling is on but the sampler's tables are not on the device");
+  K.envimg = image_sampling_launch(pt);
   // two-ray batches (dead BSDF-sampled direct ray not traced): asked for, sweep build, no delta / environment light, and
   // every continuous BSDF Lambertian (pt_wave.h)
   K.two = elision_provable(pt) && !K.stamp && K.trav != 2;
@@ -284,10 +291,10 @@ int resolve_form(const srt_pt* pt, KernelForm* out) {
 using WaveKernel = void (*)(DScene, WaveParams, const Object*, const Tri*, const TriNrm*, const Node*, const Light*, const LightTri*,
                             const Material*, const WaveInterior*, const WaveInterior*, float*, float*);
 using CastKernel = void (*)(DScene, CastParams);
-struct WaveEntry { bool stamp; int trav; bool dl; int nr, phase; WaveKernel kern; };
-template <bool STAMP, int TRAV, bool DL, int NR, int PHASE = 0>
-WaveEntry wave_entry() { return {STAMP, TRAV, DL, NR, PHASE, pt_wave_kernel<STAMP, TRAV, DL, NR, PHASE>}; }
-WaveKernel wave_kernel(bool stamp, int trav, bool dl, int nr, int phase = 0) {
+struct WaveEntry { bool stamp; int trav; bool dl; int nr, phase; bool envimg; WaveKernel kern; };
+template <bool STAMP, int TRAV, bool DL, int NR, int PHASE = 0, bool ENVIMG = false>
+WaveEntry wave_entry() { return {STAMP, TRAV, DL, NR, PHASE, ENVIMG, pt_wave_kernel<STAMP, TRAV, DL, NR, PHASE, ENVIMG>}; }
+WaveKernel wave_kernel(bool stamp, int trav, bool dl, int nr, int phase = 0, bool envimg = false) {
   static const WaveEntry table[] = {
       // the persistent kernel: two-ray batches, section stamps, delta / environment lights, plain
       wave_entry<false, 0, false, 2>(), wave_entry<false, 1, false, 2>(),
@@ -300,9 +307,12 @@ WaveKernel wave_kernel(bool stamp, int trav, bool dl, int nr, int phase = 0) {
       wave_entry<false, 4, false, 2, 2>(), wave_entry<false, 4, false, 3, 2>(),
       // the logic kernel with every ray through the ray-cast kernel
       wave_entry<false, 3, false, 2>(), wave_entry<false, 3, true, 3>(), wave_entry<false, 3, false, 3>(),
+      // the environment-light builds once more with Env_Map's image sampler (srt_pt_set_env_sampling)
+      wave_entry<false, 0, true, 3, 0, true>(), wave_entry<false, 1, true, 3, 0, true>(),
+      wave_entry<false, 4, true, 3, 0, true>(), wave_entry<false, 3, true, 3, 0, true>(),
   };
   for (const WaveEntry& e : table)
-    if (e.stamp == stamp && e.trav == trav && e.dl == dl && e.nr == nr && e.phase == phase) return e.kern;
+    if (e.stamp == stamp && e.trav == trav && e.dl == dl && e.nr == nr && e.phase == phase && e.envimg == envimg) return e.kern;
   return nullptr;
 }
 CastKernel cast_kernel(bool stats, bool walk) {
@@ -383,8 +393,8 @@ int render_epoch_wave(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t s
   const size_t nq = (F.use_bvh && trav != 2) ? F.wave_tlas.size() : 0;
   const size_t lds = (size_t)4 * (nq > 0 ? nq - 1 : 0) * (2 * burst) * 64 * sizeof(float)   // 4 waves x (Q - 1) x rays x 2 fields
                      + (cold_in_lds(trav) ? (size_t)kColdWords * 256 * sizeof(uint32_t) : 0); // + the lanes' cold path state
-  const WaveKernel kern = wave_kernel(K.stamp, trav, K.dl, K.two ? 2 : 3);
-  if (!kern) return srt::fail(SRT_ERR_STATE, "no wave kernel for stamp %d, traversal %d, lights %d, %u-ray batches", K.stamp, trav, K.dl, K.two ? 2u : 3u);
+  const WaveKernel kern = wave_kernel(K.stamp, trav, K.dl, K.two ? 2 : 3, 0, K.envimg);
+  if (!kern) return srt::fail(SRT_ERR_STATE, "no wave kernel for stamp %d, traversal %d, lights %d, %u-ray batches, image sampler %d", K.stamp, trav, K.dl, K.two ? 2u : 3u, K.envimg);
   if (pt->wave_blocks == 0 || pt->wave_lds != lds || pt->wave_mode != pt->kernel_mode || pt->wave_kern != (const void*)kern) {
     pt->wave_mode = pt->kernel_mode;
     pt->wave_kern = (const void*)kern;
@@ -539,7 +549,7 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
   // the streamed sweeps without delta / environment lights run a generation's two passes as two kernels (pt_wave.h, PHASE):
   // resolve (sweep slots in LDS) and probe (no LDS); SRT_STREAM_FUSED=1 (diagnostic) keeps them in one kernel
   const bool split = trav == 4 && !dl && !getenv("SRT_STREAM_FUSED");
-  const WaveKernel lkern = wave_kernel(false, trav, dl, two ? 2 : 3, split ? 1 : 0);
+  const WaveKernel lkern = wave_kernel(false, trav, dl, two ? 2 : 3, split ? 1 : 0, K.envimg);
   const WaveKernel probe = split ? wave_kernel(false, trav, dl, two ? 2 : 3, 2) : nullptr;
   if (!lkern || (split && !probe)) return srt::fail(SRT_ERR_STATE, "no streamed logic kernel for traversal %d, lights %d, %u-ray batches, split %d", trav, dl, two ? 2u : 3u, split);
   if (logic_lds > 160u * 1024u) return srt::fail(SRT_ERR_UNSUPPORTED, "the streamed sweeps' LDS slots (%zu bytes) do not fit", logic_lds);
@@ -644,7 +654,7 @@ int render_epoch_stream(srt_pt* pt, hipStream_t s, const KernelForm& K, uint64_t
 }
 
 // One epoch with one lane per sample (general scenes).
-int render_epoch_units(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t sample_base, uint32_t samples, float* d_tiles_out) {
+int render_epoch_units(srt_pt* pt, hipStream_t s, bool envimg, uint64_t seed, uint32_t sample_base, uint32_t samples, float* d_tiles_out) {
   const TileMap& T = pt->tiles;
   const uint32_t px = T.local_tiles * T.tile_w * T.tile_h;
   int st;
@@ -655,7 +665,7 @@ int render_epoch_units(srt_pt* pt, hipStream_t s, uint64_t seed, uint32_t sample
   auto stage = [](uint32_t, uint32_t) -> int { return SRT_OK; };
   auto launch = [&](uint32_t first_sample, uint32_t n) -> int {
     const uint64_t units = (uint64_t)px * n;
-    pt_unit_kernel<<<dim3((unsigned)((units + 63) / 64)), dim3(64), 0, s>>>(DS, T, seed, first_sample, n, (uint32_t)units, B.d_samples, pt->d_totals + C_COUNT,
+    (envimg ? pt_unit_kernel<true> : pt_unit_kernel<false>)<<<dim3((unsigned)((units + 63) / 64)), dim3(64), 0, s>>>(DS, T, seed, first_sample, n, (uint32_t)units, B.d_samples, pt->d_totals + C_COUNT,
                                                                             pt->h_cancel.device(), B.d_cancel);
     return SRT_OK;
   };
@@ -700,6 +710,11 @@ DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B) {
   S.tlas_nodes = F.tlas_nodes; S.use_bvh = F.use_bvh ? 1u : 0u; S.light_tri_first = F.light_tri_first;
   S.cam = pt->cam; S.w = pt->w; S.h = pt->h; S.max_depth = pt->max_depth;
   S.elide = elision_provable(pt) ? 1u : 0u;
+  if (image_sampling_launch(pt)) {
+    const size_t texels = (size_t)pt->env_w * pt->env_h;
+    S.env_cdf = pt->env_image.d_tables; S.env_pdf = pt->env_image.d_tables + texels; S.env_trig = pt->env_image.d_trig;
+    S.env_sampling = 1u;
+  }
   return S;
 }
 
@@ -779,6 +794,7 @@ namespace {
 int render_device(srt_pt* pt, const char* what, void* stream, uint64_t seed, uint32_t sample_base, uint32_t samples, float* d_tiles_out) {
   int st = need_ready(pt, what);
   if (st != SRT_OK) return st;
+  if ((st = env_image_ready(pt, what)) != SRT_OK) return st;   // srt_pt_set_env_sampling: the refusal, or the tables of this map
   if (__atomic_load_n(pt->h_cancel.get(), __ATOMIC_ACQUIRE) != 0u) return SRT_CANCELLED;   // nothing more is enqueued until srt_pt_clear_cancel
   hipStream_t s = (hipStream_t)stream;  // exactly the caller's stream; NULL is the HIP default stream
   const TileMap& T = pt->tiles;
@@ -793,14 +809,14 @@ int render_device(srt_pt* pt, const char* what, void* stream, uint64_t seed, uin
     } else if (pt->kernel_mode != 1) {
       st = K.trav >= 3 ? render_epoch_stream(pt, s, K, seed, sample_base, samples, d_tiles_out)
          : K.trav >= 0 ? render_epoch_wave(pt, s, K, seed, sample_base, samples, d_tiles_out)
-                       : render_epoch_units(pt, s, seed, sample_base, samples, d_tiles_out);
+                       : render_epoch_units(pt, s, K.envimg, seed, sample_base, samples, d_tiles_out);
       if (st != SRT_OK) return st;
     } else {                                              // mode 1, one lane per pixel: no per-sample buffer, no reduction
       const uint32_t blocks = (uint32_t)((lanes + 63) / 64);
       srt_pt::EpochBuffers* Bp = nullptr;
       if ((st = stream_buffers(pt, s, &Bp)) != SRT_OK) return st;
       if ((st = time_begin(pt, s, pt->timed, pt->timing)) != SRT_OK) return st;
-      pt_epoch_kernel<<<dim3(blocks), dim3(64), 0, s>>>(device_scene(pt, Bp), T, seed, sample_base, samples, d_tiles_out,
+      (K.envimg ? pt_epoch_kernel<true> : pt_epoch_kernel<false>)<<<dim3(blocks), dim3(64), 0, s>>>(device_scene(pt, Bp), T, seed, sample_base, samples, d_tiles_out,
                                                         pt->d_totals + C_COUNT, pt->h_cancel.device(), Bp->d_cancel);
       SRT_HIP(hipGetLastError());
       if ((st = time_end(s, pt->timed, pt->timing)) != SRT_OK) return st;

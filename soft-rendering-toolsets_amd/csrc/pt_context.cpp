@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pt_context.h"
+#include "pt_env_image.h"
 #include "pt_trace.h"
 #include "srt_pt_debug.h"
 
@@ -24,6 +25,15 @@ void update_tiling(srt_pt* pt) {
   const uint32_t ntiles = T.tiles_x * T.tiles_y;
   pt->tiles_per_rank = (ntiles + T.world - 1) / T.world;
   T.local_tiles = (ntiles > T.rank) ? (ntiles - T.rank + T.world - 1) / T.world : 0;
+}
+
+// The image sampler's tables describe a map that goes (launches that read the device copies may still be in flight on any stream).
+void drop_env_image(srt_pt* pt) {
+  if (pt->env_image.d_tables || pt->env_image.d_trig) {
+    (void)hipSetDevice(pt->device);
+    (void)hipDeviceSynchronize();
+  }
+  pt->env_image.drop();
 }
 
 }  // namespace
@@ -42,6 +52,31 @@ int need_ready(srt_pt* pt, const char* what) {
   if (!pt->committed) return not_committed(what);
   if (!pt->have_cam) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_camera", what);
   if (!pt->w || !pt->h) return srt::fail(SRT_ERR_STATE, "%s before srt_pt_set_params", what);
+  return SRT_OK;
+}
+
+int env_image_host_tables(srt_pt* pt, const char* what) {
+  if (pt->env_type != SRT_ENV_MAP)
+    return srt::fail(SRT_ERR_INVALID, "%s: image sampling (srt_pt_set_env_sampling) needs an environment map (srt_pt_set_env_map); the scene has %s",
+                     what, pt->env_type == SRT_ENV_NONE ? "no environment light" : pt->env_type == SRT_ENV_SPHERE ? "a uniform sphere" : "a uniform hemisphere");
+  if (pt->env_image.cdf_pdf.empty()) {
+    EnvImageTables T;
+    build_env_image_tables(pt->env_map.data(), pt->env_w, pt->env_h, &T);
+    pt->env_image.cdf_pdf = std::move(T.cdf_pdf); pt->env_image.trig = std::move(T.trig); pt->env_image.total = T.total;
+  }
+  return SRT_OK;
+}
+
+int env_image_ready(srt_pt* pt, const char* what) {
+  if (pt->env_sampling != SRT_ENV_SAMPLING_IMAGE || pt->normal_colors) return SRT_OK;
+  return env_image_upload(pt, what);
+}
+
+int env_image_upload(srt_pt* pt, const char* what) {
+  int st = env_image_host_tables(pt, what);
+  if (st != SRT_OK || pt->env_image.valid) return st;
+  if ((st = upload(pt, &pt->env_image.d_tables, pt->env_image.cdf_pdf)) || (st = upload(pt, &pt->env_image.d_trig, pt->env_image.trig))) return st;
+  pt->env_image.valid = true;
   return SRT_OK;
 }
 }  // namespace srt
@@ -99,6 +134,7 @@ int srt_pt_scene_begin(srt_pt* pt) {
   pt->delta_lights.clear();
   pt->env_type = 0;
   pt->env_map.clear(); pt->env_w = pt->env_h = 0;
+  drop_env_image(pt);
   pt->committed = false;
   pt->scene_generation++;
   return SRT_OK;
@@ -217,6 +253,7 @@ int srt_pt_set_env_map(srt_pt* pt, uint32_t width, uint32_t height, const float*
   pt->env_type = SRT_ENV_MAP;
   pt->env_w = width; pt->env_h = height;
   pt->env_map.assign(rgb, rgb + 3 * (size_t)width * height);
+  drop_env_image(pt);                                     // the sampler's tables describe the map that goes
   return SRT_OK;
 }
 
@@ -331,6 +368,20 @@ int srt_pt_set_elision(srt_pt* pt, int on) {
 int srt_pt_set_dynamic_lights(srt_pt* pt, int on) {
   if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_dynamic_lights: NULL context");
   pt->built.dynamic_lights = on != 0;
+  return SRT_OK;
+}
+
+int srt_pt_set_env_sampling(srt_pt* pt, uint32_t mode) {
+  if (!pt) return srt::fail(SRT_ERR_INVALID, "srt_pt_set_env_sampling: NULL context");
+  if (mode > SRT_ENV_SAMPLING_IMAGE)
+    return srt::fail(SRT_ERR_INVALID, "srt_pt_set_env_sampling: unknown mode %u (0 uniform, 1 image)", mode);
+  pt->env_sampling = mode;                                // the tables follow at the first launch that needs them (env_image_ready)
+  return SRT_OK;
+}
+
+int srt_pt_env_sampling(srt_pt* pt, uint32_t* mode) {
+  if (!pt || !mode) return srt::fail(SRT_ERR_INVALID, "srt_pt_env_sampling: NULL argument");
+  *mode = pt->env_sampling;
   return SRT_OK;
 }
 

@@ -54,6 +54,17 @@ struct srt_pt {
   std::vector<srt::DeltaLight> delta_lights;   // srt_pt_add_light, in call order
   uint32_t env_type = 0; float env_radiance[3] = {0, 0, 0};   // srt_pt_set_env_light
   std::vector<float> env_map; uint32_t env_w = 0, env_h = 0; srt::DeviceBuffer<float> d_env_map;   // srt_pt_set_env_map
+  // srt_pt_set_env_sampling: the mode (read whenever a launch is enqueued) and, from the first launch that needs them until the map
+  // goes (srt_pt_scene_begin, srt_pt_set_env_map), the tables of Samplers::Sphere::Image for env_map (pt_env_image.h) and their
+  // device copies - d_tables: _cdf then _pdf, d_trig: the doubles of sample().  Nothing here is made while the mode is off.
+  uint32_t env_sampling = 0;
+  struct EnvImage {
+    bool valid = false;
+    float total = 0.0f;
+    std::vector<float> cdf_pdf; std::vector<double> trig;
+    srt::DeviceBuffer<float> d_tables; srt::DeviceBuffer<double> d_trig;
+    void drop() { valid = false; total = 0.0f; cdf_pdf.clear(); trig.clear(); d_tables.reset(); d_trig.reset(); }
+  } env_image;
   srt::DeviceBuffer<float> d_tile_buf;
   int kernel_mode = 0;        // srt_pt_set_kernel: 0 auto, 1 per-lane (lane per pixel), 2 wave-uniform, 3 wave-uniform with section stamps, 4 per-lane (lane per
                               // sample), 5 flattened per-lane walk, 6 streamed (logic + ray-cast kernels), 7 streamed sweeps; wave_trav() picks the form
@@ -245,6 +256,17 @@ inline int upload(srt_pt* pt, DeviceBuffer<T>* dst, const std::vector<T>& src, b
 int need_device(srt_pt* pt, const char* what);            // (pt_context.cpp)
 // need_device, and the scene is committed, has a camera and an image size (pt_context.cpp)
 int need_ready(srt_pt* pt, const char* what);
+// In front of a launch of `what` that samples lights: SRT_OK with the mode off (and under the normal-colors view, which samples
+// none); with SRT_ENV_SAMPLING_IMAGE the refusal of a scene whose environment is no Env_Map, else the sampler's tables, built and
+// uploaded if this map has none yet (pt_context.cpp)
+int env_image_ready(srt_pt* pt, const char* what);
+// Which build a launch that env_image_ready let through takes: the ENVIMG one exactly when the mode is on and the tables are on the
+// device.  device_scene() fills the table pointers under the same condition, so the two cannot disagree.
+inline bool image_sampling_launch(const srt_pt* pt) { return pt->env_sampling == SRT_ENV_SAMPLING_IMAGE && pt->env_image.valid; }
+// The same without a device: the refusal, or the host's copy of the tables in pt->env_image (the dump reads them)
+int env_image_host_tables(srt_pt* pt, const char* what);
+// env_image_ready whatever the mode says (the probes of srt_pt_debug.h): the refusal, or the tables on the device
+int env_image_upload(srt_pt* pt, const char* what);
 // The kernels' view of the committed scene; B: the scratch set whose ray-log ring they write, if any (pt.hip)
 DScene device_scene(const srt_pt* pt, const srt_pt::EpochBuffers* B = nullptr);
 // The scene fits the flattened per-lane walk of pt_flat.h (pt.hip)

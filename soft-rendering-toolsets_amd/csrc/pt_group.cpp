@@ -489,6 +489,11 @@ int srt_pt_group_clear_cancel(srt_pt_group* g) {
   return st != SRT_OK ? st : each_member(g, [](srt_pt* c) { return srt_pt_clear_cancel(c); });
 }
 
+int srt_pt_group_set_env_sampling(srt_pt_group* g, uint32_t mode) {
+  const int st = need_group(g, "srt_pt_group_set_env_sampling");
+  return st != SRT_OK ? st : each_member(g, [&](srt_pt* c) { return srt_pt_set_env_sampling(c, mode); });
+}
+
 int srt_pt_group_set_normal_colors(srt_pt_group* g, int on) {
   const int st = need_group(g, "srt_pt_group_set_normal_colors");
   return st != SRT_OK ? st : each_member(g, [&](srt_pt* c) { return srt_pt_set_normal_colors(c, on); });

@@ -2,6 +2,7 @@
 // caller-supplied operands, so that a test can compare it with the host's libm or with the plain per-ray form.  No scene, no render.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <type_traits>
 
 #include "pt_anim.h"
@@ -29,6 +30,27 @@ __global__ void pt_sincos2_kernel(const float* __restrict__ x, size_t n, float* 
 __global__ void pt_acos_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = srt_acosf(x[i]);
+}
+
+__global__ void pt_sin_unit_kernel(const float* __restrict__ x, size_t n, double* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = srt_sin_unit(x[i]);
+}
+
+// Samplers::Sphere::Image through the render's own device functions (pt_trace.h): lane i < nu bisects u[i] and forms the direction,
+// lane nu + j evaluates pdf() of direction j.
+__global__ void pt_env_sampler_kernel(DScene S, const float* __restrict__ u, size_t nu, uint32_t* __restrict__ index_out, float* __restrict__ dir_out,
+                                      const float* __restrict__ dirs, size_t nd, float* __restrict__ pdf_out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nu) {
+    const uint32_t index = env_image_upper_bound(S, u[i]);
+    const V3 d = env_image_direction(S, index);
+    index_out[i] = index;
+    dir_out[3 * i] = d.x; dir_out[3 * i + 1] = d.y; dir_out[3 * i + 2] = d.z;
+  } else if (i - nu < nd) {
+    const size_t j = i - nu;
+    pdf_out[j] = env_image_pdf(S, v3(dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]));
+  }
 }
 
 __global__ void pt_atan2_kernel(const float* __restrict__ y, const float* __restrict__ x, size_t n, float* __restrict__ out) {
@@ -346,6 +368,76 @@ int srt_pt_math_sincos2(srt_pt* pt, const float* x, size_t n, float* cos_out, fl
 int srt_pt_math_acos(srt_pt* pt, const float* x, size_t n, float* out) {
   return math_round_trip(pt, "srt_pt_math_acos", {x}, n, {out}, n, [&](float* const* d, float* const* o) {
     pt_acos_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(d[0], n, o[0]); });
+}
+
+int srt_pt_math_sin_unit(srt_pt* pt, const float* x, size_t n, double* out) {
+  int st = need_device(pt, "srt_pt_math_sin_unit");
+  if (st != SRT_OK) return st;
+  if (n == 0) return SRT_OK;
+  if (!x || !out) return srt::fail(SRT_ERR_INVALID, "srt_pt_math_sin_unit: NULL argument");
+  DeviceBuffer<float> dx;
+  DeviceBuffer<double> dout;
+  if ((st = dx.ensure(n)) || (st = dout.ensure(n))) return st;
+  SRT_HIP(hipMemcpyAsync(dx, x, n * sizeof(float), hipMemcpyHostToDevice, pt->stream));
+  pt_sin_unit_kernel<<<math_grid(n), dim3(256), 0, pt->stream>>>(dx, n, dout);
+  SRT_HIP(hipGetLastError());
+  SRT_HIP(hipMemcpyAsync(out, dout, n * sizeof(double), hipMemcpyDeviceToHost, pt->stream));
+  SRT_HIP(hipStreamSynchronize(pt->stream));
+  return SRT_OK;
+}
+
+int srt_pt_dump_env_sampler(srt_pt* pt, int from_device, uint32_t dims[2], float* total, float* cdf, float* pdf, size_t cap_texels,
+                            double* trig, size_t cap_trig) {
+  if (!pt || !dims) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_env_sampler: NULL argument");
+  int st;
+  if (from_device) {
+    if (pt->device < 0) return srt::fail(SRT_ERR_UNSUPPORTED, "srt_pt_dump_env_sampler: a host-only context has no device tables");
+    if ((st = need_device(pt, "srt_pt_dump_env_sampler")) || (st = env_image_upload(pt, "srt_pt_dump_env_sampler"))) return st;
+  } else if ((st = env_image_host_tables(pt, "srt_pt_dump_env_sampler"))) {
+    return st;
+  }
+  const size_t texels = (size_t)pt->env_w * pt->env_h, ntrig = pt->env_image.trig.size();
+  dims[0] = pt->env_w; dims[1] = pt->env_h;
+  if (total) *total = pt->env_image.total;                // (the host's: the device holds the normalised tables only)
+  if ((cdf || pdf) && cap_texels < texels) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_env_sampler: room for %zu texels, the map has %zu", cap_texels, texels);
+  if (trig && cap_trig < ntrig) return srt::fail(SRT_ERR_INVALID, "srt_pt_dump_env_sampler: room for %zu doubles, the tables have %zu", cap_trig, ntrig);
+  if (from_device) {
+    SRT_HIP(hipDeviceSynchronize());
+    if (cdf) SRT_HIP(hipMemcpy(cdf, pt->env_image.d_tables, texels * sizeof(float), hipMemcpyDeviceToHost));
+    if (pdf) SRT_HIP(hipMemcpy(pdf, pt->env_image.d_tables + texels, texels * sizeof(float), hipMemcpyDeviceToHost));
+    if (trig) SRT_HIP(hipMemcpy(trig, pt->env_image.d_trig, ntrig * sizeof(double), hipMemcpyDeviceToHost));
+  } else {
+    if (cdf) memcpy(cdf, pt->env_image.cdf_pdf.data(), texels * sizeof(float));
+    if (pdf) memcpy(pdf, pt->env_image.cdf_pdf.data() + texels, texels * sizeof(float));
+    if (trig) memcpy(trig, pt->env_image.trig.data(), ntrig * sizeof(double));
+  }
+  return SRT_OK;
+}
+
+int srt_pt_env_sampler_probe(srt_pt* pt, const float* u, size_t nu, uint32_t* index_out, float* dir_out, const float* dirs, size_t nd, float* pdf_out) {
+  int st = need_device(pt, "srt_pt_env_sampler_probe");
+  if (st != SRT_OK) return st;
+  if ((nu && (!u || !index_out || !dir_out)) || (nd && (!dirs || !pdf_out))) return srt::fail(SRT_ERR_INVALID, "srt_pt_env_sampler_probe: NULL argument");
+  if ((st = env_image_upload(pt, "srt_pt_env_sampler_probe"))) return st;
+  if (nu + nd == 0) return SRT_OK;
+  DeviceBuffer<float> du, ddir, ddirs, dpdf;
+  DeviceBuffer<uint32_t> dindex;
+  if ((st = du.ensure(nu + 1)) || (st = dindex.ensure(nu + 1)) || (st = ddir.ensure(3 * nu + 1)) || (st = ddirs.ensure(3 * nd + 1)) || (st = dpdf.ensure(nd + 1))) return st;
+  if (nu) SRT_HIP(hipMemcpyAsync(du, u, nu * sizeof(float), hipMemcpyHostToDevice, pt->stream));
+  if (nd) SRT_HIP(hipMemcpyAsync(ddirs, dirs, 3 * nd * sizeof(float), hipMemcpyHostToDevice, pt->stream));
+  DScene S{};
+  const size_t texels = (size_t)pt->env_w * pt->env_h;
+  S.env_type = SRT_ENV_MAP; S.env_w = pt->env_w; S.env_h = pt->env_h; S.env_sampling = 1u;
+  S.env_cdf = pt->env_image.d_tables; S.env_pdf = pt->env_image.d_tables + texels; S.env_trig = pt->env_image.d_trig;
+  pt_env_sampler_kernel<<<math_grid(nu + nd), dim3(256), 0, pt->stream>>>(S, du, nu, dindex, ddir, ddirs, nd, dpdf);
+  SRT_HIP(hipGetLastError());
+  if (nu) {
+    SRT_HIP(hipMemcpyAsync(index_out, dindex, nu * sizeof(uint32_t), hipMemcpyDeviceToHost, pt->stream));
+    SRT_HIP(hipMemcpyAsync(dir_out, ddir, 3 * nu * sizeof(float), hipMemcpyDeviceToHost, pt->stream));
+  }
+  if (nd) SRT_HIP(hipMemcpyAsync(pdf_out, dpdf, nd * sizeof(float), hipMemcpyDeviceToHost, pt->stream));
+  SRT_HIP(hipStreamSynchronize(pt->stream));
+  return SRT_OK;
 }
 
 int srt_pt_math_atan2(srt_pt* pt, const float* y, const float* x, size_t n, float* out) {

@@ -18,7 +18,8 @@
 namespace srt {
 
 // Explicit (x, y, sample) triples; instrumented when COUNT.  NORMALS: the normal-colors view (normal_sample) instead of a path.
-template <bool COUNT, bool NORMALS = false>
+// ENVIMG: path_sample's build with Env_Map's image sampler (srt_pt_set_env_sampling).
+template <bool COUNT, bool NORMALS = false, bool ENVIMG = false>
 __global__ __launch_bounds__(64) void pt_samples_kernel(DScene S, uint64_t seed, const uint32_t* __restrict__ xs,
                                                         const uint32_t* __restrict__ ys, const uint32_t* __restrict__ ss,
                                                         uint32_t n, float* __restrict__ rgb, uint32_t* __restrict__ draws,
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(64) void pt_samples_kernel(DScene S, uint64_t seed,
   for (int k = 0; k < C_COUNT; k++) cnt.v[k] = 0;
   Rng rng;
   rng.key(seed, ys[i] * S.w + xs[i], ss[i]);
-  const Spec p = NORMALS ? normal_sample<COUNT>(S, xs[i], ys[i], rng, cnt) : path_sample<COUNT>(S, xs[i], ys[i], rng, cnt);
+  const Spec p = NORMALS ? normal_sample<COUNT>(S, xs[i], ys[i], rng, cnt) : path_sample<COUNT, ENVIMG>(S, xs[i], ys[i], rng, cnt);
   rgb[3 * i] = p.r; rgb[3 * i + 1] = p.g; rgb[3 * i + 2] = p.b;
   if (draws) draws[i] = rng.draws;
   if (COUNT) {
@@ -97,6 +98,7 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
   int st = need_ready(pt, "srt_pt_trace_samples");
   if (st != SRT_OK) return st;
   if ((st = settle(pt)) != SRT_OK) return st;
+  if ((st = env_image_ready(pt, "srt_pt_trace_samples")) != SRT_OK) return st;
   if (n == 0) return SRT_OK;
   if (!xs || !ys || !ss || !rgb_out) return srt::fail(SRT_ERR_INVALID, "srt_pt_trace_samples: NULL argument");
   if (n > 0x7fffffffull) return srt::fail(SRT_ERR_UNSUPPORTED, "too many samples in one call");
@@ -109,7 +111,8 @@ int srt_pt_trace_samples(srt_pt* pt, uint64_t seed, const uint32_t* xs, const ui
   SRT_HIP(hipMemcpyAsync(dy, ys, n * 4, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemcpyAsync(ds, ss, n * 4, hipMemcpyHostToDevice, pt->stream));
   SRT_HIP(hipMemsetAsync(pt->d_totals, 0, C_COUNT * sizeof(unsigned long long), pt->stream));
-  const auto kern = pt->normal_colors ? pt_samples_kernel<true, true> : pt_samples_kernel<true, false>;
+  const auto kern = pt->normal_colors ? pt_samples_kernel<true, true>
+                  : image_sampling_launch(pt) ? pt_samples_kernel<true, false, true> : pt_samples_kernel<true, false>;
   kern<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pt->stream>>>(device_scene(pt), seed, dx, dy, ds, (uint32_t)n, drgb, dd, dr, pt->d_totals);
   SRT_HIP(hipGetLastError());
   SRT_HIP(hipMemcpyAsync(rgb_out, drgb, n * 12, hipMemcpyDeviceToHost, pt->stream));

@@ -7,6 +7,7 @@
 
 #include "pt_device.h"
 #include "pt_scene.h"
+#include "pt_sin_unit.h"   // srt_sin_unit: glibc's double sin on [0, 1] (env_image_pdf)
 
 namespace srt {
 
@@ -39,6 +40,14 @@ struct DScene {
   // kRayLogWords words from word kRayLogHeader on.  NULL: nothing is logged (the coin is drawn all the same).
   uint32_t* ray_log;
   uint32_t ray_log_cap;
+  // srt_pt_set_env_sampling(SRT_ENV_SAMPLING_IMAGE): Env_Map::image_sampler (rays/env_light.h:52), the host-built tables of
+  // Samplers::Sphere::Image (pt_env_image.h).  env_cdf / env_pdf: _cdf and _pdf, env_w * env_h floats each; env_trig: the doubles
+  // sample() multiplies - sin theta and cos theta of the env_h + 1 rows it can return, then cos phi and sin phi of the env_w columns.
+  // Default initialisers: whoever fills a DScene field by field and knows nothing of the mode gets the uniform sampler.
+  const float* env_cdf = nullptr;
+  const float* env_pdf = nullptr;
+  const double* env_trig = nullptr;
+  uint32_t env_sampling = 0;
 };
 
 constexpr uint32_t kRayLogHeader = 8, kRayLogWords = 8;
@@ -737,13 +746,73 @@ SRT_DEV V3 env_sample(Rng& rng) {
   return v3(st * cp, ct, st * sp);
 }
 
+// ---- Env_Map::sample / pdf through image_sampler: Samplers::Sphere::Image (student/samplers.cpp:81-137), quirks included ----
+// sample(): ONE draw; std::upper_bound over _cdf as libstdc++ walks it (bits/stl_algo.h __upper_bound: half = len >> 1, go right
+// when !(u < cdf[mid])) - on a table that is not sorted (negative texels) or holds NaN (a black map) the result is whatever these
+// very steps arrive at, so they are followed one for one; the index may be w * h (row h, column 0: u at or above the last entry,
+// or a NaN table).  The direction is the texel's corner, not jittered: theta and phi are functions of (row, column) alone, their
+// trigonometry is the double overload (unqualified sin / cos), and the host tabulated it per row and per column (env_trig) -
+// what stays here is the double product and its rounding to float on assignment.
+// The loads: up to log2(w * h) dependent reads of env_cdf per light sample, from global memory.  The first steps of every lane read
+// the same few entries (the middle, the quartiles: they stay in the vector L1), the last ones scatter over the table, which for a
+// 2048 x 1024 map is 8 MB and lives in L2 / MALL; LDS could hold 64 KB of it and would have to be filled per workgroup.  Lanes of a
+// wave take the same number of steps to within one (len halves regardless of the branch), so the loop does not diverge in length.
+SRT_DEV uint32_t env_image_upper_bound(const DScene& S, float u) {
+  const float* __restrict__ cdf = S.env_cdf;
+  uint32_t first = 0u, len = S.env_w * S.env_h;
+  while (len > 0u) {
+    const uint32_t half = len >> 1, mid = first + half;
+    if (u < cdf[mid]) len = half;
+    else { first = mid + 1u; len = len - half - 1u; }
+  }
+  return first;
+}
+SRT_DEV V3 env_image_direction(const DScene& S, uint32_t index) {
+  const uint32_t col = index % S.env_w, row = index / S.env_w;          // index_to_image_coor: row <= env_h
+  const double* __restrict__ t = S.env_trig;
+  const double st = t[row], ct = t[(S.env_h + 1u) + row];
+  const double cp = t[2u * (S.env_h + 1u) + col], sp = t[2u * (S.env_h + 1u) + S.env_w + col];
+  return v3((float)(st * cp), (float)ct, (float)(st * sp));
+}
+SRT_DEV V3 env_image_sample(const DScene& S, Rng& rng) { return env_image_direction(S, env_image_upper_bound(S, rng.unit())); }
+// (size_t)(v) of pdf() for v = theta * h or phi * w with theta, phi clamped to [0, 1] - or NaN, which std::clamp passes on.  The
+// reference's x86-64 code (cvttss2si, and for the unsigned range a second conversion of v - 2^63 merged in by the sign of the first)
+// gives 2^63 for a NaN, which the `> h - 1` clamp that follows turns into h - 1; every other v is in [0, 2^28] and truncates.
+SRT_DEV uint32_t env_image_index(float v, uint32_t n) {
+  const uint32_t i = (v == v) ? (uint32_t)v : 0xffffffffu;
+  return i > n - 1u ? n - 1u : i;
+}
+// pdf(dir): theta from acos(dir.y) WITHOUT normalising dir (student/samplers.cpp:122-123), the Jacobian with sin of the NORMALISED
+// theta in [0, 1] - not of theta - taken in double (cvtss2sd, sin, the division in double, cvtsd2ss), times _pdf of the texel.
+// sin(0) = 0 gives an infinite Jacobian (times a zero _pdf: NaN), a NaN dir.y a NaN.
+SRT_DEV float env_image_pdf(const DScene& S, V3 dir) {
+  float theta = kPi - srt_acosf(dir.y);
+  float phi = srt_atan2f(dir.z, dir.x);
+  if (phi < 0) phi = phi + 2.f * kPi;
+  theta = std_clamp(theta / kPi, 0.f, 1.f);
+  phi = std_clamp(phi / (2.0f * kPi), 0.f, 1.f);
+  const uint32_t y = env_image_index(theta * (float)S.env_h, S.env_h);
+  const uint32_t x = env_image_index(phi * (float)S.env_w, S.env_w);
+  const float jacobian = (float)((double)((float)S.env_w * (float)S.env_h) / ((double)(2.f * kPi * kPi) * srt_sin_unit(theta)));
+  return jacobian * S.env_pdf[(size_t)y * S.env_w + x];
+}
+
 // Pathtracer::sample_area_lights (rays/pathtracer.cpp:301-311): List<Object>::sample -> Object::sample ->
 // List<Triangle>::sample -> Samplers::Triangle::sample; with an environment light a coin picks between the two.
-template <bool W1 = false>
+// ENVIMG (here, in light_pdf and in path_sample): the instantiation samples the environment - an Env_Map - through its image
+// sampler; the others hold none of that code and compile as they did without it.  The template parameter is the ONE switch: the
+// host picks the ENVIMG build exactly when the mode is on and the tables are on the device (image_sampling_launch, pt_context.h),
+// and S.env_sampling only records that choice for whoever reads a DScene.
+template <bool ENVIMG>
+SRT_DEV V3 env_light_sample(const DScene& S, Rng& rng) {   // Env_Light::sample: Env_Map picks its sampler, the others have one
+  if constexpr (ENVIMG) return env_image_sample(S, rng);
+  else return env_sample(rng);
+}
+template <bool W1 = false, bool ENVIMG = false>
 SRT_DEV V3 light_sample(const DScene& S, V3 from, Rng& rng) {
   if (S.env_type != 0u) {
-    if (S.nlights == 0) return env_sample(rng);
-    if (rng.coin(0.5f)) return env_sample(rng);
+    if (S.nlights == 0) return env_light_sample<ENVIMG>(S, rng);
+    if (rng.coin(0.5f)) return env_light_sample<ENVIMG>(S, rng);
   }
   if (S.nlights == 0) return v3(0, 0, 0);
   const Light& L = S.lights[rng.integer(0, (int)S.nlights)];
@@ -760,7 +829,7 @@ SRT_DEV V3 light_sample(const DScene& S, V3 from, Rng& rng) {
   return dir;
 }
 // Pathtracer::area_lights_pdf -> List<Object>::pdf -> Object::pdf -> List<Triangle>::pdf -> Triangle::pdf.
-template <bool COUNT, bool W1 = false>
+template <bool COUNT, bool W1 = false, bool ENVIMG = false>
 SRT_DEV float light_pdf(const DScene& S, V3 from, V3 dir, Counters& cnt) {
   int n = 0;
   float pdf = 0.0f;
@@ -795,7 +864,8 @@ SRT_DEV float light_pdf(const DScene& S, V3 from, V3 dir, Counters& cnt) {
     n++;
   }
   if (S.env_type != 0u) {                          // Env_Sphere::pdf = 1 / (4 PI), Env_Hemisphere::pdf = 1 / (2 PI)
-    pdf += (S.env_type == 2u) ? (1.0f / (2.0f * kPi)) : (1.0f / (4.0f * kPi));
+    if constexpr (ENVIMG) pdf += env_image_pdf(S, dir);
+    else pdf += (S.env_type == 2u) ? (1.0f / (2.0f * kPi)) : (1.0f / (4.0f * kPi));
     n++;
   }
   if (n) pdf /= n;
@@ -868,7 +938,7 @@ SRT_DEV Spec point_lighting(const DScene& S, const Material& m, V3 position, V3 
 struct Bounce { Spec direct, atten; float inv_pdf; uint32_t discrete; };
 
 // Pathtracer::trace_pixel for pixel (x, y); the RNG must already be keyed.
-template <bool COUNT>
+template <bool COUNT, bool ENVIMG = false>
 SRT_DEV Spec path_sample(const DScene& S, uint32_t x, uint32_t y, Rng& rng, Counters& cnt) {
   const float jx = rng.unit() * 1.0f;   // Samplers::Rect(1,1).sample(): x first (braced init)
   const float jy = rng.unit() * 1.0f;
@@ -915,13 +985,13 @@ SRT_DEV Spec path_sample(const DScene& S, uint32_t x, uint32_t y, Rng& rng, Coun
     radiance = radiance + direct;
     if (!discrete) {
       radiance = radiance - direct;
-      const V3 to_light = light_sample(S, sf.position, rng);
+      const V3 to_light = light_sample<false, ENVIMG>(S, sf.position, rng);
       const V3 chosen = rng.coin(0.5f) ? world_in : to_light;
       const Ray r6 = make_ray(sf.position, chosen, kEps, FLT_MAX);
       // the ray-log coin is always flipped (student/pathtracer.cpp:148); when it fires the ray goes to the GUI's log
       if (rng.coin(0.0005f) && S.ray_log) log_ray_event(S.ray_log, S.ray_log_cap, r6.o.x, r6.o.y, r6.o.z, r6.d.x, r6.d.y, r6.d.z, rng.inc, (uint32_t)level);
       Spec d6 = emitted_along<COUNT>(S, r6, cnt);
-      const float pdf_area = light_pdf<COUNT>(S, sf.position, to_light, cnt);
+      const float pdf_area = light_pdf<COUNT, false, ENVIMG>(S, sf.position, to_light, cnt);
       const float pdf4 = lambert_pdf(out_dir);
       pdf = (pdf4 + pdf_area) / 2.0f;
       const Spec att6 = lambert_evaluate(m, out_dir);

@@ -493,7 +493,9 @@ template <> struct WaveFlags<true> {
 // One kernel carrying a slot's whole state through both sweeps wanted ~245 VGPRs at four waves per SIMD (121 spilled, ~150 GB of
 // scratch traffic per 64-spp epoch of BASELINE configs[4]); the resolve kernel alone is the Cornell kernel's loop body, and the
 // probe kernel needs neither the sweep slots in LDS nor most of the state.
-template <bool STAMP, int TRAV, bool DL, int NR, int PHASE = 0>
+// ENVIMG: the DL build that can sample an Env_Map through its image sampler (srt_pt_set_env_sampling; light_sample / light_pdf in
+// pt_trace.h).  An instantiation of its own, so that every other one - the headline form among them - holds none of that code.
+template <bool STAMP, int TRAV, bool DL, int NR, int PHASE = 0, bool ENVIMG = false>
 #ifndef SRT_WAVE_OCC
 #define SRT_WAVE_OCC 4
 #endif
@@ -521,6 +523,7 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   static_assert(NR == 3 || (NR == 2 && TRAV != 2 && !DL), "two-ray batches: sweep builds without delta / environment lights only");
   static_assert(!(STAMP && TRAV >= 3), "the streamed builds have no section stamps");
   static_assert(PHASE == 0 || (TRAV == 4 && !DL), "split generations: the streamed sweeps without delta / environment lights");
+  static_assert(!ENVIMG || DL, "the image sampler belongs to an environment light");
   constexpr int C = NR - 1;                              // slot of the indirect ray
   constexpr bool STREAM = TRAV >= 3;                     // pt_stream.h: 3 = every ray through the ray-cast kernel, 4 = sweeps here, BVH<Triangle> walks queued
   constexpr bool LAZY = TRAV == 1 || TRAV == 4;          // meshes with a real BVH<Triangle> are evaluated lazily inside the sweeps
@@ -1397,10 +1400,10 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         V3 chosen = world_in;
         bool log_fire = false;
         if (!discrete) {
-          const V3 to_light = light_sample<true>(S, sf.position, rng);
+          const V3 to_light = light_sample<true, ENVIMG>(S, sf.position, rng);
           chosen = rng.coin(0.5f) ? world_in : to_light;
           log_fire = rng.coin(0.0005f);                 // log_ray(world_ray_task6, 5.0f) with probability 0.0005 (student/pathtracer.cpp:148)
-          pdf_area = light_pdf<false, true>(S, sf.position, to_light, cnt);
+          pdf_area = light_pdf<false, true, ENVIMG>(S, sf.position, to_light, cnt);
         }
         if (m.type == 0) { s2.atten = s1.atten; s2.dir = lambert_direction(rng); }
         else s2 = scatter(m, out_dir, rng);

@@ -233,6 +233,8 @@ void Pathtracer::begin_render(Scene& layout_scene, const Camera& cam, bool add_s
     mat_to_array(srt_host::camera_iview(cam), iview);
     // "Pathtracer: use normal colors" (student/debug.cpp:43): trace's early out at student/pathtracer.cpp:199, read once per render
     core.set_normal_colors(debug_data.normal_colors);
+    for(int r = 0; r < core.ranks(); r++)   // (no launch is being enqueued: cancel() joined the worker)
+        check(srt_pt_set_env_sampling(core.context(r), env_image_sampling ? SRT_ENV_SAMPLING_IMAGE : SRT_ENV_SAMPLING_UNIFORM), "srt_pt_set_env_sampling");
     core.begin(iview, cam.get_fov(), cam.get_ar(), add_samples);
 }
 

@@ -62,6 +62,10 @@ public:
 
     // Not in the reference: RNG seed of the next render (the reference is unseeded).
     void set_seed(unsigned long long s) { core.set_seed(s); }
+    // Not in the reference's class: its Env_Map builds image_sampler and never uses it (student/env_light.cpp:8-32).  on: the next
+    // begin_render samples an environment map through it (srt_pt_set_env_sampling on every device's context, read once per render
+    // like debug_data.normal_colors); a scene whose environment is no map is then refused.  Default: the reference's uniform sampler.
+    void set_env_image_sampling(bool on) { env_image_sampling = on; }
 
 private:
     static void deliver_logged_rays(void* self, const srt_pt_logged_ray* rays, size_t n);   // Pathtracer::log_ray -> gui.log_ray
@@ -78,6 +82,7 @@ private:
     GL::Tex2D output_tex;            // display texture fed by tonemap_to
     std::vector<unsigned char> tonemap_out;
     bool scene_use_bvh = true;
+    bool env_image_sampling = false;
     // BVH<Object> node arrays of the last build_scene, kept for visualize_bvh (no context call while a render is in flight)
     std::vector<float> bvh_boxes;
     std::vector<uint32_t> bvh_links;
