@@ -75,6 +75,23 @@ __host__ __device__ constexpr bool camera_table(bool stamp, int trav, int nr) {
   return SRT_CAMERA_TABLE != 0 && trav >= 0 && trav <= 2 && !(trav == 0 && (stamp || nr == 2));
 }
 
+// The read-back of a finished path's records (terminate) was one memory round trip per level - two loads, a wait, sixteen vector
+// instructions, a back edge - and the wave waits for its deepest lane.  None of the addresses depends on the fold, so the records of
+// four consecutive levels - kRecGroup, one 128-byte line of a lane's run - are loaded, both halves, before any of them is folded; the
+// fold is the old one, level by level, deepest first, and levels at or above `level` (a group is aligned, so it is always inside the
+// lane's kMaxPathDepth records, whatever they hold) are skipped by the fold.  The same loads feed the same operations in the same
+// order: no output bit changes.  SRT_TAIL_BATCH=0 keeps the parent's loop (A/B builds); tail_batch() names the forms.
+#ifndef SRT_TAIL_BATCH
+#define SRT_TAIL_BATCH 1
+#endif
+constexpr int kRecGroup = 4;               // (8 costs the headline kernel 64 B of scratch per lane: DESIGN.md section 6)
+static_assert(kMaxPathDepth % kRecGroup == 0, "a group of records never reaches past the lane's run");
+// Which forms: all but the streamed forms with delta / environment lights.  Three of those four would pay 4 B of scratch per lane
+// for the groups (592 -> 596, 644 -> 648, 636 -> 640; the fourth stays at 588) and all four keep the parent's loop.
+__host__ __device__ constexpr bool tail_batch(int trav, bool dl) {
+  return SRT_TAIL_BATCH != 0 && !(trav >= 3 && dl);
+}
+
 struct WaveParams {
   TileMap T;
   uint64_t seed;
@@ -537,6 +554,8 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
   // Camera rays from the launch's camera table instead of the inline arithmetic - in the refill, in shade and in the environment
   // map's lookup; see camera_table().
   constexpr bool CAMTAB = camera_table(STAMP, TRAV, NR);
+  // The read-back of a finished path's records in groups of kRecGroup levels instead of level by level; see tail_batch().
+  constexpr bool TAILR = tail_batch(TRAV, DL);
   if constexpr (STREAM) {
     if (P_in.sc->done != 0u) return;                     // every unit is finished: the remaining generations are no-ops
   }
@@ -1326,14 +1345,33 @@ __global__ __launch_bounds__(256, PHASE == 2 ? SRT_PROBE_OCC : TRAV == 4 ? SRT_S
         }
         if (!terminal) { need_shade = true; break; }
         Spec L = spec(0, 0, 0);
-        for (int k = (int)level - 1; k >= 0; k--) {
-          const f32x4 r0 = REC_LOAD(k, 0);
-          const f32x4 r1 = REC_LOAD(k, 1);
-          const Spec dk = spec(r0.x, r0.y, r0.z);
-          const Spec ak = spec(r1.x, r1.y, r1.z);
-          Spec ind = (r0.w != 0.0f) ? (L * ak) : ((L * ak) * r1.w);
-          ind = spec(0, 0, 0) + ind;
-          L = dk + ind;
+        if constexpr (TAILR) {
+          // a group = levels [kRecGroup * g, kRecGroup * (g + 1)), one line: eight loads in flight, then the fold of the levels below `level`
+          for (int g = ((int)level - 1) / kRecGroup; (int)level > 0 && g >= 0; g--) {
+            f32x4 r0[kRecGroup], r1[kRecGroup];
+#pragma unroll
+            for (int i = 0; i < kRecGroup; i++) { r0[i] = REC_LOAD(kRecGroup * g + i, 0); r1[i] = REC_LOAD(kRecGroup * g + i, 1); }
+#pragma unroll
+            for (int i = kRecGroup - 1; i >= 0; i--) {
+              if (kRecGroup * g + i < (int)level) {
+                const Spec dk = spec(r0[i].x, r0[i].y, r0[i].z);
+                const Spec ak = spec(r1[i].x, r1[i].y, r1[i].z);
+                Spec ind = (r0[i].w != 0.0f) ? (L * ak) : ((L * ak) * r1[i].w);
+                ind = spec(0, 0, 0) + ind;
+                L = dk + ind;
+              }
+            }
+          }
+        } else {
+          for (int k = (int)level - 1; k >= 0; k--) {
+            const f32x4 r0 = REC_LOAD(k, 0);
+            const f32x4 r1 = REC_LOAD(k, 1);
+            const Spec dk = spec(r0.x, r0.y, r0.z);
+            const Spec ak = spec(r1.x, r1.y, r1.z);
+            Spec ind = (r0.w != 0.0f) ? (L * ak) : ((L * ak) * r1.w);
+            ind = spec(0, 0, 0) + ind;
+            L = dk + ind;
+          }
         }
         const Spec out = ((level == 0) ? e : spec(0, 0, 0)) + L;
         __builtin_nontemporal_store(f32x4{out.r, out.g, out.b, 0.0f}, reinterpret_cast<f32x4*>(P.sample_out) + ((size_t)S_CUR_ * P.npix + pixel_slot));
